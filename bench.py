@@ -33,6 +33,8 @@ import os
 import sys
 import time
 
+import numpy as np
+
 REPO = os.path.dirname(os.path.abspath(__file__))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
@@ -47,6 +49,9 @@ PEAK_HBM_GBS = 8000.0
 PROFILE_TAG = "r06"                # profiles/<tag>_pmc_traffic*.json: the PMC passes whose `traffic` this build may quote
 WEIGHT_SEED, OBJ_BIAS, HEAD_GAIN = 3, -16.0, 4.0
 OBJ_BIAS_SPARSE = -18.5     # a few tens of detections per image (-18: 67, -19: 11, -20: 3, <= -24: none)
+INPUT_SEEDS = (1000, 2000)  # the two input batches taken in turn (+ rank)
+DUMP_BYTES = 60 * 10 ** 6   # --dump-outputs writes at most this much (64 MB with room to spare)
+DUMP_PIXEL_SEED = 0
 
 
 def post_config(h, w):
@@ -156,6 +161,43 @@ class ClockSampler:
 def lib_sha256():
     from orienmask_amd import lib as omlib
     return hashlib.sha256(open(omlib.LIB_PATH, "rb").read()).hexdigest()
+
+
+def dump_pixel_index(h, w, batch, max_dets, budget=DUMP_BYTES):
+    """The flat pixel positions at which --dump-outputs samples every mask: a fixed seeded draw whose size depends on the
+    arguments only (never on the detections), so that two builds sample the same pixels.  As many as the budget leaves after
+    the per-detection arrays at batch x max_dets detections (4 KiB kept for the .npy headers); all of them if they fit."""
+    n = batch * max_dets
+    per_mask = (budget - 4096 - 8 * batch - (5 * 4 + 8 + 8) * n) // (4 * n)
+    if per_mask < 1:
+        raise SystemExit("bench.py: --dump-outputs cannot fit %d x %d detections into %d bytes" % (batch, max_dets, budget))
+    if per_mask >= h * w:
+        return np.arange(h * w)
+    return np.sort(np.random.RandomState(DUMP_PIXEL_SEED).permutation(h * w)[:per_mask])
+
+
+def dump_outputs(dets, out_dir, max_dets, budget=DUMP_BYTES):
+    """--dump-outputs: the detections a caller of the timed path received in its last step (one dict per image, as
+    OrienMaskYOLOPostProcess returns them), images concatenated in batch order, as out_dir/<name>.npy:
+      counts       [B]     float64  detections per image (how the rows below split into images)
+      bbox         [N, 5]  float32  cx, cy, w, h, score
+      cls          [N]     float64  class index
+      mask_area    [N]     float64  pixels set in each whole mask
+      mask_sample  [N, P]  float32  each mask at the P pixels of dump_pixel_index (the whole masks, B x 100 x H x W, would not
+                                    fit the budget)"""
+    h, w = dets[0]["mask"].shape[1:]
+    idx = dump_pixel_index(h, w, len(dets), max_dets, budget)
+    idx_dev = torch.from_numpy(idx).to(dets[0]["mask"].device)
+    masks = [d["mask"].reshape(d["mask"].shape[0], h * w) for d in dets]
+    arrays = dict(
+        counts=np.array([d["bbox"].shape[0] for d in dets], dtype=np.float64),
+        bbox=torch.cat([d["bbox"] for d in dets]).cpu().numpy().astype(np.float32).reshape(-1, 5),
+        cls=torch.cat([d["cls"] for d in dets]).cpu().numpy().astype(np.float64),
+        mask_area=torch.cat([m.sum(1) for m in masks]).cpu().numpy().astype(np.float64),
+        mask_sample=torch.cat([m.index_select(1, idx_dev) for m in masks]).cpu().numpy().astype(np.float32).reshape(-1, len(idx)))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def post_occupancy(B, post_cfg_):
@@ -346,7 +388,15 @@ def main():
                          "the fp32-operand time reported beside it as `f32_operands`.  f32: fp32 operands on "
                          "v_mfma_f32_32x32x2_f32 only.  f16: BASELINE configs[4], fp16 activations and weights with fp32 "
                          "accumulation -- a separate, clearly labelled line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the detections of the last step of the timed path behind `value` (rank 0's) "
+                         "as DIR/<name>.npy, float32 / float64, at most 64 MB (masks as a fixed seeded sample of their pixels): "
+                         "two builds run with the same arguments can be compared output for output (dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs:
+        dump_pixel_index(args.size, args.size, args.batch, post_config(args.size, args.size)["nms_post"])     # fits, or fails now
     from orienmask_amd.model import DEFAULT_PRECISION
     if args.dtype is None:
         args.dtype = DEFAULT_PRECISION
@@ -406,10 +456,10 @@ def main():
     if args.latency_mode:
         net.set_latency_mode(True, ksplit=args.latency_ksplit)
     post = OrienMaskYOLOPostProcess(device=dev, **post_config(H, W))
-    x_cpu = synth.synth_image_batch(1000 + rank, B, H, W)
+    x_cpu = synth.synth_image_batch(INPUT_SEEDS[0] + rank, B, H, W)
     x = x_cpu.to(dev)
     # two input batches taken in turn: a step never re-reads the tensor the step before it left in the 256 MiB Infinity Cache
-    xs = [x, synth.synth_image_batch(2000 + rank, B, H, W).to(dev)]
+    xs = [x, synth.synth_image_batch(INPUT_SEEDS[1] + rank, B, H, W).to(dev)]
     step_no = [0]
 
     def step():
@@ -537,6 +587,7 @@ def main():
         elapsed = time.perf_counter() - t0
         sclk_flight = clock.stop()
         elapsed, per_rank = over_ranks(elapsed)
+    timed_dets = dets                                              # the last step behind `value`: what --dump-outputs writes
     # ---- split mode: the same K steps with fp32 operands (v_mfma_f32_32x32x2_f32 everywhere), for comparison
     f32_operands = None
     if split and not args.no_f32_compare:
@@ -972,6 +1023,8 @@ def main():
             line["extras"] = measure_neighbours(dev, dets, B)
         if world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(sd, x_cpu, f16=f16)
+        if args.dump_outputs:
+            dump_outputs(timed_dets, args.dump_outputs, post.nms_post)
         print(json.dumps(line))
     if use_dist:
         dist.barrier()

@@ -2831,3 +2831,37 @@ def test_bench_line_with_the_rccl_path_on_one_gpu(dev):
     assert rf["kernel"].startswith("wino14_split_kernel") and 0 < rf["frac"] < rf["executed_frac"] < 1
     assert abs(rf["executed_frac"] / rf["frac"] - 1.5) < 0.01 and abs(rf["achieved"] / rf["peak"] - rf["frac"]) < 1e-3
     assert rf["one_batch_in_flight_images_per_s"] == line["one_batch_in_flight"]["value"]
+
+
+def test_bench_dump_outputs_are_the_last_timed_step(dev, tmp_path):
+    """`bench.py --dump-outputs DIR` writes the detections of the last of its --steps timed steps: with two batches in flight and
+    3 steps that is the first input batch again, and the files are those of forward + postprocess of that batch computed here with
+    the bench's weights, precision and postprocess configuration -- the same bits."""
+    import json
+    import subprocess
+    import sys
+    import bench
+    from orienmask_amd.dist import broadcast_packed_weights
+    from orienmask_amd.eval import OrienMaskYOLOPostProcess
+    from orienmask_amd.model import OrienMaskYOLOFPNPlus
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "OM_BENCH_FORCE_DIST")}
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "2", "--in-flight", "2",
+                        "--no-cpu-baseline", "--no-extras", "--no-f32-compare", "--no-f16-compare", "--no-small-batch",
+                        "--dump-outputs", str(tmp_path / "bench")], capture_output=True, text=True, timeout=900, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 3 and line["config"]["per_gpu_batch"] == 2
+    sd = synth.synth_state_dict(bench.WEIGHT_SEED, obj_bias=bench.OBJ_BIAS, head_gain=bench.HEAD_GAIN)
+    net = OrienMaskYOLOFPNPlus(3, 80).eval().set_precision(line["precision"])
+    net.load_state_dict(sd, strict=True)
+    broadcast_packed_weights(net, dev, src=0)
+    post = OrienMaskYOLOPostProcess(device=dev, **bench.post_config(544, 544))
+    x = synth.synth_image_batch(bench.INPUT_SEEDS[0], 2, 544, 544).to(dev)          # steps take xs[0], xs[1], xs[0]
+    with torch.no_grad():
+        bench.dump_outputs(post(net(x)), str(tmp_path / "want"), post.nms_post)
+    names = sorted(os.listdir(tmp_path / "want"))
+    assert sorted(os.listdir(tmp_path / "bench")) == names and len(names) == 5
+    for n in names:
+        got, want = np.load(tmp_path / "bench" / n), np.load(tmp_path / "want" / n)
+        assert got.dtype == want.dtype and np.array_equal(got, want), n
+    assert np.load(tmp_path / "want" / "counts.npy").min() > 0

@@ -534,6 +534,45 @@ def test_bench_clock_sampler_reads_the_drivers_table(tmp_path):
     assert s.start().stop() is None
 
 
+def test_bench_dump_outputs_layout_and_budget(tmp_path):
+    """bench.dump_outputs (--dump-outputs): the last step's detections as float32 / float64 .npy files, images concatenated in
+    batch order, masks at pixel positions that depend on the arguments only; the same detections give the same bytes, and the
+    files stay within the budget even when every image has the most detections."""
+    import numpy as np
+    import bench
+    g = torch.Generator().manual_seed(5)
+    h, w, max_dets, budget = 24, 40, 6, 20000
+
+    def fake(counts):
+        return [dict(bbox=torch.rand(k, 5, generator=g), cls=torch.randint(0, 80, (k,), generator=g),
+                     mask=torch.rand(k, h, w, generator=g) > 0.5) for k in counts]
+
+    idx = bench.dump_pixel_index(h, w, 3, max_dets, budget)
+    assert 0 < len(idx) < h * w and np.array_equal(idx, np.unique(idx))             # a sample: sorted, no repeats
+    assert np.array_equal(idx, bench.dump_pixel_index(h, w, 3, max_dets, budget))
+    dets = fake((6, 0, 3))
+    bench.dump_outputs(dets, str(tmp_path / "a"), max_dets, budget)
+    bench.dump_outputs([{k: v.clone() for k, v in d.items()} for d in dets], str(tmp_path / "b"), max_dets, budget)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["bbox.npy", "cls.npy", "counts.npy", "mask_area.npy", "mask_sample.npy"]
+    assert all((tmp_path / "a" / f).read_bytes() == (tmp_path / "b" / f).read_bytes() for f in files)
+    out = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    assert out["counts"].tolist() == [6, 0, 3]
+    assert np.array_equal(out["bbox"], torch.cat([d["bbox"] for d in dets]).numpy())
+    assert np.array_equal(out["cls"], torch.cat([d["cls"] for d in dets]).numpy())
+    m = torch.cat([d["mask"] for d in dets]).reshape(9, h * w).numpy()
+    assert np.array_equal(out["mask_area"], m.sum(1)) and np.array_equal(out["mask_sample"], m[:, idx])
+    bench.dump_outputs(fake((max_dets,) * 3), str(tmp_path / "full"), max_dets, budget)
+    assert sum(os.path.getsize(tmp_path / "full" / f) for f in files) <= budget
+    assert np.array_equal(bench.dump_pixel_index(h, w, 3, max_dets), np.arange(h * w))     # room for every pixel
+    with pytest.raises(SystemExit):
+        bench.dump_pixel_index(h, w, 3, max_dets, 1000)
+    # the bench's own workload, 32 images x 100 detections at 544^2 (npy headers: 128 bytes each)
+    n, p = 3200, len(bench.dump_pixel_index(544, 544, 32, 100))
+    assert 32 * 8 + n * (20 + 8 + 8 + 4 * p) + 5 * 128 <= bench.DUMP_BYTES <= 64 * 10 ** 6
+
+
 def test_blob_checksum_tells_blobs_apart():
     """orienmask_amd.dist.blob_checksum (round 6: every rank packs the broadcast weights itself and the ranks all-gather a checksum of
     each packed blob): equal bytes -> equal checksums; one changed word, two swapped words or a changed fp16 half -> another."""
