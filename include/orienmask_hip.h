@@ -482,6 +482,35 @@ int om_recover_masks_rle_strings(const om_rle_image* images, int n_images, uint3
                                  uint8_t* str_bytes, long long str_capacity, int32_t* str_cursor, int32_t* str_off,
                                  int32_t* str_len, om_stream stream);
 
+/* ---- InferenceVisualizer (utils/visualizer.py:33-127 of the reference; orienmask_amd/visualizer.py) ------------------------
+ * om_visualize: the device part of InferenceVisualizer.__call__ for a BATCH of images of any sizes -- _recover_shape_segm (crop
+ *   the paddings, bilinear resize align_corners=False, float values kept), the ascending sort by resized area, plot_all_mask's
+ *   alpha composite and round() to uint8 -- in one pass over each output, without a [K,h,w] intermediate: per pixel, every kept
+ *   mask whose nonzero extent covers it is sampled with the bilinear code of om_recover_masks_rle, the cumulative product is
+ *   kept in double (torch's cumprod) and the weighted colour sum in float, in the reference's association.  Optionally the
+ *   thickness-1 box outlines cv2.rectangle would draw (rows y1, y2 over [x1, x2], columns x1, x2 over [y1, y2], clipped; where
+ *   outlines cross, the later box in kept order wins).  Two launches per OM_VIS_BATCH images (a per-mask pre-pass, then the
+ *   composite).  images: HOST array; the source images are only read.  workspace: om_visualize_workspace_bytes(images, n)
+ *   bytes of device memory (32 B per kept mask), contents undefined on entry. */
+#define OM_VIS_MAX_KEPT 512     /* kept detections per image */
+#define OM_VIS_BATCH 16         /* images per launch pair */
+typedef struct om_vis_image {
+    const float* image;         /* [h,w,3] float32 HWC, device, 16-byte aligned */
+    uint8_t* out;               /* [h,w,3] uint8 HWC, device, 4-byte aligned */
+    float* out_float;           /* optional [h,w,3] float32: the composite before rounding (tests); NULL: not written */
+    const uint8_t* mask;        /* [K,Hn,Wn] 0/1 bytes at the network input size, device; read when with_mask and n_keep > 0 */
+    const int32_t* keep;        /* [n_keep] device: index into mask of each kept detection, in kept order */
+    const float* colors;        /* [n_keep,3] device: RGB colour of each kept detection */
+    const int32_t* boxes;       /* [n_keep,4] device: x1, y1, x2, y2 of each kept detection; read when draw_boxes */
+    int32_t n_keep, Hn, Wn;
+    int32_t crop_left, crop_right, crop_top, crop_down;    /* pad_info[:4] */
+    int32_t h, w;
+    int32_t with_mask, draw_boxes;
+    float alpha;
+} om_vis_image;
+size_t om_visualize_workspace_bytes(const om_vis_image* images, int n_images);
+int om_visualize(const om_vis_image* images, int n_images, void* workspace, size_t ws_bytes, om_stream stream);
+
 /* ---- unit-test entry: the elementary functions the decode uses, restated bit-exactly from what torch-CPU runs at the
  * reference's call sites eval/orienmask_yolo_postprocess.py:127-136 (csrc/ref_math.h).  func: 0 = glibc expf (torch's
  * scalar loop), 1 = Sleef expf_u10 (torch's vectorised loop), 2 / 3 = sigmoid through either, 4 = sigmoid of a

@@ -27,6 +27,7 @@
 // taps combined as in preprocess.hip), so the resized masks are bit-identical to the reference's.
 #include <atomic>
 #include "om_common.h"
+#include "bilinear.h"
 
 namespace om {
 
@@ -80,16 +81,6 @@ struct RleParams {
     float scale_h, scale_w;
 };
 
-__device__ __forceinline__ void tap(int d, float scale, int n_in, int& i0, int& i1, float& w0, float& w1) {
-    float src = fmaf(scale, (float)d + 0.5f, -0.5f);
-    src = src < 0.f ? 0.f : src;
-    i0 = (int)src;
-    if (i0 > n_in - 1) i0 = n_in - 1;
-    i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
-    w1 = src - (float)i0;
-    w0 = 1.0f - w1;
-}
-
 constexpr int RLE_THREADS = 1024;
 
 __global__ __launch_bounds__(RLE_THREADS) void recover_rle_kernel(const RleParams q) {
@@ -110,9 +101,7 @@ __global__ __launch_bounds__(RLE_THREADS) void recover_rle_kernel(const RleParam
         if (q.hflip) { x0 = q.cw - 1 - x0; x1 = q.cw - 1 - x1; }
         const uint8_t* r0 = m + (size_t)(q.crop_top + y0) * q.W + q.crop_left;
         const uint8_t* r1 = m + (size_t)(q.crop_top + y1) * q.W + q.crop_left;
-        const float top = fmaf((float)r0[x0], wx0, (float)r0[x1] * wx1);
-        const float bot = fmaf((float)r1[x0], wx0, (float)r1[x1] * wx1);
-        const float v = fmaf(top, wy0, bot * wy1);
+        const float v = bilinear_blend((float)r0[x0], (float)r0[x1], (float)r1[x0], (float)r1[x1], wx0, wx1, wy0, wy1);
         return (int)rintf(v);                          // torch.round: half to even
     };
 
@@ -341,9 +330,8 @@ __global__ __launch_bounds__(RLE_THREADS) void recover_rle_lds_kernel(const RleB
             }
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                const float top = fmaf((float)a00[j], wx0, (float)a01[j] * wx1);
-                const float bot = fmaf((float)a10[j], wx0, (float)a11[j] * wx1);
-                const float v = fmaf(top, __int_as_float(t[j].z), bot * __int_as_float(t[j].w));
+                const float v = bilinear_blend((float)a00[j], (float)a01[j], (float)a10[j], (float)a11[j], wx0, wx1,
+                                               __int_as_float(t[j].z), __int_as_float(t[j].w));
                 const int bit = (int)rintf(v);                      // torch.round: half to even
                 word |= (i0 + j < ylim ? (uint32_t)(bit & 1) : 0u) << ((i0 + j) & 31);
             }

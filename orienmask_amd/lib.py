@@ -50,6 +50,19 @@ class RleImage(ctypes.Structure):
                 ("orig_h", ctypes.c_int32), ("orig_w", ctypes.c_int32)]
 
 
+class VisImage(ctypes.Structure):
+    """include/orienmask_hip.h: om_vis_image"""
+    _fields_ = [("image", ctypes.c_void_p), ("out", ctypes.c_void_p), ("out_float", ctypes.c_void_p), ("mask", ctypes.c_void_p),
+                ("keep", ctypes.c_void_p), ("colors", ctypes.c_void_p), ("boxes", ctypes.c_void_p),
+                ("n_keep", ctypes.c_int32), ("Hn", ctypes.c_int32), ("Wn", ctypes.c_int32),
+                ("crop_left", ctypes.c_int32), ("crop_right", ctypes.c_int32), ("crop_top", ctypes.c_int32),
+                ("crop_down", ctypes.c_int32), ("h", ctypes.c_int32), ("w", ctypes.c_int32),
+                ("with_mask", ctypes.c_int32), ("draw_boxes", ctypes.c_int32), ("alpha", ctypes.c_float)]
+
+
+OM_VIS_MAX_KEPT = 512
+OM_VIS_BATCH = 16
+
 _vp, _i, _f, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 
 # symbol -> (restype, argtypes); must list every function include/orienmask_hip.h declares
@@ -131,6 +144,8 @@ SIGNATURES = {
                              _vp, _vp]),
     "om_recover_masks_rle": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "om_recover_masks_rle_strings": (_i, [_vp, _i, _vp, _i, _vp, _vp, ctypes.c_longlong, _vp, _vp, _vp, _vp]),
+    "om_visualize_workspace_bytes": (_sz, [_vp, _i]),
+    "om_visualize": (_i, [_vp, _i, _vp, _sz, _vp]),
     "om_post_kernel_occupancy": (_i, [_i, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "om_nms_workspace_bytes": (_sz, [_i]),
     "om_nms": (_i, [_vp, _i, _f, _vp, _vp, _vp, _sz, _vp]),

@@ -139,9 +139,14 @@ class Tester:
         return stats
 
 
-def infer_loop(model, transform, postprocess, images, device, warmup=10, size_divisor=32, use_graph=True, latency_mode=True):
+def infer_loop(model, transform, postprocess, images, device, warmup=10, size_divisor=32, use_graph=True, latency_mode=True,
+               visualizer=None):
     """images: list of [h,w,3] float32 tensors (what cv2.imread + cvtColor give infer.py).
     Returns (list of per-image detections, list of pad_info, timer log in ms).
+
+    visualizer (infer.py -v, :166-172): called as visualizer(detections, image on the device, pad_info) after each image's
+    forward + postprocess and timed as 'Visualize'; the loop then returns a fourth element, the list of what it returned (for
+    visualizer.InferenceVisualizer, uint8 [h,w,3] numpy images).
 
     use_graph (default): forward + postprocess of every network input SHAPE that occurs run as one captured hipGraph
     (graph.GraphedPipeline: ~95 kernel launches become one graph launch; bit-identical detections, tests/test_hip_parity.py::
@@ -155,7 +160,7 @@ def infer_loop(model, transform, postprocess, images, device, warmup=10, size_di
     _timer.reset()
     _timer.cuda()
     model.eval()
-    results, pads = [], []
+    results, pads, shows = [], [], []
     graphs = {}
     restore = None
     if latency_mode and getattr(model, "precision", None) == "f32_split" and hasattr(model, "set_latency_mode"):
@@ -195,12 +200,18 @@ def infer_loop(model, transform, postprocess, images, device, warmup=10, size_di
             with _timer.timer("Main Loop"):
                 for img in images:
                     with _timer.timer("Load data"):
-                        x, pad_info = transform.padded(img.to(device).unsqueeze(0), size_divisor)
+                        src = img.to(device)
+                        x, pad_info = transform.padded(src.unsqueeze(0), size_divisor)
                     with _timer.timer("Forward & Postprocess"):
                         det = run(x)
                     results.append(det[0])
                     pads.append(pad_info)
+                    if visualizer is not None:
+                        with _timer.timer("Visualize"):
+                            shows.append(visualizer(det[0], src, pad_info))
     finally:
         if restore is not None:
             model.set_latency_mode(restore > 0, restore or None)
+    if visualizer is not None:
+        return results, pads, _timer.get_all_elapsed_time(), shows
     return results, pads, _timer.get_all_elapsed_time()
