@@ -511,6 +511,43 @@ typedef struct om_vis_image {
 size_t om_visualize_workspace_bytes(const om_vis_image* images, int n_images);
 int om_visualize(const om_vis_image* images, int n_images, void* workspace, size_t ws_bytes, om_stream stream);
 
+/* ---- COCO evaluation without pycocotools (orienmask_amd/cocoeval.py; the reference's eval/coco_eval.py:80-105 calls
+ * pycocotools' COCO / COCOeval).  Masks are column-major bit-packed bitmaps: with hw = ceil(h/32), word x * hw + yb holds rows
+ * 32 yb .. 32 yb + 31 of column x; bits past row h are zero.  Every array below is a caller-allocated DEVICE buffer.
+ * om_cocoeval_masks builds n_masks bitmaps from sources.  Mask m: mask_hw[2m] = h, [2m+1] = w, its bitmap at word
+ *   mask_word_off[m] of the workspace; its sources' bitmaps are at the words mask_src_word_off[mask_src_first[m] ..
+ *   mask_src_first[m+1]) and are ORed into it (maskUtils.merge).
+ *   Source s: src_kind 0 = polygon (src_len doubles x0 y0 x1 y1 ... at poly + src_data_off; pycocotools' rleFrPoly, at most
+ *   4096 vertices), 1 = uncompressed RLE (src_len uint32 counts at counts + src_data_off), 2 = compressed RLE string
+ *   (src_len bytes at strings + src_data_off; rleFrString); src_mask = its mask, src_word_off = its own bitmap (the mask's
+ *   when it is the mask's only source).  Sources [0, n_poly) are the polygons.  bitmap_words = words of every bitmap in the
+ *   workspace; workspace: om_cocoeval_workspace_bytes(bitmap_words, n_masks) bytes, 256-byte aligned, contents undefined on
+ *   entry; after the call it holds the bitmaps, then per mask {area, first column, last column} (int32; empty: w, -1).
+ * om_cocoeval_mask_stats copies those [n_masks][3] int32 out.
+ * om_cocoeval_mask_iou: for pair p = (pairs[2p] det mask, pairs[2p+1] gt mask) of one workspace, maskUtils.iou: i / u in
+ *   double, 0 when i == 0, u = the det's area when pair_crowd[p]; -1 for masks of different sizes.
+ * om_cocoeval_bbox_iou: the same pairs over boxes [.][4] x, y, w, h (double): pycocotools' bbIou.
+ * om_cocoeval_match: COCOeval.evaluateImg for n_groups (image, category) groups, one wave each: dets [dt_first[g],
+ *   dt_first[g+1]) already in score order and cut to maxDets[-1], gts [gt_first[g], gt_first[g+1]) in json order, ious
+ *   [D][G] at iou_off[g].  area_rng [4][2], iou_thrs [10] (numpy's linspace values).  Lane t + 10 a (IoU threshold t, area
+ *   range a) writes dt_match[lane][det] = matched gt id (0: none) and dt_ignore[lane][det]; gt_matched [40][n_gt_total] is
+ *   scratch.  As in pycocotools, a match is "gt id != 0": a gt with id 0 counts as unmatched. */
+size_t om_cocoeval_workspace_bytes(long long bitmap_words, int n_masks);
+int om_cocoeval_masks(int n_masks, const int32_t* mask_hw, const int64_t* mask_word_off, const int32_t* mask_src_first,
+                      const int64_t* mask_src_word_off, int n_poly, int n_srcs, const int32_t* src_kind, const int32_t* src_mask, const int64_t* src_data_off,
+                      const int32_t* src_len, const int64_t* src_word_off, const double* poly, const uint32_t* counts,
+                      const uint8_t* strings, long long bitmap_words, void* workspace, size_t ws_bytes, om_stream stream);
+int om_cocoeval_mask_stats(int n_masks, long long bitmap_words, const void* workspace, int32_t* stats, om_stream stream);
+int om_cocoeval_mask_iou(int n_pairs, const int32_t* pairs, const uint8_t* pair_crowd, int n_masks, const int32_t* mask_hw,
+                         const int64_t* mask_word_off, long long bitmap_words, const void* workspace, double* iou,
+                         om_stream stream);
+int om_cocoeval_bbox_iou(int n_pairs, const int32_t* pairs, const uint8_t* pair_crowd, const double* det_box,
+                         const double* gt_box, double* iou, om_stream stream);
+int om_cocoeval_match(int n_groups, const int32_t* dt_first, const int32_t* gt_first, const int64_t* iou_off,
+                      const double* ious, const double* dt_area, const double* gt_area, const uint8_t* gt_crowd,
+                      const int64_t* gt_id, const double* area_rng, const double* iou_thrs, int n_dt_total, int n_gt_total,
+                      uint8_t* gt_matched, int64_t* dt_match, uint8_t* dt_ignore, om_stream stream);
+
 /* ---- unit-test entry: the elementary functions the decode uses, restated bit-exactly from what torch-CPU runs at the
  * reference's call sites eval/orienmask_yolo_postprocess.py:127-136 (csrc/ref_math.h).  func: 0 = glibc expf (torch's
  * scalar loop), 1 = Sleef expf_u10 (torch's vectorised loop), 2 / 3 = sigmoid through either, 4 = sigmoid of a

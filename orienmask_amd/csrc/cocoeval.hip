@@ -1,0 +1,430 @@
+// COCO bbox / segm evaluation without pycocotools (orienmask_amd/cocoeval.py): mask building, IoU and the greedy matching of
+// COCOeval.evaluateImg.  Accumulate and summarize stay on the host (numpy), where pycocotools' exact float64 arithmetic lives.
+//
+// Masks are column-major bit-packed bitmaps, the layout coco_format.hip's RLE kernel keeps in LDS: with hw = ceil(h/32), word
+// x * hw + yb holds rows 32 yb .. 32 yb + 31 of column x (bit r = row 32 yb + r); padding bits past row h are zero.  Every source
+// of a mask is first turned into TOGGLES -- positions p = x * h + y in pycocotools' column-major pixel order where the value
+// flips -- XORed into a zeroed bitmap, then a prefix XOR in pixel order turns the toggles into the mask:
+//   polygon          rleFrPoly's points (maskApi.c): each kept boundary point toggles x * h + y; equal positions cancel, which is
+//                    the zero-run merge after rleFrPoly's sort, and y = h toggles the top of column x + 1 (the sort is global)
+//   counts           an uncompressed RLE: a toggle at every prefix sum of the counts
+//   string           a compressed RLE: rleFrString's decode, then the same toggles
+// The polygons of one annotation get a bitmap each and are ORed (maskUtils.merge, intersect = 0).
+//
+//   coco_poly_toggle_kernel    one wave per polygon, a lane per edge
+//   coco_seq_toggle_kernel     one thread per counts / string source
+//   coco_scan_kernel           one workgroup per source bitmap: prefix XOR in pixel order, padding cleared
+//   coco_merge_kernel          one workgroup per mask: OR of its sources, popcount area, first / last nonempty column
+//   coco_mask_iou_kernel       one wave per (det, gt) pair: popcount of the AND over the shared columns; union = sum of the
+//                              areas - intersection
+//   coco_bbox_iou_kernel       one thread per pair: bbIou in float64
+//   coco_match_kernel          one wave per (image, category): lane t + 10 a runs evaluateImg's loop for IoU threshold t, area
+//                              range a; lanes 40..63 idle
+//
+// Built with -ffp-contract=off: the polygon arithmetic and bbIou must round as C does.
+#include "om_common.h"
+
+namespace om {
+
+constexpr int COCO_SCAN_THREADS = 256;
+constexpr int COCO_MERGE_THREADS = 256;
+constexpr int COCO_T = 10;              // IoU thresholds
+constexpr int COCO_A = 4;               // area ranges
+
+__device__ inline void toggle(uint32_t* bm, int h, int hw, long long p, long long n_pix) {
+    if (p < 0 || p >= n_pix) return;    // the position h * w closing the last column is no pixel
+    const int x = (int)(p / h), y = (int)(p - (long long)x * h);
+    atomicXor(bm + (size_t)x * hw + (y >> 5), 1u << (y & 31));
+}
+
+// point d of edge j of the upsampled polygon (rleFrPoly's first loop, including its flip rule).  A zero-length edge (a repeated
+// vertex) divides 0 / 0: its one point has u = xs exactly and v = (int)NaN, undefined in C (x86: INT_MIN, here 0); v only ever
+// enters through min(v, v_prev) and the clamp of y at 0, so every value <= 0 gives the same mask.
+__device__ inline void edge_point(const int* xs_, const int* ys_, int k, int j, int d, int& u, int& v) {
+    int xs = xs_[j], xe = xs_[j + 1 == k ? 0 : j + 1], ys = ys_[j], ye = ys_[j + 1 == k ? 0 : j + 1];
+    const int dx = abs(xe - xs), dy = abs(ys - ye);
+    const bool flip = (dx >= dy && xs > xe) || (dx < dy && ys > ye);
+    if (flip) { int t = xs; xs = xe; xe = t; t = ys; ys = ye; ye = t; }
+    const double s = dx >= dy ? (double)(ye - ys) / dx : (double)(xe - xs) / dy;
+    if (dx >= dy) {
+        const int t = flip ? dx - d : d;
+        u = t + xs; v = (int)(ys + s * t + .5);
+    } else {
+        const int t = flip ? dy - d : d;
+        v = t + ys; u = (int)(xs + s * t + .5);
+    }
+}
+
+__device__ inline int edge_points(const int* xs_, const int* ys_, int k, int j) {
+    const int n = j + 1 == k ? 0 : j + 1;
+    return max(abs(xs_[j] - xs_[n]), abs(ys_[j] - ys_[n])) + 1;
+}
+
+constexpr int COCO_MAX_POLY = 4096;     // vertices per polygon held in LDS
+
+__global__ __launch_bounds__(64) void coco_poly_toggle_kernel(const int32_t* src_mask, const int64_t* src_data_off,
+                                                              const int32_t* src_len, const int64_t* src_word_off,
+                                                              const int32_t* mask_hw, const double* poly, uint32_t* bitmaps) {
+    __shared__ int s_x[COCO_MAX_POLY], s_y[COCO_MAX_POLY];
+    const int s = blockIdx.x, lane = threadIdx.x;
+    const int m = src_mask[s], h = mask_hw[2 * m], w = mask_hw[2 * m + 1], hw = (h + 31) >> 5;
+    const int k = src_len[s] / 2;                               // vertices (an odd trailing number is ignored, as frPoly does)
+    if (k > COCO_MAX_POLY) return;                              // the host refuses these; never index past the LDS arrays
+    const double* xy = poly + src_data_off[s];
+    uint32_t* bm = bitmaps + src_word_off[s];
+    const double scale = 5;
+    for (int j = lane; j < k; j += 64) {
+        s_x[j] = (int)(scale * xy[2 * j] + .5);
+        s_y[j] = (int)(scale * xy[2 * j + 1] + .5);
+    }
+    __syncthreads();
+    const long long n_pix = (long long)h * w;
+    for (int j = lane; j < k; j += 64) {
+        const int n = edge_points(s_x, s_y, k, j);
+        int pu, pv;                                             // the previous point of the flattened list
+        if (j > 0) edge_point(s_x, s_y, k, j - 1, edge_points(s_x, s_y, k, j - 1) - 1, pu, pv);
+        for (int d = 0; d < n; ++d) {
+            int u, v;
+            edge_point(s_x, s_y, k, j, d, u, v);
+            if ((j > 0 || d > 0) && u != pu) {
+                double xd = (double)(u < pu ? u : u - 1);
+                xd = (xd + .5) / scale - .5;
+                if (!(floor(xd) != xd || xd < 0 || xd > w - 1)) {
+                    double yd = (double)(v < pv ? v : pv);
+                    yd = (yd + .5) / scale - .5;
+                    if (yd < 0) yd = 0;
+                    else if (yd > h) yd = h;
+                    yd = ceil(yd);
+                    toggle(bm, h, hw, (long long)(int)xd * h + (int)yd, n_pix);
+                }
+            }
+            pu = u; pv = v;
+        }
+    }
+}
+
+// kind 1: uint32 counts at data_off; kind 2: string bytes at data_off (rleFrString: 5 bits per char from '0', bit 5 continues,
+// bit 4 of the last char sign-extends; from the fourth count on, the value is a difference against the count two back)
+__global__ __launch_bounds__(256) void coco_seq_toggle_kernel(int first, int n, const int32_t* src_kind, const int32_t* src_mask,
+                                                              const int64_t* src_data_off, const int32_t* src_len,
+                                                              const int64_t* src_word_off, const int32_t* mask_hw,
+                                                              const uint32_t* counts, const uint8_t* strings, uint32_t* bitmaps) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int s = first + i, m = src_mask[s], h = mask_hw[2 * m], w = mask_hw[2 * m + 1], hw = (h + 31) >> 5;
+    const long long n_pix = (long long)h * w;
+    uint32_t* bm = bitmaps + src_word_off[s];
+    const int len = src_len[s];
+    long long pos = 0;
+    if (src_kind[s] == 1) {
+        const uint32_t* c = counts + src_data_off[s];
+        for (int j = 0; j < len && pos < n_pix; ++j) {
+            pos += c[j];
+            toggle(bm, h, hw, pos, n_pix);
+        }
+    } else {
+        const uint8_t* str = strings + src_data_off[s];
+        uint32_t c1 = 0, c2 = 0;                                // the counts one and two back
+        int p = 0, mcnt = 0;
+        while (p < len && pos < n_pix) {
+            long x = 0;
+            int kk = 0, more = 1;
+            while (more && p < len) {
+                const int c = (int)str[p] - 48;
+                if (kk < 12) x |= (long)(c & 0x1f) << 5 * kk;          // a valid string never has more than 7 chars per count
+                more = c & 0x20;
+                p++; kk++;
+                if (!more && (c & 0x10) && kk < 12) x |= -1L << 5 * kk;
+            }
+            if (mcnt > 2) x += (long)c2;
+            const uint32_t cnt = (uint32_t)x;
+            c2 = c1; c1 = cnt; ++mcnt;
+            pos += cnt;
+            toggle(bm, h, hw, pos, n_pix);
+        }
+    }
+}
+
+// prefix XOR over one source bitmap in pixel order: within a word x ^= x << 1, << 2, ... << 16; across words the workgroup scans
+// the words' parities.  Padding bits hold no toggle, so a column's last word carries exactly the parity at its last row.
+__global__ __launch_bounds__(COCO_SCAN_THREADS) void coco_scan_kernel(const int32_t* src_mask, const int64_t* src_word_off,
+                                                                      const int32_t* mask_hw, uint32_t* bitmaps) {
+    __shared__ uint32_t s_par[COCO_SCAN_THREADS];
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const int m = src_mask[s], h = mask_hw[2 * m], w = mask_hw[2 * m + 1], hw = (h + 31) >> 5;
+    uint32_t* bm = bitmaps + src_word_off[s];
+    const long long n_words = (long long)w * hw;
+    const long long per = (n_words + COCO_SCAN_THREADS - 1) / COCO_SCAN_THREADS;
+    const long long lo = min(n_words, per * tid), hi = min(n_words, lo + per);
+    uint32_t par = 0;
+    for (long long i = lo; i < hi; ++i) par ^= __popc(bm[i]) & 1u;
+    s_par[tid] = par;
+    __syncthreads();
+    for (int off = 1; off < COCO_SCAN_THREADS; off <<= 1) {     // inclusive Hillis-Steele XOR scan
+        const uint32_t v = tid >= off ? s_par[tid - off] : 0u;
+        __syncthreads();
+        s_par[tid] ^= v;
+        __syncthreads();
+    }
+    uint32_t carry = tid > 0 ? s_par[tid - 1] : 0u;
+    const int tail = h & 31;
+    const uint32_t tail_mask = tail ? (1u << tail) - 1u : 0xffffffffu;
+    for (long long i = lo; i < hi; ++i) {
+        uint32_t x = bm[i];
+        x ^= x << 1; x ^= x << 2; x ^= x << 4; x ^= x << 8; x ^= x << 16;
+        if (carry) x = ~x;
+        carry = x >> 31;
+        if ((int)(i % hw) == hw - 1) x &= tail_mask;
+        bm[i] = x;
+    }
+}
+
+// mask = OR of its sources (one source: its bitmap IS the mask's), area = popcount, [col_lo, col_hi] = nonempty columns
+__global__ __launch_bounds__(COCO_MERGE_THREADS) void coco_merge_kernel(const int32_t* mask_hw, const int64_t* mask_word_off,
+                                                                        const int32_t* mask_src_first,
+                                                                        const int64_t* mask_src_word_off,
+                                                                        uint32_t* bitmaps, int32_t* mask_stats) {
+    __shared__ unsigned long long s_area;
+    __shared__ int s_lo, s_hi;
+    const int m = blockIdx.x, tid = threadIdx.x;
+    const int h = mask_hw[2 * m], w = mask_hw[2 * m + 1], hw = (h + 31) >> 5;
+    const int s0 = mask_src_first[m], s1 = mask_src_first[m + 1];
+    if (tid == 0) { s_area = 0; s_lo = w; s_hi = -1; }
+    __syncthreads();
+    uint32_t* dst = bitmaps + mask_word_off[m];
+    const long long n_words = (long long)w * hw;
+    unsigned long long area = 0;
+    int lo = w, hi = -1;
+    for (long long i = tid; i < n_words; i += COCO_MERGE_THREADS) {
+        uint32_t v = 0;
+        for (int s = s0; s < s1; ++s) v |= bitmaps[mask_src_word_off[s] + i];
+        if (s1 - s0 != 1 || mask_src_word_off[s0] != mask_word_off[m]) dst[i] = v;
+        if (v) {
+            area += __popc(v);
+            const int x = (int)(i / hw);
+            lo = min(lo, x); hi = max(hi, x);
+        }
+    }
+    atomicAdd(&s_area, area);
+    atomicMin(&s_lo, lo);
+    atomicMax(&s_hi, hi);
+    __syncthreads();
+    if (tid == 0) {
+        mask_stats[3 * m] = (int32_t)s_area;
+        mask_stats[3 * m + 1] = s_lo;
+        mask_stats[3 * m + 2] = s_hi;
+    }
+}
+
+__device__ inline unsigned long long wave_sum(unsigned long long v) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// maskUtils.iou on two RLEs (rleIou): i / u in double, 0 when i == 0, u = the det's area for a crowd GT; masks of different
+// sizes give -1.  Only the columns both masks occupy are read (pycocotools' bounding-box pre-filter gives 0 where they do not
+// overlap, and i = 0 there anyway).
+__global__ __launch_bounds__(64) void coco_mask_iou_kernel(int n_pairs, const int32_t* pairs, const uint8_t* pair_crowd,
+                                                           const int32_t* mask_hw, const int64_t* mask_word_off,
+                                                           const int32_t* mask_stats, const uint32_t* bitmaps, double* iou) {
+    const int p = blockIdx.x, lane = threadIdx.x;
+    if (p >= n_pairs) return;
+    const int d = pairs[2 * p], g = pairs[2 * p + 1];
+    if (mask_hw[2 * d] != mask_hw[2 * g] || mask_hw[2 * d + 1] != mask_hw[2 * g + 1]) {
+        if (lane == 0) iou[p] = -1.0;
+        return;
+    }
+    const int hw = (mask_hw[2 * d] + 31) >> 5;
+    const int lo = max(mask_stats[3 * d + 1], mask_stats[3 * g + 1]), hi = min(mask_stats[3 * d + 2], mask_stats[3 * g + 2]);
+    unsigned long long inter = 0;
+    if (lo <= hi) {
+        const uint32_t* a = bitmaps + mask_word_off[d];
+        const uint32_t* b = bitmaps + mask_word_off[g];
+        for (long long i = (long long)lo * hw + lane; i < (long long)(hi + 1) * hw; i += 64) {
+            inter += __popc(a[i] & b[i]);
+        }
+        inter = wave_sum(inter);
+    }
+    if (lane != 0) return;
+    if (inter == 0) { iou[p] = 0.0; return; }
+    // the union outside the shared columns is each mask's own area there: area_d + area_g - inter over everything
+    const unsigned long long u = pair_crowd[p] ? (unsigned long long)mask_stats[3 * d]
+                                               : (unsigned long long)mask_stats[3 * d] + mask_stats[3 * g] - inter;
+    iou[p] = (double)(uint32_t)inter / (double)(uint32_t)u;
+}
+
+// bbIou (maskApi.c), boxes x, y, w, h in double
+__global__ __launch_bounds__(256) void coco_bbox_iou_kernel(int n_pairs, const int32_t* pairs, const uint8_t* pair_crowd,
+                                                            const double* det_box, const double* gt_box, double* iou) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_pairs) return;
+    const double* D = det_box + 4 * pairs[2 * p];
+    const double* G = gt_box + 4 * pairs[2 * p + 1];
+    const double ga = G[2] * G[3], da = D[2] * D[3];
+    double r = 0;
+    const double w = fmin(D[2] + D[0], G[2] + G[0]) - fmax(D[0], G[0]);
+    if (w > 0) {
+        const double hh = fmin(D[3] + D[1], G[3] + G[1]) - fmax(D[1], G[1]);
+        if (hh > 0) {
+            const double i = w * hh;
+            const double u = pair_crowd[p] ? da : da + ga - i;
+            r = i / u;
+        }
+    }
+    iou[p] = r;
+}
+
+// evaluateImg (cocoeval.py) for one (image, category): dets already in score order and cut to maxDets[-1]; gts in json order.
+// ious: [D][G] row-major at iou_off.  Lane t + 10 a: gts with _ignore = 0 are visited first, then the ignored ones, each group in
+// json order (the stable mergesort of _ignore).  Outputs per lane and det: the matched gt's id (0: none), ignore flag.
+__global__ __launch_bounds__(64) void coco_match_kernel(int n_groups, const int32_t* dt_first, const int32_t* gt_first,
+                                                        const int64_t* iou_off, const double* ious, const double* dt_area,
+                                                        const double* gt_area, const uint8_t* gt_crowd, const int64_t* gt_id,
+                                                        const double* area_rng, const double* iou_thrs, int n_dt_total,
+                                                        int n_gt_total, uint8_t* gt_matched, int64_t* dt_match,
+                                                        uint8_t* dt_ignore) {
+    const int grp = blockIdx.x, lane = threadIdx.x;
+    if (grp >= n_groups || lane >= COCO_T * COCO_A) return;
+    const int t = lane % COCO_T, a = lane / COCO_T;
+    const int d0 = dt_first[grp], D = dt_first[grp + 1] - d0, g0 = gt_first[grp], G = gt_first[grp + 1] - g0;
+    const double lo = area_rng[2 * a], hi = area_rng[2 * a + 1];
+    const double* io = ious + iou_off[grp];
+    uint8_t* gtm = gt_matched + (size_t)lane * n_gt_total + g0;
+    for (int g = 0; g < G; ++g) gtm[g] = 0;
+    auto ig = [&](int g) -> int {
+        const double ar = gt_area[g0 + g];
+        return (gt_crowd[g0 + g] || ar < lo || ar > hi) ? 1 : 0;
+    };
+    const double thr = fmin(iou_thrs[t], 1 - 1e-10);
+    for (int d = 0; d < D; ++d) {
+        double best = thr;
+        int m = -1, m_ig = 0;
+        if (G > 0) {
+            for (int pass = 0; pass < 2; ++pass) {
+                if (pass == 1 && m > -1 && m_ig == 0) break;    // an ignored gt after a matched regular one
+                for (int g = 0; g < G; ++g) {
+                    if (ig(g) != pass) continue;
+                    if (gtm[g] && !gt_crowd[g0 + g]) continue;
+                    const double v = io[(size_t)d * G + g];
+                    if (v < best) continue;
+                    best = v; m = g; m_ig = pass;
+                }
+            }
+        }
+        int64_t id = 0;
+        int dig = 0;
+        if (m > -1) {
+            dig = m_ig;
+            id = gt_id[g0 + m];
+            gtm[m] = 1;
+        }
+        // "matched" is dtm != 0: a gt with id 0 counts as unmatched here, as in pycocotools
+        const double ar = dt_area[d0 + d];
+        if (id == 0 && (ar < lo || ar > hi)) dig = 1;
+        dt_match[(size_t)lane * n_dt_total + d0 + d] = id;
+        dt_ignore[(size_t)lane * n_dt_total + d0 + d] = (uint8_t)dig;
+    }
+}
+
+}  // namespace om
+
+
+extern "C" {
+
+size_t om_cocoeval_workspace_bytes(long long bitmap_words, int n_masks) {
+    if (bitmap_words < 0 || n_masks < 0) return 0;
+    return om::align_up((size_t)bitmap_words * 4, 256) + om::align_up((size_t)n_masks * 12, 256);
+}
+
+int om_cocoeval_masks(int n_masks, const int32_t* mask_hw, const int64_t* mask_word_off, const int32_t* mask_src_first,
+                      const int64_t* mask_src_word_off, int n_poly, int n_srcs, const int32_t* src_kind, const int32_t* src_mask, const int64_t* src_data_off,
+                      const int32_t* src_len, const int64_t* src_word_off, const double* poly, const uint32_t* counts,
+                      const uint8_t* strings, long long bitmap_words, void* workspace, size_t ws_bytes, om_stream stream) {
+    OM_REQUIRE(n_masks >= 0 && n_poly >= 0 && n_srcs >= n_poly && bitmap_words >= 0, OM_EINVAL, "om_cocoeval_masks: bad argument");
+    if (n_masks == 0) return OM_OK;
+    OM_REQUIRE(mask_hw && mask_word_off && mask_src_first && workspace && (n_srcs == 0 || mask_src_word_off), OM_EINVAL, "om_cocoeval_masks: null pointer");
+    OM_REQUIRE(n_srcs == 0 || (src_kind && src_mask && src_data_off && src_len && src_word_off), OM_EINVAL,
+               "om_cocoeval_masks: null source pointer");
+    const size_t need = om_cocoeval_workspace_bytes(bitmap_words, n_masks);
+    OM_REQUIRE(ws_bytes >= need, OM_ENOMEM, "om_cocoeval_masks: workspace of %zu bytes, %zu needed", ws_bytes, need);
+    OM_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 256 == 0, OM_EINVAL, "om_cocoeval_masks: workspace not 256-byte aligned");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    uint32_t* bitmaps = static_cast<uint32_t*>(workspace);
+    int32_t* stats = reinterpret_cast<int32_t*>(static_cast<char*>(workspace) + om::align_up((size_t)bitmap_words * 4, 256));
+    OM_CHECK_HIP(hipMemsetAsync(bitmaps, 0, (size_t)bitmap_words * 4, st));
+    if (n_poly > 0) {
+        OM_REQUIRE(poly, OM_EINVAL, "om_cocoeval_masks: polygons without coordinates");
+        hipLaunchKernelGGL(om::coco_poly_toggle_kernel, dim3(n_poly), dim3(64), 0, st, src_mask, src_data_off, src_len,
+                           src_word_off, mask_hw, poly, bitmaps);
+        OM_CHECK_HIP(hipGetLastError());
+    }
+    if (n_srcs > n_poly) {
+        const int n = n_srcs - n_poly;
+        hipLaunchKernelGGL(om::coco_seq_toggle_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n_poly, n, src_kind, src_mask,
+                           src_data_off, src_len, src_word_off, mask_hw, counts, strings, bitmaps);
+        OM_CHECK_HIP(hipGetLastError());
+    }
+    if (n_srcs > 0) {
+        hipLaunchKernelGGL(om::coco_scan_kernel, dim3(n_srcs), dim3(om::COCO_SCAN_THREADS), 0, st, src_mask, src_word_off, mask_hw,
+                           bitmaps);
+        OM_CHECK_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(om::coco_merge_kernel, dim3(n_masks), dim3(om::COCO_MERGE_THREADS), 0, st, mask_hw, mask_word_off,
+                       mask_src_first, mask_src_word_off, bitmaps, stats);
+    OM_CHECK_HIP(hipGetLastError());
+    return OM_OK;
+}
+
+int om_cocoeval_mask_iou(int n_pairs, const int32_t* pairs, const uint8_t* pair_crowd, int n_masks, const int32_t* mask_hw,
+                         const int64_t* mask_word_off, long long bitmap_words, const void* workspace, double* iou,
+                         om_stream stream) {
+    OM_REQUIRE(n_pairs >= 0 && n_masks >= 0, OM_EINVAL, "om_cocoeval_mask_iou: bad argument");
+    if (n_pairs == 0) return OM_OK;
+    OM_REQUIRE(pairs && pair_crowd && mask_hw && mask_word_off && workspace && iou, OM_EINVAL, "om_cocoeval_mask_iou: null pointer");
+    const uint32_t* bitmaps = static_cast<const uint32_t*>(workspace);
+    const int32_t* stats =
+        reinterpret_cast<const int32_t*>(static_cast<const char*>(workspace) + om::align_up((size_t)bitmap_words * 4, 256));
+    hipLaunchKernelGGL(om::coco_mask_iou_kernel, dim3(n_pairs), dim3(64), 0, static_cast<hipStream_t>(stream), n_pairs, pairs,
+                       pair_crowd, mask_hw, mask_word_off, stats, bitmaps, iou);
+    OM_CHECK_HIP(hipGetLastError());
+    return OM_OK;
+}
+
+int om_cocoeval_mask_stats(int n_masks, long long bitmap_words, const void* workspace, int32_t* stats, om_stream stream) {
+    OM_REQUIRE(n_masks >= 0 && bitmap_words >= 0, OM_EINVAL, "om_cocoeval_mask_stats: bad argument");
+    if (n_masks == 0) return OM_OK;
+    OM_REQUIRE(workspace && stats, OM_EINVAL, "om_cocoeval_mask_stats: null pointer");
+    OM_CHECK_HIP(hipMemcpyAsync(stats, static_cast<const char*>(workspace) + om::align_up((size_t)bitmap_words * 4, 256),
+                                (size_t)n_masks * 12, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+    return OM_OK;
+}
+
+int om_cocoeval_bbox_iou(int n_pairs, const int32_t* pairs, const uint8_t* pair_crowd, const double* det_box,
+                         const double* gt_box, double* iou, om_stream stream) {
+    OM_REQUIRE(n_pairs >= 0, OM_EINVAL, "om_cocoeval_bbox_iou: bad argument");
+    if (n_pairs == 0) return OM_OK;
+    OM_REQUIRE(pairs && pair_crowd && det_box && gt_box && iou, OM_EINVAL, "om_cocoeval_bbox_iou: null pointer");
+    hipLaunchKernelGGL(om::coco_bbox_iou_kernel, dim3((n_pairs + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       n_pairs, pairs, pair_crowd, det_box, gt_box, iou);
+    OM_CHECK_HIP(hipGetLastError());
+    return OM_OK;
+}
+
+int om_cocoeval_match(int n_groups, const int32_t* dt_first, const int32_t* gt_first, const int64_t* iou_off,
+                      const double* ious, const double* dt_area, const double* gt_area, const uint8_t* gt_crowd,
+                      const int64_t* gt_id, const double* area_rng, const double* iou_thrs, int n_dt_total, int n_gt_total,
+                      uint8_t* gt_matched, int64_t* dt_match, uint8_t* dt_ignore, om_stream stream) {
+    OM_REQUIRE(n_groups >= 0 && n_dt_total >= 0 && n_gt_total >= 0, OM_EINVAL, "om_cocoeval_match: bad argument");
+    if (n_groups == 0 || n_dt_total == 0) return OM_OK;
+    OM_REQUIRE(dt_first && gt_first && iou_off && dt_area && area_rng && iou_thrs && dt_match && dt_ignore, OM_EINVAL,
+               "om_cocoeval_match: null pointer");
+    OM_REQUIRE(n_gt_total == 0 || (ious && gt_area && gt_crowd && gt_id && gt_matched), OM_EINVAL,
+               "om_cocoeval_match: null gt pointer");
+    hipLaunchKernelGGL(om::coco_match_kernel, dim3(n_groups), dim3(64), 0, static_cast<hipStream_t>(stream), n_groups, dt_first,
+                       gt_first, iou_off, ious, dt_area, gt_area, gt_crowd, gt_id, area_rng, iou_thrs, n_dt_total, n_gt_total,
+                       gt_matched, dt_match, dt_ignore);
+    OM_CHECK_HIP(hipGetLastError());
+    return OM_OK;
+}
+
+}  // extern "C"

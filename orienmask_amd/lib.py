@@ -146,6 +146,12 @@ SIGNATURES = {
     "om_recover_masks_rle_strings": (_i, [_vp, _i, _vp, _i, _vp, _vp, ctypes.c_longlong, _vp, _vp, _vp, _vp]),
     "om_visualize_workspace_bytes": (_sz, [_vp, _i]),
     "om_visualize": (_i, [_vp, _i, _vp, _sz, _vp]),
+    "om_cocoeval_workspace_bytes": (_sz, [ctypes.c_longlong, _i]),
+    "om_cocoeval_masks": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _vp, _sz, _vp]),
+    "om_cocoeval_mask_stats": (_i, [_i, ctypes.c_longlong, _vp, _vp, _vp]),
+    "om_cocoeval_mask_iou": (_i, [_i, _vp, _vp, _i, _vp, _vp, ctypes.c_longlong, _vp, _vp, _vp]),
+    "om_cocoeval_bbox_iou": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "om_cocoeval_match": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "om_post_kernel_occupancy": (_i, [_i, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "om_nms_workspace_bytes": (_sz, [_i]),
     "om_nms": (_i, [_vp, _i, _f, _vp, _vp, _vp, _sz, _vp]),

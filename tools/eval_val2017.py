@@ -102,8 +102,18 @@ def synthetic_checkpoint():
     return {"epoch": 0, "state_dict": synth.synth_state_dict(3, obj_bias=-16.0, head_gain=4.0), "config": {"model": dict(DEFAULT_MODEL)}}
 
 
-def coco_eval(gt_file, out_dir, with_mask=True):
-    """coco_eval.py:80-101: returns {'bbox': stats[12], 'segm': stats[12]}, or None when pycocotools is absent."""
+def coco_eval(gt_file, out_dir, with_mask=True, evaluator="pycocotools"):
+    """coco_eval.py:80-101: returns {'bbox': stats[12], 'segm': stats[12]}, or None when pycocotools is absent.
+    evaluator='native': orienmask_amd.cocoeval.COCOEvaluator (HIP, no pycocotools) scores the same files."""
+    if evaluator == "native":
+        from orienmask_amd.cocoeval import COCOEvaluator, COCOGroundTruth
+        gt = COCOGroundTruth.from_file(gt_file)
+        out = {}
+        for kind in (("bbox", "segm") if with_mask else ("bbox",)):
+            ev = COCOEvaluator(gt, os.path.join(out_dir, "%s_prediction.json" % kind), kind)
+            ev.evaluate(); ev.accumulate(); ev.summarize()
+            out[kind] = [float(v) for v in ev.stats]
+        return out
     try:
         from pycocotools.coco import COCO
         from pycocotools.cocoeval import COCOeval
@@ -129,6 +139,8 @@ def main():
     ap.add_argument("--precision", default=None, choices=("f32", "f32_split", "f16"))
     ap.add_argument("--in-flight", type=int, default=1, help="batches in flight (1 = the reference's loop and timers)")
     ap.add_argument("--tol", type=float, default=0.001)
+    ap.add_argument("--evaluator", default="pycocotools", choices=("pycocotools", "native"),
+                    help="who scores the json files: pycocotools (default) or orienmask_amd.cocoeval (HIP, no pycocotools)")
     ap.add_argument("--synthetic", type=int, default=0,
                     help="no data: N synthetic images through a seeded random checkpoint, up to the json files (no AP)")
     args = ap.parse_args()
@@ -192,8 +204,9 @@ def main():
     rc = 3
     gt_file = os.path.join(args.coco_root, "annotations", "instances_val2017.json")
     if not args.synthetic and os.path.exists(gt_file):
-        ev = coco_eval(gt_file, args.out)
+        ev = coco_eval(gt_file, args.out, evaluator=args.evaluator)
         if ev is not None:
+            summary["evaluator"] = args.evaluator
             summary["eval"] = {k: dict(zip(METRIC_KEYS, v)) for k, v in ev.items()}
             if args.limit:
                 rc = 0
