@@ -587,3 +587,79 @@ def test_blob_checksum_tells_blobs_apart():
     h = torch.randn(4099, generator=g).half()
     h2 = h.clone(); h2[77] = h2[77] + 1
     assert blob_checksum(h) == blob_checksum(h.clone()) and blob_checksum(h2) != blob_checksum(h)
+
+
+@pytest.mark.parametrize("model", ["OrienMaskYOLOFPNPlus", "OrienMaskYOLO"])
+def test_audit_wiring_table_matches_the_oracle(model):
+    """tests/test_layer_audit.py builds every layer's input from its wiring table out of the HIP forward's stored outputs.  Pin
+    the table to the oracle's forward: with its _cbl / _plain calls recorded (1 x 3 x 64 x 96), building each layer's input and
+    residual from the table out of the recorded outputs reproduces what the oracle fed that layer, bit for bit."""
+    import torch.nn.functional as F
+    from test_layer_audit import record_oracle_calls, wiring
+    from oracle import orienmask_ref as R
+    sd = synth.synth_state_dict(3, model=model)
+    x = synth.synth_image_batch(5, 1, 64, 96)
+    rec = record_oracle_calls(R.forward if model == "OrienMaskYOLOFPNPlus" else R.forward_yolo, sd, x)
+    table = wiring(model)
+    assert sorted(rec) == sorted(table), set(rec) ^ set(table)
+    outs = {n: r[2] for n, r in rec.items()}
+    outs["x"] = x
+    for name, (inputs, res) in table.items():
+        parts = [F.interpolate(outs[p], scale_factor=u, mode="nearest") if u > 1 else outs[p] for p, u in inputs]
+        built_in = parts[0] if len(parts) == 1 else torch.cat(parts, 1)
+        got_in, got_res, _ = rec[name]
+        assert built_in.shape == got_in.shape and torch.equal(built_in, got_in), name
+        if res is None:
+            assert got_res is None, name
+        else:
+            assert got_res is not None and torch.equal(outs[res], got_res), name
+
+
+# kernels the chooser reaches only WITHOUT kept activations (fused stems, up-sampling on read), so the layer audit cannot read their
+# layers; each is pinned, bit for bit or within its bound, to the path the audit covers by these tests of tests/test_hip_parity.py
+AUDIT_EXEMPT = [
+    ("f32_split", r"conv_stem2_split_kernel<\d+,\d+>", ("test_stem2_split_matches_two_kernels", "test_stem3_split_equals_stem2_then_1x1")),
+    ("f32_split", re.escape("(in the previous layer's kernel)"),
+     ("test_stem2_split_matches_two_kernels", "test_stem3_split_equals_stem2_then_1x1")),
+    ("f32_split", r"conv_igemm_split_kernel<\d+,\d+,gather>", ("test_conv_split_gather_equals_materialised_concat",)),
+    ("f16", r"conv_stem2_f16_kernel<\d+,\d+>", ("test_stem2_f16_matches_two_kernels",)),
+    ("f16", re.escape("(in the previous layer's kernel)"), ("test_stem2_f16_matches_two_kernels",)),
+    ("f16", r"conv_igemm_f16_kernel<\d+,\d+,gather>", ("test_forward_gather_equals_replicated_concat",)),
+]
+
+
+def test_layer_audit_covers_every_chooser_kernel(built):
+    """Every kernel / tile the chooser picks for the bench's shapes (bs 32 and 64 at 544^2) and for bs 1 and 6 at 544^2, 1 x 160 x 128
+    and 2 x 320 x 416 -- activations not kept, each precision -- runs some layer of tests/test_layer_audit.py's configurations (with
+    activations kept), or is one of AUDIT_EXEMPT's, whose pinning tests must exist.  A chooser change that adds a kernel or tile
+    fails here until the audit reaches it; an exemption nothing needs any more fails too."""
+    from orienmask_amd import model as M
+    from test_layer_audit import AUDIT_CONFIGS
+    nets = {}
+
+    def kernels(model, precision, keep, shape):
+        key = (model, precision, keep)
+        if key not in nets:
+            nets[key] = getattr(M, model)(3, 80).set_precision(precision).keep_activations(keep)
+        return {k for _, k in nets[key].layer_kernels(*shape)}
+
+    audited = set()
+    for _, model, precision, _, shape in AUDIT_CONFIGS:
+        audited |= {(precision, k) for k in kernels(model, precision, True, shape)}
+    shapes = [(32, 544, 544), (64, 544, 544), (1, 544, 544), (6, 544, 544), (1, 160, 128), (2, 320, 416)]
+    needed = {(p, k) for p in ("f32", "f32_split", "f16") for s in shapes for k in kernels("OrienMaskYOLOFPNPlus", p, False, s)}
+    # the issue-level list of what the audit must reach, so that a chooser change which drops one is noticed as well
+    for k in ("conv_igemm_f32_kernel<128,128>", "wino24_gemm_kernel<64,64>", "wino_gemm_kernel<64,64>", "wino_fused_kernel<64,128>",
+              "wino14_wide_kernel<128,128>", "wino14_split_kernel<128,64>", "conv3x3_f16_tall_kernel<512,128>",
+              "conv_igemm_f16_kernel<64,64>"):
+        assert any(a[1] == k for a in audited), k
+    hip_tests = set(re.findall(r"^def (test_\w+)", open(os.path.join(REPO, "tests", "test_hip_parity.py")).read(), re.M))
+    used = set()
+    for p, k in sorted(needed - audited):
+        hit = [i for i, (ep, pat, _) in enumerate(AUDIT_EXEMPT) if ep == p and re.fullmatch(pat, k)]
+        assert hit, "%s kernel %s is chosen for a benchmarked shape but no layer audit configuration runs it" % (p, k)
+        used.update(hit)
+    for i, (p, pat, tests) in enumerate(AUDIT_EXEMPT):
+        assert i in used, "stale exemption: the chooser no longer picks %s %s without kept activations" % (p, pat)
+        for t in tests:
+            assert t in hip_tests, "exemption %s %s names %s, which tests/test_hip_parity.py no longer has" % (p, pat, t)
