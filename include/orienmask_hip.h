@@ -569,6 +569,64 @@ int om_nms(const float* dets, int n, float thresh, int64_t* keep, int32_t* n_kee
 int om_nms_ex(const float* dets, int n, float thresh, int semantics, int64_t* keep, int32_t* n_keep, void* workspace,
               size_t ws_bytes, om_stream stream);
 
+/* ---- Loss of the validation epoch: OrienMaskYOLOMultiScaleLoss (eval/orienmask_yolo_loss.py, eval/base.py), values only.
+ *
+ * om_loss_cfg: the loss's constants.  Per scale s < num_scales: grid_h/grid_w, anchors_of_scale[s] (1..3) anchors
+ * anchor_mask[s][.] into anchor_w/anchor_h (num_anchors_total <= 9), weight[s][0..6] = the scale's per-item weight
+ * (scales_weight[s] * weight[j], or 1 without `weight`: eval/orienmask_yolo_loss.py:313-315).  label_smooth / label_on are the
+ * values tcls holds off / on the GT's class (float32 of ls and of 1 - ls, ls = 1 / max(C, 40) or 0).  num_classes <= OM_LOSS_MAX_CLASSES; orientation maps are exactly image/4 per side.
+ *
+ * Heads: per scale a bbox head [B, A*(5+C), nH, nW] and an orientation head [B, 2A, H/4, W/4], each read through its element
+ * strides (bbox_stride[s] = b, channel, row, column; orien_stride[s] = b, channel, row; the orientation column stride is 1).
+ * Targets as the reference's collate makes them: gt_bbox [N][4] f32 (normalised cx, cy, w, h), gt_cls [N] i64,
+ * gt_index [B+1] i64 prefix offsets, gt_mask [N][H][W] u8 (0/1), all contiguous.  At most OM_LOSS_MAX_GT GTs per image.
+ *
+ * om_loss writes `result` (device, OM_LOSS_RESULT_FLOATS floats): per scale s at s*OM_LOSS_SCALE_FLOATS the 7 weighted terms
+ * (loss_xy, loss_wh, loss_obj, loss_noobj, loss_cls, loss_orien_pos, loss_orien_neg) then 8 (numerator, count) pairs
+ * (cls_conf, obj_pos, obj_neg, avg_iou, recall50, recall75, orien_pos_acc, orien_neg_acc); at OM_LOSS_FLAG_OFF a flag word
+ * (int32 bits, OM_LOSS_FLAG_*).  No host synchronisation, no allocation; workspace: om_loss_workspace_bytes(cfg, B, N).
+ * The result is bit-identical from call to call: every sum has a fixed order (workgroup partials, then one fixed-order pass).
+ *
+ * om_loss_targets (test entry): scale s's built targets.  Any output may be null.  [B][A][nH][nW](x2 / xC) f32: bbox_pos,
+ * bbox_neg, pos_scale, txy, twh, tiou, tcls; [B][A][H][W] i32 orien_mask (-1 positive, k > 0 negative count, 0 neither)
+ * and [B][A][H][W][2] f32 torien (final: divided by anchor/2 and by the count).  Its workspace: om_loss_workspace_bytes + 512. */
+#define OM_LOSS_MAX_CLASSES 2047
+#define OM_LOSS_MAX_GT 1024
+#define OM_LOSS_TERMS 7
+#define OM_LOSS_METRICS 8
+#define OM_LOSS_SCALE_FLOATS (OM_LOSS_TERMS + 2 * OM_LOSS_METRICS)
+#define OM_LOSS_FLAG_OFF (OM_MAX_SCALES * OM_LOSS_SCALE_FLOATS)
+#define OM_LOSS_RESULT_FLOATS (OM_LOSS_FLAG_OFF + 1)
+#define OM_LOSS_FLAG_NONFINITE_WH 1     /* a pred_wh element is not finite (the reference prints and exits) */
+#define OM_LOSS_FLAG_TOO_MANY_GT 2      /* an image has more than OM_LOSS_MAX_GT GTs or gt_index is not a valid prefix */
+#define OM_LOSS_FLAG_BAD_CLASS 4        /* a gt_cls value outside [0, num_classes) */
+
+typedef struct om_loss_cfg {
+    int32_t num_scales;
+    int32_t grid_h[OM_MAX_SCALES], grid_w[OM_MAX_SCALES];
+    int32_t image_h, image_w;
+    int32_t anchors_of_scale[OM_MAX_SCALES];
+    int32_t anchor_mask[OM_MAX_SCALES][3];
+    int32_t num_anchors_total;
+    float anchor_w[OM_MAX_ANCHORS], anchor_h[OM_MAX_ANCHORS];
+    int32_t num_classes;
+    float center_region, valid_region;
+    float label_smooth, label_on;        /* tcls off / on values: float32(ls) and float32(1 - ls) */
+    float obj_ignore_threshold;
+    float weight[OM_MAX_SCALES][OM_LOSS_TERMS];
+    int64_t bbox_stride[OM_MAX_SCALES][4];
+    int64_t orien_stride[OM_MAX_SCALES][3];
+} om_loss_cfg;
+
+size_t om_loss_workspace_bytes(const om_loss_cfg* cfg, int B, int N);
+int om_loss(const om_loss_cfg* cfg, const float* const* bbox, const float* const* orien, int B, const float* gt_bbox,
+            const int64_t* gt_cls, const int64_t* gt_index, const uint8_t* gt_mask, int N, float* result, void* workspace,
+            size_t ws_bytes, om_stream stream);
+int om_loss_targets(const om_loss_cfg* cfg, const float* const* bbox, int B, const float* gt_bbox, const int64_t* gt_cls,
+                    const int64_t* gt_index, const uint8_t* gt_mask, int N, int scale, float* bbox_pos, float* bbox_neg,
+                    float* pos_scale, float* txy, float* twh, float* tiou, float* tcls, int32_t* orien_mask, float* torien,
+                    void* workspace, size_t ws_bytes, om_stream stream);
+
 /* ---- Several batches in flight.  Every entry point only enqueues kernels on the caller's stream and keeps no per-call state in
  *      the model handle (profiling apart): om_forward / om_forward_f16 / om_postprocess may be issued for different batches
  *      on different HIP streams at the same time, provided each batch in flight has its OWN workspace (and output buffers);

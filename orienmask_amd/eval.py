@@ -389,3 +389,7 @@ class OrienMaskYOLOPostProcess:
         self.last_keep = [out_keep[b, :k] for b, k in enumerate(counts)]
         return [{"bbox": out_bbox[b, :k], "mask": mask_bool[b, :k], "cls": out_cls[b, :k]}
                 for b, k in enumerate(counts)]
+
+
+# the validation loss and its counter (orienmask_amd/loss.py): eval/orienmask_yolo_loss.py, eval/counter.py
+from .loss import EvalCounter, OrienMaskYOLOMultiScaleLoss  # noqa: E402,F401

@@ -60,6 +60,36 @@ class VisImage(ctypes.Structure):
                 ("with_mask", ctypes.c_int32), ("draw_boxes", ctypes.c_int32), ("alpha", ctypes.c_float)]
 
 
+OM_LOSS_MAX_CLASSES = 2047      # include/orienmask_hip.h: the loss's limits and result vector layout
+OM_LOSS_MAX_GT = 1024
+OM_LOSS_TERMS = 7
+OM_LOSS_METRICS = 8
+OM_LOSS_SCALE_FLOATS = OM_LOSS_TERMS + 2 * OM_LOSS_METRICS
+OM_LOSS_FLAG_OFF = OM_MAX_SCALES * OM_LOSS_SCALE_FLOATS
+OM_LOSS_RESULT_FLOATS = OM_LOSS_FLAG_OFF + 1
+OM_LOSS_FLAG_NONFINITE_WH = 1
+OM_LOSS_FLAG_TOO_MANY_GT = 2
+OM_LOSS_FLAG_BAD_CLASS = 4
+
+
+class LossCfg(ctypes.Structure):
+    """include/orienmask_hip.h: om_loss_cfg"""
+    _fields_ = [("num_scales", ctypes.c_int32),
+                ("grid_h", ctypes.c_int32 * OM_MAX_SCALES), ("grid_w", ctypes.c_int32 * OM_MAX_SCALES),
+                ("image_h", ctypes.c_int32), ("image_w", ctypes.c_int32),
+                ("anchors_of_scale", ctypes.c_int32 * OM_MAX_SCALES),
+                ("anchor_mask", (ctypes.c_int32 * 3) * OM_MAX_SCALES),
+                ("num_anchors_total", ctypes.c_int32),
+                ("anchor_w", ctypes.c_float * OM_MAX_ANCHORS), ("anchor_h", ctypes.c_float * OM_MAX_ANCHORS),
+                ("num_classes", ctypes.c_int32),
+                ("center_region", ctypes.c_float), ("valid_region", ctypes.c_float),
+                ("label_smooth", ctypes.c_float), ("label_on", ctypes.c_float),
+                ("obj_ignore_threshold", ctypes.c_float),
+                ("weight", (ctypes.c_float * OM_LOSS_TERMS) * OM_MAX_SCALES),
+                ("bbox_stride", (ctypes.c_int64 * 4) * OM_MAX_SCALES),
+                ("orien_stride", (ctypes.c_int64 * 3) * OM_MAX_SCALES)]
+
+
 OM_VIS_MAX_KEPT = 512
 OM_VIS_BATCH = 16
 
@@ -157,6 +187,10 @@ SIGNATURES = {
     "om_nms": (_i, [_vp, _i, _f, _vp, _vp, _vp, _sz, _vp]),
     "om_nms_ex": (_i, [_vp, _i, _f, _i, _vp, _vp, _vp, _sz, _vp]),
     "om_ref_math": (_i, [_vp, ctypes.c_longlong, _i, _i, _vp, _vp]),
+    "om_loss_workspace_bytes": (_sz, [ctypes.POINTER(LossCfg), _i, _i]),
+    "om_loss": (_i, [ctypes.POINTER(LossCfg), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
+    "om_loss_targets": (_i, [ctypes.POINTER(LossCfg), ctypes.POINTER(_vp), _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,
+                             _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -1,0 +1,369 @@
+"""The reference's validation loss and its counter on the HIP path.
+
+  OrienMaskYOLOMultiScaleLoss  same constructor, attributes and call contract as
+                               the reference's eval/orienmask_yolo_loss.py:259-325 with eval/base.py's aggregation
+  EvalCounter                  the counter semantics of the reference's eval/counter.py
+
+The values come from ``om_loss`` (csrc/loss.hip): four kernel launches for all scales and ONE device-to-host copy per call,
+against the reference's per-image, per-instance Python loops over full-image tensors and dozens of ``.item()`` calls.  The
+per-scale and cross-scale aggregation (eval/base.py:29-32,90-121) runs on the host in torch float32, the reference's own ops.
+
+Deliberate departures from the reference:
+  * no autograd: the values only (the validation epoch runs under no_grad).  A head that requires grad raises
+    NotImplementedError -- the loss's backward is out of scope;
+  * a non-finite pred_wh raises FloatingPointError (the reference prints and calls exit());
+  * loud limits: 1..3 scales of 1..3 anchors, at most 9 anchors, 2047 classes and OM_LOSS_MAX_GT (1024) GTs per image; the
+    orientation maps are exactly image / 4 per side;
+  * scales_weight=None means ones (the reference reads num_scales before setting it and fails).
+Duplicate positives (two GTs on one cell) follow torch-CPU's answer: box targets from the highest GT index, tcls the union of
+their classes (csrc/loss.hip).
+"""
+import ctypes
+
+import torch
+
+from . import lib as _lib
+
+
+def _pair(v):
+    return (int(v), int(v)) if isinstance(v, int) else (int(v[0]), int(v[1]))
+
+
+class EvalCounter:
+    """Sums of values and item counts per key, for one stage (``counter`` / ``items``) and for the epoch (``*_epoch``).
+
+    ``update(key, value)`` adds a plain value as one item, a ``(sum, count)`` pair as ``count`` items.  ``reset`` folds the
+    stage into the epoch; ``average`` is the stage mean and ``average_epoch`` folds the stage in and returns the epoch mean;
+    both return -1 when there are no items."""
+
+    def __init__(self):
+        self.keys = []
+        self.items = {}
+        self.counter = {}
+        self.items_epoch = {}
+        self.counter_epoch = {}
+
+    def update(self, key, value):
+        if isinstance(value, (tuple, dict)):
+            value, item = value
+        else:
+            item = 1
+        if key not in self.items:
+            self.keys.append(key)
+            self.items[key], self.counter[key] = item, value
+            self.items_epoch[key], self.counter_epoch[key] = 0, 0.
+            return
+        self.items[key] += item
+        self.counter[key] += value
+
+    def _fold(self, key):
+        self.items_epoch[key] += self.items[key]
+        self.counter_epoch[key] += self.counter[key]
+        self.items[key], self.counter[key] = 0, 0.
+
+    def reset(self):
+        for key in self.keys:
+            self._fold(key)
+
+    def reset_epoch(self):
+        for key in self.keys:
+            self.items[key], self.counter[key] = 0, 0.
+            self.items_epoch[key], self.counter_epoch[key] = 0, 0.
+
+    @staticmethod
+    def _mean(total, n):
+        try:
+            return total / n
+        except ZeroDivisionError:
+            return -1
+
+    def average(self, key):
+        return self._mean(self.counter[key], self.items[key])
+
+    def average_epoch(self, key):
+        self._fold(key)
+        return self._mean(self.counter_epoch[key], self.items_epoch[key])
+
+    def save(self, filename):
+        torch.save({"items": self.items, "counter": self.counter}, filename)
+
+    def save_epoch(self, filename):
+        torch.save({"items_epoch": self.items_epoch, "counter_epoch": self.counter_epoch}, filename)
+
+    def merge(self, counter_dict):
+        for key in self.keys:
+            self.items[key] += counter_dict["items"][key]
+            self.counter[key] += counter_dict["counter"][key]
+
+    def merge_epoch(self, counter_dict):
+        for key in self.keys:
+            self.items_epoch[key] += counter_dict["items_epoch"][key]
+            self.counter_epoch[key] += counter_dict["counter_epoch"][key]
+
+
+class OrienMaskYOLOMultiScaleLoss:
+    def __init__(self, grid_size, image_size, anchors, anchor_mask, num_classes,
+                 loss_id=("loss_xy", "loss_wh", "loss_obj", "loss_noobj",
+                          "loss_cls", "loss_orien_pos", "loss_orien_neg"),
+                 loss_sum_id="loss_sum", scales_id=("S32", "S16", "S08"),
+                 metric_id=("cls_conf", "obj_pos", "obj_neg", "avg_iou",
+                            "recall50", "recall75", "orien_pos_acc", "orien_neg_acc"),
+                 center_region=0.6, valid_region=0.7, label_smooth=False,
+                 obj_ignore_threshold=0.5, weight=None, scales_weight=None):
+        assert len(grid_size) == len(anchor_mask) == len(scales_id)
+        self.grid_size = grid_size
+        self.image_size = image_size
+        self.anchors = anchors
+        self.anchor_mask = anchor_mask
+        self.num_classes = num_classes
+        self.center_region = center_region
+        self.valid_region = valid_region
+        self.label_smooth = label_smooth
+        self.obj_ignore_threshold = obj_ignore_threshold
+        self.weight = weight
+        if len(loss_id) != _lib.OM_LOSS_TERMS or len(metric_id) != _lib.OM_LOSS_METRICS:
+            raise ValueError("the loss has %d terms and %d metrics" % (_lib.OM_LOSS_TERMS, _lib.OM_LOSS_METRICS))
+        # eval/base.py:66-98
+        self.num_scales = len(scales_id)
+        self.loss_suffix = list(loss_id) + [loss_sum_id]
+        self.metric_suffix = list(metric_id)
+        self.scales_prefix = list(scales_id)
+        self.loss_sum_id = loss_sum_id
+        self.loss_id, self.metric_id = [], []
+        self.scales_loss_id, self.scales_loss_sum_id, self.scales_metric_id = [], [], []
+        self.scales_weight = torch.tensor(scales_weight).float() if scales_weight is not None else torch.ones(self.num_scales)
+        for sid in scales_id:
+            sl = [sid + "_" + k for k in loss_id]
+            self.loss_id += sl + [sid + "_" + loss_sum_id]
+            self.metric_id += [sid + "_" + k for k in metric_id]
+            self.scales_loss_id.append(sl)
+            self.scales_loss_sum_id.append(sid + "_" + loss_sum_id)
+            self.scales_metric_id.append([sid + "_" + k for k in metric_id])
+        self.cross_scale_loss_id = ["cross_scale_" + k for k in self.loss_suffix]
+        self.loss_id += self.cross_scale_loss_id
+        self.cross_scale_metric_id = ["cross_scale_" + k for k in self.metric_suffix]
+        self.metric_id += self.cross_scale_metric_id
+        # per-scale item weights (orienmask_yolo_loss.py:311-315, base.py:24-25): float32(scales_weight[i] * weight[j]) or ones
+        self.scale_item_weight = [torch.tensor([self.scales_weight[i] * w for w in weight]).float() if weight is not None
+                                  else torch.ones(len(loss_id)) for i in range(self.num_scales)]
+        self._check_limits()
+        self._ws = None
+
+    def _check_limits(self):
+        S = self.num_scales
+        self.grids = [_pair(g) for g in self.grid_size]
+        self.image_h, self.image_w = _pair(self.image_size)
+        nA = [len(m) for m in self.anchor_mask]
+        if not 1 <= S <= _lib.OM_MAX_SCALES:
+            raise ValueError("the HIP loss holds 1..%d scales, got %d" % (_lib.OM_MAX_SCALES, S))
+        if any(not 1 <= n <= 3 for n in nA):
+            raise ValueError("the HIP loss holds 1..3 anchors per scale, got %s" % (nA,))
+        if not 1 <= len(self.anchors) <= _lib.OM_MAX_ANCHORS or any(not 0 <= a < len(self.anchors) for m in self.anchor_mask for a in m):
+            raise ValueError("at most %d anchors, anchor_mask entries index them" % _lib.OM_MAX_ANCHORS)
+        if not 1 <= int(self.num_classes) <= _lib.OM_LOSS_MAX_CLASSES:
+            raise ValueError("the HIP loss holds 1..%d classes, got %d" % (_lib.OM_LOSS_MAX_CLASSES, self.num_classes))
+        if self.image_h % 4 or self.image_w % 4:
+            raise ValueError("image sides must be multiples of 4 (the orientation maps are image / 4), got %s" % (self.image_size,))
+
+    def cfg_struct(self, predict=None):
+        c = _lib.LossCfg()
+        c.num_scales = self.num_scales
+        for s, (gh, gw) in enumerate(self.grids):
+            c.grid_h[s], c.grid_w[s] = gh, gw
+            c.anchors_of_scale[s] = len(self.anchor_mask[s])
+            for a, k in enumerate(self.anchor_mask[s]):
+                c.anchor_mask[s][a] = int(k)
+            for j in range(_lib.OM_LOSS_TERMS):
+                c.weight[s][j] = float(self.scale_item_weight[s][j])
+        c.image_h, c.image_w = self.image_h, self.image_w
+        c.num_anchors_total = len(self.anchors)
+        for k, (w, h) in enumerate(self.anchors):
+            c.anchor_w[k], c.anchor_h[k] = float(w), float(h)
+        c.num_classes = int(self.num_classes)
+        c.center_region, c.valid_region = float(self.center_region), float(self.valid_region)
+        ls = 1.0 / max(int(self.num_classes), 40) if self.label_smooth else 0
+        c.label_smooth, c.label_on = float(ls), float(1 - ls)      # ctypes rounds the doubles to float32, as the tensor writes do
+        c.obj_ignore_threshold = float(self.obj_ignore_threshold)
+        if predict is not None:
+            for s, (bbox, orien) in enumerate(predict):
+                for i, v in enumerate(bbox.stride()):
+                    c.bbox_stride[s][i] = v
+                for i, v in enumerate(orien.stride()[:3]):
+                    c.orien_stride[s][i] = v
+        return c
+
+    # -- inputs: the heads are read in place through their strides
+    def _heads(self, predict):
+        if len(predict) != self.num_scales:
+            raise ValueError("predict has %d scales, the loss was built for %d" % (len(predict), self.num_scales))
+        out = []
+        for s, (bbox, orien) in enumerate(predict):
+            for t, name in ((bbox, "bbox head"), (orien, "orientation head")):
+                _lib.require_cuda_tensor(t, name, torch.float32)
+                if t.requires_grad:
+                    raise NotImplementedError("the HIP loss computes values only; its backward is out of scope (call it under "
+                                              "torch.no_grad() or on detached heads)")
+            nA = len(self.anchor_mask[s])
+            gh, gw = self.grids[s]
+            want = (nA * (5 + int(self.num_classes)), gh, gw)
+            if bbox.dim() != 4 or tuple(bbox.shape[1:]) != want:
+                raise ValueError("bbox head %d has shape %s, expected [B,%d,%d,%d]" % ((s, tuple(bbox.shape)) + want))
+            wo = (2 * nA, self.image_h // 4, self.image_w // 4)
+            if orien.dim() != 4 or tuple(orien.shape[1:]) != wo or orien.shape[0] != bbox.shape[0]:
+                raise ValueError("orientation head %d has shape %s, expected [B,%d,%d,%d]" % ((s, tuple(orien.shape)) + wo))
+            if orien.stride(3) != 1:
+                orien = orien.contiguous()
+            out.append((bbox, orien))
+        return out
+
+    def _targets(self, target, B, dev):
+        gt_bbox, gt_cls, gt_index, gt_mask = target[:4]
+        for t, name in ((gt_bbox, "gt_bbox"), (gt_cls, "gt_cls"), (gt_index, "gt_index"), (gt_mask, "gt_mask")):
+            _lib.require_cuda_tensor(t, name)
+            if t.device != dev:
+                raise ValueError("%s is on %s, the heads on %s" % (name, t.device, dev))
+        N = int(gt_bbox.shape[0])
+        if gt_bbox.dtype != torch.float32 or tuple(gt_bbox.shape) != (N, 4):
+            raise ValueError("gt_bbox must be float32 [N,4], got %s %s" % (gt_bbox.dtype, tuple(gt_bbox.shape)))
+        if gt_cls.dtype != torch.int64 or tuple(gt_cls.shape) != (N,):
+            raise ValueError("gt_cls must be int64 [N]")
+        if gt_index.dtype != torch.int64 or tuple(gt_index.shape) != (B + 1,):
+            raise ValueError("gt_index must be int64 [B+1] = [%d], got %s" % (B + 1, tuple(gt_index.shape)))
+        if tuple(gt_mask.shape) != (N, self.image_h, self.image_w) or gt_mask.dtype not in (torch.bool, torch.uint8):
+            raise ValueError("gt_mask must be bool [N,%d,%d], got %s %s" % (self.image_h, self.image_w, gt_mask.dtype,
+                                                                          tuple(gt_mask.shape)))
+        if N > B * _lib.OM_LOSS_MAX_GT:
+            raise ValueError("%d GTs for %d images: the HIP loss holds at most %d GTs per image" % (N, B, _lib.OM_LOSS_MAX_GT))
+        gt_mask = gt_mask.contiguous()
+        if gt_mask.dtype == torch.bool:
+            gt_mask = gt_mask.view(torch.uint8)
+        return gt_bbox.contiguous(), gt_cls.contiguous(), gt_index.contiguous(), gt_mask, N
+
+    def workspace_bytes(self, B, N):
+        n = _lib.load().om_loss_workspace_bytes(ctypes.byref(self.cfg_struct()), int(B), int(N))
+        if n == 0:
+            _lib.check(-1, "om_loss_workspace_bytes")
+        return n
+
+    def _workspace(self, nbytes, dev):
+        if self._ws is None or self._ws.device != dev or self._ws.numel() < nbytes:
+            self._ws = None
+            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        return self._ws
+
+    def prepare(self, predict, target):
+        """Check the inputs and bind everything om_loss reads and writes; returns a callable that enqueues om_loss on the current
+        stream (no host work but the C call itself) and returns the device result vector (OM_LOSS_RESULT_FLOATS floats)."""
+        heads = self._heads(predict)
+        B, dev = heads[0][0].shape[0], heads[0][0].device
+        gt_bbox, gt_cls, gt_index, gt_mask, N = self._targets(target, B, dev)
+        L = _lib.load()
+        cfg = self.cfg_struct(heads)
+        ws = self._workspace(self.workspace_bytes(B, N), dev)
+        result = torch.empty(_lib.OM_LOSS_RESULT_FLOATS, dtype=torch.float32, device=dev)
+        bb = (ctypes.c_void_p * 3)(*[h[0].data_ptr() for h in heads] + [None] * (3 - len(heads)))
+        oo = (ctypes.c_void_p * 3)(*[h[1].data_ptr() for h in heads] + [None] * (3 - len(heads)))
+        args = (ctypes.byref(cfg), bb, oo, B, ctypes.c_void_p(gt_bbox.data_ptr()), ctypes.c_void_p(gt_cls.data_ptr()),
+                ctypes.c_void_p(gt_index.data_ptr()), ctypes.c_void_p(gt_mask.data_ptr()), N, ctypes.c_void_p(result.data_ptr()),
+                ctypes.c_void_p(ws.data_ptr()), ws.numel())
+        keep = (cfg, heads, gt_bbox, gt_cls, gt_index, gt_mask, ws)        # alive as long as the callable
+
+        def run():
+            with torch.cuda.device(dev):
+                _lib.check(L.om_loss(*args, _lib.current_stream_ptr(dev)), "om_loss")
+            run.keep = keep
+            return result
+        return run
+
+    def launch(self, predict, target):
+        """Enqueue om_loss on the current stream; returns the device result vector (OM_LOSS_RESULT_FLOATS floats)."""
+        return self.prepare(predict, target)()
+
+    def __call__(self, predict, target, training=True):
+        return self.forward(predict, target, training)
+
+    def forward(self, predict, target, training=True):
+        """Returns (loss_sum: 0-dim tensor on the heads' device, loss_log: {key: float}, metric_log: {key: (num, count)}) with
+        eval/base.py:90-121's keys in its order; metric_log is empty when training is True (orienmask_yolo_loss.py:148)."""
+        result = self.launch(predict, target)
+        dev = result.device
+        host = result.cpu()                                  # the call's one device-to-host copy
+        flags = int(host[_lib.OM_LOSS_FLAG_OFF:].view(torch.int32)[0])
+        if flags & _lib.OM_LOSS_FLAG_NONFINITE_WH:
+            raise FloatingPointError("pred_wh not finite")
+        if flags & _lib.OM_LOSS_FLAG_TOO_MANY_GT:
+            raise ValueError("gt_index is not a prefix of the GTs or an image has more than %d GTs (the HIP loss's limit)"
+                             % _lib.OM_LOSS_MAX_GT)
+        if flags & _lib.OM_LOSS_FLAG_BAD_CLASS:
+            raise ValueError("a gt_cls value lies outside [0, %d)" % self.num_classes)
+        return self.aggregate(host, training, dev)
+
+    def aggregate(self, host, training=False, device=None):
+        """eval/base.py:27-40 (per scale) and :90-121 (across scales) on the host result vector, in torch float32."""
+        T, M, SF = _lib.OM_LOSS_TERMS, _lib.OM_LOSS_METRICS, _lib.OM_LOSS_SCALE_FLOATS
+        loss_log, metric_log, scale_sums = {}, {}, []
+        for s in range(self.num_scales):
+            r = host[s * SF:(s + 1) * SF]
+            loss_cat = r[:T].clone()
+            for key, v in zip(self.scales_loss_id[s], loss_cat):
+                loss_log[key] = v.item()
+            scale_sum = loss_cat.sum()
+            loss_log[self.scales_loss_sum_id[s]] = scale_sum.item()
+            scale_sums.append(scale_sum)
+            if training is not True:
+                m = r[T:].tolist()
+                for j, key in enumerate(self.scales_metric_id[s]):
+                    num = int(m[2 * j]) if j in (4, 5) else m[2 * j]          # recall50 / recall75 are integer sums
+                    metric_log[key] = (num, m[2 * j + 1])
+        loss_sum = (torch.stack(scale_sums) * self.scales_weight).sum()
+        loss_log[self.loss_sum_id] = loss_sum.item()
+        cross = torch.tensor([[loss_log[k] for k in self.scales_loss_id[s]] + [loss_log[self.scales_loss_sum_id[s]]]
+                              for s in range(self.num_scales)])
+        cross = (cross * self.scales_weight.unsqueeze(-1)).sum(dim=0)
+        for key, v in zip(self.cross_scale_loss_id, cross):
+            loss_log[key] = v.item()
+        if metric_log:
+            cm = torch.tensor([[metric_log[k] for k in self.scales_metric_id[s]] for s in range(self.num_scales)]).sum(dim=0)
+            for key, v in zip(self.cross_scale_metric_id, cm):
+                metric_log[key] = (v[0].item(), v[1].item())
+        if device is not None:
+            loss_sum = loss_sum.to(device, non_blocking=True)
+        return loss_sum, loss_log, metric_log
+
+    def targets(self, predict_bbox, target, scale):
+        """Test entry (om_loss_targets): scale `scale`'s built targets, as build_targets returns them
+        (orienmask_yolo_loss.py:249-264) plus the raw orien_mask (int32: -1 positive, k > 0 negative count, 0 neither)."""
+        if len(predict_bbox) != self.num_scales or not 0 <= scale < self.num_scales:
+            raise ValueError("%d bbox heads and scale %d for a %d-scale loss" % (len(predict_bbox), scale, self.num_scales))
+        for s, bbox in enumerate(predict_bbox):
+            _lib.require_cuda_tensor(bbox, "bbox head", torch.float32)
+            want = (len(self.anchor_mask[s]) * (5 + int(self.num_classes)),) + self.grids[s]
+            if bbox.dim() != 4 or tuple(bbox.shape[1:]) != want or bbox.shape[0] != predict_bbox[0].shape[0]:
+                raise ValueError("bbox head %d has shape %s, expected [B,%d,%d,%d]" % ((s, tuple(bbox.shape)) + want))
+        B, dev = predict_bbox[0].shape[0], predict_bbox[0].device
+        gt_bbox, gt_cls, gt_index, gt_mask, N = self._targets(target, B, dev)
+        nA = len(self.anchor_mask[scale])
+        gh, gw = self.grids[scale]
+        H, W, C = self.image_h, self.image_w, int(self.num_classes)
+        f = dict(device=dev, dtype=torch.float32)
+        out = dict(bbox_pos_mask=torch.empty(B, nA, gh, gw, **f), bbox_neg_mask=torch.empty(B, nA, gh, gw, **f),
+                   bbox_pos_scale=torch.empty(B, nA, gh, gw, **f), txy=torch.empty(B, nA, gh, gw, 2, **f),
+                   twh=torch.empty(B, nA, gh, gw, 2, **f), tiou=torch.empty(B, nA, gh, gw, **f),
+                   tcls=torch.empty(B, nA, gh, gw, C, **f),
+                   orien_mask=torch.empty(B, nA, H, W, dtype=torch.int32, device=dev), torien=torch.empty(B, nA, H, W, 2, **f))
+        cfg = self.cfg_struct()
+        for s, b in enumerate(predict_bbox):
+            for i, v in enumerate(b.stride()):
+                cfg.bbox_stride[s][i] = v
+        L = _lib.load()
+        ws = torch.empty(self.workspace_bytes(B, N) + 512, dtype=torch.uint8, device=dev)
+        bb = (ctypes.c_void_p * 3)(*[t.data_ptr() for t in predict_bbox] + [None] * (3 - len(predict_bbox)))
+        ptr = lambda k: ctypes.c_void_p(out[k].data_ptr())     # noqa: E731
+        with torch.cuda.device(dev):
+            rc = L.om_loss_targets(ctypes.byref(cfg), bb, B, ctypes.c_void_p(gt_bbox.data_ptr()), ctypes.c_void_p(gt_cls.data_ptr()),
+                                   ctypes.c_void_p(gt_index.data_ptr()), ctypes.c_void_p(gt_mask.data_ptr()), N, scale,
+                                   ptr("bbox_pos_mask"), ptr("bbox_neg_mask"), ptr("bbox_pos_scale"), ptr("txy"), ptr("twh"),
+                                   ptr("tiou"), ptr("tcls"), ptr("orien_mask"), ptr("torien"), ctypes.c_void_p(ws.data_ptr()),
+                                   ws.numel(), _lib.current_stream_ptr(dev))
+        _lib.check(rc, "om_loss_targets")
+        return out

@@ -406,3 +406,47 @@ def synth_heads(seed, batch, grid_sizes, num_anchors=3, num_classes=80, regime="
         out.append((torch.from_numpy(bbox.reshape(batch, num_anchors * per_anchor, nh, nw).copy()),
                     torch.from_numpy(orien.reshape(batch, num_anchors * 2, oh, ow).copy())))
     return tuple(out)
+
+
+def _fill_polygon(vx, vy, H, W):
+    """Even-odd fill of one polygon (float64 vertices, pixel units) sampled at pixel centres: bool [H, W]."""
+    ys = np.arange(H, dtype=np.float64)[:, None] + 0.5
+    xs = np.arange(W, dtype=np.float64)[None, :] + 0.5
+    inside = np.zeros((H, W), dtype=bool)
+    n = len(vx)
+    for i in range(n):
+        x0, y0, x1, y1 = vx[i], vy[i], vx[(i + 1) % n], vy[(i + 1) % n]
+        if y0 == y1:
+            continue
+        crosses = (ys >= min(y0, y1)) & (ys < max(y0, y1))
+        xi = x0 + (ys - y0) * (x1 - x0) / (y1 - y0)
+        inside ^= crosses & (xs < xi)
+    return inside
+
+
+def synth_targets(seed, batch, height, width, gts_per_image=7, num_classes=80, vertices=9):
+    """Seeded targets in the reference's collate format (the reference's data/collate.py:13-30: gt_bbox [N,4] normalised cx, cy, w, h
+    float32, gt_cls [N] int64, gt_index [B+1] int64, gt_mask [N,H,W] bool), as numpy arrays.
+
+    Every instance is a filled star-shaped polygon inside its box; `gts_per_image` is an int or a list (one count per image).
+    Box sizes span small to large so that every scale gets positives."""
+    rng = _rng(seed)
+    counts = [int(gts_per_image)] * batch if np.isscalar(gts_per_image) else [int(c) for c in gts_per_image]
+    boxes, classes, masks = [], [], []
+    for b in range(batch):
+        for _ in range(counts[b]):
+            w = float(np.exp(rng.uniform(np.log(8.0), np.log(0.8 * width))))
+            h = float(np.clip(w * np.exp(rng.normal(0.0, 0.4)), 6.0, 0.9 * height))
+            cx = float(rng.uniform(w / 4, width - w / 4))
+            cy = float(rng.uniform(h / 4, height - h / 4))
+            ang = np.sort(rng.uniform(0, 2 * np.pi, vertices))
+            rad = rng.uniform(0.45, 1.0, vertices)
+            vx = np.clip(cx + np.cos(ang) * rad * w / 2, 0, width)
+            vy = np.clip(cy + np.sin(ang) * rad * h / 2, 0, height)
+            boxes.append([cx / width, cy / height, w / width, h / height])
+            classes.append(int(rng.integers(num_classes)))
+            masks.append(_fill_polygon(vx, vy, height, width))
+    index = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    gt_bbox = np.asarray(boxes, dtype=np.float32).reshape(-1, 4)
+    gt_mask = np.asarray(masks, dtype=bool).reshape(-1, height, width)
+    return gt_bbox, np.asarray(classes, dtype=np.int64), index, gt_mask

@@ -215,3 +215,73 @@ def infer_loop(model, transform, postprocess, images, device, warmup=10, size_di
     if visualizer is not None:
         return results, pads, _timer.get_all_elapsed_time(), shows
     return results, pads, _timer.get_all_elapsed_time()
+
+
+class SyntheticLossLoader:
+    """SyntheticLoader with targets: yields (image[B,3,H,W], (gt_bbox, gt_cls, gt_index, gt_mask), batch_info) as the reference's
+    collate does (the reference's data/collate.py:13-30), with seeded boxes, classes and filled-polygon masks
+    (synth.synth_targets).  Everything is made once, on `device`."""
+
+    def __init__(self, n_images, batch_size, size=(544, 544), seed=0, gts_per_image=7, num_classes=80, device="cuda"):
+        from . import synth
+        self.batch_size = batch_size
+        self._batches = []
+        for s in range(0, n_images, batch_size):
+            n = min(batch_size, n_images - s)
+            img = torch.cat([synth.synth_image_batch(seed + s + k, 1, size[0], size[1]) for k in range(n)], 0)
+            gb, gc, gi, gm = synth.synth_targets(seed + 7919 + s, n, size[0], size[1], gts_per_image, num_classes)
+            target = tuple(torch.from_numpy(a).to(device) for a in (gb, gc, gi, gm))
+            info = [dict(id=s + k, height=size[0], width=size[1]) for k in range(n)]
+            self._batches.append((img.to(device), target, info))
+
+    def __len__(self):
+        return len(self._batches)
+
+    def __iter__(self):
+        return iter(self._batches)
+
+
+def _model_device(model):
+    for p in model.parameters():
+        return p.device
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def validate(model, loss, postprocess, loader, coco_metrics=None):
+    """Trainer._val_epoch (the reference's trainer/trainer.py:135-209) for ONE rank: forward, loss(training=False), and -- when a
+    cocoeval.COCOMetrics is given -- postprocess, to_coco_format / update_results and coco_eval.  The image and the targets
+    are moved to the device of the model's parameters, as _val_epoch moves them to the trainer's.  Returns its val_log:
+    val_loss, val_<loss_id>, val_<metric_id> (EvalCounter epoch averages) and val_<coco key>.  Merging the counters and COCO
+    results of several ranks (the reference's _temp_counter_*.pth / _temp_coco_eval_*.json exchange) is not done here; the
+    tensorboard writes are left out.  Without coco_metrics the postprocess is not run (its output would go nowhere)."""
+    from .loss import EvalCounter
+    if coco_metrics is not None:
+        coco_metrics.reset()
+    counter = EvalCounter()
+    dev = _model_device(model)
+    with torch.no_grad():
+        for sample in loader:
+            # trainer.py:152-154: the image and every label tensor to the model's device (collate yields CPU tensors)
+            image = sample[0].to(dev)
+            target = [anno.to(dev) for anno in sample[1]]
+            batch_info = sample[2]
+            predict = model(image)
+            loss_v, loss_log, metric_log = loss(predict, target, training=False)
+            if coco_metrics is not None:
+                detections = postprocess(predict)
+                coco_metrics.update_results(coco_metrics.to_coco_format(batch_info, detections))
+            counter.update("loss", loss_v.item())
+            for key, value in loss_log.items():
+                counter.update(key, value)
+            for key, value in metric_log.items():
+                counter.update(key, value)
+    val_log = {"val_loss": counter.average_epoch("loss")}
+    for key in loss.loss_id:
+        val_log["val_%s" % key] = counter.average_epoch(key)
+    for key in loss.metric_id:
+        val_log["val_%s" % key] = counter.average_epoch(key)
+    if coco_metrics is not None:
+        for key, value in coco_metrics.coco_eval().items():
+            val_log["val_%s" % key] = value
+    counter.reset_epoch()
+    return val_log
