@@ -450,13 +450,35 @@ def bilinear_x4_restated(plane):
 # --------------------------------------------------------------------------------------
 
 
+class _multi_thread:
+    """torch-CPU's bilinear F.interpolate picks its kernel by the output size (the channels-last loop when height + width <= 128,
+    the generic one above) -- except on ONE thread with exactly 3 channels, where it takes the channels-last loop at every size,
+    whose float32 sums round differently.  The reference runs torch multi-threaded; the oracle evaluates the resizes the kernels
+    restate (preprocess.hip, coco_format.hip, visualize.hip) on at least two threads, so that its bits do not depend on the
+    machine's thread setting."""
+
+    def __enter__(self):
+        self.n = torch.get_num_threads()
+        if self.n < 2:
+            torch.set_num_threads(2)
+
+    def __exit__(self, *a):
+        torch.set_num_threads(self.n)
+
+
+def interpolate_bilinear(x, size):
+    """F.interpolate(x, size, mode='bilinear', align_corners=False) as the reference evaluates it (see _multi_thread)."""
+    with _multi_thread():
+        return F.interpolate(x, size=tuple(size), mode="bilinear", align_corners=False)
+
+
 def fast_coco_transform(image_nhwc, size=None, mean=(0, 0, 0), std=(255, 255, 255)):
     """FastCOCOTransform.__call__ with pipeline [Resize(size), Normalize(mean, std)]:
     /root/reference/data/transform.py:455-461 (permute + contiguous), :470-473 (F.interpolate bilinear,
     align_corners=False), :504-508 (sub_ mean, div_ std)."""
     x = image_nhwc.detach().float().cpu().permute(0, 3, 1, 2).contiguous()
     if size is not None:
-        x = F.interpolate(x, size=tuple(size), mode="bilinear", align_corners=False)
+        x = interpolate_bilinear(x, size)
     m = torch.tensor(mean, dtype=torch.float32)
     s = torch.tensor(std, dtype=torch.float32)
     x.sub_(m[:, None, None]).div_(s[:, None, None])
@@ -519,7 +541,7 @@ def recover_shape_segm(mask, sample_info):
     if sample_info.get("vflip", False):
         mask = torch.flip(mask, dims=(1,))
     oh, ow = sample_info["height"], sample_info["width"]
-    mask = F.interpolate(mask.unsqueeze(0).float(), size=(oh, ow), mode="bilinear", align_corners=False)
+    mask = interpolate_bilinear(mask.unsqueeze(0).float(), (oh, ow))
     return mask.squeeze(0).round().to(torch.uint8)
 
 

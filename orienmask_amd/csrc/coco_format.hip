@@ -78,6 +78,7 @@ struct RleParams {
     int K, H, W;
     int crop_top, crop_left, ch, cw;     // cropped region of the network-resolution mask
     int hflip, vflip, oh, ow, max_runs;
+    int small_out;           // oh + ow <= BILINEAR_SMALL_OUT: torch's small-output blend (bilinear.h)
     float scale_h, scale_w;
 };
 
@@ -101,7 +102,7 @@ __global__ __launch_bounds__(RLE_THREADS) void recover_rle_kernel(const RleParam
         if (q.hflip) { x0 = q.cw - 1 - x0; x1 = q.cw - 1 - x1; }
         const uint8_t* r0 = m + (size_t)(q.crop_top + y0) * q.W + q.crop_left;
         const uint8_t* r1 = m + (size_t)(q.crop_top + y1) * q.W + q.crop_left;
-        const float v = bilinear_blend((float)r0[x0], (float)r0[x1], (float)r1[x0], (float)r1[x1], wx0, wx1, wy0, wy1);
+        const float v = bilinear_value(q.small_out, (float)r0[x0], (float)r0[x1], (float)r1[x0], (float)r1[x1], wx0, wx1, wy0, wy1);
         return (int)rintf(v);                          // torch.round: half to even
     };
 
@@ -330,7 +331,7 @@ __global__ __launch_bounds__(RLE_THREADS) void recover_rle_lds_kernel(const RleB
             }
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                const float v = bilinear_blend((float)a00[j], (float)a01[j], (float)a10[j], (float)a11[j], wx0, wx1,
+                const float v = bilinear_value(q.small_out, (float)a00[j], (float)a01[j], (float)a10[j], (float)a11[j], wx0, wx1,
                                                __int_as_float(t[j].z), __int_as_float(t[j].w));
                 const int bit = (int)rintf(v);                      // torch.round: half to even
                 word |= (i0 + j < ylim ? (uint32_t)(bit & 1) : 0u) << ((i0 + j) & 31);
@@ -431,6 +432,7 @@ static int fill_rle_params(om::RleParams& q, const uint8_t* mask, int K, int H, 
     q.K = K; q.H = H; q.W = W;
     q.crop_top = crop_top; q.crop_left = crop_left; q.ch = H - crop_top - crop_down; q.cw = W - crop_left - crop_right;
     q.hflip = hflip; q.vflip = vflip; q.oh = orig_h; q.ow = orig_w; q.max_runs = max_runs;
+    q.small_out = orig_h + orig_w <= om::BILINEAR_SMALL_OUT ? 1 : 0;
     q.scale_h = (float)q.ch / (float)orig_h;
     q.scale_w = (float)q.cw / (float)orig_w;
     return OM_OK;

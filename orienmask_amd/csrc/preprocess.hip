@@ -9,7 +9,15 @@
 // fmaf(row(y0), wy0, row(y1) * wy1) with row(y) = fmaf(v[x0], wx0, v[x1] * wx1) -- the placement torch's
 // CPU kernel compiles to (found by search, see oracle/orienmask_ref.py); this file is built with
 // -ffp-contract=off so nothing else fuses.  Division by std is IEEE.
+//
+// torch-CPU takes another kernel when the resized height + width is at most 128 (its channels-last loop, which it prefers for
+// small outputs): the four weights h_i * w_j are rounded first and the taps summed left to right,
+// fmaf(v11, w11, fmaf(v10, w10, fmaf(v00, w00, v01 * w01))).  A 7 x 7 image resized to 5 x 9 showed the difference
+// (tests/test_geometry_sweep.py); preprocess_kernel follows both.  torch also takes that loop at EVERY size when it runs on one
+// thread and the image has 3 channels: the kernel follows torch multi-threaded, as the reference runs and as the oracle
+// (oracle/orienmask_ref.py) evaluates it.
 #include "om_common.h"
+#include "bilinear.h"
 
 namespace om {
 
@@ -17,6 +25,7 @@ struct PreParams {
     const float* in;     // [N,h,w,3]
     float* out;          // [N,3,out_h,out_w]
     int N, h, w, rh, rw, out_h, out_w, pad_top, pad_left;
+    int small_out;       // rh + rw <= BILINEAR_SMALL_OUT: torch-CPU blends with another kernel (bilinear.h)
     float mean[3], stdv[3], pad_value, scale_h, scale_w;
 };
 
@@ -54,6 +63,15 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const PreParams p) {
     const float* p01 = img + ((size_t)y0 * p.w + x1) * 3;
     const float* p10 = img + ((size_t)y1 * p.w + x0) * 3;
     const float* p11 = img + ((size_t)y1 * p.w + x1) * 3;
+    if (p.small_out) {
+        // torch-CPU's kernel for outputs with height + width <= 128: four weights h_i * w_j, summed left to right
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float v = bilinear_blend_small(p00[c], p01[c], p10[c], p11[c], wx0, wx1, wy0, wy1);
+            o[c * plane] = (v - p.mean[c]) / p.stdv[c];
+        }
+        return;
+    }
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const float top = fmaf(p00[c], wx0, p01[c] * wx1);
@@ -97,6 +115,7 @@ int om_preprocess(const float* in_nhwc, int N, int h, int w, int resize_h, int r
     for (int c = 0; c < 3; ++c) { p.mean[c] = mean3[c]; p.stdv[c] = std3[c]; }
     p.scale_h = (float)h / (float)resize_h;      // area_pixel_compute_scale with size= given
     p.scale_w = (float)w / (float)resize_w;
+    p.small_out = resize_h + resize_w <= om::BILINEAR_SMALL_OUT ? 1 : 0;
     const long long total = (long long)N * out_h * out_w;
     hipLaunchKernelGGL(om::preprocess_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), p);

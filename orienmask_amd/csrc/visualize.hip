@@ -275,6 +275,7 @@ __global__ __launch_bounds__(VIS_THREADS) void vis_composite_kernel(const VisBat
             c1[e] = j1;
         }
         const float alpha = q.alpha;
+        const bool small = q.h + q.w <= BILINEAR_SMALL_OUT;
         double P[VIS_PIX_PER_THREAD];
         float first[VIS_PIX_PER_THREAD][3], sum[VIS_PIX_PER_THREAD][3];
         for (int e = 0; e < VIS_PIX_PER_THREAD; ++e) {
@@ -294,7 +295,7 @@ __global__ __launch_bounds__(VIS_THREADS) void vis_composite_kernel(const VisBat
             for (int e = 0; e < VIS_PIX_PER_THREAD; ++e) {
                 v[e] = 0.f;
                 if (py[e] >= ext.x && py[e] <= ext.y && px[e] >= ext.z && px[e] <= ext.w)
-                    v[e] = bilinear_blend((float)m[r0[e] + c0[e]], (float)m[r0[e] + c1[e]], (float)m[r1[e] + c0[e]],
+                    v[e] = bilinear_value(small, (float)m[r0[e] + c0[e]], (float)m[r0[e] + c1[e]], (float)m[r1[e] + c0[e]],
                                           (float)m[r1[e] + c1[e]], wx0[e], wx1[e], wy0[e], wy1[e]);
             }
 #pragma unroll

@@ -144,13 +144,17 @@ class InferenceVisualizer:
         self._launch(items, outs, draw_boxes=False)
         return outs
 
-    def _composite_float(self, detections, image, pad_info):
-        """Test entry: (uint8 composite, float32 composite before round()) of one image, no boxes drawn."""
+    def _composite_float(self, detections, image, pad_info, with_areas=False):
+        """Test entry: (uint8 composite, float32 composite before round()) of one image, no boxes drawn; with_areas: also the
+        kept masks' resized areas the composite sorted by (float64, kept order)."""
         item = self._prepare(detections, image, pad_info)
         out = torch.empty(image.shape, dtype=torch.uint8, device=image.device)
         out_f = torch.empty(image.shape, dtype=torch.float32, device=image.device)
-        self._launch([item], [out], draw_boxes=False, out_floats=[out_f])
-        return out, out_f
+        ws = self._launch([item], [out], draw_boxes=False, out_floats=[out_f])
+        if not with_areas:
+            return out, out_f
+        n = item["n"] if item["mask"] is not None else 0
+        return out, out_f, ws[:32 * n].view(torch.float64).view(n, 4)[:, 0]    # VisMaskStat: 32 bytes, the area first
 
     # ---- helpers ------------------------------------------------------------------------------------------------------
     def _cv2(self):
@@ -231,7 +235,8 @@ class InferenceVisualizer:
         ws = torch.empty(int(L.om_visualize_workspace_bytes(imgs, len(items))), dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):
             _lib.check(L.om_visualize(imgs, len(items), ctypes_ptr(ws), ws.numel(), _lib.current_stream_ptr(dev)), "om_visualize")
-        return alive
+        del alive
+        return ws
 
     def _plot_one_box(self, cv2, bbox, text, image, color):
         """utils/visualizer.py:84-93, call for call."""
