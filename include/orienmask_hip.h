@@ -569,7 +569,8 @@ int om_nms(const float* dets, int n, float thresh, int64_t* keep, int32_t* n_kee
 int om_nms_ex(const float* dets, int n, float thresh, int semantics, int64_t* keep, int32_t* n_keep, void* workspace,
               size_t ws_bytes, om_stream stream);
 
-/* ---- Loss of the validation epoch: OrienMaskYOLOMultiScaleLoss (eval/orienmask_yolo_loss.py, eval/base.py), values only.
+/* ---- Loss of the validation epoch: OrienMaskYOLOMultiScaleLoss (eval/orienmask_yolo_loss.py, eval/base.py), values
+ *      (om_loss) and, for training, the gradient with respect to the heads (om_loss_backward, below).
  *
  * om_loss_cfg: the loss's constants.  Per scale s < num_scales: grid_h/grid_w, anchors_of_scale[s] (1..3) anchors
  * anchor_mask[s][.] into anchor_w/anchor_h (num_anchors_total <= 9), weight[s][0..6] = the scale's per-item weight
@@ -626,6 +627,21 @@ int om_loss_targets(const om_loss_cfg* cfg, const float* const* bbox, int B, con
                     const int64_t* gt_index, const uint8_t* gt_mask, int N, int scale, float* bbox_pos, float* bbox_neg,
                     float* pos_scale, float* txy, float* twh, float* tiou, float* tcls, int32_t* orien_mask, float* torien,
                     void* workspace, size_t ws_bytes, om_stream stream);
+
+/* ---- The loss's backward: d(out) / d(pred_bbox) and d(out) / d(pred_orien) for every scale, following the reference's autograd
+ *      chain (BCELoss / sigmoid / MSELoss / SmoothL1Loss backward and the adjoint of the x4 bilinear up-sample, in torch-CPU's
+ *      float32 operation order), multiplied by grad_out = d(out) / d(loss_sum), a device float read by the kernels (no host
+ *      synchronisation).  scales_weight: host array of num_scales floats, the multi-scale weights (eval/base.py:119); the
+ *      per-item weights come from cfg->weight, which already holds them once more, as the reference's chain does.
+ *
+ *      Call it after om_loss on the same cfg, heads and targets, with that call's `result` and `workspace` untouched since: it reads
+ *      the match records from the workspace and the bbox_pos / orientation pos / neg counts from the result vector.  grad_bbox[s]
+ *      and grad_orien[s] are written through the SAME strides as the heads (cfg->bbox_stride / orien_stride), every element exactly
+ *      once, zeros included; the result is bit-identical from call to call.  Two launches; no atomics, no allocation. */
+int om_loss_backward(const om_loss_cfg* cfg, const float* const* bbox, const float* const* orien, int B, const int64_t* gt_index,
+                     const uint8_t* gt_mask, int N, const float* result, const void* workspace, size_t ws_bytes,
+                     const float* grad_out, const float* scales_weight, float* const* grad_bbox, float* const* grad_orien,
+                     om_stream stream);
 
 /* ---- Several batches in flight.  Every entry point only enqueues kernels on the caller's stream and keeps no per-call state in
  *      the model handle (profiling apart): om_forward / om_forward_f16 / om_postprocess may be issued for different batches

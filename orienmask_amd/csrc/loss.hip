@@ -15,6 +15,13 @@
 //   loss_reduce_kernel  one workgroup per scale: the workgroup partials (doubles) summed in a fixed order, the reference's
 //                       normalisations in float32, the per-item weights.
 //
+// The backward (om_loss_backward, two launches after om_loss on the same inputs):
+//   loss_box_grad_kernel    one lane per prediction cell: the forward's decode / ignore / winner again, then the gradient of
+//                           all 5 + C channels of the cell (zeros included) along the BCE / sigmoid / MSE chain.
+//   loss_orien_grad_kernel  one workgroup per (scale, image, anchor, 16 x 16 quarter-resolution tile): targets and
+//                           d loss / d(up-sampled head) of the tile plus a 2-pixel halo into LDS, then each quarter pixel gathers
+//                           the up-sample's adjoint in a fixed order.  No atomics, no full-resolution scratch in memory.
+//
 // Duplicate positives (two GTs of one image on the same (a, gy, gx)): the reference's index_put_ writes are last-writer-wins
 // on torch-CPU and unspecified on CUDA.  Here: txy, twh, bbox_pos_scale and tiou come from the HIGHEST GT index on the cell, tcls is
 // the UNION of their classes (different class indices are different elements, so every write survives) -- the CPU answer.
@@ -563,6 +570,288 @@ static int loss_run(const om_loss_cfg* cfg, const float* const* bbox, const floa
     return OM_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// backward: d(g * loss_sum) / d(pred_bbox, pred_orien) along the reference's autograd chain, in torch-CPU's float32 order
+// (probed on torch 2.10: binary_cross_entropy_backward, sigmoid_backward, mse_loss_backward, smooth_l1_loss_backward and
+// upsample_bilinear2d_backward bit for bit).  Runs after om_loss on the same inputs: the LossGt records come from its workspace,
+// the counts (bbox_pos, orientation pos / neg) from its result vector.  Every gradient element is written exactly once.
+// ------------------------------------------------------------------------------------------------
+constexpr int LOSS_GQ = 16;                     // quarter-resolution tile side of loss_orien_grad_kernel
+constexpr int LOSS_GR = 4 * LOSS_GQ + 4;        // full-resolution rows / columns its adjoint reads (2 above, 2 below)
+
+struct LossGradParams {
+    om_loss_cfg cfg;
+    const float* bbox[OM_MAX_SCALES];
+    const float* orien[OM_MAX_SCALES];
+    float* gbbox[OM_MAX_SCALES];                // written through the heads' strides
+    float* gorien[OM_MAX_SCALES];
+    float sw[OM_MAX_SCALES];                    // scales_weight
+    int B, N;
+    const int64_t* gt_index;
+    const uint8_t* gt_mask;
+    const LossGt* gts;
+    const float* result;
+    const float* gout;                          // d(out) / d(loss_sum), device scalar
+    int qtiles, qtiles_x;
+};
+
+__device__ __forceinline__ void image_range(const LossGradParams& p, int b, int& g0, int& n) {
+    long long lo = p.gt_index[b], hi = p.gt_index[b + 1];
+    lo = lo < 0 ? 0 : lo > p.N ? p.N : lo;
+    hi = hi < lo ? lo : hi > p.N ? p.N : hi;
+    g0 = (int)lo;
+    n = (int)(hi - lo);
+    if (n > OM_LOSS_MAX_GT) n = OM_LOSS_MAX_GT;
+}
+
+// binary_cross_entropy_backward: grad * (p - t) / max((1 - p) * p, EPSILON); sigmoid_backward: grad * (1 - p) * p
+__device__ __forceinline__ float bce_grad(float d, float pr, float t) { return (d * (pr - t)) / maxf_((1.0f - pr) * pr, 1e-12f); }
+__device__ __forceinline__ float sigmoid_grad(float d, float pr) { return (d * (1.0f - pr)) * pr; }
+
+// upstream gradient of term j of scale s: (g * scales_weight[s]) * weight[s][j]  (base.py:119 then base.py:32)
+__device__ __forceinline__ float term_grad(const LossGradParams& p, int s, int j) {
+    return (p.gout[0] * p.sw[s]) * p.cfg.weight[s][j];
+}
+
+// box: one lane per prediction cell (b, a, gy, gx), all 5 + C channels of the cell.  grid (box_blocks, B, scales)
+__global__ __launch_bounds__(LOSS_BOX_THREADS) void loss_box_grad_kernel(const LossGradParams p) {
+    __shared__ float4 s_box[OM_LOSS_MAX_GT];
+    __shared__ int s_key[OM_LOSS_MAX_GT];
+    __shared__ int s_cls[OM_LOSS_MAX_GT];
+    const int s = blockIdx.z, b = blockIdx.y;
+    const om_loss_cfg& c = p.cfg;
+    if (s >= c.num_scales) return;
+    const int nH = c.grid_h[s], nW = c.grid_w[s], A = c.anchors_of_scale[s], C = c.num_classes;
+    const int ncell = A * nH * nW;
+    if ((int)blockIdx.x * LOSS_BOX_THREADS >= ncell) return;
+    int g0, ng;
+    image_range(p, b, g0, ng);
+    const LossGt* gts = p.gts + (size_t)s * p.N + g0;
+    for (int j = threadIdx.x; j < ng; j += LOSS_BOX_THREADS) {
+        const LossGt& g = gts[j];
+        s_box[j] = make_float4(g.gx, g.gy, g.gw, g.gh);
+        s_key[j] = g.key;
+        s_cls[j] = g.cls;
+    }
+    __syncthreads();
+    const int cell = blockIdx.x * LOSS_BOX_THREADS + threadIdx.x;
+    if (cell >= ncell) return;
+    const int a = cell / (nH * nW), rem = cell - a * (nH * nW);
+    const int gy = rem / nW, gx = rem - gy * nW;
+    const int64_t* st = c.bbox_stride[s];
+    const int64_t off = b * st[0] + (int64_t)a * (5 + C) * st[1] + gy * st[2] + gx * st[3];
+    const float* hp = p.bbox[s] + off;
+    float* gp = p.gbbox[s] + off;
+    // the forward's decode, ignore mask and winner (loss_box_kernel)
+    const float vx = hp[0], vy = hp[st[1]], vw = hp[2 * st[1]], vh = hp[3 * st[1]], vo = hp[4 * st[1]];
+    const int ag = c.anchor_mask[s][a];
+    const float sw = (float)c.image_w / (float)nW, sh = (float)c.image_h / (float)nH;
+    const float sx = sigmoid_scalar_ref(vx), sy = sigmoid_scalar_ref(vy), so = sigmoid_scalar_ref(vo);
+    const float x = sx + (float)gx, y = sy + (float)gy;
+    const float w = expf_cr(vw) * (c.anchor_w[ag] / sw), h = expf_cr(vh) * (c.anchor_h[ag] / sh);
+    const float b1x1 = x - w / 2.0f, b1y1 = y - h / 2.0f, b1x2 = x + w / 2.0f, b1y2 = y + h / 2.0f;
+    const float area1 = (b1x2 - b1x1) * (b1y2 - b1y1);
+    bool ignore = false;
+    int win = -1, nmatch = 0;
+    int cls4[4];
+    for (int j = 0; j < ng; ++j) {
+        const float4 g = s_box[j];
+        const float b2x1 = g.x - g.z / 2.0f, b2y1 = g.y - g.w / 2.0f, b2x2 = g.x + g.z / 2.0f, b2y2 = g.y + g.w / 2.0f;
+        float dx = minf_(b1x2, b2x2) - maxf_(b1x1, b2x1);
+        float dy = minf_(b1y2, b2y2) - maxf_(b1y1, b2y1);
+        dx = dx < 0.0f ? 0.0f : dx;
+        dy = dy < 0.0f ? 0.0f : dy;
+        const float inter = dx * dy;
+        const float area2 = (b2x2 - b2x1) * (b2y2 - b2y1);
+        const float iou = inter / ((area1 + area2) - inter);
+        ignore = ignore || iou > c.obj_ignore_threshold;
+        if (s_key[j] == cell) {
+            win = j;
+            if (nmatch < 4) cls4[nmatch] = s_cls[j];
+            ++nmatch;
+        }
+    }
+    const bool pos = win >= 0, neg = !pos && !ignore;
+    const float nB = (float)p.B;
+    const int64_t cs = st[1];
+    // obj / noobj share loss_obj_all: its gradient is G2 / nB * pos_mask + G3 / nB * neg_mask (the ignored cells get neither)
+    const float d_obj = pos ? term_grad(p, s, 2) / nB : neg ? term_grad(p, s, 3) / nB : 0.0f;
+    const float g_obj = sigmoid_grad(bce_grad(d_obj, so, pos ? 1.0f : 0.0f), so);
+    if (!pos) {
+        gp[0] = 0.0f;
+        gp[cs] = 0.0f;
+        gp[2 * cs] = 0.0f;
+        gp[3 * cs] = 0.0f;
+        gp[4 * cs] = g_obj;
+        for (int k = 0; k < C; ++k) gp[(5 + k) * cs] = 0.0f;
+        return;
+    }
+    const LossGt& gw_ = gts[win];
+    const float ps = gw_.pscale;
+    const float d_xy = (term_grad(p, s, 0) / nB) * ps;                    // (bce * pos_scale).sum() / nB
+    const float d_wh = ((term_grad(p, s, 1) / nB) / 2.0f) * ps;           // (mse * pos_scale).sum() / 2 / nB
+    gp[0] = sigmoid_grad(bce_grad(d_xy, sx, gw_.tx), sx);
+    gp[cs] = sigmoid_grad(bce_grad(d_xy, sy, gw_.ty), sy);
+    gp[2 * cs] = (2.0f * (vw - gw_.tw)) * d_wh;                          // mse_loss_backward: 2 * (x - t) * grad
+    gp[3 * cs] = (2.0f * (vh - gw_.th)) * d_wh;
+    gp[4 * cs] = g_obj;
+    const float d_cls = term_grad(p, s, 4) / nB;                         // (bce * pos_mask).sum() / nB
+    const float* cp = hp + 5 * cs;
+    for (int k = 0; k < C; ++k) {
+        bool on = false;
+        if (nmatch <= 4) {
+            for (int m = 0; m < nmatch; ++m) on = on || cls4[m] == k;
+        } else {
+            for (int j = 0; j < ng; ++j) on = on || (s_key[j] == cell && s_cls[j] == k);
+        }
+        const float t = on ? c.label_on : c.label_smooth;
+        const float sc = sigmoid_class_ref(cp[k * cs], k, C);
+        gp[(5 + k) * cs] = sigmoid_grad(bce_grad(d_cls, sc, t), sc);
+    }
+}
+
+// orientation: one workgroup per (scale, image, anchor, LOSS_GQ^2 quarter-resolution tile).  The full-resolution targets and
+// d loss / d(up-sampled head) of the tile and its halo go to LDS (the forward's culled, collate-order walk); each quarter pixel
+// then gathers the adjoint of the x4 bilinear up-sample from its <= 8 x 8 contributors in upsample_bilinear2d_backward's order
+// (output pixels row-major, taps 00 01 10 11, each acc = fma(h * w, grad, acc)).  grid (qtiles, B * 3, scales)
+__global__ __launch_bounds__(LOSS_OR_THREADS) void loss_orien_grad_kernel(const LossGradParams p) {
+    __shared__ int4 s_roi[OM_LOSS_MAX_GT];
+    __shared__ float4 s_geo[OM_LOSS_MAX_GT];
+    __shared__ int s_idx[OM_LOSS_MAX_GT];
+    __shared__ int s_n;
+    __shared__ float2 s_d[LOSS_GR * LOSS_GR];
+    static_assert(LOSS_GQ * LOSS_GQ == LOSS_OR_THREADS, "one lane per quarter pixel");
+    const int s = blockIdx.z, b = blockIdx.y / 3, a = blockIdx.y - 3 * (blockIdx.y / 3);
+    const om_loss_cfg& c = p.cfg;
+    if (s >= c.num_scales || a >= c.anchors_of_scale[s]) return;
+    const int H = c.image_h, W = c.image_w, oh = H / 4, ow = W / 4;
+    const int qy0 = (blockIdx.x / p.qtiles_x) * LOSS_GQ, qx0 = (blockIdx.x % p.qtiles_x) * LOSS_GQ;
+    const int fy0 = max(4 * qy0 - 2, 0), fy1 = min(4 * (qy0 + LOSS_GQ) + 2, H);
+    const int fx0 = max(4 * qx0 - 2, 0), fx1 = min(4 * (qx0 + LOSS_GQ) + 2, W);
+    const int qi = qy0 + threadIdx.x / LOSS_GQ, qj = qx0 + threadIdx.x % LOSS_GQ;
+    const bool qin = qi < oh && qj < ow;
+    const int64_t* ost = c.orien_stride[s];
+    float* gxp = p.gorien[s] + b * ost[0] + (int64_t)(2 * a) * ost[1];
+    float* gyp = gxp + ost[1];
+    int g0, ng;
+    image_range(p, b, g0, ng);
+    const LossGt* gts = p.gts + (size_t)s * p.N + g0;
+    if (threadIdx.x < 64) {         // cull in collate order: one wave, ballot + prefix
+        const int lane = threadIdx.x;
+        int base = 0;
+        for (int j0 = 0; j0 < ng; j0 += 64) {
+            const int j = j0 + lane;
+            bool mine = false;
+            LossGt g;
+            if (j < ng) {
+                g = gts[j];
+                mine = g.key >= 0 && g.a == a && g.x1 < fx1 && g.x2 > fx0 && g.y1 < fy1 && g.y2 > fy0;
+            }
+            const unsigned long long votes = __ballot(mine);
+            if (mine) {
+                const int slot = base + __popcll(votes & ((1ull << lane) - 1ull));
+                s_roi[slot] = make_int4(g.x1, g.x2, g.y1, g.y2);
+                s_geo[slot] = make_float4(g.px, g.py, g.cw, g.ch);
+                s_idx[slot] = g0 + j;
+            }
+            base += __popcll(votes);
+        }
+        if (lane == 0) s_n = base;
+    }
+    __syncthreads();
+    const int n_inst = s_n;
+    if (n_inst == 0) {              // no ROI meets the tile: the gradient is zero
+        if (qin) {
+            gxp[qi * ost[2] + qj] = 0.0f;
+            gyp[qi * ost[2] + qj] = 0.0f;
+        }
+        return;
+    }
+    // d loss_orien_{pos,neg} / d loss_orien_all: G / nB * bbox_pos.sum() / num_orien_{pos,neg} (none when the count is 0)
+    const float* r = p.result + s * OM_LOSS_SCALE_FLOATS;
+    const float nB = (float)p.B, nbox = r[OM_LOSS_TERMS + 1];
+    const float nop = r[OM_LOSS_TERMS + 13] / 2.0f, non = r[OM_LOSS_TERMS + 15] / 2.0f;
+    const float c_pos = nop > 0.0f ? ((term_grad(p, s, 5) / nB) * nbox) / nop : 0.0f;
+    const float c_neg = non > 0.0f ? ((term_grad(p, s, 6) / nB) * nbox) / non : 0.0f;
+    const int ag = c.anchor_mask[s][a];
+    const float haw = c.anchor_w[ag] / 2.0f, hah = c.anchor_h[ag] / 2.0f;
+    const float* pxp = p.orien[s] + b * ost[0] + (int64_t)(2 * a) * ost[1];
+    const float* pyp = pxp + ost[1];
+    const int rh = fy1 - fy0, rw = fx1 - fx0;
+    for (int k = threadIdx.x; k < rh * rw; k += LOSS_OR_THREADS) {
+        const int ry = k / rw, rx = k - ry * rw;
+        const int py = fy0 + ry, px = fx0 + rx;
+        int state = 0;
+        float t0 = 0.0f, t1 = 0.0f;
+        const float fx = (float)px, fy = (float)py;
+        for (int i = 0; i < n_inst; ++i) {
+            const int4 roi = s_roi[i];
+            if (px < roi.x || px >= roi.y || py < roi.z || py >= roi.w) continue;
+            const float4 g = s_geo[i];
+            const float ox = fx - g.x, oy = fy - g.y;
+            if (p.gt_mask[((size_t)s_idx[i] * H + py) * W + px]) {
+                state = -1;
+                t0 = ox;
+                t1 = oy;
+            } else if (state >= 0) {
+                state += 1;
+                const float lx = maxf_(fabsf(ox), 1e-8f), ly = maxf_(fabsf(oy), 1e-8f);
+                const float qx = maxf_(g.z / lx, 1.0f), qy = maxf_(g.w / ly, 1.0f);
+                const float q = minf_(qx, qy) - 1.0f;
+                const float sgx = ox > 0.0f ? 1.0f : ox < 0.0f ? -1.0f : 0.0f;
+                const float sgy = oy > 0.0f ? 1.0f : oy < 0.0f ? -1.0f : 0.0f;
+                t0 = t0 + (q * sgx) * lx;
+                t1 = t1 + (q * sgy) * ly;
+            }
+        }
+        float2 d = make_float2(0.0f, 0.0f);
+        if (state != 0) {
+            t0 = t0 / haw;
+            t1 = t1 / hah;
+            const float den = state < 0 ? -1.0f : (float)state;
+            t0 = t0 / den;
+            t1 = t1 / den;
+            int i0, i1, j0, j1;
+            float wy0, wy1, wx0, wx1;
+            tap(py, 0.25f, oh, i0, i1, wy0, wy1);
+            tap(px, 0.25f, ow, j0, j1, wx0, wx1);
+            const float pox = bilinear_blend(pxp[i0 * ost[2] + j0], pxp[i0 * ost[2] + j1], pxp[i1 * ost[2] + j0],
+                                             pxp[i1 * ost[2] + j1], wx0, wx1, wy0, wy1);
+            const float poy = bilinear_blend(pyp[i0 * ost[2] + j0], pyp[i0 * ost[2] + j1], pyp[i1 * ost[2] + j0],
+                                             pyp[i1 * ost[2] + j1], wx0, wx1, wy0, wy1);
+            const float dd = state < 0 ? c_pos : c_neg;
+            // smooth_l1_loss_backward, beta 1: (|x| < 1 ? x : sign(x)) * grad
+            const float ex = pox - t0, ey = poy - t1;
+            d.x = (fabsf(ex) < 1.0f ? ex : ex > 0.0f ? 1.0f : -1.0f) * dd;
+            d.y = (fabsf(ey) < 1.0f ? ey : ey > 0.0f ? 1.0f : -1.0f) * dd;
+        }
+        s_d[ry * LOSS_GR + rx] = d;
+    }
+    __syncthreads();
+    if (!qin) return;
+    float ax = 0.0f, ay = 0.0f;
+    const int r0 = max(4 * qi - 2, 0), r1 = min(4 * qi + 6, H), c0 = max(4 * qj - 2, 0), c1 = min(4 * qj + 6, W);
+    for (int y = r0; y < r1; ++y) {
+        int i0, i1;
+        float wy0, wy1;
+        tap(y, 0.25f, oh, i0, i1, wy0, wy1);
+        if (i0 != qi && i1 != qi) continue;
+        for (int x = c0; x < c1; ++x) {
+            int j0, j1;
+            float wx0, wx1;
+            tap(x, 0.25f, ow, j0, j1, wx0, wx1);
+            if (j0 != qj && j1 != qj) continue;
+            const float2 d = s_d[(y - fy0) * LOSS_GR + (x - fx0)];
+            if (i0 == qi && j0 == qj) { const float l = wy0 * wx0; ax = fmaf(l, d.x, ax); ay = fmaf(l, d.y, ay); }
+            if (i0 == qi && j1 == qj) { const float l = wy0 * wx1; ax = fmaf(l, d.x, ax); ay = fmaf(l, d.y, ay); }
+            if (i1 == qi && j0 == qj) { const float l = wy1 * wx0; ax = fmaf(l, d.x, ax); ay = fmaf(l, d.y, ay); }
+            if (i1 == qi && j1 == qj) { const float l = wy1 * wx1; ax = fmaf(l, d.x, ax); ay = fmaf(l, d.y, ay); }
+        }
+    }
+    gxp[qi * ost[2] + qj] = ax;
+    gyp[qi * ost[2] + qj] = ay;
+}
+
 }  // namespace om
 
 extern "C" {
@@ -603,6 +892,44 @@ int om_loss_targets(const om_loss_cfg* cfg, const float* const* bbox, int B, con
     float* res = reinterpret_cast<float*>(static_cast<char*>(workspace) + L.total);
     return om::loss_run(cfg, bbox, nullptr, B, gt_bbox, gt_cls, gt_index, gt_mask, N, res, workspace, ws_bytes,
                         static_cast<hipStream_t>(stream), p, "om_loss_targets");
+}
+
+int om_loss_backward(const om_loss_cfg* cfg, const float* const* bbox, const float* const* orien, int B, const int64_t* gt_index,
+                     const uint8_t* gt_mask, int N, const float* result, const void* workspace, size_t ws_bytes,
+                     const float* grad_out, const float* scales_weight, float* const* grad_bbox, float* const* grad_orien,
+                     om_stream stream) {
+    OM_REQUIRE(om::loss_cfg_ok(cfg), OM_EINVAL, "om_loss_backward: unsupported configuration");
+    OM_REQUIRE(B >= 1 && N >= 0 && N <= B * OM_LOSS_MAX_GT, OM_EINVAL, "om_loss_backward: B = %d, N = %d", B, N);
+    OM_REQUIRE(bbox && orien && grad_bbox && grad_orien && gt_index && gt_mask && result && workspace && grad_out && scales_weight,
+               OM_EINVAL, "om_loss_backward: null pointer");
+    const om::LossLayout L = om::loss_layout(cfg, B, N);
+    OM_REQUIRE(ws_bytes >= L.total, OM_ENOMEM, "om_loss_backward: workspace of %zu bytes, %zu needed", ws_bytes, L.total);
+    om::LossGradParams p = {};
+    p.cfg = *cfg;
+    for (int s = 0; s < cfg->num_scales; ++s) {
+        OM_REQUIRE(bbox[s] && orien[s] && grad_bbox[s] && grad_orien[s], OM_EINVAL, "om_loss_backward: null head of scale %d", s);
+        p.bbox[s] = bbox[s];
+        p.orien[s] = orien[s];
+        p.gbbox[s] = grad_bbox[s];
+        p.gorien[s] = grad_orien[s];
+        p.sw[s] = scales_weight[s];
+    }
+    p.B = B;
+    p.N = N;
+    p.gt_index = gt_index;
+    p.gt_mask = gt_mask;
+    p.gts = reinterpret_cast<const om::LossGt*>(static_cast<const char*>(workspace) + L.gts);
+    p.result = result;
+    p.gout = grad_out;
+    p.qtiles_x = (cfg->image_w / 4 + om::LOSS_GQ - 1) / om::LOSS_GQ;
+    p.qtiles = p.qtiles_x * ((cfg->image_h / 4 + om::LOSS_GQ - 1) / om::LOSS_GQ);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int S = cfg->num_scales;
+    hipLaunchKernelGGL(om::loss_box_grad_kernel, dim3(L.box_blocks, B, S), dim3(om::LOSS_BOX_THREADS), 0, st, p);
+    OM_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(om::loss_orien_grad_kernel, dim3(p.qtiles, B * 3, S), dim3(om::LOSS_OR_THREADS), 0, st, p);
+    OM_CHECK_HIP(hipGetLastError());
+    return OM_OK;
 }
 
 }  // extern "C"

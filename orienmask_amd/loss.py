@@ -10,7 +10,7 @@ per-scale and cross-scale aggregation (eval/base.py:29-32,90-121) runs on the ho
 
 Deliberate departures from the reference:
   * no autograd: the values only (the validation epoch runs under no_grad).  A head that requires grad raises
-    NotImplementedError -- the loss's backward is out of scope;
+    NotImplementedError: the class with a backward (om_loss_backward) is orienmask_amd.train.OrienMaskYOLOMultiScaleLoss;
   * a non-finite pred_wh raises FloatingPointError (the reference prints and calls exit());
   * loud limits: 1..3 scales of 1..3 anchors, at most 9 anchors, 2047 classes and OM_LOSS_MAX_GT (1024) GTs per image; the
     orientation maps are exactly image / 4 per side;
@@ -201,8 +201,8 @@ class OrienMaskYOLOMultiScaleLoss:
             for t, name in ((bbox, "bbox head"), (orien, "orientation head")):
                 _lib.require_cuda_tensor(t, name, torch.float32)
                 if t.requires_grad:
-                    raise NotImplementedError("the HIP loss computes values only; its backward is out of scope (call it under "
-                                              "torch.no_grad() or on detached heads)")
+                    raise NotImplementedError("this HIP loss computes values only (call it under torch.no_grad() or on detached "
+                                              "heads); orienmask_amd.train.OrienMaskYOLOMultiScaleLoss has the backward")
             nA = len(self.anchor_mask[s])
             gh, gw = self.grids[s]
             want = (nA * (5 + int(self.num_classes)), gh, gw)
@@ -251,15 +251,22 @@ class OrienMaskYOLOMultiScaleLoss:
             self._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         return self._ws
 
-    def prepare(self, predict, target):
+    def prepare(self, predict, target, workspace=None):
         """Check the inputs and bind everything om_loss reads and writes; returns a callable that enqueues om_loss on the current
-        stream (no host work but the C call itself) and returns the device result vector (OM_LOSS_RESULT_FLOATS floats)."""
+        stream (no host work but the C call itself) and returns the device result vector (OM_LOSS_RESULT_FLOATS floats).
+        `workspace`: a uint8 device tensor of at least workspace_bytes(B, N) to use instead of the loss's own.  The callable's
+        attributes `heads`, `target` (gt_bbox, gt_cls, gt_index, gt_mask), `B`, `N`, `ws` and `result` are what it binds."""
         heads = self._heads(predict)
         B, dev = heads[0][0].shape[0], heads[0][0].device
         gt_bbox, gt_cls, gt_index, gt_mask, N = self._targets(target, B, dev)
         L = _lib.load()
         cfg = self.cfg_struct(heads)
-        ws = self._workspace(self.workspace_bytes(B, N), dev)
+        if workspace is None:
+            ws = self._workspace(self.workspace_bytes(B, N), dev)
+        else:
+            ws = workspace
+            if ws.dtype != torch.uint8 or ws.device != dev or ws.numel() < self.workspace_bytes(B, N):
+                raise ValueError("workspace must be uint8 on %s with at least %d bytes" % (dev, self.workspace_bytes(B, N)))
         result = torch.empty(_lib.OM_LOSS_RESULT_FLOATS, dtype=torch.float32, device=dev)
         bb = (ctypes.c_void_p * 3)(*[h[0].data_ptr() for h in heads] + [None] * (3 - len(heads)))
         oo = (ctypes.c_void_p * 3)(*[h[1].data_ptr() for h in heads] + [None] * (3 - len(heads)))
@@ -273,6 +280,7 @@ class OrienMaskYOLOMultiScaleLoss:
                 _lib.check(L.om_loss(*args, _lib.current_stream_ptr(dev)), "om_loss")
             run.keep = keep
             return result
+        run.heads, run.target, run.B, run.N, run.ws, run.result = heads, (gt_bbox, gt_cls, gt_index, gt_mask), B, N, ws, result
         return run
 
     def launch(self, predict, target):
@@ -286,7 +294,10 @@ class OrienMaskYOLOMultiScaleLoss:
         """Returns (loss_sum: 0-dim tensor on the heads' device, loss_log: {key: float}, metric_log: {key: (num, count)}) with
         eval/base.py:90-121's keys in its order; metric_log is empty when training is True (orienmask_yolo_loss.py:148)."""
         result = self.launch(predict, target)
-        dev = result.device
+        return self._finish(result, training, result.device)
+
+    def _finish(self, result, training, dev):
+        """The host side of a call: the flag word, then aggregate."""
         host = result.cpu()                                  # the call's one device-to-host copy
         flags = int(host[_lib.OM_LOSS_FLAG_OFF:].view(torch.int32)[0])
         if flags & _lib.OM_LOSS_FLAG_NONFINITE_WH:
