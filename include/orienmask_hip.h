@@ -643,6 +643,40 @@ int om_loss_backward(const om_loss_cfg* cfg, const float* const* bbox, const flo
                      const float* grad_out, const float* scales_weight, float* const* grad_bbox, float* const* grad_orien,
                      om_stream stream);
 
+/* ---- Training / validation augmentation: COCOTransform + collate (data/transform.py:65-441, data/collate.py:13-30 of the
+ *      reference; orienmask_amd/augment.py plans every random draw on the host, these kernels do the pixel work).
+ *      One record per image, in DEVICE memory; every offset and window in it was checked by the host planner.  Per output pixel:
+ *      undo the flips, write the pad colour in the pad region, else cv2 INTER_LINEAR (or the INTER_AREA 2x2 mean of an exact 2x
+ *      downscale) into the crop window with the jitter chain applied to each tap, then (x - mean) / std, NCHW.  Per output GT o:
+ *      gt_table[2o] is the source GT (batch-global index, ToTensor's randperm already applied), gt_table[2o+1] its image;
+ *      cv2 INTER_NEAREST from the row-packed bits (np.packbits, MSB first), pad 0, flips, one byte 0/1 per pixel.
+ *      When any image's chain has contrast, two extra launches first reduce the grey mean of its full source in a fixed order
+ *      (per-workgroup double partials, then one fixed tree per image: bit-identical from run to run, no atomics).
+ *      workspace: om_augment_workspace_bytes(n_images) bytes of device memory, contents undefined on entry. */
+#define OM_AUG_MAX_OPS 4
+#define OM_AUG_BRIGHTNESS 0
+#define OM_AUG_CONTRAST 1
+#define OM_AUG_SATURATION 2
+#define OM_AUG_HUE 3
+typedef struct om_aug_sample {
+    int64_t image_off;          /* element offset of the [src_h,src_w,3] HWC source in `images` */
+    int64_t mask_off;           /* byte offset of the image's first packed mask ([src_h, (src_w+7)/8] bytes per GT) */
+    double scale_x, scale_y;    /* cv2: 1 / ((double)nw / crop_w), 1 / ((double)nh / crop_h) */
+    int32_t src_h, src_w;
+    int32_t crop_top, crop_left, crop_h, crop_w;
+    int32_t nh, nw, pad_top, pad_left;
+    int32_t hflip, vflip, area2x, n_ops;
+    int32_t op[OM_AUG_MAX_OPS];   /* OM_AUG_*, in the shuffled order */
+    float fa[OM_AUG_MAX_OPS];     /* float32(factor) */
+    float fb[OM_AUG_MAX_OPS];     /* float32(1 - factor); hue: float32(factor * 360) */
+    float pad_value[3];
+    int32_t gt_first, n_gt, reserved;
+} om_aug_sample;
+size_t om_augment_workspace_bytes(int n_images);
+int om_augment(const om_aug_sample* samples, int n_images, const void* images, int images_u8, const float* mean3,
+               const float* std3, int out_h, int out_w, float* out_image, const uint8_t* masks, const int32_t* gt_table, int n_gt,
+               uint8_t* out_mask, int any_contrast, void* workspace, size_t ws_bytes, om_stream stream);
+
 /* ---- Several batches in flight.  Every entry point only enqueues kernels on the caller's stream and keeps no per-call state in
  *      the model handle (profiling apart): om_forward / om_forward_f16 / om_postprocess may be issued for different batches
  *      on different HIP streams at the same time, provided each batch in flight has its OWN workspace (and output buffers);

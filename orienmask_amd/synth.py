@@ -450,3 +450,31 @@ def synth_targets(seed, batch, height, width, gts_per_image=7, num_classes=80, v
     gt_bbox = np.asarray(boxes, dtype=np.float32).reshape(-1, 4)
     gt_mask = np.asarray(masks, dtype=bool).reshape(-1, height, width)
     return gt_bbox, np.asarray(classes, dtype=np.int64), index, gt_mask
+
+
+def synth_coco_sample(seed, height, width, n_gt, border=False, with_info=True, image_id=0):
+    """One sample as the reference's COCODataset._load_sample_data returns it (data/dataset.py:70-87): image [h,w,3] float32 RGB
+    holding uint8 values, bbox [n,4] float32 (cx, cy, w, h normalised), cls [n] int64, mask = list of n uint8 [h,w] 0/1 arrays
+    (elliptic blobs, each inside its box), info {id, height, width}.  border=True puts the first GT against the image's corner."""
+    rng = _rng(seed)
+    yy, xx = np.mgrid[0:height, 0:width]
+    base = rng.uniform(0, 255, 3)[None, None, :] + 60 * np.sin(xx[..., None] / (3 + 7 * rng.random(3)) + yy[..., None] / (4 + 9 * rng.random(3)))
+    image = np.clip(np.rint(base + rng.normal(0, 25, (height, width, 3))), 0, 255).astype(np.float32)
+    boxes, masks = [], []
+    for k in range(n_gt):
+        bw, bh = rng.integers(1, max(2, width // 2) + 1), rng.integers(1, max(2, height // 2) + 1)
+        x0 = 0 if (border and k == 0) else int(rng.integers(0, width - bw + 1))
+        y0 = 0 if (border and k == 0) else int(rng.integers(0, height - bh + 1))
+        if border and k == 1:
+            x0, y0 = width - bw, height - bh
+        cx, cy = x0 + bw / 2.0, y0 + bh / 2.0
+        m = (((xx + 0.5 - cx) / (bw / 2.0)) ** 2 + ((yy + 0.5 - cy) / (bh / 2.0)) ** 2 <= 1.0).astype(np.uint8)
+        if border and k < 2:
+            m[y0:y0 + bh, x0:x0 + bw] = 1           # the full box: the mask touches the image's edge
+        masks.append(m)
+        boxes.append([cx / width, cy / height, bw / width, bh / height])
+    sample = {"image": image, "bbox": np.array(boxes, np.float32).reshape(-1, 4),
+              "cls": rng.integers(0, 80, n_gt).astype(np.int64), "mask": masks}
+    if with_info:
+        sample["info"] = {"id": image_id, "height": height, "width": width}
+    return sample

@@ -1,4 +1,5 @@
-"""Drop-in for the reference's GPU preprocessing.
+"""Drop-in for the reference's GPU preprocessing and, from augment.py, its training / validation
+data pipeline (COCOTransform, collate, to_device, device_batches: SURVEY.md row 14).
 
   FastCOCOTransform(pipeline, use_cuda)   /root/reference/data/transform.py:444-510
   pad(image, size_divisor=32, pad_value=0) /root/reference/infer.py:21-32
@@ -16,6 +17,7 @@ import math
 import torch
 
 from . import lib as _lib
+from .augment import COCOTransform, collate, device_batches, to_device  # noqa: F401  (build_transform resolves names here)
 
 
 def _pair(v):
