@@ -1,9 +1,10 @@
 /* CPU oracle for the reference's CUDA NMS backend.  TEST INFRASTRUCTURE ONLY -- never linked into or called
  * from the product library.
  *
- * Plain-C restatement of /root/reference/eval/src/nms_kernel.cu (which cannot be built anywhere today: it
- * includes THC headers that torch >= 1.11 no longer ships).  The algorithm is deterministic and
- * host-restatable:
+ * Plain-C restatement of /root/reference/eval/src/nms_kernel.cu.  That file itself builds for gfx950 through
+ * oracle/build_ref_cuda.py (torch's hipify, our own THC stand-ins in oracle/thc_shim/), and this restatement is
+ * pinned to its keep lists bit for bit on the case sets of tests/nms_cases.py: tests/test_nms_cuda_ref.py on the GPU,
+ * tests/golden/nms_cuda_ref.npz (recorded by tools/gen_golden_nms_cuda.py) in tests/test_oracle_golden.py.  The algorithm is deterministic and host-restatable:
  *   devIoU      :13-23   left/right/top/bottom from a[0] -+ a[2]/2 (a = cx, cy, w, h), areas Sa = a[2]*a[3],
  *                        IoU = interS / (Sa + Sb - interS)
  *   nms_kernel  :25-69   one 64-bit word per (row, 64-column block): bit i set when devIoU(row, col) > thresh
@@ -12,9 +13,12 @@
  *                        is kept and ORs its words into remv[]
  *               :136-139 returns order[keep]: ORIGINAL indices in score-descending (visiting) order
  * The boxes arrive already sorted (`sorted5`), as boxes_sorted at :76-78; the sort itself (torch's CUDA sort,
- * ties unspecified) is the caller's.  Every operation rounds once (build with -ffp-contract=off); nvcc's default
- * -fmad=true MAY fuse `Sa + Sb - width*height` on a real build -- that choice is the compiler's, not the source's.
+ * ties unspecified: stable from 33 elements up, an unstable bitonic network below) is the caller's.  Every operation rounds once (build with -ffp-contract=off), as in the
+ * reference build "nms_cuda_ref_exact"; hipcc's default contraction ("nms_cuda_ref_fused", 15 FMAs in the kernel
+ * against 5) fuses `Sb + Sa` and `... - width*height` and moves IoUs next to the threshold across it
+ * (tests/nms_cases.py, contraction family) -- that choice is the compiler's, not the source's.
  */
+#include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
@@ -24,11 +28,10 @@ static float dev_iou(const float* a, const float* b) {
     const float ar = a[0] + a[2] / 2, br = b[0] + b[2] / 2;
     const float at = a[1] - a[3] / 2, bt = b[1] - b[3] / 2;
     const float ab = a[1] + a[3] / 2, bb = b[1] + b[3] / 2;
-    const float left = al > bl ? al : bl, right = ar < br ? ar : br;
-    const float top = at > bt ? at : bt, bottom = ab < bb ? ab : bb;
-    float width = right - left, height = bottom - top;
-    if (!(width > 0.f)) width = 0.f;
-    if (!(height > 0.f)) height = 0.f;
+    /* devIoU's max / min are the device fmaxf / fminf (v_max_f32 / v_min_f32): a NaN operand yields the other one */
+    const float left = fmaxf(al, bl), right = fminf(ar, br);
+    const float top = fmaxf(at, bt), bottom = fminf(ab, bb);
+    const float width = fmaxf(right - left, 0.f), height = fmaxf(bottom - top, 0.f);
     const float inter = width * height;
     const float sa = a[2] * a[3], sb = b[2] * b[3];
     return inter / (sa + sb - inter);

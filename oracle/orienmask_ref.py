@@ -200,8 +200,8 @@ _nms_cuda_lib = None
 
 
 def nms_cuda(dets, threshold):
-    """nms_cuda, /root/reference/eval/src/nms_kernel.cu:72-140, through the C restatement oracle/nms_cuda_ref.c (the CUDA
-    source itself cannot be built: THC headers are gone).  dets [n,5] (cx,cy,w,h,score); returns int64 keep indices in
+    """nms_cuda, /root/reference/eval/src/nms_kernel.cu:72-140, through the C restatement oracle/nms_cuda_ref.c, pinned bit
+    for bit to the reference's own kernel (nms_cuda_reference below; tests/golden/nms_cuda_ref.npz).  dets [n,5] (cx,cy,w,h,score); returns int64 keep indices in
     SCORE-DESCENDING order (order_t[keep], :136-139).  The sort (:76, torch's CUDA sort: ties unspecified) is restated as a
     stable descending sort, i.e. ties are visited in ascending index order."""
     global _nms_cuda_lib
@@ -223,6 +223,34 @@ def nms_cuda(dets, threshold):
     m = _nms_cuda_lib.nms_cuda_ref_f32(sorted5.numpy().ctypes.data, n, ctypes.c_float(threshold), keep_sorted.ctypes.data)
     assert m >= 0
     return order[torch.from_numpy(keep_sorted[:m])]
+
+
+_nms_cuda_modules = {}
+
+
+def nms_cuda_reference(dets, threshold, variant="exact"):
+    """The reference's own CUDA NMS backend (eval/src/nms_cuda.cpp + nms_kernel.cu), built for gfx950 by
+    oracle/build_ref_cuda.py into oracle/_ref/ and run on cuda:0.  variant "exact": compiled with -ffp-contract=off, every
+    operation rounds once as the source states; "fused": hipcc's default contraction (FMAs in devIoU).  dets [n,5]
+    (cx,cy,w,h,score); returns the int64 keep indices on the CPU in the module's own order (order_t[keep], score-descending)."""
+    if variant not in ("exact", "fused"):
+        raise ValueError("variant must be 'exact' or 'fused', got %r" % (variant,))
+    mod = _nms_cuda_modules.get(variant)
+    if mod is None:
+        import importlib.util
+        import sysconfig
+        name = "nms_cuda_ref_" + variant
+        path = os.path.join(_HERE, "_ref", name + sysconfig.get_config_var("EXT_SUFFIX"))
+        if not os.path.exists(path):
+            raise RuntimeError("%s not built: run `make -C oracle ref` (oracle/build_ref_cuda.py, part of "
+                               "__graft_entry__.build() where the reference tree is present)" % os.path.relpath(path, _HERE))
+        spec = importlib.util.spec_from_file_location(name, path)
+        mod = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+        _nms_cuda_modules[variant] = mod
+    d = dets.detach().to(device="cuda:0", dtype=torch.float32).contiguous()
+    keep = mod.nms(d, float(threshold))
+    return keep.cpu().to(torch.long)
 
 
 def nms_numpy(dets, threshold, order=None):

@@ -1520,8 +1520,9 @@ def test_nms_random_vs_oracle(dev):
 
 
 def test_nms_cuda_backend_semantics(dev):
-    """The reference's CUDA backend (eval/src/nms_kernel.cu, unbuildable today) restated in oracle/nms_cuda_ref.c: strict >,
-    w*h areas, keep in score-descending order.  Known answers where the two backends differ, then random boxes."""
+    """The reference's CUDA backend (eval/src/nms_kernel.cu) through its C restatement oracle/nms_cuda_ref.c (pinned to the
+    reference's own kernel in tests/test_nms_cuda_ref.py): strict >, w*h areas, keep in score-descending order.  Known answers where the two
+    backends differ, then random boxes."""
     from orienmask_amd.eval import batched_nms, nms
     # IoU exactly 0.5 (overlap 2 of union 4): the CPU backend suppresses (>=), the CUDA backend keeps both (>)
     d = torch.tensor([[1.5, 0.5, 3.0, 1.0, 0.9], [2.5, 0.5, 3.0, 1.0, 0.8], [8.0, 0.5, 3.0, 1.0, 0.7]])

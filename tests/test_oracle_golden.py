@@ -73,8 +73,8 @@ def _nms_cuda_numpy(dets, thr):
 
 
 def test_nms_cuda_backend_oracle():
-    """oracle/nms_cuda_ref.c (the reference's CUDA backend, nms_kernel.cu:13-140, which cannot be built: parity of this
-    backend is pinned by restatement only) against the independent numpy restatement above, and the semantic differences
+    """oracle/nms_cuda_ref.c (the reference's CUDA backend, nms_kernel.cu:13-140; parity of this backend is pinned by
+    restatement) against the independent numpy restatement above, and the semantic differences
     from the CPU backend on hand-built boxes: IoU == threshold is kept (strict >), keep comes back score-descending."""
     d = torch.tensor([[1.5, 0.5, 3.0, 1.0, 0.9], [2.5, 0.5, 3.0, 1.0, 0.8], [8.0, 0.5, 3.0, 1.0, 0.95]])
     assert R.nms_cpu(d, 0.5).tolist() == [0, 2] and R.nms_cuda(d, 0.5).tolist() == [2, 0, 1]
@@ -92,6 +92,65 @@ def test_nms_cuda_backend_oracle():
         dn = np.concatenate([rng.random((n, 2)), rng.random((n, 2)) * 0.3 + 0.02, rng.random((n, 1))], 1).astype(np.float32)
         dn[::5, 4] = dn[1::5, 4][:dn[::5].shape[0]]                       # score ties: visited in index order
         assert R.nms_cuda(torch.from_numpy(dn), 0.45).tolist() == _nms_cuda_numpy(dn, 0.45).tolist(), n
+
+
+@pytest.mark.parametrize("family", ["threshold", "contraction", "blocks", "chains", "degenerate", "nan", "ties"])
+def test_nms_cuda_restatement_on_adversarial_sets(family):
+    """oracle/nms_cuda_ref.c against the case sets of tests/nms_cases.py, whose keep lists come from an independent numpy
+    float32 restatement of devIoU (fmaxf / fminf, w * h areas, strict >, stable score-descending visiting order): IoU at and one
+    ulp around the threshold, contraction-sensitive pairs, n across the 64-box blocks up to 9000, suppression chains across
+    blocks, degenerate, NaN and tied boxes.  Three wrong readings of nms_kernel.cu (>= for >, corner areas, keep in ascending
+    index order) each change a keep list of the sets, and hipcc's default contraction changes one in the contraction family."""
+    import nms_cases as N
+    sets = N.cases((family,))
+    assert sets
+    for c in sets:
+        assert R.nms_cuda(torch.from_numpy(c["dets"]), float(c["thr"])).tolist() == c["keep"].tolist(), c["name"]
+    small = [c for c in sets if c["dets"].shape[0] <= 1024]
+    if family == "threshold":
+        for kw in (dict(ge=True), dict(iou=N.iou_corner_area), dict(ascending=True)):
+            assert any(N.nms_exact(c["dets"], c["thr"], **kw).tolist() != c["keep"].tolist() for c in small), kw
+    if family == "contraction":
+        assert all(N.nms_exact(c["dets"], c["thr"], iou=N.iou_fused).tolist() != c["keep"].tolist() for c in small)
+
+
+def test_nms_cuda_restatement_matches_reference_kernel():
+    """tests/golden/nms_cuda_ref.npz holds the keep lists that the reference's own nms_cuda.cpp + nms_kernel.cu (built for
+    gfx950 by oracle/build_ref_cuda.py; recorded by tools/gen_golden_nms_cuda.py) returned on the case sets of
+    tests/nms_cases.py, in both builds.  The case sets are rebuilt unchanged; oracle/nms_cuda_ref.c reproduces the exact build's
+    lists bit for bit and in order on every family; the fused build's lists are what nms_cases.iou_fused predicts on the
+    contraction family and differ from the exact ones there.  Score ties: where the reference's visiting order (the recorded
+    order of torch's GPU sort) is not the stable one, the recorded list is greedy NMS over that order and the restatement gives
+    the stable order's."""
+    import nms_cases as N
+    g = np.load(os.path.join(GOLDEN, "nms_cuda_ref.npz"))
+    built = {c["name"]: c for c in N.cases()}
+    names = g["names"].tolist()
+    assert sorted(names) == sorted(built) and set(g["families"].tolist()) == set(N.FAMILIES)
+    fused_differs = 0
+    for name in names:
+        c = built[name]
+        if name + "_dets" in g.files:
+            assert np.array_equal(g[name + "_dets"], c["dets"], equal_nan=True), name
+        else:
+            assert c["dets"].shape[0] > N.STORED_MAX_N
+        assert np.array_equal(g[name + "_checksum"], [c["dets"].astype(np.float64).sum()], equal_nan=True), name
+        assert np.array_equal(g[name + "_cats"], c["cats"]) and g[name + "_thr"] == c["thr"], name
+        keep = g[name + "_keep"].astype(np.int64).tolist()
+        restated = R.nms_cuda(torch.from_numpy(c["dets"]), float(c["thr"])).tolist()
+        if c["family"] == "ties":
+            order = g[name + "_order"].astype(np.int64)
+            assert N.nms_exact(c["dets"], c["thr"], order=order).tolist() == keep, name
+            assert restated == c["keep"].tolist(), name
+            if np.array_equal(order, N.visiting_order(c["dets"])):
+                assert restated == keep, name
+        else:
+            assert restated == keep, name
+        if c["family"] == "contraction":
+            fused = g[name + "_keep_fused"].astype(np.int64).tolist()
+            assert N.nms_exact(c["dets"], c["thr"], iou=N.iou_fused).tolist() == fused, name
+            fused_differs += fused != keep
+    assert fused_differs >= 1
 
 
 @pytest.mark.parametrize("fname", golden_files("post_"))
