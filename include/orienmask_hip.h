@@ -677,6 +677,44 @@ int om_augment(const om_aug_sample* samples, int n_images, const void* images, i
                const float* std3, int out_h, int out_w, float* out_image, const uint8_t* masks, const int32_t* gt_table, int n_gt,
                uint8_t* out_mask, int any_contrast, void* workspace, size_t ws_bytes, om_stream stream);
 
+/* ---- The optimizer step: torch.optim.SGD (trainer/trainer.py:53 `self.optimizer.step()`, the optimizer trainer/builder.py:118-130
+ *      builds) for every tensor of every parameter group in ONE launch; orienmask_amd/optim.py (class SGD) is the host side.
+ *      Per element, float32, in torch-CPU's rounding (each add(alpha=) is one fma, buf.mul_(momentum) rounds on its own):
+ *          d   = fma(p, wd, g)                           (OM_SGD_HAS_WD;  g negated first under OM_SGD_MAXIMIZE)
+ *          buf = d                                       (OM_SGD_FIRST: the tensor's first step)
+ *          buf = fma(d, 1 - dampening, buf * momentum)   (later steps)
+ *          d   = nesterov ? fma(buf, momentum, d) : buf  (both only under OM_SGD_HAS_MOMENTUM)
+ *          p   = fma(d, -lr, p)
+ *      table: one om_sgd_tensor per tensor in DEVICE memory; lr, weight_decay and the three pointers are read from it by the
+ *      kernel, so a scheduler step changes a row and nothing else.  table_host (may be null: the device table is used as it is):
+ *      n_tensors rows in pinned host memory, copied to `table` on `stream` ahead of the launch (hipMemcpyAsync; the caller keeps
+ *      the host rows unchanged until that copy has run).  chunks: the DEVICE work list, one om_sgd_chunk per OM_SGD_CHUNK
+ *      elements of a tensor (chunk k of tensor t covers elements [k * OM_SGD_CHUNK, min(n, (k + 1) * OM_SGD_CHUNK))), built once
+ *      from the element counts; rows flagged OM_SGD_SKIP (grad is None) are passed over.  param / grad / buf are dense tensors
+ *      of n floats in the SAME storage order; 16-byte accesses where all three are 16-byte aligned, 4-byte accesses otherwise.
+ *      No allocation, no host synchronisation; every element is written exactly once. */
+#define OM_SGD_CHUNK 4096
+#define OM_SGD_SKIP 1
+#define OM_SGD_FIRST 2
+#define OM_SGD_NESTEROV 4
+#define OM_SGD_MAXIMIZE 8
+#define OM_SGD_HAS_MOMENTUM 16
+#define OM_SGD_HAS_WD 32
+typedef struct om_sgd_tensor {
+    float* param;
+    const float* grad;
+    float* buf;                 /* momentum buffer; unused without OM_SGD_HAS_MOMENTUM */
+    int64_t n;
+    float neg_lr, weight_decay, momentum, one_minus_dampening;   /* float32(-lr), float32(wd), float32(m), float32(1 - dampening) */
+    uint32_t flags;             /* OM_SGD_* */
+    uint32_t reserved[3];
+} om_sgd_tensor;
+typedef struct om_sgd_chunk {
+    int32_t tensor, chunk;
+} om_sgd_chunk;
+int om_sgd_step(const om_sgd_tensor* table_host, om_sgd_tensor* table, int n_tensors, const om_sgd_chunk* chunks, int n_chunks,
+                om_stream stream);
+
 /* ---- Several batches in flight.  Every entry point only enqueues kernels on the caller's stream and keeps no per-call state in
  *      the model handle (profiling apart): om_forward / om_forward_f16 / om_postprocess may be issued for different batches
  *      on different HIP streams at the same time, provided each batch in flight has its OWN workspace (and output buffers);

@@ -1,4 +1,4 @@
-"""The reference's type-keyed registry for the inference path.
+"""The reference's type-keyed registry for the inference path, and the optimizer of the training path.
 
 Mirrors /root/reference/trainer/builder.py:61-77: ``build(cfg, module)`` looks ``cfg['type']`` up in a
 module and calls it with the remaining keys; ``build_postprocess`` pops ``nms`` and injects the bound
@@ -70,3 +70,23 @@ def build_tester(config, checkpoint, test_loader, device=None, on_batch=None):
     model = build_model(train_config["model"], device, weights=state_dict)
     postprocess = build_postprocess(config["postprocess"], device=device)
     return Tester(model, postprocess, test_loader, device, on_batch=on_batch)
+
+
+def build_optimizer(config, accumulate, model, is_distributed=False):
+    """trainer/builder.py:118-130 against orienmask_amd.optim: the learning rate is divided by `accumulate`; an optional
+    `param_groups` entry is resolved by orienmask_amd.optim.param_groups with `base_lr` / `weight_decay` injected from the
+    optimizer's; a DistributedDataParallel wrapper is looked through (`.module`).  `config['type']` "SGD" is the HIP step, any
+    other torch.optim name is torch's.  The caller's dicts are not mutated."""
+    import copy
+    from . import optim as _optim
+    model = model.module if is_distributed else model
+    cfg = copy.deepcopy(config)
+    cfg["lr"] = cfg["lr"] / accumulate
+    groups_cfg = cfg.pop("param_groups", None)
+    if groups_cfg:
+        groups_cfg["base_lr"] = cfg["lr"]
+        groups_cfg["weight_decay"] = cfg["weight_decay"]
+        params = _optim.param_groups(model, **groups_cfg)
+    else:
+        params = [p for p in model.parameters() if p.requires_grad]
+    return build(cfg, _optim, params=params)

@@ -195,6 +195,7 @@ SIGNATURES = {
     "om_augment": (_i, [_vp, _i, _vp, _i, ctypes.POINTER(_f), ctypes.POINTER(_f), _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _sz, _vp]),
     "om_loss_backward": (_i, [ctypes.POINTER(LossCfg), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _i, _vp, _vp, _i, _vp, _vp, _sz, _vp,
                               ctypes.POINTER(_f), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp]),
+    "om_sgd_step": (_i, [_vp, _vp, _i, _vp, _i, _vp]),
 }
 
 _lib = None

@@ -1,0 +1,388 @@
+"""The reference's ``optim`` package on the HIP path: ``builder.build(config["lr_scheduler"], orienmask_amd.optim, ...)``.
+
+  SGD            torch.optim.SGD with the same constructor whose ``step()`` is ONE launch of om_sgd_step (csrc/optim.hip) over
+                 every tensor of every parameter group
+  param_groups   the reference's optim/param_groups.py: one group per parameter with its own lr / weight_decay
+  WarmupLR, PolyLR, StepWarmUpLR    the reference's optim/lr_scheduler.py
+  everything else of torch.optim and torch.optim.lr_scheduler, re-exported as the reference's package re-exports it, so any other
+  optimizer or scheduler type named in a config resolves to torch's.
+
+This is the swap of trainer/builder.py:35-36 (``optim_module``); orienmask_amd.builder.build_optimizer is :118-130.
+
+SGD is a subclass: ``param_groups``, ``state`` (``momentum_buffer`` per parameter), ``state_dict()`` / ``load_state_dict()``,
+``add_param_group``, ``zero_grad`` and torch's schedulers work as they are, and a checkpoint written by the reference's trainer
+resumes here and the other way round.  The arithmetic is torch.optim.SGD's in torch-CPU's float32 rounding, bit for bit
+(DESIGN.md section 3.16).  What the kernel does not take is refused: parameters that are not float32 tensors on a GPU, sparse
+gradients, ``differentiable=True``, a tensor ``lr``.  There is no eager fallback.
+
+How a step works.  Per device the optimizer keeps a table with one 64-byte row per parameter (pointers to parameter, gradient and
+momentum buffer, element count, float32 -lr / weight_decay / momentum / 1 - dampening, flags) and a chunk list built once from the
+element counts (``plan_chunks``), both resident on the device.  ``step()`` refreshes the host copy of the table (gradients may
+have been reallocated by ``zero_grad(set_to_none=True)``; a scheduler has usually changed lr), copies it into one of ``_RING``
+pinned staging buffers and hands that to om_sgd_step, which enqueues the host-to-device copy and the kernel on the current
+stream.  A staging buffer is reused only after the event recorded behind its copy has completed.  After a parameter's first step
+nothing is allocated and nothing is read back from the device.
+"""
+import ctypes as _ctypes
+
+import numpy as _np
+import torch as _torch
+from torch.optim import *                   # noqa: F401,F403  (the reference's optim/__init__.py:1)
+from torch.optim.lr_scheduler import *      # noqa: F401,F403  (optim/lr_scheduler.py:3)
+from torch.optim import SGD as _TorchSGD
+from torch.optim.lr_scheduler import LRScheduler as _LRScheduler, MultiStepLR as _MultiStepLR
+
+from . import lib as _lib
+
+OM_SGD_CHUNK = 4096         # include/orienmask_hip.h
+OM_SGD_SKIP, OM_SGD_FIRST, OM_SGD_NESTEROV, OM_SGD_MAXIMIZE, OM_SGD_HAS_MOMENTUM, OM_SGD_HAS_WD = 1, 2, 4, 8, 16, 32
+# om_sgd_tensor / om_sgd_chunk as numpy records
+TENSOR_ROW = _np.dtype([("param", "<u8"), ("grad", "<u8"), ("buf", "<u8"), ("n", "<i8"), ("neg_lr", "<f4"), ("weight_decay", "<f4"),
+                        ("momentum", "<f4"), ("one_minus_dampening", "<f4"), ("flags", "<u4"), ("reserved", "<u4", (3,))])
+assert TENSOR_ROW.itemsize == 64
+_RING = 4                   # pinned staging buffers per device
+
+
+def plan_chunks(counts):
+    """The work list of om_sgd_step for tensors of ``counts`` elements: int32 [n_chunks, 2] rows (tensor, chunk), tensor by
+    tensor; chunk k of a tensor covers its elements [k * OM_SGD_CHUNK, min(n, (k + 1) * OM_SGD_CHUNK))."""
+    counts = _np.asarray(counts, dtype=_np.int64).reshape(-1)
+    if counts.size == 0 or (counts <= 0).any():
+        raise ValueError("every tensor needs at least one element")
+    per = (counts + (OM_SGD_CHUNK - 1)) // OM_SGD_CHUNK
+    if int(per.max()) >= 2 ** 31 or int(per.sum()) >= 2 ** 31 or counts.size >= 2 ** 31:
+        raise ValueError("too many chunks for the 32-bit chunk list")
+    tensor = _np.repeat(_np.arange(counts.size, dtype=_np.int64), per)
+    first = _np.cumsum(per) - per
+    chunk = _np.arange(int(per.sum()), dtype=_np.int64) - _np.repeat(first, per)
+    return _np.ascontiguousarray(_np.stack([tensor, chunk], axis=1).astype(_np.int32))
+
+
+def chunk_ranges(plan, counts):
+    """(tensor, start, stop) of every row of ``plan`` as the kernel derives them."""
+    counts = _np.asarray(counts, dtype=_np.int64).reshape(-1)
+    tensor = plan[:, 0].astype(_np.int64)
+    start = plan[:, 1].astype(_np.int64) * OM_SGD_CHUNK
+    stop = _np.minimum(start + OM_SGD_CHUNK, counts[tensor])
+    return tensor, start, stop
+
+
+def _layout(t):
+    """Strides of the dimensions that have more than one element (the others do not place anything)."""
+    return tuple(st for sz, st in zip(t.shape, t.stride()) if sz != 1)
+
+
+def _is_dense(t):
+    """True when the tensor's elements fill numel() consecutive storage slots, each once (any permutation of a contiguous one)."""
+    expect = 1
+    for st, sz in sorted((st, sz) for sz, st in zip(t.shape, t.stride()) if sz != 1):
+        if st != expect:
+            return False
+        expect *= sz
+    return True
+
+
+def _check_param(p):
+    if not isinstance(p, _torch.Tensor):
+        raise TypeError("optimizer can only optimize Tensors, but one of the params is " + _torch.typename(p))
+    if not p.is_cuda or p.dtype != _torch.float32 or p.layout is not _torch.strided:
+        raise _lib.OrienMaskHipError("orienmask_amd.optim.SGD updates float32 tensors on an MI355X device; got %s %s on %s "
+                                     "(there is no CPU or eager fallback)" % (p.layout, p.dtype, p.device))
+    if p.numel() == 0:
+        raise _lib.OrienMaskHipError("orienmask_amd.optim.SGD: a parameter without elements")
+    if not _is_dense(p):
+        raise _lib.OrienMaskHipError("orienmask_amd.optim.SGD: a parameter must be dense in its storage (shape %s, strides %s)"
+                                     % (tuple(p.shape), p.stride()))
+
+
+class _Plan:
+    """One device's tables."""
+
+    def __init__(self, device, params, group_of):
+        self.device = device
+        self.params = params
+        self.group_of = group_of                          # slot -> index into optimizer.param_groups
+        n = len(params)
+        self.n = n
+        counts = [p.numel() for p in params]
+        self.layouts = [_layout(p) for p in params]
+        self.strides = [p.stride() for p in params]
+        self.rows = _np.zeros(n, dtype=TENSOR_ROW)
+        self.rows["n"] = counts
+        self.param_ptrs = [p.data_ptr() for p in params]
+        self.rows["param"] = self.param_ptrs
+        self.states = [None] * n                          # optimizer.state[p], once the parameter has one
+        self.bufs = [None] * n
+        self.base_flags = [0] * n
+        self.has_mom = [False] * n
+        self.hyper = {}                                   # group index -> the values its rows were written from
+        self.group_slots = {}
+        for i, g in enumerate(group_of):
+            self.group_slots.setdefault(g, []).append(i)
+        self.group_slots = {g: _np.asarray(s, dtype=_np.int64) for g, s in self.group_slots.items()}
+        chunks = plan_chunks(counts)
+        self.n_chunks = int(chunks.shape[0])
+        self.chunks = _torch.from_numpy(chunks).to(device)
+        self.table = _torch.empty(n * TENSOR_ROW.itemsize, dtype=_torch.uint8, device=device)
+        self.staging = [_torch.empty(n * TENSOR_ROW.itemsize, dtype=_torch.uint8).pin_memory() for _ in range(_RING)]
+        self.staging_rows = [s.numpy().view(TENSOR_ROW) for s in self.staging]
+        self.events = [_torch.cuda.Event() for _ in range(_RING)]
+        self.turn = 0
+        self.signature = [p.numel() for p in params]
+
+
+class SGD(_TorchSGD):
+    """torch.optim.SGD (same constructor, same state, same state_dict) whose step is one HIP launch; see the module docstring."""
+
+    def __init__(self, params, *args, **kwargs):
+        super().__init__(params, *args, **kwargs)
+        if self.defaults.get("differentiable"):
+            raise _lib.OrienMaskHipError("orienmask_amd.optim.SGD: differentiable=True is not supported (the step is a HIP kernel "
+                                         "outside autograd)")
+        self._plans = None
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        self._plans = None                                # load_state_dict replaces every state dict and momentum buffer
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        self._plans = None
+
+    def add_param_group(self, param_group):
+        if not isinstance(param_group, dict):
+            raise TypeError("param_group must be a dict, but got " + _torch.typename(param_group))
+        params = param_group["params"]
+        params = [params] if isinstance(params, _torch.Tensor) else list(params)
+        for p in params:
+            _check_param(p)
+        if param_group.get("differentiable", False):
+            raise _lib.OrienMaskHipError("orienmask_amd.optim.SGD: differentiable=True is not supported")
+        super().add_param_group(dict(param_group, params=params))
+        self._plans = None
+
+    # ---- tables -------------------------------------------------------------------------------------------------------------
+    def _structure(self):
+        return [len(g["params"]) for g in self.param_groups]
+
+    def _build_plans(self):
+        per_device = {}
+        for gi, group in enumerate(self.param_groups):
+            if group.get("differentiable", False):
+                raise _lib.OrienMaskHipError("orienmask_amd.optim.SGD: differentiable=True is not supported")
+            for p in group["params"]:
+                _check_param(p)
+                params, group_of = per_device.setdefault(p.device, ([], []))
+                params.append(p)
+                group_of.append(gi)
+        self._plans = [_Plan(dev, params, group_of) for dev, (params, group_of) in per_device.items()]
+        self._built_for = self._structure()
+
+    @staticmethod
+    def _write_hyper(plan, gi, key):
+        lr, wd, momentum, dampening, nesterov, maximize = key
+        for v, name in ((lr, "lr"), (wd, "weight_decay"), (momentum, "momentum"), (dampening, "dampening")):
+            if isinstance(v, _torch.Tensor):
+                raise _lib.OrienMaskHipError("orienmask_amd.optim.SGD: %s is a tensor; the step takes Python numbers (reading a "
+                                             "tensor back would synchronise)" % name)
+        slots = plan.group_slots[gi]
+        rows = plan.rows
+        rows["neg_lr"][slots] = -float(lr)
+        rows["weight_decay"][slots] = float(wd)
+        rows["momentum"][slots] = float(momentum)
+        rows["one_minus_dampening"][slots] = 1.0 - float(dampening)          # in double, rounded once (torch: alpha=1 - dampening)
+        flags = ((OM_SGD_NESTEROV if nesterov else 0) | (OM_SGD_MAXIMIZE if maximize else 0) |
+                 (OM_SGD_HAS_MOMENTUM if momentum != 0 else 0) | (OM_SGD_HAS_WD if wd != 0 else 0))
+        for i in slots.tolist():
+            plan.base_flags[i] = flags
+            plan.has_mom[i] = momentum != 0
+        plan.hyper[gi] = key
+
+    def _conform_grad(self, p, g):
+        """A gradient in the parameter's storage order (the kernel walks the three tensors element by element in that order)."""
+        if g.layout is not _torch.strided:
+            raise _lib.OrienMaskHipError("orienmask_amd.optim.SGD does not support sparse gradients (got %s)" % g.layout)
+        out = _torch.empty_like(p, requires_grad=False)                  # dense parameter: same strides
+        out.copy_(g)
+        return out
+
+    def _conform_buf(self, p, b):
+        if not isinstance(b, _torch.Tensor) or b.shape != p.shape:
+            raise _lib.OrienMaskHipError("orienmask_amd.optim.SGD: momentum_buffer does not match its parameter's shape")
+        if b.device != p.device or b.dtype != _torch.float32 or b.layout is not _torch.strided:
+            raise _lib.OrienMaskHipError("orienmask_amd.optim.SGD: momentum_buffer must be float32 on the parameter's device; got "
+                                         "%s on %s" % (b.dtype, b.device))
+        if _layout(b) != _layout(p):
+            nb = _torch.empty_like(p, requires_grad=False)
+            nb.copy_(b)
+            b = nb
+        return b
+
+    def _step_plan(self, plan, L):
+        groups = self.param_groups
+        for gi in plan.group_slots:
+            g = groups[gi]
+            key = (g["lr"], g["weight_decay"], g["momentum"], g["dampening"], g["nesterov"], g["maximize"])
+            if plan.hyper.get(gi) != key:
+                self._write_hyper(plan, gi, key)
+        params, layouts, strides, states, bufs, has_mom = plan.params, plan.layouts, plan.strides, plan.states, plan.bufs, plan.has_mom
+        rows = plan.rows
+        flags = list(plan.base_flags)
+        grad_ptrs = [0] * plan.n
+        keep = []
+        active = 0
+        for i, p in enumerate(params):
+            g = p.grad
+            if g is None:
+                flags[i] = OM_SGD_SKIP
+                continue
+            ptr = p.data_ptr()
+            if ptr != plan.param_ptrs[i]:                 # the parameter's data was replaced (p.data = ..., module.to(...))
+                _check_param(p)
+                if p.numel() != plan.signature[i]:
+                    self._plans = None
+                    raise _lib.OrienMaskHipError("orienmask_amd.optim.SGD: a parameter changed its element count; step again")
+                layouts[i] = _layout(p)
+                strides[i] = p.stride()
+                plan.param_ptrs[i] = ptr
+                rows["param"][i] = ptr
+            if g.layout is not _torch.strided or (g.stride() != strides[i] and _layout(g) != layouts[i]):
+                g = self._conform_grad(p, g)
+                keep.append(g)
+            grad_ptrs[i] = g.data_ptr()
+            if has_mom[i]:
+                st = states[i]
+                if st is None:
+                    st = states[i] = self.state[p]
+                b = st.get("momentum_buffer")
+                if b is None:
+                    b = _torch.empty_like(p, requires_grad=False)      # written, not read, by this step (OM_SGD_FIRST)
+                    st["momentum_buffer"] = b
+                    flags[i] |= OM_SGD_FIRST
+                    bufs[i] = None
+                if b is not bufs[i]:
+                    nb = self._conform_buf(p, b)
+                    if nb is not b:
+                        st["momentum_buffer"] = b = nb
+                    bufs[i] = b
+                    rows["buf"][i] = b.data_ptr()
+            active += 1
+        if active == 0:
+            return
+        rows["grad"] = grad_ptrs
+        rows["flags"] = flags
+        k = plan.turn
+        plan.turn = (k + 1) % _RING
+        ev = plan.events[k]
+        if not ev.query():
+            ev.synchronize()                              # the copy out of this staging buffer, _RING steps ago, has not run yet
+        plan.staging_rows[k][:] = rows
+        dev = plan.device
+        stream = _torch.cuda.current_stream(dev)
+        args = (_ctypes.c_void_p(plan.staging[k].data_ptr()), _ctypes.c_void_p(plan.table.data_ptr()), plan.n,
+                _ctypes.c_void_p(plan.chunks.data_ptr()), plan.n_chunks, _ctypes.c_void_p(stream.cuda_stream))
+        if _torch.cuda.current_device() == dev.index:
+            _lib.check(L.om_sgd_step(*args), "om_sgd_step")
+            ev.record(stream)
+        else:
+            with _torch.cuda.device(dev):
+                _lib.check(L.om_sgd_step(*args), "om_sgd_step")
+                ev.record(stream)
+        del keep
+
+    def step(self, closure=None):
+        """One optimization step; ``closure`` (optional) re-evaluates the model and returns the loss, as torch's does."""
+        loss = None
+        if closure is not None:
+            with _torch.enable_grad():
+                loss = closure()
+        L = _lib.load()
+        if getattr(self, "_plans", None) is None or self._built_for != self._structure():
+            self._build_plans()
+        with _torch.no_grad():
+            for plan in self._plans:
+                self._step_plan(plan, L)
+        return loss
+
+
+# ---- optim/param_groups.py ------------------------------------------------------------------------------------------------------
+_NORM_TYPES = (_torch.nn.BatchNorm1d, _torch.nn.BatchNorm2d, _torch.nn.BatchNorm3d, _torch.nn.SyncBatchNorm, _torch.nn.GroupNorm,
+               _torch.nn.InstanceNorm1d, _torch.nn.InstanceNorm2d, _torch.nn.InstanceNorm3d, _torch.nn.LayerNorm,
+               _torch.nn.LocalResponseNorm)
+
+
+def param_groups(model, base_lr=1e-3, weight_decay=1e-4, norm_weight_decay=0.0, bias_lr_factor=1.0, bias_weight_decay=1e-4):
+    """The reference's optim/param_groups.py: one ``{"params": [p], "lr", "weight_decay"}`` per trainable parameter, in
+    ``model.modules()`` order, a shared parameter once.  Parameters of normalisation modules get ``norm_weight_decay``; a parameter
+    named ``bias`` elsewhere gets ``base_lr * bias_lr_factor`` and ``bias_weight_decay``.
+
+    Kept, not repaired: the reference never resets the decay for the next parameter (optim/param_groups.py:32 assigns the
+    variable to itself), so the decay CARRIES OVER from one parameter to the next.  After the first normalisation module every
+    later convolution weight gets ``norm_weight_decay``, and after a bias the weights that follow get ``bias_weight_decay``, until
+    the next norm or bias changes it again.  conv / BatchNorm / conv with bias / conv gives decays weight_decay, norm, norm, norm,
+    bias (the bias), bias.  This returns what the reference returns (tests/golden/optim_param_groups.npz), as aug_crop_quirk does
+    for the crop."""
+    groups = []
+    seen = set()
+    decay = weight_decay                                  # carried from parameter to parameter (see above)
+    for module in model.modules():
+        is_norm = isinstance(module, _NORM_TYPES)
+        for name, value in module.named_parameters(recurse=False):
+            if not value.requires_grad or value in seen:
+                continue
+            seen.add(value)
+            lr = base_lr
+            if is_norm:
+                decay = norm_weight_decay
+            elif name == "bias":
+                lr = base_lr * bias_lr_factor
+                decay = bias_weight_decay
+            groups.append({"params": [value], "lr": lr, "weight_decay": decay})
+    return groups
+
+
+# ---- optim/lr_scheduler.py ------------------------------------------------------------------------------------------------------
+class WarmupLR:
+    """optim/lr_scheduler.py:7-21: the warm-up learning rate at iteration ``iters`` of ``warmup_iter``, in double."""
+
+    def __init__(self, warmup_type, warmup_iter, warmup_ratio):
+        if warmup_type not in ("const", "linear", "power"):
+            raise AssertionError("warmup_type must be 'const', 'linear' or 'power', got %r" % (warmup_type,))
+        self.type = warmup_type
+        self.iter = warmup_iter
+        self.ratio = warmup_ratio
+
+    def get_warmup_lr(self, iters, base_lr):
+        if self.type == "const":
+            return base_lr * self.ratio
+        if self.type == "linear":
+            return base_lr * (self.ratio + (1 - self.ratio) * iters / self.iter)
+        return base_lr * ((iters / self.iter) ** self.ratio)
+
+
+class PolyLR(_LRScheduler):
+    """optim/lr_scheduler.py:24-32: base_lr * (1 - last_epoch / max_iter) ** power."""
+
+    def __init__(self, optimizer, max_iter, power=0.9, last_epoch=-1):
+        self.max_iter = max_iter
+        self.power = power
+        super().__init__(optimizer, last_epoch)
+
+    def get_lr(self):
+        import math
+        return [base_lr * math.pow(1 - self.last_epoch / self.max_iter, self.power) for base_lr in self.base_lrs]
+
+
+class StepWarmUpLR(_MultiStepLR):
+    """optim/lr_scheduler.py:35-48: the warm-up rate while last_epoch <= warmup_iter, torch's MultiStepLR after it (its chained
+    form: the rate the optimizer holds, times gamma at a milestone -- so the rate after the warm-up is the LAST warm-up rate,
+    which is base_lr for 'linear' and 'power' and base_lr * warmup_ratio for 'const', as in the reference)."""
+
+    def __init__(self, warmup_type, warmup_iter, warmup_ratio, optimizer, milestones, gamma=0.1, last_epoch=-1):
+        self.warmup = WarmupLR(warmup_type, warmup_iter, warmup_ratio)
+        super().__init__(optimizer, milestones, gamma, last_epoch)
+
+    def get_lr(self):
+        if self.last_epoch > self.warmup.iter:
+            return super().get_lr()
+        return [self.warmup.get_warmup_lr(self.last_epoch, base_lr) for base_lr in self.base_lrs]

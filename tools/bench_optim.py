@@ -1,0 +1,129 @@
+"""Time one optimizer step on the model's 266 parameter tensors (63,662,063 float32 elements): orienmask_amd.optim.SGD (one launch
+of om_sgd_step, csrc/optim.hip) against torch.optim.SGD on the same tensors on the same GPU -- its single-tensor loop
+(foreach=False), its default (foreach) and fused=True where this torch offers it -- as ONE parameter group and as 266 groups with
+the lr / weight_decay split of param_groups.  torch is the baseline: the parent commit has no optimizer.
+
+Method: momentum 0.9 and weight decay, so a step reads parameter, gradient and momentum buffer and writes parameter and buffer
+(5 x 4 bytes per element = 1.27 GB).  Every variant is warmed up, then timed in ROUNDS interleaved rounds (variant after variant
+inside a round, so drift hits all alike); a round times INNER back-to-back steps between two HIP events on the current stream
+and divides.  Reported per variant: median, min and max of the rounds' per-step times, the spread (max - min) / median, the
+bytes per second at the median, and the host time per step (what the Python side of step() costs; where it exceeds the device
+time the event figure is host-bound and says so).  The device clock is read before and after where the runtime exposes it.
+
+    python tools/bench_optim.py [--rounds 15] [--inner 20] [--warmup 5]
+
+prints one JSON line.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.dont_write_bytecode = True
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+import torch  # noqa: E402
+
+from orienmask_amd import optim as O  # noqa: E402
+from orienmask_amd.model import OrienMaskYOLOFPNPlus  # noqa: E402
+
+HYPER = dict(lr=1e-3, momentum=0.9, weight_decay=5e-4)
+SPLIT = dict(base_lr=1e-3, weight_decay=5e-4, norm_weight_decay=0.0, bias_lr_factor=2.0, bias_weight_decay=1e-4)
+
+
+def clock_mhz():
+    try:
+        return int(torch.cuda.clock_rate())
+    except Exception:
+        return None
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=15)
+    ap.add_argument("--inner", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_optim.py needs an MI355X: there is nothing to time on a CPU")
+    dev = torch.device("cuda:0")
+    net = OrienMaskYOLOFPNPlus(num_anchors=3, num_classes=80, pretrained=None, freeze_backbone=False, backbone_batchnorm_eval=False)
+    cpu_params = list(net.parameters())
+    for p in cpu_params:
+        p.requires_grad_(True)                                # the inference model holds its weights frozen
+    index = {id(p): i for i, p in enumerate(cpu_params)}
+    split = [None] * len(cpu_params)
+    for g in O.param_groups(net, **SPLIT):
+        split[index[id(g["params"][0])]] = (g["lr"], g["weight_decay"])
+    gen = torch.Generator(device=dev).manual_seed(0)
+    shapes = [tuple(p.shape) for p in cpu_params]
+    elements = sum(p.numel() for p in cpu_params)
+    del net, cpu_params
+    grads = [torch.randn(s, device=dev, generator=gen) * 1e-2 for s in shapes]
+
+    def fresh_params():
+        ps = [torch.nn.Parameter(torch.randn(s, device=dev, generator=gen) * 0.05) for s in shapes]
+        for p, g in zip(ps, grads):
+            p.grad = g
+        return ps
+
+    def groups(ps, per_tensor):
+        if not per_tensor:
+            return ps
+        return [{"params": [p], "lr": lr, "weight_decay": wd} for p, (lr, wd) in zip(ps, split)]
+
+    variants = {}
+    skipped = {}
+    for per_tensor, tag in ((False, "1group"), (True, "266groups")):
+        variants["hip_" + tag] = O.SGD(groups(fresh_params(), per_tensor), **HYPER)
+        variants["torch_single_" + tag] = torch.optim.SGD(groups(fresh_params(), per_tensor), foreach=False, **HYPER)
+        variants["torch_foreach_" + tag] = torch.optim.SGD(groups(fresh_params(), per_tensor), **HYPER)
+        try:
+            opt = torch.optim.SGD(groups(fresh_params(), per_tensor), fused=True, **HYPER)
+            opt.step()
+            torch.cuda.synchronize()
+            variants["torch_fused_" + tag] = opt
+        except Exception as e:                                # this torch build has no fused SGD on this device
+            skipped["torch_fused_" + tag] = "%s: %s" % (type(e).__name__, str(e)[:200])
+
+    for opt in variants.values():
+        for _ in range(args.warmup):
+            opt.step()
+    torch.cuda.synchronize()
+    clock_before = clock_mhz()
+    dev_ms = {k: [] for k in variants}
+    host_ms = {k: [] for k in variants}
+    for _ in range(args.rounds):
+        for name, opt in variants.items():
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            start.record()
+            for _ in range(args.inner):
+                opt.step()
+            stop.record()
+            t1 = time.perf_counter()
+            stop.synchronize()
+            dev_ms[name].append(start.elapsed_time(stop) / args.inner)
+            host_ms[name].append((t1 - t0) * 1e3 / args.inner)
+    clock_after = clock_mhz()
+    nbytes = 5 * 4 * elements
+    out = {"bench": "optim_step", "tensors": len(shapes), "elements": elements, "bytes_per_step": nbytes, "rounds": args.rounds,
+           "inner": args.inner, "warmup": args.warmup, "device": torch.cuda.get_device_name(0), "torch": torch.__version__,
+           "clock_mhz_before": clock_before, "clock_mhz_after": clock_after, "floor_ms_at_6.3TBps": nbytes / 6.3e12 * 1e3,
+           "variants": {}, "skipped": skipped}
+    for name in variants:
+        v = sorted(dev_ms[name])
+        med = statistics.median(v)
+        out["variants"][name] = {"ms_median": round(med, 4), "ms_min": round(v[0], 4), "ms_max": round(v[-1], 4),
+                                 "spread_pct": round(100 * (v[-1] - v[0]) / med, 1), "GBps_at_median": round(nbytes / med / 1e6, 1),
+                                 "host_ms_median": round(statistics.median(host_ms[name]), 4),
+                                 "host_bound": statistics.median(host_ms[name]) > 0.9 * med}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
