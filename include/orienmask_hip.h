@@ -715,6 +715,34 @@ typedef struct om_sgd_chunk {
 int om_sgd_step(const om_sgd_tensor* table_host, om_sgd_tensor* table, int n_tensors, const om_sgd_chunk* chunks, int n_chunks,
                 om_stream stream);
 
+/* ---- The Conv -> BatchNorm2d -> LeakyReLU(0.1) block of the reference without its convolution (model/base.py:104-137,278-279: the
+ *      nn.BatchNorm2d and nn.LeakyReLU of ConvBNRelu.conv_block), optionally with the residual add that closes a DarkNet block
+ *      (model/backbone/darknet.py:14-15 `x + self.conv(x)`), for the training forward of trainer/trainer.py:47 and its backward (:52).
+ *      x, y, residual, dy, dx: fp32 NCHW contiguous [B,C,H,W]; gamma, beta and the running buffers: C floats; save_mean and
+ *      save_invstd: 2C floats each, [0,C) the float32 value (what torch reports) and [C,2C) the float32 remainder of the double the
+ *      kernels computed with, so that the backward rebuilds z with the forward's bits.  Every element-wise intermediate is a double;
+ *      each output is rounded to float32 once.
+ *      Forward, training != 0: per-channel batch mean and biased variance (every element accumulated in double around the channel's
+ *      first element, never E[x^2] - E[x]^2), save_mean / save_invstd = 1 / sqrt(var + eps) written, running_mean and running_var
+ *      (unbiased variance) updated with `momentum` and *num_batches_tracked incremented on the device as torch.nn.BatchNorm2d does
+ *      (each of the three may be null); needs B*H*W >= 2.  training == 0: the running statistics normalise, no buffer changes,
+ *      save_mean / save_invstd receive what was used.  Then z = fma(x - mean, gamma * invstd, beta), y = z > 0 ? z : z * slope,
+ *      plus residual[i] when residual is not null.
+ *      Backward: z is recomputed from x with the same expression; dz = dy * (z > 0 ? 1 : slope); dbeta = sum dz; dgamma = sum dz * xhat;
+ *      dx = gamma * invstd * (dz - dbeta / M - xhat * dgamma / M) with M = B*H*W (training) or gamma * invstd * dz (eval); dx may be
+ *      null (the input needs no gradient): only the sums are computed.  The residual's gradient is dy itself.
+ *      One launch where a channel has at most 16384 elements, else two (per-workgroup partial sums in `workspace`, summed in a fixed
+ *      order by the second): no atomics, bit-identical from run to run, no allocation, no host synchronisation.  workspace: the
+ *      number of bytes the size query returns for the shape (0 for a shape that is refused), 16-byte aligned, undefined on entry. */
+size_t om_bn_act_workspace_bytes(int B, int C, int H, int W);
+int om_bn_act_forward(const float* x, int B, int C, int H, int W, const float* gamma, const float* beta, float* running_mean,
+                      float* running_var, int64_t* num_batches_tracked, int training, double momentum, double eps, float slope,
+                      const float* residual, float* y, float* save_mean, float* save_invstd, void* workspace, size_t ws_bytes,
+                      om_stream stream);
+int om_bn_act_backward(const float* x, const float* dy, int B, int C, int H, int W, const float* gamma, const float* beta,
+                       const float* save_mean, const float* save_invstd, int training, float slope, float* dx, float* dgamma,
+                       float* dbeta, void* workspace, size_t ws_bytes, om_stream stream);
+
 /* ---- Several batches in flight.  Every entry point only enqueues kernels on the caller's stream and keeps no per-call state in
  *      the model handle (profiling apart): om_forward / om_forward_f16 / om_postprocess may be issued for different batches
  *      on different HIP streams at the same time, provided each batch in flight has its OWN workspace (and output buffers);

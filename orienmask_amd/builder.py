@@ -90,3 +90,19 @@ def build_optimizer(config, accumulate, model, is_distributed=False):
     else:
         params = [p for p in model.parameters() if p.requires_grad]
     return build(cfg, _optim, params=params)
+
+
+def build_train_model(config, is_distributed=False, ignore_pretrained=False):
+    """trainer/builder.py:80-88 against orienmask_amd.train: the model of config (a reference `model` dict, optionally with
+    `backend`) on the current device, in training mode as a freshly built nn.Module is.  The caller's dict is not mutated.
+    is_distributed=True raises: the reference converts to SyncBatchNorm there (statistics reduced across ranks), which the HIP
+    block does not do."""
+    import torch
+    from . import train as _train
+    if is_distributed:
+        raise NotImplementedError("build_train_model(is_distributed=True): SyncBatchNorm / DistributedDataParallel are not supported")
+    cfg = dict(config)
+    if ignore_pretrained:
+        cfg["pretrained"] = None
+    net = build(cfg, _train)
+    return net.to(torch.device("cuda", torch.cuda.current_device()))

@@ -1,0 +1,446 @@
+// The part of the reference's Conv -> BatchNorm2d -> LeakyReLU(0.1) block that is not the convolution (model/base.py:104-137,
+// 278-279; 88 of the network's 90 convolutions), with the residual add of a DarkNet block (model/backbone/darknet.py:14-15), for
+// TRAINING: batch statistics, the running-buffer update, and the backward.  fp32 NCHW contiguous, as torch's convolution leaves it.
+//   bn_fwd_kernel   phase STATS   per-workgroup partial sums of a channel           -> workspace
+//                   phase APPLY   finalise the channel, write save_mean / save_invstd / running buffers, y = leaky(z) (+ residual)
+//                   phase FUSED   both in one launch, one workgroup per channel (small layers are launch-bound)
+//                   phase EVAL    APPLY with the running statistics; no buffer changes
+//   bn_bwd_kernel   the same three phases for (sum dz, sum dz * (x - mean)) and dx; the LeakyReLU mask is recomputed from x
+// A channel is B planes of H*W floats.  Work is counted in UNITS of V floats (V = 4 where H*W is a multiple of 4 and every tensor is
+// 16-byte aligned, else 1): unit u of channel c lies in plane u / (HW/V), so a unit never straddles planes and one 32-bit division
+// serves 16 bytes.  A workgroup takes tiles of BN_THREADS * BN_UNROLL units, strided by the number of workgroups of its channel,
+// and issues the BN_UNROLL loads of every stream before it uses one.
+// Arithmetic: every element is widened to double, every intermediate is a double, and each output is rounded to float32 once (the
+// vector double rate is far above what a pass at memory speed needs).  The forward's sums are taken around a shift K (the channel's
+// first element), so the variance is sum((x-K)^2) - sum(x-K)^2/n on numbers of the size of the spread, never E[x^2] - E[x]^2.
+// Per-thread sums -> wave shuffles -> four LDS slots -> per-workgroup partials in the caller's workspace -> one fixed-order sum per
+// channel: no atomics, the same bits on every run.  Compiled with -ffp-contract=off: z = fma(x - mean, gamma * invstd, beta) is
+// written out once and is the SAME expression, on the same doubles, in the forward and in the backward's mask.
+#include "om_common.h"
+
+namespace om {
+
+constexpr int BN_THREADS = 256;
+constexpr int BN_UNROLL = 4;                      // loads in flight per thread and stream
+constexpr int BN_TILE = BN_THREADS * BN_UNROLL;   // units per tile
+constexpr int BN_MAX_BLOCKS = 2048;               // 256 CUs x 8 workgroups
+constexpr long long BN_FUSED_MAX = 16384;         // elements per channel up to which one workgroup does the whole channel
+
+enum { BN_STATS = 0, BN_APPLY = 1, BN_FUSED = 2, BN_EVAL = 3 };
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+struct BnGeom {
+    int C;
+    unsigned plane_units;      // H*W / V
+    unsigned units;            // B * plane_units: units per channel
+    unsigned n_tiles;          // ceil(units / BN_TILE)
+    double n;                  // elements per channel
+};
+
+struct BnFwdArgs {
+    const float* x; const float* gamma; const float* beta; const float* residual;
+    float* running_mean; float* running_var; long long* num_batches_tracked;
+    float* y; float* save_mean; float* save_invstd;
+    double* partial;           // [C][splits][2]
+    int splits;                // workgroups per channel that wrote partials
+    double momentum, eps;
+    float slope;
+};
+
+struct BnBwdArgs {
+    const float* x; const float* dy; const float* gamma; const float* beta; const float* save_mean; const float* save_invstd;
+    float* dx; float* dgamma; float* dbeta;
+    double* partial;
+    int splits;
+    int training;
+    float slope;
+};
+
+template <int V>
+__device__ __forceinline__ void load_unit(const float* __restrict__ p, size_t idx, float (&o)[V]) {
+    if constexpr (V == 4) {
+        const f32x4 t = reinterpret_cast<const f32x4*>(p)[idx];
+        o[0] = t[0]; o[1] = t[1]; o[2] = t[2]; o[3] = t[3];
+    } else {
+        o[0] = p[idx];
+    }
+}
+
+template <int V>
+__device__ __forceinline__ void store_unit(float* __restrict__ p, size_t idx, const float (&o)[V]) {
+    if constexpr (V == 4) {
+        reinterpret_cast<f32x4*>(p)[idx] = f32x4{o[0], o[1], o[2], o[3]};
+    } else {
+        p[idx] = o[0];
+    }
+}
+
+// index, in units, of unit u of channel c
+__device__ __forceinline__ size_t unit_index(const BnGeom& g, int c, unsigned u) {
+    const unsigned b = u / g.plane_units, p = u - b * g.plane_units;
+    return ((size_t)b * g.C + c) * g.plane_units + p;
+}
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
+
+// (a, b) summed over the workgroup in a fixed order; every thread returns with the totals
+__device__ __forceinline__ void block_sum2(double& a, double& b, double* lds) {
+    a = wave_sum(a);
+    b = wave_sum(b);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    __syncthreads();            // the slots may still be read from the previous call
+    if (lane == 0) { lds[2 * w] = a; lds[2 * w + 1] = b; }
+    __syncthreads();
+    a = (lds[0] + lds[2]) + (lds[4] + lds[6]);
+    b = (lds[1] + lds[3]) + (lds[5] + lds[7]);
+}
+
+// the channel's partials, written by `splits` workgroups, summed in a fixed order
+__device__ __forceinline__ void sum_partials(const double* __restrict__ partial, int c, int splits, double& a, double& b, double* lds) {
+    a = 0.0; b = 0.0;
+    for (int i = threadIdx.x; i < splits; i += BN_THREADS) {
+        a += partial[((size_t)c * splits + i) * 2];
+        b += partial[((size_t)c * splits + i) * 2 + 1];
+    }
+    block_sum2(a, b, lds);
+}
+
+// What the element-wise passes know about a channel, in double.  mean and invstd are carried as float32 pairs (value, remainder) in
+// the save vectors, so the backward rebuilds exactly the doubles the forward used and z has the same bits in both.
+struct BnChannel {
+    double mean, invstd, w, beta;      // w = gamma * invstd
+};
+
+__device__ __forceinline__ void split_hi_lo(double v, float& hi, float& lo) {
+    hi = (float)v;
+    lo = (float)(v - (double)hi);
+}
+
+__device__ __forceinline__ BnChannel bn_channel(float mean_hi, float mean_lo, float invstd_hi, float invstd_lo, float gamma, float beta) {
+    BnChannel ch;
+    ch.mean = (double)mean_hi + (double)mean_lo;
+    ch.invstd = (double)invstd_hi + (double)invstd_lo;
+    ch.w = (double)gamma * ch.invstd;
+    ch.beta = (double)beta;
+    return ch;
+}
+
+// z = gamma * xhat + beta: THE expression of the forward and of the backward's mask (one fma on exact operands)
+__device__ __forceinline__ double bn_z(float x, const BnChannel& ch) { return fma((double)x - ch.mean, ch.w, ch.beta); }
+
+// ---------------------------------------------------------------------------------------------------------------- forward
+template <int V>
+__device__ __forceinline__ void fwd_sums(const BnFwdArgs& a, const BnGeom& g, int c, int s, int S, float K, double& s1, double& s2) {
+    s1 = 0.0; s2 = 0.0;
+    const double Kd = (double)K;
+    for (unsigned tile = s; tile < g.n_tiles; tile += S) {
+        float v[BN_UNROLL][V];
+        bool ok[BN_UNROLL];
+#pragma unroll
+        for (int k = 0; k < BN_UNROLL; ++k) {
+            const unsigned u = tile * BN_TILE + k * BN_THREADS + threadIdx.x;
+            ok[k] = u < g.units;
+            if (ok[k]) load_unit<V>(a.x, unit_index(g, c, u), v[k]);
+        }
+#pragma unroll
+        for (int k = 0; k < BN_UNROLL; ++k) {
+            if (!ok[k]) continue;
+#pragma unroll
+            for (int e = 0; e < V; ++e) {
+                const double d = (double)v[k][e] - Kd;
+                s1 += d;
+                s2 = fma(d, d, s2);
+            }
+        }
+    }
+}
+
+template <int V>
+__device__ __forceinline__ void fwd_apply(const BnFwdArgs& a, const BnGeom& g, int c, int s, int S, const BnChannel& ch) {
+    const bool has_res = a.residual != nullptr;
+    const double slope = (double)a.slope;
+    for (unsigned tile = s; tile < g.n_tiles; tile += S) {
+        float v[BN_UNROLL][V], r[BN_UNROLL][V];
+        size_t idx[BN_UNROLL];
+        bool ok[BN_UNROLL];
+#pragma unroll
+        for (int k = 0; k < BN_UNROLL; ++k) {
+            const unsigned u = tile * BN_TILE + k * BN_THREADS + threadIdx.x;
+            ok[k] = u < g.units;
+            if (ok[k]) {
+                idx[k] = unit_index(g, c, u);
+                load_unit<V>(a.x, idx[k], v[k]);
+                if (has_res) load_unit<V>(a.residual, idx[k], r[k]);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < BN_UNROLL; ++k) {
+            if (!ok[k]) continue;
+            float o[V];
+#pragma unroll
+            for (int e = 0; e < V; ++e) {
+                const double z = bn_z(v[k][e], ch);
+                double y = z > 0.0 ? z : z * slope;
+                if (has_res) y = y + (double)r[k][e];
+                o[e] = (float)y;                                // the only rounding to float32
+            }
+            store_unit<V>(a.y, idx[k], o);
+        }
+    }
+}
+
+template <int V>
+__global__ void __launch_bounds__(BN_THREADS) bn_fwd_kernel(BnFwdArgs a, BnGeom g, int phase) {
+    __shared__ double lds[8];
+    const int s = blockIdx.x, S = gridDim.x, c = blockIdx.y;
+    float mean_hi, mean_lo = 0.f, invstd_hi, invstd_lo;
+    if (phase == BN_EVAL) {
+        mean_hi = a.running_mean[c];
+        split_hi_lo(1.0 / sqrt((double)a.running_var[c] + a.eps), invstd_hi, invstd_lo);
+    } else {
+        const float K = a.x[(size_t)c * g.plane_units * V];      // the channel's first element (image 0)
+        double s1, s2;
+        if (phase == BN_APPLY) {
+            sum_partials(a.partial, c, a.splits, s1, s2, lds);
+        } else {
+            fwd_sums<V>(a, g, c, s, S, K, s1, s2);
+            block_sum2(s1, s2, lds);
+            if (phase == BN_STATS) {
+                if (threadIdx.x == 0) {
+                    a.partial[((size_t)c * S + s) * 2] = s1;
+                    a.partial[((size_t)c * S + s) * 2 + 1] = s2;
+                }
+                return;
+            }
+        }
+        const double shifted = s1 / g.n;
+        const double mean_d = (double)K + shifted;
+        double var_d = (s2 - s1 * shifted) / g.n;               // biased
+        if (var_d < 0.0) var_d = 0.0;
+        split_hi_lo(mean_d, mean_hi, mean_lo);
+        split_hi_lo(1.0 / sqrt(var_d + a.eps), invstd_hi, invstd_lo);
+        if (s == 0 && threadIdx.x == 0) {
+            if (a.running_mean) a.running_mean[c] = (float)(a.momentum * mean_d + (1.0 - a.momentum) * (double)a.running_mean[c]);
+            if (a.running_var) {
+                const double unbiased = var_d * (g.n / (g.n - 1.0));
+                a.running_var[c] = (float)(a.momentum * unbiased + (1.0 - a.momentum) * (double)a.running_var[c]);
+            }
+            if (c == 0 && a.num_batches_tracked) *a.num_batches_tracked += 1;
+        }
+    }
+    if (s == 0 && threadIdx.x == 0) {
+        a.save_mean[c] = mean_hi;   a.save_mean[g.C + c] = mean_lo;
+        a.save_invstd[c] = invstd_hi; a.save_invstd[g.C + c] = invstd_lo;
+    }
+    const BnChannel ch = bn_channel(mean_hi, mean_lo, invstd_hi, invstd_lo, a.gamma[c], a.beta[c]);
+    fwd_apply<V>(a, g, c, s, S, ch);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- backward
+template <int V>
+__device__ __forceinline__ void bwd_sums(const BnBwdArgs& a, const BnGeom& g, int c, int s, int S, const BnChannel& ch, double& sb,
+                                         double& sg) {
+    sb = 0.0; sg = 0.0;
+    const double slope = (double)a.slope;
+    for (unsigned tile = s; tile < g.n_tiles; tile += S) {
+        float v[BN_UNROLL][V], d[BN_UNROLL][V];
+        bool ok[BN_UNROLL];
+#pragma unroll
+        for (int k = 0; k < BN_UNROLL; ++k) {
+            const unsigned u = tile * BN_TILE + k * BN_THREADS + threadIdx.x;
+            ok[k] = u < g.units;
+            if (ok[k]) {
+                const size_t idx = unit_index(g, c, u);
+                load_unit<V>(a.x, idx, v[k]);
+                load_unit<V>(a.dy, idx, d[k]);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < BN_UNROLL; ++k) {
+            if (!ok[k]) continue;
+#pragma unroll
+            for (int e = 0; e < V; ++e) {
+                const double z = bn_z(v[k][e], ch);
+                const double dz = z > 0.0 ? (double)d[k][e] : (double)d[k][e] * slope;
+                sb += dz;
+                sg = fma(dz, (double)v[k][e] - ch.mean, sg);
+            }
+        }
+    }
+}
+
+template <int V>
+__device__ __forceinline__ void bwd_apply(const BnBwdArgs& a, const BnGeom& g, int c, int s, int S, const BnChannel& ch, double c1,
+                                          double c2) {
+    const double slope = (double)a.slope;
+    for (unsigned tile = s; tile < g.n_tiles; tile += S) {
+        float v[BN_UNROLL][V], d[BN_UNROLL][V];
+        size_t idx[BN_UNROLL];
+        bool ok[BN_UNROLL];
+#pragma unroll
+        for (int k = 0; k < BN_UNROLL; ++k) {
+            const unsigned u = tile * BN_TILE + k * BN_THREADS + threadIdx.x;
+            ok[k] = u < g.units;
+            if (ok[k]) {
+                idx[k] = unit_index(g, c, u);
+                load_unit<V>(a.x, idx[k], v[k]);
+                load_unit<V>(a.dy, idx[k], d[k]);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < BN_UNROLL; ++k) {
+            if (!ok[k]) continue;
+            float o[V];
+#pragma unroll
+            for (int e = 0; e < V; ++e) {
+                const double xm = (double)v[k][e] - ch.mean;
+                const double z = fma(xm, ch.w, ch.beta);        // bn_z, with x - mean shared
+                const double dz = z > 0.0 ? (double)d[k][e] : (double)d[k][e] * slope;
+                const double t = fma(-xm, c2, dz - c1);
+                o[e] = (float)(t * ch.w);
+            }
+            store_unit<V>(a.dx, idx[k], o);
+        }
+    }
+}
+
+template <int V>
+__global__ void __launch_bounds__(BN_THREADS) bn_bwd_kernel(BnBwdArgs a, BnGeom g, int phase) {
+    __shared__ double lds[8];
+    const int s = blockIdx.x, S = gridDim.x, c = blockIdx.y;
+    const BnChannel ch = bn_channel(a.save_mean[c], a.save_mean[g.C + c], a.save_invstd[c], a.save_invstd[g.C + c], a.gamma[c], a.beta[c]);
+    double sb, sg;
+    if (phase == BN_APPLY) {
+        sum_partials(a.partial, c, a.splits, sb, sg, lds);
+    } else {
+        bwd_sums<V>(a, g, c, s, S, ch, sb, sg);
+        block_sum2(sb, sg, lds);
+        if (phase == BN_STATS) {
+            if (threadIdx.x == 0) {
+                a.partial[((size_t)c * S + s) * 2] = sb;
+                a.partial[((size_t)c * S + s) * 2 + 1] = sg;
+            }
+            return;
+        }
+    }
+    // sg = sum dz * (x - mean): dgamma = sg * invstd, and xhat * dgamma / M = (x - mean) * (sg * invstd^2 / M)
+    if (s == 0 && threadIdx.x == 0) {
+        a.dbeta[c] = (float)sb;
+        a.dgamma[c] = (float)(sg * ch.invstd);
+    }
+    if (!a.dx) return;
+    const double c1 = a.training ? sb / g.n : 0.0;
+    const double c2 = a.training ? sg * ch.invstd * ch.invstd / g.n : 0.0;
+    bwd_apply<V>(a, g, c, s, S, ch, c1, c2);
+}
+
+// workgroups per channel for the two-launch form
+static int bn_splits(unsigned n_tiles, int C) {
+    int per = BN_MAX_BLOCKS / C;
+    if (per < 1) per = 1;
+    return (unsigned)per < n_tiles ? per : (int)n_tiles;
+}
+
+static bool bn_geometry(int B, int C, int H, int W, int V, BnGeom* g) {
+    const long long hw = (long long)H * W, m = hw * B;
+    if (B < 1 || C < 1 || C > 65535 || H < 1 || W < 1 || m >= (1ll << 31) - BN_TILE) return false;
+    g->C = C;
+    g->plane_units = (unsigned)(hw / V);
+    g->units = (unsigned)(m / V);
+    g->n_tiles = (g->units + BN_TILE - 1) / BN_TILE;
+    g->n = (double)m;
+    return true;
+}
+
+static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+}  // namespace om
+
+extern "C" {
+
+size_t om_bn_act_workspace_bytes(int B, int C, int H, int W) {
+    om::BnGeom g;
+    if (!om::bn_geometry(B, C, H, W, 1, &g)) return 0;
+    return (size_t)C * om::bn_splits(g.n_tiles, C) * 2 * sizeof(double);
+}
+
+int om_bn_act_forward(const float* x, int B, int C, int H, int W, const float* gamma, const float* beta, float* running_mean,
+                      float* running_var, int64_t* num_batches_tracked, int training, double momentum, double eps, float slope,
+                      const float* residual, float* y, float* save_mean, float* save_invstd, void* workspace, size_t ws_bytes,
+                      om_stream stream) {
+    OM_REQUIRE(x && gamma && beta && y && save_mean && save_invstd, OM_EINVAL, "om_bn_act_forward: null pointer");
+    OM_REQUIRE(y != x && y != residual, OM_EINVAL, "om_bn_act_forward: y must not alias x or the residual (x is what the backward reads)");
+    OM_REQUIRE(training || (running_mean && running_var), OM_EINVAL, "om_bn_act_forward: eval mode needs the running statistics");
+    OM_REQUIRE(eps > 0.0 && momentum >= 0.0 && momentum <= 1.0, OM_EINVAL, "om_bn_act_forward: eps %g, momentum %g", eps, momentum);
+    const bool vec = ((long long)H * W) % 4 == 0 && om::aligned16(x) && om::aligned16(y) && om::aligned16(residual);
+    om::BnGeom g;
+    OM_REQUIRE(om::bn_geometry(B, C, H, W, vec ? 4 : 1, &g), OM_EINVAL, "om_bn_act_forward: shape [%d,%d,%d,%d] (C <= 65535, B*H*W < 2^31)",
+               B, C, H, W);
+    OM_REQUIRE(!training || g.n >= 2.0, OM_EINVAL,
+               "om_bn_act_forward: training needs more than 1 value per channel, got shape [%d,%d,%d,%d]", B, C, H, W);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    om::BnFwdArgs a;
+    a.x = x; a.gamma = gamma; a.beta = beta; a.residual = residual;
+    a.running_mean = running_mean; a.running_var = running_var; a.num_batches_tracked = reinterpret_cast<long long*>(num_batches_tracked);
+    a.y = y; a.save_mean = save_mean; a.save_invstd = save_invstd;
+    a.partial = static_cast<double*>(workspace); a.splits = 0;
+    a.momentum = momentum; a.eps = eps; a.slope = slope;
+    const int S = om::bn_splits(g.n_tiles, C);
+    auto launch = [&](int splits, int phase) {
+        if (vec) hipLaunchKernelGGL(om::bn_fwd_kernel<4>, dim3(splits, C), dim3(om::BN_THREADS), 0, st, a, g, phase);
+        else hipLaunchKernelGGL(om::bn_fwd_kernel<1>, dim3(splits, C), dim3(om::BN_THREADS), 0, st, a, g, phase);
+    };
+    if (!training) {
+        launch(S, om::BN_EVAL);
+    } else if (g.n <= (double)om::BN_FUSED_MAX || S == 1) {
+        launch(1, om::BN_FUSED);
+    } else {
+        OM_REQUIRE(workspace && om::aligned16(workspace) && ws_bytes >= (size_t)C * S * 2 * sizeof(double), OM_EINVAL,
+                   "om_bn_act_forward: workspace of %zu bytes, need %zu (16-byte aligned)", ws_bytes, (size_t)C * S * 2 * sizeof(double));
+        a.splits = S;
+        launch(S, om::BN_STATS);
+        launch(S, om::BN_APPLY);
+    }
+    OM_CHECK_HIP(hipGetLastError());
+    return OM_OK;
+}
+
+int om_bn_act_backward(const float* x, const float* dy, int B, int C, int H, int W, const float* gamma, const float* beta,
+                       const float* save_mean, const float* save_invstd, int training, float slope, float* dx, float* dgamma,
+                       float* dbeta, void* workspace, size_t ws_bytes, om_stream stream) {
+    OM_REQUIRE(x && dy && gamma && beta && save_mean && save_invstd && dgamma && dbeta, OM_EINVAL, "om_bn_act_backward: null pointer");
+    OM_REQUIRE(dx != x, OM_EINVAL, "om_bn_act_backward: dx must not alias x");
+    const bool vec = ((long long)H * W) % 4 == 0 && om::aligned16(x) && om::aligned16(dy) && om::aligned16(dx);
+    om::BnGeom g;
+    OM_REQUIRE(om::bn_geometry(B, C, H, W, vec ? 4 : 1, &g), OM_EINVAL, "om_bn_act_backward: shape [%d,%d,%d,%d] (C <= 65535, B*H*W < 2^31)",
+               B, C, H, W);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    om::BnBwdArgs a;
+    a.x = x; a.dy = dy; a.gamma = gamma; a.beta = beta; a.save_mean = save_mean; a.save_invstd = save_invstd;
+    a.dx = dx; a.dgamma = dgamma; a.dbeta = dbeta;
+    a.partial = static_cast<double*>(workspace); a.splits = 0;
+    a.training = training ? 1 : 0; a.slope = slope;
+    const int S = om::bn_splits(g.n_tiles, C);
+    auto launch = [&](int splits, int phase) {
+        if (vec) hipLaunchKernelGGL(om::bn_bwd_kernel<4>, dim3(splits, C), dim3(om::BN_THREADS), 0, st, a, g, phase);
+        else hipLaunchKernelGGL(om::bn_bwd_kernel<1>, dim3(splits, C), dim3(om::BN_THREADS), 0, st, a, g, phase);
+    };
+    if (g.n <= (double)om::BN_FUSED_MAX || S == 1) {
+        launch(1, om::BN_FUSED);
+    } else {
+        OM_REQUIRE(workspace && om::aligned16(workspace) && ws_bytes >= (size_t)C * S * 2 * sizeof(double), OM_EINVAL,
+                   "om_bn_act_backward: workspace of %zu bytes, need %zu (16-byte aligned)", ws_bytes, (size_t)C * S * 2 * sizeof(double));
+        a.splits = S;
+        launch(S, om::BN_STATS);
+        launch(dx ? S : 1, om::BN_APPLY);       // without dx only the per-channel sums are finalised
+    }
+    OM_CHECK_HIP(hipGetLastError());
+    return OM_OK;
+}
+
+}  // extern "C"

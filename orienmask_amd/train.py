@@ -12,16 +12,34 @@ backward follows the reference's autograd chain in torch-CPU's float32 order (cs
 enqueues two kernels on the current stream and never synchronises with the host: the upstream gradient is read on the device.
 Each call that builds a graph owns its workspace (the match records om_loss_backward reads) and result vector until the graph is
 freed, so several losses may be computed before one ``backward()``.
+
+And the reference's model in training mode: ``builder.build(config["model"], orienmask_amd.train)`` (trainer/builder.py:84).
+
+  ConvBNLeaky                  the reference's Conv -> BatchNorm2d -> LeakyReLU(0.1) block (model/base.py:104-137,278-279) with
+                               trainable parameters: torch's convolution, then BatchNorm + LeakyReLU (+ the DarkNet residual add)
+                               as om_bn_act_forward / om_bn_act_backward (csrc/bn_act.hip) under autograd
+  OrienMaskYOLOFPNPlus         the reference's two models (model/orienmask_yolo_fpnplus.py, model/orienmask_yolo.py) built from
+  OrienMaskYOLO                arch.model_convs, with the reference's state_dict keys and parameter order
+
+The convolutions, forward and gradients, are torch's; the up-sampling, cat and split stay torch ops.
 """
+import contextlib
 import ctypes
 
 import torch
+import torch.nn as nn
+import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
+from torch.nn.modules.batchnorm import _BatchNorm
 
 from . import lib as _lib
+from . import pack as _pack
+from .arch import DARKNET_STAGES, LEAKY_SLOPE, model_convs
 from .loss import EvalCounter, OrienMaskYOLOMultiScaleLoss as _ValuesLoss
 
-__all__ = ["OrienMaskYOLOMultiScaleLoss", "EvalCounter"]
+__all__ = ["OrienMaskYOLOMultiScaleLoss", "EvalCounter", "ConvBNLeaky", "bn_leaky", "OrienMaskYOLOFPNPlus", "OrienMaskYOLO"]
+
+BACKENDS = ("hip", "torch")
 
 
 class _LossBackward(torch.autograd.Function):
@@ -119,3 +137,270 @@ class OrienMaskYOLOMultiScaleLoss(_ValuesLoss):
         call.loss_sum = loss_sum
         out = _LossBackward.apply(call, *flat)
         return out, loss_log, metric_log
+
+
+# ---------------------------------------------------------------------------------------------------------------- the model
+def _vp(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+_WORKSPACES = {}
+_NO_SWITCH = contextlib.nullcontext()
+
+
+def _device(dev):
+    """The launches go to the tensors' device: switch only when it is not the current one (the switch costs as much as a launch)."""
+    return _NO_SWITCH if torch.cuda.current_device() == dev.index else torch.cuda.device(dev)
+
+
+def _workspace(dev, stream, nbytes):
+    """The partial-sum workspace of (device, stream): the second launch of a call consumes what the first wrote, and calls on one
+    stream are ordered, so a stream's calls share one grow-only buffer; another stream has its own."""
+    key = (dev, stream.value)
+    ws = _WORKSPACES.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, device=dev)
+        _WORKSPACES[key] = ws
+    return ws
+
+
+class _BNAct(torch.autograd.Function):
+    """forward(ctx, x, gamma, beta, residual, bn, slope) -> leaky(batch_norm(x)) (+ residual): om_bn_act_forward.  `bn` is the
+    nn.BatchNorm2d whose buffers the kernel updates in training mode and reads in eval mode.  Saved for the backward: x, gamma, beta
+    and one per-channel buffer the forward wrote (save_mean and save_invstd, 2C floats each); the LeakyReLU mask is recomputed from
+    x (om_bn_act_backward)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, residual, bn, slope):
+        B, C, H, W = x.shape
+        dev = x.device
+        L = _lib.load()
+        training = bool(bn.training or bn.running_mean is None)
+        y = torch.empty_like(x)
+        save = torch.empty(4 * C, dtype=torch.float32, device=dev)      # save_mean | save_invstd (include/orienmask_hip.h)
+        track = training and bn.running_mean is not None
+        stream = _lib.current_stream_ptr(dev)
+        ws = _workspace(dev, stream, L.om_bn_act_workspace_bytes(B, C, H, W))
+        with _device(dev):
+            _lib.check(L.om_bn_act_forward(
+                _vp(x), B, C, H, W, _vp(gamma), _vp(beta), _vp(bn.running_mean), _vp(bn.running_var),
+                _vp(bn.num_batches_tracked) if track else None, 1 if training else 0, float(bn.momentum), float(bn.eps),
+                float(slope), _vp(residual), _vp(y), save.data_ptr(), save.data_ptr() + 8 * C, ws.data_ptr(), ws.numel(), stream),
+                "om_bn_act_forward")
+        ctx.save_for_backward(x, gamma, beta, save)
+        ctx.training, ctx.slope, ctx.has_residual = training, float(slope), residual is not None
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        x, gamma, beta, save = ctx.saved_tensors
+        B, C, H, W = x.shape
+        dev = x.device
+        L = _lib.load()
+        dy = dy.contiguous()
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        dgb = torch.empty((2, C), dtype=torch.float32, device=dev)
+        stream = _lib.current_stream_ptr(dev)
+        ws = _workspace(dev, stream, L.om_bn_act_workspace_bytes(B, C, H, W))
+        with _device(dev):
+            _lib.check(L.om_bn_act_backward(
+                _vp(x), _vp(dy), B, C, H, W, _vp(gamma), _vp(beta), save.data_ptr(), save.data_ptr() + 8 * C, 1 if ctx.training else 0,
+                ctx.slope, _vp(dx), dgb.data_ptr(), dgb.data_ptr() + 4 * C, ws.data_ptr(), ws.numel(), stream), "om_bn_act_backward")
+        return (dx, dgb[0] if ctx.needs_input_grad[1] else None, dgb[1] if ctx.needs_input_grad[2] else None,
+                dy if ctx.has_residual and ctx.needs_input_grad[3] else None, None, None)
+
+
+def bn_leaky(x, bn, residual=None, slope=LEAKY_SLOPE):
+    """leaky_relu(bn(x), slope) (+ residual) as the HIP block: `bn` is an nn.BatchNorm2d in training or eval mode, x (and residual)
+    CUDA float32 NCHW-contiguous; anything else raises."""
+    _lib.require_cuda_tensor(x, "the BatchNorm input (backend 'hip')", torch.float32)
+    if bn.momentum is None:
+        raise ValueError("bn_leaky: momentum=None (a cumulative moving average) is not supported")
+    if x.dim() != 4 or not x.is_contiguous():
+        raise _lib.OrienMaskHipError("backend 'hip' takes NCHW-contiguous [B,C,H,W] activations, got strides %s for shape %s"
+                                     % (x.stride(), tuple(x.shape)))
+    if (bn.training or bn.running_mean is None) and x.numel() // x.shape[1] <= 1:
+        raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(x.shape),))
+    if residual is not None:
+        _lib.require_cuda_tensor(residual, "residual", torch.float32)
+        if residual.shape != x.shape or not residual.is_contiguous():
+            raise _lib.OrienMaskHipError("residual must be NCHW-contiguous with the block's output shape %s, got %s strides %s"
+                                         % (tuple(x.shape), tuple(residual.shape), residual.stride()))
+    return _BNAct.apply(x, bn.weight, bn.bias, residual, bn, slope)
+
+
+class ConvBNLeaky(nn.Module):
+    """The reference's conv_bn_leaky block (model/base.py:104-137,278-279) with its sub-structure and keys: conv_block.0 the
+    bias-free nn.Conv2d, conv_block.1 the nn.BatchNorm2d, conv_block.2 the LeakyReLU(0.1).  forward(x, residual=None) returns
+    leaky(bn(conv(x))) + residual.
+
+    backend 'hip' (default): F.conv2d, then BatchNorm + LeakyReLU + residual as one HIP block under autograd (csrc/bn_act.hip);
+    CUDA float32 tensors only -- anything else raises, there is no fallback.  backend 'torch': F.conv2d -> F.batch_norm ->
+    F.leaky_relu, the comparator, and the only path that takes CPU tensors.  The block normalises with batch statistics while
+    its BatchNorm module is in training mode and with the running statistics otherwise (model.eval(), backbone_batchnorm_eval)."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, backend="hip"):
+        super().__init__()
+        if backend not in BACKENDS:
+            raise ValueError("backend must be one of %s, got %r" % (BACKENDS, backend))
+        self.backend = backend
+        self.conv_block = nn.Sequential(
+            nn.Conv2d(in_channels, out_channels, kernel_size, stride=stride, padding=padding, bias=False),
+            nn.BatchNorm2d(out_channels),
+            nn.LeakyReLU(negative_slope=LEAKY_SLOPE, inplace=True))
+
+    def forward(self, x, residual=None):
+        conv, bn, act = self.conv_block[0], self.conv_block[1], self.conv_block[2]
+        if bn.momentum is None:
+            raise ValueError("ConvBNLeaky: momentum=None (a cumulative moving average) is not supported")
+        h = F.conv2d(x, conv.weight, None, conv.stride, conv.padding)
+        training = bn.training or bn.running_mean is None
+        if training and h.numel() // h.shape[1] <= 1:
+            raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(h.shape),))
+        if self.backend == "torch":
+            y = F.batch_norm(h, bn.running_mean, bn.running_var, bn.weight, bn.bias, training, bn.momentum, bn.eps)
+            if training and bn.num_batches_tracked is not None:
+                bn.num_batches_tracked.add_(1)
+            y = F.leaky_relu(y, act.negative_slope, inplace=True)
+            return y if residual is None else y + residual
+        return bn_leaky(h, bn, residual=residual, slope=act.negative_slope)
+
+
+class _Container(nn.Module):
+    """Holds sub-modules under the reference's names; the model's forward addresses them by name."""
+
+
+class _Backbone(_Container):
+    """BaseBackbone.train (model/base.py:71-77): with batchnorm_eval the BatchNorm modules stay in eval mode."""
+
+    def __init__(self, batchnorm_eval):
+        super().__init__()
+        self.batchnorm_eval = batchnorm_eval
+
+    def train(self, mode=True):
+        super().train(mode)
+        if mode and self.batchnorm_eval:
+            for m in self.modules():
+                if isinstance(m, _BatchNorm):
+                    m.eval()
+        return self
+
+
+class OrienMaskYOLOFPNPlus(nn.Module):
+    """The reference's OrienMaskYOLOFPNPlus (model/orienmask_yolo_fpnplus.py:9-90) for training: the same constructor arguments
+    plus `backend` ('hip' / 'torch', see ConvBNLeaky), the same state_dict keys and parameters() order as the reference and as
+    orienmask_amd.model (checkpoints and optimizer state move in both directions), trainable parameters, and a forward that
+    returns the reference's ((bbox32, orien32), (bbox16, orien16), (bbox8, orien8)) with a graph behind it."""
+
+    def __init__(self, num_anchors, num_classes, pretrained=None, freeze_backbone=False, backbone_batchnorm_eval=False,
+                 backend="hip"):
+        super().__init__()
+        if freeze_backbone is not False:
+            # the reference's DarkNet53._freeze_network calls self._freeze_module, which does not exist (darknet.py:31-38)
+            raise NotImplementedError("freeze_backbone=%r: the reference's own _freeze_network cannot run; not supported" % (freeze_backbone,))
+        if backend not in BACKENDS:
+            raise ValueError("backend must be one of %s, got %r" % (BACKENDS, backend))
+        self.num_anchors = num_anchors
+        self.num_classes = num_classes
+        self.pretrained = pretrained
+        self.freeze_backbone = freeze_backbone
+        self.backbone_batchnorm_eval = backbone_batchnorm_eval
+        self.backend = backend
+        self.backbone = _Backbone(backbone_batchnorm_eval)
+        self._plus = type(self).__name__ == "OrienMaskYOLOFPNPlus"
+        self._by_name = {}
+        for spec in model_convs(type(self).__name__, num_anchors, num_classes):
+            *path, leaf = spec.name.split(".")
+            node = self
+            for p in path:
+                if p not in node._modules:
+                    node.add_module(p, _Container())
+                node = node._modules[p]
+            pad = spec.ksize // 2
+            if spec.bn:
+                m = ConvBNLeaky(spec.cin, spec.cout, spec.ksize, stride=spec.stride, padding=pad, backend=backend)
+            else:
+                m = nn.Conv2d(spec.cin, spec.cout, spec.ksize, stride=spec.stride, padding=pad)
+            node.add_module(leaf, m)
+            self._by_name[spec.name] = m
+        if pretrained is not None:
+            self._load_pretrained_backbone(pretrained)
+        self._init_weights()
+
+    def _init_weights(self):
+        """model/base.py:26-32: BatchNorm outside the backbone starts at gamma 1, beta 0."""
+        for name, module in self.named_modules():
+            if "backbone" in name:
+                continue
+            if isinstance(module, _BatchNorm):
+                nn.init.ones_(module.weight)
+                nn.init.zeros_(module.bias)
+
+    def _load_pretrained_backbone(self, path):
+        """As orienmask_amd.model loads it (BaseBackbone._load_pretrained_weights, model/base.py:48-64): backbone-relative keys;
+        keys that are missing or of another shape are ignored and reported.  Returns the ignored keys."""
+        import warnings
+        sd = _pack.unwrap_checkpoint(torch.load(path, map_location="cpu", weights_only=False))
+        own = self.backbone.state_dict()
+        picked = {k: v for k, v in sd.items() if k in own and tuple(v.shape) == tuple(own[k].shape)}
+        ignored = [k for k in sd if k not in picked]
+        if not picked:
+            warnings.warn("pretrained file %s: none of its %d keys matches the backbone (expected backbone-relative keys such "
+                          "as 'conv1.conv_block.0.weight'); the model keeps its initialisation" % (path, len(sd)))
+        elif ignored:
+            warnings.warn("pretrained file %s: ignored keys %s" % (path, ignored[:8] + (["..."] if len(ignored) > 8 else [])))
+        own.update(picked)
+        self.backbone.load_state_dict(own)
+        return ignored
+
+    # ------------------------------------------------------------------ forward
+    def _run(self, prefix, x, n=5):
+        for i in range(n):
+            x = self._by_name["%s.%d" % (prefix, i)](x)
+        return x
+
+    def _route(self, name, x, up):
+        x = self._by_name[name](x)
+        return F.interpolate(x, scale_factor=up, mode="nearest") if up > 1 else x
+
+    def _backbone_forward(self, x):
+        """model/backbone/darknet.py:47-54 with the blocks of :14-15."""
+        m = self._by_name
+        x = m["backbone.conv1"](x)
+        feats = {}
+        for idx, _, nblocks in DARKNET_STAGES:
+            stage = "backbone.conv%d" % idx
+            x = m[stage + ".0"](x)
+            for j in range(1, nblocks + 1):
+                h = m["%s.%d.conv.0" % (stage, j)](x)
+                x = m["%s.%d.conv.1" % (stage, j)](h, residual=x)
+            feats[idx] = x
+        return feats[6], feats[5], feats[4], feats[3]
+
+    def _bbox_head(self, s, x):
+        return self._by_name["bbox_head%d.1" % s](self._by_name["bbox_head%d.0" % s](x))
+
+    def forward(self, x):
+        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] % 32 or x.shape[3] % 32:
+            raise ValueError("x must be [B,3,H,W] with H and W multiples of 32, got %s" % (tuple(x.shape),))
+        x32, x16, x8, x4 = self._backbone_forward(x)
+        neck32 = self._run("neck32", x32)
+        neck16 = self._run("neck16", torch.cat([self._route("route32.0", neck32, 2), x16], dim=1))
+        neck8 = self._run("neck8", torch.cat([self._route("route16.0", neck16, 2), x8], dim=1))
+        bbox32 = self._bbox_head(32, neck32)
+        bbox16 = self._bbox_head(16, neck16)
+        bbox8 = self._bbox_head(8, neck8)
+        if self._plus:
+            cat4 = [self._route("skip32.0", neck32, 8), self._route("skip16.0", neck16, 4), self._route("skip8.0", neck8, 2),
+                    self._route("skip4", x4, 1)]
+        else:
+            cat4 = [self._route("route8.0", neck8, 2), x4]
+        oriens = self._run("neck4", torch.cat(cat4, dim=1))
+        oriens = self._by_name["orien_head.5"](self._run("orien_head", oriens))
+        orien32, orien16, orien8 = torch.split(oriens, self.num_anchors * 2, dim=1)
+        return (bbox32, orien32), (bbox16, orien16), (bbox8, orien8)
+
+
+class OrienMaskYOLO(OrienMaskYOLOFPNPlus):
+    """The reference's non-Plus model (model/orienmask_yolo.py:8-86): route8 and x4 feed a 192-channel neck4."""

@@ -484,9 +484,64 @@ def preprocess_golden():
     print("preprocess: %d cases, %.0f KB" % (len(cases), os.path.getsize(os.path.join(OUT, "preprocess.npz")) / 1024))
 
 
+def train_step_golden():
+    """G9: one training step of the reference model on CPU (model.train(); tests/golden/train_step_*.npz): the six heads, every
+    BatchNorm layer's buffers after the step, the gradient of a fixed seeded cotangent on the heads (tests/bn_act_np.py: cotangents)
+    with respect to every parameter as float64 sum and L2 norm, in full for bn_act_np.GRAD_NAMES; once more with
+    backbone_batchnorm_eval=True.  Weights and image are fwd_f96_b2's, regenerated from the stored seeds.  And the reference's
+    state_dict keys and named_parameters() names, in order, for both model types (model_keys.npz)."""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import bn_act_np as N
+    cfg, rmodel, reval, rfunc = import_reference()
+    torch.set_num_threads(8)
+    wseed, xseed, gseed, size, batch, obj_bias, head_gain = 1, 21, 71, (96, 96), 2, -22.0, 4.0
+    sd = synth.synth_state_dict(wseed, obj_bias=obj_bias, head_gain=head_gain)
+    x = synth.synth_image_batch(xseed, batch, size[0], size[1])
+    for name, bneval in (("train_step_f96_b2", False), ("train_step_bneval_f96_b2", True)):
+        net = rmodel.OrienMaskYOLOFPNPlus(num_anchors=3, num_classes=80, pretrained=None, backbone_batchnorm_eval=bneval)
+        net.load_state_dict(sd, strict=True)
+        net.train()
+        out = net(x)
+        heads = [t for pair in out for t in pair]
+        cot = N.cotangents(gseed, [t.shape for t in heads])
+        torch.autograd.backward(heads, [torch.from_numpy(c) for c in cot])
+        rec = dict(size=np.array(size), batch=np.int64(batch), wseed=np.int64(wseed), xseed=np.int64(xseed), gseed=np.int64(gseed),
+                   obj_bias=np.float32(obj_bias), head_gain=np.float32(head_gain), bneval=np.int64(bneval))
+        for k, t in zip(N.HEAD_KEYS, heads):
+            assert torch.isfinite(t).all(), k
+            rec[k] = t.detach().numpy()
+        after = net.state_dict()
+        bn_keys = [k for k in after if k.endswith("running_mean")]
+        rec["bn_layers"] = np.array([k[:-len(".running_mean")] for k in bn_keys])
+        rec["running_mean"] = np.concatenate([after[k].numpy().ravel() for k in bn_keys])
+        rec["running_var"] = np.concatenate([after[k[:-4] + "var"].numpy().ravel() for k in bn_keys])
+        rec["num_batches_tracked"] = np.array([int(after[k[:-len("running_mean")] + "num_batches_tracked"]) for k in bn_keys])
+        names = [n for n, _ in net.named_parameters()]
+        rec["param_names"] = np.array(names)
+        g64 = [p.grad.double() for _, p in net.named_parameters()]
+        rec["grad_sum"] = np.array([g.sum().item() for g in g64])
+        rec["grad_l2"] = np.array([g.norm().item() for g in g64])
+        params = dict(net.named_parameters())
+        for i, n in enumerate(N.GRAD_NAMES):
+            rec["grad_%d" % i] = params[n].grad.numpy()
+        path = os.path.join(OUT, name + ".npz")
+        np.savez_compressed(path, **rec)
+        print(name, "%.0f KB" % (os.path.getsize(path) / 1024), "tracked", sorted(set(rec["num_batches_tracked"].tolist())),
+              "|grad| range %.3g .. %.3g" % (rec["grad_l2"].min(), rec["grad_l2"].max()))
+    rec = {}
+    for model in ("OrienMaskYOLOFPNPlus", "OrienMaskYOLO"):
+        net = getattr(rmodel, model)(num_anchors=3, num_classes=80, pretrained=None)
+        rec[model + "_state_dict"] = np.array(list(net.state_dict()))
+        rec[model + "_parameters"] = np.array([n for n, _ in net.named_parameters()])
+    np.savez_compressed(os.path.join(OUT, "model_keys.npz"), **rec)
+    print("model_keys: %.0f KB" % (os.path.getsize(os.path.join(OUT, "model_keys.npz")) / 1024))
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "preprocess":
         preprocess_golden()
+    elif len(sys.argv) > 1 and sys.argv[1] == "train":
+        train_step_golden()
     elif len(sys.argv) > 1 and sys.argv[1] == "yolo":
         yolo_golden()
     elif len(sys.argv) > 1 and sys.argv[1] == "coco":
@@ -502,3 +557,4 @@ if __name__ == "__main__":
         preprocess_golden()
         stress_golden()
         trained_golden()
+        train_step_golden()
