@@ -266,10 +266,14 @@ static TileChoiceH choose_tile_f16(int M, int cout_pad) {
     return best;
 }
 
-void conv_tile_for_f16(int M, int cout_pad, int cin, int* bm, int* bn) {
+void conv_tile_for_f16(int M, int cout_pad, int cin, int* bm, int* bn, bool gather) {
     (void)cin;
     const TileChoiceH t = choose_tile_f16(M, cout_pad);
     *bm = t.bm; *bn = t.bn;
+    if (gather) {      // the gathered-input forms that are built: 256 x 128 and 128 x 128 (cout_pad % 128 == 0)
+        if (!(*bm == 256 && *bn == 128)) *bm = 128;
+        *bn = 128;
+    }
 }
 
 template <int BM, int BN, int WM, int WN, bool GATHER = false>
@@ -334,7 +338,7 @@ int launch_conv_igemm_f16(const ConvArgsH& a, hipStream_t stream) {
     p.nseg = 0; p.nimg = a.B;
     for (int g = 0; g < 4; ++g) { p.seg_ptr[g] = p.in; p.seg_stride[g] = 0; p.seg_shift[g] = 0; p.seg_end[g] = 0x7FFFFFFF; }
     int bm, bn;
-    conv_tile_for_f16(p.M, a.cout_pad, a.cin, &bm, &bn);
+    conv_tile_for_f16(p.M, a.cout_pad, a.cin, &bm, &bn, a.nseg > 0);
     if (a.nseg > 0) {
         // gathered input: 1x1, whole 32-channel chunks per segment, every segment's resolution a power-of-two fraction of this one
         OM_REQUIRE(a.nseg <= 4 && a.ks == 1 && a.stride == 1 && a.cout_pad % 128 == 0, OM_EINVAL,

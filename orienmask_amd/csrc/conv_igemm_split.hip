@@ -932,7 +932,8 @@ static int launch_tile_split(IgemmSParams p, int cout_pad, int blocks_per_cu, hi
     return OM_OK;
 }
 
-void conv_tile_for_split(int M, int cout_pad, int* bm, int* bn) {
+void conv_tile_for_split(int M, int cout_pad, int* bm, int* bn, bool gather) {
+    if (gather) { *bm = 128; *bn = 128; return; }      // the one gathered-input form that is built (cout_pad % 128 == 0)
     // time over all tiles ~ tiles x tile area / how well the shape feeds the pipe (tools/split_tile_sweep.py on the forward's
     // layer shapes: 128 x 128 is the fastest wherever cout allows it, 256 x 128 -- two workgroups per CU, 256 registers -- 9 %
     // behind, then 128 x 64, 64 x 64, 128 x 32)
@@ -1018,10 +1019,11 @@ int launch_conv_igemm_split(const ConvArgs& a, hipStream_t stream) {
         OM_REQUIRE(end * 32 == a.cin, OM_EINVAL, "conv split: the segments hold %d channels, the layer reads %d", end * 32, a.cin);
         p.nseg = a.nseg;
         p.in = p.seg_ptr[0];
-        return launch_tile_split<128, 128, 64, 64, true, true>(p, a.cout_pad, 2, stream);
     }
     int bm, bn;
-    conv_tile_for_split(p.M, a.cout_pad, &bm, &bn);
+    conv_tile_for_split(p.M, a.cout_pad, &bm, &bn, a.nseg > 0);
+    OM_REQUIRE(a.nseg == 0 || (bm == 128 && bn == 128), OM_EINVAL, "conv split: no gathered-input kernel with a %d x %d tile", bm, bn);
+    if (a.nseg > 0) return launch_tile_split<128, 128, 64, 64, true, true>(p, a.cout_pad, 2, stream);
     if (a.force_bm || a.force_bn) {      // unit-test entry: this call's tile shape
         const bool built = (a.force_bm == 256 && a.force_bn == 128) || (a.force_bm == 128 && (a.force_bn == 128 || a.force_bn == 64 || a.force_bn == 32)) ||
                            (a.force_bm == 64 && a.force_bn == 64);

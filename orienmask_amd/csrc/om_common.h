@@ -75,7 +75,7 @@ constexpr size_t SK_PARTIAL_BYTES = (size_t)512 * 32 * 256 * 16;   // Winograd F
 int launch_conv_igemm(const ConvArgs& a, hipStream_t stream);
 // split-operand form (conv_igemm_split.hip): a.w = packed hi/lo fp16 weights, a.scale = scale * 2^-e
 int launch_conv_igemm_split(const ConvArgs& a, hipStream_t stream);
-void conv_tile_for_split(int M, int cout_pad, int* bm, int* bn);
+void conv_tile_for_split(int M, int cout_pad, int* bm, int* bn, bool gather = false);      // gather: a.nseg > 0
 
 // fp16-activation path (conv_igemm_f16.hip): in / w / res are fp16, scale / shift fp32, out fp16 unless out_f32.
 struct ConvArgsH {
@@ -106,7 +106,7 @@ bool conv3x3_f16_supported(const ConvArgsH& a);
 void conv3x3_tile_for_f16(int M, int cout_pad, int W, int kc, int* bm, int* bn);
 int conv3x3_f16_get_tall();
 void conv3x3_f16_set_tall(int mode);      // conv3x3_f16.hip: 0 never / 1 where the tile chooser picks it (default) / 2 wherever it can run
-void conv_tile_for_f16(int M, int cout_pad, int cin, int* bm, int* bn);
+void conv_tile_for_f16(int M, int cout_pad, int cin, int* bm, int* bn, bool gather = false);      // gather: a.nseg > 0
 inline size_t conv_f16_weight_halfs(int cout_pad, int ks, int cin) {
     return (size_t)cout_pad * ks * ks * cin;
 }

@@ -61,18 +61,80 @@ struct LayerDef {
     std::vector<Seg> gather;
 };
 
+// The kernel form that runs one layer of one forward: om_model::plan() picks it, om_layer_tile / om_layer_tile_f16 report it as
+// their `algo` code (algo_code below; include/orienmask_hip.h has the table), launch_layer launches it.
+enum class Form {
+    Stem,                                       // conv_stem.hip (fp32 or fp16 output)
+    Stem2Split, Stem3Split, Stem2F16,           // conv_stem2.hip: the stem and the next layer (Stem3Split: the next two) as one kernel
+    InPrevious,                                 // ... and those layers themselves: nothing to launch
+    Igemm,                                      // conv_igemm.hip, fp32 operands
+    Split, SplitGather, SplitDirect3x3,         // conv_igemm_split.hip: plain / input up-sampled on read / a stride-1 3x3 layer (latency mode)
+    Wino, WinoFused, Wino24,                    // conv_wino.hip F(2x2): transform + GEMM / transform in the GEMM's loader; conv_wino24.hip F(2x4)
+    Wino14, Wino14Wide,                         // conv_wino14.hip, split operands: fused F(4,3) / V pre-pass + 128 x 128 tile kernel
+    IgemmF16, IgemmF16Gather,                   // conv_igemm_f16.hip: plain / input up-sampled on read
+    Conv3x3F16, Conv3x3F16Tall,                 // conv3x3_f16.hip and its tall-patch form
+};
+
+struct LayerPlan {
+    Form form = Form::Stem;
+    int bm = 0, bn = 0;             // the tile om_layer_tile reports (0 x 0: no tile queue)
+    size_t scratch_floats = 0;      // Winograd scratch the workspace reserves for this layer
+    enum Blob { F32, SPLIT, F16 } blob = F32;      // the weights are at w_off of om_model::weights / weights_split / weights16 ...
+    int64_t w_off = -1, scale_off = -1;            // ... the scales at scale_off of weights_split (SPLIT) or weights (F32, F16)
+    int ksplit_max = 0;             // ConvArgs::ksplit_max
+    bool to_side = false;           // the output goes, once and not up-sampled, to the layer's `side` buffer
+    bool gather = false;            // the input is the layer's gather table
+};
+
+static int algo_code(Form f, bool f16) {
+    switch (f) {
+        case Form::Stem: return 0;
+        case Form::Igemm: case Form::IgemmF16: return 1;
+        case Form::Wino: return 2;
+        case Form::WinoFused: return 3;
+        case Form::Conv3x3F16: return 4;
+        case Form::Wino24: case Form::IgemmF16Gather: return 5;
+        case Form::Conv3x3F16Tall: return 6;
+        case Form::Split: case Form::SplitDirect3x3: case Form::Stem2F16: return 7;
+        case Form::Wino14: return 8;
+        case Form::Stem2Split: case Form::Stem3Split: return 9;
+        case Form::InPrevious: return f16 ? 8 : 10;
+        case Form::SplitGather: return 11;
+        case Form::Wino14Wide: return 12;
+    }
+    return -1;
+}
+
+// The shape, stride and mode fields of one launch (ConvArgs or ConvArgsH)
+template <class Args>
+static void fill_conv_shape(Args& a, int B, int H, int W, int cin, int in_pix_stride, int cout, int cout_pad, int ks, int stride, int leaky,
+                            int res_pix_stride, int out_pix_stride, int out_mode = 0, int up = 1) {
+    a.B = B; a.H = H; a.W = W; a.cin = cin; a.in_pix_stride = in_pix_stride;
+    a.Ho = H / stride; a.Wo = W / stride; a.cout = cout; a.cout_pad = cout_pad;
+    a.ks = ks; a.stride = stride; a.leaky = leaky; a.res_pix_stride = res_pix_stride;
+    a.out_pix_stride = out_pix_stride; a.out_mode = out_mode; a.up = up;
+}
+
 }  // namespace om
 
-// process-wide A/B switch (default on; om_set_wino14_wide, or OM_NO_W14_WIDE=1 in the environment read once): om_forward runs the
-// stride-1 3x3 layers with at least 512 input channels of precision mode 1 in the two-kernel wide form (conv_wino14.hip:
-// wino14_v_kernel + wino14_wide_kernel); off: the fused kernel everywhere.  Bit-identical either way.
-static int g_wino14_wide = -1;
-static bool wino14_wide_on() {
-    if (g_wino14_wide < 0) {
-        const char* e = std::getenv("OM_NO_W14_WIDE");
-        g_wino14_wide = (e && e[0] == '1') ? 0 : 1;
+// Process-wide A/B switches, default on; each is off while its environment variable (read once) is 1, or by its setter:
+//   SW_STEM3 / SW_STEM2_F16 (om_set_stem_fusion 0 / 1): the third layer inside the split-operand stem kernel / the fp16
+//     first-two-layers kernel (om_model::first_layers_fusable);
+//   SW_W14_WIDE (om_set_wino14_wide): om_forward runs the stride-1 3x3 layers with at least 512 input channels of precision mode 1 in
+//     the two-kernel wide form (conv_wino14.hip: wino14_v_kernel + wino14_wide_kernel); off: the fused kernel everywhere.  Bit-identical.
+enum : int { SW_STEM3 = 0, SW_STEM2_F16 = 1, SW_W14_WIDE = 2 };
+static int& switch_flag(int which) {
+    static int flags[3] = {-1, -1, -1};
+    return flags[which];
+}
+static bool switch_on(int which) {
+    static const char* const env[3] = {"OM_NO_STEM3", "OM_NO_STEM2_F16", "OM_NO_W14_WIDE"};
+    int& f = switch_flag(which);
+    if (f < 0) {
+        const char* e = std::getenv(env[which]);
+        f = (e && e[0] == '1') ? 0 : 1;
     }
-    return g_wino14_wide != 0;
+    return f != 0;
 }
 
 struct om_model {
@@ -125,26 +187,25 @@ struct om_model {
             weight_floats = om::align_up(weight_floats, 4);
             L.info.wino_off = (int64_t)weight_floats;
             weight_floats += (size_t)L.info.wino_planes * L.info.cout_pad * cin;
-            if (L.info.wino_planes == 24) {
-                // small problems (a few images) have too few 2 x 4 tiles to fill the chip: those forwards use F(2x2,3x3)
-                weight_floats = om::align_up(weight_floats, 4);
-                L.info.wino_alt_off = (int64_t)weight_floats;
-                weight_floats += (size_t)16 * L.info.cout_pad * cin;
-            }
+            // small problems (a few images) have too few 2 x 4 tiles to fill the chip: those forwards use F(2x2,3x3)
+            weight_floats = om::align_up(weight_floats, 4);
+            L.info.wino_alt_off = (int64_t)weight_floats;
+            weight_floats += (size_t)16 * L.info.cout_pad * cin;
         }
+        const bool wino = L.info.wino_planes != 0;
         L.info.wsplit_off = L.info.wsplit_scale_off = -1;
         if (!stem) {
             // split-operand mode: the fused F(4,3) form of the stride-1 3x3 layers (conv_wino14.hip: 3 kernel rows x 6 transform
             // points = 18 planes), the direct weights of every other layer
             L.info.wsplit_off = (int64_t)split_words;
-            split_words += (size_t)(L.info.wino_planes == 24 ? 18 : ks * ks) * L.info.cout_pad * cin;
+            split_words += (size_t)(wino ? 18 : ks * ks) * L.info.cout_pad * cin;
             L.info.wsplit_scale_off = (int64_t)split_words;
             split_words = om::align_up(split_words + L.info.cout_pad, 4);
         }
         // ... and for the stride-1 3x3 layers their DIRECT weights as well (own per-channel exponents): the latency mode
         // (om_model_set_latency_cells) runs them through the implicit GEMM when the batch has too few tiles to fill the chip
         L.info.wsplit_direct_off = L.info.wsplit_direct_scale_off = -1;
-        if (!stem && L.info.wino_planes == 24) {
+        if (wino) {
             L.info.wsplit_direct_off = (int64_t)split_words;
             split_words += (size_t)ks * ks * L.info.cout_pad * cin;
             L.info.wsplit_direct_scale_off = (int64_t)split_words;
@@ -294,15 +355,8 @@ struct om_model {
             C.gather = segs;
         }
     }
-    // split operands, fp32 tensors, activations not kept for om_layer_output_view (which reports a slice of the concat buffer)
     bool upsample_on_read = true;      // om_model_set_upsample_on_read
-    bool gather_active(bool f16) const { return (f16 || precision == 1) && !keep_all && upsample_on_read; }
-
-    // F(2x4,3x3) needs enough tiles to fill the chip: measured at 544^2, bs=4 is 4 % faster with F(2x2) and bs=8 is 4 % faster
-    // with F(2x4); the switch is on the number of 1/32-scale cells in the batch (289 per 544^2 image).
-    // With split operands (precision 1) F(2x4) runs at every size: its matrix instructions are 5.3x cheaper than the fp32-operand
-    // F(2x2) kernel's, which outweighs idle workgroup slots at small batches -- and an image's results then do not depend on the
-    // batch it is in.
+    bool keep_all = false;             // om_model_keep_activations
     // Latency mode (precision 1, opt-in: 0 = off): a forward whose batch holds fewer than this many 1/32-scale cells runs its
     // stride-1 3x3 layers as direct convolutions in the implicit GEMM (small tiles, one short round) instead of the fused
     // F(4,3) kernel, whose 128 x 64 tiles leave most of the chip idle at one or two images and take cin / 16 x 6 groups of
@@ -310,9 +364,6 @@ struct om_model {
     // tolerance against the reference), so outputs then depend on which side of the switch a batch is: off by default.
     long long latency_cells = 0;
     int latency_ksplit = 8;      // latency mode: most parts a tile's k loop is cut into (conv_igemm_split.hip; 1 = whole tiles)
-    bool direct_3x3(int B, int H, int W) const {
-        return precision == 1 && !keep_all && latency_cells > 0 && (long long)B * (H / 32) * (W / 32) < latency_cells;
-    }
     // om_model_attach_postprocess: the step's postprocess rides on the forward.  Decode + select (which read the box heads only)
     // are launched on a SECOND stream of the library's own as soon as the last box-head layer is in the caller's stream -- forked
     // there by an event, joined behind the forward's last layer -- and the mask kernel follows on the caller's stream.  The
@@ -347,64 +398,176 @@ struct om_model {
         for (int l = 0; l < (int)layers.size(); ++l)
             if (std::strncmp(layers[l].info.name, "bbox_head", 9) == 0) head_last = l;
     }
-    // ... per layer: only where the fused kernel would have at most 128 of its 128 x 64 tiles (half the CUs idle); with more
-    // tiles it is the faster form again (136^2 128 -> 256, one image: 160 tiles, 0.057 ms against 0.080 ms direct)
-    bool direct_3x3_layer(const om::LayerDef& L, int B, int H, int W) const {
-        if (!direct_3x3(B, H, W) || L.info.wino_planes != 24) return false;
-        int R = 0, Ct = 0, ncb = 0, nrb = 0;
-        om::wino14_geometry(B, H / L.in_div, W / L.in_div, &R, &Ct, &ncb, &nrb);
-        return (long long)nrb * ncb * (L.info.cout_pad / 64) <= 128;
-    }
 
-    bool use_f24(int B, int H, int W) const {
-        return precision == 1 || (long long)B * (H / 32) * (W / 32) >= 1700ll;
-    }
-
-    // A/B switches of the two fusions below (process-wide; om_set_stem_fusion, or OM_NO_STEM3=1 / OM_NO_STEM2_F16=1 in the
-    // environment read once): 0 = the third layer inside the split-operand stem kernel, 1 = the fp16 first-two-layers kernel
-    static int& stem_fusion_flag(int which) {
-        static int flags[2] = {-1, -1};
-        return flags[which];
-    }
-    static bool stem_fusion_on(int which) {
-        int& f = stem_fusion_flag(which);
-        if (f < 0) {
-            const char* e = std::getenv(which == 0 ? "OM_NO_STEM3" : "OM_NO_STEM2_F16");
-            f = (e && e[0] == '1') ? 0 : 1;
+    // The attachment as it is when a forward begins and, where decode + select run beside the rest of the forward (a non-fp16 forward
+    // with an attachment and a box head), the second stream that serves the caller's: `sd->side` stays null otherwise.
+    int take_side(hipStream_t main_stream, bool f16, PostAttach* post_q, Side* sd) {
+        std::lock_guard<std::mutex> lock(side_mutex);
+        *post_q = post;
+        if (!post.on || f16 || head_last < 0) return OM_OK;
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(main_stream, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive) {
+            // torch.cuda.graph captures on a stream of its own, after warm-ups elsewhere: the capture's side stream is the one
+            // om_model_attach_postprocess created for this purpose (the capture isolates it)
+            OM_REQUIRE(capture_side.side, OM_ESTATE, "om_forward: stream capture with an attached postprocess, but no capture stream (re-attach)");
+            *sd = capture_side;
+            sd->main = main_stream;
+            return OM_OK;
         }
-        return f != 0;
+        for (Side& have : sides)
+            if (have.main == main_stream) { have.used = ++side_clock; *sd = have; }
+        if (sd->side) return OM_OK;
+        if (sides.size() >= 64) {      // first forward with an attachment on this stream, and no entry left
+            // the least recently used entry changes owner: its side stream has long joined its old caller stream
+            // (every forward ends with the join), so the stream and its events are free to serve another
+            size_t lru = 0;
+            for (size_t i = 1; i < sides.size(); ++i)
+                if (sides[i].used < sides[lru].used) lru = i;
+            sides[lru].main = main_stream;
+            sides[lru].used = ++side_clock;
+            *sd = sides[lru];
+            return OM_OK;
+        }
+        sd->main = main_stream;
+        sd->used = ++side_clock;
+        OM_CHECK_HIP(hipStreamCreateWithFlags(&sd->side, hipStreamNonBlocking));
+        OM_CHECK_HIP(hipEventCreateWithFlags(&sd->ev_fork, hipEventDisableTiming));
+        OM_CHECK_HIP(hipEventCreateWithFlags(&sd->ev_join, hipEventDisableTiming));
+        sides.push_back(*sd);
+        return OM_OK;
     }
 
-    // split-operand mode: conv1 (the stem) and conv2.0 run as ONE kernel (conv_stem2.hip) when the second is the 32 -> 64 3x3
-    // stride-2 layer reading the first one's output -- unless every activation is kept for om_layer_output_view
-    // (never in the fp16-activation forward, whatever the precision mode says: its buffers hold 2-byte elements)
-    bool stem2_fused(size_t index, bool f16 = false) const {
-        if (f16 || precision != 1 || keep_all || index != 0 || layers.size() < 2 || !layers[0].stem) return false;
+    // plan()'s helper: how many layers behind the stem CAN run inside its kernel, by their shapes and the switches above.
+    // One: conv1 and conv2.0 as one kernel (conv_stem2.hip: conv_stem2_split_kernel / conv_stem2_f16_kernel, round 5) when the second
+    // is the 32 -> 64 3x3 stride-2 layer reading the first one's output, so that conv1's activation never reaches memory.
+    // Two (split operands only): the 64 -> 32 1x1 convolution behind them (backbone.conv2.1.conv.0) inside the same kernel too.
+    int first_layers_fusable(bool f16) const {
+        if (layers.size() < 2 || !layers[0].stem || (f16 && !switch_on(SW_STEM2_F16))) return 0;
         const om::LayerDef& a = layers[0];
         const om::LayerDef& b = layers[1];
-        return a.info.cout == 32 && b.info.cin == 32 && b.info.cout == 64 && b.info.cout_pad == 64 && b.info.ksize == 3 &&
-               b.info.stride == 2 && !b.has_res && b.out_mode == 0 && b.in.buf == a.out.buf && b.in.ch_off == a.out.ch_off &&
-               b.info.wsplit_off >= 0 && b.info.wino_planes != 24;
-    }
-
-    // ... and the 64 -> 32 1x1 convolution behind them (backbone.conv2.1.conv.0) inside the same kernel (round 5)
-    bool stem3_fused() const {
-        if (!stem_fusion_on(0) || !stem2_fused(0) || layers.size() < 3) return false;
-        const om::LayerDef& b = layers[1];
+        if (!(a.info.cout == 32 && b.info.cin == 32 && b.info.cout == 64 && b.info.cout_pad == 64 && b.info.ksize == 3 &&
+              b.info.stride == 2 && !b.has_res && b.out_mode == 0 && b.in.buf == a.out.buf && b.in.ch_off == a.out.ch_off))
+            return 0;
+        if (f16) return b.info.w16_off >= 0 && b.out.buf >= 0 ? 1 : 0;
+        if (b.info.wsplit_off < 0 || b.info.wino_planes != 0) return 0;
+        if (!switch_on(SW_STEM3) || layers.size() < 3) return 1;
         const om::LayerDef& c = layers[2];
         return c.info.cin == 64 && c.info.cout == 32 && c.info.cout_pad == 32 && c.info.ksize == 1 && c.info.stride == 1 && !c.has_res &&
-               c.out_mode == 0 && c.in.buf == b.out.buf && c.in.ch_off == b.out.ch_off && c.info.wsplit_off >= 0 && c.out.buf >= 0 &&
-               c.gather.empty() && c.side < 0;
+                       c.out_mode == 0 && c.in.buf == b.out.buf && c.in.ch_off == b.out.ch_off && c.info.wsplit_off >= 0 && c.out.buf >= 0 &&
+                       c.gather.empty() && c.side < 0
+                   ? 2 : 1;
     }
 
-    // the fp16-activation forward: the same two layers as conv_stem2_f16_kernel (round 5), under the same conditions
-    bool stem2_fused_f16(size_t index) const {
-        if (!stem_fusion_on(1) || keep_all || index != 0 || layers.size() < 2 || !layers[0].stem) return false;
-        const om::LayerDef& a = layers[0];
-        const om::LayerDef& b = layers[1];
-        return a.info.cout == 32 && b.info.cin == 32 && b.info.cout == 64 && b.info.cout_pad == 64 && b.info.ksize == 3 &&
-               b.info.stride == 2 && !b.has_res && b.out_mode == 0 && b.in.buf == a.out.buf && b.in.ch_off == a.out.ch_off &&
-               b.info.w16_off >= 0 && b.out.buf >= 0;
+    // The shape, stride and mode fields of layer L's launch under plan p (ConvArgs or ConvArgsH); pointers are the launch's business.
+    template <class Args>
+    void layer_shape(Args& a, const om::LayerDef& L, const om::LayerPlan& p, int B, int H, int W) const {
+        const om_layer_info& li = L.info;
+        om::fill_conv_shape(a, B, H / L.in_div, W / L.in_div, li.cin, pix_stride(L.in.buf), li.cout, li.cout_pad, li.ksize, li.stride,
+                            li.leaky, L.has_res ? pix_stride(L.res.buf) : 0, pix_stride(p.to_side ? L.side : L.out.buf),
+                            p.to_side ? 0 : L.out_mode, p.to_side ? 1 : L.up);
+    }
+
+    // THE chooser: which kernel runs layer `index` of a forward at this batch, size and precision, and what that kernel needs.
+    // om_layer_tile / om_layer_tile_f16 report it, layout() reserves its scratch and its side buffers, launch_layer launches it:
+    // nothing else decides.  Reads the A/B switches (om_set_wino14_wide, om_set_stem_fusion, om_model_set_upsample_on_read; the
+    // variants of single kernels -- om_set_conv3x3_f16_variant, om_set_wino14_variant -- sit behind their files' own tile functions).
+    // `unfused`: the first layers each as a kernel of its own (launch_first_layers' fallback).
+    om::LayerPlan plan(int index, int B, int H, int W, bool f16, bool unfused = false) const {
+        using om::Form;
+        const om::LayerDef& L = layers[index];
+        const om_layer_info& li = L.info;
+        om::LayerPlan p;
+        p.w_off = li.w_off; p.scale_off = li.scale_off;
+        const bool split = !f16 && precision == 1;
+        const int fused = (f16 || split) && !keep_all && !unfused ? first_layers_fusable(f16) : 0;
+        if (L.stem) {
+            if (index == 0 && fused) { p.form = f16 ? Form::Stem2F16 : fused == 2 ? Form::Stem3Split : Form::Stem2Split; p.bm = 128; p.bn = 64; }
+            return p;
+        }
+        if (index >= 1 && index <= fused) { p.form = Form::InPrevious; return p; }
+        const int Hin = H / L.in_div, Win = W / L.in_div, Ho = Hin / li.stride, Wo = Win / li.stride;
+        const long long cells = (long long)B * (H / 32) * (W / 32);      // 1/32-scale cells in the batch (289 per 544^2 image)
+        // Up-sampling on read: split operands or fp16 tensors, activations not kept for om_layer_output_view (which reports a slice
+        // of the concat buffer).  A route / skip then stores one copy at its own resolution (`side`), the 1x1 layer behind the concat
+        // reads the slices where they are (find_gathers).
+        const bool on_read = (f16 || split) && !keep_all && upsample_on_read;
+        if (f16) {
+            p.blob = om::LayerPlan::F16; p.w_off = li.w16_off;
+            p.to_side = on_read && L.side >= 0; p.gather = on_read && !L.gather.empty();
+            om::ConvArgsH a{};
+            layer_shape(a, L, p, B, H, W);
+            if (!p.gather && om::conv3x3_f16_supported(a)) {      // (launch_conv_igemm_f16 hands these to conv3x3_f16.hip)
+                om::conv3x3_tile_for_f16(B * Ho * Wo, li.cout_pad, Wo, li.cin / 32, &p.bm, &p.bn);
+                p.form = p.bm == 512 ? Form::Conv3x3F16Tall : Form::Conv3x3F16;
+            } else {
+                om::conv_tile_for_f16(B * Ho * Wo, li.cout_pad, li.cin, &p.bm, &p.bn, p.gather);
+                p.form = p.gather ? Form::IgemmF16Gather : Form::IgemmF16;
+            }
+            return p;
+        }
+        const bool latency = split && !keep_all && latency_cells > 0 && cells < latency_cells;
+        p.ksplit_max = latency ? latency_ksplit : 0;
+        const bool wino = li.wino_planes != 0 && om::wino_enabled();      // wino_planes is 24 (F(2x4) at wino_off, F(2x2) at wino_alt_off) or 0
+        if (wino && split) {
+            // With split operands F(2x4)'s successor, the fused F(4,3) kernel (conv_wino14.hip transforms its input on chip), runs at
+            // every size: its matrix instructions are 5.3x cheaper than the fp32-operand F(2x2) kernel's, which outweighs idle
+            // workgroup slots at small batches -- and an image's results then do not depend on the batch it is in.
+            int R = 0, Ct = 0, ncb = 0, nrb = 0;
+            om::wino14_geometry(B, Hin, Win, &R, &Ct, &ncb, &nrb);
+            const long long tiles = (long long)nrb * ncb * (li.cout_pad / 64);      // the fused kernel's 128 x 64 tiles
+            p.blob = om::LayerPlan::SPLIT;
+            if (latency && tiles <= 128) {
+                // latency mode, per layer: only where the fused kernel would have at most 128 tiles (half the CUs idle); with more
+                // tiles it is the faster form again (136^2 128 -> 256, one image: 160 tiles, 0.057 ms against 0.080 ms direct).
+                // The same layer as a direct 3x3 convolution with split operands, its own per-channel exponents.
+                p.form = Form::SplitDirect3x3;
+                p.w_off = li.wsplit_direct_off; p.scale_off = li.wsplit_direct_scale_off;
+                om::conv_tile_for_split(B * Hin * Win, li.cout_pad, &p.bm, &p.bn);
+                return p;
+            }
+            p.form = Form::Wino14; p.bm = 128; p.bn = 64;
+            p.w_off = li.wsplit_off; p.scale_off = li.wsplit_scale_off;
+            // The two-kernel wide form (wino14_v_kernel + wino14_wide_kernel, round 6): from 512 input channels on (where the
+            // pre-pass's 2.5 x the input through HBM is small next to the layer's work), and only where the fused kernel's tiles
+            // outnumber the CUs: while ONE round of them covers the layer, a round of half as many 128 x 128 tiles takes longer
+            // (17^2 512 -> 1024: 0.14 against 0.21 ms per round; at bs = 32 the fused kernel needs 1.56 rounds = 0.26-0.28 ms, the
+            // wide form one round + the pre-pass = 0.22-0.23 ms).  Its launcher's own conditions are asked here, on stand-in
+            // pointers: layout() places every buffer 256-byte aligned, so a view is as aligned as its channel offset; a caller's
+            // tensor (a head) is not known to be.
+            if (switch_on(SW_W14_WIDE) && li.cin >= 512 && tiles > 256 && L.out.buf >= 0 && (!L.has_res || L.res.buf >= 0)) {
+                om::ConvArgs a{};
+                layer_shape(a, L, p, B, H, W);
+                a.out = reinterpret_cast<float*>((uintptr_t)256 + (size_t)L.out.ch_off * sizeof(float));
+                a.res = L.has_res ? reinterpret_cast<const float*>((uintptr_t)256 + (size_t)L.res.ch_off * sizeof(float)) : nullptr;
+                if (om::wino14_wide_supported(a)) {
+                    p.form = Form::Wino14Wide; p.bn = 128;
+                    p.scratch_floats = om::wino14_wide_scratch_floats(B, Hin, Win, li.cin);
+                }
+            }
+        } else if (wino && cells >= 1700ll) {
+            // F(2x4,3x3) needs enough tiles to fill the chip: measured at 544^2, bs=4 is 4 % faster with F(2x2) and bs=8 is 4 %
+            // faster with F(2x4); the switch is on the number of 1/32-scale cells in the batch.
+            p.form = Form::Wino24; p.bm = 64; p.bn = 64;
+            p.w_off = li.wino_off;
+            p.scratch_floats = om::wino24_scratch_floats(B, Hin, Win, li.cin);
+        } else if (wino) {
+            const bool fused_transform = om::wino_fused_for(li.cin);
+            p.form = fused_transform ? Form::WinoFused : Form::Wino;
+            p.bm = 64;
+            p.bn = fused_transform ? (li.cout_pad % 128 == 0 ? 128 : 64) : om::wino_bn((long long)B * ((Hin + 1) / 2) * ((Win + 1) / 2), li.cout_pad);
+            p.w_off = li.wino_alt_off;
+            p.scratch_floats = om::wino_scratch_floats(B, Hin, Win, li.cin);
+        } else if (split && li.wino_planes == 0) {
+            p.blob = om::LayerPlan::SPLIT;
+            p.w_off = li.wsplit_off; p.scale_off = li.wsplit_scale_off;
+            p.to_side = on_read && L.side >= 0; p.gather = on_read && !L.gather.empty();
+            p.form = p.gather ? Form::SplitGather : Form::Split;
+            om::conv_tile_for_split(B * Ho * Wo, li.cout_pad, &p.bm, &p.bn, p.gather);
+        } else {
+            p.form = Form::Igemm;
+            om::conv_tile_for(B * Ho * Wo, li.cout_pad, &p.bm, &p.bn);
+        }
+        return p;
     }
 
     size_t buf_floats(int i, int B, int H, int W) const {
@@ -418,43 +581,23 @@ struct om_model {
     // DESIGN.md).  keep_all (om_model_keep_activations) gives every tensor its own slab again so that om_layer_output_view
     // can be read after the forward.
     struct Layout {
+        std::vector<om::LayerPlan> plans;   // per layer: what the layout was made for, and what the forward then launches
         std::vector<size_t> buf_off;        // per activation buffer
         std::vector<size_t> scratch_off;    // per layer (Winograd layers only)
         size_t tickets_off = 0, partial_off = 0, total = 0;
     };
-    bool keep_all = false;
-
-    // split-operand mode: the layers that run the two-kernel wide form of the fused 3x3 kernel (conv_wino14.hip, round 6): from 512
-    // input channels on (where the pre-pass's 2.5 x the input through HBM is small next to the layer's work), whole pairs of N tiles
-    // ... and only where the fused kernel's 128 x 64 tiles outnumber the CUs: while ONE round of them covers the layer, a round of half
-    // as many 128 x 128 tiles takes longer (17^2 512 -> 1024: 0.14 against 0.21 ms per round; at bs = 32 the fused kernel needs 1.56
-    // rounds = 0.26-0.28 ms, the wide form one round + the pre-pass = 0.22-0.23 ms)
-    bool wide_3x3_layer(const om::LayerDef& L, int B, int H, int W) const {
-        if (!(precision == 1 && wino14_wide_on() && L.info.wino_off >= 0 && L.info.wino_planes == 24 && L.info.ksize == 3 &&
-              L.info.stride == 1 && L.out_mode == 0 && L.info.cin >= 512 && L.info.cout_pad % 128 == 0 && L.info.cout % 4 == 0) ||
-            direct_3x3_layer(L, B, H, W))
-            return false;
-        int R = 0, Ct = 0, ncb = 0, nrb = 0;
-        om::wino14_geometry(B, H / L.in_div, W / L.in_div, &R, &Ct, &ncb, &nrb);
-        return (long long)nrb * ncb * (L.info.cout_pad / 64) > 256;
-    }
-
-    size_t layer_scratch_floats(const om::LayerDef& L, int B, int H, int W) const {
-        if (L.info.wino_off < 0) return 0;
-        if (precision == 1 && L.info.wino_planes == 24)      // conv_wino14.hip transforms its input on chip, but for the wide form's V
-            return wide_3x3_layer(L, B, H, W) ? om::wino14_wide_scratch_floats(B, H / L.in_div, W / L.in_div, L.info.cin) : 0;
-        return (L.info.wino_planes == 24 && use_f24(B, H, W)) ? om::wino24_scratch_floats(B, H / L.in_div, W / L.in_div, L.info.cin)
-                                                               : om::wino_scratch_floats(B, H / L.in_div, W / L.in_div, L.info.cin);
-    }
 
     Layout layout(int B, int H, int W, bool f16) const {
         const size_t esz = f16 ? 2 : 4;
         const int nb = (int)bufs.size(), nl = (int)layers.size();
+        Layout out;
+        out.plans.resize(nl);
         struct Item { size_t bytes; int first, last; size_t off; };
         std::vector<Item> items(nb + nl);
         for (int i = 0; i < nb; ++i) items[i] = {om::align_up(buf_floats(i, B, H, W) * esz, 256), nl, -1, 0};      // never touched: not placed
         for (int l = 0; l < nl; ++l) {
             const om::LayerDef& L = layers[l];
+            const om::LayerPlan& p = out.plans[l] = plan(l, B, H, W, f16);
             auto touch = [&](int buf) {
                 if (buf < 0) return;
                 if (l < items[buf].first) items[buf].first = l;
@@ -462,12 +605,11 @@ struct om_model {
             };
             touch(L.in.buf); touch(L.out.buf);
             if (L.has_res) touch(L.res.buf);
-            if (gather_active(f16)) {
-                if (L.side >= 0) touch(L.side);
+            if (p.to_side) touch(L.side);
+            if (p.gather)
                 for (const auto& sg : L.gather)
                     if (sg.producer >= 0) touch(layers[sg.producer].side);
-            }
-            items[nb + l] = {f16 ? 0 : om::align_up(layer_scratch_floats(L, B, H, W) * sizeof(float), 256), l, l, 0};
+            items[nb + l] = {om::align_up(p.scratch_floats * sizeof(float), 256), l, l, 0};
         }
         if (keep_all)
             for (int i = 0; i < nb; ++i) { items[i].first = 0; items[i].last = nl; }
@@ -493,7 +635,6 @@ struct om_model {
             if (at + it.bytes > peak) peak = at + it.bytes;
             placed.push_back(id);
         }
-        Layout out;
         out.buf_off.resize(nb);
         out.scratch_off.resize(nl);
         for (int i = 0; i < nb; ++i) out.buf_off[i] = items[i].off;
@@ -504,6 +645,203 @@ struct om_model {
         return out;
     }
 };
+
+namespace {
+
+// A failed launch's message, with the layer(s) it belongs to in front
+int fail_in(int rc, const char* what, const char* name, const char* name2 = nullptr) {
+    char msg[512];
+    std::snprintf(msg, sizeof(msg), "%s", om::g_err);
+    if (name2) om::set_error("%s %s + %s: %s", what, name, name2, msg);
+    else om::set_error("%s %s: %s", what, name, msg);
+    return rc;
+}
+
+// One layer's profiling events (om_profile_*): begin() records its start, mid() the boundary between its pre-pass and its main
+// kernel (a single-kernel layer: mid == start), the destructor its stop -- whatever path leaves the layer.
+struct LayerEvents {
+    hipEvent_t ev_mid = nullptr, ev_stop = nullptr;
+    hipStream_t stream = nullptr;
+    int begin(om_model* m, int layer, hipStream_t s) {
+        stream = s;
+        if (!m->profiling || !(m->prof_mask.empty() || m->prof_mask[layer])) return OM_OK;
+        while (m->ev_used + 3 > m->ev_pool.size()) {
+            hipEvent_t e;
+            OM_CHECK_HIP(hipEventCreate(&e));
+            m->ev_pool.push_back(e);
+        }
+        OM_CHECK_HIP(hipEventRecord(m->ev_pool[m->ev_used], s));
+        ev_mid = m->ev_pool[m->ev_used + 1];
+        ev_stop = m->ev_pool[m->ev_used + 2];
+        m->ev_used += 3;
+        return OM_OK;
+    }
+    int mid() const {
+        if (ev_mid) OM_CHECK_HIP(hipEventRecord(ev_mid, stream));
+        return OM_OK;
+    }
+    ~LayerEvents() { if (ev_stop) (void)hipEventRecord(ev_stop, stream); }
+};
+
+struct JoinGuard {      // whatever path leaves the forward: the caller's stream waits for the side stream's work
+    om_model::Side sd; bool forked;
+    void join() {
+        if (!forked) return;
+        forked = false;
+        (void)hipEventRecord(sd.ev_join, sd.side);
+        (void)hipStreamWaitEvent(sd.main, sd.ev_join, 0);
+    }
+    ~JoinGuard() { join(); }
+};
+
+// One forward's launches: where its tensors are, the words its kernels synchronise on, and how a planned layer becomes a launch.
+struct ForwardRun {
+    const om_model* m;
+    const float* x;
+    int B, H, W;
+    bool f16;
+    float *bbox32, *bbox16, *bbox8, *oriens;
+    char* workspace;
+    const om_model::Layout* lay;
+    hipStream_t stream;
+    int* tickets;          // SYNC_WORDS per layer, then the status words (om_forward_status_offset); zeroed by every forward
+    float* sk_partial;
+    int* status;
+
+    char* buf(int i) const { return workspace + lay->buf_off[i]; }
+    // element pointer of a view: workspace buffers hold 2- (f16) or 4-byte elements, the four outputs are always fp32
+    void* ptr_of(const om::View& v) const {
+        switch (v.buf) {
+            case om::BUF_BBOX32: return bbox32;
+            case om::BUF_BBOX16: return bbox16;
+            case om::BUF_BBOX8: return bbox8;
+            case om::BUF_ORIENS: return oriens;
+            default: return buf(v.buf) + (size_t)v.ch_off * (f16 ? 2 : 4);
+        }
+    }
+    const void* weights_of(const om::LayerPlan& p) const {
+        if (p.blob == om::LayerPlan::F16) return m->weights16 + p.w_off;
+        return (p.blob == om::LayerPlan::SPLIT ? m->weights_split : m->weights) + p.w_off;
+    }
+    const float* scale_of(const om::LayerPlan& p) const { return (p.blob == om::LayerPlan::SPLIT ? m->weights_split : m->weights) + p.scale_off; }
+
+    // ConvArgs / ConvArgsH of layer `index` under plan p: shapes, views, weights, the layer's sync words and its gather table
+    template <class Args>
+    Args conv_args(int index, const om::LayerPlan& p) const {
+        const om::LayerDef& L = m->layers[index];
+        Args a{};
+        m->layer_shape(a, L, p, B, H, W);
+        a.in = static_cast<decltype(a.in)>(ptr_of(L.in));
+        a.w = static_cast<decltype(a.w)>(weights_of(p));
+        a.scale = scale_of(p);
+        a.shift = m->weights + L.info.shift_off;
+        a.res = L.has_res ? static_cast<decltype(a.res)>(ptr_of(L.res)) : nullptr;
+        a.out = static_cast<decltype(a.out)>(p.to_side ? static_cast<void*>(buf(L.side)) : ptr_of(L.out));
+        a.ticket = tickets + (size_t)index * om::SYNC_WORDS;
+        if (p.gather) {      // routes / skips stored once at their own resolution (their `side`), read up-sampled
+            a.nseg = (int)L.gather.size();
+            for (int g = 0; g < a.nseg; ++g) {
+                const om::LayerDef::Seg& sg = L.gather[g];
+                const int side = sg.producer >= 0 ? m->layers[sg.producer].side : -1;
+                a.seg_ptr[g] = static_cast<decltype(a.in)>(side >= 0 ? static_cast<void*>(buf(side)) : ptr_of(sg.view));
+                a.seg_pix_stride[g] = m->pix_stride(side >= 0 ? side : sg.view.buf);
+                a.seg_channels[g] = sg.channels; a.seg_up[g] = sg.up;
+            }
+        }
+        return a;
+    }
+
+    int launch_layer(int index, const om::LayerPlan& p, const LayerEvents& ev) const {
+        using om::Form;
+        const om::LayerDef& L = m->layers[index];
+        if (p.form == Form::Stem) {
+            if (int rc = ev.mid()) return rc;
+            const float* shift = m->weights + L.info.shift_off;
+            return f16 ? om::launch_conv_stem_f16(x, B, H / L.in_div, W / L.in_div, m->weights + p.w_off, scale_of(p), shift, L.info.cout, ptr_of(L.out), stream)
+                       : om::launch_conv_stem(x, B, H / L.in_div, W / L.in_div, m->weights + p.w_off, scale_of(p), shift, L.info.cout,
+                                              static_cast<float*>(ptr_of(L.out)), stream);
+        }
+        if (f16) {
+            om::ConvArgsH a = conv_args<om::ConvArgsH>(index, p);
+            a.out_f32 = L.out.buf < 0 ? 1 : 0;
+            if (int rc = ev.mid()) return rc;
+            return om::launch_conv_igemm_f16(a, stream);      // (every fp16 form: it hands the 3x3 layers to conv3x3_f16.hip)
+        }
+        om::ConvArgs a = conv_args<om::ConvArgs>(index, p);
+        a.sk_partial = sk_partial;
+        a.status = status;
+        a.ksplit_max = p.ksplit_max;
+        a.split = p.form == Form::Wino14 || p.form == Form::Wino14Wide ? 1 : 0;
+        float* scratch = reinterpret_cast<float*>(workspace + lay->scratch_off[index]);
+        switch (p.form) {      // two kernels: the launcher records the mid event between them
+            case Form::Wino: case Form::WinoFused: a.mid_event = ev.ev_mid; return om::launch_conv_winograd(a, scratch, stream);
+            case Form::Wino24: a.mid_event = ev.ev_mid; return om::launch_conv_winograd24(a, scratch, stream);
+            case Form::Wino14Wide: a.mid_event = ev.ev_mid; return om::launch_conv_wino14_wide(a, scratch, stream);
+            default: break;
+        }
+        if (int rc = ev.mid()) return rc;
+        switch (p.form) {
+            case Form::Wino14: return om::launch_conv_wino14_split(a, stream);
+            case Form::Split: case Form::SplitGather: case Form::SplitDirect3x3: return om::launch_conv_igemm_split(a, stream);
+            case Form::Igemm: return om::launch_conv_igemm(a, stream);
+            default: break;
+        }
+        om::set_error("no launch for kernel form %d", (int)p.form);
+        return OM_ESTATE;
+    }
+
+    // The first layers as one kernel (plan forms Stem2Split / Stem3Split / Stem2F16); *consumed = how many layers behind the stem
+    // ran inside it.  THE ONLY LAUNCH-TIME FALLBACK of the forward: plan() looks at layer shapes and views, the launchers also have
+    // preconditions on the caller's image pointer.  What they refuse (OM_EINVAL) takes the path that was the only one before the
+    // fusion existed -- first without the third layer, then (*consumed = 0) the separate kernels, which the caller plans `unfused`.
+    int launch_first_layers(const om::LayerPlan& p, const LayerEvents& ev, int* consumed) const {
+        const om::LayerDef& S = m->layers[0];
+        const om::LayerDef& N = m->layers[1];
+        const float *w = m->weights + p.w_off, *scale = scale_of(p), *shift = m->weights + S.info.shift_off;
+        const float* n_shift = m->weights + N.info.shift_off;
+        const int n_stride = m->pix_stride(N.out.buf);
+        *consumed = 0;
+        if (int rc = ev.mid()) return rc;
+        int rc;
+        if (p.form == om::Form::Stem2F16) {
+            rc = om::launch_conv_stem2_f16(x, B, H, W, w, scale, shift, m->weights16 + N.info.w16_off, m->weights + N.info.scale_off, n_shift,
+                                           N.info.cout, N.info.leaky, ptr_of(N.out), n_stride, stream);
+            if (rc == OM_OK) *consumed = 1;
+        } else {
+            const float *n_w = m->weights_split + N.info.wsplit_off, *n_scale = m->weights_split + N.info.wsplit_scale_off;
+            float* n_out = static_cast<float*>(ptr_of(N.out));
+            rc = OM_EINVAL;
+            if (p.form == om::Form::Stem3Split) {
+                const om::LayerDef& T = m->layers[2];
+                const om::Stem2Third third{m->weights_split + T.info.wsplit_off, m->weights_split + T.info.wsplit_scale_off,
+                                           m->weights + T.info.shift_off, static_cast<float*>(ptr_of(T.out)), T.info.cout, T.info.leaky,
+                                           m->pix_stride(T.out.buf)};
+                rc = om::launch_conv_stem2_split(x, B, H, W, w, scale, shift, n_w, n_scale, n_shift, N.info.cout, N.info.leaky, n_out, n_stride,
+                                                 status, stream, &third);
+                if (rc == OM_OK) *consumed = 2;
+            }
+            if (rc == OM_EINVAL) {
+                rc = om::launch_conv_stem2_split(x, B, H, W, w, scale, shift, n_w, n_scale, n_shift, N.info.cout, N.info.leaky, n_out, n_stride,
+                                                 status, stream, nullptr);
+                if (rc == OM_OK) *consumed = 1;
+            }
+        }
+        if (rc == OM_OK || rc == OM_EINVAL) return OM_OK;
+        return fail_in(rc, "layers", S.info.name, N.info.name);
+    }
+};
+
+// The om_conv2d_* unit-test entries: ONE library-owned block of sync words, zeroed before every launch, so that the persistent tile
+// queue (what om_forward uses, with tickets carved from the caller's workspace) is what gets tested and benchmarked.
+int unit_ticket(hipStream_t stream, int** out) {
+    static int* g_ticket = nullptr;
+    if (!g_ticket) OM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&g_ticket), om::SYNC_WORDS * sizeof(int)));
+    if (int rc = om::launch_zero_words(g_ticket, om::SYNC_WORDS, stream)) return rc;
+    *out = g_ticket;
+    return OM_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -612,281 +950,43 @@ static int forward_impl(om_model* m, const float* x, int B, int H, int W, float*
                "om_forward: precision mode 1 needs om_model_load_weights_split first");
     OM_REQUIRE(B > 0 && H > 0 && W > 0 && H % 32 == 0 && W % 32 == 0, OM_EINVAL,
                "om_forward: B=%d H=%d W=%d (H and W must be positive multiples of 32)", B, H, W);
-    const size_t need = forward_workspace_bytes(m, B, H, W, f16);
-    OM_REQUIRE(ws_bytes >= need, OM_ENOMEM, "om_forward: workspace %zu bytes < %zu needed", ws_bytes, need);
+    const om_model::Layout lay = m->layout(B, H, W, f16);      // every layer's plan, and where its tensors and scratch are
+    OM_REQUIRE(ws_bytes >= lay.total, OM_ENOMEM, "om_forward: workspace %zu bytes < %zu needed", ws_bytes, lay.total);
     OM_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, OM_EINVAL, "om_forward: workspace not 256-byte aligned");
     hipStream_t const main_stream = static_cast<hipStream_t>(stream_);
-    const size_t esz = f16 ? 2 : 4;
     // an attached postprocess (om_model_attach_postprocess): decode + select on the library's second stream behind the last box head
-    om_model::Side sd;
     om_model::PostAttach post_q;      // the attachment as it was when this forward began
-    bool fused_post, early;
-    {
-        std::lock_guard<std::mutex> lock(m->side_mutex);
-        post_q = m->post;
-        fused_post = m->post.on && !f16;
-        early = fused_post && m->head_last >= 0;
-        if (early) {
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            const bool capturing = hipStreamIsCapturing(main_stream, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive;
-            if (capturing) {
-                // torch.cuda.graph captures on a stream of its own, after warm-ups elsewhere: the capture's side stream is the one
-                // om_model_attach_postprocess created for this purpose (the capture isolates it)
-                OM_REQUIRE(m->capture_side.side, OM_ESTATE, "om_forward: stream capture with an attached postprocess, but no capture stream (re-attach)");
-                sd = m->capture_side;
-                sd.main = main_stream;
-            } else {
-                for (om_model::Side& have : m->sides)
-                    if (have.main == main_stream) { have.used = ++m->side_clock; sd = have; }
-                if (!sd.side) {      // first forward with an attachment on this stream
-                    if (m->sides.size() >= 64) {
-                        // the least recently used entry changes owner: its side stream has long joined its old caller stream
-                        // (every forward ends with the join), so the stream and its events are free to serve another
-                        size_t lru = 0;
-                        for (size_t i = 1; i < m->sides.size(); ++i)
-                            if (m->sides[i].used < m->sides[lru].used) lru = i;
-                        m->sides[lru].main = main_stream;
-                        m->sides[lru].used = ++m->side_clock;
-                        sd = m->sides[lru];
-                    } else {
-                        sd.main = main_stream;
-                        sd.used = ++m->side_clock;
-                        OM_CHECK_HIP(hipStreamCreateWithFlags(&sd.side, hipStreamNonBlocking));
-                        OM_CHECK_HIP(hipEventCreateWithFlags(&sd.ev_fork, hipEventDisableTiming));
-                        OM_CHECK_HIP(hipEventCreateWithFlags(&sd.ev_join, hipEventDisableTiming));
-                        m->sides.push_back(sd);
-                    }
-                }
-            }
-        }
-    }
-    struct JoinGuard {      // whatever path leaves the function: the caller's stream waits for the side stream's work
-        om_model::Side sd; bool forked;
-        void join() {
-            if (!forked) return;
-            forked = false;
-            (void)hipEventRecord(sd.ev_join, sd.side);
-            (void)hipStreamWaitEvent(sd.main, sd.ev_join, 0);
-        }
-        ~JoinGuard() { join(); }
-    } join_guard{sd, false};
+    om_model::Side sd;
+    if (int rc = m->take_side(main_stream, f16, &post_q, &sd)) return rc;
+    const bool fused_post = post_q.on && !f16, early = sd.side != nullptr;
+    JoinGuard join_guard{sd, false};
 
-    const om_model::Layout lay = m->layout(B, H, W, f16);
-    std::vector<char*> base(m->bufs.size());
-    for (size_t i = 0; i < m->bufs.size(); ++i) base[i] = static_cast<char*>(workspace) + lay.buf_off[i];
-    int* tickets = reinterpret_cast<int*>(static_cast<char*>(workspace) + lay.tickets_off);
-    float* sk_partial = f16 ? nullptr : reinterpret_cast<float*>(static_cast<char*>(workspace) + lay.partial_off);
-    int* status = tickets + m->layers.size() * om::SYNC_WORDS;      // om_forward_status_offset
-    if (int rc = om::launch_zero_words(tickets, m->layers.size() * om::SYNC_WORDS + om::STATUS_WORDS, main_stream)) return rc;
-    // element pointer of a view: workspace buffers hold esz-byte elements, the four outputs are always fp32
-    auto ptr_of = [&](const om::View& v) -> void* {
-        switch (v.buf) {
-            case om::BUF_BBOX32: return bbox32;
-            case om::BUF_BBOX16: return bbox16;
-            case om::BUF_BBOX8: return bbox8;
-            case om::BUF_ORIENS: return oriens;
-            default: return base[v.buf] + (size_t)v.ch_off * esz;
-        }
-    };
+    const int nl = (int)m->layers.size();
+    char* const ws = static_cast<char*>(workspace);
+    int* const tickets = reinterpret_cast<int*>(ws + lay.tickets_off);
+    const ForwardRun run{m, x, B, H, W, f16, bbox32, bbox16, bbox8, oriens, ws, &lay, main_stream, tickets,
+                         f16 ? nullptr : reinterpret_cast<float*>(ws + lay.partial_off), tickets + (size_t)nl * om::SYNC_WORDS};
+    if (int rc = om::launch_zero_words(tickets, (size_t)nl * om::SYNC_WORDS + om::STATUS_WORDS, main_stream)) return rc;
 
-    int fused_into_previous = 0;
-    for (const om::LayerDef& L : m->layers) {
-        const om_layer_info& li = L.info;
-        const int layer_index = (int)(&L - m->layers.data());
-        hipStream_t const stream = main_stream;
-        hipEvent_t ev_stop = nullptr, ev_mid = nullptr;
-        if (m->profiling && (m->prof_mask.empty() || m->prof_mask[&L - m->layers.data()])) {
-            if (m->ev_used + 3 > m->ev_pool.size()) {
-                for (int k = 0; k < 3; ++k) {
-                    hipEvent_t e;
-                    OM_CHECK_HIP(hipEventCreate(&e));
-                    m->ev_pool.push_back(e);
-                }
-            }
-            OM_CHECK_HIP(hipEventRecord(m->ev_pool[m->ev_used], stream));
-            ev_mid = m->ev_pool[m->ev_used + 1];
-            ev_stop = m->ev_pool[m->ev_used + 2];
-            m->ev_used += 3;
-        }
-        struct StopGuard {
-            hipEvent_t e; hipStream_t s;
-            ~StopGuard() { if (e) (void)hipEventRecord(e, s); }
-        } stop_guard{ev_stop, stream};
-        const float* w = m->weights + li.w_off;
-        const float* scale = m->weights + li.scale_off;
-        const float* shift = m->weights + li.shift_off;
-        const int Hin = H / L.in_div, Win = W / L.in_div;
-        if (fused_into_previous > 0) {      // conv2.0 (and conv2.1.conv.0) after the fused kernel: nothing to launch (its events bracket nothing)
-            --fused_into_previous;
-            if (ev_mid) OM_CHECK_HIP(hipEventRecord(ev_mid, stream));
+    int in_previous = 0;      // layers ahead that ran inside the first layers' kernel: nothing to launch (their events bracket nothing)
+    for (int l = 0; l < nl; ++l) {
+        LayerEvents ev;
+        if (int rc = ev.begin(m, l, main_stream)) return rc;
+        if (in_previous > 0) {
+            --in_previous;
+            if (int rc = ev.mid()) return rc;
             continue;
         }
-        if (L.stem && m->stem2_fused(&L - m->layers.data(), f16)) {
-            // split-operand mode: conv1 and conv2.0 as one kernel (conv_stem2.hip) -- conv1's activation never reaches memory
-            const om::LayerDef& N = m->layers[(&L - m->layers.data()) + 1];
-            if (ev_mid) OM_CHECK_HIP(hipEventRecord(ev_mid, stream));
-            om::Stem2Third third{};
-            const bool three = m->stem3_fused();
-            if (three) {
-                const om::LayerDef& T = m->layers[(&L - m->layers.data()) + 2];
-                third.w_split = m->weights_split + T.info.wsplit_off; third.scale_split = m->weights_split + T.info.wsplit_scale_off;
-                third.shift = m->weights + T.info.shift_off; third.out = static_cast<float*>(ptr_of(T.out));
-                third.cout = T.info.cout; third.leaky = T.info.leaky; third.out_pix_stride = m->pix_stride(T.out.buf);
-            }
-            bool three_done = three;
-            int rc = om::launch_conv_stem2_split(x, B, Hin, Win, w, scale, shift, m->weights_split + N.info.wsplit_off,
-                                                 m->weights_split + N.info.wsplit_scale_off, m->weights + N.info.shift_off, N.info.cout,
-                                                 N.info.leaky, static_cast<float*>(ptr_of(N.out)), m->pix_stride(N.out.buf), status, stream,
-                                                 three ? &third : nullptr);
-            // the predicates above look at layer shapes; the launcher also has preconditions on the views (alignment, pixel
-            // stride, descriptor size).  A view it refuses takes the path that was the only one before the fusion existed: first
-            // without the third layer, then the separate kernels below.
-            if (rc == OM_EINVAL && three) {
-                three_done = false;
-                rc = om::launch_conv_stem2_split(x, B, Hin, Win, w, scale, shift, m->weights_split + N.info.wsplit_off,
-                                                 m->weights_split + N.info.wsplit_scale_off, m->weights + N.info.shift_off, N.info.cout,
-                                                 N.info.leaky, static_cast<float*>(ptr_of(N.out)), m->pix_stride(N.out.buf), status, stream, nullptr);
-            }
-            if (rc == OM_OK) {
-                fused_into_previous = three_done ? 2 : 1;
-                continue;
-            }
-            if (rc != OM_EINVAL) {
-                char msg[512];
-                std::snprintf(msg, sizeof(msg), "%s", om::g_err);
-                om::set_error("layers %s + %s: %s", li.name, N.info.name, msg);
-                return rc;
-            }
-        } else if (L.stem && f16 && m->stem2_fused_f16(&L - m->layers.data())) {
-            // fp16 activations: conv1 and conv2.0 as one kernel too (conv_stem2_f16_kernel)
-            const om::LayerDef& N = m->layers[(&L - m->layers.data()) + 1];
-            if (ev_mid) OM_CHECK_HIP(hipEventRecord(ev_mid, stream));
-            int rc = om::launch_conv_stem2_f16(x, B, Hin, Win, w, scale, shift, m->weights16 + N.info.w16_off,
-                                               m->weights + N.info.scale_off, m->weights + N.info.shift_off, N.info.cout, N.info.leaky,
-                                               ptr_of(N.out), m->pix_stride(N.out.buf), stream);
-            if (rc == OM_OK) {
-                fused_into_previous = 1;
-                continue;
-            }
-            if (rc != OM_EINVAL) {      // OM_EINVAL: a view the fused launcher refuses -> the separate kernels below
-                char msg[512];
-                std::snprintf(msg, sizeof(msg), "%s", om::g_err);
-                om::set_error("layers %s + %s: %s", li.name, N.info.name, msg);
-                return rc;
-            }
+        om::LayerPlan p = lay.plans[l];
+        const bool first_layers = p.form == om::Form::Stem2Split || p.form == om::Form::Stem3Split || p.form == om::Form::Stem2F16;
+        if (first_layers) {
+            if (int rc = run.launch_first_layers(p, ev, &in_previous)) return rc;
+            if (in_previous > 0) continue;
         }
-        if (L.stem) {
-            if (ev_mid) OM_CHECK_HIP(hipEventRecord(ev_mid, stream));
-            int rc = f16 ? om::launch_conv_stem_f16(x, B, Hin, Win, w, scale, shift, li.cout, ptr_of(L.out), stream)
-                         : om::launch_conv_stem(x, B, Hin, Win, w, scale, shift, li.cout,
-                                                static_cast<float*>(ptr_of(L.out)), stream);
-            if (rc != OM_OK) return rc;
-            continue;
-        }
-        int rc;
-        if (f16) {
-            om::ConvArgsH a;
-            a.in = ptr_of(L.in); a.w = m->weights16 + li.w16_off; a.scale = scale; a.shift = shift;
-            a.res = L.has_res ? ptr_of(L.res) : nullptr;
-            a.out = ptr_of(L.out);
-            a.B = B; a.H = Hin; a.W = Win; a.cin = li.cin; a.in_pix_stride = m->pix_stride(L.in.buf);
-            a.Ho = Hin / li.stride; a.Wo = Win / li.stride; a.cout = li.cout; a.cout_pad = li.cout_pad;
-            a.ks = li.ksize; a.stride = li.stride; a.leaky = li.leaky;
-            a.res_pix_stride = L.has_res ? m->pix_stride(L.res.buf) : 0;
-            a.out_pix_stride = m->pix_stride(L.out.buf);
-            a.out_mode = L.out_mode; a.up = L.up;
-            a.out_f32 = L.out.buf < 0 ? 1 : 0;
-            a.ticket = tickets + (&L - m->layers.data()) * om::SYNC_WORDS;
-            if (m->gather_active(f16)) {      // routes / skips stored once at their own resolution, read up-sampled (as in split mode below)
-                if (L.side >= 0) {
-                    a.out = base[L.side];
-                    a.out_pix_stride = m->pix_stride(L.side); a.out_mode = 0; a.up = 1;
-                }
-                a.nseg = (int)L.gather.size();
-                for (int g = 0; g < a.nseg; ++g) {
-                    const om::LayerDef::Seg& sg = L.gather[g];
-                    const int side = sg.producer >= 0 ? m->layers[sg.producer].side : -1;
-                    a.seg_ptr[g] = side >= 0 ? static_cast<const void*>(base[side]) : ptr_of(sg.view);
-                    a.seg_pix_stride[g] = side >= 0 ? m->pix_stride(side) : m->pix_stride(sg.view.buf);
-                    a.seg_channels[g] = sg.channels; a.seg_up[g] = sg.up;
-                }
-            }
-            if (ev_mid) OM_CHECK_HIP(hipEventRecord(ev_mid, stream));
-            rc = om::launch_conv_igemm_f16(a, stream);
-        } else {
-            om::ConvArgs a;
-            a.in = static_cast<const float*>(ptr_of(L.in)); a.w = w; a.scale = scale; a.shift = shift;
-            a.res = L.has_res ? static_cast<const float*>(ptr_of(L.res)) : nullptr;
-            a.out = static_cast<float*>(ptr_of(L.out));
-            a.B = B; a.H = Hin; a.W = Win; a.cin = li.cin; a.in_pix_stride = m->pix_stride(L.in.buf);
-            a.Ho = Hin / li.stride; a.Wo = Win / li.stride; a.cout = li.cout; a.cout_pad = li.cout_pad;
-            a.ks = li.ksize; a.stride = li.stride; a.leaky = li.leaky;
-            a.res_pix_stride = L.has_res ? m->pix_stride(L.res.buf) : 0;
-            a.out_pix_stride = m->pix_stride(L.out.buf);
-            a.out_mode = L.out_mode; a.up = L.up;
-            a.ticket = tickets + (&L - m->layers.data()) * om::SYNC_WORDS;
-            a.sk_partial = sk_partial;
-            a.status = status;
-            a.ksplit_max = (m->precision == 1 && m->direct_3x3(B, H, W)) ? m->latency_ksplit : 0;      // latency mode only
-            if (li.wino_off >= 0 && om::wino_enabled()) {
-                float* wino_scratch = reinterpret_cast<float*>(static_cast<char*>(workspace) + lay.scratch_off[&L - m->layers.data()]);
-                a.mid_event = ev_mid;
-                if (li.wino_planes == 24 && m->precision == 1 && m->direct_3x3_layer(L, B, H, W)) {
-                    // latency mode: the same layer as a direct 3x3 convolution with split operands (implicit GEMM)
-                    a.w = m->weights_split + li.wsplit_direct_off;
-                    a.scale = m->weights_split + li.wsplit_direct_scale_off;
-                    if (ev_mid) OM_CHECK_HIP(hipEventRecord(ev_mid, stream));
-                    rc = om::launch_conv_igemm_split(a, stream);
-                } else if (li.wino_planes == 24 && m->precision == 1) {
-                    // split operands: the fused F(4,3) form, one kernel, no transformed input in memory
-                    a.w = m->weights_split + li.wsplit_off;
-                    a.scale = m->weights_split + li.wsplit_scale_off;
-                    a.split = 1;
-                    if (m->wide_3x3_layer(L, B, H, W) && om::wino14_wide_supported(a)) {
-                        rc = om::launch_conv_wino14_wide(a, wino_scratch, stream);      // (records ev_mid between its two kernels)
-                    } else {
-                        if (ev_mid) OM_CHECK_HIP(hipEventRecord(ev_mid, stream));
-                        rc = om::launch_conv_wino14_split(a, stream);
-                    }
-                } else if (li.wino_planes == 24 && m->use_f24(B, H, W)) {
-                    a.w = m->weights + li.wino_off;
-                    rc = om::launch_conv_winograd24(a, wino_scratch, stream);
-                } else {
-                    a.w = m->weights + (li.wino_planes == 24 ? li.wino_alt_off : li.wino_off);
-                    rc = om::launch_conv_winograd(a, wino_scratch, stream);
-                }
-            } else {
-                if (ev_mid) OM_CHECK_HIP(hipEventRecord(ev_mid, stream));     // single-kernel layer: mid == start
-                if (m->precision == 1 && li.wino_planes != 24) {
-                    a.w = m->weights_split + li.wsplit_off;
-                    a.scale = m->weights_split + li.wsplit_scale_off;
-                    if (m->gather_active(f16)) {
-                        if (L.side >= 0) {          // up-sampling producer: one copy at its own resolution, read up-sampled
-                            a.out = reinterpret_cast<float*>(base[L.side]);
-                            a.out_pix_stride = m->pix_stride(L.side); a.out_mode = 0; a.up = 1;
-                        }
-                        a.nseg = (int)L.gather.size();
-                        for (int g = 0; g < a.nseg; ++g) {
-                            const om::LayerDef::Seg& sg = L.gather[g];
-                            const int side = sg.producer >= 0 ? m->layers[sg.producer].side : -1;
-                            a.seg_ptr[g] = side >= 0 ? reinterpret_cast<const float*>(base[side]) : static_cast<const float*>(ptr_of(sg.view));
-                            a.seg_pix_stride[g] = side >= 0 ? m->pix_stride(side) : m->pix_stride(sg.view.buf);
-                            a.seg_channels[g] = sg.channels; a.seg_up[g] = sg.up;
-                        }
-                    }
-                    rc = om::launch_conv_igemm_split(a, stream);
-                } else {
-                    rc = om::launch_conv_igemm(a, stream);
-                }
-            }
-        }
-        if (rc != OM_OK) {
-            char msg[512];
-            std::snprintf(msg, sizeof(msg), "%s", om::g_err);
-            om::set_error("layer %s: %s", li.name, msg);
-            return rc;
-        }
-        if (early && layer_index == m->head_last) {
+        // a fused form left here was refused by launch_first_layers, whole or in part: this layer runs as a kernel of its own
+        if (first_layers || p.form == om::Form::InPrevious) p = m->plan(l, B, H, W, f16, true);
+        if (int rc = run.launch_layer(l, p, ev)) return fail_in(rc, "layer", m->layers[l].info.name);
+        if (early && l == m->head_last) {
             // the box heads are complete in the caller's stream: decode + select beside the rest of the forward
             OM_CHECK_HIP(hipEventRecord(sd.ev_fork, main_stream));
             OM_CHECK_HIP(hipStreamWaitEvent(sd.side, sd.ev_fork, 0));
@@ -931,31 +1031,21 @@ int om_model_load_weights_f16(om_model* m, const void* packed_f16_dev, size_t by
     return OM_OK;
 }
 
-int om_layer_tile_f16(const om_model* m, int index, int B, int H, int W, int* bm, int* bn, int* algo) {
-    OM_REQUIRE(m && bm && bn && algo, OM_EINVAL, "om_layer_tile_f16: null argument");
-    OM_REQUIRE(index >= 0 && index < (int)m->layers.size(), OM_EINVAL, "om_layer_tile_f16: index %d", index);
-    const om::LayerDef& L = m->layers[index];
-    if (L.stem && m->stem2_fused_f16((size_t)index)) { *bm = 128; *bn = 64; *algo = 7; return OM_OK; }      // conv1 + conv2.0 in one kernel
-    if (L.stem) { *bm = 0; *bn = 0; *algo = 0; return OM_OK; }
-    if (index == 1 && m->stem2_fused_f16(0)) { *bm = 0; *bn = 0; *algo = 8; return OM_OK; }                // ... which this layer is part of
-    const int Hin = H / L.in_div, Win = W / L.in_div;
-    const int Ho = Hin / L.info.stride, Wo = Win / L.info.stride;
-    om::ConvArgsH a{};
-    a.B = B; a.H = Hin; a.W = Win; a.cin = L.info.cin; a.in_pix_stride = m->pix_stride(L.in.buf);
-    a.cout = L.info.cout; a.cout_pad = L.info.cout_pad; a.ks = L.info.ksize; a.stride = L.info.stride; a.out_mode = L.out_mode;
-    if (om::conv3x3_f16_supported(a)) {
-        om::conv3x3_tile_for_f16(B * Ho * Wo, L.info.cout_pad, Wo, L.info.cin / 32, bm, bn);
-        *algo = *bm == 512 ? 6 : 4;       // 6: conv3x3_f16_tall_kernel
-        return OM_OK;
-    }
-    om::conv_tile_for_f16(B * Ho * Wo, L.info.cout_pad, L.info.cin, bm, bn);
-    *algo = 1;
-    if (m->gather_active(true) && !L.gather.empty()) {      // up-sampling on read: conv_igemm_f16_kernel<..., GATHER>
-        if (!(*bm == 256 && *bn == 128)) *bm = 128;
-        *bn = 128;
-        *algo = 5;
-    }
+// om_layer_tile / om_layer_tile_f16: the layer's plan as (tile, algo code)
+static int layer_tile(const om_model* m, int index, int B, int H, int W, bool f16, int* bm, int* bn, int* algo, const char* who) {
+    OM_REQUIRE(m && bm && bn && algo, OM_EINVAL, "%s: null argument", who);
+    OM_REQUIRE(index >= 0 && index < (int)m->layers.size(), OM_EINVAL, "%s: index %d", who, index);
+    const om::LayerPlan p = m->plan(index, B, H, W, f16);
+    *bm = p.bm; *bn = p.bn; *algo = om::algo_code(p.form, f16);
     return OM_OK;
+}
+
+int om_layer_tile_f16(const om_model* m, int index, int B, int H, int W, int* bm, int* bn, int* algo) {
+    return layer_tile(m, index, B, H, W, true, bm, bn, algo, "om_layer_tile_f16");
+}
+
+int om_layer_tile(const om_model* m, int index, int B, int H, int W, int* bm, int* bn, int* algo) {
+    return layer_tile(m, index, B, H, W, false, bm, bn, algo, "om_layer_tile");
 }
 
 int om_layer_output_view(const om_model* m, int index, int B, int H, int W, int f16, size_t* byte_offset, int* channels,
@@ -1017,48 +1107,6 @@ int om_model_keep_activations(om_model* m, int keep) {
     return OM_OK;
 }
 
-int om_layer_tile(const om_model* m, int index, int B, int H, int W, int* bm, int* bn, int* algo) {
-    OM_REQUIRE(m && bm && bn && algo, OM_EINVAL, "om_layer_tile: null argument");
-    OM_REQUIRE(index >= 0 && index < (int)m->layers.size(), OM_EINVAL, "om_layer_tile: index %d", index);
-    const om::LayerDef& L = m->layers[index];
-    if (L.stem && m->stem2_fused((size_t)index)) { *bm = 128; *bn = 64; *algo = 9; return OM_OK; }      // conv1 + conv2.0 in one kernel
-    if (L.stem) { *bm = 0; *bn = 0; *algo = 0; return OM_OK; }
-    if (index == 1 && m->stem2_fused(0)) { *bm = 0; *bn = 0; *algo = 10; return OM_OK; }                // ... which this layer is part of
-    if (index == 2 && m->stem3_fused()) { *bm = 0; *bn = 0; *algo = 10; return OM_OK; }
-    if (L.info.wino_off >= 0 && om::wino_enabled() && L.info.wino_planes == 24 && m->precision == 1 && m->direct_3x3_layer(L, B, H, W)) {
-        om::conv_tile_for_split(B * (H / L.in_div) * (W / L.in_div), L.info.cout_pad, bm, bn);
-        *algo = 7;
-        return OM_OK;
-    }
-    if (L.info.wino_off >= 0 && om::wino_enabled() && L.info.wino_planes == 24 && m->precision == 1) {
-        if (m->wide_3x3_layer(L, B, H, W)) { *algo = 12; *bm = 128; *bn = 128; return OM_OK; }      // two kernels: V pre-pass + 128 x 128 tile
-        *algo = 8; *bm = 128; *bn = 64;
-        return OM_OK;
-    }
-    if (L.info.wino_off >= 0 && om::wino_enabled() && L.info.wino_planes == 24 && m->use_f24(B, H, W)) {
-        *algo = 5; *bm = 64; *bn = 64;
-        return OM_OK;
-    }
-    if (L.info.wino_off >= 0 && om::wino_enabled()) {
-        const int Hl = H / L.in_div, Wl = W / L.in_div;
-        *algo = om::wino_fused_for(L.info.cin) ? 3 : 2;
-        *bm = 64;
-        *bn = *algo == 3 ? (L.info.cout_pad % 128 == 0 ? 128 : 64)
-                         : om::wino_bn((long long)B * ((Hl + 1) / 2) * ((Wl + 1) / 2), L.info.cout_pad);
-        return OM_OK;
-    }
-    const int Ho = H / L.in_div / L.info.stride, Wo = W / L.in_div / L.info.stride;
-    if (m->precision == 1 && L.info.wino_planes != 24) {
-        om::conv_tile_for_split(B * Ho * Wo, L.info.cout_pad, bm, bn);
-        *algo = 7;
-        if (m->gather_active(false) && !L.gather.empty()) { *bm = 128; *bn = 128; *algo = 11; }      // up-sampling on read
-        return OM_OK;
-    }
-    om::conv_tile_for(B * Ho * Wo, L.info.cout_pad, bm, bn);
-    *algo = 1;
-    return OM_OK;
-}
-
 int om_profile_enable(om_model* m, int enable) {
     OM_REQUIRE(m, OM_EINVAL, "om_profile_enable: null model");
     m->profiling = enable != 0;
@@ -1114,16 +1162,8 @@ int om_conv2d_mode(const float* in, int B, int H, int W, int cin, int in_pix_str
                "om_conv2d_mode: out_mode=%d up=%d (0 NHWC, 1 NHWC replicated up x up, 2 NCHW)", out_mode, up);
     om::ConvArgs a;
     a.in = in; a.w = w; a.scale = scale; a.shift = shift; a.res = res; a.out = out;
-    a.B = B; a.H = H; a.W = W; a.cin = cin; a.in_pix_stride = in_pix_stride;
-    a.Ho = H / stride; a.Wo = W / stride; a.cout = cout; a.cout_pad = om::round_up(cout, 32);
-    a.ks = ksize; a.stride = stride; a.leaky = leaky; a.res_pix_stride = res_pix_stride;
-    a.out_pix_stride = out_pix_stride; a.out_mode = out_mode; a.up = up;
-    // unit-test entry only: a library-owned ticket word so that the persistent tile queue (what om_forward
-    // uses, with tickets carved from the caller's workspace) is what gets tested and benchmarked
-    static int* g_ticket = nullptr;
-    if (!g_ticket) OM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&g_ticket), om::SYNC_WORDS * sizeof(int)));
-    if (int rc = om::launch_zero_words(g_ticket, om::SYNC_WORDS, static_cast<hipStream_t>(stream))) return rc;
-    a.ticket = g_ticket;
+    om::fill_conv_shape(a, B, H, W, cin, in_pix_stride, cout, om::round_up(cout, 32), ksize, stride, leaky, res_pix_stride, out_pix_stride, out_mode, up);
+    if (int rc = unit_ticket(static_cast<hipStream_t>(stream), &a.ticket)) return rc;
     return om::launch_conv_igemm(a, static_cast<hipStream_t>(stream));
 }
 
@@ -1137,15 +1177,9 @@ int om_conv2d_split(const float* in, int B, int H, int W, int cin, int in_pix_st
                "om_conv2d_split: out_mode=%d up=%d (0 NHWC, 1 NHWC replicated up x up, 2 NCHW)", out_mode, up);
     om::ConvArgs a;
     a.in = in; a.w = static_cast<const float*>(w_split); a.scale = scale_split; a.shift = shift; a.res = res; a.out = out;
-    a.B = B; a.H = H; a.W = W; a.cin = cin; a.in_pix_stride = in_pix_stride;
-    a.Ho = H / stride; a.Wo = W / stride; a.cout = cout; a.cout_pad = om::round_up(cout, 32);
-    a.ks = ksize; a.stride = stride; a.leaky = leaky; a.res_pix_stride = res_pix_stride;
-    a.out_pix_stride = out_pix_stride; a.out_mode = out_mode; a.up = up;
+    om::fill_conv_shape(a, B, H, W, cin, in_pix_stride, cout, om::round_up(cout, 32), ksize, stride, leaky, res_pix_stride, out_pix_stride, out_mode, up);
     a.force_bm = tile_bm; a.force_bn = tile_bn; a.status = status_dev;
-    static int* g_ticket = nullptr;      // unit-test entry only (see om_conv2d_mode)
-    if (!g_ticket) OM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&g_ticket), om::SYNC_WORDS * sizeof(int)));
-    if (int rc = om::launch_zero_words(g_ticket, om::SYNC_WORDS, static_cast<hipStream_t>(stream))) return rc;
-    a.ticket = g_ticket;
+    if (int rc = unit_ticket(static_cast<hipStream_t>(stream), &a.ticket)) return rc;
     return om::launch_conv_igemm_split(a, static_cast<hipStream_t>(stream));
 }
 
@@ -1160,19 +1194,13 @@ int om_conv2d_split_k(const float* in, int B, int H, int W, int cin, int in_pix_
     OM_REQUIRE(max_parts >= 1 && max_parts <= 8, OM_EINVAL, "om_conv2d_split_k: max_parts=%d (1 .. 8)", max_parts);
     om::ConvArgs a;
     a.in = in; a.w = static_cast<const float*>(w_split); a.scale = scale_split; a.shift = shift; a.res = res; a.out = out;
-    a.B = B; a.H = H; a.W = W; a.cin = cin; a.in_pix_stride = in_pix_stride;
-    a.Ho = H / stride; a.Wo = W / stride; a.cout = cout; a.cout_pad = om::round_up(cout, 32);
-    a.ks = ksize; a.stride = stride; a.leaky = leaky; a.res_pix_stride = res_pix_stride;
-    a.out_pix_stride = out_pix_stride; a.out_mode = out_mode; a.up = up;
+    om::fill_conv_shape(a, B, H, W, cin, in_pix_stride, cout, om::round_up(cout, 32), ksize, stride, leaky, res_pix_stride, out_pix_stride, out_mode, up);
     a.force_bm = tile_bm; a.force_bn = tile_bn; a.status = status_dev;
     a.ksplit_max = max_parts;
-    // unit-test entry only (see om_conv2d_mode): library-owned sync words and room for 512 parts of 128 x 64 floats
-    static int* g_ticket = nullptr;
+    // unit-test entry only: room of the library's own for 512 parts of 128 x 64 floats
     static float* g_partial = nullptr;
-    if (!g_ticket) OM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&g_ticket), om::SYNC_WORDS * sizeof(int)));
     if (!g_partial) OM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&g_partial), (size_t)512 * 128 * 64 * sizeof(float)));
-    if (int rc = om::launch_zero_words(g_ticket, om::SYNC_WORDS, static_cast<hipStream_t>(stream))) return rc;
-    a.ticket = g_ticket;
+    if (int rc = unit_ticket(static_cast<hipStream_t>(stream), &a.ticket)) return rc;
     a.sk_partial = g_partial;
     return om::launch_conv_igemm_split(a, static_cast<hipStream_t>(stream));
 }
@@ -1184,21 +1212,16 @@ int om_conv2d_split_gather(int nseg, const float* const* seg_ptr, const int* seg
                "om_conv2d_split_gather: bad shape / null segment table (nseg=%d)", nseg);
     om::ConvArgs a;
     a.in = nullptr; a.w = static_cast<const float*>(w_split); a.scale = scale_split; a.shift = shift; a.res = nullptr; a.out = out;
-    a.B = B; a.H = H; a.W = W; a.cin = 0; a.in_pix_stride = 0;
     a.nseg = nseg;
+    int cin = 0;
     for (int g = 0; g < nseg; ++g) {
         a.seg_ptr[g] = seg_ptr[g]; a.seg_channels[g] = seg_channels[g]; a.seg_pix_stride[g] = seg_pix_stride[g]; a.seg_up[g] = seg_up[g];
-        a.cin += seg_channels[g];
+        cin += seg_channels[g];
     }
-    OM_REQUIRE(a.cin > 0 && a.cin % 32 == 0, OM_EINVAL, "om_conv2d_split_gather: %d input channels", a.cin);
-    a.Ho = H; a.Wo = W; a.cout = cout; a.cout_pad = om::round_up(cout, 32);
-    a.ks = 1; a.stride = 1; a.leaky = leaky; a.res_pix_stride = 0;
-    a.out_pix_stride = out_pix_stride; a.out_mode = 0; a.up = 1;
+    OM_REQUIRE(cin > 0 && cin % 32 == 0, OM_EINVAL, "om_conv2d_split_gather: %d input channels", cin);
+    om::fill_conv_shape(a, B, H, W, cin, 0, cout, om::round_up(cout, 32), 1, 1, leaky, 0, out_pix_stride);
     a.status = status_dev;
-    static int* g_ticket = nullptr;      // unit-test entry only (see om_conv2d_mode)
-    if (!g_ticket) OM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&g_ticket), om::SYNC_WORDS * sizeof(int)));
-    if (int rc = om::launch_zero_words(g_ticket, om::SYNC_WORDS, static_cast<hipStream_t>(stream))) return rc;
-    a.ticket = g_ticket;
+    if (int rc = unit_ticket(static_cast<hipStream_t>(stream), &a.ticket)) return rc;
     return om::launch_conv_igemm_split(a, static_cast<hipStream_t>(stream));
 }
 
@@ -1223,14 +1246,8 @@ int om_conv2d_winograd(const float* in, int B, int H, int W, int cin, int in_pix
                "om_conv2d_winograd: scratch too small");
     om::ConvArgs a;
     a.in = in; a.w = u; a.scale = scale; a.shift = shift; a.res = res; a.out = out;
-    a.B = B; a.H = H; a.W = W; a.cin = cin; a.in_pix_stride = in_pix_stride;
-    a.Ho = H; a.Wo = W; a.cout = cout; a.cout_pad = om::round_up(cout, 64);
-    a.ks = 3; a.stride = 1; a.leaky = leaky; a.res_pix_stride = res_pix_stride;
-    a.out_pix_stride = out_pix_stride; a.out_mode = 0; a.up = 1;
-    static int* g_ticket = nullptr;
-    if (!g_ticket) OM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&g_ticket), om::SYNC_WORDS * sizeof(int)));
-    if (int rc = om::launch_zero_words(g_ticket, om::SYNC_WORDS, static_cast<hipStream_t>(stream))) return rc;
-    a.ticket = g_ticket;
+    om::fill_conv_shape(a, B, H, W, cin, in_pix_stride, cout, om::round_up(cout, 64), 3, 1, leaky, res_pix_stride, out_pix_stride);
+    if (int rc = unit_ticket(static_cast<hipStream_t>(stream), &a.ticket)) return rc;
     return om::launch_conv_winograd(a, static_cast<float*>(scratch), static_cast<hipStream_t>(stream));
 }
 
@@ -1241,14 +1258,9 @@ int om_conv2d_f16(const void* in, int B, int H, int W, int cin, int in_pix_strid
                "om_conv2d_f16: bad shape");
     om::ConvArgsH a;
     a.in = in; a.w = w; a.scale = scale; a.shift = shift; a.res = res; a.out = out;
-    a.B = B; a.H = H; a.W = W; a.cin = cin; a.in_pix_stride = in_pix_stride;
-    a.Ho = H / stride; a.Wo = W / stride; a.cout = cout; a.cout_pad = om::round_up(cout, 32);
-    a.ks = ksize; a.stride = stride; a.leaky = leaky; a.res_pix_stride = res_pix_stride;
-    a.out_pix_stride = out_pix_stride; a.out_mode = 0; a.up = 1; a.out_f32 = out_f32;
-    static int* g_ticket = nullptr;
-    if (!g_ticket) OM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&g_ticket), om::SYNC_WORDS * sizeof(int)));
-    if (int rc = om::launch_zero_words(g_ticket, om::SYNC_WORDS, static_cast<hipStream_t>(stream))) return rc;
-    a.ticket = g_ticket;
+    om::fill_conv_shape(a, B, H, W, cin, in_pix_stride, cout, om::round_up(cout, 32), ksize, stride, leaky, res_pix_stride, out_pix_stride);
+    a.out_f32 = out_f32;
+    if (int rc = unit_ticket(static_cast<hipStream_t>(stream), &a.ticket)) return rc;
     return om::launch_conv_igemm_f16(a, static_cast<hipStream_t>(stream));
 }
 
@@ -1257,22 +1269,9 @@ int om_conv2d_stem_f16(const float* in, int B, int H, int W, const float* w, con
     return om::launch_conv_stem_f16(in, B, H, W, w, scale, shift, cout, out, static_cast<hipStream_t>(stream));
 }
 
-static int conv2d_winograd24_impl(const float* in, int B, int H, int W, int cin, int in_pix_stride, const float* u,
-                                  const float* scale, const float* shift, int cout, int leaky, const float* res,
-                                  int res_pix_stride, float* out, int out_pix_stride, void* scratch, size_t scratch_bytes,
-                                  om_stream stream, int split, int32_t* status_dev);
-
 size_t om_conv2d_winograd24_scratch_bytes(int B, int H, int W, int cin) {
     if (B <= 0 || H <= 0 || W <= 0 || cin <= 0) return 0;
     return om::align_up(om::wino24_scratch_floats(B, H, W, cin) * sizeof(float), 256) + om::SK_PARTIAL_BYTES;
-}
-
-int om_conv2d_winograd24(const float* in, int B, int H, int W, int cin, int in_pix_stride, const float* u,
-                         const float* scale, const float* shift, int cout, int leaky, const float* res,
-                         int res_pix_stride, float* out, int out_pix_stride, void* scratch, size_t scratch_bytes,
-                         om_stream stream) {
-    return conv2d_winograd24_impl(in, B, H, W, cin, in_pix_stride, u, scale, shift, cout, leaky, res, res_pix_stride, out,
-                                  out_pix_stride, scratch, scratch_bytes, stream, 0, nullptr);
 }
 
 static int conv2d_winograd24_impl(const float* in, int B, int H, int W, int cin, int in_pix_stride, const float* u,
@@ -1284,16 +1283,19 @@ static int conv2d_winograd24_impl(const float* in, int B, int H, int W, int cin,
                "om_conv2d_winograd24: scratch too small");
     om::ConvArgs a;
     a.in = in; a.w = u; a.scale = scale; a.shift = shift; a.res = res; a.out = out;
-    a.B = B; a.H = H; a.W = W; a.cin = cin; a.in_pix_stride = in_pix_stride;
-    a.Ho = H; a.Wo = W; a.cout = cout; a.cout_pad = om::round_up(cout, 64);
-    a.ks = 3; a.stride = 1; a.leaky = leaky; a.res_pix_stride = res_pix_stride;
-    a.out_pix_stride = out_pix_stride; a.out_mode = 0; a.up = 1; a.split = split; a.status = status_dev;
-    static int* g_ticket = nullptr;
-    if (!g_ticket) OM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&g_ticket), om::SYNC_WORDS * sizeof(int)));
-    if (int rc = om::launch_zero_words(g_ticket, om::SYNC_WORDS, static_cast<hipStream_t>(stream))) return rc;
-    a.ticket = g_ticket;
+    om::fill_conv_shape(a, B, H, W, cin, in_pix_stride, cout, om::round_up(cout, 64), 3, 1, leaky, res_pix_stride, out_pix_stride);
+    a.split = split; a.status = status_dev;
+    if (int rc = unit_ticket(static_cast<hipStream_t>(stream), &a.ticket)) return rc;
     a.sk_partial = reinterpret_cast<float*>(static_cast<char*>(scratch) + om::align_up(om::wino24_scratch_floats(B, H, W, cin) * sizeof(float), 256));
     return om::launch_conv_winograd24(a, static_cast<float*>(scratch), static_cast<hipStream_t>(stream));
+}
+
+int om_conv2d_winograd24(const float* in, int B, int H, int W, int cin, int in_pix_stride, const float* u,
+                         const float* scale, const float* shift, int cout, int leaky, const float* res,
+                         int res_pix_stride, float* out, int out_pix_stride, void* scratch, size_t scratch_bytes,
+                         om_stream stream) {
+    return conv2d_winograd24_impl(in, B, H, W, cin, in_pix_stride, u, scale, shift, cout, leaky, res, res_pix_stride, out,
+                                  out_pix_stride, scratch, scratch_bytes, stream, 0, nullptr);
 }
 
 int om_conv2d_winograd24_split(const float* in, int B, int H, int W, int cin, int in_pix_stride, const void* u_split,
@@ -1310,14 +1312,9 @@ int om_conv2d_wino14_split(const float* in, int B, int H, int W, int cin, int in
     OM_REQUIRE(B > 0 && H > 0 && W > 0, OM_EINVAL, "om_conv2d_wino14_split: bad shape");
     om::ConvArgs a;
     a.in = in; a.w = static_cast<const float*>(u14_split); a.scale = scale_split; a.shift = shift; a.res = res; a.out = out;
-    a.B = B; a.H = H; a.W = W; a.cin = cin; a.in_pix_stride = in_pix_stride;
-    a.Ho = H; a.Wo = W; a.cout = cout; a.cout_pad = om::round_up(cout, 64);
-    a.ks = 3; a.stride = 1; a.leaky = leaky; a.res_pix_stride = res_pix_stride;
-    a.out_pix_stride = out_pix_stride; a.out_mode = 0; a.up = 1; a.split = 1; a.status = status_dev;
-    static int* g_ticket = nullptr;      // unit-test entry only (see om_conv2d_mode)
-    if (!g_ticket) OM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&g_ticket), om::SYNC_WORDS * sizeof(int)));
-    if (int rc = om::launch_zero_words(g_ticket, om::SYNC_WORDS, static_cast<hipStream_t>(stream))) return rc;
-    a.ticket = g_ticket;
+    om::fill_conv_shape(a, B, H, W, cin, in_pix_stride, cout, om::round_up(cout, 64), 3, 1, leaky, res_pix_stride, out_pix_stride);
+    a.split = 1; a.status = status_dev;
+    if (int rc = unit_ticket(static_cast<hipStream_t>(stream), &a.ticket)) return rc;
     return om::launch_conv_wino14_split(a, static_cast<hipStream_t>(stream));
 }
 
@@ -1335,23 +1332,18 @@ int om_conv2d_wino14_wide(const float* in, int B, int H, int W, int cin, int in_
                "om_conv2d_wino14_wide: scratch too small");
     om::ConvArgs a;
     a.in = in; a.w = static_cast<const float*>(u14_split); a.scale = scale_split; a.shift = shift; a.res = res; a.out = out;
-    a.B = B; a.H = H; a.W = W; a.cin = cin; a.in_pix_stride = in_pix_stride;
-    a.Ho = H; a.Wo = W; a.cout = cout; a.cout_pad = om::round_up(cout, 64);
-    a.ks = 3; a.stride = 1; a.leaky = leaky; a.res_pix_stride = res_pix_stride;
-    a.out_pix_stride = out_pix_stride; a.out_mode = 0; a.up = 1; a.split = 1; a.status = status_dev;
-    static int* g_ticket = nullptr;      // unit-test entry only (see om_conv2d_mode)
-    if (!g_ticket) OM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&g_ticket), om::SYNC_WORDS * sizeof(int)));
-    if (int rc = om::launch_zero_words(g_ticket, om::SYNC_WORDS, static_cast<hipStream_t>(stream))) return rc;
-    a.ticket = g_ticket;
+    om::fill_conv_shape(a, B, H, W, cin, in_pix_stride, cout, om::round_up(cout, 64), 3, 1, leaky, res_pix_stride, out_pix_stride);
+    a.split = 1; a.status = status_dev;
+    if (int rc = unit_ticket(static_cast<hipStream_t>(stream), &a.ticket)) return rc;
     return om::launch_conv_wino14_wide(a, static_cast<float*>(scratch), static_cast<hipStream_t>(stream));
 }
 
 int om_set_wino14_wide(int on) {
     OM_REQUIRE(on == 0 || on == 1, OM_EINVAL, "om_set_wino14_wide: %d", on);
-    g_wino14_wide = on;
+    switch_flag(SW_W14_WIDE) = on;
     return OM_OK;
 }
-int om_get_wino14_wide(void) { return wino14_wide_on() ? 1 : 0; }
+int om_get_wino14_wide(void) { return switch_on(SW_W14_WIDE) ? 1 : 0; }
 
 int om_wino14_dual_built(void) {
 #ifdef OM_WITH_W14D
@@ -1389,13 +1381,13 @@ int om_get_wino14_variant(void) { return om::wino14_variant(); }
 
 int om_set_stem_fusion(int which, int on) {
     OM_REQUIRE((which == 0 || which == 1) && (on == 0 || on == 1), OM_EINVAL, "om_set_stem_fusion: which=%d on=%d", which, on);
-    om_model::stem_fusion_flag(which) = on;
+    switch_flag(which) = on;
     return OM_OK;
 }
 
 int om_get_stem_fusion(int which) {
     if (which != 0 && which != 1) return -1;
-    return om_model::stem_fusion_on(which) ? 1 : 0;
+    return switch_on(which) ? 1 : 0;
 }
 
 int om_get_conv3x3_f16_variant(void) { return om::conv3x3_f16_get_tall(); }

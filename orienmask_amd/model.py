@@ -462,7 +462,7 @@ class OrienMaskYOLOFPNPlus(nn.Module):
             _lib.check(_lib.load().om_layer_tile(h, i, B, H, W, ctypes.byref(bm), ctypes.byref(bn), ctypes.byref(algo)),
                        "om_layer_tile")
             fmt = {0: "conv_stem_kernel", 1: "conv_igemm_f32_kernel<%d,%d>", 2: "wino_gemm_kernel<%d,%d>",
-                   3: "wino_fused_kernel<%d,%d>", 5: "wino24_gemm_kernel<%d,%d>", 6: "wino24_gemm_kernel<%d,%d,split>",
+                   3: "wino_fused_kernel<%d,%d>", 5: "wino24_gemm_kernel<%d,%d>",
                    7: "conv_igemm_split_kernel<%d,%d>", 8: "wino14_split_kernel<%d,%d>",
                    9: "conv_stem2_split_kernel<%d,%d>", 10: "(in the previous layer's kernel)",
                    11: "conv_igemm_split_kernel<%d,%d,gather>", 12: "wino14_wide_kernel<%d,%d>"}[algo.value]
