@@ -743,6 +743,33 @@ int om_bn_act_backward(const float* x, const float* dy, int B, int C, int H, int
                        const float* save_mean, const float* save_invstd, int training, float slope, float* dx, float* dgamma,
                        float* dbeta, void* workspace, size_t ws_bytes, om_stream stream);
 
+/* ---- The same block with batch statistics over R ranks (torch.nn.SyncBatchNorm; trainer/builder.py:85-87), as four staged calls
+ *      with the caller's collectives between them.  Tensors, save vectors, arithmetic and workspace as above; R >= 1.
+ *      om_bn_sync_stats: this rank's per-channel RECORD, doubles [3][C]: n = B*H*W, mean = K + s1/n, M2 = s2 - s1*(s1/n) clamped at
+ *      0, with K the channel's first element and s1, s2 the sums of (x-K), (x-K)^2 in the unsynchronised kernel's order; B*H*W >= 1.
+ *      om_bn_sync_forward: `records` is [R][3][C], the all-gather of every rank's record.  Per channel the records are merged in rank
+ *      order, starting from record 0: delta = mean_r - mean, M2 += M2_r + delta*delta*n*n_r/(n+n_r), mean += delta*n_r/(n+n_r),
+ *      n += n_r.  Then var = M2/N, invstd = 1/sqrt(var+eps), the running buffers take mean and var*N/(N-1), the counter is
+ *      incremented, the save vectors are written, *n_total_out (device) = N, y as above.  Every rank merges the same bytes in the same
+ *      order: save vectors and running buffers are bit-identical across ranks.  Every rank holds at least one value per channel, so
+ *      N >= B*H*W + R - 1; a call for which that is below 2 is refused.
+ *      om_bn_sync_backward_sums: this rank's doubles [2][C] = (sum dz, sum dz * xhat), and its own float32 dgamma / dbeta (they stay
+ *      local, as in torch's SyncBatchNorm: DistributedDataParallel averages them).
+ *      om_bn_sync_backward_dx: `sums_all` is [R][2][C], summed in rank order; n_total the device double of the forward;
+ *      dx = gamma * invstd * (dz - Sdz/N - xhat * Sdzxhat/N).
+ *      With R == 1, records = this rank's record and sums_all = its sums, every output has the bits of om_bn_act_forward /
+ *      om_bn_act_backward.  Three passes over the activation forward, five backward; no atomics, no host synchronisation. */
+int om_bn_sync_stats(const float* x, int B, int C, int H, int W, double* record, void* workspace, size_t ws_bytes, om_stream stream);
+int om_bn_sync_forward(const float* x, int B, int C, int H, int W, const double* records, int R, const float* gamma, const float* beta,
+                       float* running_mean, float* running_var, int64_t* num_batches_tracked, double momentum, double eps, float slope,
+                       const float* residual, float* y, float* save_mean, float* save_invstd, double* n_total_out, om_stream stream);
+int om_bn_sync_backward_sums(const float* x, const float* dy, int B, int C, int H, int W, const float* gamma, const float* beta,
+                             const float* save_mean, const float* save_invstd, float slope, double* sums, float* dgamma, float* dbeta,
+                             void* workspace, size_t ws_bytes, om_stream stream);
+int om_bn_sync_backward_dx(const float* x, const float* dy, int B, int C, int H, int W, const float* gamma, const float* beta,
+                           const float* save_mean, const float* save_invstd, float slope, const double* sums_all, int R,
+                           const double* n_total, float* dx, om_stream stream);
+
 /* ---- Several batches in flight.  Every entry point only enqueues kernels on the caller's stream and keeps no per-call state in
  *      the model handle (profiling apart): om_forward / om_forward_f16 / om_postprocess may be issued for different batches
  *      on different HIP streams at the same time, provided each batch in flight has its OWN workspace (and output buffers);

@@ -95,14 +95,23 @@ def build_optimizer(config, accumulate, model, is_distributed=False):
 def build_train_model(config, is_distributed=False, ignore_pretrained=False):
     """trainer/builder.py:80-88 against orienmask_amd.train: the model of config (a reference `model` dict, optionally with
     `backend`) on the current device, in training mode as a freshly built nn.Module is.  The caller's dict is not mutated.
-    is_distributed=True raises: the reference converts to SyncBatchNorm there (statistics reduced across ranks), which the HIP
-    block does not do."""
+    is_distributed=True is the reference's lines 85-87: the blocks are converted to synchronised batch statistics
+    (train.convert_sync_batchnorm, the default process group) and the model is returned inside DistributedDataParallel on the
+    current device.  It needs an initialised default process group and raises NotImplementedError without one."""
     import torch
     from . import train as _train
     if is_distributed:
-        raise NotImplementedError("build_train_model(is_distributed=True): SyncBatchNorm / DistributedDataParallel are not supported")
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()):
+            raise NotImplementedError("build_train_model(is_distributed=True): SyncBatchNorm / DistributedDataParallel need an initialised "
+                                      "default process group; call torch.distributed.init_process_group first")
     cfg = dict(config)
     if ignore_pretrained:
         cfg["pretrained"] = None
     net = build(cfg, _train)
-    return net.to(torch.device("cuda", torch.cuda.current_device()))
+    dev = torch.device("cuda", torch.cuda.current_device())
+    net = net.to(dev)
+    if is_distributed:
+        from torch.nn.parallel import DistributedDataParallel
+        net = DistributedDataParallel(_train.convert_sync_batchnorm(net), device_ids=[dev.index])
+    return net

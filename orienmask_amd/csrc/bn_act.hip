@@ -6,6 +6,7 @@
 //                   phase FUSED   both in one launch, one workgroup per channel (small layers are launch-bound)
 //                   phase EVAL    APPLY with the running statistics; no buffer changes
 //   bn_bwd_kernel   the same three phases for (sum dz, sum dz * (x - mean)) and dx; the LeakyReLU mask is recomputed from x
+//   bn_sync_*       the phases as separate entry points with the cross-rank all-gather between them (SyncBatchNorm), further down
 // A channel is B planes of H*W floats.  Work is counted in UNITS of V floats (V = 4 where H*W is a multiple of 4 and every tensor is
 // 16-byte aligned, else 1): unit u of channel c lies in plane u / (HW/V), so a unit never straddles planes and one 32-bit division
 // serves 16 bytes.  A workgroup takes tiles of BN_THREADS * BN_UNROLL units, strided by the number of workgroups of its channel,
@@ -339,6 +340,103 @@ __global__ void __launch_bounds__(BN_THREADS) bn_bwd_kernel(BnBwdArgs a, BnGeom 
     bwd_apply<V>(a, g, c, s, S, ch, c1, c2);
 }
 
+// ---------------------------------------------------------------------------------------------------------------- several ranks
+// The same two phases with the cross-rank exchange between them (SyncBatchNorm).  Each rank reduces its own slice of the batch to a
+// per-channel RECORD of doubles [3][C] = (n, mean, M2 = sum (x - mean)^2); the caller all-gathers the records, and every rank merges
+// the SAME R records in rank order with the pairwise formula, so the statistics and the running buffers have the same bits on every
+// rank without a broadcast.  The backward exchanges (sum dz, sum dz * xhat) the same way.  With R == 1 every expression below is the
+// unsynchronised kernel's: the record holds K + s1/n and s2 - s1 * (s1/n), and var = M2 / n.
+template <int V>
+__global__ void __launch_bounds__(BN_THREADS) bn_sync_stats_kernel(BnFwdArgs a, BnGeom g, double* __restrict__ record) {
+    __shared__ double lds[8];
+    const int c = blockIdx.y;
+    const float K = a.x[(size_t)c * g.plane_units * V];          // the channel's first element on this rank
+    double s1, s2;
+    if (a.splits > 0) {
+        sum_partials(a.partial, c, a.splits, s1, s2, lds);
+    } else {
+        fwd_sums<V>(a, g, c, 0, 1, K, s1, s2);
+        block_sum2(s1, s2, lds);
+    }
+    if (threadIdx.x != 0) return;
+    const double shifted = s1 / g.n;
+    double m2 = s2 - s1 * shifted;
+    if (m2 < 0.0) m2 = 0.0;
+    record[c] = g.n;
+    record[g.C + c] = (double)K + shifted;
+    record[2 * g.C + c] = m2;
+}
+
+template <int V>
+__global__ void __launch_bounds__(BN_THREADS) bn_sync_fwd_kernel(BnFwdArgs a, BnGeom g, const double* __restrict__ records, int R,
+                                                                 double* __restrict__ n_total_out) {
+    const int s = blockIdx.x, S = gridDim.x, c = blockIdx.y;
+    // every workgroup of every rank merges the same doubles in the same order
+    double n = records[c], mean_d = records[g.C + c], m2 = records[2 * g.C + c];
+    for (int r = 1; r < R; ++r) {
+        const double* rec = records + (size_t)r * 3 * g.C;
+        const double nr = rec[c], delta = rec[g.C + c] - mean_d, tot = n + nr;
+        m2 += rec[2 * g.C + c] + delta * delta * n * nr / tot;
+        mean_d += delta * nr / tot;
+        n = tot;
+    }
+    const double var_d = m2 / n;                                    // biased
+    float mean_hi, mean_lo, invstd_hi, invstd_lo;
+    split_hi_lo(mean_d, mean_hi, mean_lo);
+    split_hi_lo(1.0 / sqrt(var_d + a.eps), invstd_hi, invstd_lo);
+    if (s == 0 && threadIdx.x == 0) {
+        if (a.running_mean) a.running_mean[c] = (float)(a.momentum * mean_d + (1.0 - a.momentum) * (double)a.running_mean[c]);
+        if (a.running_var) {
+            const double unbiased = var_d * (n / (n - 1.0));
+            a.running_var[c] = (float)(a.momentum * unbiased + (1.0 - a.momentum) * (double)a.running_var[c]);
+        }
+        if (c == 0) {
+            if (a.num_batches_tracked) *a.num_batches_tracked += 1;
+            *n_total_out = n;
+        }
+        a.save_mean[c] = mean_hi;   a.save_mean[g.C + c] = mean_lo;
+        a.save_invstd[c] = invstd_hi; a.save_invstd[g.C + c] = invstd_lo;
+    }
+    const BnChannel ch = bn_channel(mean_hi, mean_lo, invstd_hi, invstd_lo, a.gamma[c], a.beta[c]);
+    fwd_apply<V>(a, g, c, s, S, ch);
+}
+
+// sums: [2][C] doubles (sum dz, sum dz * xhat) of this rank; dgamma / dbeta are this rank's own, as in torch's SyncBatchNorm
+template <int V>
+__global__ void __launch_bounds__(BN_THREADS) bn_sync_bwd_sums_kernel(BnBwdArgs a, BnGeom g, double* __restrict__ sums) {
+    __shared__ double lds[8];
+    const int c = blockIdx.y;
+    const BnChannel ch = bn_channel(a.save_mean[c], a.save_mean[g.C + c], a.save_invstd[c], a.save_invstd[g.C + c], a.gamma[c], a.beta[c]);
+    double sb, sg;
+    if (a.splits > 0) {
+        sum_partials(a.partial, c, a.splits, sb, sg, lds);
+    } else {
+        bwd_sums<V>(a, g, c, 0, 1, ch, sb, sg);
+        block_sum2(sb, sg, lds);
+    }
+    if (threadIdx.x != 0) return;
+    const double dg = sg * ch.invstd;                               // sg = sum dz * (x - mean)
+    sums[c] = sb;
+    sums[g.C + c] = dg;
+    a.dbeta[c] = (float)sb;
+    a.dgamma[c] = (float)dg;
+}
+
+template <int V>
+__global__ void __launch_bounds__(BN_THREADS) bn_sync_dx_kernel(BnBwdArgs a, BnGeom g, const double* __restrict__ sums_all, int R,
+                                                                const double* __restrict__ n_total) {
+    const int s = blockIdx.x, S = gridDim.x, c = blockIdx.y;
+    const BnChannel ch = bn_channel(a.save_mean[c], a.save_mean[g.C + c], a.save_invstd[c], a.save_invstd[g.C + c], a.gamma[c], a.beta[c]);
+    double sb = sums_all[c], dg = sums_all[g.C + c];
+    for (int r = 1; r < R; ++r) {
+        sb += sums_all[(size_t)r * 2 * g.C + c];
+        dg += sums_all[(size_t)r * 2 * g.C + g.C + c];
+    }
+    const double n = *n_total;
+    // xhat * dgamma / N = (x - mean) * (dgamma * invstd / N)
+    bwd_apply<V>(a, g, c, s, S, ch, sb / n, dg * ch.invstd / n);
+}
+
 // workgroups per channel for the two-launch form
 static int bn_splits(unsigned n_tiles, int C) {
     int per = BN_MAX_BLOCKS / C;
@@ -439,6 +537,113 @@ int om_bn_act_backward(const float* x, const float* dy, int B, int C, int H, int
         launch(S, om::BN_STATS);
         launch(dx ? S : 1, om::BN_APPLY);       // without dx only the per-channel sums are finalised
     }
+    OM_CHECK_HIP(hipGetLastError());
+    return OM_OK;
+}
+
+int om_bn_sync_stats(const float* x, int B, int C, int H, int W, double* record, void* workspace, size_t ws_bytes, om_stream stream) {
+    OM_REQUIRE(x && record, OM_EINVAL, "om_bn_sync_stats: null pointer");
+    const bool vec = ((long long)H * W) % 4 == 0 && om::aligned16(x);
+    om::BnGeom g;
+    OM_REQUIRE(om::bn_geometry(B, C, H, W, vec ? 4 : 1, &g), OM_EINVAL, "om_bn_sync_stats: shape [%d,%d,%d,%d] (C <= 65535, B*H*W < 2^31)",
+               B, C, H, W);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    om::BnFwdArgs a = {};
+    a.x = x;
+    a.partial = static_cast<double*>(workspace); a.splits = 0;
+    const int S = om::bn_splits(g.n_tiles, C);
+    if (!(g.n <= (double)om::BN_FUSED_MAX || S == 1)) {
+        OM_REQUIRE(workspace && om::aligned16(workspace) && ws_bytes >= (size_t)C * S * 2 * sizeof(double), OM_EINVAL,
+                   "om_bn_sync_stats: workspace of %zu bytes, need %zu (16-byte aligned)", ws_bytes, (size_t)C * S * 2 * sizeof(double));
+        if (vec) hipLaunchKernelGGL(om::bn_fwd_kernel<4>, dim3(S, C), dim3(om::BN_THREADS), 0, st, a, g, (int)om::BN_STATS);
+        else hipLaunchKernelGGL(om::bn_fwd_kernel<1>, dim3(S, C), dim3(om::BN_THREADS), 0, st, a, g, (int)om::BN_STATS);
+        a.splits = S;
+    }
+    if (vec) hipLaunchKernelGGL(om::bn_sync_stats_kernel<4>, dim3(1, C), dim3(om::BN_THREADS), 0, st, a, g, record);
+    else hipLaunchKernelGGL(om::bn_sync_stats_kernel<1>, dim3(1, C), dim3(om::BN_THREADS), 0, st, a, g, record);
+    OM_CHECK_HIP(hipGetLastError());
+    return OM_OK;
+}
+
+int om_bn_sync_forward(const float* x, int B, int C, int H, int W, const double* records, int R, const float* gamma, const float* beta,
+                       float* running_mean, float* running_var, int64_t* num_batches_tracked, double momentum, double eps, float slope,
+                       const float* residual, float* y, float* save_mean, float* save_invstd, double* n_total_out, om_stream stream) {
+    OM_REQUIRE(x && records && gamma && beta && y && save_mean && save_invstd && n_total_out, OM_EINVAL, "om_bn_sync_forward: null pointer");
+    OM_REQUIRE(R >= 1, OM_EINVAL, "om_bn_sync_forward: R = %d ranks, need at least 1", R);
+    OM_REQUIRE(y != x && y != residual, OM_EINVAL, "om_bn_sync_forward: y must not alias x or the residual (x is what the backward reads)");
+    OM_REQUIRE(eps > 0.0 && momentum >= 0.0 && momentum <= 1.0, OM_EINVAL, "om_bn_sync_forward: eps %g, momentum %g", eps, momentum);
+    const bool vec = ((long long)H * W) % 4 == 0 && om::aligned16(x) && om::aligned16(y) && om::aligned16(residual);
+    om::BnGeom g;
+    OM_REQUIRE(om::bn_geometry(B, C, H, W, vec ? 4 : 1, &g), OM_EINVAL, "om_bn_sync_forward: shape [%d,%d,%d,%d] (C <= 65535, B*H*W < 2^31)",
+               B, C, H, W);
+    // every rank contributes at least one value per channel, so N >= B*H*W + R - 1
+    OM_REQUIRE(g.n + (double)(R - 1) >= 2.0, OM_EINVAL,
+               "om_bn_sync_forward: training needs more than 1 value per channel over all ranks, got shape [%d,%d,%d,%d] on %d rank(s)",
+               B, C, H, W, R);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    om::BnFwdArgs a = {};
+    a.x = x; a.gamma = gamma; a.beta = beta; a.residual = residual;
+    a.running_mean = running_mean; a.running_var = running_var; a.num_batches_tracked = reinterpret_cast<long long*>(num_batches_tracked);
+    a.y = y; a.save_mean = save_mean; a.save_invstd = save_invstd;
+    a.momentum = momentum; a.eps = eps; a.slope = slope;
+    int S = om::bn_splits(g.n_tiles, C);
+    if (g.n <= (double)om::BN_FUSED_MAX) S = 1;
+    if (vec) hipLaunchKernelGGL(om::bn_sync_fwd_kernel<4>, dim3(S, C), dim3(om::BN_THREADS), 0, st, a, g, records, R, n_total_out);
+    else hipLaunchKernelGGL(om::bn_sync_fwd_kernel<1>, dim3(S, C), dim3(om::BN_THREADS), 0, st, a, g, records, R, n_total_out);
+    OM_CHECK_HIP(hipGetLastError());
+    return OM_OK;
+}
+
+int om_bn_sync_backward_sums(const float* x, const float* dy, int B, int C, int H, int W, const float* gamma, const float* beta,
+                             const float* save_mean, const float* save_invstd, float slope, double* sums, float* dgamma, float* dbeta,
+                             void* workspace, size_t ws_bytes, om_stream stream) {
+    OM_REQUIRE(x && dy && gamma && beta && save_mean && save_invstd && sums && dgamma && dbeta, OM_EINVAL,
+               "om_bn_sync_backward_sums: null pointer");
+    const bool vec = ((long long)H * W) % 4 == 0 && om::aligned16(x) && om::aligned16(dy);
+    om::BnGeom g;
+    OM_REQUIRE(om::bn_geometry(B, C, H, W, vec ? 4 : 1, &g), OM_EINVAL,
+               "om_bn_sync_backward_sums: shape [%d,%d,%d,%d] (C <= 65535, B*H*W < 2^31)", B, C, H, W);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    om::BnBwdArgs a = {};
+    a.x = x; a.dy = dy; a.gamma = gamma; a.beta = beta; a.save_mean = save_mean; a.save_invstd = save_invstd;
+    a.dgamma = dgamma; a.dbeta = dbeta;
+    a.partial = static_cast<double*>(workspace); a.splits = 0;
+    a.training = 1; a.slope = slope;
+    const int S = om::bn_splits(g.n_tiles, C);
+    if (!(g.n <= (double)om::BN_FUSED_MAX || S == 1)) {
+        OM_REQUIRE(workspace && om::aligned16(workspace) && ws_bytes >= (size_t)C * S * 2 * sizeof(double), OM_EINVAL,
+                   "om_bn_sync_backward_sums: workspace of %zu bytes, need %zu (16-byte aligned)", ws_bytes,
+                   (size_t)C * S * 2 * sizeof(double));
+        if (vec) hipLaunchKernelGGL(om::bn_bwd_kernel<4>, dim3(S, C), dim3(om::BN_THREADS), 0, st, a, g, (int)om::BN_STATS);
+        else hipLaunchKernelGGL(om::bn_bwd_kernel<1>, dim3(S, C), dim3(om::BN_THREADS), 0, st, a, g, (int)om::BN_STATS);
+        a.splits = S;
+    }
+    if (vec) hipLaunchKernelGGL(om::bn_sync_bwd_sums_kernel<4>, dim3(1, C), dim3(om::BN_THREADS), 0, st, a, g, sums);
+    else hipLaunchKernelGGL(om::bn_sync_bwd_sums_kernel<1>, dim3(1, C), dim3(om::BN_THREADS), 0, st, a, g, sums);
+    OM_CHECK_HIP(hipGetLastError());
+    return OM_OK;
+}
+
+int om_bn_sync_backward_dx(const float* x, const float* dy, int B, int C, int H, int W, const float* gamma, const float* beta,
+                           const float* save_mean, const float* save_invstd, float slope, const double* sums_all, int R,
+                           const double* n_total, float* dx, om_stream stream) {
+    OM_REQUIRE(x && dy && gamma && beta && save_mean && save_invstd && sums_all && n_total && dx, OM_EINVAL,
+               "om_bn_sync_backward_dx: null pointer");
+    OM_REQUIRE(R >= 1, OM_EINVAL, "om_bn_sync_backward_dx: R = %d ranks, need at least 1", R);
+    OM_REQUIRE(dx != x, OM_EINVAL, "om_bn_sync_backward_dx: dx must not alias x");
+    const bool vec = ((long long)H * W) % 4 == 0 && om::aligned16(x) && om::aligned16(dy) && om::aligned16(dx);
+    om::BnGeom g;
+    OM_REQUIRE(om::bn_geometry(B, C, H, W, vec ? 4 : 1, &g), OM_EINVAL,
+               "om_bn_sync_backward_dx: shape [%d,%d,%d,%d] (C <= 65535, B*H*W < 2^31)", B, C, H, W);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    om::BnBwdArgs a = {};
+    a.x = x; a.dy = dy; a.gamma = gamma; a.beta = beta; a.save_mean = save_mean; a.save_invstd = save_invstd;
+    a.dx = dx;
+    a.training = 1; a.slope = slope;
+    int S = om::bn_splits(g.n_tiles, C);
+    if (g.n <= (double)om::BN_FUSED_MAX) S = 1;
+    if (vec) hipLaunchKernelGGL(om::bn_sync_dx_kernel<4>, dim3(S, C), dim3(om::BN_THREADS), 0, st, a, g, sums_all, R, n_total);
+    else hipLaunchKernelGGL(om::bn_sync_dx_kernel<1>, dim3(S, C), dim3(om::BN_THREADS), 0, st, a, g, sums_all, R, n_total);
     OM_CHECK_HIP(hipGetLastError());
     return OM_OK;
 }

@@ -200,6 +200,11 @@ SIGNATURES = {
     "om_bn_act_forward": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, ctypes.c_double, ctypes.c_double, _f, _vp, _vp, _vp, _vp,
                                _vp, _sz, _vp]),
     "om_bn_act_backward": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "om_bn_sync_stats": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "om_bn_sync_forward": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double, _f, _vp, _vp,
+                                _vp, _vp, _vp, _vp]),
+    "om_bn_sync_backward_sums": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "om_bn_sync_backward_dx": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _i, _vp, _vp, _vp]),
 }
 
 _lib = None

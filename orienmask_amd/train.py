@@ -21,6 +21,10 @@ And the reference's model in training mode: ``builder.build(config["model"], ori
   OrienMaskYOLOFPNPlus         the reference's two models (model/orienmask_yolo_fpnplus.py, model/orienmask_yolo.py) built from
   OrienMaskYOLO                arch.model_convs, with the reference's state_dict keys and parameter order
 
+  convert_sync_batchnorm       the reference's nn.SyncBatchNorm.convert_sync_batchnorm (trainer/builder.py:86) for these blocks: batch
+                               statistics over every rank of a process group (om_bn_sync_*: an all-gather of per-channel double
+                               records between the block's two phases, merged in rank order on every rank)
+
 The convolutions, forward and gradients, are torch's; the up-sampling, cat and split stay torch ops.
 """
 import contextlib
@@ -37,7 +41,8 @@ from . import pack as _pack
 from .arch import DARKNET_STAGES, LEAKY_SLOPE, model_convs
 from .loss import EvalCounter, OrienMaskYOLOMultiScaleLoss as _ValuesLoss
 
-__all__ = ["OrienMaskYOLOMultiScaleLoss", "EvalCounter", "ConvBNLeaky", "bn_leaky", "OrienMaskYOLOFPNPlus", "OrienMaskYOLO"]
+__all__ = ["OrienMaskYOLOMultiScaleLoss", "EvalCounter", "ConvBNLeaky", "bn_leaky", "OrienMaskYOLOFPNPlus", "OrienMaskYOLO",
+           "convert_sync_batchnorm"]
 
 BACKENDS = ("hip", "torch")
 
@@ -211,22 +216,97 @@ class _BNAct(torch.autograd.Function):
                 dy if ctx.has_residual and ctx.needs_input_grad[3] else None, None, None)
 
 
-def bn_leaky(x, bn, residual=None, slope=LEAKY_SLOPE):
+class _SyncBNAct(torch.autograd.Function):
+    """forward(ctx, x, gamma, beta, residual, bn, slope, group) -> leaky(batch_norm(x)) (+ residual) with the batch statistics of
+    every rank of `group` (torch.nn.SyncBatchNorm's): om_bn_sync_stats, an all-gather of the 3C-double record, om_bn_sync_forward;
+    backward: om_bn_sync_backward_sums, an all-gather of the 2C-double sums, om_bn_sync_backward_dx.  Every rank merges the same
+    gathered bytes in rank order, so the running buffers stay bit-identical across ranks.  The collectives are enqueued against the
+    current stream; nothing synchronises with the host.  dgamma / dbeta are this rank's own (DistributedDataParallel averages them).
+    Without an input gradient the second all-gather and the dx kernel are skipped."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, residual, bn, slope, group):
+        import torch.distributed as dist
+        B, C, H, W = x.shape
+        dev = x.device
+        L = _lib.load()
+        R = dist.get_world_size(group)
+        y = torch.empty_like(x)
+        save = torch.empty(4 * C, dtype=torch.float32, device=dev)      # save_mean | save_invstd (include/orienmask_hip.h)
+        record = torch.empty(3 * C, dtype=torch.float64, device=dev)
+        records = torch.empty(R * 3 * C, dtype=torch.float64, device=dev)
+        n_total = torch.empty(1, dtype=torch.float64, device=dev)
+        track = bn.running_mean is not None
+        stream = _lib.current_stream_ptr(dev)
+        ws = _workspace(dev, stream, L.om_bn_act_workspace_bytes(B, C, H, W))
+        with _device(dev):
+            _lib.check(L.om_bn_sync_stats(_vp(x), B, C, H, W, _vp(record), ws.data_ptr(), ws.numel(), stream), "om_bn_sync_stats")
+            dist.all_gather_into_tensor(records, record, group=group)
+            _lib.check(L.om_bn_sync_forward(
+                _vp(x), B, C, H, W, _vp(records), R, _vp(gamma), _vp(beta), _vp(bn.running_mean), _vp(bn.running_var),
+                _vp(bn.num_batches_tracked) if track else None, float(bn.momentum), float(bn.eps), float(slope), _vp(residual),
+                _vp(y), save.data_ptr(), save.data_ptr() + 8 * C, _vp(n_total), stream), "om_bn_sync_forward")
+        ctx.save_for_backward(x, gamma, beta, save, n_total)
+        ctx.slope, ctx.has_residual, ctx.group, ctx.R = float(slope), residual is not None, group, R
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        import torch.distributed as dist
+        x, gamma, beta, save, n_total = ctx.saved_tensors
+        B, C, H, W = x.shape
+        dev = x.device
+        L = _lib.load()
+        R = ctx.R
+        dy = dy.contiguous()
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        dgb = torch.empty((2, C), dtype=torch.float32, device=dev)
+        sums = torch.empty(2 * C, dtype=torch.float64, device=dev)
+        stream = _lib.current_stream_ptr(dev)
+        ws = _workspace(dev, stream, L.om_bn_act_workspace_bytes(B, C, H, W))
+        with _device(dev):
+            _lib.check(L.om_bn_sync_backward_sums(
+                _vp(x), _vp(dy), B, C, H, W, _vp(gamma), _vp(beta), save.data_ptr(), save.data_ptr() + 8 * C, ctx.slope, _vp(sums),
+                dgb.data_ptr(), dgb.data_ptr() + 4 * C, ws.data_ptr(), ws.numel(), stream), "om_bn_sync_backward_sums")
+            if dx is not None:
+                sums_all = torch.empty(R * 2 * C, dtype=torch.float64, device=dev)
+                dist.all_gather_into_tensor(sums_all, sums, group=ctx.group)
+                _lib.check(L.om_bn_sync_backward_dx(
+                    _vp(x), _vp(dy), B, C, H, W, _vp(gamma), _vp(beta), save.data_ptr(), save.data_ptr() + 8 * C, ctx.slope,
+                    _vp(sums_all), R, _vp(n_total), _vp(dx), stream), "om_bn_sync_backward_dx")
+        return (dx, dgb[0] if ctx.needs_input_grad[1] else None, dgb[1] if ctx.needs_input_grad[2] else None,
+                dy if ctx.has_residual and ctx.needs_input_grad[3] else None, None, None, None)
+
+
+def _sync_world_size(group):
+    """Ranks the block's statistics span: 1 without an initialised process group (then nothing is exchanged)."""
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()):
+        return 1
+    return dist.get_world_size(group)
+
+
+def bn_leaky(x, bn, residual=None, slope=LEAKY_SLOPE, sync=False, process_group=None):
     """leaky_relu(bn(x), slope) (+ residual) as the HIP block: `bn` is an nn.BatchNorm2d in training or eval mode, x (and residual)
-    CUDA float32 NCHW-contiguous; anything else raises."""
+    CUDA float32 NCHW-contiguous; anything else raises.  sync=True: in training mode and with more than one rank in `process_group`
+    (None: the default group) the batch statistics are those of every rank's batch (_SyncBNAct); otherwise nothing is exchanged."""
+    synced = sync and bn.training and _sync_world_size(process_group) > 1
     _lib.require_cuda_tensor(x, "the BatchNorm input (backend 'hip')", torch.float32)
     if bn.momentum is None:
         raise ValueError("bn_leaky: momentum=None (a cumulative moving average) is not supported")
     if x.dim() != 4 or not x.is_contiguous():
         raise _lib.OrienMaskHipError("backend 'hip' takes NCHW-contiguous [B,C,H,W] activations, got strides %s for shape %s"
                                      % (x.stride(), tuple(x.shape)))
-    if (bn.training or bn.running_mean is None) and x.numel() // x.shape[1] <= 1:
+    if (bn.training or bn.running_mean is None) and x.numel() // x.shape[1] <= 1 and not synced:
         raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(x.shape),))
     if residual is not None:
         _lib.require_cuda_tensor(residual, "residual", torch.float32)
         if residual.shape != x.shape or not residual.is_contiguous():
             raise _lib.OrienMaskHipError("residual must be NCHW-contiguous with the block's output shape %s, got %s strides %s"
                                          % (tuple(x.shape), tuple(residual.shape), residual.stride()))
+    if synced:
+        return _SyncBNAct.apply(x, bn.weight, bn.bias, residual, bn, slope, process_group)
     return _BNAct.apply(x, bn.weight, bn.bias, residual, bn, slope)
 
 
@@ -238,13 +318,15 @@ class ConvBNLeaky(nn.Module):
     backend 'hip' (default): F.conv2d, then BatchNorm + LeakyReLU + residual as one HIP block under autograd (csrc/bn_act.hip);
     CUDA float32 tensors only -- anything else raises, there is no fallback.  backend 'torch': F.conv2d -> F.batch_norm ->
     F.leaky_relu, the comparator, and the only path that takes CPU tensors.  The block normalises with batch statistics while
-    its BatchNorm module is in training mode and with the running statistics otherwise (model.eval(), backbone_batchnorm_eval)."""
+    its BatchNorm module is in training mode and with the running statistics otherwise (model.eval(), backbone_batchnorm_eval).
+    After convert_sync_batchnorm (`sync` True) the batch statistics are those of every rank of `process_group`."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, backend="hip"):
         super().__init__()
         if backend not in BACKENDS:
             raise ValueError("backend must be one of %s, got %r" % (BACKENDS, backend))
         self.backend = backend
+        self.sync, self.process_group = False, None          # set by convert_sync_batchnorm
         self.conv_block = nn.Sequential(
             nn.Conv2d(in_channels, out_channels, kernel_size, stride=stride, padding=padding, bias=False),
             nn.BatchNorm2d(out_channels),
@@ -256,7 +338,8 @@ class ConvBNLeaky(nn.Module):
             raise ValueError("ConvBNLeaky: momentum=None (a cumulative moving average) is not supported")
         h = F.conv2d(x, conv.weight, None, conv.stride, conv.padding)
         training = bn.training or bn.running_mean is None
-        if training and h.numel() // h.shape[1] <= 1:
+        synced = self.sync and bn.training and _sync_world_size(self.process_group) > 1
+        if training and h.numel() // h.shape[1] <= 1 and not synced:
             raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(h.shape),))
         if self.backend == "torch":
             y = F.batch_norm(h, bn.running_mean, bn.running_var, bn.weight, bn.bias, training, bn.momentum, bn.eps)
@@ -264,7 +347,23 @@ class ConvBNLeaky(nn.Module):
                 bn.num_batches_tracked.add_(1)
             y = F.leaky_relu(y, act.negative_slope, inplace=True)
             return y if residual is None else y + residual
-        return bn_leaky(h, bn, residual=residual, slope=act.negative_slope)
+        return bn_leaky(h, bn, residual=residual, slope=act.negative_slope, sync=self.sync, process_group=self.process_group)
+
+
+def convert_sync_batchnorm(model, process_group=None):
+    """The reference's nn.SyncBatchNorm.convert_sync_batchnorm(model) (trainer/builder.py:86) for this module's models: marks every
+    ConvBNLeaky so that, in training mode and with more than one rank in `process_group` (None: the default group), its batch
+    statistics are taken over every rank's batch.  The module tree, the state_dict keys and the parameters() order are unchanged.
+    Blocks in eval mode (model.eval(), backbone_batchnorm_eval) and a world of one rank exchange nothing, as torch's SyncBatchNorm.
+    Backend 'torch' is refused: F.batch_norm cannot synchronise.  Returns `model`."""
+    blocks = [m for m in model.modules() if isinstance(m, ConvBNLeaky)]
+    for m in blocks:
+        if m.backend != "hip":
+            raise ValueError("convert_sync_batchnorm: backend %r cannot synchronise its batch statistics (F.batch_norm); build the "
+                             "model with backend 'hip'" % (m.backend,))
+    for m in blocks:
+        m.sync, m.process_group = True, process_group
+    return model
 
 
 class _Container(nn.Module):
