@@ -1,6 +1,6 @@
 """Headline benchmark: images/sec end-to-end (forward + postprocess) at 544x544, bs=32 per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -9,6 +9,12 @@ A step is what the reference times around `model(image); postprocess(predict)`
 synthetic 544x544 images already resident in HBM (BASELINE.json configs[2]).  Each rank runs its own
 batch (weak scaling, no collective in the timed region); rank 0's packed weights are broadcast once
 over RCCL before timing.  Rank 0 prints ONE JSON line.
+
+A plain run does what `value` needs and nothing more: set-up, W warm-up steps, the K timed steps with batches in flight,
+--dump-outputs, the line.  Everything below is measured by `--full` only, in runs of their own beside the headline's: the
+one-batch-at-a-time region with its per-kernel events (`one_batch_in_flight`, `roofline`), fp32 operands and the fp16
+configuration (`f32_operands`, `f16_config`), `small_batches`, `extras`, `cpu_baseline`, and at N > 1 rank 0's solo run
+(`solo_reference`, `scaling_efficiency`).  The --no-* options leave single ones of them out of a --full run.
 
 roofline:     the dominant kernel (default precision: the fused F(4,3) 3x3 convolution on the fp16 matrix cores with split
               fp32 operands).  achieved = ALGORITHMIC flops -- the direct convolution's 2 * B * Ho * Wo * cout * cin * k^2 of the
@@ -333,6 +339,12 @@ def plumbing_only(args, world, rank):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure, each in a run of its own: the K steps one batch at a "
+                         "time with per-kernel events (`one_batch_in_flight`, `roofline`, --layers, --streams), fp32 operands and "
+                         "the fp16 configuration, small batches, the preprocess / COCO-format extras, the CPU baseline, and at "
+                         "N > 1 rank 0's solo reference run.  Off by default: a plain run warms up, times the steps behind "
+                         "`value` and prints the line")
     ap.add_argument("--no-solo-reference", action="store_true",
                     help="N > 1: skip rank 0's solo run of the same steps (the denominator of `scaling_efficiency`)")
     ap.add_argument("--plumbing-only", action="store_true",
@@ -373,7 +385,7 @@ def main():
                          "kernels).  1 = the reference's loop, one batch at a time; that region is ALWAYS timed too (it carries "
                          "the per-kernel events of the roofline object) and reported as `one_batch_in_flight`.  Default: 2 in fp32, "
                          "3 in fp16 (its steps are a third as long and the host's read of the counts weighs more: 3790 against 3700 "
-                         "images/s; in fp32 a third batch changes nothing, a fourth costs 3 %)")
+                         "images/s; in fp32 a third batch changes nothing, a fourth costs 3 %%)")
     ap.add_argument("--replicated-concat", action="store_true",
                     help="A/B: f32_split with the routes / skips stored replicated into the concat buffers (set_upsample_on_read(False)) "
                          "instead of read up-sampled by the 1x1 layer behind the concat")
@@ -395,6 +407,9 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be >= 1")
+    full = args.full
+    if not full and (args.layers or args.streams != 1):
+        ap.error("--layers and --streams act on the one-batch-at-a-time region, which only a --full run has")
     if args.dump_outputs:
         dump_pixel_index(args.size, args.size, args.batch, post_config(args.size, args.size)["nms_post"])     # fits, or fails now
     from orienmask_amd.model import DEFAULT_PRECISION
@@ -488,7 +503,7 @@ def main():
     # ---- N > 1: rank 0 alone (every other GPU idle at the barrier) runs the K steps one batch at a time and with batches in
     # flight: the SAME binary's single-GPU figures, which `scaling_efficiency` divides by
     solo = None
-    if use_dist and (world > 1 or os.environ.get("OM_BENCH_FORCE_DIST") == "1") and not args.no_solo_reference:
+    if full and use_dist and not args.no_solo_reference:
         dist.barrier()
         if rank == 0:
             import itertools
@@ -514,60 +529,68 @@ def main():
             solo = dict(value=round(B * args.steps / solo_flight, 2), one_batch_in_flight=round(B * args.steps / solo_serial, 2))
         dist.barrier()
 
-    # ---- untimed pass with events around EVERY layer: the per-kernel table, and which kernel dominates
-    specs = {s.name: s for s in arch.fpnplus_convs()}
-    kernel_of = dict(net.layer_kernels(B, H, W))
-    n_prof = 3
-    net.profile_enable(True)
-    post_ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_prof)]
-    for i in range(n_prof):
-        with torch.no_grad():
-            pred = net(x)
-            post_ev[i][0].record()
-            outs = post.launch(pred)
-            post_ev[i][1].record()                                 # kernels only: collect()'s host read is not GPU time
-            dets = post.collect(outs)
-    torch.cuda.synchronize()
-    layer_ms, n_fw = net.profile_read()
-    post_ms = sum(a.elapsed_time(b) for a, b in post_ev) / n_prof
-    by_kernel = {}
-    for name, ms, pre in layer_ms:
-        by_kernel[kernel_of[name]] = by_kernel.get(kernel_of[name], 0.0) + ms + pre
-    dom = max(by_kernel, key=by_kernel.get)
-    dom_layers = [name for name, _, _ in layer_ms if kernel_of[name] == dom]
-
-    # ---- timed region: K steps, HIP events only around the dominant kernel's launches (an event pair costs a few
-    # microseconds of GPU time; around all ~90 layers that was 3 % of the step)
-    net.profile_enable_layers(dom_layers)
-    net.set_streams(args.streams)
-    for _ in range(2 if args.streams > 1 else 0):
-        step()                                                     # allocate the per-stream workspaces outside the timing
-    if args.streams > 1:
-        net.profile_enable_layers(dom_layers)                      # drop the warm-up's events
-    if use_dist:
-        dist.barrier()
-    torch.cuda.synchronize()
     clock = ClockSampler(dev)
     sclk_idle = clock._read() if clock.path else None
-    clock.start()
-    t0 = time.perf_counter()
-    for i in range(args.steps):
-        dets = step()
-    torch.cuda.synchronize()
-    if use_dist:
-        dist.barrier()
-    elapsed = time.perf_counter() - t0
-    sclk_serial = clock.stop()
-    sclk_flight = None
-    elapsed, per_rank_serial = over_ranks(elapsed)
-    per_rank = per_rank_serial
-    timed_ms, timed_fw = net.profile_read()
-    net.profile_enable(False)
-    net.set_streams(1)
+    sclk_serial = sclk_flight = None
+    elapsed = elapsed_serial = per_rank = per_rank_serial = None
+    if full:
+        # ---- untimed pass with events around EVERY layer: the per-kernel table, and which kernel dominates
+        specs = {s.name: s for s in arch.fpnplus_convs()}
+        kernel_of = dict(net.layer_kernels(B, H, W))
+        n_prof = 3
+        net.profile_enable(True)
+        post_ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_prof)]
+        for i in range(n_prof):
+            with torch.no_grad():
+                pred = net(x)
+                post_ev[i][0].record()
+                outs = post.launch(pred)
+                post_ev[i][1].record()                             # kernels only: collect()'s host read is not GPU time
+                dets = post.collect(outs)
+        torch.cuda.synchronize()
+        layer_ms, n_fw = net.profile_read()
+        post_ms = sum(a.elapsed_time(b) for a, b in post_ev) / n_prof
+        by_kernel = {}
+        for name, ms, pre in layer_ms:
+            by_kernel[kernel_of[name]] = by_kernel.get(kernel_of[name], 0.0) + ms + pre
+        dom = max(by_kernel, key=by_kernel.get)
+        dom_layers = [name for name, _, _ in layer_ms if kernel_of[name] == dom]
+
+        # HIP events only around the dominant kernel's launches in the timed region below (an event pair costs a few
+        # microseconds of GPU time; around all ~90 layers that was 3 % of the step)
+        net.profile_enable_layers(dom_layers)
+        net.set_streams(args.streams)
+        for _ in range(2 if args.streams > 1 else 0):
+            step()                                                 # allocate the per-stream workspaces outside the timing
+        if args.streams > 1:
+            net.profile_enable_layers(dom_layers)                  # drop the warm-up's events
+        sclk_idle = clock._read() if clock.path else None
+
+    # ---- timed region, one batch at a time: K steps.  A run of its own beside the headline's (--full), or the headline
+    # itself with --in-flight 1
+    if full or args.in_flight == 1:
+        if use_dist:
+            dist.barrier()
+        torch.cuda.synchronize()
+        clock.start()
+        t0 = time.perf_counter()
+        for i in range(args.steps):
+            dets = step()
+        torch.cuda.synchronize()
+        if use_dist:
+            dist.barrier()
+        elapsed = time.perf_counter() - t0
+        sclk_serial = clock.stop()
+        elapsed, per_rank_serial = over_ranks(elapsed)
+        per_rank = per_rank_serial
+        elapsed_serial = elapsed
+    if full:
+        timed_ms, timed_fw = net.profile_read()
+        net.profile_enable(False)
+        net.set_streams(1)
 
     # ---- the same K steps with args.in_flight whole batches in flight (no per-kernel events: kernels of different batches
     # overlap here, their individual durations say nothing)
-    elapsed_serial = elapsed
     if args.in_flight > 1:
         import itertools
         from orienmask_amd.pipeline import InFlightPipeline
@@ -590,7 +613,7 @@ def main():
     timed_dets = dets                                              # the last step behind `value`: what --dump-outputs writes
     # ---- split mode: the same K steps with fp32 operands (v_mfma_f32_32x32x2_f32 everywhere), for comparison
     f32_operands = None
-    if split and not args.no_f32_compare:
+    if full and split and not args.no_f32_compare:
         net.set_precision("f32")
         def timed(fn):
             if use_dist:
@@ -618,7 +641,7 @@ def main():
     # ---- split mode: the same K steps in the fp16-activation configuration (BASELINE configs[4]: fp16 activations and weights,
     # fp32 accumulate -- NARROWER arithmetic than the headline, reported beside it so that the driver's run times it too)
     f16_config = None
-    if split and not args.no_f16_compare:
+    if full and split and not args.no_f16_compare:
         import itertools
         from orienmask_amd.pipeline import InFlightPipeline
         net.set_precision("f16")
@@ -713,7 +736,7 @@ def main():
     # images per step, one at a time (the reference's loop) through the hipGraph of forward + postprocess that infer_loop uses,
     # eagerly, and with four batches in flight; same weights, same precision
     small = None
-    if not args.no_small_batch and args.streams == 1:
+    if full and not args.no_small_batch and args.streams == 1:
         import itertools
         from orienmask_amd.graph import GraphedPipeline
         from orienmask_amd.pipeline import InFlightPipeline
@@ -762,11 +785,13 @@ def main():
                          "with four batches in flight (InFlightPipeline), and -- f32_split -- one at a time through the graph in the model's "
                          "latency mode (model.set_latency_mode, what tester.infer_loop switches on: stride-1 3x3 layers as direct "
                          "convolutions where the fused kernel would have <= 128 tiles, split-K parts in the implicit GEMM's small launches)")
-    timed_fw //= max(args.streams, 1)                              # one om_forward per sub-batch
-    dom_main_ms = sum(ms for name, ms, pre in timed_ms if name in set(dom_layers)) / timed_fw      # per step, all launches
-    dom_timed_ms = dom_main_ms + sum(pre for name, ms, pre in timed_ms if name in set(dom_layers)) / timed_fw
+    if full:
+        timed_fw //= max(args.streams, 1)                          # one om_forward per sub-batch
+        dom_main_ms = sum(ms for name, ms, pre in timed_ms if name in set(dom_layers)) / timed_fw      # per step, all launches
+        dom_timed_ms = dom_main_ms + sum(pre for name, ms, pre in timed_ms if name in set(dom_layers)) / timed_fw
 
-    if rank == 0:
+    roofline = None
+    if rank == 0 and full:
         kern = {}
 
         def acc(name, ms, flops, exec_flops, byts, pre_ms=0.0):
@@ -959,6 +984,7 @@ def main():
                     k, t["launches"], t["ms"], t["flops"] / (t["ms"] * 1e-3) / 1e12,
                     t["exec_flops"] / (t["ms"] * 1e-3) / 1e12, t["bytes"] / (t["ms"] * 1e-3) / 1e9), file=sys.stderr)
             print("forward kernels %.3f ms, postprocess %.3f ms" % (fwd_ms, post_ms), file=sys.stderr)
+    if rank == 0:
         total_images = world * B * args.steps
         metric = "images/sec end-to-end (544^2, bs=32) forward+postprocess"
         if f16:
@@ -967,18 +993,13 @@ def main():
                                   "fp16 MFMAs per product group)",
                      "f32": "f32 (fp32 operands on v_mfma_f32_32x32x2_f32)", "f16": "f16"}[args.dtype]
         line = dict(metric=metric, value=round(total_images / elapsed, 2),
-                    one_batch_in_flight_value=round(total_images / elapsed_serial, 2),      # the reference's loop (trainer/tester.py:39-44): like for like
                     unit="images/s", n_gpus=world, steps=args.steps, warmup=args.warmup,
                     ms_per_step=round(elapsed / args.steps * 1e3, 3), higher_is_better=True, scaling="weak",
-                    vs_baseline=None, dtype=dtype_out, precision=args.dtype, plugin_default_precision=DEFAULT_PRECISION,
+                    vs_baseline=None, dtype=dtype_out, precision=args.dtype, plugin_default_precision=DEFAULT_PRECISION, full=full,
                     data="synthetic (two seeded input batches taken in turn)",
                     rccl_ranks=world if use_dist else 0,
                     per_rank_value=[round(B * args.steps / t, 2) for t in per_rank],       # images/s of every rank's own steps
-                    scaling_efficiency=(round(total_images / elapsed / (world * solo["value"]), 4) if solo else None),
-                    solo_reference=solo,      # rank 0 alone on this node, same binary, same steps (null at N = 1: `value` is it)
-                    rank_ms_per_step=dict(min=round(min(per_rank) / args.steps * 1e3, 3), max=round(max(per_rank) / args.steps * 1e3, 3),
-                                          one_batch_in_flight_min=round(min(per_rank_serial) / args.steps * 1e3, 3),
-                                          one_batch_in_flight_max=round(max(per_rank_serial) / args.steps * 1e3, 3)),
+                    rank_ms_per_step=dict(min=round(min(per_rank) / args.steps * 1e3, 3), max=round(max(per_rank) / args.steps * 1e3, 3)),
                     weight_broadcast=dict(bytes=bc_stats.get("bytes"), ms=bc_stats.get("ms"), blobs=bc_stats.get("blobs"),
                                           gbs=(round(bc_stats["bytes"] / (bc_stats["ms"] * 1e-3) / 1e9, 1) if (use_dist and bc_stats.get("ms")) else None),
                                           pack_ms_per_rank=bc_stats.get("pack_ms_per_rank"), packed_bytes=bc_stats.get("packed_bytes"),
@@ -995,33 +1016,47 @@ def main():
                                          "hundreds of scores at exactly 1.0, so detections are compared as sets per tie group)"
                                          % (B, H, W, WEIGHT_SEED, obj_bias, head_gain, args.heads),
                                 per_gpu_batch=B, image_size=[H, W], forward_streams=args.streams, batches_in_flight=args.in_flight, detections_per_image=round(sum(int(d_["bbox"].shape[0]) for d_ in dets) / B, 1),
-                                parallelism="batch shard x%d, one RCCL weight broadcast, no collective in the step" % world),
-                    one_batch_in_flight=dict(value=round(total_images / elapsed_serial, 2), ms_per_step=round(elapsed_serial / args.steps * 1e3, 3),
-                                             note="the same K steps one batch at a time (the reference's loop: forward, postprocess, "
-                                                  "host reads the counts, next batch); the roofline object's per-kernel events were "
-                                                  "recorded in THIS region, where kernels do not overlap.  `value` keeps "
-                                                  "batches_in_flight whole batches enqueued on alternating HIP streams"),
-                    roofline=roofline)
-        # whole-step utilisation over the time behind `value` (kernels of the batches in flight overlap: per-kernel figures above
-        # come from the one-at-a-time region, these from the step time itself)
-        step_s = elapsed / args.steps
-        line["roofline"]["step"] = dict(
-            ms=round(step_s * 1e3, 3), batches_in_flight=args.in_flight,
-            executed_tflops=round(total_exec / step_s / 1e12, 2), executed_frac=round(total_exec / step_s / 1e12 / peak_tf, 4),
-            hbm_algorithmic_gbs=round(total_bytes / step_s / 1e9, 1), hbm_algorithmic_frac=round(total_bytes / step_s / 1e9 / PEAK_HBM_GBS, 4),
-            hbm_pmc_gbs=round(conv_stack["bytes_per_step"] / step_s / 1e9, 1) if conv_stack else None,
-            hbm_pmc_frac=round(conv_stack["bytes_per_step"] / step_s / 1e9 / PEAK_HBM_GBS, 4) if conv_stack else None,
-            note="forward flops the matrix pipe executed / algorithmic forward bytes / PMC conv-stack bytes, each per step, over the "
-                 "step time of the timed region behind `value` (forward + postprocess, batches_in_flight batches overlapping)")
+                                parallelism="batch shard x%d, one RCCL weight broadcast, no collective in the step" % world))
+        if full:
+            # what a --full run measured beside the headline, in the places the line has always had them
+            line["one_batch_in_flight_value"] = round(total_images / elapsed_serial, 2)    # the reference's loop (trainer/tester.py:39-44): like for like
+            line["scaling_efficiency"] = round(total_images / elapsed / (world * solo["value"]), 4) if solo else None
+            line["solo_reference"] = solo     # rank 0 alone on this node, same binary, same steps (null at N = 1: `value` is it)
+            line["rank_ms_per_step"].update(one_batch_in_flight_min=round(min(per_rank_serial) / args.steps * 1e3, 3),
+                                            one_batch_in_flight_max=round(max(per_rank_serial) / args.steps * 1e3, 3))
+            line["one_batch_in_flight"] = dict(
+                value=round(total_images / elapsed_serial, 2), ms_per_step=round(elapsed_serial / args.steps * 1e3, 3),
+                note="the same K steps one batch at a time (the reference's loop: forward, postprocess, host reads the counts, next "
+                     "batch); the roofline object's per-kernel events were recorded in THIS region, where kernels do not overlap.  "
+                     "`value` keeps batches_in_flight whole batches enqueued on alternating HIP streams")
+            line["roofline"] = roofline
+            order = ["metric", "value", "one_batch_in_flight_value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
+                     "higher_is_better", "scaling", "vs_baseline", "dtype", "precision", "plugin_default_precision", "full", "data",
+                     "rccl_ranks", "per_rank_value", "scaling_efficiency", "solo_reference"]
+            line = {**{k: line[k] for k in order}, **{k: v for k, v in line.items() if k not in order}}
+            # whole-step utilisation over the time behind `value` (kernels of the batches in flight overlap: per-kernel figures
+            # above come from the one-at-a-time region, these from the step time itself)
+            step_s = elapsed / args.steps
+            line["roofline"]["step"] = dict(
+                ms=round(step_s * 1e3, 3), batches_in_flight=args.in_flight,
+                executed_tflops=round(total_exec / step_s / 1e12, 2), executed_frac=round(total_exec / step_s / 1e12 / peak_tf, 4),
+                hbm_algorithmic_gbs=round(total_bytes / step_s / 1e9, 1), hbm_algorithmic_frac=round(total_bytes / step_s / 1e9 / PEAK_HBM_GBS, 4),
+                hbm_pmc_gbs=round(conv_stack["bytes_per_step"] / step_s / 1e9, 1) if conv_stack else None,
+                hbm_pmc_frac=round(conv_stack["bytes_per_step"] / step_s / 1e9 / PEAK_HBM_GBS, 4) if conv_stack else None,
+                note="forward flops the matrix pipe executed / algorithmic forward bytes / PMC conv-stack bytes, each per step, over the "
+                     "step time of the timed region behind `value` (forward + postprocess, batches_in_flight batches overlapping)")
+        elif sclk_flight or sclk_serial:
+            # data: the shader clock this GPU held during the timed steps (a --full run has it in roofline.sclk_mhz)
+            line["sclk_mhz"] = dict(timed_steps=sclk_flight or sclk_serial, before=sclk_idle, nominal=2400)
         if f32_operands is not None:
             line["f32_operands"] = f32_operands
         if f16_config is not None:
             line["f16_config"] = f16_config
         if small is not None:
             line["small_batches"] = small
-        if not args.no_extras:
+        if full and not args.no_extras:
             line["extras"] = measure_neighbours(dev, dets, B)
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(sd, x_cpu, f16=f16)
         if args.dump_outputs:
             dump_outputs(timed_dets, args.dump_outputs, post.nms_post)

@@ -155,6 +155,22 @@ def test_bench_gpus_flag_is_binding():
         assert e.value.code not in (0, None) and "--gpus" in str(e.value.code)
 
 
+def test_bench_full_is_an_option_and_its_regions_need_it(monkeypatch, capsys):
+    """`--full` exists and is off by default; the options that act on the one-batch-at-a-time region, which only a --full run
+    has, are refused without it at the command line -- before any GPU work, not ignored."""
+    import pytest
+    bench, path = _bench_module()
+    for argv in (["--layers"], ["--streams", "2"]):
+        monkeypatch.setattr("sys.argv", [path] + argv)
+        with pytest.raises(SystemExit) as e:
+            bench.main()
+        assert e.value.code == 2 and "--full" in capsys.readouterr().err
+    monkeypatch.setattr("sys.argv", [path, "--help"])
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert e.value.code == 0 and "--full" in capsys.readouterr().out
+
+
 def test_bench_gpus_2_without_a_launcher_runs_two_ranks(built):
     """The command the driver types for N = 1 must work verbatim for N > 1: no launcher, `--gpus 2` -> two ranks, a line with
     n_gpus 2 (here on gloo with --plumbing-only: no GPU in this container), the slowest rank's time in it."""

@@ -2803,7 +2803,7 @@ def test_eval_val2017_harness_synthetic(dev, tmp_path):
 
 
 def test_bench_line_with_the_rccl_path_on_one_gpu(dev):
-    """`bench.py` end to end as the driver runs it (a short one: 3 steps), with the N > 1 code path forced on ONE GPU
+    """`bench.py --full` end to end (a short one: 3 steps), with the N > 1 code path forced on ONE GPU
     (OM_BENCH_FORCE_DIST=1: nccl process group of one rank, weight broadcast, rank 0's solo reference run, per-rank reduction): the
     line carries BASELINE.json's metric, `roofline` with the like-for-like figures up front, and the multi-GPU fields of VERDICT
     round 4, item 8 -- at one rank `scaling_efficiency` is the timed region over the solo run of the same steps, i.e. ~1."""
@@ -2815,12 +2815,12 @@ def test_bench_line_with_the_rccl_path_on_one_gpu(dev):
         s_.bind(("127.0.0.1", 0))
         port = s_.getsockname()[1]
     env = dict(os.environ, OM_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0", LOCAL_RANK="0", WORLD_SIZE="1")
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-extras",
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-extras",
                         "--no-f32-compare", "--no-f16-compare", "--no-small-batch"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["metric"].startswith("images/sec end-to-end (544^2, bs=32)") and line["unit"] == "images/s" and line["n_gpus"] == 1
-    assert line["rccl_ranks"] == 1 and line["value"] > 0 and line["one_batch_in_flight_value"] > 0
+    assert line["rccl_ranks"] == 1 and line["value"] > 0 and line["one_batch_in_flight_value"] > 0 and line["full"] is True
     assert len(line["per_rank_value"]) == 1 and abs(line["per_rank_value"][0] - line["value"]) < 1e-6 * line["value"] + 0.02
     assert line["solo_reference"]["value"] > 0 and 0.8 < line["scaling_efficiency"] < 1.25
     # ONE blob: the raw fp32 state_dict (~255 MB), packed per rank on the device
@@ -2837,7 +2837,8 @@ def test_bench_line_with_the_rccl_path_on_one_gpu(dev):
 def test_bench_dump_outputs_are_the_last_timed_step(dev, tmp_path):
     """`bench.py --dump-outputs DIR` writes the detections of the last of its --steps timed steps: with two batches in flight and
     3 steps that is the first input batch again, and the files are those of forward + postprocess of that batch computed here with
-    the bench's weights, precision and postprocess configuration -- the same bits."""
+    the bench's weights, precision and postprocess configuration -- the same bits.  A plain run (no --full): the line has the
+    headline figure and none of what is measured beside it."""
     import json
     import subprocess
     import sys
@@ -2852,6 +2853,8 @@ def test_bench_dump_outputs_are_the_last_timed_step(dev, tmp_path):
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["steps"] == 3 and line["config"]["per_gpu_batch"] == 2
+    assert line["full"] is False and line["value"] > 0 and abs(line["value"] * line["ms_per_step"] - 2 * 1e3) < 0.01 * 2 * 1e3
+    assert not {"roofline", "one_batch_in_flight", "f32_operands", "f16_config", "small_batches", "extras", "cpu_baseline"} & set(line)
     sd = synth.synth_state_dict(bench.WEIGHT_SEED, obj_bias=bench.OBJ_BIAS, head_gain=bench.HEAD_GAIN)
     net = OrienMaskYOLOFPNPlus(3, 80).eval().set_precision(line["precision"])
     net.load_state_dict(sd, strict=True)

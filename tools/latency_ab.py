@@ -62,7 +62,7 @@ def main():
                     del gp
             if args.layers:      # per-layer table of this batch size in latency mode (bench.py's events), to stderr of that run
                 import subprocess
-                subprocess.call([sys.executable, "bench.py", "--batch", str(bsz), "--steps", "10", "--warmup", "3", "--latency-mode",
+                subprocess.call([sys.executable, "bench.py", "--full", "--batch", str(bsz), "--steps", "10", "--warmup", "3", "--latency-mode",
                                  "--no-small-batch", "--layers"])
             net.set_latency_mode(False)
 
