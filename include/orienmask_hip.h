@@ -329,15 +329,6 @@ int om_conv2d_wino14_wide(const float* in, int B, int H, int W, int cin, int in_
                           int32_t* status_dev, om_stream stream);
 int om_set_wino14_wide(int on);
 int om_get_wino14_wide(void);
-/* Which kernel runs that layer (process-wide; the outputs are bit-identical): 0 (default; environment OM_W14_VARIANT) the
- * twelve-wave kernel (conv_wino14.hip) everywhere; 1 the four-dual-role-wave kernel of round 5 (conv_wino14d.hip: one wave per
- * SIMD, accumulators owned by name) wherever it applies -- an even number >= 2 of 16-channel chunks, 16-byte aligned views.
- * The second form is kept as a measured alternative (8-25 % slower: profiles/r05_experiments.md), not as the product's path:
- * only a library built with `make -C orienmask_amd/csrc W14D=1` contains it (om_wino14_dual_built() == 1); in the default
- * library om_set_wino14_variant(1) returns OM_EINVAL. */
-int om_set_wino14_variant(int variant);
-int om_get_wino14_variant(void);
-int om_wino14_dual_built(void);
 /* A/B switches of the two first-layers fusions (process-wide; default on; OM_NO_STEM3=1 / OM_NO_STEM2_F16=1 in the environment
  * turn them off before the first use): which = 0 the third layer (backbone.conv2.1.conv.0) inside the split-operand
  * first-two-layers kernel, which = 1 the fp16 first-two-layers kernel.  Off -> the separate kernels: bit-identical results for

@@ -28,25 +28,6 @@
 
 namespace om {
 
-#ifndef OM_SPLIT_WIDE
-#define OM_SPLIT_WIDE 1        // 128 x 128 tiles with 128-byte operand rows (conv_igemm_split_wide_kernel) where cin % 32 == 0
-#endif
-
-#if defined(OM_SPLIT_NO_XCD_PLACEMENT) && !defined(OM_MEASUREMENT_BUILD)
-#error "OM_SPLIT_NO_XCD_PLACEMENT is a measurement switch: tools/build_variant.sh only"
-#endif
-#ifndef OM_SPLIT_TRACE
-#define OM_SPLIT_TRACE 0       // measurement builds only: s_memtime stamps per tile of the wide kernel (tools/split_trace.py)
-#endif
-#if (OM_SPLIT_TRACE) && !defined(OM_MEASUREMENT_BUILD)
-#error "measurement switches (wrong numerics / trace stores) are only for ab/ variants: build them with tools/build_variant.sh, which defines OM_MEASUREMENT_BUILD and never writes orienmask_amd/lib/"
-#endif
-#if OM_SPLIT_TRACE
-static unsigned long long* g_split_trace = nullptr;
-extern "C" void om_debug_split_trace(void* buf) { g_split_trace = static_cast<unsigned long long*>(buf); }
-#define SPLIT_STAMP(x) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(x)::"memory")
-#endif
-
 struct IgemmSParams {
     const _Float16* in;   // the fp32 activations, addressed in halfs (pixel stride and channel counts doubled)
     const _Float16* w;    // packed hi/lo weights: [cout_pad][taps][cin / 16][4][8] halfs
@@ -76,9 +57,6 @@ struct IgemmSParams {
     // resolution -- the nearest-neighbour up-sampling of the reference's routes and skips (orienmask_yolo_fpnplus.py:78-86,
     // F.interpolate + torch.cat) happens in the operand addresses instead of in replicated stores
     int nseg, nimg;
-#if OM_SPLIT_TRACE
-    unsigned long long* trace;      // [workgroup < 16][tile < 16][8]
-#endif
     const _Float16* seg_ptr[4];
     int seg_stride_h[4], seg_shift[4], seg_end[4];
 };
@@ -93,7 +71,7 @@ constexpr int split_blocks_per_cu() { return BM * BN >= 256 * 128 ? 2 : (BM * BN
 // stride-2 layer of the forward but the up-sampling producers and the two heads): the row sweeps contain NO load.  In the
 // generic form the residual's conditional loads sit in the sweep loop, and the compiler's wait-count bookkeeping then waits for
 // vmcnt(0) at the top of every sweep -- which, loads and stores sharing one in-order counter, is the round trip of the PREVIOUS
-// sweep's stores: eight store round trips per tile, 10-18 k cycles of a 40 k-cycle 1x1 tile (tools/split_trace.py,
+// sweep's stores: eight store round trips per tile, 10-18 k cycles of a 40 k-cycle 1x1 tile (time stamps per tile phase,
 // profiles/r03_experiments.md section 14; the same serialisation as conv_wino14.hip's first epilogue).
 template <int BM, int BN, int WM, int WN, bool FAST = false>
 __device__ __forceinline__ void split_epilogue(const IgemmSParams& p, f32x4* smem, const f32x16 (&acc)[WM / 32][WN / 32],
@@ -290,14 +268,6 @@ __global__ __launch_bounds__(256, (NBUF > 3 ? 2 : split_blocks_per_cu<BM, BN>())
     // CONTIGUOUS range of units in (part, N tile, M tile) order -- an XCD then reads about an eighth of the weights and an eighth of
     // the input's k range instead of all of both.  One 544 x 544 image's 17 x 17 layers stream 19 MB of weights: drawn from a
     // chip-wide queue every XCD pulled all of them through its 4 MiB L2 (8 x 19 MB from the Infinity Cache per layer).
-#if OM_SPLIT_TRACE
-    // deep-ring forms (tools/deep_trace.py): start, first stage landed, k loop done, arrival counted, parts summed, stored
-    unsigned long long dts[6] = {0, 0, 0, 0, 0, 0};
-    auto deep_dump = [&]() {
-        if (KSPLIT && tid == 0 && p.trace && blockIdx.x < 512)
-            for (int i = 0; i < 6; ++i) p.trace[blockIdx.x * 8 + i] = dts[i];
-    };
-#endif
     for (int round = 0;; ++round) {
         int tile;
         int s_begin = 0, nsteps = p.ksteps;      // this unit's part of the k loop
@@ -305,15 +275,9 @@ __global__ __launch_bounds__(256, (NBUF > 3 ? 2 : split_blocks_per_cu<BM, BN>())
         int tile_n, tile_m;
         if constexpr (KSPLIT) {
             if (round) break;
-#if OM_SPLIT_TRACE
-            SPLIT_STAMP(dts[0]);
-#endif
             const int b = blockIdx.x, x = b & 7;
             int unit = b >> 3;
             for (int y = 0; y < x; ++y) unit += (p.total_tickets - y + 7) >> 3;      // units of the XCDs before this one
-#ifdef OM_SPLIT_NO_XCD_PLACEMENT      // measurement build: units in launch order, i.e. round-robin over the XCDs
-            unit = b;
-#endif
             tile_m = unit % p.m_tiles;
             const int t = unit / p.m_tiles;
             tile_n = t % p.n_tiles;
@@ -438,9 +402,6 @@ __global__ __launch_bounds__(256, (NBUF > 3 ? 2 : split_blocks_per_cu<BM, BN>())
         }
         asm volatile("s_waitcnt vmcnt(%0)" ::"i"((NBUF - 1) * NP) : "memory");
         __builtin_amdgcn_s_barrier();
-#if OM_SPLIT_TRACE
-        SPLIT_STAMP(dts[1]);
-#endif
         read_raw(0);
         convert();
         int buf = 0;
@@ -470,9 +431,6 @@ __global__ __launch_bounds__(256, (NBUF > 3 ? 2 : split_blocks_per_cu<BM, BN>())
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __syncthreads();
 
-#if OM_SPLIT_TRACE
-        SPLIT_STAMP(dts[2]);
-#endif
         if constexpr (KSPLIT) {
             if (p.ksplit > 1) {
                 // publish this part's raw accumulators (write-through stores, as conv_wino24.hip's stream-K form), count the arrival
@@ -496,10 +454,6 @@ __global__ __launch_bounds__(256, (NBUF > 3 ? 2 : split_blocks_per_cu<BM, BN>())
                 // with sc1 loads, which pass this CU's L1: no acquire either.  MI355X_MICROARCH.md, inter-workgroup visibility)
                 if (tid == 0) s_ticket[1] = __hip_atomic_fetch_add(p.kflags + tile, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 __syncthreads();
-#if OM_SPLIT_TRACE
-                SPLIT_STAMP(dts[3]);
-                if (s_ticket[1] != p.ksplit - 1) deep_dump();
-#endif
                 if (s_ticket[1] != p.ksplit - 1) break;         // another part stores the tile
                 // the last arrival: every part has published; the sum runs in part order (this part's own copy included), so the
                 // result does not depend on which part came last
@@ -526,17 +480,9 @@ __global__ __launch_bounds__(256, (NBUF > 3 ? 2 : split_blocks_per_cu<BM, BN>())
             }
         }
 
-#if OM_SPLIT_TRACE
-        SPLIT_STAMP(dts[4]);
-#endif
         float sc[8], sh[8];      // (four blocks per CU: no registers to hold them across the k loop)
         if constexpr (FAST) split_scale_shift<BN>(p, n0, tid, sc, sh);
         split_epilogue<BM, BN, WM, WN, FAST>(p, smem, acc, m0, n0, tid, wm, wn, fi, fk, sc, sh);
-#if OM_SPLIT_TRACE
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        SPLIT_STAMP(dts[5]);
-        deep_dump();
-#endif
     }
 }
 
@@ -554,7 +500,7 @@ __global__ __launch_bounds__(256, (NBUF > 3 ? 2 : split_blocks_per_cu<BM, BN>())
 // NBUF > 2: the DEEP-RING form of the small launches (a batch of one or a few images; conv_igemm_split_kernel's KSPLIT form with
 // whole-line rows): no tile queue -- one unit (tile x part of the k loop) per workgroup, placed XCD-contiguously --, NBUF stages of
 // two k-steps in the ring, split-K parts summed by the last arrival.  The 64-byte-row form of those launches ran its k loop at
-// ~30 B/clk/CU, the half-line request rate (tools/deep_trace.py: 545 cycles per 8 KB k-step, two workgroups per CU).
+// ~30 B/clk/CU, the half-line request rate (time stamps per phase: 545 cycles per 8 KB k-step, two workgroups per CU).
 template <int BM, int BN, int WM, int WN, bool GATHER = false, bool FAST = false, int NBUF = 2>
 __global__ __launch_bounds__(256, 2) void conv_igemm_split_wide_kernel(const IgemmSParams p) {
     constexpr int TM = WM / 32, TN = WN / 32;
@@ -578,9 +524,6 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_split_wide_kernel(const Ige
     const int scol = lcol ^ ((lrow >> 1) & 7);     // logical chunk this lane fetches (the LDS image stays lane-linear)
     const int fi = lane & 31, fk = lane >> 5;
     const int fsw = (fi >> 1) & 7;
-#if OM_SPLIT_TRACE
-    int n_traced = 0;
-#endif
 
     // The tile queue's NEXT ticket is drawn while this tile's k loop runs and handed over through LDS before the epilogue (its
     // value must not be consumed behind the epilogue's stores: loads, atomics and stores retire through one in-order counter).
@@ -589,26 +532,11 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_split_wide_kernel(const Ige
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
     }
-#if OM_SPLIT_TRACE
-    // deep-ring forms (tools/deep_trace.py): start, first stage landed, k loop done, arrival counted, parts summed, stored
-    unsigned long long dts[6] = {0, 0, 0, 0, 0, 0};
-    auto deep_dump = [&]() {
-        if (KSPLIT && tid == 0 && p.trace && blockIdx.x < 512)
-            for (int i = 0; i < 6; ++i) p.trace[blockIdx.x * 8 + i] = dts[i];
-    };
-#endif
     for (int round = 0;; ++round) {
-#if OM_SPLIT_TRACE
-        unsigned long long ts0, ts1, ts2, ts3, twait = 0, wa, wb;
-        SPLIT_STAMP(ts0);
-#endif
         int tile, tile_n, tile_m;
         [[maybe_unused]] int part = 0;
         if constexpr (KSPLIT) {
             if (round) break;
-#if OM_SPLIT_TRACE
-            SPLIT_STAMP(dts[0]);
-#endif
             const int b = blockIdx.x, x = b & 7;      // (conv_igemm_split_kernel: XCD-contiguous units in (part, N tile, M tile) order)
             int unit = b >> 3;
             for (int y = 0; y < x; ++y) unit += (p.total_tickets - y + 7) >> 3;
@@ -772,12 +700,6 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_split_wide_kernel(const Ige
         }
         asm volatile("s_waitcnt vmcnt(%0)" ::"i"((NBUF - 1) * NP) : "memory");
         __builtin_amdgcn_s_barrier();
-#if OM_SPLIT_TRACE
-        SPLIT_STAMP(ts1);
-#endif
-#if OM_SPLIT_TRACE
-        SPLIT_STAMP(dts[1]);
-#endif
         read_raw(0, 0);
         convert();
         int buf = 0;
@@ -787,15 +709,8 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_split_wide_kernel(const Ige
             convert();                               // operands of (s, 1); my reads of `buf` are complete
             // stage s + 1 has landed (only the NBUF - 2 stages behind it may still fly); every wave is done reading `buf`: it takes
             // stage s + NBUF
-#if OM_SPLIT_TRACE
-            SPLIT_STAMP(wa);
-#endif
             asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"i"((NBUF - 2) * NP) : "memory");
             __builtin_amdgcn_s_barrier();
-#if OM_SPLIT_TRACE
-            SPLIT_STAMP(wb);
-            twait += wb - wa;
-#endif
             const bool live2 = s + NBUF < nstages;
 #pragma unroll
             for (int piece = 0; piece < NP; ++piece) issue_piece(piece, buf, live2);
@@ -811,9 +726,6 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_split_wide_kernel(const Ige
             if (tid == 0) *s_ticket = next_ticket;      // every wave read the current ticket many barriers ago
         }
         __syncthreads();
-#if OM_SPLIT_TRACE
-        SPLIT_STAMP(dts[2]);
-#endif
         if constexpr (KSPLIT) {
             if (p.ksplit > 1) {
                 // publish / count / sum in part order: conv_igemm_split_kernel's split-K hand-off (write-through stores, drained
@@ -835,10 +747,6 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_split_wide_kernel(const Ige
                 __syncthreads();
                 if (tid == 0) s_ticket[1] = __hip_atomic_fetch_add(p.kflags + tile, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 __syncthreads();
-#if OM_SPLIT_TRACE
-                SPLIT_STAMP(dts[3]);
-                if (s_ticket[1] != p.ksplit - 1) deep_dump();
-#endif
                 if (s_ticket[1] != p.ksplit - 1) break;         // another part stores the tile
 #pragma unroll
                 for (int a = 0; a < TM; ++a)
@@ -862,27 +770,8 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_split_wide_kernel(const Ige
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
         }
-#if OM_SPLIT_TRACE
-        SPLIT_STAMP(ts2);
-#endif
 
-#if OM_SPLIT_TRACE
-        SPLIT_STAMP(dts[4]);
-#endif
         split_epilogue<BM, BN, WM, WN, FAST>(p, smem, acc, m0, n0, tid, wm, wn, fi, fk, sc, sh);
-#if OM_SPLIT_TRACE
-        if constexpr (KSPLIT) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            SPLIT_STAMP(dts[5]);
-            deep_dump();
-        }
-        SPLIT_STAMP(ts3);
-        if (p.trace && blockIdx.x < 16 && n_traced < 16 && tid == 0) {
-            unsigned long long* t = p.trace + ((size_t)blockIdx.x * 16 + n_traced) * 8;
-            t[0] = ts0; t[1] = ts1; t[2] = ts2; t[3] = ts3; t[4] = twait; t[5] = (unsigned long long)tile;
-        }
-        ++n_traced;
-#endif
     }
 }
 
@@ -945,7 +834,6 @@ void conv_tile_for_split(int M, int cout_pad, int* bm, int* bn, bool gather) {
         const double cost = (double)((M + c.bm - 1) / c.bm) * (cout_pad / c.bn) * c.bm * c.bn / c.eff;
         if (cost < best) { best = cost; *bm = c.bm; *bn = c.bn; }
     }
-#ifndef OM_SPLIT_NO_LATENCY_TILES
     // Few tiles (a batch of one or a few images: /root/reference/infer.py:143-172 runs bs = 1): a launch is then ONE round and
     // its time is a tile's latency, which is k-steps x the time of a k-step -- 12 matrix instructions per SIMD for 128 x 128, 3 for
     // 64 x 64.  While the chosen shape leaves more than half of the CUs without a tile, take the next smaller one.  (An output
@@ -956,7 +844,6 @@ void conv_tile_for_split(int M, int cout_pad, int* bm, int* bn, bool gather) {
         if (tiles > 128 || cout_pad % c.bn || c.bm * c.bn >= *bm * *bn) continue;
         *bm = c.bm; *bn = c.bn;
     }
-#endif
 }
 
 // a.w: packed hi/lo weights (include/orienmask_hip.h: om_layer_info.wsplit_off); a.scale: scale * 2^-e
@@ -993,9 +880,6 @@ int launch_conv_igemm_split(const ConvArgs& a, hipStream_t stream) {
                 (!a.res || (a.res_pix_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(a.res) & 15) == 0)))
                    ? 1 : 0;
     p.nseg = 0; p.nimg = a.B;
-#if OM_SPLIT_TRACE
-    p.trace = g_split_trace;
-#endif
     for (int g = 0; g < 4; ++g) { p.seg_ptr[g] = p.in; p.seg_stride_h[g] = 0; p.seg_shift[g] = 0; p.seg_end[g] = 0x7FFFFFFF; }
     if (a.nseg > 0) {
         // gathered input: 1x1, whole 32-channel chunks per segment, every segment's resolution a power-of-two fraction of this one
@@ -1032,27 +916,17 @@ int launch_conv_igemm_split(const ConvArgs& a, hipStream_t stream) {
         bm = a.force_bm; bn = a.force_bn;
     }
     if (bm == 256 && bn == 128) return launch_tile_split<256, 128, 128, 64>(p, a.cout_pad, 2, stream);
-    if (bm == 128 && bn == 128 && a.cin % 32 == 0 && !a.force_bm && OM_SPLIT_WIDE) return launch_tile_split<128, 128, 64, 64, true>(p, a.cout_pad, 2, stream);
+    if (bm == 128 && bn == 128 && a.cin % 32 == 0 && !a.force_bm) return launch_tile_split<128, 128, 64, 64, true>(p, a.cout_pad, 2, stream);
     if (bm == 128 && bn == 128) return launch_tile_split<128, 128, 64, 64>(p, a.cout_pad, 3, stream);
     // the latency form (deep ring, conv_igemm_split_kernel's NBUF) for launches that cannot fill the chip anyway
     const long long ntile = (long long)((p.M + bm - 1) / bm) * (a.cout_pad / bn);
     const bool deep = ntile <= 256 && (!a.force_bm || a.ksplit_max >= 1);      // (om_conv2d_split_k: a forced shape in its deep-ring form)
-#ifndef OM_DEEP_WIDE
-#define OM_DEEP_WIDE 1          // whole-line rows in the deep-ring forms where cin % 32 == 0
-#endif
-    if (OM_DEEP_WIDE && deep && a.cin % 32 == 0) {      // three stages of 24 KiB / four of 16 KiB: two workgroups per CU
+    if (deep && a.cin % 32 == 0) {      // whole-line rows in the deep-ring forms: three stages of 24 KiB / four of 16 KiB: two workgroups per CU
         if (bm == 128 && bn == 64) return launch_tile_split<128, 64, 64, 32, true, false, 3, 3>(p, a.cout_pad, 2, stream);
         if (bm == 64 && bn == 64) return launch_tile_split<64, 64, 32, 32, true, false, 3, 4>(p, a.cout_pad, 2, stream);
     }
     if (bm == 128 && bn == 64 && deep) return launch_tile_split<128, 64, 64, 32, false, false, 5>(p, a.cout_pad, 2, stream);
     if (bm == 64 && bn == 64 && deep) return launch_tile_split<64, 64, 32, 32, false, false, 8>(p, a.cout_pad, 2, stream);
-#ifndef OM_SPLIT_WIDE_SMALLN
-#define OM_SPLIT_WIDE_SMALLN 0
-#endif
-#if OM_SPLIT_WIDE_SMALLN
-    if (bm == 128 && bn == 64 && a.cin % 32 == 0 && !a.force_bm) return launch_tile_split<128, 64, 64, 32, true>(p, a.cout_pad, OM_SPLIT_WIDE_SMALLN, stream);
-    if (bm == 128 && bn == 32 && a.cin % 32 == 0 && !a.force_bm) return launch_tile_split<128, 32, 32, 32, true>(p, a.cout_pad, OM_SPLIT_WIDE_SMALLN + 1, stream);
-#endif
     if (bm == 128 && bn == 64) return launch_tile_split<128, 64, 64, 32>(p, a.cout_pad, 4, stream);
     if (bm == 64 && bn == 64) return launch_tile_split<64, 64, 32, 32>(p, a.cout_pad, 4, stream);
     return launch_tile_split<128, 32, 32, 32>(p, a.cout_pad, 4, stream);

@@ -17,9 +17,6 @@
 //      store).
 // LDS: weights 73 728 + activations 17 x 36 x 128 = 78 336 + patch 7 980 bytes: one 512-thread workgroup per CU, tiles by a
 // static stride (every tile costs the same).
-#if defined(OM_S2_TRACE) && !defined(OM_MEASUREMENT_BUILD)
-#error "OM_S2_TRACE writes time stamps through the status word and disables the range guard: only for ab/ variants (tools/build_variant.sh defines OM_MEASUREMENT_BUILD and never writes orienmask_amd/lib/)"
-#endif
 #include "om_common.h"
 
 namespace om {
@@ -133,7 +130,7 @@ __global__ __launch_bounds__(S2_THREADS, 2) void conv_stem2_split_kernel(const S
     // Round 6, with the third layer: waves 4-7 are idle while waves 0-3 multiply it, so THEY own the patch (twice the registers each,
     // nothing requested by waves 0-3: their offsets are out of range) and store the next tile's into LDS during that phase -- the
     // patch area is dead from the end of conv1 on -- instead of all eight waves at the top of the next tile (1 100 of a tile's
-    // 17 500 cycles, tools/stem2_trace.py).
+    // 17 500 cycles, measured with time stamps per phase).
     constexpr int S2_PATCH_THREADS = THIRD ? S2_THREADS / 2 : S2_THREADS;
     constexpr int NSTAGE = (S2_P_FLOATS + S2_PATCH_THREADS - 1) / S2_PATCH_THREADS;
     const int ptid = THIRD ? tid - S2_THREADS / 2 : tid;        // < 0: not a patch thread
@@ -170,16 +167,9 @@ __global__ __launch_bounds__(S2_THREADS, 2) void conv_stem2_split_kernel(const S
         const int ty = tr / p.tiles_x, tx = tr - ty * p.tiles_x;
         const int oy0 = ty * S2_TY, ox0 = tx * S2_TX;
         const int y0 = 2 * oy0 - 1, x0 = 2 * ox0 - 1;       // conv1 activation (row 0, column 0) of the tile
-#ifdef OM_S2_TRACE
-        unsigned long long t0, t1, t2, t3, t4;      // tools/stem2_trace.py
-        asm volatile("s_memtime %0" : "=s"(t0)::"memory");
-#endif
         // ---- 1. the image patch: rows y0 - 1 .., columns x0 - 1 ..
         if constexpr (!THIRD) store_patch();
         __syncthreads();
-#ifdef OM_S2_TRACE
-        asm volatile("s_memtime %0" : "=s"(t1)::"memory");
-#endif
         // ---- 2. conv1 + BatchNorm + LeakyReLU, hi/lo split, into conv2.0's matrix operand layout
 #pragma unroll 1
         for (int blk = wave; blk < (S2_SR * S2_SC + 31) / 32; blk += S2_THREADS / 64) {
@@ -240,9 +230,6 @@ __global__ __launch_bounds__(S2_THREADS, 2) void conv_stem2_split_kernel(const S
             }
         }
         __syncthreads();
-#ifdef OM_S2_TRACE
-        asm volatile("s_memtime %0" : "=s"(t2)::"memory");
-#endif
         request_patch(tile + gridDim.x);        // the patch is dead: its registers take the next tile's
         // the third layer's weights of this lane (fi = output channel, fk), hi and lo of its four k-steps: requested a matrix phase
         // and an epilogue before their use (~2 500 cycles from L2 under this kernel's load)
@@ -290,9 +277,6 @@ __global__ __launch_bounds__(S2_THREADS, 2) void conv_stem2_split_kernel(const S
 #pragma unroll
             for (int i = 0; i < 4; ++i) cur[i] = nxt[i];
         }
-#ifdef OM_S2_TRACE
-        asm volatile("s_memtime %0" : "=s"(t3)::"memory");
-#endif
         __syncthreads();        // every wave is done with the activations: their LDS takes the transposes
         // the third layer's operands of this lane (fi = output channel, fk): hi and lo weights of its four k-steps, scale and shift --
         // requested HERE, an epilogue before their use (requested where they are used, their round trip to L2 stood in front of every
@@ -335,14 +319,10 @@ __global__ __launch_bounds__(S2_THREADS, 2) void conv_stem2_split_kernel(const S
                 // the third layer's operand: the tile's activation as fp32 rows [output][64 channels] behind the transposes, the
                 // 16-byte chunk index XOR-ed with s2_row_swizzle(row): a wave WRITES eight chunks of eight rows here and READS one
                 // chunk of 32 rows below, both without bank conflicts (with the plain row & 15 the writes were 8-way conflicts,
-                // eight waves at once: 3 000 cycles per tile, tools/stem2_trace.py)
+                // eight waves at once: 3 000 cycles per tile)
                 if constexpr (THIRD) *reinterpret_cast<f32x4*>(sS + 32768 + mm * 256 + (((nb >> 2) ^ s2_row_swizzle(mm)) * 16)) = v;
             }
         }
-#ifdef OM_S2_TRACE
-        unsigned long long t3b;
-        asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(t3b)::"memory");
-#endif
         if constexpr (THIRD) {
             __syncthreads();        // the activation rows are complete
             if (wave >= 4) store_patch();       // the next tile's patch (requested before conv2.0: landed long ago) beside the third layer
@@ -393,18 +373,9 @@ __global__ __launch_bounds__(S2_THREADS, 2) void conv_stem2_split_kernel(const S
                 nonfinite += ok ? nf : 0.f;
             }
         }
-#ifdef OM_S2_TRACE
-        asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(t4)::"memory");
-        if (blockIdx.x == 0 && tid == 0 && tile == blockIdx.x + 3 * gridDim.x) {
-            unsigned long long* tr = reinterpret_cast<unsigned long long*>(p.status);
-            tr[0] = t0; tr[1] = t1; tr[2] = t2; tr[3] = t3; tr[4] = t4; tr[5] = t3b;
-        }
-#endif
         // the next tile's barrier (after its patch is staged) orders these transposes before the next activations
     }
-#ifndef OM_S2_TRACE
     if (p.status && nonfinite != nonfinite) atomicOr(p.status, OM_STATUS_SPLIT_RANGE);
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------

@@ -21,9 +21,9 @@
 //   * (eight consumer waves) runs 18 (ky, j) steps of three v_mfma_f32_32x32x16_f16 per wave: the A fragment of tap ky is the SAME LDS plane read Ct
 //     entries further on (row oy + ky of the block: conv3x3_f16.hip's shared patch, one dimension up), so V is stored once for
 //     the three kernel rows; zero padding is zero ENTRIES (rows / columns outside the image are written as zeros), no masks;
-//   * streams U through a ring of W14_RING (four since round 4; three before) LDS-DMA slots of (j; ky = 0..2) groups, 12 KiB each, contiguous in the packed blob; a
-//     group's first weight fragments are read AFTER the barrier that starts the group, so a group requested in group g is not
-//     needed before group g + 2 (two groups to land: the landing time of this stream is the consumers' critical path).
+//   * streams U through a ring of W14_RING (four) LDS-DMA slots of (j; ky = 0..2) groups, 12 KiB each, contiguous in the packed
+//     blob; a group is requested three groups ahead and its first weight fragments are read BEFORE the barrier that starts it, so
+//     it has two groups to land (the landing time of this stream is the consumers' critical path).
 // What binds the kernel is the CU's vector-memory request path (L1 pending-request stalls 41 % of the time: 72 KB of weights and
 // 61 KB of input per chunk of a 128 x 64 tile against ~20 B/clk of ingest), not HBM, the matrix pipe (27 % busy) or the producers.
 // Tiles are blocks of the PADDED row space G = b (H + 2) + y + 1 (one zero row above and below every image), so a block may
@@ -38,30 +38,16 @@
 
 namespace om {
 
-#ifndef W14_RING
-#define W14_RING 4             // weight-ring slots.  4: blocks of (R + 2) * Ct <= 144 entries (two V buffers of 110 592 B leave room for a
-#endif                         // fourth 12 KiB slot), a group's first fragments are read BEFORE the barrier that starts it (no LDS round
-                               // trip between the barrier and the group's first matrix instruction) and its weights still have two
-                               // groups to land (requested three groups ahead)
-constexpr int W14_EMAX = W14_RING == 4 ? 144 : 160;      // LDS entries per plane: (R + 2) * Ct <= W14_EMAX
+// Weight-ring slots.  Four: two V buffers of 110 592 B leave room for a fourth 12 KiB slot with blocks of (R + 2) * Ct <= 144
+// entries; a group's first fragments are read before the barrier that starts it (no LDS round trip between the barrier and the
+// group's first matrix instruction) and its weights still have two groups to land.  Measured against a three-slot ring, the request
+// at another point of the group, waves 0-3 alone requesting, and per-XCD queues over N tiles: profiles/r04_experiments.md section 2.
+constexpr int W14_RING = 4;
+constexpr int W14_EMAX = 144;                 // LDS entries per plane: (R + 2) * Ct <= W14_EMAX
 constexpr int W14_VPLANE = W14_EMAX * 4;      // f32x4 units (16 B) per plane
-constexpr int W14_VBUF = 6 * W14_VPLANE;      // one transformed chunk: 61440 B
+constexpr int W14_VBUF = 6 * W14_VPLANE;      // one transformed chunk: 55296 B
 constexpr int W14_UGRP = 3 * W14_BN * 4;      // one (j; ky = 0..2) weight group: 12288 B
-#ifndef W14_QUEUE
-#define W14_QUEUE 0            // per-XCD tile queues: 0 = M blocks partitioned (N-tile siblings share the input behind one L2),
-#endif                         // 1 = N tiles partitioned (an XCD streams one or two N tiles' weights: they stay in its L2)
-#ifndef W14_B_ACROSS
-#define W14_B_ACROSS (W14_RING == 4)   // 1: the first weight fragments of a group are read before the barrier that starts it (its weights
-#endif                         // landed a group earlier); 0: after it -- the requests get two groups to land (three-slot ring)
-#ifndef W14_DMA_AFTER
-#define W14_DMA_AFTER 0        // the weight request follows the matrix instructions of this kernel row of the group
-#endif
-#ifndef W14_DMA_WAVES
-#define W14_DMA_WAVES 0        // who requests a weight group's twelve 1-KiB pieces: 0 = every consumer wave one, waves 0-3 a second one;
-#endif                         // 1 = waves 0-3 three each (they reach the group barrier ~280 cycles before waves 4-7: a request that
-                               // stalls on a full vector-memory queue costs them slack instead of matrix-instruction issue)
 constexpr int W14_THREADS = 768;              // waves 0-7: consumers (LDS reads + matrix instructions), 8-11: producers
-
 
 // Roles.  The matrix waves must never wait on global memory: with the input loads, the transform and the weight DMA in their
 // own instruction streams (round 3's first version) a 16-channel chunk cost a third more than its matrix instructions -- VMEM
@@ -99,24 +85,11 @@ __global__ __launch_bounds__(W14_THREADS, 3) void wino14_split_kernel(const Wino
     int q_xcd = 0, q_hops = 0;
     auto draw_tile = [&]() {
         const int m_tiles = p.total_tiles / p.n_tiles;
-#if W14_QUEUE == 1
-        // queue q: N tiles k, k + classes, ... (k = q % classes) of the M blocks' part q / classes
-        const int classes = p.n_tiles >= 8 ? 8 : (p.n_tiles == 4 || p.n_tiles == 2 || p.n_tiles == 1) ? p.n_tiles : 1;
-        const int mparts = 8 / classes;
-#endif
         while (q_hops < 8) {
             const int q = (q_xcd + q_hops) & 7;
-#if W14_QUEUE == 1
-            const int k = q % classes, mp = q / classes;
-            const int pm0 = (int)((long long)m_tiles * mp / mparts), pm1 = (int)((long long)m_tiles * (mp + 1) / mparts);
-            const int nk = (p.n_tiles - k + classes - 1) / classes;
-            const int v = atomicAdd(p.ticket + q, 1);
-            if (v < (pm1 - pm0) * nk) return (pm0 + v / nk) * p.n_tiles + k + classes * (v % nk);
-#else
             const int pm0 = (int)((long long)m_tiles * q >> 3), pm1 = (int)((long long)m_tiles * (q + 1) >> 3);
             const int v = atomicAdd(p.ticket + q, 1);
             if (v < (pm1 - pm0) * p.n_tiles) return pm0 * p.n_tiles + v;
-#endif
             ++q_hops;
         }
         return p.total_tiles;
@@ -124,17 +97,12 @@ __global__ __launch_bounds__(W14_THREADS, 3) void wino14_split_kernel(const Wino
     if (tid == 512) {
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(q_xcd));
         q_xcd &= 7;
-        if (OM_W14_ABLATE & 8192) q_xcd = 0;        // measurement: one queue order for the whole chip
         s_ticket[0] = draw_tile();
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     int tile = __builtin_amdgcn_readfirstlane(s_ticket[0]);
     int tslot = 0;                      // s_ticket[tslot] is this tile's ticket, s_ticket[tslot ^ 1] takes the next one
-#if OM_W14_TRACE
-    bool first_tile = true;
-    int n_traced = 0;
-#endif
 
     if (wave >= 8) {
         // ================================================================ producers
@@ -142,7 +110,7 @@ __global__ __launch_bounds__(W14_THREADS, 3) void wino14_split_kernel(const Wino
         const int hp2 = p.H + 2;
         const int ecount = (p.R + 2) * p.Ct;
         // a producer's few instructions per group are on everybody's critical path (the group barrier): issue them first
-        if (!(OM_W14_ABLATE & 4096)) __builtin_amdgcn_s_setprio(3);
+        __builtin_amdgcn_s_setprio(3);
         const auto rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in), 0, p.in_bytes, 0x00020000);
 
         // Items.  Entry e = rr * Ct + t is padded row g0 - 1 + rr, tile column t0 + t: six pixels x = 4 t - 1 .. 4 t + 4 of 16
@@ -172,8 +140,6 @@ __global__ __launch_bounds__(W14_THREADS, 3) void wino14_split_kernel(const Wino
                 for (int x = 0; x < 6; ++x) ok |= (rowok && (unsigned)(x0 + x) < (unsigned)p.W ? 1u : 0u) << x;
                 xok[k] = ok;
                 xbase[k] = (((b * p.H + y) * p.W + x0) * p.in_ps + ch) * 4;
-                // measurement (262144): the addresses a channel-chunk-major activation [B][cin / 16][H][W][16] would be read at
-                if (OM_W14_ABLATE & 262144) xbase[k] = (((b * p.nch * p.H + y) * p.W + x0) * 16 + ch) * 4;
                 const int sw = (e >> 2) & 3;
                 xlds[k] = e < ecount ? e * 64 + (((q >> 1) ^ sw) * 16) + (ch & 7) * 2 : -1;
             }
@@ -182,23 +148,16 @@ __global__ __launch_bounds__(W14_THREADS, 3) void wino14_split_kernel(const Wino
         f32x2 xp[2][6];         // the pair item's, of two chunks in turn (it is in use in every group: see the schedule below)
         auto item_offset = [&](int k, int x, int c) {
             // a pixel outside the image (or a pad row) gets an offset beyond the descriptor's range: the load returns zeros
-            int off = ((xok[k] >> x) & 1u) ? xbase[k] + x * p.in_ps * 4 + c * 64 : (int)0x80000000;
-            if (OM_W14_ABLATE & 262144) off = ((xok[k] >> x) & 1u) ? xbase[k] + x * 64 + c * (p.H * p.W * 64) : (int)0x80000000;
-            if (OM_W14_ABLATE & 512) off = lane * 16 + (k * 6 + x) * 1024;      // measurement: every request hits the same 18 KiB
-            if ((OM_W14_ABLATE & 16384) && (c & 1)) off = (int)0x80000000;     // measurement: half the input requests (odd chunks none)
-            if ((OM_W14_ABLATE & 32768) && (x == 0 || x == 5)) off = (int)0x80000000;   // measurement: no halo pixels (4 of 6 requests)
-            return off;
+            return ((xok[k] >> x) & 1u) ? xbase[k] + x * p.in_ps * 4 + c * 64 : (int)0x80000000;
         };
         // pixels [x0, x1) of an item
         auto load_quad_px = [&](int k, int c, int x0, int x1) {
-            if (OM_W14_ABLATE & 16) return;
 #pragma unroll
             for (int x = 0; x < 6; ++x)
                 if (x >= x0 && x < x1) xq[k][x] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_in, item_offset(k, x, c), 0, 0));
         };
         auto load_quad = [&](int k, int c) { load_quad_px(k, c, 0, 6); };
         auto load_pair_px = [&](auto buf, int c, int x0, int x1) {
-            if (OM_W14_ABLATE & 16) return;
 #pragma unroll
             for (int x = 0; x < 6; ++x)
                 if (x >= x0 && x < x1)
@@ -216,7 +175,6 @@ __global__ __launch_bounds__(W14_THREADS, 3) void wino14_split_kernel(const Wino
             asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(rem[2]) : "v"(hb[1]), "v"(v[2]));
             asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(rem[3]) : "v"(hb[1]), "v"(v[3]));
             const f16x4 l = __builtin_convertvector(rem, f16x4);
-            if ((OM_W14_ABLATE & 256) && h[0] != (_Float16)123.f) return;
             *reinterpret_cast<u32x2*>(dst) = hb;
             *reinterpret_cast<u32x2*>(dst + lo_off) = __builtin_bit_cast(u32x2, l);
         };
@@ -227,7 +185,6 @@ __global__ __launch_bounds__(W14_THREADS, 3) void wino14_split_kernel(const Wino
             asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(rem[0]) : "v"(hb), "v"(v[0]));
             asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(rem[1]) : "v"(hb), "v"(v[1]));
             const f16x2 l = __builtin_convertvector(rem, f16x2);
-            if ((OM_W14_ABLATE & 256) && h[0] != (_Float16)123.f) return;
             *reinterpret_cast<unsigned*>(dst) = hb;
             *reinterpret_cast<unsigned*>(dst + lo_off) = __builtin_bit_cast(unsigned, l);
         };
@@ -248,7 +205,7 @@ __global__ __launch_bounds__(W14_THREADS, 3) void wino14_split_kernel(const Wino
         };
         // two planes (positions i and i + 1 of the consumers' plane order) of quad item k into V buffer vb
         auto quad_planes = [&](int k, int vb, int i) {
-            if ((OM_W14_ABLATE & (16 | 64)) || xlds[k] < 0) return;
+            if (xlds[k] < 0) return;
             char* base = reinterpret_cast<char*>(smem + vb * W14_VBUF) + xlds[k];
             // lo lives two 16-byte chunks after hi (chunk index XOR-swizzled: + 2 flips bit 1 of the chunk)
             const int lo_off = ((((xlds[k] >> 4) & 3) ^ 2) - ((xlds[k] >> 4) & 3)) * 16;
@@ -257,7 +214,7 @@ __global__ __launch_bounds__(W14_THREADS, 3) void wino14_split_kernel(const Wino
             split_store4(point(xq[k], jb), base + jb * (W14_VPLANE * 16), lo_off);
         };
         auto pair_plane = [&](auto buf, int vb, int i) {
-            if ((OM_W14_ABLATE & (16 | 64)) || xlds[2] < 0) return;
+            if (xlds[2] < 0) return;
             char* base = reinterpret_cast<char*>(smem + vb * W14_VBUF) + xlds[2];
             const int lo_off = ((((xlds[2] >> 4) & 3) ^ 2) - ((xlds[2] >> 4) & 3)) * 16;
             const int j = w14_plane(i);
@@ -272,10 +229,6 @@ __global__ __launch_bounds__(W14_THREADS, 3) void wino14_split_kernel(const Wino
             load_pair(std::integral_constant<int, 0>{}, 0);
         }
         while (tile < p.total_tiles) {
-#if OM_W14_TRACE
-            unsigned long long pp0, pp1, pp2 = 0, pp3 = 0;
-            W14_STAMP(pp0);
-#endif
             // prologue: the next ticket requested, chunk 0 transformed, chunk 1 requested
             int next_ticket = 0;
             if (pid == 0) next_ticket = draw_tile();
@@ -289,9 +242,6 @@ __global__ __launch_bounds__(W14_THREADS, 3) void wino14_split_kernel(const Wino
                 load_quad(1, 1);
                 load_pair(std::integral_constant<int, 1>{}, 1);
             }
-#if OM_W14_TRACE
-            W14_STAMP(pp1);
-#endif
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
             const int next_tile = __builtin_amdgcn_readfirstlane(s_ticket[tslot ^ 1]);
@@ -315,21 +265,10 @@ __global__ __launch_bounds__(W14_THREADS, 3) void wino14_split_kernel(const Wino
                 constexpr int PAR = decltype(par)::value;           // c & 1: chunk c + 1's pair item is in xp[PAR ^ 1]
 #pragma unroll
                 for (int g = 0; g < 6; ++g) {
-#if OM_W14_TRACE
-                    unsigned long long ta, tb = 0, tc, td = 0;
-                    W14_STAMP(ta);
-#endif
                     if constexpr (FORM < 2) {
-                        if constexpr (FORM == 0 && !W14_SPREAD) {
-                            if (g == 0) load_pair(std::integral_constant<int, PAR>{}, c + 2);
-                        }
                         quad_planes(g / 3, PAR ^ 1, 2 * (g % 3));
                         pair_plane(std::integral_constant<int, PAR ^ 1>{}, PAR ^ 1, g);
-                        if constexpr (FORM == 0 && !W14_SPREAD) {
-                            if (g == 2) load_quad(0, c + 2);
-                            if (g == 5) load_quad(1, c + 2);
-                        }
-                        if constexpr (FORM == 0 && W14_SPREAD) {
+                        if constexpr (FORM == 0) {
                             // planes (0, 5) come first: only they read pixels 0 and 5, whose registers are free after the
                             // item's first group (2 requests); pixels 1..4 after its last (4); the pair item's free set in
                             // two threes: 2, 3, 4, 2, 3, 4 requests per group
@@ -345,15 +284,8 @@ __global__ __launch_bounds__(W14_THREADS, 3) void wino14_split_kernel(const Wino
                             if (g == 4) load_pair(std::integral_constant<int, 0>{}, 0);
                         }
                     }
-#if OM_W14_TRACE
-                    W14_STAMP(tc);
-#endif
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // my LDS writes are done
-                    if (!(OM_W14_ABLATE & 4)) __builtin_amdgcn_s_barrier();
-#if OM_W14_TRACE
-                    W14_SETTLE2(ta, tc);
-                    if (first_tile) w14_trace_put(p, wave, c * 6 + g, ta, tb, tc, td);
-#endif
+                    __builtin_amdgcn_s_barrier();
                 }
             };
             using I0 = std::integral_constant<int, 0>;
@@ -371,11 +303,6 @@ __global__ __launch_bounds__(W14_THREADS, 3) void wino14_split_kernel(const Wino
             } else {                        // nch == 1
                 chunk(c, I2{}, I0{});
             }
-#if OM_W14_TRACE
-            W14_SETTLE(pp0, pp1, pp2, pp3);
-            if (wave == 8 && !first_tile && pp3 == 0) w14_trace_put(p, 8, 62, pp0, pp1, pp2, pp3);      // a steady-state prologue
-            first_tile = false;
-#endif
             tile = next_tile;
             tslot ^= 1;
         }
@@ -388,11 +315,10 @@ __global__ __launch_bounds__(W14_THREADS, 3) void wino14_split_kernel(const Wino
     // weight-group DMA: a group's 192 rows of 64 bytes are twelve 1-KiB pieces of 16 rows; wave w requests piece w, waves 0-3
     // also piece 8 + w
     const int drow = lane >> 2, dcol = lane & 3;
-    constexpr int W14_NPIECE = W14_DMA_WAVES ? 3 : 2, W14_PSTEP = W14_DMA_WAVES ? 4 : 8;
-    int dvo[W14_NPIECE];
+    int dvo[2];
 #pragma unroll
-    for (int i = 0; i < W14_NPIECE; ++i) {
-        const int row = 16 * (wave + W14_PSTEP * i) + drow;
+    for (int i = 0; i < 2; ++i) {
+        const int row = 16 * (wave + 8 * i) + drow;
         dvo[i] = row * 64 + ((dcol ^ ((row >> 2) & 3)) * 16);      // swizzle on the SOURCE chunk: the LDS image stays lane-linear
     }
     const auto rs_u = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(p.u), 0, p.u_bytes, 0x00020000);
@@ -411,22 +337,12 @@ __global__ __launch_bounds__(W14_THREADS, 3) void wino14_split_kernel(const Wino
     }
     // weight group g = 6 c + j of N tile tn: 12 KiB at ((tn * nch + c) * 6 + j) * 12288 bytes of the packed blob
     auto issue_group = [&](int ubase, int g) {
-        if (!(OM_W14_ABLATE & 8) && g < ngroups) {
+        if (g < ngroups) {
             const int slot = g % W14_RING;
             const int soff = ubase + (g - g % 6 + w14_plane(g % 6)) * (W14_UGRP * 16);
-            // measurement (65536): every second weight group is not requested (the DMA writes zeros for out-of-range offsets)
-            const int oob = ((OM_W14_ABLATE & 65536) && (g & 1)) ? (int)0x80000000 : 0;
-            if (W14_DMA_WAVES) {
-                if (wave < 4) {
-#pragma unroll
-                    for (int i = 0; i < W14_NPIECE; ++i)
-                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_u, (lds_ptr_t)(s_u + slot * W14_UGRP + (wave + 4 * i) * 64), 16, dvo[i] | oob, soff, 0, 0);
-                }
-            } else {
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_u, (lds_ptr_t)(s_u + slot * W14_UGRP + wave * 64), 16, dvo[0] | oob, soff, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_u, (lds_ptr_t)(s_u + slot * W14_UGRP + wave * 64), 16, dvo[0], soff, 0, 0);
             if (wave < 4)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_u, (lds_ptr_t)(s_u + slot * W14_UGRP + (wave + 8) * 64), 16, dvo[1] | oob, soff, 0, 0);
-            }
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_u, (lds_ptr_t)(s_u + slot * W14_UGRP + (wave + 8) * 64), 16, dvo[1], soff, 0, 0);
         }
     };
     Wino14Tile tl;
@@ -436,7 +352,7 @@ __global__ __launch_bounds__(W14_THREADS, 3) void wino14_split_kernel(const Wino
         const int ubase = tl.tile_n * p.nch * 6 * (W14_UGRP * 16);
         issue_group(ubase, 0);
         issue_group(ubase, 1);
-        if (W14_RING == 4) issue_group(ubase, 2);
+        issue_group(ubase, 2);
     }
     while (tile < p.total_tiles) {
         const int ubase = tl.tile_n * p.nch * 6 * (W14_UGRP * 16);
@@ -445,19 +361,15 @@ __global__ __launch_bounds__(W14_THREADS, 3) void wino14_split_kernel(const Wino
         for (int j = 0; j < 6; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-        // weight groups 0 and 1 have landed: they were requested before the previous tile's epilogue stores, which need not have
+        // weight groups 0 to 2 have landed: they were requested before the previous tile's epilogue stores, which need not have
         // (the counter retires in order; the very first tile has nothing behind its requests)
-        if ((OM_W14_ABLATE & 32) || W14_EPI_OPS<MODE> == 0 || first_of_wg) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (W14_EPI_OPS<MODE> == 0 || first_of_wg) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(W14_EPI_OPS<MODE>) : "memory");
         first_of_wg = false;
-        __builtin_amdgcn_s_barrier();           // prologue: chunk 0 (producers), weight groups 0, 1 and the next ticket are in LDS
+        __builtin_amdgcn_s_barrier();           // prologue: chunk 0 (producers), weight groups 0 to 2 and the next ticket are in LDS
         const int next_tile = __builtin_amdgcn_readfirstlane(s_ticket[tslot ^ 1]);
-#if OM_W14_TRACE
-        unsigned long long pt0, pt1, pt2, pt3 = 0;
-        W14_STAMP(pt0);
-#endif
-        // fragments are read one step ahead, across the group barrier too: weight group g + 1 -- requested in group g - 1
-        // -- is waited for at the END of group g - 1 (one group of matrix work for 12 KiB from L2), and the next chunk's V is
+        // fragments are read one step ahead, across the group barrier too: weight group g + 1 -- requested in group g - 2
+        // -- is waited for at the END of group g - 1 (two groups of matrix work for 12 KiB from L2), and the next chunk's V is
         // published by the barrier that ends group 4
         f32x4 ca[4], na[4];        // A hi, A lo, B hi, B lo of the current / next step
         auto read_a = [&](f32x4(&f)[4], const f32x4* sV, int j, int ky) {
@@ -469,27 +381,18 @@ __global__ __launch_bounds__(W14_THREADS, 3) void wino14_split_kernel(const Wino
             f[3] = s_u[slot * W14_UGRP + ky * (W14_BN * 4) + boff_lo];
         };
         auto read_frags = [&](f32x4(&f)[4], const f32x4* sV, int j, int ky, int slot) {
-            if constexpr (OM_W14_ABLATE & 2) {
-                f[0] = f[1] = f[2] = f[3] = f32x4{(float)(j + ky), 1.f, 2.f, (float)lane};
-            } else {
-                read_a(f, sV, j, ky);
-                read_b(f, ky, slot);
-            }
+            read_a(f, sV, j, ky);
+            read_b(f, ky, slot);
         };
-        if (W14_B_ACROSS) read_frags(ca, smem, 0, 0, 0);
-        else read_a(ca, smem, 0, 0);
+        read_frags(ca, smem, 0, 0, 0);
         // weights first: D[i = channel][j = entry]
         auto mma = [&](const f32x4(&f)[4], auto plc) {
             constexpr int pl = decltype(plc)::value;
             const f16x8 ah = __builtin_bit_cast(f16x8, f[0]), al = __builtin_bit_cast(f16x8, f[1]);
             const f16x8 bh = __builtin_bit_cast(f16x8, f[2]), bl = __builtin_bit_cast(f16x8, f[3]);
-            if constexpr (OM_W14_ABLATE & 1024) {
-                asm volatile("" ::"v"(ah), "v"(al), "v"(bh), "v"(bl));
-            } else {
-                acc[pl] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh, al, acc[pl], 0, 0, 0);
-                acc[pl] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl, ah, acc[pl], 0, 0, 0);
-                acc[pl] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh, ah, acc[pl], 0, 0, 0);
-            }
+            acc[pl] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh, al, acc[pl], 0, 0, 0);
+            acc[pl] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl, ah, acc[pl], 0, 0, 0);
+            acc[pl] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh, ah, acc[pl], 0, 0, 0);
         };
         int g = 0;
         for (int c = 0; c < p.nch; ++c) {
@@ -499,50 +402,24 @@ __global__ __launch_bounds__(W14_THREADS, 3) void wino14_split_kernel(const Wino
             auto group = [&](auto jc) {
                 constexpr int j = decltype(jc)::value;
                 const int slot = g % W14_RING, slot1 = slot == W14_RING - 1 ? 0 : slot + 1;
-#if OM_W14_TRACE
-                unsigned long long ta, tb = 0, tc = 0, td;
-                W14_STAMP(ta);
-#endif
-                // groups g and g + 1 are in LDS; every wave has left group g - 1: its slot takes group g + 2 (requested below),
-                // which has to land by the end of this group
-                if (W14_DMA_AFTER < 0) issue_group(ubase, g + W14_RING - 1);
+                // groups g and g + 1 are in LDS; every wave has left group g - 1: its slot takes group g + 3 (requested below),
+                // which has to land by the end of the next group
 #pragma unroll
                 for (int ky = 0; ky < 3; ++ky) {
-                    if constexpr (OM_W14_ABLATE & 2048) continue;       // idle consumers: the producers' own speed
-                    if (!W14_B_ACROSS && ky == 0) read_b(ca, 0, slot);       // this group's weights: published by the barrier just passed
                     if (ky < 2) read_frags(na, sV, j, ky + 1, slot);
-                    else if (W14_B_ACROSS) {
-                        if (j < 5) read_frags(na, sV, j + 1, 0, slot1);
-                        else if (c + 1 < p.nch) read_frags(na, sVn, 0, 0, slot1);
-                    } else {
-                        if (j < 5) read_a(na, sV, j + 1, 0);
-                        else if (c + 1 < p.nch) read_a(na, sVn, 0, 0);
-                    }
+                    else if (j < 5) read_frags(na, sV, j + 1, 0, slot1);
+                    else if (c + 1 < p.nch) read_frags(na, sVn, 0, 0, slot1);
                     mma(ca, std::integral_constant<int, w14_plane(j)>{});
 #pragma unroll
                     for (int i = 0; i < 4; ++i) ca[i] = na[i];
                     // the request (60-200 cycles of issue) behind the first matrix instructions, not in front of them
-                    if (ky == W14_DMA_AFTER) {
-                        issue_group(ubase, g + W14_RING - 1);
-                    }
+                    if (ky == 0) issue_group(ubase, g + W14_RING - 1);
                 }
                 // my pieces of weight group g + 2 have landed; my reads of this group's slot and plane are done
-                if (OM_W14_ABLATE & 131072) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // measurement: late weights are not waited for
-                else if ((W14_B_ACROSS && W14_RING == 3) || g + W14_RING - 1 >= ngroups) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-                else if (W14_DMA_WAVES) {
-                    if (wave < 4) asm volatile("s_waitcnt vmcnt(3) lgkmcnt(0)" ::: "memory");
-                    else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                         // these waves requested nothing
-                }
+                if (g + W14_RING - 1 >= ngroups) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
                 else if (wave < 4) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");      // all but the pieces requested in this group
                 else asm volatile("s_waitcnt vmcnt(1) lgkmcnt(0)" ::: "memory");
-#if OM_W14_TRACE
-                W14_STAMP(td);
-#endif
-                if (!(OM_W14_ABLATE & 4)) __builtin_amdgcn_s_barrier();
-#if OM_W14_TRACE
-                W14_SETTLE2(ta, td);
-                if (first_tile) w14_trace_put(p, wave, g, ta, tb, tc, td);
-#endif
+                __builtin_amdgcn_s_barrier();
                 ++g;
             };
             group(std::integral_constant<int, 0>{});
@@ -552,10 +429,7 @@ __global__ __launch_bounds__(W14_THREADS, 3) void wino14_split_kernel(const Wino
             group(std::integral_constant<int, 4>{});
             group(std::integral_constant<int, 5>{});
         }
-#if OM_W14_TRACE
-        W14_STAMP(pt1);
-#endif
-        // every operand in LDS is dead (the last group's barrier has passed): the next tile's first two weight groups are
+        // every operand in LDS is dead (the last group's barrier has passed): the next tile's first three weight groups are
         // requested before the epilogue, its first chunk is being transformed by the producers meanwhile
         Wino14Tile tn = tl;
         if (next_tile < p.total_tiles) wino14_decode(p, next_tile, tn);
@@ -564,17 +438,9 @@ __global__ __launch_bounds__(W14_THREADS, 3) void wino14_split_kernel(const Wino
                 const int ub = tn.tile_n * p.nch * 6 * (W14_UGRP * 16);
                 issue_group(ub, 0);
                 issue_group(ub, 1);
-                if (W14_RING == 4) issue_group(ub, 2);
+                issue_group(ub, 2);
             }
         });
-#if OM_W14_TRACE
-        W14_STAMP(pt2);
-        W14_SETTLE(pt0, pt1, pt2, pt3);
-        if (wave == 0 && first_tile) w14_trace_put(p, 0, 60, pt0, pt1, pt2, pt3);
-        if (wave == 1 && n_traced < 8) w14_trace_put(p, 1, 48 + n_traced, pt0, pt1, pt2, pt3);      // phases of this workgroup's first eight tiles
-        ++n_traced;
-        first_tile = false;
-#endif
         tl = tn;
         tile = next_tile;
         tslot ^= 1;
@@ -668,6 +534,7 @@ struct Wino14WideParams {
 template <int MODE>
 __global__ __launch_bounds__(512, 2) void wino14_wide_kernel(const Wino14WideParams pw) {
     const Wino14Params& p = pw.k;
+    static_assert(W14_EMAX == 144, "the nine 1-KiB pieces of a V plane and the 128-entry sub-tile offsets below assume 144 entries");
     // two V buffers (chunk parity) + two weight slots of 24 KiB.  (Measured against it and not kept: ONE V buffer refilled plane by
     // plane behind the group that read it + a four-slot weight ring requested three groups ahead -- bit-identical, 0.238 against
     // 0.224-0.230 ms on 17^2 512 -> 1024: the weights' landing time is not what a group waits for.)
@@ -833,7 +700,7 @@ __global__ __launch_bounds__(512, 2) void wino14_wide_kernel(const Wino14WidePar
 }
 
 // Block shape for a layer: Ct tile columns (a divisor-like split of ceil(W / 4)) x R padded rows with R * Ct <= 128 and
-// (R + 2) * Ct <= 160, picked for the largest share of useful rows in the 128-row matrix tile.
+// (R + 2) * Ct <= W14_EMAX, picked for the largest share of useful rows in the 128-row matrix tile.
 void wino14_geometry(int B, int H, int W, int* R, int* Ct, int* ncb, int* nrb) {
     const int TW = (W + 3) / 4;
     const long long gtot = (long long)B * (H + 2);
@@ -852,16 +719,6 @@ void wino14_geometry(int B, int H, int W, int* R, int* Ct, int* ncb, int* nrb) {
         if (util > best) { best = util; *R = r; *Ct = ct; *ncb = cbs; *nrb = (int)rbs; }
     }
 }
-
-static int g_w14_variant = -1;
-int wino14_variant() {
-    if (g_w14_variant < 0) {
-        const char* e = std::getenv("OM_W14_VARIANT");
-        g_w14_variant = e ? std::atoi(e) : 0;
-    }
-    return g_w14_variant;
-}
-void wino14_set_variant(int v) { g_w14_variant = v; }
 
 size_t wino14_weight_halfs(int cout_pad, int cin) { return (size_t)18 * cout_pad * cin * 2; }
 
@@ -902,10 +759,6 @@ static int wino14_fill_params(const ConvArgs& a, Wino14Params& p) {
     const size_t ub = wino14_weight_halfs(a.cout_pad, a.cin) * 2;
     OM_REQUIRE(ub < 0x7FFFFFF0ull, OM_EINVAL, "wino14: weights exceed a buffer descriptor");
     p.u_bytes = (int)ub;
-#if OM_W14_TRACE
-    p.trace = g_w14_trace;
-    OM_REQUIRE(p.trace, OM_EINVAL, "wino14 trace build: om_debug_w14_trace() first");
-#endif
     return OM_OK;
 }
 
@@ -914,12 +767,6 @@ int launch_conv_wino14_split(const ConvArgs& a, hipStream_t stream) {
     Wino14Params p;
     if (int rc = wino14_fill_params(a, p)) return rc;
     const long long total = p.total_tiles;
-    // round 5: the four-dual-role-wave form (conv_wino14d.hip) on request only (om_set_wino14_variant(1) / OM_W14_VARIANT=1): bit-identical,
-    // but measured 8-25 % slower than this file's twelve-wave kernel on every layer shape (profiles/r05_experiments.md 1).  Since round 6
-    // it is only in libraries built with `make W14D=1` (the default library holds no kernel the forward cannot reach).
-#ifdef OM_WITH_W14D
-    if (wino14_variant() == 1 && wino14_dual_supported(p)) return launch_wino14_dual(p, a.res != nullptr, stream);
-#endif
     const long long grid = total < 256 ? total : 256;        // one 768-thread workgroup per CU (156 KiB of LDS)
     if (!p.fast_io) hipLaunchKernelGGL(wino14_split_kernel<2>, dim3((unsigned)grid), dim3(W14_THREADS), 0, stream, p);
     else if (a.res) hipLaunchKernelGGL(wino14_split_kernel<1>, dim3((unsigned)grid), dim3(W14_THREADS), 0, stream, p);

@@ -17,20 +17,15 @@
 // scale, against 3.6e-7 for F(2x2) and 2.4e-7 for MKLDNN's direct fp32 -- the F(4,3) matrices carry the constants
 // 4, 5, 2 (input), 1/4, 1/6, 1/12, 1/24 (weights, applied on the host in float64) and 2, 4, 8 (output; exact scalings).
 // Far inside the 1e-4 parity budget; the full-size F(4x4,3x3) would be at 4.8e-6 and needs 16 output accumulators.
-#if (defined(OM_EXP_V_RESIDENT) || defined(OM_EXP_U_RESIDENT)) && !defined(OM_MEASUREMENT_BUILD)
-#error "OM_EXP_*_RESIDENT read stale operands (upper-bound experiments): only for ab/ variants (tools/build_variant.sh defines OM_MEASUREMENT_BUILD and never writes orienmask_amd/lib/)"
-#endif
 #include <cstdlib>
 
 #include "om_common.h"
 
-#ifndef OM_W24_NBUF
-#define OM_W24_NBUF 4          // operand ring depth of the split-operand GEMM: 3 steps of LDS-DMA in flight (+2.7 % end to end
-                              // over 3 deep, same-box A/B); the fp32 form is built around 3
-#endif
-
 namespace om {
 
+// operand ring depth of the split-operand GEMM: 3 steps of LDS-DMA in flight (+2.7 % end to end over 3 deep, same-box A/B); the
+// fp32 form is built around 3
+constexpr int OM_W24_NBUF = 4;
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -282,16 +277,8 @@ __global__ __launch_bounds__(256, 2) void wino24_gemm_kernel(const Wino24Params 
             if (++n_cc == p.kc) { n_cc = 0; ++n_xi; }
         };
         auto issue_piece = [&](int piece, int buf, bool live) {
-#ifdef OM_EXP_V_RESIDENT        // upper-bound experiment (wrong numerics): every workgroup reads the SAME M panel of V -> V stays in L2
-            const float* abase = p.V + (size_t)n_xi * v_plane;
-#else
             const float* abase = p.V + (size_t)n_xi * v_plane + (size_t)m0 * p.C;
-#endif
-#ifdef OM_EXP_U_RESIDENT        // ... and / or the same N tile of U
-            const float* bbase = p.U + (size_t)n_xi * u_plane;
-#else
             const float* bbase = p.U + (size_t)n_xi * u_plane + (size_t)n0 * p.C;
-#endif
             const auto rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(abase), 0,
                                                                live ? rows_valid * p.C * 4 : 0, 0x00020000);
             const auto rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(bbase), 0, live ? BN * p.C * 4 : 0,

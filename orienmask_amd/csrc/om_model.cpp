@@ -470,7 +470,7 @@ struct om_model {
     // THE chooser: which kernel runs layer `index` of a forward at this batch, size and precision, and what that kernel needs.
     // om_layer_tile / om_layer_tile_f16 report it, layout() reserves its scratch and its side buffers, launch_layer launches it:
     // nothing else decides.  Reads the A/B switches (om_set_wino14_wide, om_set_stem_fusion, om_model_set_upsample_on_read; the
-    // variants of single kernels -- om_set_conv3x3_f16_variant, om_set_wino14_variant -- sit behind their files' own tile functions).
+    // variant of a single kernel -- om_set_conv3x3_f16_variant -- sits behind its file's own tile function).
     // `unfused`: the first layers each as a kernel of its own (launch_first_layers' fallback).
     om::LayerPlan plan(int index, int B, int H, int W, bool f16, bool unfused = false) const {
         using om::Form;
@@ -1345,22 +1345,6 @@ int om_set_wino14_wide(int on) {
 }
 int om_get_wino14_wide(void) { return switch_on(SW_W14_WIDE) ? 1 : 0; }
 
-int om_wino14_dual_built(void) {
-#ifdef OM_WITH_W14D
-    return 1;
-#else
-    return 0;
-#endif
-}
-
-int om_set_wino14_variant(int variant) {
-    OM_REQUIRE(variant == 0 || variant == 1, OM_EINVAL, "om_set_wino14_variant: %d", variant);
-    OM_REQUIRE(variant == 0 || om_wino14_dual_built(), OM_EINVAL,
-               "om_set_wino14_variant: this library was built without the dual-role kernel (make W14D=1)");
-    om::wino14_set_variant(variant);
-    return OM_OK;
-}
-
 int om_conv2d_stem3_split(const float* in, int B, int H, int W, const float* w1, const float* scale1, const float* shift1,
                           const void* w2_split, const float* scale2_split, const float* shift2, int cout2, int leaky2, float* out,
                           int out_pix_stride, const void* w3_split, const float* scale3_split, const float* shift3, int cout3, int leaky3,
@@ -1376,8 +1360,6 @@ int om_conv2d_stem2_f16(const float* in, int B, int H, int W, const float* w1, c
     return om::launch_conv_stem2_f16(in, B, H, W, w1, scale1, shift1, w2_f16, scale2, shift2, cout2, leaky2, out, out_pix_stride,
                                      static_cast<hipStream_t>(stream));
 }
-
-int om_get_wino14_variant(void) { return om::wino14_variant(); }
 
 int om_set_stem_fusion(int which, int on) {
     OM_REQUIRE((which == 0 || which == 1) && (on == 0 || on == 1), OM_EINVAL, "om_set_stem_fusion: which=%d on=%d", which, on);

@@ -1,6 +1,6 @@
-// Pieces shared by the two fused F(4,3)-along-the-rows kernels with split operands: conv_wino14.hip (eight consumer waves + four
-// producer waves, round 3) and conv_wino14d.hip (four dual-role waves, one per SIMD, round 5).  Same layer, same packed weights,
-// same epilogue, the same sequence of fp32 operations per output -- the two kernels are bit-identical.
+// Pieces shared by the kernels of conv_wino14.hip, the fused F(4,3)-along-the-rows 3x3 convolution with split operands: the
+// twelve-wave fused kernel and the two-kernel wide form.  Same layer, same packed weights, same epilogue, the same sequence of fp32
+// operations per output -- the two are bit-identical.
 #pragma once
 #include <cstdlib>
 #include <type_traits>
@@ -15,22 +15,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4v __attribute__((__vector_size__(4 * sizeof(unsigned))));
 
-
-#ifndef OM_W14_ABLATE
-#define OM_W14_ABLATE 0        // measurement builds only (wrong numerics): 2 no fragment reads, 4 no per-group barrier, 8 no weight
-#endif                         // DMA, 16 no input loads / transform, 32 no epilogue stores, 1024 no matrix instructions, 262144 the
-                               // input read at a channel-chunk-major layout's addresses (round 6, profiles/r06_experiments.md 1)
-#ifndef OM_W14_TRACE
-#define OM_W14_TRACE 0         // measurement builds only: s_memtime stamps of one tile's groups (tools/wino14_trace.py)
-#endif
-#if (OM_W14_ABLATE || OM_W14_TRACE) && !defined(OM_MEASUREMENT_BUILD)
-#error "measurement switches (wrong numerics / trace stores) are only for ab/ variants: build them with tools/build_variant.sh, which defines OM_MEASUREMENT_BUILD and never writes orienmask_amd/lib/"
-#endif
 constexpr int W14_BM = 128, W14_BN = 64;
-constexpr int W14_EMAX_ALL = 144;      // LDS entries per plane both kernels allow: (R + 2) * Ct <= 144 (wino14_geometry)
-#ifndef W14_SPREAD
-#define W14_SPREAD 1           // plane order of a chunk's six groups: 1 = 0, 5, 1, 2, 3, 4 (conv_wino14.hip: the producers' schedule)
-#endif
 
 struct Wino14Params {
     const float* in;        // NHWC fp32 view
@@ -46,33 +31,13 @@ struct Wino14Params {
     int R, Ct, ncb, gtot;   // block = R padded rows x Ct tile columns; ncb column blocks per row block; gtot = B * (H + 2)
     int n_tiles, total_tiles, nch;      // nch = cin / 16
     int u_bytes;
-#if OM_W14_TRACE
-    unsigned long long* trace;
-#endif
 };
 
-#if OM_W14_TRACE
-// Time stamps without disturbing the LDS queue: s_memtime is issued where the event happens and its result is only read behind
-// a wait the kernel has anyway.  [block][wave 0 / 4 / 8][group 0..63][4 stamps]
-static unsigned long long* g_w14_trace = nullptr;
-extern "C" void om_debug_w14_trace(void* buf) { g_w14_trace = static_cast<unsigned long long*>(buf); }
-#define W14_STAMP(x) asm volatile("s_memtime %0" : "=s"(x)::"memory")
-#define W14_SETTLE(a, b, c, d) asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(a), "+s"(b), "+s"(c), "+s"(d)::"memory")
-#define W14_SETTLE2(a, b) asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(a), "+s"(b)::"memory")
-__device__ __forceinline__ void w14_trace_put(const Wino14Params& p, int slot, int g, unsigned long long a, unsigned long long b,
-                                              unsigned long long c, unsigned long long d) {
-    if (blockIdx.x < 8 && g < 64 && (threadIdx.x & 63) == 0) {
-        unsigned long long* t = p.trace + ((blockIdx.x * 12 + slot) * 64 + g) * 4;
-        t[0] = a; t[1] = b; t[2] = c; t[3] = d;
-    }
-}
-#endif
-
 // Order in which the six planes (transform points) of a chunk are multiplied: group g of a chunk works on plane w14_plane(g) of V
-// and of U.  Pairs (1, 2), (3, 4), (0, 5): what the producers make in one group from shared differences of the same pixels.
-__host__ __device__ constexpr int w14_plane(int g) {
-    return W14_SPREAD ? (g == 0 ? 0 : g == 1 ? 5 : g - 1) : (g == 0 ? 1 : g == 1 ? 2 : g == 2 ? 3 : g == 3 ? 4 : g == 4 ? 0 : 5);
-}
+// and of U.  Pairs (1, 2), (3, 4), (0, 5): what the producers make in one group from shared differences of the same pixels.  The
+// order 0, 5, 1, 2, 3, 4 spreads the producers' input requests over the groups (conv_wino14.hip: the producers' schedule;
+// profiles/r03_experiments.md).
+__host__ __device__ constexpr int w14_plane(int g) { return g == 0 ? 0 : g == 1 ? 5 : g - 1; }
 
 struct Wino14Tile {
     int g0, t0, n0, tile_n;
@@ -193,10 +158,8 @@ __device__ __forceinline__ void wino14_epilogue(const Wino14Params& p, const f32
                     rc[rd] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_res, offset(rd, nx, p.res_ps), 0, 0));
             }
 #pragma unroll
-            for (int rd = 0; rd < 4; ++rd) {
-                if ((OM_W14_ABLATE & 32) && v[rd][0] != 123.f) continue;
+            for (int rd = 0; rd < 4; ++rd)
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, v[rd]), rs_out, offset(rd, px, p.out_ps), 0, 0);
-            }
             asm volatile("" ::: "memory");
         };
         using std::integral_constant;
@@ -228,11 +191,5 @@ __device__ __forceinline__ void wino14_epilogue(const Wino14Params& p, const f32
     }
     if (p.status && nonfinite != nonfinite) atomicOr(p.status, OM_STATUS_SPLIT_RANGE);
 }
-
-// conv_wino14d.hip
-bool wino14_dual_supported(const Wino14Params& p);
-int launch_wino14_dual(const Wino14Params& p, bool has_res, hipStream_t stream);
-int wino14_variant();               // 0: the twelve-wave kernel everywhere (default); 1: the dual-role kernel where it applies (OM_W14_VARIANT)
-void wino14_set_variant(int v);
 
 }  // namespace om

@@ -6,7 +6,7 @@ R=$PWD
 export TMPDIR=/tmp
 cd /tmp
 i=0
-# PMC_SHORT=1: the request-path counters only;  OM_LIB=ab/NAME.so: a variant build (tools/build_variant.sh);  PMC_TAG: output directory suffix
+# PMC_SHORT=1: the request-path counters only;  OM_LIB=path/to/liborienmask_hip.so: another build of the library;  PMC_TAG: output directory suffix
 if [ -n "$OM_LIB" ]; then case "$OM_LIB" in /*) ;; *) export OM_LIB=$R/$OM_LIB;; esac; ls -la $OM_LIB || exit 1; fi
 TAG=${PMC_TAG:-}
 rm -rf $R/gpurun_out/pmc14${TAG}_*

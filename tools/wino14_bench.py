@@ -22,9 +22,7 @@ def main():
     tot14 = tot24 = tot12 = 0.0
     shapes = SHAPES if not os.environ.get("OM_SHAPES") else [SHAPES[int(i)] for i in os.environ["OM_SHAPES"].split(",")]
     for hw, cin, cout, n in shapes:
-        # OM_W14_PROBE_INPUT=1 (with a -DW14_BIG_PROBE=1 build, conv_wino14.hip): the input tensor allocated twice as large (pixel stride
-        # 2 cin) -- the probe reads a transformed input of 1.5x the activation's bytes from it
-        ps = 2 * cin if os.environ.get("OM_W14_PROBE_INPUT") else cin
+        ps = cin
         x = torch.randn(B, hw, hw, ps, device=dev)
         if os.environ.get("ZERO_X"):        # the same instruction stream on zeros: what the clock under load costs (profiles/r05_experiments.md section 4)
             x.zero_()
@@ -39,9 +37,6 @@ def main():
         scratch = torch.empty(L.om_conv2d_winograd24_scratch_bytes(B, hw, hw, cin), dtype=torch.uint8, device=dev)
         st = omlib.current_stream_ptr(dev)
 
-        def run14_dual():
-            L.om_set_wino14_variant(1); run14(); L.om_set_wino14_variant(0)
-
         def run14():
             omlib.check(L.om_conv2d_wino14_split(p(x), B, hw, hw, cin, ps, p(u14), p(s14), p(hd), cout, 1, None, 0, p(out), cout, None, st), "w14")
 
@@ -55,8 +50,7 @@ def main():
         def run14_wide():       # the two-kernel wide form (round 6): V pre-pass + 128 x 128 tiles
             omlib.check(L.om_conv2d_wino14_wide(p(x), B, hw, hw, cin, ps, p(u14), p(s14), p(hd), cout, 1, None, 0, p(out), cout, p(vscratch), nb, None, st), "w14 wide")
         res = []
-        dual = bool(L.om_wino14_dual_built())       # only in libraries built with W14D=1
-        if os.environ.get("OM_W14_WIDE"):           # first column: the wide form instead of the dual-role kernel
+        if os.environ.get("OM_W14_WIDE"):           # the wide form next to the fused kernel, instead of the F(2x4) comparison
             for fn in ((run14_wide if wide_ok else run14), run14):
                 for _ in range(3):
                     fn()
@@ -71,7 +65,7 @@ def main():
             print("%3dx%-3d %4d->%-4d x%2d  two-kernel wide form %.3f ms   fused twelve-wave %.3f ms" % (hw, hw, cin, cout, n, res[0], res[1]), flush=True)
             tot14 += n * res[0]; tot12 += n * res[1]
             continue
-        for fn in ((run14_dual if dual else run14), run24, run14):
+        for fn in (run14, run24):
             for _ in range(3):
                 fn()
             torch.cuda.synchronize()
@@ -83,10 +77,13 @@ def main():
             torch.cuda.synchronize()
             res.append(a.elapsed_time(b) / 10)
         fl = 2.0 * B * hw * hw * cin * cout * 9
-        print("%3dx%-3d %4d->%-4d x%2d  fused F(4,3) dual-role %.3f ms (%.0f TF alg, %.0f TF executed)   twelve-wave %.3f ms   F(2x4) two kernels %.3f ms" % (
-            hw, hw, cin, cout, n, res[0], fl / res[0] / 1e9, 1.5 * fl / res[0] / 1e9, res[2], res[1]), flush=True)
-        tot14 += n * res[0]; tot24 += n * res[1]; tot12 += n * res[2]
-    print("all 37 layers: fused dual-role %.2f ms, twelve-wave %.2f ms, two-kernel %.2f ms" % (tot14, tot12, tot24))
+        print("%3dx%-3d %4d->%-4d x%2d  fused F(4,3) twelve-wave %.3f ms (%.0f TF alg, %.0f TF executed)   F(2x4) two kernels %.3f ms" % (
+            hw, hw, cin, cout, n, res[0], fl / res[0] / 1e9, 1.5 * fl / res[0] / 1e9, res[1]), flush=True)
+        tot14 += n * res[0]; tot24 += n * res[1]
+    if os.environ.get("OM_W14_WIDE"):
+        print("all 37 layers: wide form where it applies %.2f ms, fused twelve-wave %.2f ms" % (tot14, tot12))
+    else:
+        print("all 37 layers: fused twelve-wave %.2f ms, two-kernel F(2x4) %.2f ms" % (tot14, tot24))
 
 
 if __name__ == "__main__":
