@@ -761,6 +761,30 @@ int om_bn_sync_backward_dx(const float* x, const float* dy, int B, int C, int H,
                            const float* save_mean, const float* save_invstd, float slope, const double* sums_all, int R,
                            const double* n_total, float* dx, om_stream stream);
 
+/* ---- The gradients of the training model's convolutions (trainer/trainer.py:52 `loss.backward()` through every nn.Conv2d of
+ *      model/base.py:104-137 and the four plain head convolutions), for the three geometries the two models contain: ksize 1 stride 1,
+ *      ksize 3 stride 1, ksize 3 stride 2, padding ksize / 2, no dilation, no groups; anything else returns OM_EINVAL.  All tensors
+ *      fp32 NCHW contiguous: x, dx [B,cin,H,W]; dy [B,cout,Ho,Wo] with Ho = (H + 2*(ksize/2) - ksize) / stride + 1; w, dw
+ *      [cout,cin,ksize,ksize]; dbias [cout].  H and W are the INPUT's.  Any B, cin, cout, H, W >= 1 (B <= 16383, B*H*W < 2^30);
+ *      no alignment is required.
+ *      om_conv2d_grad_input:  dx = sum over co and the taps that reach the pixel of dy * w; at stride 2 the four parity classes of
+ *      input pixels are separate tile families with 1, 2, 2 and 4 taps.  An accumulation chain of the matrix instruction holds at
+ *      most 32 products; the chains of an element are summed in double and rounded once.  Needs no workspace (the arguments are
+ *      accepted and ignored).
+ *      om_conv2d_grad_weight: dw = sum over b and the output pixels of dy * x, the pixels split over workgroups, at most 2048 each: a
+ *      chain of the matrix instruction holds 32 products, a workgroup sums its chains in fp32 (at most 64), and with more than one
+ *      split the partial tiles go to `workspace` and a second kernel sums them in split order in double.  dbias (may be null) = sum
+ *      of dy over b and the plane, in double; dw may be null when dbias is not.  The number of splits is a function of the shape
+ *      and of the device's compute-unit count.  workspace: om_conv2d_grad_workspace_bytes for the shape on the current device (0
+ *      where one split suffices or the geometry is refused), undefined on entry; too small: OM_ENOMEM.
+ *      Fp32 operands on the f32 matrix instruction, fp32 accumulation.  Everything is enqueued on `stream`; no allocation, no host
+ *      synchronisation, no atomics, bit-identical from run to run.  A null dy / w / x / dx, or dw and dbias both null, returns OM_EINVAL. */
+size_t om_conv2d_grad_workspace_bytes(int B, int cin, int H, int W, int cout, int ksize, int stride);
+int om_conv2d_grad_input(const float* dy, const float* w, int B, int cin, int H, int W, int cout, int ksize, int stride, float* dx,
+                         void* workspace, size_t ws_bytes, om_stream stream);
+int om_conv2d_grad_weight(const float* x, const float* dy, int B, int cin, int H, int W, int cout, int ksize, int stride, float* dw,
+                          float* dbias, void* workspace, size_t ws_bytes, om_stream stream);
+
 /* ---- Several batches in flight.  Every entry point only enqueues kernels on the caller's stream and keeps no per-call state in
  *      the model handle (profiling apart): om_forward / om_forward_f16 / om_postprocess may be issued for different batches
  *      on different HIP streams at the same time, provided each batch in flight has its OWN workspace (and output buffers);

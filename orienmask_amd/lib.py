@@ -202,6 +202,9 @@ SIGNATURES = {
                                 _vp, _vp, _vp, _vp]),
     "om_bn_sync_backward_sums": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     "om_bn_sync_backward_dx": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _i, _vp, _vp, _vp]),
+    "om_conv2d_grad_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
+    "om_conv2d_grad_input": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "om_conv2d_grad_weight": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -25,7 +25,11 @@ And the reference's model in training mode: ``builder.build(config["model"], ori
                                statistics over every rank of a process group (om_bn_sync_*: an all-gather of per-channel double
                                records between the block's two phases, merged in rank order on every rank)
 
-The convolutions, forward and gradients, are torch's; the up-sampling, cat and split stay torch ops.
+  conv2d                       F.conv2d whose input, weight and bias gradients are om_conv2d_grad_input / om_conv2d_grad_weight
+                               (csrc/conv_grad.hip); the models use it with conv_backend='hip'
+
+The forward convolution is torch's.  Its gradients are torch's with conv_backend='torch' (the default) and the HIP kernels of
+csrc/conv_grad.hip with conv_backend='hip'; the up-sampling, cat and split stay torch ops.
 """
 import contextlib
 import ctypes
@@ -41,10 +45,11 @@ from . import pack as _pack
 from .arch import DARKNET_STAGES, LEAKY_SLOPE, model_convs
 from .loss import EvalCounter, OrienMaskYOLOMultiScaleLoss as _ValuesLoss
 
-__all__ = ["OrienMaskYOLOMultiScaleLoss", "EvalCounter", "ConvBNLeaky", "bn_leaky", "OrienMaskYOLOFPNPlus", "OrienMaskYOLO",
+__all__ = ["OrienMaskYOLOMultiScaleLoss", "EvalCounter", "ConvBNLeaky", "bn_leaky", "conv2d", "OrienMaskYOLOFPNPlus", "OrienMaskYOLO",
            "convert_sync_batchnorm"]
 
 BACKENDS = ("hip", "torch")
+CONV_BACKENDS = ("torch", "hip")
 
 
 class _LossBackward(torch.autograd.Function):
@@ -216,6 +221,74 @@ class _BNAct(torch.autograd.Function):
                 dy if ctx.has_residual and ctx.needs_input_grad[3] else None, None, None)
 
 
+class _Conv2d(torch.autograd.Function):
+    """forward(ctx, x, weight, bias, stride) -> F.conv2d(x, weight, bias, stride, ksize // 2).  Saved for the backward: x and the
+    weight, what torch's own node saves.  The backward enqueues om_conv2d_grad_input and om_conv2d_grad_weight (csrc/conv_grad.hip)
+    on the current stream for the gradients that are needed: no input gradient for an input that needs none, no weight gradient for
+    a frozen weight; the bias gradient comes from the weight-gradient call."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride):
+        ctx.save_for_backward(x, weight)
+        ctx.stride, ctx.has_bias = stride, bias is not None
+        return F.conv2d(x, weight, bias, stride, weight.shape[2] // 2)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        B, cin, H, W = x.shape
+        cout, ks = weight.shape[0], weight.shape[2]
+        dev = x.device
+        L = _lib.load()
+        dy = dy.contiguous()
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
+        dx = torch.empty_like(x) if need_x else None
+        dw = torch.empty_like(weight) if need_w else None
+        db = torch.empty(cout, dtype=torch.float32, device=dev) if need_b else None
+        stream = _lib.current_stream_ptr(dev)
+        geom = (B, cin, H, W, cout, ks, ctx.stride)
+        with _device(dev):
+            ws = _workspace(dev, stream, L.om_conv2d_grad_workspace_bytes(*geom))
+            if need_x:
+                _lib.check(L.om_conv2d_grad_input(_vp(dy), _vp(weight), *geom, _vp(dx), ws.data_ptr(), ws.numel(), stream),
+                           "om_conv2d_grad_input")
+            if need_w or need_b:
+                _lib.check(L.om_conv2d_grad_weight(_vp(x), _vp(dy), *geom, _vp(dw), _vp(db), ws.data_ptr(), ws.numel(), stream),
+                           "om_conv2d_grad_weight")
+        return dx, dw, db, None
+
+
+def _pair_of(v, what):
+    a, b = (v, v) if isinstance(v, int) else tuple(v)
+    if a != b:
+        raise _lib.OrienMaskHipError("conv2d: %s %r must be the same along both axes" % (what, v))
+    return int(a)
+
+
+def conv2d(x, weight, bias=None, stride=1, padding=0):
+    """F.conv2d(x, weight, bias, stride, padding) with the gradients as HIP kernels (csrc/conv_grad.hip).  x, weight and bias CUDA
+    float32, x NCHW-contiguous [B,cin,H,W], weight contiguous [cout,cin,k,k]; the geometry one of 1x1 stride 1 padding 0, 3x3
+    stride 1 padding 1, 3x3 stride 2 padding 1, without dilation or groups.  Anything else raises: there is no fallback."""
+    _lib.require_cuda_tensor(x, "the convolution input (conv_backend 'hip')", torch.float32)
+    _lib.require_cuda_tensor(weight, "the convolution weight (conv_backend 'hip')", torch.float32)
+    if bias is not None:
+        _lib.require_cuda_tensor(bias, "the convolution bias (conv_backend 'hip')", torch.float32)
+    if x.dim() != 4 or not x.is_contiguous():
+        raise _lib.OrienMaskHipError("conv_backend 'hip' takes NCHW-contiguous [B,C,H,W] activations, got strides %s for shape %s"
+                                     % (x.stride(), tuple(x.shape)))
+    if weight.dim() != 4 or not weight.is_contiguous() or weight.shape[1] != x.shape[1] or weight.shape[2] != weight.shape[3]:
+        raise _lib.OrienMaskHipError("conv2d: weight must be contiguous [cout,%d,k,k], got %s strides %s"
+                                     % (x.shape[1], tuple(weight.shape), weight.stride()))
+    if bias is not None and (tuple(bias.shape) != (weight.shape[0],) or not bias.is_contiguous()):
+        raise _lib.OrienMaskHipError("conv2d: bias must be contiguous [%d], got %s" % (weight.shape[0], tuple(bias.shape)))
+    ks, s, p = int(weight.shape[2]), _pair_of(stride, "stride"), _pair_of(padding, "padding")
+    if (ks, s, p) not in ((1, 1, 0), (3, 1, 1), (3, 2, 1)):
+        raise _lib.OrienMaskHipError("conv2d: kernel %d stride %d padding %d; the HIP gradients cover 1x1 stride 1 padding 0, 3x3 "
+                                     "stride 1 padding 1 and 3x3 stride 2 padding 1" % (ks, s, p))
+    return _Conv2d.apply(x, weight, bias, s)
+
+
 class _SyncBNAct(torch.autograd.Function):
     """forward(ctx, x, gamma, beta, residual, bn, slope, group) -> leaky(batch_norm(x)) (+ residual) with the batch statistics of
     every rank of `group` (torch.nn.SyncBatchNorm's): om_bn_sync_stats, an all-gather of the 3C-double record, om_bn_sync_forward;
@@ -319,13 +392,19 @@ class ConvBNLeaky(nn.Module):
     CUDA float32 tensors only -- anything else raises, there is no fallback.  backend 'torch': F.conv2d -> F.batch_norm ->
     F.leaky_relu, the comparator, and the only path that takes CPU tensors.  The block normalises with batch statistics while
     its BatchNorm module is in training mode and with the running statistics otherwise (model.eval(), backbone_batchnorm_eval).
-    After convert_sync_batchnorm (`sync` True) the batch statistics are those of every rank of `process_group`."""
+    After convert_sync_batchnorm (`sync` True) the batch statistics are those of every rank of `process_group`.
 
-    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, backend="hip"):
+    conv_backend 'torch' (default): the convolution is F.conv2d with torch's gradients.  conv_backend 'hip': the same forward
+    through conv2d, whose gradients are the HIP kernels of csrc/conv_grad.hip; CUDA float32 NCHW-contiguous tensors only."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, backend="hip", conv_backend="torch"):
         super().__init__()
         if backend not in BACKENDS:
             raise ValueError("backend must be one of %s, got %r" % (BACKENDS, backend))
+        if conv_backend not in CONV_BACKENDS:
+            raise ValueError("conv_backend must be one of %s, got %r" % (CONV_BACKENDS, conv_backend))
         self.backend = backend
+        self.conv_backend = conv_backend
         self.sync, self.process_group = False, None          # set by convert_sync_batchnorm
         self.conv_block = nn.Sequential(
             nn.Conv2d(in_channels, out_channels, kernel_size, stride=stride, padding=padding, bias=False),
@@ -336,7 +415,10 @@ class ConvBNLeaky(nn.Module):
         conv, bn, act = self.conv_block[0], self.conv_block[1], self.conv_block[2]
         if bn.momentum is None:
             raise ValueError("ConvBNLeaky: momentum=None (a cumulative moving average) is not supported")
-        h = F.conv2d(x, conv.weight, None, conv.stride, conv.padding)
+        if self.conv_backend == "hip":
+            h = conv2d(x, conv.weight, None, conv.stride, conv.padding)
+        else:
+            h = F.conv2d(x, conv.weight, None, conv.stride, conv.padding)
         training = bn.training or bn.running_mean is None
         synced = self.sync and bn.training and _sync_world_size(self.process_group) > 1
         if training and h.numel() // h.shape[1] <= 1 and not synced:
@@ -388,24 +470,28 @@ class _Backbone(_Container):
 
 class OrienMaskYOLOFPNPlus(nn.Module):
     """The reference's OrienMaskYOLOFPNPlus (model/orienmask_yolo_fpnplus.py:9-90) for training: the same constructor arguments
-    plus `backend` ('hip' / 'torch', see ConvBNLeaky), the same state_dict keys and parameters() order as the reference and as
+    plus `backend` ('hip' / 'torch') and `conv_backend` ('torch' / 'hip': whose convolution gradients, see ConvBNLeaky; with 'hip'
+    the plain head convolutions go through conv2d on the nn.Conv2d modules' parameters), the same state_dict keys and parameters() order as the reference and as
     orienmask_amd.model (checkpoints and optimizer state move in both directions), trainable parameters, and a forward that
     returns the reference's ((bbox32, orien32), (bbox16, orien16), (bbox8, orien8)) with a graph behind it."""
 
     def __init__(self, num_anchors, num_classes, pretrained=None, freeze_backbone=False, backbone_batchnorm_eval=False,
-                 backend="hip"):
+                 backend="hip", conv_backend="torch"):
         super().__init__()
         if freeze_backbone is not False:
             # the reference's DarkNet53._freeze_network calls self._freeze_module, which does not exist (darknet.py:31-38)
             raise NotImplementedError("freeze_backbone=%r: the reference's own _freeze_network cannot run; not supported" % (freeze_backbone,))
         if backend not in BACKENDS:
             raise ValueError("backend must be one of %s, got %r" % (BACKENDS, backend))
+        if conv_backend not in CONV_BACKENDS:
+            raise ValueError("conv_backend must be one of %s, got %r" % (CONV_BACKENDS, conv_backend))
         self.num_anchors = num_anchors
         self.num_classes = num_classes
         self.pretrained = pretrained
         self.freeze_backbone = freeze_backbone
         self.backbone_batchnorm_eval = backbone_batchnorm_eval
         self.backend = backend
+        self.conv_backend = conv_backend
         self.backbone = _Backbone(backbone_batchnorm_eval)
         self._plus = type(self).__name__ == "OrienMaskYOLOFPNPlus"
         self._by_name = {}
@@ -418,7 +504,8 @@ class OrienMaskYOLOFPNPlus(nn.Module):
                 node = node._modules[p]
             pad = spec.ksize // 2
             if spec.bn:
-                m = ConvBNLeaky(spec.cin, spec.cout, spec.ksize, stride=spec.stride, padding=pad, backend=backend)
+                m = ConvBNLeaky(spec.cin, spec.cout, spec.ksize, stride=spec.stride, padding=pad, backend=backend,
+                                conv_backend=conv_backend)
             else:
                 m = nn.Conv2d(spec.cin, spec.cout, spec.ksize, stride=spec.stride, padding=pad)
             node.add_module(leaf, m)
@@ -477,8 +564,15 @@ class OrienMaskYOLOFPNPlus(nn.Module):
             feats[idx] = x
         return feats[6], feats[5], feats[4], feats[3]
 
+    def _plain(self, name, x):
+        """A head's nn.Conv2d: the module itself, or conv2d on its parameters (conv_backend 'hip')."""
+        m = self._by_name[name]
+        if self.conv_backend == "hip":
+            return conv2d(x, m.weight, m.bias, m.stride, m.padding)
+        return m(x)
+
     def _bbox_head(self, s, x):
-        return self._by_name["bbox_head%d.1" % s](self._by_name["bbox_head%d.0" % s](x))
+        return self._plain("bbox_head%d.1" % s, self._by_name["bbox_head%d.0" % s](x))
 
     def forward(self, x):
         if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] % 32 or x.shape[3] % 32:
@@ -496,7 +590,7 @@ class OrienMaskYOLOFPNPlus(nn.Module):
         else:
             cat4 = [self._route("route8.0", neck8, 2), x4]
         oriens = self._run("neck4", torch.cat(cat4, dim=1))
-        oriens = self._by_name["orien_head.5"](self._run("orien_head", oriens))
+        oriens = self._plain("orien_head.5", self._run("orien_head", oriens))
         orien32, orien16, orien8 = torch.split(oriens, self.num_anchors * 2, dim=1)
         return (bbox32, orien32), (bbox16, orien16), (bbox8, orien8)
 
