@@ -7,7 +7,8 @@
 // flips -- XORed into a zeroed bitmap, then a prefix XOR in pixel order turns the toggles into the mask:
 //   polygon          rleFrPoly's points (maskApi.c): each kept boundary point toggles x * h + y; equal positions cancel, which is
 //                    the zero-run merge after rleFrPoly's sort, and y = h toggles the top of column x + 1 (the sort is global)
-//   counts           an uncompressed RLE: a toggle at every prefix sum of the counts
+//   counts           an uncompressed RLE: a toggle at every prefix sum of the counts (but none after a last run of zeros: where
+//                    the counts stop short of the image, the rest stays 0 as in rleDecode)
 //   string           a compressed RLE: rleFrString's decode, then the same toggles
 // The polygons of one annotation get a bitmap each and are ORed (maskUtils.merge, intersect = 0).
 //
@@ -38,8 +39,9 @@ __device__ inline void toggle(uint32_t* bm, int h, int hw, long long p, long lon
 }
 
 // point d of edge j of the upsampled polygon (rleFrPoly's first loop, including its flip rule).  A zero-length edge (a repeated
-// vertex) divides 0 / 0: its one point has u = xs exactly and v = (int)NaN, undefined in C (x86: INT_MIN, here 0); v only ever
-// enters through min(v, v_prev) and the clamp of y at 0, so every value <= 0 gives the same mask.
+// vertex) divides 0 / 0: its one point has u = xs exactly and v = (int)NaN, undefined in C (x86: INT_MIN, here 0); v is only read
+// where u differs from a neighbouring point's, and both neighbours lie on the same vertex, so no value changes the mask
+// (tests/test_cocoeval_kernels_cpu.py proves it).
 __device__ inline void edge_point(const int* xs_, const int* ys_, int k, int j, int d, int& u, int& v) {
     int xs = xs_[j], xe = xs_[j + 1 == k ? 0 : j + 1], ys = ys_[j], ye = ys_[j + 1 == k ? 0 : j + 1];
     const int dx = abs(xe - xs), dy = abs(ys - ye);
@@ -120,7 +122,9 @@ __global__ __launch_bounds__(256) void coco_seq_toggle_kernel(int first, int n, 
         const uint32_t* c = counts + src_data_off[s];
         for (int j = 0; j < len && pos < n_pix; ++j) {
             pos += c[j];
-            toggle(bm, h, hw, pos, n_pix);
+            // rleDecode leaves the pixels after the last run 0: where the counts stop short of the image, only a run of ones
+            // (odd j) ends in a toggle
+            if (j + 1 < len || (j & 1)) toggle(bm, h, hw, pos, n_pix);
         }
     } else {
         const uint8_t* str = strings + src_data_off[s];
@@ -140,7 +144,7 @@ __global__ __launch_bounds__(256) void coco_seq_toggle_kernel(int first, int n, 
             const uint32_t cnt = (uint32_t)x;
             c2 = c1; c1 = cnt; ++mcnt;
             pos += cnt;
-            toggle(bm, h, hw, pos, n_pix);
+            if (p < len || !(mcnt & 1)) toggle(bm, h, hw, pos, n_pix);         // as above: mcnt - 1 is this run's index
         }
     }
 }

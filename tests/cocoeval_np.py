@@ -23,8 +23,9 @@ def _c_int(v):
     return int(math.trunc(v))
 
 
-def rle_fr_poly(xy, h, w):
-    """maskApi.c rleFrPoly -> run lengths."""
+def rle_fr_poly(xy, h, w, trace=None):
+    """maskApi.c rleFrPoly -> run lengths.  trace: a dict that receives the upsampled points u, v and the kept boundary points
+    x, y (for tests that must know what a polygon exercised); it changes nothing."""
     k = len(xy) // 2
     scale = 5.0
     x = [_c_int(scale * xy[j * 2 + 0] + .5) for j in range(k)] + [0]
@@ -69,6 +70,8 @@ def rle_fr_poly(xy, h, w):
             yd = math.ceil(yd)
             xs_.append(int(xd))
             ys_.append(int(yd))
+    if trace is not None:
+        trace.update(u=u, v=v, x=xs_, y=ys_)
     a = [xs_[j] * h + ys_[j] for j in range(len(xs_))]
     a.append(h * w)
     a.sort()
@@ -101,8 +104,33 @@ def counts_to_mask(counts, h, w):
     return flat.reshape(w, h).T.copy()
 
 
-def ann_mask(segm, h, w):
-    """annToRLE + decode: polygons (or the 4-number box quirk) merged by OR, uncompressed and compressed RLE."""
+def rle_fr_string(s):
+    """maskApi.c rleFrString -> counts (uint32, as C keeps them), in plain Python.  Where the string ends in the middle of a
+    count the C code reads past the terminator (undefined); here the count keeps the bits read so far, without a sign
+    extension, which is the one defined reading of "the input ends"."""
+    if isinstance(s, str):
+        s = s.encode('ascii')
+    cnts, p = [], 0
+    while p < len(s):
+        x, k, more = 0, 0, 1
+        while more and p < len(s):
+            c = s[p] - 48
+            x |= (c & 0x1f) << 5 * k
+            more = c & 0x20
+            p += 1
+            k += 1
+            if not more and (c & 0x10):
+                x |= -1 << 5 * k
+        if len(cnts) > 2:
+            x += cnts[-2]
+        cnts.append(x & 0xffffffff)
+    return cnts
+
+
+def ann_mask(segm, h, w, strict=True):
+    """annToRLE + decode: polygons (or the 4-number box quirk) merged by OR, uncompressed and compressed RLE.
+    strict=False decodes a string with rle_fr_string above and lets the counts stop short of or overrun h * w (the runs past
+    the last pixel are dropped), for the malformed sources of tests/cocoeval_cases.py."""
     if isinstance(segm, list):
         m = np.zeros((h, w), dtype=np.uint8)
         for p in segm:
@@ -115,6 +143,8 @@ def ann_mask(segm, h, w):
     rh, rw = segm['size']
     if isinstance(segm['counts'], list):
         return counts_to_mask(segm['counts'], rh, rw)
+    if not strict:
+        return counts_to_mask(rle_fr_string(segm['counts']), rh, rw)
     from oracle.orienmask_ref import rle_string_decode
     return counts_to_mask(rle_string_decode(segm['counts'], rh * rw), rh, rw)
 
@@ -263,6 +293,37 @@ class Eval:
         a = np.array([d['area'] < aRng[0] or d['area'] > aRng[1] for d in dt]).reshape((1, len(dt)))
         dtIg = np.logical_or(dtIg, np.logical_and(dtm == 0, np.repeat(a, T, 0)))
         return {'dtMatches': dtm, 'gtMatches': gtm, 'dtScores': [d['score'] for d in dt], 'gtIgnore': gtIg, 'dtIgnore': dtIg}
+
+    @classmethod
+    def match_direct(cls, gts, dts, ious):
+        """evaluate_img on one (image, category) group given directly: gts (dicts with id, area, iscrowd, in json order), dts
+        (dicts with id, area, score, already in descending score order and cut to maxDets[-1]) and their [D, G] IoU matrix.
+        Returns one evaluate_img record per area range, with gtMatches and gtIgnore put back into the json order of gts."""
+        e = cls.__new__(cls)
+        key = (0, 0)
+        e._gts = {key: [dict(g, ignore=g.get('iscrowd', 0)) for g in gts]} if gts else {}
+        e._dts = {key: [dict(d) for d in dts]} if dts else {}
+        e.ious = {key: np.asarray(ious, dtype=np.float64).reshape(len(dts), len(gts)) if len(gts) and len(dts) else []}
+        out = []
+        for aRng in AREA_RNG:
+            r = e.evaluate_img(0, 0, aRng, MAX_DETS[-1])
+            if r is not None and len(gts):
+                gtind = np.argsort([g['_ignore'] for g in e._gts[key]], kind='mergesort')
+                inv = np.argsort(gtind, kind='mergesort')
+                r = dict(r, gtMatches=r['gtMatches'][:, inv], gtIgnore=r['gtIgnore'][inv])
+            out.append(r)
+        return out
+
+    @classmethod
+    def match_lanes(cls, gts, dts, ious):
+        """match_direct as three arrays of 40 rows, row t + 10 a for IoU threshold t and area range a: the matched gt's id per
+        det (0: none), the det's ignore flag, and gtMatches > 0 per gt in json order."""
+        D, G = len(dts), len(gts)
+        recs = cls.match_direct(gts, dts, ious)
+        n = len(IOU_THRS) * len(AREA_RNG)
+        return (np.concatenate([r['dtMatches'] for r in recs]).astype(np.int64).reshape(n, D),
+                np.concatenate([np.asarray(r['dtIgnore']) for r in recs]).astype(np.uint8).reshape(n, D),
+                np.concatenate([r['gtMatches'] > 0 for r in recs]).astype(np.uint8).reshape(n, G))
 
     def accumulate(self):
         self.eval = accumulate(self.evalImgs, len(self.cat_ids), len(self.img_ids))

@@ -15,7 +15,20 @@ def _free_port():
         return s.getsockname()[1]
 
 
+def _few_threads():
+    """Two ranks share this machine's CPUs: torch's default of one thread per CPU it sees, in each rank, oversubscribes them
+    several times over wherever the process may use fewer CPUs than it sees, and the packing then takes minutes instead of seconds."""
+    torch.set_num_threads(min(4, torch.get_num_threads()))
+
+
+def _stop(procs):
+    for p in procs:                             # a rank that outlived a failed test must not load the tests after it
+        if p.is_alive():
+            p.terminate()
+
+
 def _worker(rank, world, port, q):
+    _few_threads()
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -71,16 +84,20 @@ def test_two_rank_broadcast_and_merge(built):
     procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()
-    results = sorted(q.get(timeout=300) for _ in range(2))
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    try:
+        results = sorted(q.get(timeout=300) for _ in range(2))
+        for p in procs:
+            p.join(timeout=60)
+            assert p.exitcode == 0
+    finally:
+        _stop(procs)
     assert [r[1] for r in results] == [True, True]              # both ranks hold rank 0's weights and packed them identically
     assert (results[0][2], results[0][3], results[1][2], results[1][3]) == (0, 34, 34, 67)
     assert results[0][4] == list(range(67)) and results[1][4] == list(range(67))
 
 
 def _tester_worker(rank, world, port, q):
+    _few_threads()
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -115,10 +132,13 @@ def test_two_rank_sharded_tester_merges_in_dataset_order(built):
     procs = [ctx.Process(target=_tester_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()
-    results = sorted(q.get(timeout=300) for _ in range(2))
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    try:
+        results = sorted(q.get(timeout=300) for _ in range(2))
+        for p in procs:
+            p.join(timeout=60)
+            assert p.exitcode == 0
+    finally:
+        _stop(procs)
     assert [r[1] for r in results] == [6, 5]
     assert results[0][2] == results[1][2] and [m["id"] for m in results[0][2]] == list(range(11))
     # the single-process loader sees the same images (SyntheticLoader seeds every image by its id): ALL merged fingerprints are
