@@ -6,6 +6,9 @@ coefficients, double nearest indices); pixel arithmetic is float64.
   resize_linear / resize_nearest          resize.cpp INTER_LINEAR (INTER_AREA at an exact 2x downscale), resizeNN
   copy_make_border                        BORDER_CONSTANT
   render(plan)                            the collated image and masks of one planned sample
+  jitter_branches                         the chain and its twin whose hue at the 0/360 seam is carried across it
+  jitter32 / render_image32               the same composition in float32, in the kernels' operation order: a CPU stand-in for the
+                                          device in tests/test_augment_directed_cpu.py, never an expected value
 
 Not checked against cv2 itself (cv2 is not a dependency of this project): this is what the kernels and the fixtures agree on.
 """
@@ -20,8 +23,10 @@ BORDER_CONSTANT = 0
 SECTOR = np.array([[1, 3, 0], [1, 0, 2], [3, 0, 1], [0, 2, 1], [0, 1, 3], [2, 1, 0]])
 
 
-def gray(img):
+def gray(img, mut=()):
     img = np.asarray(img, np.float64)
+    if "gray_bgr" in mut:
+        return img[..., 2] * GRAY[0] + img[..., 1] * GRAY[1] + img[..., 0] * GRAY[2]
     return img[..., 0] * GRAY[0] + img[..., 1] * GRAY[1] + img[..., 2] * GRAY[2]
 
 
@@ -38,7 +43,16 @@ def rgb2hsv(img):
     return np.stack([h, s, v], axis=-1)
 
 
-def hsv2rgb(hsv):
+def sector_table(mut=()):
+    """cv2's sector table, or mutation 'sector_swap': the g and r entries of sector 2 exchanged."""
+    if "sector_swap" not in mut:
+        return SECTOR
+    tab = SECTOR.copy()
+    tab[2, 1], tab[2, 2] = SECTOR[2, 2], SECTOR[2, 1]
+    return tab
+
+
+def hsv2rgb(hsv, mut=()):
     hsv = np.asarray(hsv, np.float64)
     h, s, v = hsv[..., 0] * (6.0 / 360.0), hsv[..., 1], hsv[..., 2]
     h = np.mod(h, 6.0)
@@ -48,7 +62,7 @@ def hsv2rgb(hsv):
     sector = np.where(bad, 0, sector)
     h = np.where(bad, 0.0, h)
     tab = np.stack([v, v * (1 - s), v * (1 - s * h), v * (1 - s * (1 - h))], axis=-1)
-    idx = SECTOR[sector]
+    idx = sector_table(mut)[sector]
     b = np.take_along_axis(tab, idx[..., 0:1], -1)[..., 0]
     g = np.take_along_axis(tab, idx[..., 1:2], -1)[..., 0]
     r = np.take_along_axis(tab, idx[..., 2:3], -1)[..., 0]
@@ -74,11 +88,27 @@ def is_area2x(src_hw, dst_hw):
     return src_hw[0] == 2 * dst_hw[0] and src_hw[1] == 2 * dst_hw[1]
 
 
-def resize_linear(img, dsize):
-    """img [h,w,c] -> [dh,dw,c] float64; dsize = (dw, dh) as cv2 takes it."""
+def area2x_taps(src, dst):
+    """Rows (or columns) 2d and 2d + 1 of the 2x2 mean, kept inside the window (they only leave it under 'area2x_one_axis')."""
+    d = np.arange(dst)
+    return np.minimum(2 * d, src - 1), np.minimum(2 * d + 1, src - 1)
+
+
+def takes_area2x(src_hw, dst_hw, mut=()):
+    """Mutation 'area2x_one_axis': the 2x2 mean taken as soon as ONE axis halves."""
+    if "area2x_one_axis" in mut:
+        return src_hw[0] == 2 * dst_hw[0] or src_hw[1] == 2 * dst_hw[1]
+    return is_area2x(src_hw, dst_hw)
+
+
+def resize_linear(img, dsize, mut=()):
+    """img [h,w,c] -> [dh,dw,c] float64; dsize = (dw, dh) as cv2 takes it.  mut: 'area2x_one_axis'."""
     img = np.asarray(img, np.float64)
     dw, dh = dsize
     h, w = img.shape[:2]
+    if "area2x_one_axis" in mut and takes_area2x((h, w), (dh, dw), mut):
+        (ya, yb), (xa, xb) = area2x_taps(h, dh), area2x_taps(w, dw)
+        return (img[ya][:, xa] + img[ya][:, xb] + img[yb][:, xa] + img[yb][:, xb]) * 0.25
     if is_area2x((h, w), (dh, dw)):
         return (img[0::2, 0::2] + img[0::2, 1::2] + img[1::2, 0::2] + img[1::2, 1::2]) * 0.25
     x0, x1, fx, ax = linear_coeffs(dw, w)
@@ -111,19 +141,145 @@ def copy_make_border(img, top, bottom, left, right, value):
 
 
 # ---- the jitter ops of BaseTransform (adjust_*), float64 ------------------------------------------------------------
-def jitter(img, ops, mut=()):
-    img = np.asarray(img, np.float64)
+GRAY_BLOCKS, GRAY_THREADS = 256, 256        # the grey-mean reduction's grid: workgroups per image, threads per workgroup
+
+
+def contrast_mean(g, mut=(), crop=None):
+    """Mean (a Python float) of the grey plane g [h,w] that adjust_contrast takes: over the FULL source.  Mutations:
+    'mean_of_crop' (over the crop window), 'mean_first_pass' (a reduction loop that runs once: only the first 256 pixels of each of
+    the 256 chunks are summed)."""
+    if "mean_of_crop" in mut and crop is not None:
+        top, left, ch, cw = crop
+        g = g[top:top + ch, left:left + cw]
+    if "mean_first_pass" in mut:
+        flat = np.asarray(g, np.float64).reshape(-1)
+        chunk = (flat.size + GRAY_BLOCKS - 1) // GRAY_BLOCKS
+        return float(sum(flat[b * chunk:min(b * chunk + min(chunk, GRAY_THREADS), flat.size)].sum() for b in range(GRAY_BLOCKS))
+                     / flat.size)
+    if g.dtype == np.float64:
+        return float(g.mean())
+    return float(g.sum(dtype=np.float64) / g.size)
+
+
+def _hue_op(img, f, mut=(), move=None):
+    """adjust_hue in float64.  move: bool per pixel -- the hue is carried across the 0/360 seam before the shift and the clip."""
+    hsv = rgb2hsv(img)
+    h = hsv[..., 0]
+    if move is not None:
+        h = np.where(move, np.where(h > 180, h - 360, h + 360), h)
+    hsv[..., 0] = np.mod(h + f * 360, 360) if "hue_wrap" in mut else np.clip(h + f * 360, 0, 360)
+    out = hsv2rgb(hsv, mut)
+    return np.clip(out, 0, 255) if "hue_clip_255" in mut else out
+
+
+def _op(img, src, code, f, mut, crop, move=None, mean_of=None):
+    if code == 0:
+        return np.clip(img * f, 0, 255)
+    if code == 1:
+        mean = contrast_mean(gray(src if "mean_before_ops" in mut else img if mean_of is None else mean_of, mut), mut, crop)
+        return np.clip(img * f + mean * (1 - f), 0, 255)
+    if code == 2:
+        return np.clip(img * f + gray(img, mut)[..., None] * (1 - f), 0, 255)
+    return _hue_op(img, f, mut, move)
+
+
+def jitter(img, ops, mut=(), crop=None):
+    """mut: 'hue_wrap', 'sector_swap', 'gray_bgr', 'mean_of_crop' (needs crop = (top, left, h, w)), 'mean_before_ops',
+    'hue_clip_255', 'mean_first_pass'."""
+    src = img = np.asarray(img, np.float64)
     for code, f in ops:
+        img = _op(img, src, code, f, mut, crop)
+    return img
+
+
+def near_seam(h, eps):
+    return (h < eps) | (h > 360 - eps)
+
+
+def jitter_branches(img, ops, eps):
+    """(a, alt, seam): a is jitter(img, ops); alt is the same chain where, at every hue op, the pixels whose float64 hue before the
+    shift lies within eps of the 0/360 seam have that hue carried across it (h - 360 if h > 180, else h + 360) before the shift
+    and the clip; seam [h,w] bool is the union of those pixels.  A later contrast takes a's grey mean in both, so alt differs from
+    a on seam pixels only.  A float32 hue that rounds to the other side of the seam lands on alt, so a seam pixel must match one
+    of two stated values."""
+    src = a = alt = np.asarray(img, np.float64)
+    seam = np.zeros(a.shape[:-1], bool)
+    for code, f in ops:
+        move = None
+        if code == 3:
+            move = near_seam(rgb2hsv(alt)[..., 0], eps)
+            seam = seam | move | near_seam(rgb2hsv(a)[..., 0], eps)
+        a, alt = _op(a, src, code, f, (), None), _op(alt, src, code, f, (), None, move, a)
+    return a, alt, seam
+
+
+# ---- the same chain in float32, operation by operation as csrc/augment.hip's apply_ops runs it (no fused multiply-add: numpy
+# rounds every product).  The CPU stand-in for the device in tests/test_augment_directed_cpu.py; never an expected value.
+F32 = np.float32
+EPS32 = F32(FLT_EPSILON)
+GRAY32 = tuple(F32(c) for c in (0.299, 0.587, 0.114))
+
+
+def gray32(img, mut=()):
+    r, g, b = (img[..., 2], img[..., 1], img[..., 0]) if "gray_bgr" in mut else (img[..., 0], img[..., 1], img[..., 2])
+    return r * GRAY32[0] + g * GRAY32[1] + b * GRAY32[2]
+
+
+def rgb2hsv32(img):
+    r, g, b = img[..., 0], img[..., 1], img[..., 2]
+    v = np.maximum(np.maximum(r, g), b)
+    vmin = np.minimum(np.minimum(r, g), b)
+    diff = v - vmin
+    s = diff / (np.abs(v) + EPS32)
+    k = (60.0 / (diff + EPS32).astype(np.float64)).astype(F32)
+    h = np.where(v == r, (g - b) * k, np.where(v == g, (b - r) * k + F32(120), (r - g) * k + F32(240)))
+    h = np.where(h < 0, h + F32(360), h)
+    return h, s, v
+
+
+def hsv2rgb32(h, s, v, mut=()):
+    h = h * (F32(6) / F32(360))
+    while (h < 0).any():
+        h = np.where(h < 0, h + F32(6), h)
+    while (h >= 6).any():
+        h = np.where(h >= 6, h - F32(6), h)
+    sector = np.floor(h).astype(np.int64)
+    h = h - sector.astype(F32)
+    bad = (sector < 0) | (sector >= 6)
+    sector = np.where(bad, 0, sector)
+    h = np.where(bad, F32(0), h)
+    one = F32(1)
+    tab = np.stack([v, v * (one - s), v * (one - s * h), v * (one - s * (one - h))], axis=-1)
+    idx = sector_table(mut)[sector]
+    b = np.take_along_axis(tab, idx[..., 0:1], -1)[..., 0]
+    g = np.take_along_axis(tab, idx[..., 1:2], -1)[..., 0]
+    r = np.take_along_axis(tab, idx[..., 2:3], -1)[..., 0]
+    out = np.stack([r, g, b], axis=-1)
+    return np.where((s == 0)[..., None], v[..., None], out)
+
+
+def jitter32(img, ops, mut=(), crop=None):
+    """[h,w,3] float32.  fa = float32(f); fb = float32(1 - f), float32(360 f) for hue; the grey mean summed in double and rounded
+    to float32, its product with fb in float32; 60 / (diff + eps) in double and rounded.  mut as jitter's."""
+    src = img = np.asarray(img).astype(F32)
+    lo, hi = F32(0), F32(255)
+    for code, f in ops:
+        fa = F32(f)
+        fb = F32(f * 360) if code == 3 else F32(1 - f)
         if code == 0:
-            img = np.clip(img * f, 0, 255)
+            img = np.clip(img * fa, lo, hi)
         elif code == 1:
-            img = np.clip(img * f + gray(img).mean() * (1 - f), 0, 255)
+            mean = F32(contrast_mean(gray32(src if "mean_before_ops" in mut else img, mut), mut, crop))
+            img = np.clip(img * fa + mean * fb, lo, hi)
         elif code == 2:
-            img = np.clip(img * f + gray(img)[..., None] * (1 - f), 0, 255)
+            img = np.clip(img * fa + (gray32(img, mut) * fb)[..., None], lo, hi)
         else:
-            hsv = rgb2hsv(img)
-            hsv[..., 0] = np.mod(hsv[..., 0] + f * 360, 360) if "hue_wrap" in mut else np.clip(hsv[..., 0] + f * 360, 0, 360)
-            img = hsv2rgb(hsv)
+            h, s, v = rgb2hsv32(img)
+            h = np.mod(h + fb, F32(360)) if "hue_wrap" in mut else np.clip(h + fb, lo, F32(360))
+            img = hsv2rgb32(h, s, v, mut)
+            if "hue_clip_255" in mut:
+                img = np.clip(img, lo, hi)
+        assert img.dtype == F32
     return img
 
 
@@ -151,34 +307,34 @@ def _flip(a, plan):
     return a
 
 
+def _edge_axis(dst, src, off, full):
+    """Mutation 'image_edge' along one axis: (g0, g1, w1) as indices into the SOURCE, clamped at the source's border."""
+    scale = 1.0 / (float(dst) / src)
+    f = (((np.arange(dst, dtype=np.float64) + 0.5) * scale) - 0.5).astype(np.float32)
+    s0 = np.floor(f).astype(np.int64)
+    f = (f - s0.astype(np.float32)).astype(np.float64)
+    g0 = s0 + off
+    lo, hi = g0 < 0, g0 >= full - 1
+    g0[lo], f[lo] = 0, 0
+    g0[hi], f[hi] = full - 1, 0
+    return g0, np.minimum(g0 + 1, full - 1), f
+
+
 def _resize_image_edge(img, plan):
     """Mutation 'image_edge': INTER_LINEAR whose taps clamp at the SOURCE image's border instead of the crop window's."""
     top, left, ch, cw = plan['crop']
     nh, nw = plan['resize'][:2]
-
-    def axis(dst, src, off, full):
-        scale = 1.0 / (float(dst) / src)
-        f = (((np.arange(dst, dtype=np.float64) + 0.5) * scale) - 0.5).astype(np.float32)
-        s0 = np.floor(f).astype(np.int64)
-        f = (f - s0.astype(np.float32)).astype(np.float64)
-        g0 = s0 + off
-        lo, hi = g0 < 0, g0 >= full - 1
-        g0[lo], f[lo] = 0, 0
-        g0[hi], f[hi] = full - 1, 0
-        return g0, np.minimum(g0 + 1, full - 1), f
-
-    x0, x1, fx = axis(nw, cw, left, img.shape[1])
-    y0, y1, fy = axis(nh, ch, top, img.shape[0])
+    x0, x1, fx = _edge_axis(nw, cw, left, img.shape[1])
+    y0, y1, fy = _edge_axis(nh, ch, top, img.shape[0])
     rows = img[:, x0] * (1 - fx)[:, None] + img[:, x1] * fx[:, None]
     return rows[y0] * (1 - fy)[:, None, None] + rows[y1] * fy[:, None, None]
 
 
-def render_image(image, plan, mut=()):
-    """[3,H,W] float64: the collated, normalised image of one planned sample (image: the SOURCE [h,w,3]).  mut: deliberate bugs
-    for the mutation tests ('image_edge', 'hue_wrap', 'flip_before_pad')."""
-    img = jitter(image, plan['ops'], mut)
+def place_image(img, plan, mut=()):
+    """[3,H,W] float64: the geometry half of render_image -- crop, resize, pad, flips, Normalize -- of an already jittered SOURCE
+    [h,w,3].  mut: 'image_edge', 'flip_before_pad', 'area2x_one_axis'."""
     win, (nh, nw, pt, pl, oh, ow) = _geometry(plan, img)
-    res = _resize_image_edge(img, plan) if "image_edge" in mut else resize_linear(win, (nw, nh))
+    res = _resize_image_edge(img, plan) if "image_edge" in mut else resize_linear(win, (nw, nh), mut)
     pad = [float(np.float32(v)) for v in plan['pad_value']]
     if "flip_before_pad" in mut:
         out = copy_make_border(_flip(res, plan), pt, oh - nh - pt, pl, ow - nw - pl, pad)
@@ -187,6 +343,43 @@ def render_image(image, plan, mut=()):
     mean = np.asarray(plan['mean'], np.float64)
     std = np.asarray(plan['std'], np.float64)
     return ((out - mean) / std).transpose(2, 0, 1)
+
+
+def render_image(image, plan, mut=()):
+    """[3,H,W] float64: the collated, normalised image of one planned sample (image: the SOURCE [h,w,3]).  mut: deliberate bugs
+    for the mutation tests (jitter's and place_image's)."""
+    return place_image(jitter(image, plan['ops'], mut, plan['crop']), plan, mut)
+
+
+def render_image32(image, plan, mut=()):
+    """[3,H,W] float32: jitter32 on every tap, then the blend, the pad and Normalize in float32 in the image kernel's order -- the
+    CPU stand-in for the device.  mut: jitter32's, 'image_edge', 'area2x_one_axis'."""
+    img = jitter32(image, plan['ops'], mut, plan['crop'])
+    top, left, ch, cw = plan['crop']
+    nh, nw, pt, pl = plan['resize']
+    oh, ow = plan['out']
+    if takes_area2x((ch, cw), (nh, nw), mut):
+        (ya, yb), (xa, xb) = area2x_taps(ch, nh), area2x_taps(cw, nw)
+        ya, yb, xa, xb = ya + top, yb + top, xa + left, xb + left
+        res = (img[ya][:, xa] + img[ya][:, xb] + img[yb][:, xa] + img[yb][:, xb]) * F32(0.25)
+    else:
+        if "image_edge" in mut:
+            x0, x1, fx = _edge_axis(nw, cw, left, img.shape[1])
+            y0, y1, fy = _edge_axis(nh, ch, top, img.shape[0])
+        else:
+            x0, x1, fx, _ = linear_coeffs(nw, cw)
+            y0, y1, fy, _ = linear_coeffs(nh, ch)
+            x0, x1, y0, y1 = x0 + left, x1 + left, y0 + top, y1 + top
+        fx, fy = fx.astype(F32)[None, :, None], fy.astype(F32)[:, None, None]
+        ax, ay = F32(1) - fx, F32(1) - fy
+        res = (img[y0][:, x0] * ax + img[y0][:, x1] * fx) * ay + (img[y1][:, x0] * ax + img[y1][:, x1] * fx) * fy
+    full = np.empty((oh, ow, 3), F32)
+    full[...] = np.asarray(plan['pad_value'], F32)
+    full[pt:pt + nh, pl:pl + nw] = res
+    full = _flip(full, plan)
+    res = (full - np.asarray(plan['mean'], F32)) / np.asarray(plan['std'], F32)
+    assert res.dtype == F32
+    return np.ascontiguousarray(res.transpose(2, 0, 1))
 
 
 def render_seam(image, plan, eps):
