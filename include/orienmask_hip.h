@@ -333,8 +333,8 @@ int om_get_wino14_wide(void);
  * turn them off before the first use): which = 0 the third layer (backbone.conv2.1.conv.0) inside the split-operand
  * first-two-layers kernel, which = 1 the fp16 first-two-layers kernel.  Off -> the separate kernels: bit-identical results for
  * which = 0; for which = 1 conv1's fp32 sums are formed in another order before their one rounding to fp16 (a few per cent of the
- * activations move by one fp16 step: inside the fp16 configuration's tolerance, not bit-identical).  A
- * view the fused launcher cannot take (alignment, pixel stride, descriptor size) runs the separate kernels by itself. */
+ * activations move by one fp16 step: inside the fp16 configuration's tolerance, not bit-identical).  For a
+ * view the fused launcher cannot take (alignment, pixel stride, descriptor size) the forward plans the separate kernels ahead. */
 int om_set_stem_fusion(int which, int on);
 int om_get_stem_fusion(int which);      /* 1 on, 0 off, -1 bad argument */
 /* Which kernel runs the stride-1 3x3 layers of the fp16 configuration (process-wide; the results are the same sums in the same

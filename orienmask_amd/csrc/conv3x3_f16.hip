@@ -16,6 +16,7 @@
 //     is double buffered and requested during the first two taps of the previous patch; counted vmcnt per tap.
 // LDS: 2 x (BM + 64) + 3 x BN rows of 64 B = 64 KiB for the 256x128 tile (2 workgroups/CU), exactly the fp32 C tile of
 // one wave-row for the epilogue (conv_f16_common.h).
+#include <atomic>
 #include <cstdlib>
 
 #include "conv_f16_common.h"
@@ -432,15 +433,12 @@ static int launch_c3_tall(IgemmHParams p, int cout_pad, hipStream_t stream) {
 
 // 0: never the tall-patch form; 1 (default): where conv3x3_tile_for_f16 picks it; 2: wherever it can run.  OM_C3_TALL in the
 // environment, or om_set_conv3x3_f16_variant (A/B runs, tools/conv16_bench.py, the unit tests of both forms).
-static int g_c3_tall = -1;
-static int c3_tall_mode() {
-    if (g_c3_tall < 0) {
-        const char* e = std::getenv("OM_C3_TALL");
-        g_c3_tall = e ? std::atoi(e) : 1;
-    }
-    return g_c3_tall;
+static std::atomic<int>& c3_tall_flag() {      // the environment is read once, by the first call that asks
+    static std::atomic<int> flag{[] { const char* e = std::getenv("OM_C3_TALL"); return e ? std::atoi(e) : 1; }()};
+    return flag;
 }
-void conv3x3_f16_set_tall(int mode) { g_c3_tall = mode; }
+static int c3_tall_mode() { return c3_tall_flag().load(std::memory_order_relaxed); }
+void conv3x3_f16_set_tall(int mode) { c3_tall_flag().store(mode, std::memory_order_relaxed); }
 int conv3x3_f16_get_tall() { return c3_tall_mode(); }
 
 void conv3x3_tile_for_f16(int M, int cout_pad, int W, int kc, int* bm, int* bn) {

@@ -601,17 +601,35 @@ __global__ __launch_bounds__(S2_THREADS, 4) void conv_stem2_f16_kernel(const Ste
     }
 }
 
+// What both launchers ask of shapes, strides and the output view (esz bytes per element, stores of four channels): cout2 == 64, even
+// H and W, the image and one image's output view within a buffer descriptor, the tile count within an int.
+static bool stem2_shape_ok(int B, int H, int W, int cout2, int out_pix_stride, int out_align_bytes, int esz) {
+    if (cout2 != 64 || B <= 0 || H <= 1 || W <= 1 || H % 2 || W % 2) return false;
+    if (out_pix_stride % 4 || out_pix_stride < 64 || out_align_bytes < 4 * esz) return false;
+    if ((long long)(H / 2) * (W / 2) * out_pix_stride * esz >= 0x7FFFFFF0ll || (long long)3 * H * W * 4 >= 0x7FFFFFF0ll) return false;
+    const long long tiles = (long long)B * ((W / 2 + S2_TX - 1) / S2_TX) * ((H / 2 + S2_TY - 1) / S2_TY);
+    return tiles < (1ll << 31);
+}
+
+bool stem2_f16_supported(int B, int H, int W, int cout2, int out_pix_stride, int out_align_bytes) {
+    return stem2_shape_ok(B, H, W, cout2, out_pix_stride, out_align_bytes, 2);
+}
+
+bool stem2_split_supported(int B, int H, int W, int cout2, int out_pix_stride, int out_align_bytes, int cout3, int out3_pix_stride,
+                           int out3_align_bytes) {
+    if (!stem2_shape_ok(B, H, W, cout2, out_pix_stride, out_align_bytes, 4)) return false;
+    if (cout3 == 0) return true;
+    return cout3 == 32 && out3_pix_stride % 4 == 0 && out3_pix_stride >= 32 && out3_align_bytes >= 16 &&
+           (long long)(H / 2) * (W / 2) * out3_pix_stride * 4 < 0x7FFFFFF0ll;
+}
+
 int launch_conv_stem2_f16(const float* in_nchw, int B, int H, int W, const float* w1, const float* scale1, const float* shift1,
                           const void* w2_f16, const float* scale2, const float* shift2, int cout2, int leaky2, void* out_nhwc_f16,
                           int out_pix_stride, hipStream_t stream) {
     OM_REQUIRE(in_nchw && w1 && scale1 && shift1 && w2_f16 && scale2 && shift2 && out_nhwc_f16, OM_EINVAL, "stem2 f16: null pointer");
-    OM_REQUIRE(cout2 == 64, OM_EINVAL, "stem2 f16: cout=%d, only 64 supported", cout2);
-    OM_REQUIRE(B > 0 && H > 1 && W > 1 && H % 2 == 0 && W % 2 == 0, OM_EINVAL, "stem2 f16: bad shape B=%d H=%d W=%d", B, H, W);
-    OM_REQUIRE(out_pix_stride % 4 == 0 && out_pix_stride >= 64 && (reinterpret_cast<uintptr_t>(out_nhwc_f16) & 7) == 0 &&
-                   (reinterpret_cast<uintptr_t>(w2_f16) & 15) == 0,
-               OM_EINVAL, "stem2 f16: output view must be 8-byte, the weights 16-byte aligned");
-    OM_REQUIRE((long long)(H / 2) * (W / 2) * out_pix_stride * 2 < 0x7FFFFFF0ll && (long long)3 * H * W * 4 < 0x7FFFFFF0ll, OM_EINVAL,
-               "stem2 f16: an image of %d x %d exceeds a buffer descriptor", H, W);
+    OM_REQUIRE((reinterpret_cast<uintptr_t>(w2_f16) & 15) == 0, OM_EINVAL, "stem2 f16: the weights must be 16-byte aligned");
+    OM_REQUIRE(stem2_f16_supported(B, H, W, cout2, out_pix_stride, align_bytes(out_nhwc_f16)), OM_EINVAL,
+               "stem2 f16: B=%d H=%d W=%d cout=%d stride=%d: shape, 8-byte view alignment or descriptor size", B, H, W, cout2, out_pix_stride);
     Stem2HParams p;
     p.img = in_nchw; p.w1 = w1; p.sc1 = scale1; p.sh1 = shift1;
     p.w2 = static_cast<const _Float16*>(w2_f16); p.sc2 = scale2; p.sh2 = shift2;
@@ -619,7 +637,6 @@ int launch_conv_stem2_f16(const float* in_nchw, int B, int H, int W, const float
     p.B = B; p.H = H; p.W = W; p.Ho = H / 2; p.Wo = W / 2; p.out_ps = out_pix_stride; p.leaky2 = leaky2;
     p.tiles_x = (p.Wo + S2_TX - 1) / S2_TX; p.tiles_y = (p.Ho + S2_TY - 1) / S2_TY;
     const long long total = (long long)B * p.tiles_x * p.tiles_y;
-    OM_REQUIRE(total < (1ll << 31), OM_EINVAL, "stem2 f16: %lld tiles out of range", total);
     p.total_tiles = (int)total;
     const unsigned grid = (unsigned)(total < 512 ? total : 512);
     hipLaunchKernelGGL(conv_stem2_f16_kernel, dim3(grid), dim3(S2_THREADS), 0, stream, p);
@@ -632,13 +649,9 @@ int launch_conv_stem2_split(const float* in_nchw, int B, int H, int W, const flo
                             const void* w2_split, const float* scale2_split, const float* shift2, int cout2, int leaky2,
                             float* out_nhwc, int out_pix_stride, int* status, hipStream_t stream, const Stem2Third* third) {
     OM_REQUIRE(in_nchw && w1 && scale1 && shift1 && w2_split && scale2_split && shift2 && out_nhwc, OM_EINVAL, "stem2: null pointer");
-    OM_REQUIRE(cout2 == 64, OM_EINVAL, "stem2: cout=%d, only 64 supported", cout2);
-    OM_REQUIRE(B > 0 && H > 1 && W > 1 && H % 2 == 0 && W % 2 == 0, OM_EINVAL, "stem2: bad shape B=%d H=%d W=%d", B, H, W);
-    OM_REQUIRE(out_pix_stride % 4 == 0 && out_pix_stride >= 64 && (reinterpret_cast<uintptr_t>(out_nhwc) & 15) == 0 &&
-                   (reinterpret_cast<uintptr_t>(w2_split) & 15) == 0,
-               OM_EINVAL, "stem2: output view / weights must be 16-byte aligned");
-    OM_REQUIRE((long long)(H / 2) * (W / 2) * out_pix_stride * 4 < 0x7FFFFFF0ll && (long long)3 * H * W * 4 < 0x7FFFFFF0ll, OM_EINVAL,
-               "stem2: an image of %d x %d exceeds a buffer descriptor", H, W);
+    OM_REQUIRE((reinterpret_cast<uintptr_t>(w2_split) & 15) == 0, OM_EINVAL, "stem2: the weights must be 16-byte aligned");
+    OM_REQUIRE(stem2_split_supported(B, H, W, cout2, out_pix_stride, align_bytes(out_nhwc)), OM_EINVAL,
+               "stem2: B=%d H=%d W=%d cout=%d stride=%d: shape, 16-byte view alignment or descriptor size", B, H, W, cout2, out_pix_stride);
     Stem2Params p;
     p.img = in_nchw; p.w1 = w1; p.sc1 = scale1; p.sh1 = shift1;
     p.w2 = static_cast<const _Float16*>(w2_split); p.sc2 = scale2_split; p.sh2 = shift2;
@@ -646,14 +659,12 @@ int launch_conv_stem2_split(const float* in_nchw, int B, int H, int W, const flo
     p.B = B; p.H = H; p.W = W; p.Ho = H / 2; p.Wo = W / 2; p.out_ps = out_pix_stride; p.leaky2 = leaky2;
     p.tiles_x = (p.Wo + S2_TX - 1) / S2_TX; p.tiles_y = (p.Ho + S2_TY - 1) / S2_TY;
     const long long total = (long long)B * p.tiles_x * p.tiles_y;
-    OM_REQUIRE(total < (1ll << 31), OM_EINVAL, "stem2: %lld tiles out of range", total);
     p.total_tiles = (int)total;
     p.w3 = nullptr; p.sc3 = nullptr; p.sh3 = nullptr; p.out3 = nullptr; p.out3_ps = 0; p.leaky3 = 0;
     if (third) {
-        OM_REQUIRE(third->w_split && third->scale_split && third->shift && third->out && third->cout == 32 && third->out_pix_stride % 4 == 0 &&
-                       third->out_pix_stride >= 32 && (reinterpret_cast<uintptr_t>(third->out) & 15) == 0 &&
-                       (reinterpret_cast<uintptr_t>(third->w_split) & 15) == 0 &&
-                       (long long)(H / 2) * (W / 2) * third->out_pix_stride * 4 < 0x7FFFFFF0ll,
+        OM_REQUIRE(third->w_split && third->scale_split && third->shift && third->out && (reinterpret_cast<uintptr_t>(third->w_split) & 15) == 0 &&
+                       stem2_split_supported(B, H, W, cout2, out_pix_stride, align_bytes(out_nhwc), third->cout, third->out_pix_stride,
+                                             align_bytes(third->out)),
                    OM_EINVAL, "stem2: the third layer must be a 64 -> 32 1x1 with a 16-byte aligned output view");
         p.w3 = static_cast<const _Float16*>(third->w_split); p.sc3 = third->scale_split; p.sh3 = third->shift;
         p.out3 = third->out; p.out3_ps = third->out_pix_stride; p.leaky3 = third->leaky;

@@ -722,43 +722,55 @@ void wino14_geometry(int B, int H, int W, int* R, int* Ct, int* ncb, int* nrb) {
 
 size_t wino14_weight_halfs(int cout_pad, int cin) { return (size_t)18 * cout_pad * cin * 2; }
 
+// The sizes of a layer's launch, from its shape, its strides and its views' alignments alone (om_common.h: align_bytes): what
+// wino14_fill_params puts into the kernel's parameters and what wino14_wide_supported asks ahead of any pointer.
+struct Wino14Shape {
+    long long npix, in_bytes, out_bytes, res_bytes, total_tiles;      // a view's bytes: up to the end of its last pixel's channels
+    size_t u_bytes;
+    int R, Ct, ncb, nrb;
+    bool aligned_in;      // the loader's form: 16-byte aligned input view, whole channel quads
+    bool fast_io;         // the epilogue's buffer-descriptor form: 16-byte aligned views below 2 GiB, whole channel quads
+    bool fits() const {   // the input view, the weights and the counters within a buffer descriptor / an int; a block shape exists
+        return aligned_in && in_bytes < 0x7FFFFFF0ll && npix < (1ll << 31) && R >= 1 && Ct >= 1 && total_tiles > 0 &&
+               total_tiles < (1ll << 31) && u_bytes < 0x7FFFFFF0ull;
+    }
+};
+static Wino14Shape wino14_shape(const ConvArgs& a, int in_align_bytes, int out_align_bytes, bool has_res, int res_align_bytes) {
+    Wino14Shape s{};
+    s.npix = (long long)a.B * a.H * a.W;
+    s.in_bytes = (s.npix - 1) * a.in_pix_stride * 4 + (long long)a.cin * 4;
+    s.out_bytes = ((s.npix - 1) * a.out_pix_stride + a.cout) * 4;
+    s.res_bytes = has_res ? ((s.npix - 1) * a.res_pix_stride + a.cout) * 4 : 0;
+    s.aligned_in = a.in_pix_stride % 4 == 0 && in_align_bytes >= 16;
+    s.fast_io = a.cout % 4 == 0 && a.out_pix_stride % 4 == 0 && out_align_bytes >= 16 &&
+                (!has_res || (a.res_pix_stride % 4 == 0 && res_align_bytes >= 16)) && s.out_bytes < 0x7FFFFFF0ll && s.res_bytes < 0x7FFFFFF0ll;
+    wino14_geometry(a.B, a.H, a.W, &s.R, &s.Ct, &s.ncb, &s.nrb);
+    s.total_tiles = (long long)s.nrb * s.ncb * (a.cout_pad / W14_BN);
+    s.u_bytes = wino14_weight_halfs(a.cout_pad, a.cin) * 2;
+    return s;
+}
+static bool wino14_layer_kind_ok(const ConvArgs& a) { return a.ks == 3 && a.stride == 1 && a.out_mode == 0 && a.cin % 16 == 0 && a.cin >= 16 && a.cout_pad % 64 == 0; }
+
 // the fused kernel's parameters from a layer's arguments (shared by the two-kernel wide form)
 static int wino14_fill_params(const ConvArgs& a, Wino14Params& p) {
     OM_REQUIRE(a.in && a.w && a.scale && a.shift && a.out && a.ticket, OM_EINVAL, "wino14: null pointer");
-    OM_REQUIRE(a.ks == 3 && a.stride == 1 && a.out_mode == 0, OM_EINVAL, "wino14: 3x3 stride-1 NHWC layers only");
-    OM_REQUIRE(a.cin % 16 == 0 && a.cin >= 16 && a.cout_pad % 64 == 0, OM_EINVAL, "wino14: cin=%d cout_pad=%d", a.cin, a.cout_pad);
-    OM_REQUIRE(a.in_pix_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(a.in) & 15) == 0 &&
-                   (reinterpret_cast<uintptr_t>(a.w) & 15) == 0,
-               OM_EINVAL, "wino14: operands must be 16-byte aligned");
-    const long long in_bytes = ((long long)a.B * a.H * a.W - 1) * a.in_pix_stride * 4 + (long long)a.cin * 4;
-    OM_REQUIRE(in_bytes < 0x7FFFFFF0ll, OM_EINVAL, "wino14: input view of %lld bytes exceeds a buffer descriptor", in_bytes);
+    OM_REQUIRE(wino14_layer_kind_ok(a), OM_EINVAL, "wino14: 3x3 stride-1 NHWC layers only, cin=%d cout_pad=%d", a.cin, a.cout_pad);
+    OM_REQUIRE((reinterpret_cast<uintptr_t>(a.w) & 15) == 0, OM_EINVAL, "wino14: the weights must be 16-byte aligned");
+    const Wino14Shape s = wino14_shape(a, align_bytes(a.in), align_bytes(a.out), a.res != nullptr, align_bytes(a.res));
+    OM_REQUIRE(s.fits(), OM_EINVAL, "wino14: %d x %d x %d: input view (%lld bytes) not 16-byte aligned, or it, the weights, %lld pixels or "
+               "%lld tiles (block %d x %d) out of range", a.B, a.H, a.W, s.in_bytes, s.npix, s.total_tiles, s.R, s.Ct);
     p.in = a.in; p.u = reinterpret_cast<const _Float16*>(a.w); p.scale = a.scale; p.shift = a.shift; p.res = a.res; p.out = a.out;
     p.ticket = a.ticket; p.status = a.status;
-    p.B = a.B; p.H = a.H; p.W = a.W; p.in_ps = a.in_pix_stride; p.in_bytes = (int)in_bytes;
+    p.B = a.B; p.H = a.H; p.W = a.W; p.in_ps = a.in_pix_stride; p.in_bytes = (int)s.in_bytes;
     p.cout = a.cout; p.out_ps = a.out_pix_stride; p.res_ps = a.res_pix_stride; p.leaky = a.leaky;
-    // the epilogue's buffer-descriptor form: 16-byte aligned views below 2 GiB, whole channel quads
-    const long long npix = (long long)a.B * a.H * a.W;
-    const long long out_bytes = ((npix - 1) * a.out_pix_stride + a.cout) * 4;
-    const long long res_bytes = a.res ? ((npix - 1) * a.res_pix_stride + a.cout) * 4 : 0;
-    p.fast_io = (a.cout % 4 == 0 && a.out_pix_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(a.out) & 15) == 0 &&
-                 (!a.res || (a.res_pix_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(a.res) & 15) == 0)) &&
-                 out_bytes < 0x7FFFFFF0ll && res_bytes < 0x7FFFFFF0ll)
-                    ? 1 : 0;
-    p.out_bytes = p.fast_io ? (int)out_bytes : 0;
-    p.res_bytes = p.fast_io ? (int)res_bytes : 0;
-    OM_REQUIRE(npix < (1ll << 31), OM_EINVAL, "wino14: %lld pixels out of range", npix);
-    int R = 0, Ct = 0, ncb = 0, nrb = 0;
-    wino14_geometry(a.B, a.H, a.W, &R, &Ct, &ncb, &nrb);
-    OM_REQUIRE(R >= 1 && Ct >= 1, OM_EINVAL, "wino14: no block shape for %d x %d", a.H, a.W);
-    p.R = R; p.Ct = Ct; p.ncb = ncb; p.gtot = a.B * (a.H + 2);
+    p.fast_io = s.fast_io ? 1 : 0;
+    p.out_bytes = s.fast_io ? (int)s.out_bytes : 0;
+    p.res_bytes = s.fast_io ? (int)s.res_bytes : 0;
+    p.R = s.R; p.Ct = s.Ct; p.ncb = s.ncb; p.gtot = a.B * (a.H + 2);
     p.n_tiles = a.cout_pad / W14_BN;
     p.nch = a.cin / 16;
-    const long long total = (long long)nrb * ncb * p.n_tiles;
-    OM_REQUIRE(total > 0 && total < (1ll << 31), OM_EINVAL, "wino14: %lld tiles out of range", total);
-    p.total_tiles = (int)total;
-    const size_t ub = wino14_weight_halfs(a.cout_pad, a.cin) * 2;
-    OM_REQUIRE(ub < 0x7FFFFFF0ull, OM_EINVAL, "wino14: weights exceed a buffer descriptor");
-    p.u_bytes = (int)ub;
+    p.total_tiles = (int)s.total_tiles;
+    p.u_bytes = (int)s.u_bytes;
     return OM_OK;
 }
 
@@ -781,25 +793,20 @@ size_t wino14_wide_scratch_floats(int B, int H, int W, int cin) {
     return (size_t)(cin / 16) * 6 * B * (H + 2) * ((W + 3) / 4) * 16;
 }
 
-// can this layer run it?  Whole pairs of 64-channel N tiles, the epilogue's buffer-descriptor form, V below 2 GiB.
-bool wino14_wide_supported(const ConvArgs& a) {
-    if (a.ks != 3 || a.stride != 1 || a.out_mode != 0 || a.cin % 16 || a.cout_pad % 128 || a.cout % 4 || a.out_pix_stride % 4) return false;
-    if ((reinterpret_cast<uintptr_t>(a.out) & 15) || (a.res && ((a.res_pix_stride % 4) || (reinterpret_cast<uintptr_t>(a.res) & 15)))) return false;
-    return wino14_wide_scratch_floats(a.B, a.H, a.W, a.cin) * 4 < 0x7FFFFFF0ull;
+// can this layer run it?  Everything launch_conv_wino14_wide asks beyond non-null pointers and its own blobs' alignment: whole pairs of
+// 64-channel N tiles, the epilogue's buffer-descriptor form, every view and V below 2 GiB.
+bool wino14_wide_supported(const ConvArgs& a, int in_align_bytes, int out_align_bytes, bool has_res, int res_align_bytes) {
+    if (!wino14_layer_kind_ok(a) || a.cout_pad % 128) return false;
+    const Wino14Shape s = wino14_shape(a, in_align_bytes, out_align_bytes, has_res, res_align_bytes);
+    return s.fits() && s.fast_io && wino14_wide_scratch_floats(a.B, a.H, a.W, a.cin) * 4 < 0x7FFFFFF0ull;
 }
-
-// which layers take it (om_forward's choice; the unit entry om_conv2d_wino14_wide runs it on any supported layer): the pre-pass moves
-// 2.5 x the layer's input through HBM, the wide tile saves 13-20 % of the fused kernel's time -- it pays where the input is small next
-// to the layer's work, i.e. from 512 input channels on (the 512 -> 1024 layers at 1/32 scale: 47 MB of pre-pass traffic for 87 GFLOP;
-// profiles/r06_experiments.md section 1)
-bool wino14_wide_pays(const ConvArgs& a) { return a.cin >= 512 && wino14_wide_supported(a); }
 
 int launch_conv_wino14_wide(const ConvArgs& a, float* scratch, hipStream_t stream) {
     OM_REQUIRE(scratch && (reinterpret_cast<uintptr_t>(scratch) & 15) == 0, OM_EINVAL, "wino14 wide: scratch must be 16-byte aligned");
-    OM_REQUIRE(wino14_wide_supported(a), OM_EINVAL, "wino14 wide: cout_pad=%d must be a multiple of 128 and the views 16-byte aligned", a.cout_pad);
+    OM_REQUIRE(wino14_wide_supported(a, align_bytes(a.in), align_bytes(a.out), a.res != nullptr, align_bytes(a.res)), OM_EINVAL,
+               "wino14 wide: cout_pad=%d must be a multiple of 128, the views 16-byte aligned and, like V, below 2 GiB", a.cout_pad);
     Wino14WideParams pw;
     if (int rc = wino14_fill_params(a, pw.k)) return rc;
-    OM_REQUIRE(pw.k.fast_io && pw.k.n_tiles % 2 == 0, OM_EINVAL, "wino14 wide: views not in the epilogue's buffer-descriptor form");
     const int TW = (a.W + 3) / 4;
     pw.TW = TW;
     pw.v = reinterpret_cast<const _Float16*>(scratch);

@@ -30,6 +30,10 @@ void set_error(const char* fmt, ...);
 
 static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// Byte alignment of an address, as far as 256: what the *_supported predicates below take in place of a pointer.  A launcher passes
+// its pointer; om_model::plan(), which has none yet, the view's byte offset in its 256-byte aligned buffer.
+static inline int align_bytes(uintptr_t addr) { return (int)((addr | 256) & (~(addr | 256) + 1)); }
+static inline int align_bytes(const void* p) { return align_bytes(reinterpret_cast<uintptr_t>(p)); }
 
 // One fused convolution launch.  Pointers already include any channel offset of a view
 // into a wider (concatenated) buffer; *_pix_stride is the float distance between pixels.
@@ -124,11 +128,13 @@ int launch_conv_wino14_split(const ConvArgs& a, hipStream_t stream);
 // the same layer as two kernels with a 128 x 128 tile (conv_wino14.hip, round 6): V = the transformed input, written by a pre-pass into
 // `scratch` (wino14_wide_scratch_floats floats), read by LDS-DMA; bit-identical to the fused kernel
 size_t wino14_wide_scratch_floats(int B, int H, int W, int cin);
-bool wino14_wide_supported(const ConvArgs& a);
-bool wino14_wide_pays(const ConvArgs& a);
+// can this layer run it?  Reads a's shape, stride and mode fields, never a pointer: the views' alignments come as numbers
+// (align_bytes), and has_res says whether there is a residual.  What it accepts, launch_conv_wino14_wide accepts.
+bool wino14_wide_supported(const ConvArgs& a, int in_align_bytes, int out_align_bytes, bool has_res, int res_align_bytes);
 int launch_conv_wino14_wide(const ConvArgs& a, float* scratch, hipStream_t stream);
-// backbone.conv1 + backbone.conv2.0 as one kernel with split operands (conv_stem2.hip): image NCHW -> conv2.0's NHWC output
-// conv1 + conv2.0 of the fp16-activation configuration as one kernel (conv_stem2.hip: conv_stem2_f16_kernel)
+// conv1 + conv2.0 of the fp16-activation configuration as one kernel (conv_stem2.hip: conv_stem2_f16_kernel).  *_supported: every
+// condition of the launcher on shapes, strides and view alignments, as numbers: om_model::plan() asks, the launcher requires it
+bool stem2_f16_supported(int B, int H, int W, int cout2, int out_pix_stride, int out_align_bytes);
 int launch_conv_stem2_f16(const float* in_nchw, int B, int H, int W, const float* w1, const float* scale1, const float* shift1,
                           const void* w2_f16, const float* scale2, const float* shift2, int cout2, int leaky2, void* out_nhwc_f16,
                           int out_pix_stride, hipStream_t stream);
@@ -140,13 +146,16 @@ struct Stem2Third {
     float* out;                 // NHWC [B, H/2, W/2, out_pix_stride]
     int cout, leaky, out_pix_stride;
 };
+// backbone.conv1 + backbone.conv2.0 as one kernel with split operands (conv_stem2.hip): image NCHW -> conv2.0's NHWC output
+bool stem2_split_supported(int B, int H, int W, int cout2, int out_pix_stride, int out_align_bytes, int cout3 = 0,
+                           int out3_pix_stride = 0, int out3_align_bytes = 0);      // cout3 = 0: without the third layer
 int launch_conv_stem2_split(const float* in_nchw, int B, int H, int W, const float* w1, const float* scale1, const float* shift1,
                             const void* w2_split, const float* scale2_split, const float* shift2, int cout2, int leaky2,
                             float* out_nhwc, int out_pix_stride, int* status, hipStream_t stream, const Stem2Third* third = nullptr);
 size_t wino14_weight_halfs(int cout_pad, int cin);
 void wino14_geometry(int B, int H, int W, int* R, int* Ct, int* ncb, int* nrb);
 bool wino_enabled();
-int wino_bn(long long T, int cout_pad);   // N tile of the (unfused) Winograd GEMM at this size
+int wino_bn(long long T, int cout_pad);   // N tile of the Winograd GEMM behind a transform kernel of its own, at this size
 bool wino_fused_for(int cin);     // true: the input transform is fused into the GEMM's loader   // tile shape launch_conv_igemm picks
 // Clears n 32-bit words with a kernel.  The library never uses hipMemsetAsync: a memset node captured
 // into a hipGraph was observed (ROCm 7.2, DESIGN.md "hipGraph") to leave part of the range uncleared on replay.

@@ -15,6 +15,7 @@
 //     wants), the orientation head NCHW (what the mask kernel wants);
 //   * no allocation, no synchronisation: ~90 launches on the caller's stream.
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -117,25 +118,22 @@ static void fill_conv_shape(Args& a, int B, int H, int W, int cin, int in_pix_st
 
 }  // namespace om
 
-// Process-wide A/B switches, default on; each is off while its environment variable (read once) is 1, or by its setter:
+// Process-wide A/B switches, default on; each is off while its environment variable (read once, by the first call that asks) is 1, or
+// by its setter.  Atomics: forwards may be enqueued from several threads (the threading contract below).
 //   SW_STEM3 / SW_STEM2_F16 (om_set_stem_fusion 0 / 1): the third layer inside the split-operand stem kernel / the fp16
 //     first-two-layers kernel (om_model::first_layers_fusable);
 //   SW_W14_WIDE (om_set_wino14_wide): om_forward runs the stride-1 3x3 layers with at least 512 input channels of precision mode 1 in
 //     the two-kernel wide form (conv_wino14.hip: wino14_v_kernel + wino14_wide_kernel); off: the fused kernel everywhere.  Bit-identical.
 enum : int { SW_STEM3 = 0, SW_STEM2_F16 = 1, SW_W14_WIDE = 2 };
-static int& switch_flag(int which) {
-    static int flags[3] = {-1, -1, -1};
+static int switch_default(const char* env) {
+    const char* e = std::getenv(env);
+    return (e && e[0] == '1') ? 0 : 1;
+}
+static std::atomic<int>& switch_flag(int which) {
+    static std::atomic<int> flags[3] = {{switch_default("OM_NO_STEM3")}, {switch_default("OM_NO_STEM2_F16")}, {switch_default("OM_NO_W14_WIDE")}};
     return flags[which];
 }
-static bool switch_on(int which) {
-    static const char* const env[3] = {"OM_NO_STEM3", "OM_NO_STEM2_F16", "OM_NO_W14_WIDE"};
-    int& f = switch_flag(which);
-    if (f < 0) {
-        const char* e = std::getenv(env[which]);
-        f = (e && e[0] == '1') ? 0 : 1;
-    }
-    return f != 0;
-}
+static bool switch_on(int which) { return switch_flag(which).load(std::memory_order_relaxed) != 0; }
 
 struct om_model {
     int num_anchors = 0, num_classes = 0;
@@ -437,24 +435,31 @@ struct om_model {
         return OM_OK;
     }
 
-    // plan()'s helper: how many layers behind the stem CAN run inside its kernel, by their shapes and the switches above.
+    // How aligned a view of a workspace buffer is: layout() places every buffer 256-byte aligned, so a view is as aligned as its
+    // channel offset.  (A caller's tensor -- a head -- is not known to be: plan() keeps the forms that ask away from those.)
+    static int view_align_bytes(const om::View& v, bool f16) { return om::align_bytes((uintptr_t)v.ch_off * (f16 ? 2 : 4)); }
+
+    // plan()'s helper: how many layers behind the stem run inside its kernel at this batch and size, by the graph, the switches above
+    // and the launchers' own predicates (conv_stem2.hip: stem2_f16_supported / stem2_split_supported).
     // One: conv1 and conv2.0 as one kernel (conv_stem2.hip: conv_stem2_split_kernel / conv_stem2_f16_kernel, round 5) when the second
     // is the 32 -> 64 3x3 stride-2 layer reading the first one's output, so that conv1's activation never reaches memory.
     // Two (split operands only): the 64 -> 32 1x1 convolution behind them (backbone.conv2.1.conv.0) inside the same kernel too.
-    int first_layers_fusable(bool f16) const {
+    int first_layers_fusable(bool f16, int B, int H, int W) const {
         if (layers.size() < 2 || !layers[0].stem || (f16 && !switch_on(SW_STEM2_F16))) return 0;
         const om::LayerDef& a = layers[0];
         const om::LayerDef& b = layers[1];
-        if (!(a.info.cout == 32 && b.info.cin == 32 && b.info.cout == 64 && b.info.cout_pad == 64 && b.info.ksize == 3 &&
-              b.info.stride == 2 && !b.has_res && b.out_mode == 0 && b.in.buf == a.out.buf && b.in.ch_off == a.out.ch_off))
+        if (!(a.info.cout == 32 && b.info.cin == 32 && b.info.ksize == 3 && b.info.stride == 2 && !b.has_res && b.out_mode == 0 &&
+              b.in.buf == a.out.buf && b.in.ch_off == a.out.ch_off && b.out.buf >= 0))
             return 0;
-        if (f16) return b.info.w16_off >= 0 && b.out.buf >= 0 ? 1 : 0;
-        if (b.info.wsplit_off < 0 || b.info.wino_planes != 0) return 0;
+        const int b_stride = pix_stride(b.out.buf), b_align = view_align_bytes(b.out, f16);
+        if (f16) return b.info.w16_off >= 0 && om::stem2_f16_supported(B, H, W, b.info.cout, b_stride, b_align) ? 1 : 0;
+        if (b.info.wsplit_off < 0 || b.info.wino_planes != 0 || !om::stem2_split_supported(B, H, W, b.info.cout, b_stride, b_align)) return 0;
         if (!switch_on(SW_STEM3) || layers.size() < 3) return 1;
         const om::LayerDef& c = layers[2];
-        return c.info.cin == 64 && c.info.cout == 32 && c.info.cout_pad == 32 && c.info.ksize == 1 && c.info.stride == 1 && !c.has_res &&
-                       c.out_mode == 0 && c.in.buf == b.out.buf && c.in.ch_off == b.out.ch_off && c.info.wsplit_off >= 0 && c.out.buf >= 0 &&
-                       c.gather.empty() && c.side < 0
+        return c.info.cin == 64 && c.info.ksize == 1 && c.info.stride == 1 && !c.has_res && c.out_mode == 0 && c.in.buf == b.out.buf &&
+                       c.in.ch_off == b.out.ch_off && c.info.wsplit_off >= 0 && c.out.buf >= 0 && c.gather.empty() && c.side < 0 &&
+                       om::stem2_split_supported(B, H, W, b.info.cout, b_stride, b_align, c.info.cout, pix_stride(c.out.buf),
+                                                 view_align_bytes(c.out, false))
                    ? 2 : 1;
     }
 
@@ -470,16 +475,16 @@ struct om_model {
     // THE chooser: which kernel runs layer `index` of a forward at this batch, size and precision, and what that kernel needs.
     // om_layer_tile / om_layer_tile_f16 report it, layout() reserves its scratch and its side buffers, launch_layer launches it:
     // nothing else decides.  Reads the A/B switches (om_set_wino14_wide, om_set_stem_fusion, om_model_set_upsample_on_read; the
-    // variant of a single kernel -- om_set_conv3x3_f16_variant -- sits behind its file's own tile function).
-    // `unfused`: the first layers each as a kernel of its own (launch_first_layers' fallback).
-    om::LayerPlan plan(int index, int B, int H, int W, bool f16, bool unfused = false) const {
+    // variant of a single kernel -- om_set_conv3x3_f16_variant -- sits behind its file's own tile function).  Whether a form CAN run
+    // here is asked of the predicate beside its launcher, on numbers; a launch that fails all the same is an error of the forward.
+    om::LayerPlan plan(int index, int B, int H, int W, bool f16) const {
         using om::Form;
         const om::LayerDef& L = layers[index];
         const om_layer_info& li = L.info;
         om::LayerPlan p;
         p.w_off = li.w_off; p.scale_off = li.scale_off;
         const bool split = !f16 && precision == 1;
-        const int fused = (f16 || split) && !keep_all && !unfused ? first_layers_fusable(f16) : 0;
+        const int fused = (f16 || split) && !keep_all ? first_layers_fusable(f16, B, H, W) : 0;
         if (L.stem) {
             if (index == 0 && fused) { p.form = f16 ? Form::Stem2F16 : fused == 2 ? Form::Stem3Split : Form::Stem2Split; p.bm = 128; p.bn = 64; }
             return p;
@@ -531,15 +536,13 @@ struct om_model {
             // pre-pass's 2.5 x the input through HBM is small next to the layer's work), and only where the fused kernel's tiles
             // outnumber the CUs: while ONE round of them covers the layer, a round of half as many 128 x 128 tiles takes longer
             // (17^2 512 -> 1024: 0.14 against 0.21 ms per round; at bs = 32 the fused kernel needs 1.56 rounds = 0.26-0.28 ms, the
-            // wide form one round + the pre-pass = 0.22-0.23 ms).  Its launcher's own conditions are asked here, on stand-in
-            // pointers: layout() places every buffer 256-byte aligned, so a view is as aligned as its channel offset; a caller's
-            // tensor (a head) is not known to be.
-            if (switch_on(SW_W14_WIDE) && li.cin >= 512 && tiles > 256 && L.out.buf >= 0 && (!L.has_res || L.res.buf >= 0)) {
+            // wide form one round + the pre-pass = 0.22-0.23 ms).  Its launcher's own conditions are asked here; a caller's tensor
+            // (a head) has no known alignment.
+            if (switch_on(SW_W14_WIDE) && li.cin >= 512 && tiles > 256 && L.in.buf >= 0 && L.out.buf >= 0 && (!L.has_res || L.res.buf >= 0)) {
                 om::ConvArgs a{};
                 layer_shape(a, L, p, B, H, W);
-                a.out = reinterpret_cast<float*>((uintptr_t)256 + (size_t)L.out.ch_off * sizeof(float));
-                a.res = L.has_res ? reinterpret_cast<const float*>((uintptr_t)256 + (size_t)L.res.ch_off * sizeof(float)) : nullptr;
-                if (om::wino14_wide_supported(a)) {
+                if (om::wino14_wide_supported(a, view_align_bytes(L.in, false), view_align_bytes(L.out, false), L.has_res,
+                                              L.has_res ? view_align_bytes(L.res, false) : 0)) {
                     p.form = Form::Wino14Wide; p.bn = 128;
                     p.scratch_floats = om::wino14_wide_scratch_floats(B, Hin, Win, li.cin);
                 }
@@ -648,12 +651,11 @@ struct om_model {
 
 namespace {
 
-// A failed launch's message, with the layer(s) it belongs to in front
-int fail_in(int rc, const char* what, const char* name, const char* name2 = nullptr) {
+// A failed launch's message, with the layer it belongs to in front
+int fail_in(int rc, const char* what, const char* name) {
     char msg[512];
     std::snprintf(msg, sizeof(msg), "%s", om::g_err);
-    if (name2) om::set_error("%s %s + %s: %s", what, name, name2, msg);
-    else om::set_error("%s %s: %s", what, name, msg);
+    om::set_error("%s %s: %s", what, name, msg);
     return rc;
 }
 
@@ -754,6 +756,8 @@ struct ForwardRun {
     int launch_layer(int index, const om::LayerPlan& p, const LayerEvents& ev) const {
         using om::Form;
         const om::LayerDef& L = m->layers[index];
+        if (p.form == Form::InPrevious) return ev.mid();      // it ran inside the first layers' kernel: its events bracket nothing
+        if (p.form == Form::Stem2Split || p.form == Form::Stem3Split || p.form == Form::Stem2F16) return launch_first_layers(p, ev);
         if (p.form == Form::Stem) {
             if (int rc = ev.mid()) return rc;
             const float* shift = m->weights + L.info.shift_off;
@@ -790,44 +794,28 @@ struct ForwardRun {
         return OM_ESTATE;
     }
 
-    // The first layers as one kernel (plan forms Stem2Split / Stem3Split / Stem2F16); *consumed = how many layers behind the stem
-    // ran inside it.  THE ONLY LAUNCH-TIME FALLBACK of the forward: plan() looks at layer shapes and views, the launchers also have
-    // preconditions on the caller's image pointer.  What they refuse (OM_EINVAL) takes the path that was the only one before the
-    // fusion existed -- first without the third layer, then (*consumed = 0) the separate kernels, which the caller plans `unfused`.
-    int launch_first_layers(const om::LayerPlan& p, const LayerEvents& ev, int* consumed) const {
+    // The first layers as one kernel (plan forms Stem2Split / Stem3Split / Stem2F16).  plan() chose the form with the launchers' own
+    // predicates (first_layers_fusable), and the layers planned InPrevious launch nothing: what a launcher refuses here is an error.
+    int launch_first_layers(const om::LayerPlan& p, const LayerEvents& ev) const {
         const om::LayerDef& S = m->layers[0];
         const om::LayerDef& N = m->layers[1];
         const float *w = m->weights + p.w_off, *scale = scale_of(p), *shift = m->weights + S.info.shift_off;
         const float* n_shift = m->weights + N.info.shift_off;
         const int n_stride = m->pix_stride(N.out.buf);
-        *consumed = 0;
         if (int rc = ev.mid()) return rc;
-        int rc;
-        if (p.form == om::Form::Stem2F16) {
-            rc = om::launch_conv_stem2_f16(x, B, H, W, w, scale, shift, m->weights16 + N.info.w16_off, m->weights + N.info.scale_off, n_shift,
-                                           N.info.cout, N.info.leaky, ptr_of(N.out), n_stride, stream);
-            if (rc == OM_OK) *consumed = 1;
-        } else {
-            const float *n_w = m->weights_split + N.info.wsplit_off, *n_scale = m->weights_split + N.info.wsplit_scale_off;
-            float* n_out = static_cast<float*>(ptr_of(N.out));
-            rc = OM_EINVAL;
-            if (p.form == om::Form::Stem3Split) {
-                const om::LayerDef& T = m->layers[2];
-                const om::Stem2Third third{m->weights_split + T.info.wsplit_off, m->weights_split + T.info.wsplit_scale_off,
-                                           m->weights + T.info.shift_off, static_cast<float*>(ptr_of(T.out)), T.info.cout, T.info.leaky,
-                                           m->pix_stride(T.out.buf)};
-                rc = om::launch_conv_stem2_split(x, B, H, W, w, scale, shift, n_w, n_scale, n_shift, N.info.cout, N.info.leaky, n_out, n_stride,
-                                                 status, stream, &third);
-                if (rc == OM_OK) *consumed = 2;
-            }
-            if (rc == OM_EINVAL) {
-                rc = om::launch_conv_stem2_split(x, B, H, W, w, scale, shift, n_w, n_scale, n_shift, N.info.cout, N.info.leaky, n_out, n_stride,
-                                                 status, stream, nullptr);
-                if (rc == OM_OK) *consumed = 1;
-            }
+        if (p.form == om::Form::Stem2F16)
+            return om::launch_conv_stem2_f16(x, B, H, W, w, scale, shift, m->weights16 + N.info.w16_off, m->weights + N.info.scale_off, n_shift,
+                                             N.info.cout, N.info.leaky, ptr_of(N.out), n_stride, stream);
+        om::Stem2Third third{};
+        if (p.form == om::Form::Stem3Split) {
+            const om::LayerDef& T = m->layers[2];
+            third = {m->weights_split + T.info.wsplit_off, m->weights_split + T.info.wsplit_scale_off, m->weights + T.info.shift_off,
+                     static_cast<float*>(ptr_of(T.out)), T.info.cout, T.info.leaky, m->pix_stride(T.out.buf)};
         }
-        if (rc == OM_OK || rc == OM_EINVAL) return OM_OK;
-        return fail_in(rc, "layers", S.info.name, N.info.name);
+        return om::launch_conv_stem2_split(x, B, H, W, w, scale, shift, m->weights_split + N.info.wsplit_off,
+                                           m->weights_split + N.info.wsplit_scale_off, n_shift, N.info.cout, N.info.leaky,
+                                           static_cast<float*>(ptr_of(N.out)), n_stride, status, stream,
+                                           p.form == om::Form::Stem3Split ? &third : nullptr);
     }
 };
 
@@ -968,24 +956,10 @@ static int forward_impl(om_model* m, const float* x, int B, int H, int W, float*
                          f16 ? nullptr : reinterpret_cast<float*>(ws + lay.partial_off), tickets + (size_t)nl * om::SYNC_WORDS};
     if (int rc = om::launch_zero_words(tickets, (size_t)nl * om::SYNC_WORDS + om::STATUS_WORDS, main_stream)) return rc;
 
-    int in_previous = 0;      // layers ahead that ran inside the first layers' kernel: nothing to launch (their events bracket nothing)
     for (int l = 0; l < nl; ++l) {
         LayerEvents ev;
         if (int rc = ev.begin(m, l, main_stream)) return rc;
-        if (in_previous > 0) {
-            --in_previous;
-            if (int rc = ev.mid()) return rc;
-            continue;
-        }
-        om::LayerPlan p = lay.plans[l];
-        const bool first_layers = p.form == om::Form::Stem2Split || p.form == om::Form::Stem3Split || p.form == om::Form::Stem2F16;
-        if (first_layers) {
-            if (int rc = run.launch_first_layers(p, ev, &in_previous)) return rc;
-            if (in_previous > 0) continue;
-        }
-        // a fused form left here was refused by launch_first_layers, whole or in part: this layer runs as a kernel of its own
-        if (first_layers || p.form == om::Form::InPrevious) p = m->plan(l, B, H, W, f16, true);
-        if (int rc = run.launch_layer(l, p, ev)) return fail_in(rc, "layer", m->layers[l].info.name);
+        if (int rc = run.launch_layer(l, lay.plans[l], ev)) return fail_in(rc, "layer", m->layers[l].info.name);
         if (early && l == m->head_last) {
             // the box heads are complete in the caller's stream: decode + select beside the rest of the forward
             OM_CHECK_HIP(hipEventRecord(sd.ev_fork, main_stream));
@@ -1340,7 +1314,7 @@ int om_conv2d_wino14_wide(const float* in, int B, int H, int W, int cin, int in_
 
 int om_set_wino14_wide(int on) {
     OM_REQUIRE(on == 0 || on == 1, OM_EINVAL, "om_set_wino14_wide: %d", on);
-    switch_flag(SW_W14_WIDE) = on;
+    switch_flag(SW_W14_WIDE).store(on, std::memory_order_relaxed);
     return OM_OK;
 }
 int om_get_wino14_wide(void) { return switch_on(SW_W14_WIDE) ? 1 : 0; }
@@ -1363,7 +1337,7 @@ int om_conv2d_stem2_f16(const float* in, int B, int H, int W, const float* w1, c
 
 int om_set_stem_fusion(int which, int on) {
     OM_REQUIRE((which == 0 || which == 1) && (on == 0 || on == 1), OM_EINVAL, "om_set_stem_fusion: which=%d on=%d", which, on);
-    switch_flag(which) = on;
+    switch_flag(which).store(on, std::memory_order_relaxed);
     return OM_OK;
 }
 

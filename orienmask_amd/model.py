@@ -156,7 +156,7 @@ class OrienMaskYOLOFPNPlus(nn.Module):
         self.n_streams = 1           # set_streams(): sub-batches on side HIP streams
         self._side_streams = {}
         self._packed_device = None
-        self._workspace = {}         # (device, B, H, W) -> uint8 tensor (workspace slot 0)
+        self._workspace = {}         # _forward's key (device, B, H, W, ...) -> uint8 tensor (workspace slot 0)
         self._slot = 0               # workspace_slot(): which workspace forward() uses
         self._slot_workspaces = {}   # slot > 0 -> {key: uint8 tensor}
         if pretrained is not None:
@@ -357,14 +357,16 @@ class OrienMaskYOLOFPNPlus(nn.Module):
         # them on the caller's stream; images are independent, so the results are bit-identical to one launch
         n_sub = self.n_streams if (self.n_streams > 1 and B % self.n_streams == 0) else 1
         Bs = B // n_sub
-        key = (dev, Bs, H, W, f16, n_sub, split)
+        # the process-wide switches that change the layout (the wide 3x3 form's scratch, which first layers have a buffer to write)
+        switches = (L.om_get_wino14_wide(), L.om_get_stem_fusion(0), L.om_get_stem_fusion(1))
+        key = (dev, Bs, H, W, f16, n_sub, switches, split)
         cache = self._workspace if slot == 0 else self._slot_workspaces.setdefault(slot, {})
         ws = cache.get(key)
         if ws is None:
             nbytes = (L.om_forward_f16_workspace_bytes if f16 else L.om_forward_workspace_bytes)(h, Bs, H, W)
             nbytes = (nbytes + 255) // 256 * 256
-            for k in [k for k in cache if k[:6] != key[:6]]:      # another shape: drop; the fp32-operand re-run of a split
-                del cache[k]                                      # forward keeps its workspace next to the split one
+            for k in [k for k in cache if k[:7] != key[:7]]:      # another shape or layout: drop; the fp32-operand re-run of a
+                del cache[k]                                      # split forward keeps its workspace next to the split one
             ws = torch.empty(nbytes * n_sub, dtype=torch.uint8, device=dev)
             cache[key] = ws
         ws_each = ws.numel() // n_sub

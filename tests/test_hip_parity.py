@@ -806,7 +806,7 @@ def test_wino14_wide_equals_fused(dev, case):
 
 def test_forward_wide_3x3_switch_is_bit_identical(dev):
     """om_forward runs the stride-1 3x3 layers with at least 512 input channels (the 1/32-scale ones) in the two-kernel wide form
-    (om_set_wino14_wide, default on): the layer table says so, the workspace grows by their transformed input, and all six head
+    (om_set_wino14_wide, default on): the layer table says so, the workspace is laid out anew for their transformed input, and all six head
     tensors are bit-identical to a forward with the switch off; the previous setting is restored."""
     L = omlib.load()
     sd = synth.synth_state_dict(13, obj_bias=-16.0, head_gain=4.0)
@@ -816,6 +816,14 @@ def test_forward_wide_3x3_switch_is_bit_identical(dev):
     net = _hip_model(sd, dev, "f32_split")
     was = L.om_get_wino14_wide()
     try:
+        # off first: the net's first workspace is laid out WITHOUT the V scratch, and the forward with the switch on must get one of
+        # its own (the workspace cache tells the layouts apart; nothing here clears it): where the scratch does not fall into a gap
+        # of the live-range layout, the old workspace is too small (OM_ENOMEM)
+        omlib.check(L.om_set_wino14_wide(0), "om_set_wino14_wide")
+        k_off = dict(net.layer_kernels(140, 32, 544))
+        with torch.no_grad():
+            off = [(b.clone(), o.clone()) for b, o in net(x)]
+        keys_off = set(net._workspace)
         omlib.check(L.om_set_wino14_wide(1), "om_set_wino14_wide")
         assert not any(v.startswith("wino14_wide_kernel") for _, v in net.layer_kernels(3, 32, 544))
         k_on = dict(net.layer_kernels(140, 32, 544))
@@ -823,16 +831,16 @@ def test_forward_wide_3x3_switch_is_bit_identical(dev):
             pred = net(x)
             on = [(b.clone(), o.clone()) for b, o in pred]
         assert pred.flags() == 0
-        omlib.check(L.om_set_wino14_wide(0), "om_set_wino14_wide")
-        net._workspace.clear(); net._slot_workspaces.clear()          # the layout differs (no V scratch)
-        k_off = dict(net.layer_kernels(140, 32, 544))
-        with torch.no_grad():
-            off = net(x)
+        assert keys_off and not keys_off & set(net._workspace)      # another layout (the V scratch): another workspace, the old one dropped
         for (a, b_), (c, d) in zip(on, off):
+            assert torch.equal(a, c) and torch.equal(b_, d)
+        omlib.check(L.om_set_wino14_wide(0), "om_set_wino14_wide")              # ... and back
+        with torch.no_grad():
+            back = net(x)
+        for (a, b_), (c, d) in zip(on, back):
             assert torch.equal(a, c) and torch.equal(b_, d)
     finally:
         L.om_set_wino14_wide(was)
-        net._workspace.clear(); net._slot_workspaces.clear()
     wide = sorted(k for k, v in k_on.items() if v.startswith("wino14_wide_kernel"))
     assert wide == sorted(["backbone.conv6.%d.conv.1" % i for i in range(1, 5)] + ["neck32.1", "neck32.3", "bbox_head32.0"]), wide
     assert all(k_off[k].startswith("wino14_split_kernel") for k in wide)
@@ -1002,6 +1010,47 @@ def test_stem3_split_equals_stem2_then_1x1(dev, shape):
     want = torch.nn.functional.conv2d(b2, w3.double()) * sc3.double().view(1, -1, 1, 1) + sh3.double().view(1, -1, 1, 1)
     want = torch.where(want > 0, want, want * 0.1)
     assert _rel_err(buf3[..., 8:40].cpu().permute(0, 3, 1, 2).double(), want) < 4e-6
+
+
+@pytest.mark.gpu
+def test_stem_launchers_refuse_a_misaligned_view(dev):
+    """What a first-layers launcher cannot take is an error of the call, found on the host before anything is launched
+    (conv_stem2.hip: the launchers require stem2_split_supported / stem2_f16_supported of their real pointers -- the predicates
+    om_forward's plan asks ahead): an output view 4 bytes off 16-byte alignment, the third layer's view alone so, the fp16 kernel's
+    view 2 bytes off.  Each returns OM_EINVAL, om_last_error names the stem, and the sentinel-filled tensors are untouched.
+    Every view lies inside its tensor, whatever a launch would have written."""
+    from orienmask_amd.pack import conv_weights_f16, conv_weights_split
+    B, H, W = 1, 16, 32
+    Ho, Wo = H // 2, W // 2
+    L = omlib.load()
+    g = torch.Generator().manual_seed(23)
+    xd = torch.rand(B, 3, H, W, generator=g).to(dev)
+    w1p = (torch.randn(32, 27, generator=g) * 0.3).to(dev)
+    one32, one64 = torch.ones(32, device=dev), torch.ones(64, device=dev)
+    w2 = torch.randn(64, 32, 3, 3, generator=g) / 17.0
+    ws2d, ws3d = conv_weights_split(w2, 64)[0].to(dev), conv_weights_split(torch.randn(32, 64, 1, 1, generator=g) / 8.0, 32)[0].to(dev)
+    w2h = conv_weights_f16(w2.half().float(), 64).contiguous().to(dev)
+    st = omlib.current_stream_ptr(dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    out = torch.full((B, Ho, Wo, 68), -7.5, device=dev)
+    out3 = torch.full((B, Ho, Wo, 36), -7.5, device=dev)
+    outh = torch.full((B, Ho, Wo, 68), -7.5, device=dev, dtype=torch.float16)
+    off = lambda t: ctypes.c_void_p(t.data_ptr() + t.element_size())          # one element in: channels 1 .. of the wider tensor
+    assert out.data_ptr() % 16 == 0 and out3.data_ptr() % 16 == 0 and outh.data_ptr() % 8 == 0
+    calls = [
+        lambda: L.om_conv2d_stem2_split(_p(xd), B, H, W, _p(w1p), _p(one32), _p(one32), _p(ws2d), _p(one64), _p(one64), 64, 1, off(out), 68,
+                                        _p(status), st),
+        lambda: L.om_conv2d_stem3_split(_p(xd), B, H, W, _p(w1p), _p(one32), _p(one32), _p(ws2d), _p(one64), _p(one64), 64, 1, _p(out), 68,
+                                        _p(ws3d), _p(one32), _p(one32), 32, 1, off(out3), 36, _p(status), st),
+        lambda: L.om_conv2d_stem2_f16(_p(xd), B, H, W, _p(w1p), _p(one32), _p(one32), _p(w2h), _p(one64), _p(one64), 64, 1, off(outh), 68, st),
+    ]
+    for call in calls:
+        assert call() == -1                                                   # OM_EINVAL
+        assert b"stem2" in L.om_last_error(), L.om_last_error()
+    torch.cuda.synchronize()
+    assert int(status.item()) == 0
+    for t in (out, out3, outh):
+        assert bool((t == -7.5).all())
 
 
 # ------------------------------------------------------------------------------------------------

@@ -603,3 +603,88 @@ def test_layer_audit_covers_every_chooser_kernel(built):
         assert i in used, "stale exemption: the chooser no longer picks %s %s without kept activations" % (p, pat)
         for t in tests:
             assert t in hip_tests, "exemption %s %s names %s, which tests/test_hip_parity.py no longer has" % (p, pat, t)
+
+
+def _first_layer_kernels(net, size):
+    return [k for _, k in net.layer_kernels(1, size, size)[:3]]
+
+
+@pytest.mark.parametrize("precision,esz,fused_at,kernel", [("f32_split", 4, 5792, "conv_stem2_split_kernel<"),
+                                                            ("f16", 2, 8160, "conv_stem2_f16_kernel<")])
+def test_plan_refuses_what_the_stem_launcher_would_refuse(built, precision, esz, fused_at, kernel):
+    """The first layers are fused exactly as far as their launcher takes them (conv_stem2.hip: stem2_split_supported /
+    stem2_f16_supported, asked by om_model::plan()): at one image, up to the largest square multiple of 32 whose conv2.0 output view
+    (H/2 x W/2 pixels of 64 channels) still fits a buffer descriptor; 32 more and the plan names the separate kernels.  Host
+    arithmetic only: the table and the workspace size are answered at both sizes, the latter growing with the size."""
+    from orienmask_amd.model import OrienMaskYOLOFPNPlus
+    L = omlib.load()
+    fits = lambda n: (n // 2) * (n // 2) * 64 * esz < 0x7FFFFFF0          # the launcher's arithmetic
+    n = max(s for s in range(32, 16384, 32) if fits(s))
+    assert n == fused_at and not fits(n + 32)
+    net = OrienMaskYOLOFPNPlus(3, 80).set_precision(precision)
+    h = net._ensure_handle()
+    fused, separate = _first_layer_kernels(net, n), _first_layer_kernels(net, n + 32)
+    query = L.om_forward_f16_workspace_bytes if precision == "f16" else L.om_forward_workspace_bytes
+    ws = [query(h, 1, s, s) for s in (n, n + 32)]
+    inside = "(in the previous layer's kernel)"
+    if precision == "f32_split":
+        assert fused[0].startswith(kernel) and fused[1:] == [inside, inside], fused
+        assert separate[0] == "conv_stem_kernel" and all(k.startswith("conv_igemm_split_kernel<") for k in separate[1:]), separate
+    else:       # the fp16 kernel holds the first two layers
+        assert fused[0].startswith(kernel) and fused[1] == inside and fused[2].startswith("conv_igemm_f16_kernel<"), fused
+        assert separate[0] == "conv_stem_kernel<f16>" and all(k.startswith("conv_igemm_f16_kernel<") for k in separate[1:]), separate
+    assert 0 < ws[0] < ws[1], ws
+
+
+def test_wide_3x3_predicate_is_complete(built):
+    """om_model::plan() names the two-kernel wide form only where launch_conv_wino14_wide takes the layer (conv_wino14.hip:
+    wino14_wide_supported, with the view sizes of the epilogue's buffer-descriptor form): a 1/32-scale 512 -> 1024 layer's output is
+    17 x 17 x 1024 x 4 bytes per image at 544^2, so from ceil(2^31 / that) images on the view exceeds a descriptor and the fused
+    kernel runs the layer; one image fewer is still the wide form.  Host arithmetic only."""
+    from orienmask_amd.model import OrienMaskYOLOFPNPlus
+    L = omlib.load()
+    per_image = 17 * 17 * 1024 * 4
+    B = -(-2 ** 31 // per_image)
+    assert (B - 1) * per_image < 0x7FFFFFF0 <= B * per_image
+    net = OrienMaskYOLOFPNPlus(3, 80).set_precision("f32_split")
+    was = L.om_get_wino14_wide()
+    try:
+        omlib.check(L.om_set_wino14_wide(1), "om_set_wino14_wide")
+        below, at = dict(net.layer_kernels(B - 1, 544, 544)), dict(net.layer_kernels(B, 544, 544))
+    finally:
+        L.om_set_wino14_wide(was)
+    for name in ["backbone.conv6.%d.conv.1" % i for i in range(1, 5)] + ["neck32.1", "neck32.3", "bbox_head32.0"]:
+        assert below[name] == "wino14_wide_kernel<128,128>", (name, below[name])
+        assert at[name] == "wino14_split_kernel<128,64>", (name, at[name])
+
+
+_SWITCH_CHILD = """
+from orienmask_amd import lib
+L = lib.load()
+print(L.om_get_stem_fusion(0), L.om_get_stem_fusion(1), L.om_get_wino14_wide())
+for which in (0, 1):
+    for on in (0, 1, 0):
+        assert L.om_set_stem_fusion(which, on) == 0 and L.om_get_stem_fusion(which) == on
+        assert L.om_get_stem_fusion(1 - which) in (0, 1)
+for on in (0, 1, 0):
+    assert L.om_set_wino14_wide(on) == 0 and L.om_get_wino14_wide() == on
+assert L.om_set_stem_fusion(2, 1) != 0 and b"om_set_stem_fusion" in L.om_last_error()
+assert L.om_set_stem_fusion(0, 2) != 0 and L.om_set_wino14_wide(2) != 0 and L.om_set_wino14_wide(-1) != 0
+assert L.om_get_stem_fusion(2) == -1 and L.om_get_stem_fusion(-1) == -1
+assert (L.om_get_stem_fusion(0), L.om_get_wino14_wide()) == (0, 0)          # a refused set changes nothing
+print("ok")
+"""
+
+
+@pytest.mark.parametrize("env,defaults", [({}, "1 1 1"), ({"OM_NO_STEM3": "1"}, "0 1 1"),
+                                          ({"OM_NO_STEM2_F16": "1", "OM_NO_W14_WIDE": "1", "OM_NO_STEM3": "0"}, "1 0 0")])
+def test_switch_defaults_and_setters(built, env, defaults):
+    """The process-wide switches (om_set_stem_fusion, om_set_wino14_wide): default on, off while their environment variable is 1
+    -- read once per process, hence a fresh child per setting --; a set is what the next get returns, whatever the default was;
+    an invalid argument is refused and changes nothing."""
+    import subprocess
+    import sys
+    clean = {k: v for k, v in os.environ.items() if k not in ("OM_NO_STEM3", "OM_NO_STEM2_F16", "OM_NO_W14_WIDE")}
+    r = subprocess.run([sys.executable, "-c", _SWITCH_CHILD], cwd=REPO, env=dict(clean, **env), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert r.stdout.split("\n")[:2] == [defaults, "ok"], r.stdout
