@@ -13,7 +13,8 @@ Deliberate departures from the reference:
     NotImplementedError: the class with a backward (om_loss_backward) is orienmask_amd.train.OrienMaskYOLOMultiScaleLoss;
   * a non-finite pred_wh raises FloatingPointError (the reference prints and calls exit());
   * loud limits: 1..3 scales of 1..3 anchors, at most 9 anchors, 2047 classes and OM_LOSS_MAX_GT (1024) GTs per image; the
-    orientation maps are exactly image / 4 per side;
+    orientation maps are exactly image / 4 per side.  The GT limit is exercised: tests/test_loss_crowd.py checks values,
+    targets and gradients of images with 63 .. 1024 GTs (1025 is refused, tests/test_loss.py);
   * scales_weight=None means ones (the reference reads num_scales before setting it and fails).
 Duplicate positives (two GTs on one cell) follow torch-CPU's answer: box targets from the highest GT index, tcls the union of
 their classes (csrc/loss.hip).

@@ -81,7 +81,7 @@ def test_fixture_values(dev, name):
                 assert cnt == rc and _rel(num, rn) <= REL, (name, sid, k, num, rn, cnt, rc)
 
 
-@pytest.mark.parametrize("name", [f for f in FIXTURES if "544" not in f])
+@pytest.mark.parametrize("name", [f for f in FIXTURES if "544" not in f and "ladder" not in f])     # those with full targets
 def test_fixture_targets(dev, name):
     """om_loss_targets against build_targets' outputs: orien_mask and torien bit-exact, txy / masks / bbox_pos_scale exact
     (bbox_neg up to the near-threshold allowance), twh within 1 ulp, tiou within TIOU_ULP, tcls' positive entries equal.
@@ -126,7 +126,10 @@ def _random_case(seed):
 def test_random_cases_match_restatement(dev, seed):
     """HIP against tests/loss_np.py on seeded random cases: B 1..8, 0..60 GTs per image, both anchor sets, label smoothing on and
     off.  The restatement uses correctly rounded elementary functions; so does the device except for its bit-exact sigmoids (one
-    ulp apart on a few percent of inputs): terms within 1e-5 relative, counts exact (random data lands on no threshold)."""
+    ulp apart on a few percent of inputs): terms within 1e-5 relative, counts exact (random data lands on no threshold).
+    With at most 60 GTs per image these cases stay within one ballot round of the orientation culls and one trip of the box
+    kernels' LDS fill, and rarely pile GTs on a cell; crowds of 63 .. 1024 GTs, piles of 3 .. 9, ROI edges on the tile seams
+    and anchor ties are tests/test_loss_crowd.py's directed cases (tests/loss_cases.py)."""
     cfg, heads, target = _random_case(seed)
     predict, tgt = _to(dev, heads, target)
     _, log, mlog = _loss(cfg)(predict, tgt, training=False)
