@@ -785,6 +785,21 @@ int om_conv2d_grad_input(const float* dy, const float* w, int B, int cin, int H,
 int om_conv2d_grad_weight(const float* x, const float* dy, int B, int cin, int H, int W, int cout, int ksize, int stride, float* dw,
                           float* dbias, void* workspace, size_t ws_bytes, om_stream stream);
 
+/* ---- The forward of the same convolutions (orienmask_amd.train.conv2d with forward='hip'; the models with conv_forward='hip'):
+ *      y[b,co,oy,ox] = bias[co] + sum over ci and the taps of x[b,ci,oy*stride+kh-pad,ox*stride+kw-pad] * w[co,ci,kh,kw], for the
+ *      geometries, layouts and size limits of the gradients above; y [B,cout,Ho,Wo], bias [cout] or null.  H and W are the INPUT's.
+ *      One kernel (csrc/conv_fwd.hip): 128 consecutive output pixels of the flat (b, oy, ox) index by 64 (or 32) output channels
+ *      per workgroup, the whole k = cin * ksize^2 in that workgroup: no split, no workspace.  An accumulation chain of the matrix
+ *      instruction holds at most 32 products (8 input channels x the 3 column taps of one row tap; 32 input channels at 1x1); the
+ *      chains of an element are summed in double in ci order, row taps in kh order, the bias is added as a double and the sum is
+ *      rounded once.  That order is a function of the geometry only -- not of the pixel's place in a tile, the image index, B or
+ *      the device -- so an image's y has the same bits alone and in any batch.
+ *      Fp32 operands on the f32 matrix instruction.  Everything is enqueued on `stream`; no allocation, no host synchronisation,
+ *      no atomics, bit-identical from run to run.  A null x / w / y, another geometry or sizes outside the limits return OM_EINVAL
+ *      and nothing is written. */
+int om_conv2d_forward(const float* x, const float* w, const float* bias, int B, int cin, int H, int W, int cout, int ksize, int stride,
+                      float* y, om_stream stream);
+
 /* ---- Several batches in flight.  Every entry point only enqueues kernels on the caller's stream and keeps no per-call state in
  *      the model handle (profiling apart): om_forward / om_forward_f16 / om_postprocess may be issued for different batches
  *      on different HIP streams at the same time, provided each batch in flight has its OWN workspace (and output buffers);

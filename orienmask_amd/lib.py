@@ -205,6 +205,7 @@ SIGNATURES = {
     "om_conv2d_grad_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
     "om_conv2d_grad_input": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "om_conv2d_grad_weight": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "om_conv2d_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
 }
 
 _lib = None

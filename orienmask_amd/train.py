@@ -26,9 +26,11 @@ And the reference's model in training mode: ``builder.build(config["model"], ori
                                records between the block's two phases, merged in rank order on every rank)
 
   conv2d                       F.conv2d whose input, weight and bias gradients are om_conv2d_grad_input / om_conv2d_grad_weight
-                               (csrc/conv_grad.hip); the models use it with conv_backend='hip'
+                               (csrc/conv_grad.hip); the models use it with conv_backend='hip'.  With forward='hip' the forward
+                               is om_conv2d_forward (csrc/conv_fwd.hip) too; the models pass it with conv_forward='hip'
 
-The forward convolution is torch's.  Its gradients are torch's with conv_backend='torch' (the default) and the HIP kernels of
+The forward convolution is torch's with conv_forward='torch' (the default) and om_conv2d_forward with conv_forward='hip', which
+needs conv_backend='hip'.  Its gradients are torch's with conv_backend='torch' (the default) and the HIP kernels of
 csrc/conv_grad.hip with conv_backend='hip'; the up-sampling, cat and split stay torch ops.
 """
 import contextlib
@@ -50,6 +52,15 @@ __all__ = ["OrienMaskYOLOMultiScaleLoss", "EvalCounter", "ConvBNLeaky", "bn_leak
 
 BACKENDS = ("hip", "torch")
 CONV_BACKENDS = ("torch", "hip")
+CONV_FORWARDS = ("torch", "hip")
+
+
+def _check_conv_forward(conv_backend, conv_forward):
+    if conv_forward not in CONV_FORWARDS:
+        raise ValueError("conv_forward must be one of %s, got %r" % (CONV_FORWARDS, conv_forward))
+    if conv_forward == "hip" and conv_backend != "hip":
+        raise ValueError("conv_forward 'hip' requires conv_backend 'hip', got conv_backend %r: torch's gradient node under the HIP "
+                         "forward is not supported" % (conv_backend,))
 
 
 class _LossBackward(torch.autograd.Function):
@@ -222,16 +233,27 @@ class _BNAct(torch.autograd.Function):
 
 
 class _Conv2d(torch.autograd.Function):
-    """forward(ctx, x, weight, bias, stride) -> F.conv2d(x, weight, bias, stride, ksize // 2).  Saved for the backward: x and the
-    weight, what torch's own node saves.  The backward enqueues om_conv2d_grad_input and om_conv2d_grad_weight (csrc/conv_grad.hip)
+    """forward(ctx, x, weight, bias, stride, hip_forward) -> F.conv2d(x, weight, bias, stride, ksize // 2), or with hip_forward
+    the same convolution as om_conv2d_forward (csrc/conv_fwd.hip) into a torch.empty output.  Saved for the backward either way: x
+    and the weight, what torch's own node saves.  The backward enqueues om_conv2d_grad_input and om_conv2d_grad_weight (csrc/conv_grad.hip)
     on the current stream for the gradients that are needed: no input gradient for an input that needs none, no weight gradient for
     a frozen weight; the bias gradient comes from the weight-gradient call."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, stride):
+    def forward(ctx, x, weight, bias, stride, hip_forward=False):
         ctx.save_for_backward(x, weight)
         ctx.stride, ctx.has_bias = stride, bias is not None
-        return F.conv2d(x, weight, bias, stride, weight.shape[2] // 2)
+        if not hip_forward:
+            return F.conv2d(x, weight, bias, stride, weight.shape[2] // 2)
+        B, cin, H, W = x.shape
+        cout, ks = weight.shape[0], weight.shape[2]
+        pad = ks // 2
+        dev = x.device
+        y = torch.empty((B, cout, (H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1), dtype=torch.float32, device=dev)
+        with _device(dev):
+            _lib.check(_lib.load().om_conv2d_forward(_vp(x), _vp(weight), _vp(bias), B, cin, H, W, cout, ks, stride, _vp(y),
+                                                     _lib.current_stream_ptr(dev)), "om_conv2d_forward")
+        return y
 
     @staticmethod
     @once_differentiable
@@ -256,7 +278,12 @@ class _Conv2d(torch.autograd.Function):
             if need_w or need_b:
                 _lib.check(L.om_conv2d_grad_weight(_vp(x), _vp(dy), *geom, _vp(dw), _vp(db), ws.data_ptr(), ws.numel(), stream),
                            "om_conv2d_grad_weight")
-        return dx, dw, db, None
+        return dx, dw, db, None, None
+
+
+def _forward_kw(conv_forward):
+    """conv2d's keyword for a model's conv_forward: none for the default, so the call is the one it was before the argument."""
+    return {} if conv_forward == "torch" else {"forward": conv_forward}
 
 
 def _pair_of(v, what):
@@ -266,10 +293,15 @@ def _pair_of(v, what):
     return int(a)
 
 
-def conv2d(x, weight, bias=None, stride=1, padding=0):
+def conv2d(x, weight, bias=None, stride=1, padding=0, forward="torch"):
     """F.conv2d(x, weight, bias, stride, padding) with the gradients as HIP kernels (csrc/conv_grad.hip).  x, weight and bias CUDA
     float32, x NCHW-contiguous [B,cin,H,W], weight contiguous [cout,cin,k,k]; the geometry one of 1x1 stride 1 padding 0, 3x3
-    stride 1 padding 1, 3x3 stride 2 padding 1, without dilation or groups.  Anything else raises: there is no fallback."""
+    stride 1 padding 1, 3x3 stride 2 padding 1, without dilation or groups.  Anything else raises: there is no fallback.
+    forward 'torch' (default): the forward is F.conv2d.  forward 'hip': it is om_conv2d_forward (csrc/conv_fwd.hip), enqueued on
+    the current stream and bit-identical from run to run; the backward and what it reads are the same, so for the same (x, weight,
+    dy) the gradients have the same bits under either forward."""
+    if forward not in CONV_FORWARDS:
+        raise ValueError("forward must be one of %s, got %r" % (CONV_FORWARDS, forward))
     _lib.require_cuda_tensor(x, "the convolution input (conv_backend 'hip')", torch.float32)
     _lib.require_cuda_tensor(weight, "the convolution weight (conv_backend 'hip')", torch.float32)
     if bias is not None:
@@ -286,7 +318,7 @@ def conv2d(x, weight, bias=None, stride=1, padding=0):
     if (ks, s, p) not in ((1, 1, 0), (3, 1, 1), (3, 2, 1)):
         raise _lib.OrienMaskHipError("conv2d: kernel %d stride %d padding %d; the HIP gradients cover 1x1 stride 1 padding 0, 3x3 "
                                      "stride 1 padding 1 and 3x3 stride 2 padding 1" % (ks, s, p))
-    return _Conv2d.apply(x, weight, bias, s)
+    return _Conv2d.apply(x, weight, bias, s, forward == "hip")
 
 
 class _SyncBNAct(torch.autograd.Function):
@@ -395,16 +427,22 @@ class ConvBNLeaky(nn.Module):
     After convert_sync_batchnorm (`sync` True) the batch statistics are those of every rank of `process_group`.
 
     conv_backend 'torch' (default): the convolution is F.conv2d with torch's gradients.  conv_backend 'hip': the same forward
-    through conv2d, whose gradients are the HIP kernels of csrc/conv_grad.hip; CUDA float32 NCHW-contiguous tensors only."""
+    through conv2d, whose gradients are the HIP kernels of csrc/conv_grad.hip; CUDA float32 NCHW-contiguous tensors only.
 
-    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, backend="hip", conv_backend="torch"):
+    conv_forward 'torch' (default): the forward convolution is F.conv2d.  conv_forward 'hip' (needs conv_backend 'hip'): it is
+    om_conv2d_forward (csrc/conv_fwd.hip)."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, backend="hip", conv_backend="torch",
+                 conv_forward="torch"):
         super().__init__()
         if backend not in BACKENDS:
             raise ValueError("backend must be one of %s, got %r" % (BACKENDS, backend))
         if conv_backend not in CONV_BACKENDS:
             raise ValueError("conv_backend must be one of %s, got %r" % (CONV_BACKENDS, conv_backend))
+        _check_conv_forward(conv_backend, conv_forward)
         self.backend = backend
         self.conv_backend = conv_backend
+        self.conv_forward = conv_forward
         self.sync, self.process_group = False, None          # set by convert_sync_batchnorm
         self.conv_block = nn.Sequential(
             nn.Conv2d(in_channels, out_channels, kernel_size, stride=stride, padding=padding, bias=False),
@@ -416,7 +454,7 @@ class ConvBNLeaky(nn.Module):
         if bn.momentum is None:
             raise ValueError("ConvBNLeaky: momentum=None (a cumulative moving average) is not supported")
         if self.conv_backend == "hip":
-            h = conv2d(x, conv.weight, None, conv.stride, conv.padding)
+            h = conv2d(x, conv.weight, None, conv.stride, conv.padding, **_forward_kw(self.conv_forward))
         else:
             h = F.conv2d(x, conv.weight, None, conv.stride, conv.padding)
         training = bn.training or bn.running_mean is None
@@ -471,12 +509,13 @@ class _Backbone(_Container):
 class OrienMaskYOLOFPNPlus(nn.Module):
     """The reference's OrienMaskYOLOFPNPlus (model/orienmask_yolo_fpnplus.py:9-90) for training: the same constructor arguments
     plus `backend` ('hip' / 'torch') and `conv_backend` ('torch' / 'hip': whose convolution gradients, see ConvBNLeaky; with 'hip'
-    the plain head convolutions go through conv2d on the nn.Conv2d modules' parameters), the same state_dict keys and parameters() order as the reference and as
+    the plain head convolutions go through conv2d on the nn.Conv2d modules' parameters) and `conv_forward` ('torch' / 'hip': whose
+    forward convolution, for the blocks and the four head convolutions; 'hip' needs conv_backend 'hip'), the same state_dict keys and parameters() order as the reference and as
     orienmask_amd.model (checkpoints and optimizer state move in both directions), trainable parameters, and a forward that
     returns the reference's ((bbox32, orien32), (bbox16, orien16), (bbox8, orien8)) with a graph behind it."""
 
     def __init__(self, num_anchors, num_classes, pretrained=None, freeze_backbone=False, backbone_batchnorm_eval=False,
-                 backend="hip", conv_backend="torch"):
+                 backend="hip", conv_backend="torch", conv_forward="torch"):
         super().__init__()
         if freeze_backbone is not False:
             # the reference's DarkNet53._freeze_network calls self._freeze_module, which does not exist (darknet.py:31-38)
@@ -485,6 +524,7 @@ class OrienMaskYOLOFPNPlus(nn.Module):
             raise ValueError("backend must be one of %s, got %r" % (BACKENDS, backend))
         if conv_backend not in CONV_BACKENDS:
             raise ValueError("conv_backend must be one of %s, got %r" % (CONV_BACKENDS, conv_backend))
+        _check_conv_forward(conv_backend, conv_forward)
         self.num_anchors = num_anchors
         self.num_classes = num_classes
         self.pretrained = pretrained
@@ -492,6 +532,7 @@ class OrienMaskYOLOFPNPlus(nn.Module):
         self.backbone_batchnorm_eval = backbone_batchnorm_eval
         self.backend = backend
         self.conv_backend = conv_backend
+        self.conv_forward = conv_forward
         self.backbone = _Backbone(backbone_batchnorm_eval)
         self._plus = type(self).__name__ == "OrienMaskYOLOFPNPlus"
         self._by_name = {}
@@ -505,7 +546,7 @@ class OrienMaskYOLOFPNPlus(nn.Module):
             pad = spec.ksize // 2
             if spec.bn:
                 m = ConvBNLeaky(spec.cin, spec.cout, spec.ksize, stride=spec.stride, padding=pad, backend=backend,
-                                conv_backend=conv_backend)
+                                conv_backend=conv_backend, conv_forward=conv_forward)
             else:
                 m = nn.Conv2d(spec.cin, spec.cout, spec.ksize, stride=spec.stride, padding=pad)
             node.add_module(leaf, m)
@@ -568,7 +609,7 @@ class OrienMaskYOLOFPNPlus(nn.Module):
         """A head's nn.Conv2d: the module itself, or conv2d on its parameters (conv_backend 'hip')."""
         m = self._by_name[name]
         if self.conv_backend == "hip":
-            return conv2d(x, m.weight, m.bias, m.stride, m.padding)
+            return conv2d(x, m.weight, m.bias, m.stride, m.padding, **_forward_kw(self.conv_forward))
         return m(x)
 
     def _bbox_head(self, s, x):

@@ -1,0 +1,168 @@
+"""Time the forward convolution per distinct convolution geometry of the FPNPlus model at 544 x 544: om_conv2d_forward
+(csrc/conv_fwd.hip, what orienmask_amd.train.conv2d(forward='hip') enqueues) against F.conv2d (MIOpen, what forward='torch' runs) on
+the same GPU and the same tensors, and against om_conv2d_grad_input of the same geometry (csrc/conv_grad.hip), which does the same
+flops on the same matrix instruction.
+
+Method (tools/bench_conv_grad.py's): per geometry, WARMUP calls of each of the three, then ROUNDS interleaved rounds (hip forward,
+torch forward, hip dx, hip forward, ... so drift hits all alike); a round times INNER back-to-back calls between two HIP events and
+divides.  Reported: median / min / max per call, TFLOP/s at the median (2 * B*Ho*Wo * cout * cin * taps), the sum over the model's
+90 convolutions (median x multiplicity), the geometries where the HIP forward is slower than torch's, and one whole-model training
+step (forward + backward, median of interleaved rounds) with its peak memory for (conv_backend, conv_forward) = ('torch', 'torch'),
+('hip', 'torch') and ('hip', 'hip'), all in this run.
+
+    python tools/bench_conv_fwd.py [--batches 8 32] [--rounds 5] [--inner 3] [--warmup 2] [--out profiles/conv_fwd_bench.json]
+
+prints one JSON line (and writes it to --out); a progress line per geometry goes to stderr.
+"""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import sys
+
+sys.dont_write_bytecode = True
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+import torch  # noqa: E402
+import torch.nn.functional as F  # noqa: E402
+
+from orienmask_amd import arch, lib as omlib, train  # noqa: E402
+
+STEP_CONFIGS = (("torch", "torch"), ("hip", "torch"), ("hip", "hip"))      # (conv_backend, conv_forward)
+
+
+def layer_table(size):
+    """(cin, cout, ksize, stride, H, W) with H, W the input's -> number of convolutions."""
+    table = {}
+    for spec in arch.fpnplus_convs():
+        d = arch.layer_div(spec)
+        key = (spec.cin, spec.cout, spec.ksize, spec.stride, size // d * spec.stride, size // d * spec.stride)
+        table[key] = table.get(key, 0) + 1
+    return table
+
+
+def time_calls(fn, inner):
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    start.record()
+    for _ in range(inner):
+        fn()
+    stop.record()
+    stop.synchronize()
+    return start.elapsed_time(stop) / inner
+
+
+def bench_geometry(dev, B, key, args):
+    cin, cout, ks, stride, H, W = key
+    L = omlib.load()
+    gen = torch.Generator(device=dev).manual_seed(cin + cout + H)
+    pad = ks // 2
+    Ho, Wo = (H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1
+    x = torch.randn(B, cin, H, W, device=dev, generator=gen)
+    w = torch.randn(cout, cin, ks, ks, device=dev, generator=gen) * (cin * ks * ks) ** -0.5
+    dy = torch.randn(B, cout, Ho, Wo, device=dev, generator=gen)
+    y, dx = torch.empty_like(dy), torch.empty_like(x)
+    geom = (B, cin, H, W, cout, ks, stride)
+    st = omlib.current_stream_ptr(dev)
+    vp = lambda t: ctypes.c_void_p(t.data_ptr())      # noqa: E731
+    calls = {
+        "hip_fwd": lambda: omlib.check(L.om_conv2d_forward(vp(x), vp(w), None, *geom, vp(y), st), "fwd"),
+        "torch_fwd": lambda: F.conv2d(x, w, None, stride, pad),
+        "hip_dx": lambda: omlib.check(L.om_conv2d_grad_input(vp(dy), vp(w), *geom, vp(dx), None, 0, st), "dx"),
+    }
+    for fn in calls.values():
+        for _ in range(args.warmup):
+            fn()
+    samples = {k: [] for k in calls}
+    for _ in range(args.rounds):
+        for k, fn in calls.items():
+            samples[k].append(time_calls(fn, args.inner))
+    flops = 2.0 * B * Ho * Wo * cout * cin * ks * ks
+    out = {}
+    for name, v in samples.items():
+        v = sorted(v)
+        med = statistics.median(v)
+        out[name] = {"ms_median": round(med, 5), "ms_min": round(v[0], 5), "ms_max": round(v[-1], 5),
+                     "TFLOPs_at_median": round(flops / (med * 1e-3) / 1e12, 2)}
+    return out
+
+
+def step_times_and_memory(dev, B, size, rounds):
+    """One training step (forward + backward of the whole model) per (conv_backend, conv_forward): median ms of interleaved
+    rounds, peak memory."""
+    x = torch.rand(B, 3, size, size, device=dev)
+    nets = {}
+    for cfg in STEP_CONFIGS:
+        torch.manual_seed(0)
+        nets[cfg] = train.OrienMaskYOLOFPNPlus(3, 80, backend="hip", conv_backend=cfg[0], conv_forward=cfg[1]).to(dev).train()
+
+    def step(cfg):
+        out = nets[cfg](x)
+        sum(t.square().mean() for pair in out for t in pair).backward()
+
+    result = {cfg: {"conv_backend": cfg[0], "conv_forward": cfg[1], "batch": B} for cfg in nets}
+    for cfg in nets:
+        for _ in range(2):                # the second step is the steady state (gradients exist, the allocator is warm)
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats(dev)
+            base = torch.cuda.memory_allocated(dev)
+            step(cfg)
+            torch.cuda.synchronize()
+            peak = torch.cuda.max_memory_allocated(dev)
+        result[cfg].update(peak_bytes=int(peak), peak_above_resident_bytes=int(peak - base))
+    samples = {cfg: [] for cfg in nets}
+    for _ in range(rounds):
+        for cfg in nets:
+            samples[cfg].append(time_calls(lambda: step(cfg), 1))
+    for cfg, v in samples.items():
+        v = sorted(v)
+        result[cfg].update(step_ms_median=round(statistics.median(v), 3), step_ms_min=round(v[0], 3), step_ms_max=round(v[-1], 3))
+    return [result[cfg] for cfg in STEP_CONFIGS]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", type=int, nargs="+", default=[8, 32])
+    ap.add_argument("--size", type=int, default=544)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--inner", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--step-batch", type=int, default=8)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_conv_fwd.py needs an MI355X: there is nothing to time on a CPU")
+    dev = torch.device("cuda:0")
+    table = layer_table(args.size)
+    result = {"bench": "conv_fwd", "size": args.size, "rounds": args.rounds, "inner": args.inner, "warmup": args.warmup,
+              "device": torch.cuda.get_device_name(0), "torch": torch.__version__, "batches": {}}
+    for B in args.batches:
+        rows, sums = [], {}
+        for key, count in sorted(table.items(), key=lambda kv: -kv[0][0] * kv[0][1] * kv[0][2] ** 2 * kv[0][4] * kv[0][5]):
+            r = bench_geometry(dev, B, key, args)
+            rows.append(dict(zip(("cin", "cout", "ksize", "stride", "H", "W"), key), layers=count, **r))
+            print("B=%d %s x%d: %s" % (B, key, count, {k: v["ms_median"] for k, v in r.items()}), file=sys.stderr, flush=True)
+            for k, v in r.items():
+                s = sums.setdefault(k, {"ms_median": 0.0, "ms_min": 0.0, "ms_max": 0.0})
+                for f in s:
+                    s[f] += count * v[f]
+            torch.cuda.empty_cache()
+        slower = [dict(zip(("cin", "cout", "ksize", "stride", "H"), (r["cin"], r["cout"], r["ksize"], r["stride"], r["H"])),
+                       hip_ms=r["hip_fwd"]["ms_median"], torch_ms=r["torch_fwd"]["ms_median"], hip_dx_ms=r["hip_dx"]["ms_median"])
+                  for r in rows if r["hip_fwd"]["ms_median"] > r["torch_fwd"]["ms_median"]]
+        result["batches"][str(B)] = {"geometries": rows, "layers": sum(table.values()),
+                                     "sum_over_layers_ms": {k: {f: round(x, 4) for f, x in v.items()} for k, v in sums.items()},
+                                     "geometries_where_hip_is_slower": slower}
+    result["training_step"] = step_times_and_memory(dev, args.step_batch, args.size, args.rounds)
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
