@@ -800,6 +800,29 @@ int om_conv2d_grad_weight(const float* x, const float* dy, int B, int cin, int H
 int om_conv2d_forward(const float* x, const float* w, const float* bias, int B, int cin, int H, int W, int cout, int ksize, int stride,
                       float* y, om_stream stream);
 
+/* ---- The training models' plumbing between the convolutions (model/orienmask_yolo_fpnplus.py:74-90, model/orienmask_yolo.py:71-86:
+ *      F.interpolate(mode='nearest'), torch.cat and torch.split, with autograd's backward of the three; orienmask_amd.train's
+ *      upsample_concat / split_channels, the models with route_backend='hip').  All tensors fp32 NCHW contiguous: y, dy
+ *      [B, sum(chans), H, W]; source i [B, chans[i], H / scales[i], W / scales[i]], at the channels that start at chans[0] + ... +
+ *      chans[i-1].  1 <= n <= 4 (the arrays' first n entries are read); every scale one of 1, 2, 4, 8 and a divisor of H and W; B
+ *      and every chans[i] >= 1; B * sum(chans) * H * W < 2^31.  No alignment is required: a tensor may start at any float.
+ *      om_route_concat_forward:  y[b, off_i + c, oy, ox] = src[i][b, c, oy / scales[i], ox / scales[i]] -- torch.cat of the
+ *      nearest-up-sampled sources, copies only, so bit-identical to it.  A null src[i] stands for zeros.
+ *      om_route_concat_backward: dsrc[i][b, c, sy, sx] = the scales[i] x scales[i] block of dy, summed sequentially in fp32: the
+ *      accumulator starts as the block's first element, rows top to bottom, left to right within a row (torch-CPU's
+ *      upsample_nearest2d backward order); at scale 1 a copy.  A null dsrc[i] needs no gradient: nothing is written for it.  With
+ *      every scale 1 this is torch.split(dy, chans, 1) into dense tensors, and the forward is the split's backward.
+ *      One kernel per call (csrc/route.hip), a flat grid-stride loop; each element of dy is read once, each element of y and dsrc
+ *      written once.  Two forms, chosen by the entry point from the arguments: 16-byte accesses along W where W % 4 == 0 and y / dy
+ *      and every non-null src / dsrc start on a 16-byte boundary, one element per lane otherwise; the values are the same.
+ *      Enqueued on `stream`; no allocation, no host synchronisation, no atomics, no workspace, bit-identical from run to run, and
+ *      an image's values do not depend on its place in the batch.  A null y / dy, every dsrc null, or arguments outside the
+ *      limits return OM_EINVAL: nothing is launched and nothing is written. */
+int om_route_concat_forward(const float* const src[4], const int chans[4], const int scales[4], int n, int B, int H, int W, float* y,
+                            om_stream stream);
+int om_route_concat_backward(const float* dy, const int chans[4], const int scales[4], int n, int B, int H, int W, float* const dsrc[4],
+                             om_stream stream);
+
 /* ---- Several batches in flight.  Every entry point only enqueues kernels on the caller's stream and keeps no per-call state in
  *      the model handle (profiling apart): om_forward / om_forward_f16 / om_postprocess may be issued for different batches
  *      on different HIP streams at the same time, provided each batch in flight has its OWN workspace (and output buffers);

@@ -31,7 +31,14 @@ And the reference's model in training mode: ``builder.build(config["model"], ori
 
 The forward convolution is torch's with conv_forward='torch' (the default) and om_conv2d_forward with conv_forward='hip', which
 needs conv_backend='hip'.  Its gradients are torch's with conv_backend='torch' (the default) and the HIP kernels of
-csrc/conv_grad.hip with conv_backend='hip'; the up-sampling, cat and split stay torch ops.
+csrc/conv_grad.hip with conv_backend='hip'.
+
+  upsample_concat              torch.cat of nearest-up-sampled tensors (the models' three cat sites) as om_route_concat_forward, with
+                               om_route_concat_backward (csrc/route.hip) as its backward
+  split_channels               torch.split along the channels into dense tensors: the same two kernels with the roles swapped
+
+The up-sampling, cat and split are torch ops with route_backend='torch' (the default) and these two functions with
+route_backend='hip', which is independent of the other three options.
 """
 import contextlib
 import ctypes
@@ -48,11 +55,14 @@ from .arch import DARKNET_STAGES, LEAKY_SLOPE, model_convs
 from .loss import EvalCounter, OrienMaskYOLOMultiScaleLoss as _ValuesLoss
 
 __all__ = ["OrienMaskYOLOMultiScaleLoss", "EvalCounter", "ConvBNLeaky", "bn_leaky", "conv2d", "OrienMaskYOLOFPNPlus", "OrienMaskYOLO",
-           "convert_sync_batchnorm"]
+           "convert_sync_batchnorm", "upsample_concat", "split_channels"]
 
 BACKENDS = ("hip", "torch")
 CONV_BACKENDS = ("torch", "hip")
 CONV_FORWARDS = ("torch", "hip")
+ROUTE_BACKENDS = ("torch", "hip")
+ROUTE_SCALES = (1, 2, 4, 8)
+ROUTE_MAX = 4
 
 
 def _check_conv_forward(conv_backend, conv_forward):
@@ -321,6 +331,117 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, forward="torch"):
     return _Conv2d.apply(x, weight, bias, s, forward == "hip")
 
 
+def _route_call(fn, what, ptrs, chans, scales, B, H, W, whole, dev):
+    """One om_route_concat_* call on the current stream: `ptrs` the per-source tensors (None: null), `whole` y or dy."""
+    n = len(chans)
+    table = (ctypes.c_void_p * ROUTE_MAX)(*[t.data_ptr() if t is not None else None for t in ptrs] + [None] * (ROUTE_MAX - n))
+    c = (ctypes.c_int * ROUTE_MAX)(*list(chans) + [0] * (ROUTE_MAX - n))
+    s = (ctypes.c_int * ROUTE_MAX)(*list(scales) + [0] * (ROUTE_MAX - n))
+    stream = _lib.current_stream_ptr(dev)
+    with _device(dev):
+        if fn == "forward":
+            rc = _lib.load().om_route_concat_forward(table, c, s, n, B, H, W, _vp(whole), stream)
+        else:
+            rc = _lib.load().om_route_concat_backward(_vp(whole), c, s, n, B, H, W, table, stream)
+    _lib.check(rc, what)
+
+
+class _UpsampleConcat(torch.autograd.Function):
+    """forward(ctx, scales, *tensors) -> torch.cat([F.interpolate(t, scale_factor=s, mode='nearest')], 1): om_route_concat_forward
+    into a torch.empty output.  Nothing is saved but the shapes.  The backward is om_route_concat_backward into a gradient per input
+    that needs one; the others are passed as null and nothing is computed for them."""
+
+    @staticmethod
+    def forward(ctx, scales, *tensors):
+        B = tensors[0].shape[0]
+        H, W = tensors[0].shape[2] * scales[0], tensors[0].shape[3] * scales[0]
+        chans = [int(t.shape[1]) for t in tensors]
+        dev = tensors[0].device
+        y = torch.empty((B, sum(chans), H, W), dtype=torch.float32, device=dev)
+        _route_call("forward", "om_route_concat_forward", tensors, chans, scales, B, H, W, y, dev)
+        ctx.geom = (chans, tuple(scales), B, H, W)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        chans, scales, B, H, W = ctx.geom
+        dev = dy.device
+        dy = dy.contiguous()
+        grads = [torch.empty((B, c, H // s, W // s), dtype=torch.float32, device=dev) if need else None
+                 for c, s, need in zip(chans, scales, ctx.needs_input_grad[1:])]
+        if any(g is not None for g in grads):
+            _route_call("backward", "om_route_concat_backward", grads, chans, scales, B, H, W, dy, dev)
+        return (None,) + tuple(grads)
+
+
+class _SplitChannels(torch.autograd.Function):
+    """forward(ctx, x, sizes) -> dense tensors with the values of torch.split(x, sizes, 1): om_route_concat_backward with x in the
+    place of dy and every scale 1.  The backward is om_route_concat_forward into one [B,C,H,W] gradient; an output that received
+    no gradient is passed as null and the kernel writes its zeros."""
+
+    @staticmethod
+    def forward(ctx, x, sizes):
+        B, C, H, W = x.shape
+        outs = [torch.empty((B, c, H, W), dtype=torch.float32, device=x.device) for c in sizes]
+        _route_call("backward", "om_route_concat_backward", outs, sizes, [1] * len(sizes), B, H, W, x, x.device)
+        ctx.geom = (tuple(sizes), B, H, W, x.device)
+        ctx.set_materialize_grads(False)
+        return tuple(outs)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        sizes, B, H, W, dev = ctx.geom
+        if all(g is None for g in grads):
+            return None, None
+        grads = [g.contiguous() if g is not None else None for g in grads]
+        dx = torch.empty((B, sum(sizes), H, W), dtype=torch.float32, device=dev)
+        _route_call("forward", "om_route_concat_forward", grads, sizes, [1] * len(sizes), B, H, W, dx, dev)
+        return dx, None
+
+
+def _require_route_tensor(t, what):
+    _lib.require_cuda_tensor(t, "%s (route_backend 'hip')" % what, torch.float32)
+    if t.dim() != 4 or not t.is_contiguous():
+        raise _lib.OrienMaskHipError("route_backend 'hip' takes NCHW-contiguous [B,C,H,W] activations, got strides %s for shape %s"
+                                     % (t.stride(), tuple(t.shape)))
+
+
+def upsample_concat(tensors, scales):
+    """torch.cat([F.interpolate(t, scale_factor=s, mode='nearest') for t, s in zip(tensors, scales)], dim=1) as one HIP kernel
+    (csrc/route.hip), bit-identical to it, with the backward as one kernel too: the gradient of a source is the s x s block sum of
+    its channels' dy in torch-CPU's order.  1 to 4 CUDA float32 NCHW-contiguous tensors of one batch size whose up-sampled sizes
+    agree, and their integer scales, each 1, 2, 4 or 8.  Anything else raises: there is no fallback."""
+    tensors, scales = list(tensors), list(scales)
+    if not 1 <= len(tensors) <= ROUTE_MAX or len(scales) != len(tensors):
+        raise ValueError("upsample_concat takes 1 to %d tensors and as many scales, got %d and %d" % (ROUTE_MAX, len(tensors), len(scales)))
+    for i, t in enumerate(tensors):
+        _require_route_tensor(t, "input %d of upsample_concat" % i)
+    for s in scales:
+        if isinstance(s, bool) or not isinstance(s, int) or s not in ROUTE_SCALES:
+            raise _lib.OrienMaskHipError("upsample_concat: scale %r; the scales are the integers %s" % (s, ROUTE_SCALES))
+    B, H, W = tensors[0].shape[0], tensors[0].shape[2] * scales[0], tensors[0].shape[3] * scales[0]
+    for t, s in zip(tensors, scales):
+        if t.device != tensors[0].device or t.shape[0] != B or t.shape[2] * s != H or t.shape[3] * s != W or min(t.shape) < 1:
+            raise _lib.OrienMaskHipError("upsample_concat: shapes %s at scales %s do not give one [%d,*,%d,%d] tensor on one device"
+                                         % ([tuple(t.shape) for t in tensors], scales, B, H, W))
+    return _UpsampleConcat.apply(tuple(scales), *tensors)
+
+
+def split_channels(x, sizes):
+    """torch.split(x, sizes, dim=1) as dense tensors, one HIP kernel (csrc/route.hip); the backward is one kernel that writes the
+    whole gradient of x, zeros for an output that took no part in the loss.  x CUDA float32 NCHW-contiguous, 1 to 4 sizes >= 1
+    that sum to its channels.  Anything else raises: there is no fallback."""
+    sizes = [int(c) for c in sizes]
+    if not 1 <= len(sizes) <= ROUTE_MAX:
+        raise ValueError("split_channels takes 1 to %d sizes, got %d" % (ROUTE_MAX, len(sizes)))
+    _require_route_tensor(x, "the input of split_channels")
+    if min(sizes) < 1 or sum(sizes) != x.shape[1] or min(x.shape) < 1:
+        raise _lib.OrienMaskHipError("split_channels: sizes %s do not split the %d channels of shape %s" % (sizes, x.shape[1], tuple(x.shape)))
+    return _SplitChannels.apply(x, tuple(sizes))
+
+
 class _SyncBNAct(torch.autograd.Function):
     """forward(ctx, x, gamma, beta, residual, bn, slope, group) -> leaky(batch_norm(x)) (+ residual) with the batch statistics of
     every rank of `group` (torch.nn.SyncBatchNorm's): om_bn_sync_stats, an all-gather of the 3C-double record, om_bn_sync_forward;
@@ -510,12 +631,14 @@ class OrienMaskYOLOFPNPlus(nn.Module):
     """The reference's OrienMaskYOLOFPNPlus (model/orienmask_yolo_fpnplus.py:9-90) for training: the same constructor arguments
     plus `backend` ('hip' / 'torch') and `conv_backend` ('torch' / 'hip': whose convolution gradients, see ConvBNLeaky; with 'hip'
     the plain head convolutions go through conv2d on the nn.Conv2d modules' parameters) and `conv_forward` ('torch' / 'hip': whose
-    forward convolution, for the blocks and the four head convolutions; 'hip' needs conv_backend 'hip'), the same state_dict keys and parameters() order as the reference and as
+    forward convolution, for the blocks and the four head convolutions; 'hip' needs conv_backend 'hip') and `route_backend` ('torch'
+    / 'hip': whose up-sampling, cat and split between the convolutions: torch's ops, or upsample_concat and split_channels
+    (csrc/route.hip), CUDA float32 tensors only; independent of the other three), the same state_dict keys and parameters() order as the reference and as
     orienmask_amd.model (checkpoints and optimizer state move in both directions), trainable parameters, and a forward that
     returns the reference's ((bbox32, orien32), (bbox16, orien16), (bbox8, orien8)) with a graph behind it."""
 
     def __init__(self, num_anchors, num_classes, pretrained=None, freeze_backbone=False, backbone_batchnorm_eval=False,
-                 backend="hip", conv_backend="torch", conv_forward="torch"):
+                 backend="hip", conv_backend="torch", conv_forward="torch", route_backend="torch"):
         super().__init__()
         if freeze_backbone is not False:
             # the reference's DarkNet53._freeze_network calls self._freeze_module, which does not exist (darknet.py:31-38)
@@ -525,6 +648,8 @@ class OrienMaskYOLOFPNPlus(nn.Module):
         if conv_backend not in CONV_BACKENDS:
             raise ValueError("conv_backend must be one of %s, got %r" % (CONV_BACKENDS, conv_backend))
         _check_conv_forward(conv_backend, conv_forward)
+        if route_backend not in ROUTE_BACKENDS:
+            raise ValueError("route_backend must be one of %s, got %r" % (ROUTE_BACKENDS, route_backend))
         self.num_anchors = num_anchors
         self.num_classes = num_classes
         self.pretrained = pretrained
@@ -533,6 +658,7 @@ class OrienMaskYOLOFPNPlus(nn.Module):
         self.backend = backend
         self.conv_backend = conv_backend
         self.conv_forward = conv_forward
+        self.route_backend = route_backend
         self.backbone = _Backbone(backbone_batchnorm_eval)
         self._plus = type(self).__name__ == "OrienMaskYOLOFPNPlus"
         self._by_name = {}
@@ -589,7 +715,21 @@ class OrienMaskYOLOFPNPlus(nn.Module):
 
     def _route(self, name, x, up):
         x = self._by_name[name](x)
+        if self.route_backend == "hip":
+            return x, up                     # the up-sampling happens in _cat's kernel
         return F.interpolate(x, scale_factor=up, mode="nearest") if up > 1 else x
+
+    def _cat(self, parts):
+        """torch.cat along the channels; route_backend 'hip': upsample_concat of (tensor, scale) pairs, a bare tensor at scale 1."""
+        if self.route_backend == "hip":
+            pairs = [p if isinstance(p, tuple) else (p, 1) for p in parts]
+            return upsample_concat([t for t, _ in pairs], [s for _, s in pairs])
+        return torch.cat(parts, dim=1)
+
+    def _split(self, x, size):
+        if self.route_backend == "hip":
+            return split_channels(x, [size] * (x.shape[1] // size))
+        return torch.split(x, size, dim=1)
 
     def _backbone_forward(self, x):
         """model/backbone/darknet.py:47-54 with the blocks of :14-15."""
@@ -620,8 +760,8 @@ class OrienMaskYOLOFPNPlus(nn.Module):
             raise ValueError("x must be [B,3,H,W] with H and W multiples of 32, got %s" % (tuple(x.shape),))
         x32, x16, x8, x4 = self._backbone_forward(x)
         neck32 = self._run("neck32", x32)
-        neck16 = self._run("neck16", torch.cat([self._route("route32.0", neck32, 2), x16], dim=1))
-        neck8 = self._run("neck8", torch.cat([self._route("route16.0", neck16, 2), x8], dim=1))
+        neck16 = self._run("neck16", self._cat([self._route("route32.0", neck32, 2), x16]))
+        neck8 = self._run("neck8", self._cat([self._route("route16.0", neck16, 2), x8]))
         bbox32 = self._bbox_head(32, neck32)
         bbox16 = self._bbox_head(16, neck16)
         bbox8 = self._bbox_head(8, neck8)
@@ -630,9 +770,9 @@ class OrienMaskYOLOFPNPlus(nn.Module):
                     self._route("skip4", x4, 1)]
         else:
             cat4 = [self._route("route8.0", neck8, 2), x4]
-        oriens = self._run("neck4", torch.cat(cat4, dim=1))
+        oriens = self._run("neck4", self._cat(cat4))
         oriens = self._plain("orien_head.5", self._run("orien_head", oriens))
-        orien32, orien16, orien8 = torch.split(oriens, self.num_anchors * 2, dim=1)
+        orien32, orien16, orien8 = self._split(oriens, self.num_anchors * 2)
         return (bbox32, orien32), (bbox16, orien16), (bbox8, orien8)
 
 
