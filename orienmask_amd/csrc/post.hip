@@ -805,7 +805,11 @@ __device__ __forceinline__ unsigned shift_in_sign(unsigned acc, unsigned m) {   
     return r;
 }
 
-__global__ __launch_bounds__(256) void post_mask_kernel(const PostParams p) {
+// SMALL: the form torch's CPU kernel takes when the OUTPUT's height + width is at most 128 (ATen UpSampleKernel.cpp,
+// _use_vectorized_kernel_cond_2d; launch_post_mask): the four weights are multiplied first, w00 = wy0 * wx0 ..., and the pixel is
+// fma(v11, w11, fma(v10, w10, fma(v00, w00, v01 * w01))) -- other roundings than the two-step form of every larger image.
+template <bool SMALL>
+__device__ __forceinline__ void post_mask_body(const PostParams& p) {
     // blockIdx.y = (image, anchor field): the x4 bilinear up-sampling of an anchor's two orientation planes is shared by
     // every detection of that anchor (9 fields but up to 100 detections per image), so it is evaluated ONCE per block of
     // pixels and the detections of the field are looped over with only the predicate inside the loop.
@@ -863,8 +867,10 @@ __global__ __launch_bounds__(256) void post_mask_kernel(const PostParams p) {
     const float* px = p.oriens + ((size_t)b * nfields * 2 + field * 2) * oh * ow;
     const float* py = px + (size_t)oh * ow;
 
-    // source rows (clamped at the borders exactly like torch: src >= 0, i1 = min(i0 + 1, n - 1))
-    const int r0 = max(jy - 1, 0), r1 = min(jy, oh - 1);
+    // source rows (clamped at the borders exactly like torch: src >= 0, i1 = min(i0 + 1, n - 1)).  Output rows 0 and 1 (jy == 0)
+    // clamp to src = 0: rows 0 and min(1, oh - 1) with weight 0 on the second -- which still decides the result when that row
+    // holds a non-finite value (0 * inf = NaN, "not inside"), like the second column at the left edge below
+    const int r0 = max(jy - 1, 0), r1 = jy == 0 ? min(1, oh - 1) : min(jy, oh - 1);
     // six source columns 4g-1 .. 4g+4 cover the 16 outputs; clamp the loads at the borders
     float ax[2][6], ay[2][6];
     const int c_first = 4 * g - 1;
@@ -876,7 +882,9 @@ __global__ __launch_bounds__(256) void post_mask_kernel(const PostParams p) {
     }
     const bool left_edge = (g == 0);
     // horizontal taps of both source rows, both planes (row(y) = fmaf(v[x0], wx0, v[x1] * wx1))
+    // (SMALL: the taps themselves are kept, hx / hy = the first tap, gx / gy = the second, wxs = the weight of the second)
     float hx[2][MASK_PX], hy[2][MASK_PX];
+    float gx[SMALL ? 2 : 1][SMALL ? MASK_PX : 1], gy[SMALL ? 2 : 1][SMALL ? MASK_PX : 1], wxs[SMALL ? MASK_PX : 1];
 #pragma unroll
     for (int e = 0; e < MASK_PX; ++e) {
         const int ph = e & 3, j = e >> 2;
@@ -895,8 +903,14 @@ __global__ __launch_bounds__(256) void post_mask_kernel(const PostParams p) {
             }
             const float w1 = (e < 2 && left_edge) ? 0.0f : wx1;
             const float w0 = 1.0f - w1;
-            hx[r][e] = fmaf(v0x, w0, v1x * w1);
-            hy[r][e] = fmaf(v0y, w0, v1y * w1);
+            if constexpr (SMALL) {
+                hx[r][e] = v0x; gx[r][e] = v1x;
+                hy[r][e] = v0y; gy[r][e] = v1y;
+                wxs[e] = w1;
+            } else {
+                hx[r][e] = fmaf(v0x, w0, v1x * w1);
+                hy[r][e] = fmaf(v0y, w0, v1y * w1);
+            }
         }
     }
     // the (up to) four output rows of this block
@@ -914,13 +928,15 @@ __global__ __launch_bounds__(256) void post_mask_kernel(const PostParams p) {
         float vx[MASK_PX], vy[MASK_PX];
 #pragma unroll
         for (int e = 0; e < MASK_PX; ++e) {
-            // top edge (jy == 0): both source rows are row 0 and the second weight is 0, like torch's clamped tap
-            const float tx0 = top_edge ? hx[1][e] : hx[0][e];
-            const float bx0 = hx[1][e];
-            const float ty0 = top_edge ? hy[1][e] : hy[0][e];
-            const float by0 = hy[1][e];
-            vx[e] = fmaf(tx0, wy0, bx0 * wy1);
-            vy[e] = fmaf(ty0, wy0, by0 * wy1);
+            if constexpr (SMALL) {
+                const float w1 = wxs[e], w0 = 1.0f - w1;
+                const float w00 = wy0 * w0, w01 = wy0 * w1, w10 = wy1 * w0, w11 = wy1 * w1;
+                vx[e] = fmaf(gx[1][e], w11, fmaf(hx[1][e], w10, fmaf(hx[0][e], w00, gx[0][e] * w01)));
+                vy[e] = fmaf(gy[1][e], w11, fmaf(hy[1][e], w10, fmaf(hy[0][e], w00, gy[0][e] * w01)));
+            } else {
+                vx[e] = fmaf(hx[0][e], wy0, hx[1][e] * wy1);
+                vy[e] = fmaf(hy[0][e], wy0, hy[1][e] * wy1);
+            }
         }
         // P = (v * grid_anchor) / 2 + base (postprocess.py:142-143) depends on the ANCHOR only, not on the detection: once per
         // pixel; the loop over the field's detections keeps only the two |P - c| < t tests
@@ -964,6 +980,9 @@ __global__ __launch_bounds__(256) void post_mask_kernel(const PostParams p) {
         }
     }
 }
+
+__global__ __launch_bounds__(256) void post_mask_kernel(const PostParams p) { post_mask_body<false>(p); }
+__global__ __launch_bounds__(256) void post_mask_small_kernel(const PostParams p) { post_mask_body<true>(p); }
 
 // ------------------------------------------------------------------------------------------------
 // standalone NMS (the reference's native export nms(dets, threshold) -> keep): one 1024-thread workgroup sorts,
@@ -1249,7 +1268,9 @@ static int launch_post_mask(const om_post_cfg* cfg, const om::PostParams& p, int
     om::PostParams q = p;
     q.mask_chunk = (long long)((items + 255) / 256) * B * fields >= 2048 ? cfg->nms_post : 8;
     const int chunks = (cfg->nms_post + q.mask_chunk - 1) / q.mask_chunk;
-    hipLaunchKernelGGL(om::post_mask_kernel, dim3((items + 255) / 256, B * fields, chunks), dim3(256), 0, stream, q);
+    const dim3 grid((items + 255) / 256, B * fields, chunks);
+    if (cfg->image_h + cfg->image_w <= 128) hipLaunchKernelGGL(om::post_mask_small_kernel, grid, dim3(256), 0, stream, q);      // torch's other form
+    else hipLaunchKernelGGL(om::post_mask_kernel, grid, dim3(256), 0, stream, q);
     OM_CHECK_HIP(hipGetLastError());
     return OM_OK;
 }

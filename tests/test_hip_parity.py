@@ -47,7 +47,7 @@ def _ulps(a, b):
 def _check_detections(r, want_bbox, want_cls, want_mask, tag, exact_decode):
     """One image's detections against the reference's.  exact_decode: the heads fed to both sides were bit-identical,
     so scores and box centres must be bit-identical too (csrc/ref_math.h restates torch's sigmoid paths exactly) and the box
-    sizes within 2 ulps (MKL's vsExp cannot be restated); otherwise the 1e-4 budget of north_star applies."""
+    sizes within 2 ulps (MKL's vsExp cannot be restated) and the masks equal pixel for pixel; otherwise the 1e-4 budget of north_star applies."""
     assert r["bbox"].shape[0] == want_bbox.shape[0], (tag, r["bbox"].shape, want_bbox.shape)
     assert r["mask"].dtype == torch.bool and r["cls"].dtype == torch.long
     assert np.array_equal(r["cls"].cpu().numpy(), want_cls), tag                  # indices: bit-exact
@@ -59,6 +59,10 @@ def _check_detections(r, want_bbox, want_cls, want_mask, tag, exact_decode):
             assert _ulps(got[:, 2:4], want_bbox[:, 2:4]).max() <= 2, (tag, "w / h off by more than 2 ulps")
     got_mask = r["mask"].cpu().numpy()
     assert got_mask.shape == want_mask.shape, tag
+    differing = int(np.count_nonzero(got_mask.astype(bool) != want_mask.astype(bool)))
+    print("_check_detections %s: %d detections, %d differing mask pixels" % (tag, want_mask.shape[0], differing))
+    if exact_decode:          # same heads on both sides: the mask arithmetic is torch's, bit for bit; zero in every call of the suite
+        assert differing == 0, (tag, differing)
     for k in range(want_mask.shape[0]):
         assert _mask_iou(got_mask[k], want_mask[k]) >= 1 - 1e-4, (tag, k)
 
