@@ -316,6 +316,11 @@ int om_conv2d_winograd24_split(const float* in, int B, int H, int W, int cin, in
 int om_conv2d_wino14_split(const float* in, int B, int H, int W, int cin, int in_pix_stride, const void* u14_split,
                            const float* scale_split, const float* shift, int cout, int leaky, const float* res,
                            int res_pix_stride, float* out, int out_pix_stride, int32_t* status_dev, om_stream stream);
+/* Host only: how that kernel cuts a B x H x W layer into blocks.  Returns the number n <= 2 of classes of column blocks and fills
+ * classes[5 k ..] = {first tile column, tile columns per block, blocks, padded rows per block, row blocks} for k < n (a tile column
+ * is four pixels from x = 0; a class's blocks are side by side).  The padded row space is G = b * row_pitch + y + 1, G = 0 ..
+ * B * row_pitch (row_pitch = H + 1: neighbouring images share a zero row); *m_tiles = sum of blocks x row blocks. */
+int om_conv2d_wino14_blocks(int B, int H, int W, int* classes, int* row_pitch, long long* m_tiles);
 /* The same layer as TWO kernels with a 128 x 128 tile (round 6; conv_wino14.hip: wino14_v_kernel writes the transformed input
  * V = [cin/16][6][B (H + 2)][ceil(W / 4)] entries of 64 bytes into `scratch`, wino14_wide_kernel reads it by LDS-DMA: eight waves of
  * 64 entries x 32 channels x six planes, the fused kernel's epilogue): the same products in the same order, BIT-IDENTICAL outputs.

@@ -26,8 +26,10 @@
 //     it has two groups to land (the landing time of this stream is the consumers' critical path).
 // What binds the kernel is the CU's vector-memory request path (L1 pending-request stalls 41 % of the time: 72 KB of weights and
 // 61 KB of input per chunk of a 128 x 64 tile against ~20 B/clk of ingest), not HBM, the matrix pipe (27 % busy) or the producers.
-// Tiles are blocks of the PADDED row space G = b (H + 2) + y + 1 (one zero row above and below every image), so a block may
-// span images (17 x 17 layers) and the row shift ky needs no per-lane case.  The inverse transform runs once per tile, in the
+// Tiles are blocks of the PADDED row space G = b (H + 1) + y + 1 (one zero row above the first image, one below every image: the
+// row below image b is the row above image b + 1), so a block may span images (17 x 17 layers) and the row shift ky needs no
+// per-lane case.  A block's shape (R rows x Ct tile columns) belongs to the TILE (wino14_decode): a layer's column blocks come in
+// up to two widths, and a narrower block carries more rows (wino14_blocks below).  The inverse transform runs once per tile, in the
 // epilogue, position by position from the six plane accumulators.
 //
 // Numerics: V_j grows the activation by at most 10x (|4| + |5| + 1), so the split representation's range is |activation| <
@@ -107,8 +109,7 @@ __global__ __launch_bounds__(W14_THREADS, 3) void wino14_split_kernel(const Wino
     if (wave >= 8) {
         // ================================================================ producers
         const int pid = tid - 512;
-        const int hp2 = p.H + 2;
-        const int ecount = (p.R + 2) * p.Ct;
+        const int hp = p.hp;
         // a producer's few instructions per group are on everybody's critical path (the group barrier): issue them first
         __builtin_amdgcn_s_setprio(3);
         const auto rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in), 0, p.in_bytes, 0x00020000);
@@ -124,15 +125,16 @@ __global__ __launch_bounds__(W14_THREADS, 3) void wino14_split_kernel(const Wino
         auto setup_items = [&](int tile_id) {
             Wino14Tile tl;
             wino14_decode(p, tile_id, tl);
+            const int ecount = (tl.R + 2) * tl.Ct;
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 const int e = k < 2 ? 64 * k + (pid >> 2) : 128 + (pid >> 3);
                 const int q = k < 2 ? pid & 3 : (pid >> 1) & 3;
                 const int ch = k < 2 ? 4 * q : 4 * q + 2 * (pid & 1);
-                const int rr = e / p.Ct, t = e - rr * p.Ct;
+                const int rr = e / tl.Ct, t = e - rr * tl.Ct;
                 const int g = tl.g0 - 1 + rr;
-                const int b = g / hp2;
-                const int y = g - b * hp2 - 1;
+                const int b = g / hp;
+                const int y = g - b * hp - 1;
                 const bool rowok = e < ecount && g >= 0 && g < p.gtot && y >= 0 && y < p.H;
                 const int x0 = 4 * (tl.t0 + t) - 1;
                 unsigned ok = 0;
@@ -326,15 +328,21 @@ __global__ __launch_bounds__(W14_THREADS, 3) void wino14_split_kernel(const Wino
     const int swB = (fi >> 2) & 3;
     const int boff_hi = (32 * wn + fi) * 4 + (fk ^ swB);
     const int boff_lo = (32 * wn + fi) * 4 + ((2 + fk) ^ swB);
-    // A entries of this lane for the three kernel rows: entry m + ky Ct of the plane
+    // A entries of this lane for the three kernel rows: entry m + ky Ct of the plane, Ct the TILE's
     int aoff_hi[3], aoff_lo[3];
+    auto setup_aoff = [&](int Ct) {
+        // from an opaque copy of the lane id (as in wino14_epilogue): hoisted out of the tile loop, the lane's entry and half would be
+        // live across the chunk loop beside the offsets themselves, i.e. spilled and reloaded at the head of every tile
+        int l = lane;
+        asm volatile("" : "+v"(l));
 #pragma unroll
-    for (int ky = 0; ky < 3; ++ky) {
-        const int e = 32 * wm + fi + ky * p.Ct;
-        const int sw = (e >> 2) & 3;
-        aoff_hi[ky] = e * 4 + (fk ^ sw);
-        aoff_lo[ky] = e * 4 + ((2 + fk) ^ sw);
-    }
+        for (int ky = 0; ky < 3; ++ky) {
+            const int e = 32 * wm + (l & 31) + ky * Ct;
+            const int sw = (e >> 2) & 3;
+            aoff_hi[ky] = e * 4 + ((l >> 5) ^ sw);
+            aoff_lo[ky] = e * 4 + ((2 + (l >> 5)) ^ sw);
+        }
+    };
     // weight group g = 6 c + j of N tile tn: 12 KiB at ((tn * nch + c) * 6 + j) * 12288 bytes of the packed blob
     auto issue_group = [&](int ubase, int g) {
         if (g < ngroups) {
@@ -356,6 +364,7 @@ __global__ __launch_bounds__(W14_THREADS, 3) void wino14_split_kernel(const Wino
     }
     while (tile < p.total_tiles) {
         const int ubase = tl.tile_n * p.nch * 6 * (W14_UGRP * 16);
+        setup_aoff(tl.Ct);
         f32x16 acc[6];
 #pragma unroll
         for (int j = 0; j < 6; ++j)
@@ -616,7 +625,7 @@ __global__ __launch_bounds__(512, 2) void wino14_wide_kernel(const Wino14WidePar
         if (tile >= total2) break;
         const int tn2 = tile % n_tiles2, tm = tile / n_tiles2;      // N fastest: the N-tile siblings read the same V block from L2
         Wino14Tile tl;
-        tl.g0 = (tm / p.ncb) * p.R; tl.t0 = (tm % p.ncb) * p.Ct; tl.tile_n = 2 * tn2 + (wn4 >> 1); tl.n0 = tl.tile_n * W14_BN;
+        tl.R = p.R; tl.Ct = p.Ct; tl.g0 = (tm / p.ncb) * p.R; tl.t0 = (tm % p.ncb) * p.Ct; tl.tile_n = 2 * tn2 + (wn4 >> 1); tl.n0 = tl.tile_n * W14_BN;
         setup_v(tl);
 #pragma unroll
         for (int b = 0; b < 2; ++b)
@@ -699,8 +708,8 @@ __global__ __launch_bounds__(512, 2) void wino14_wide_kernel(const Wino14WidePar
     }
 }
 
-// Block shape for a layer: Ct tile columns (a divisor-like split of ceil(W / 4)) x R padded rows with R * Ct <= 128 and
-// (R + 2) * Ct <= W14_EMAX, picked for the largest share of useful rows in the 128-row matrix tile.
+// Block shape for a layer of the WIDE form: Ct tile columns (a divisor-like split of ceil(W / 4)) x R padded rows with R * Ct <= 128
+// and (R + 2) * Ct <= W14_EMAX, picked for the largest share of useful rows in the 128-row matrix tile.
 void wino14_geometry(int B, int H, int W, int* R, int* Ct, int* ncb, int* nrb) {
     const int TW = (W + 3) / 4;
     const long long gtot = (long long)B * (H + 2);
@@ -720,6 +729,68 @@ void wino14_geometry(int B, int H, int W, int* R, int* Ct, int* ncb, int* nrb) {
     }
 }
 
+// Blocks of the FUSED kernel.  The cut that needs the fewest blocks wins: the ceil(W / 4) tile columns as na blocks of a columns and
+// nb blocks of b < a columns, every block at least min(6, TW) wide (the two halo columns stay a small share of its pixels), each
+// width with the most rows that R * Ct <= 128 and (R + 2) * Ct <= W14_EMAX allow.  Among equal counts: the fewest tile columns
+// beyond the image, then fewer blocks, one width, the wider narrow block, the wider wide block.  The padded row space has ONE zero
+// row between two images: B (H + 1) + 1 rows.  An equal cut into narrower blocks (wino14_geometry's candidates) is taken only where
+// it needs strictly fewer blocks than all of these (narrow maps of many rows: 32 x 136 x 17 as five blocks of one column), so a
+// layer never has more than under that rule.
+// Fewer tiles are less time only while other work fills the chip (measured at 32 x 544^2, profiles/wino14_blocks_ab.md): with two
+// batches in flight the step gains 1 % and the kernel 0.15 ms, nearly all of it from the 136 and 272 px cuts (with the equal cut
+// kept for those two the gain is gone); a layer ALONE on the chip takes whole rounds of 256 tiles, and there the 136 and 272 px
+// layers gain nothing (9.6 -> 9.2 rounds), the 68 and 34 px ones 2-3 %.
+static int w14_rows_for(int ct, long long gtot) {
+    int r = W14_BM / ct;
+    while (r > 1 && (r + 2) * ct > W14_EMAX) --r;
+    if (r < 1 || (r + 2) * ct > W14_EMAX) return 0;
+    return r > gtot ? (int)gtot : r;
+}
+int wino14_blocks(int B, int H, int W, Wino14Class* cls, int* pitch, long long* gtot_out, long long* m_tiles) {
+    const int TW = (W + 3) / 4;
+    const long long gtot = (long long)B * (H + 1) + 1;
+    *pitch = H + 1; *gtot_out = gtot;
+    *m_tiles = 0;
+    int n = 1;
+    {
+        constexpr int CTMAX = W14_EMAX / 3;      // R >= 1
+        const int ctmin = TW < 6 ? TW : 6, ctmax = TW < CTMAX ? TW : CTMAX;
+        long long nrb[CTMAX + 1] = {};
+        for (int ct = ctmin; ct <= ctmax; ++ct) nrb[ct] = (gtot + w14_rows_for(ct, gtot) - 1) / w14_rows_for(ct, gtot);
+        long long best[5] = {-1, 0, 0, 0, 0};       // tiles, columns beyond the image, blocks, widths, -b: the smaller the better
+        int ba = 0, bna = 0, bb = 0, bnb = 0;
+        auto offer = [&](int a, int na, int b, int nb) {
+            const long long key[5] = {na * nrb[a] + (nb ? nb * nrb[b] : 0), (long long)na * a + (long long)nb * b - TW, na + nb, nb ? 2 : 1, -b};
+            bool better = best[0] < 0;
+            for (int i = 0; i < 5 && !better; ++i) {
+                if (key[i] != best[i]) { better = key[i] < best[i]; break; }
+                if (i == 4) better = a > ba;
+            }
+            if (better) { for (int i = 0; i < 5; ++i) best[i] = key[i]; ba = a; bna = na; bb = b; bnb = nb; }
+        };
+        for (int a = ctmin; a <= ctmax; ++a) {
+            offer(a, (TW + a - 1) / a, 0, 0);
+            for (int b = ctmin; b < a; ++b)
+                for (int na = 1; na * a < TW && na * nrb[a] < best[0]; ++na) offer(a, na, b, (TW - na * a + b - 1) / b);
+        }
+        if (best[0] < 0) return 0;
+        for (int split = 2; split <= 8; ++split) {
+            const int ct = (TW + split - 1) / split;
+            if (ct >= ctmin || ct < 1) continue;
+            nrb[ct] = (gtot + w14_rows_for(ct, gtot) - 1) / w14_rows_for(ct, gtot);
+            const int n = (TW + ct - 1) / ct;
+            if (n * nrb[ct] < best[0]) { best[0] = n * nrb[ct]; ba = ct; bna = n; bnb = 0; }
+        }
+        cls[0] = Wino14Class{0, ba, bna, w14_rows_for(ba, gtot), (int)nrb[ba], 0};
+        if (bnb) {
+            cls[1] = Wino14Class{bna * ba, bb, bnb, w14_rows_for(bb, gtot), (int)nrb[bb], (int)(bna * nrb[ba])};
+            n = 2;
+        }
+        *m_tiles = best[0];
+    }
+    return n;
+}
+
 size_t wino14_weight_halfs(int cout_pad, int cin) { return (size_t)18 * cout_pad * cin * 2; }
 
 // The sizes of a layer's launch, from its shape, its strides and its views' alignments alone (om_common.h: align_bytes): what
@@ -727,15 +798,18 @@ size_t wino14_weight_halfs(int cout_pad, int cin) { return (size_t)18 * cout_pad
 struct Wino14Shape {
     long long npix, in_bytes, out_bytes, res_bytes, total_tiles;      // a view's bytes: up to the end of its last pixel's channels
     size_t u_bytes;
-    int R, Ct, ncb, nrb;
+    int R, Ct, ncb, nrb;      // the wide form's block shape
+    int ncls, hp;             // the launch's classes of blocks (fused: wino14_blocks; wide: that one shape), its rows per image
+    long long gtot;
+    Wino14Class cls[W14_MAXCLS];
     bool aligned_in;      // the loader's form: 16-byte aligned input view, whole channel quads
     bool fast_io;         // the epilogue's buffer-descriptor form: 16-byte aligned views below 2 GiB, whole channel quads
     bool fits() const {   // the input view, the weights and the counters within a buffer descriptor / an int; a block shape exists
-        return aligned_in && in_bytes < 0x7FFFFFF0ll && npix < (1ll << 31) && R >= 1 && Ct >= 1 && total_tiles > 0 &&
+        return aligned_in && in_bytes < 0x7FFFFFF0ll && npix < (1ll << 31) && ncls >= 1 && gtot < (1ll << 31) && total_tiles > 0 &&
                total_tiles < (1ll << 31) && u_bytes < 0x7FFFFFF0ull;
     }
 };
-static Wino14Shape wino14_shape(const ConvArgs& a, int in_align_bytes, int out_align_bytes, bool has_res, int res_align_bytes) {
+static Wino14Shape wino14_shape(const ConvArgs& a, bool fused, int in_align_bytes, int out_align_bytes, bool has_res, int res_align_bytes) {
     Wino14Shape s{};
     s.npix = (long long)a.B * a.H * a.W;
     s.in_bytes = (s.npix - 1) * a.in_pix_stride * 4 + (long long)a.cin * 4;
@@ -744,21 +818,31 @@ static Wino14Shape wino14_shape(const ConvArgs& a, int in_align_bytes, int out_a
     s.aligned_in = a.in_pix_stride % 4 == 0 && in_align_bytes >= 16;
     s.fast_io = a.cout % 4 == 0 && a.out_pix_stride % 4 == 0 && out_align_bytes >= 16 &&
                 (!has_res || (a.res_pix_stride % 4 == 0 && res_align_bytes >= 16)) && s.out_bytes < 0x7FFFFFF0ll && s.res_bytes < 0x7FFFFFF0ll;
-    wino14_geometry(a.B, a.H, a.W, &s.R, &s.Ct, &s.ncb, &s.nrb);
-    s.total_tiles = (long long)s.nrb * s.ncb * (a.cout_pad / W14_BN);
+    long long m_tiles = 0;
+    if (fused) {
+        s.ncls = wino14_blocks(a.B, a.H, a.W, s.cls, &s.hp, &s.gtot, &m_tiles);
+    } else {
+        wino14_geometry(a.B, a.H, a.W, &s.R, &s.Ct, &s.ncb, &s.nrb);
+        s.hp = a.H + 2; s.gtot = (long long)a.B * s.hp;
+        m_tiles = (long long)s.nrb * s.ncb;
+        s.ncls = s.R >= 1 && s.Ct >= 1 ? 1 : 0;
+        s.cls[0] = Wino14Class{0, s.Ct, s.ncb, s.R, s.nrb, 0};
+    }
+    if (s.ncls == 1) s.cls[1] = Wino14Class{0, s.cls[0].Ct, s.cls[0].ncb, s.cls[0].R, 0, m_tiles < (1ll << 31) ? (int)m_tiles : 0};
+    s.total_tiles = m_tiles * (a.cout_pad / W14_BN);
     s.u_bytes = wino14_weight_halfs(a.cout_pad, a.cin) * 2;
     return s;
 }
 static bool wino14_layer_kind_ok(const ConvArgs& a) { return a.ks == 3 && a.stride == 1 && a.out_mode == 0 && a.cin % 16 == 0 && a.cin >= 16 && a.cout_pad % 64 == 0; }
 
 // the fused kernel's parameters from a layer's arguments (shared by the two-kernel wide form)
-static int wino14_fill_params(const ConvArgs& a, Wino14Params& p) {
+static int wino14_fill_params(const ConvArgs& a, bool fused, Wino14Params& p) {
     OM_REQUIRE(a.in && a.w && a.scale && a.shift && a.out && a.ticket, OM_EINVAL, "wino14: null pointer");
     OM_REQUIRE(wino14_layer_kind_ok(a), OM_EINVAL, "wino14: 3x3 stride-1 NHWC layers only, cin=%d cout_pad=%d", a.cin, a.cout_pad);
     OM_REQUIRE((reinterpret_cast<uintptr_t>(a.w) & 15) == 0, OM_EINVAL, "wino14: the weights must be 16-byte aligned");
-    const Wino14Shape s = wino14_shape(a, align_bytes(a.in), align_bytes(a.out), a.res != nullptr, align_bytes(a.res));
+    const Wino14Shape s = wino14_shape(a, fused, align_bytes(a.in), align_bytes(a.out), a.res != nullptr, align_bytes(a.res));
     OM_REQUIRE(s.fits(), OM_EINVAL, "wino14: %d x %d x %d: input view (%lld bytes) not 16-byte aligned, or it, the weights, %lld pixels or "
-               "%lld tiles (block %d x %d) out of range", a.B, a.H, a.W, s.in_bytes, s.npix, s.total_tiles, s.R, s.Ct);
+               "%lld tiles (first block %d x %d) out of range", a.B, a.H, a.W, s.in_bytes, s.npix, s.total_tiles, s.cls[0].R, s.cls[0].Ct);
     p.in = a.in; p.u = reinterpret_cast<const _Float16*>(a.w); p.scale = a.scale; p.shift = a.shift; p.res = a.res; p.out = a.out;
     p.ticket = a.ticket; p.status = a.status;
     p.B = a.B; p.H = a.H; p.W = a.W; p.in_ps = a.in_pix_stride; p.in_bytes = (int)s.in_bytes;
@@ -766,7 +850,8 @@ static int wino14_fill_params(const ConvArgs& a, Wino14Params& p) {
     p.fast_io = s.fast_io ? 1 : 0;
     p.out_bytes = s.fast_io ? (int)s.out_bytes : 0;
     p.res_bytes = s.fast_io ? (int)s.res_bytes : 0;
-    p.R = s.R; p.Ct = s.Ct; p.ncb = s.ncb; p.gtot = a.B * (a.H + 2);
+    p.R = s.R; p.Ct = s.Ct; p.ncb = s.ncb; p.gtot = (int)s.gtot; p.hp = s.hp;
+    for (int k = 0; k < W14_MAXCLS; ++k) p.cls[k] = s.cls[k];
     p.n_tiles = a.cout_pad / W14_BN;
     p.nch = a.cin / 16;
     p.total_tiles = (int)s.total_tiles;
@@ -777,7 +862,7 @@ static int wino14_fill_params(const ConvArgs& a, Wino14Params& p) {
 // a.w: the packed F(4,3) weights (include/orienmask_hip.h: om_layer_info.wsplit_off for wino layers); a.scale: scale * 2^-e
 int launch_conv_wino14_split(const ConvArgs& a, hipStream_t stream) {
     Wino14Params p;
-    if (int rc = wino14_fill_params(a, p)) return rc;
+    if (int rc = wino14_fill_params(a, true, p)) return rc;
     const long long total = p.total_tiles;
     const long long grid = total < 256 ? total : 256;        // one 768-thread workgroup per CU (156 KiB of LDS)
     if (!p.fast_io) hipLaunchKernelGGL(wino14_split_kernel<2>, dim3((unsigned)grid), dim3(W14_THREADS), 0, stream, p);
@@ -797,7 +882,7 @@ size_t wino14_wide_scratch_floats(int B, int H, int W, int cin) {
 // 64-channel N tiles, the epilogue's buffer-descriptor form, every view and V below 2 GiB.
 bool wino14_wide_supported(const ConvArgs& a, int in_align_bytes, int out_align_bytes, bool has_res, int res_align_bytes) {
     if (!wino14_layer_kind_ok(a) || a.cout_pad % 128) return false;
-    const Wino14Shape s = wino14_shape(a, in_align_bytes, out_align_bytes, has_res, res_align_bytes);
+    const Wino14Shape s = wino14_shape(a, false, in_align_bytes, out_align_bytes, has_res, res_align_bytes);
     return s.fits() && s.fast_io && wino14_wide_scratch_floats(a.B, a.H, a.W, a.cin) * 4 < 0x7FFFFFF0ull;
 }
 
@@ -806,7 +891,7 @@ int launch_conv_wino14_wide(const ConvArgs& a, float* scratch, hipStream_t strea
     OM_REQUIRE(wino14_wide_supported(a, align_bytes(a.in), align_bytes(a.out), a.res != nullptr, align_bytes(a.res)), OM_EINVAL,
                "wino14 wide: cout_pad=%d must be a multiple of 128, the views 16-byte aligned and, like V, below 2 GiB", a.cout_pad);
     Wino14WideParams pw;
-    if (int rc = wino14_fill_params(a, pw.k)) return rc;
+    if (int rc = wino14_fill_params(a, false, pw.k)) return rc;
     const int TW = (a.W + 3) / 4;
     pw.TW = TW;
     pw.v = reinterpret_cast<const _Float16*>(scratch);

@@ -153,7 +153,17 @@ int launch_conv_stem2_split(const float* in_nchw, int B, int H, int W, const flo
                             const void* w2_split, const float* scale2_split, const float* shift2, int cout2, int leaky2,
                             float* out_nhwc, int out_pix_stride, int* status, hipStream_t stream, const Stem2Third* third = nullptr);
 size_t wino14_weight_halfs(int cout_pad, int cin);
+// conv_wino14.hip: the wide form's one block shape per layer ...
 void wino14_geometry(int B, int H, int W, int* R, int* Ct, int* ncb, int* nrb);
+// ... and the fused kernel's blocks: up to W14_MAXCLS classes of column blocks, each with its own rows per block.  Class k is ncb
+// blocks of Ct tile columns from tile column t0 on, R padded rows per block, nrb row blocks; its m-tiles are [m0, m0 + ncb * nrb).
+constexpr int W14_MAXCLS = 2;
+struct Wino14Class {
+    int t0, Ct, ncb, R, nrb, m0;
+};
+// fills cls[0..n), returns n; *pitch = padded rows per image (H + 1: neighbouring images share a zero row), *gtot = padded rows in
+// all, *m_tiles = the layer's blocks
+int wino14_blocks(int B, int H, int W, Wino14Class* cls, int* pitch, long long* gtot, long long* m_tiles);
 bool wino_enabled();
 int wino_bn(long long T, int cout_pad);   // N tile of the Winograd GEMM behind a transform kernel of its own, at this size
 bool wino_fused_for(int cin);     // true: the input transform is fused into the GEMM's loader   // tile shape launch_conv_igemm picks

@@ -517,9 +517,11 @@ struct om_model {
             // With split operands F(2x4)'s successor, the fused F(4,3) kernel (conv_wino14.hip transforms its input on chip), runs at
             // every size: its matrix instructions are 5.3x cheaper than the fp32-operand F(2x2) kernel's, which outweighs idle
             // workgroup slots at small batches -- and an image's results then do not depend on the batch it is in.
-            int R = 0, Ct = 0, ncb = 0, nrb = 0;
-            om::wino14_geometry(B, Hin, Win, &R, &Ct, &ncb, &nrb);
-            const long long tiles = (long long)nrb * ncb * (li.cout_pad / 64);      // the fused kernel's 128 x 64 tiles
+            om::Wino14Class cls[om::W14_MAXCLS];
+            int pitch = 0;
+            long long gtot = 0, m_tiles = 0;
+            om::wino14_blocks(B, Hin, Win, cls, &pitch, &gtot, &m_tiles);
+            const long long tiles = m_tiles * (li.cout_pad / 64);      // the fused kernel's 128 x 64 tiles
             p.blob = om::LayerPlan::SPLIT;
             if (latency && tiles <= 128) {
                 // latency mode, per layer: only where the fused kernel would have at most 128 tiles (half the CUs idle); with more
@@ -534,11 +536,14 @@ struct om_model {
             p.w_off = li.wsplit_off; p.scale_off = li.wsplit_scale_off;
             // The two-kernel wide form (wino14_v_kernel + wino14_wide_kernel, round 6): from 512 input channels on (where the
             // pre-pass's 2.5 x the input through HBM is small next to the layer's work), and only where the fused kernel's tiles
-            // outnumber the CUs: while ONE round of them covers the layer, a round of half as many 128 x 128 tiles takes longer
+            // (counted with the wide form's own blocks, wino14_geometry) outnumber the CUs: while ONE round of them covers the
+            // layer, a round of half as many 128 x 128 tiles takes longer
             // (17^2 512 -> 1024: 0.14 against 0.21 ms per round; at bs = 32 the fused kernel needs 1.56 rounds = 0.26-0.28 ms, the
             // wide form one round + the pre-pass = 0.22-0.23 ms).  Its launcher's own conditions are asked here; a caller's tensor
             // (a head) has no known alignment.
-            if (switch_on(SW_W14_WIDE) && li.cin >= 512 && tiles > 256 && L.in.buf >= 0 && L.out.buf >= 0 && (!L.has_res || L.res.buf >= 0)) {
+            int R = 0, Ct = 0, ncb = 0, nrb = 0;
+            om::wino14_geometry(B, Hin, Win, &R, &Ct, &ncb, &nrb);
+            if (switch_on(SW_W14_WIDE) && li.cin >= 512 && (long long)nrb * ncb * (li.cout_pad / 64) > 256 && L.in.buf >= 0 && L.out.buf >= 0 && (!L.has_res || L.res.buf >= 0)) {
                 om::ConvArgs a{};
                 layer_shape(a, L, p, B, H, W);
                 if (om::wino14_wide_supported(a, view_align_bytes(L.in, false), view_align_bytes(L.out, false), L.has_res,
@@ -1290,6 +1295,18 @@ int om_conv2d_wino14_split(const float* in, int B, int H, int W, int cin, int in
     a.split = 1; a.status = status_dev;
     if (int rc = unit_ticket(static_cast<hipStream_t>(stream), &a.ticket)) return rc;
     return om::launch_conv_wino14_split(a, static_cast<hipStream_t>(stream));
+}
+
+int om_conv2d_wino14_blocks(int B, int H, int W, int* classes, int* row_pitch, long long* m_tiles) {
+    OM_REQUIRE(B > 0 && H > 0 && W > 0 && classes && row_pitch && m_tiles, OM_EINVAL, "om_conv2d_wino14_blocks: bad argument");
+    om::Wino14Class cls[om::W14_MAXCLS];
+    long long gtot = 0;
+    const int n = om::wino14_blocks(B, H, W, cls, row_pitch, &gtot, m_tiles);
+    for (int k = 0; k < n; ++k) {
+        const int v[5] = {cls[k].t0, cls[k].Ct, cls[k].ncb, cls[k].R, cls[k].nrb};
+        for (int i = 0; i < 5; ++i) classes[5 * k + i] = v[i];
+    }
+    return n;
 }
 
 size_t om_conv2d_wino14_wide_scratch_bytes(int B, int H, int W, int cin) {

@@ -28,7 +28,11 @@ struct Wino14Params {
     int* status;
     int B, H, W, in_ps, in_bytes;
     int cout, out_ps, res_ps, leaky, fast_io, out_bytes, res_bytes;
-    int R, Ct, ncb, gtot;   // block = R padded rows x Ct tile columns; ncb column blocks per row block; gtot = B * (H + 2)
+    // Padded row space: G = b * hp + y + 1, gtot rows.  The wide form has a zero row above and below every image (hp = H + 2, gtot =
+    // B * hp) and ONE block shape: R padded rows x Ct tile columns, ncb column blocks per row block.  The fused kernel lets
+    // neighbouring images share their zero row (hp = H + 1, gtot = B * hp + 1) and takes its blocks from cls[] (wino14_decode).
+    int R, Ct, ncb, gtot, hp;
+    Wino14Class cls[W14_MAXCLS];
     int n_tiles, total_tiles, nch;      // nch = cin / 16
     int u_bytes;
 };
@@ -41,14 +45,23 @@ __host__ __device__ constexpr int w14_plane(int g) { return g == 0 ? 0 : g == 1 
 
 struct Wino14Tile {
     int g0, t0, n0, tile_n;
+    int R, Ct;      // the block's shape: R padded rows from g0 on x Ct tile columns from t0 on
 };
 
+// The fused kernel's tile -> (N tile, class, row block, column block).  A class's tiles are contiguous; within a class the column
+// block runs fastest and the N tile faster still: the workgroups that transform the same input block run at the same time (its
+// pixels come from L2).  Every value is wave-uniform.
 __device__ __forceinline__ void wino14_decode(const Wino14Params& p, int tile, Wino14Tile& t) {
-    // N fastest: the workgroups that transform the same input block run at the same time (its pixels come from L2)
+    static_assert(W14_MAXCLS == 2, "one comparison picks the class");
     t.tile_n = tile % p.n_tiles;
     const int tm = tile / p.n_tiles;
-    const int cb = tm % p.ncb, rb = tm / p.ncb;
-    t.g0 = rb * p.R; t.t0 = cb * p.Ct; t.n0 = t.tile_n * W14_BN;
+    const bool k = tm >= p.cls[1].m0;      // (a layer with one class: cls[1].m0 = its number of m-tiles)
+    const int ncb = k ? p.cls[1].ncb : p.cls[0].ncb;
+    const int tl = tm - (k ? p.cls[1].m0 : 0);
+    const int rb = tl / ncb, cb = tl - rb * ncb;
+    t.R = k ? p.cls[1].R : p.cls[0].R;
+    t.Ct = k ? p.cls[1].Ct : p.cls[0].Ct;
+    t.g0 = rb * t.R; t.t0 = (k ? p.cls[1].t0 : p.cls[0].t0) + cb * t.Ct; t.n0 = t.tile_n * W14_BN;
 }
 
 // Epilogue of a consumer wave, from its six plane accumulators, with no workgroup barrier: the inverse transform position by
@@ -77,7 +90,7 @@ __device__ __forceinline__ void wino14_epilogue(const Wino14Params& p, const f32
     // entry coordinates would be live across the main loop, i.e. spilled, and reloaded here one round trip at a time
     asm volatile("" : "+v"(lane));
     const int fi = lane & 31, fk = lane >> 5;
-    const int hp2 = p.H + 2;
+    const int hp = p.hp;
     const int c8 = lane & 7;
     const int nb = tl.n0 + 32 * wn + 4 * c8;
     const int nvalid = p.cout - nb;
@@ -88,11 +101,11 @@ __device__ __forceinline__ void wino14_epilogue(const Wino14Params& p, const f32
 #pragma unroll
     for (int rd = 0; rd < 4; ++rd) {
         const int ml = 32 * wm + 8 * rd + (lane >> 3);
-        const int r = ml / p.Ct, t = ml - r * p.Ct;
+        const int r = ml / tl.Ct, t = ml - r * tl.Ct;
         const int gg = tl.g0 + r;
-        const int b = gg / hp2;
-        const int y = gg - b * hp2 - 1;
-        const bool rowok = r < p.R && gg < p.gtot && y >= 0 && y < p.H && nvalid > 0;
+        const int b = gg / hp;
+        const int y = gg - b * hp - 1;
+        const bool rowok = r < tl.R && gg < p.gtot && y >= 0 && y < p.H && nvalid > 0;
         oxe[rd] = rowok ? 4 * (tl.t0 + t) : p.W;
         pix0[rd] = (b * p.H + y) * p.W + 4 * (tl.t0 + t);
     }
