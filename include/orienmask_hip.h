@@ -544,6 +544,28 @@ int om_cocoeval_match(int n_groups, const int32_t* dt_first, const int32_t* gt_f
                       const int64_t* gt_id, const double* area_rng, const double* iou_thrs, int n_dt_total, int n_gt_total,
                       uint8_t* gt_matched, int64_t* dt_match, uint8_t* dt_ignore, om_stream stream);
 
+/* ---- Ground-truth segmentations decoded on the device (orienmask_amd/augment.py, samples that carry 'segm'; the reference's
+ * data/dataset.py:89-100 calls pycocotools' frPyObjects / merge / decode per annotation in the loader worker).
+ * om_segm_decode turns the sources of n_masks masks (0 ... 65535) into row-packed bits, the layout om_augment reads and
+ *   np.packbits(mask > 0, axis=1) produces: mask m is mask_hw[2m] * ceil(mask_hw[2m+1] / 8) bytes at out + mask_out_off[m],
+ *   row-major, bit 7 - (x & 7) of byte x >> 3 of a row holds column x, the pad bits of a row's last byte are zero.  Every byte
+ *   of every mask is written exactly once (`out` needs no clearing) and no byte outside the masks is touched; neither `out`, the
+ *   offsets nor ceil(w / 8) need any alignment.
+ *   The source tables are om_cocoeval_masks': source s has src_kind (0 polygon, 1 uint32 counts, 2 string bytes), src_mask,
+ *   src_data_off / src_len into poly / counts / strings and src_word_off, the word offset of ITS OWN bitmap in the workspace
+ *   (w * ceil(h / 32) words each; bitmap_words = their sum); sources [0, n_poly) are the polygons (at most 4096 vertices each).
+ *   Mask m is the OR (maskUtils.merge) of the bitmaps at the words mask_src_word_off[mask_src_first[m] .. mask_src_first[m+1]);
+ *   a mask without sources is all zeros.  Every array is a caller-allocated DEVICE buffer.
+ *   workspace: om_segm_decode_workspace_bytes(bitmap_words, n_masks) bytes, 4-byte aligned, contents undefined on entry.
+ *   All launches go to `stream`; nothing is allocated, nothing synchronises; the bytes are identical from call to call (the
+ *   toggles are XORed in with atomics, and XOR commutes; the pack kernel has none).  n_masks == 0 returns OM_OK at once. */
+size_t om_segm_decode_workspace_bytes(long long bitmap_words, int n_masks);
+int om_segm_decode(int n_masks, const int32_t* mask_hw, const int32_t* mask_src_first, const int64_t* mask_src_word_off,
+                   const int64_t* mask_out_off, int n_poly, int n_srcs, const int32_t* src_kind, const int32_t* src_mask,
+                   const int64_t* src_data_off, const int32_t* src_len, const int64_t* src_word_off, const double* poly,
+                   const uint32_t* counts, const uint8_t* strings, long long bitmap_words, void* workspace, size_t ws_bytes,
+                   uint8_t* out, om_stream stream);
+
 /* ---- unit-test entry: the elementary functions the decode uses, restated bit-exactly from what torch-CPU runs at the
  * reference's call sites eval/orienmask_yolo_postprocess.py:127-136 (csrc/ref_math.h).  func: 0 = glibc expf (torch's
  * scalar loop), 1 = Sleef expf_u10 (torch's vectorised loop), 2 / 3 = sigmoid through either, 4 = sigmoid of a

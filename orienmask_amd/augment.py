@@ -5,13 +5,16 @@
   collate(batch)             /root/reference/data/collate.py:13-30, host half: one contiguous buffer per kind + the parameter table
   to_device(planned, device) the device half: three H2D copies and one launch set (om_augment, csrc/augment.hip); returns what
                              the reference's collate returns -- (image, (bbox, cls, index, mask), info) -- on the device
+                             (samples that carry 'segm': a fourth copy and om_segm_decode, csrc/segm_decode.hip, in front)
   device_batches(loader, device)
 
 ``COCOTransform.__call__`` runs in the DataLoader worker and touches no pixel.  It consumes the reference's random draws in the
 reference's order, with the reference's expressions and numpy dtypes, computes bbox / cls / info exactly as the reference does, and
 returns the SOURCE image (uint8 when that is exact: the dataset's float32 image is cv2's uint8 decode cast up), the source masks
 bit-packed per row, and a small parameter record.  The kernels then do every pixel of ColorJitter -> RandomCrop -> Resize -> flips
--> ToTensor -> Normalize in one pass over the output.  Pipelines outside "the shipped order, any subset of it" raise
+-> ToTensor -> Normalize in one pass over the output.  A sample may carry its masks as 'segm' instead of 'mask': the annotation
+json's own objects (polygons, boxes, RLE), one per GT.  Then the worker ships those few numbers, the device decodes them into the
+same packed bits (om_segm_decode) and everything behind is unchanged.  Pipelines outside "the shipped order, any subset of it" raise
 NotImplementedError, as ShortEdgeResize, Pad, collate_plus and the aspect-ratio-grouped loader do.
 """
 import ctypes
@@ -21,6 +24,7 @@ import numpy as np
 import torch
 
 from . import lib as _lib
+from . import segm as _segm
 
 # om_aug_sample (include/orienmask_hip.h)
 AUG_SAMPLE_DTYPE = np.dtype([("image_off", "<i8"), ("mask_off", "<i8"), ("scale_x", "<f8"), ("scale_y", "<f8"),
@@ -267,11 +271,15 @@ class COCOTransform:
     def __call__(self, sample):
         """sample: COCODataset._load_sample_data's dict (image [h,w,3] float32 or uint8 RGB, bbox, cls, optional mask list and
         info).  Returns the planned sample: bbox / cls tensors and info as the reference's pipeline leaves them, the source image,
-        the packed masks and the parameter record 'aug'."""
+        the packed masks and the parameter record 'aug'.  Instead of 'mask' the sample may carry 'segm': one entry per GT, each
+        what the annotation json holds (a list of polygons or of 4-number boxes, or a dict with 'size' and list or string
+        'counts'); the planned sample then carries the classified sources as flat arrays (segm.pack_sources), no pixel."""
         image = sample['image']
         if not isinstance(image, np.ndarray) or image.ndim != 3 or image.shape[2] != 3 or image.dtype not in (np.float32, np.uint8):
             raise ValueError("COCOTransform: image must be an [h,w,3] float32 or uint8 array, got %s"
                              % (getattr(image, 'shape', type(image)),))
+        if 'mask' in sample and 'segm' in sample:
+            raise ValueError("COCOTransform: a sample carries its masks as 'mask' or as 'segm', not both")
         st = _PlanState(sample)
         for t in self.pipeline:
             t(st)
@@ -283,6 +291,18 @@ class COCOTransform:
                     raise ValueError("COCOTransform: mask of shape %s for an image of %s" % (m.shape, image.shape[:2]))
             h, w = image.shape[:2]
             out['mask'] = np.packbits(np.stack(masks) > 0, axis=2) if len(masks) else np.zeros((0, h, (w + 7) // 8), np.uint8)
+        if 'segm' in sample:
+            segm = sample['segm']
+            if len(segm) != len(sample['bbox']):
+                raise ValueError("COCOTransform: %d segmentations for %d boxes" % (len(segm), len(sample['bbox'])))
+            h, w = image.shape[:2]
+            srcs = []
+            for a in segm:
+                mh, mw, lst = _segm.sources(a, h, w)
+                if (mh, mw) != (h, w):
+                    raise ValueError("COCOTransform: RLE of size %s for an image of %s" % ((mh, mw), (h, w)))
+                srcs.append(lst)
+            out['segm'] = _segm.pack_sources(srcs)
         if st.info is not None:
             out['info'] = st.info
         out['aug'] = st.record()
@@ -355,19 +375,26 @@ def _align(n, a=16):
 
 class PlannedBatch:
     """collate()'s result: host buffers (pinnable) and the layout of the meta buffer.  DataLoader(pin_memory=True) calls
-    pin_memory()."""
+    pin_memory().  A batch of 'segm' samples has an empty `mask` and, in `segm`, the arrays of om_segm_decode at the byte ranges
+    of `segm_layout`; `segm_counts` holds n_poly, n_srcs, bitmap_words and mask_bytes, the size of the device scratch that the
+    samples' mask_off point into."""
 
-    def __init__(self, image, mask, meta, layout, B, N, out_hw, mean, std, any_contrast, has_mask, info):
+    def __init__(self, image, mask, meta, layout, B, N, out_hw, mean, std, any_contrast, has_mask, info, segm=None,
+                 segm_layout=None, segm_counts=None):
         self.image, self.mask, self.meta, self.layout = image, mask, meta, layout
         self.B, self.N, self.out_hw, self.mean, self.std = B, N, out_hw, mean, std
         self.any_contrast, self.has_mask, self.info = any_contrast, has_mask, info
+        self.segm, self.segm_layout, self.segm_counts = segm, segm_layout, segm_counts
 
     def pin_memory(self, device=None):
         self.image, self.mask, self.meta = (t if t.is_pinned() else t.pin_memory() for t in (self.image, self.mask, self.meta))
+        if self.segm is not None and not self.segm.is_pinned():
+            self.segm = self.segm.pin_memory()
         return self
 
     def h2d_bytes(self):
-        return {"image": self.image.numel() * self.image.element_size(), "mask": self.mask.numel(), "meta": self.meta.numel()}
+        return {"image": self.image.numel() * self.image.element_size(), "mask": self.mask.numel(), "meta": self.meta.numel(),
+                "segm": self.segm.numel() if self.segm is not None else 0}
 
 
 def collate(batch):
@@ -385,6 +412,11 @@ def collate(batch):
     norms = {(tuple(s['aug']['mean']), tuple(s['aug']['std'])) for s in batch}
     if len(norms) != 1:
         raise ValueError("collate: samples of one batch were normalised differently")
+    has_segm = any('segm' in s for s in batch)
+    if has_segm and any('mask' in s for s in batch):
+        raise ValueError("collate: a batch carries its masks as 'mask' or as 'segm', not a mixture")
+    if has_segm and not all('segm' in s for s in batch):
+        raise ValueError("collate: some samples have segmentations and some do not")
     has_mask = 'mask' in batch[0]
     if any(('mask' in s) != has_mask for s in batch):
         raise ValueError("collate: some samples have masks and some do not")
@@ -395,6 +427,7 @@ def collate(batch):
     rows = np.zeros(B, AUG_SAMPLE_DTYPE)
     gt_table = np.zeros((N, 2), np.int32)
     image_off = mask_off = gt_first = 0
+    segm_masks, segm_out_off = [], []
     for b, s in enumerate(batch):
         aug = s['aug']
         h, w = aug['src_h'], aug['src_w']
@@ -411,6 +444,12 @@ def collate(batch):
             raise ValueError("collate: permutation of image %d is not a permutation of its %d GTs" % (b, n_gt[b]))
         if has_mask and s['mask'].shape != (n_gt[b], h, (w + 7) // 8):
             raise ValueError("collate: packed masks of image %d are %s, want %s" % (b, s['mask'].shape, (n_gt[b], h, (w + 7) // 8)))
+        if has_segm:
+            if int(s['segm']['n_gt']) != n_gt[b]:
+                raise ValueError("collate: %d segmentations for the %d GTs of image %d" % (int(s['segm']['n_gt']), n_gt[b], b))
+            for g, lst in enumerate(_segm.unpack_sources(s['segm'])):
+                segm_masks.append((h, w, lst))
+                segm_out_off.append(mask_off + g * h * ((w + 7) // 8))
         rows[b] = sample_row(aug, image_off, mask_off, gt_first, n_gt[b])
         gt_table[gt_first:gt_first + n_gt[b], 0] = gt_first + perm       # output GT gt_first + i holds source GT perm[i]
         gt_table[gt_first:gt_first + n_gt[b], 1] = b
@@ -434,8 +473,21 @@ def collate(batch):
     any_contrast = any(code == CONTRAST for s in batch for code, _ in s['aug']['ops'])
     mean, std = norms.pop()
     info = [s['info'] for s in batch] if 'info' in batch[0] else None
-    return PlannedBatch(image, mask, torch.from_numpy(meta), layout, B, N, outs.pop(), list(mean), list(std), any_contrast, has_mask,
-                        info)
+    segm = segm_layout = segm_counts = None
+    if has_segm:
+        tables, segm_counts = _segm.build_tables(segm_masks, segm_out_off)
+        segm_counts["mask_bytes"] = mask_off
+        segm_layout, off = {}, 0
+        for name in _segm.TABLE_ORDER:
+            nbytes = tables[name].size * tables[name].itemsize
+            segm_layout[name] = (off, nbytes)
+            off = _align(off + nbytes)
+        buf = np.zeros(off, np.uint8)
+        for name in _segm.TABLE_ORDER:
+            buf[segm_layout[name][0]:segm_layout[name][0] + segm_layout[name][1]] = tables[name].view(np.uint8)
+        segm = torch.from_numpy(buf)
+    return PlannedBatch(image, mask, torch.from_numpy(meta), layout, B, N, outs.pop(), list(mean), list(std), any_contrast,
+                        has_mask or has_segm, info, segm, segm_layout, segm_counts)
 
 
 def _meta_view(meta, layout, name, dtype, shape):
@@ -445,7 +497,8 @@ def _meta_view(meta, layout, name, dtype, shape):
 
 def to_device(planned, device):
     """Device half of collate: three H2D copies (non-blocking, from pinned memory) and one launch set on the current stream; no
-    D2H, no host synchronisation.  Returns (image [B,3,H,W] f32, (bbox [N,4] f32, cls [N] i64, index [B+1] i64[, mask [N,H,W]
+    D2H, no host synchronisation.  A batch of 'segm' samples takes one more copy (the source tables), and om_segm_decode fills a
+    scratch with the packed masks that the 'mask' path would have copied; om_augment then reads that scratch.  Returns (image [B,3,H,W] f32, (bbox [N,4] f32, cls [N] i64, index [B+1] i64[, mask [N,H,W]
     bool])[, info]) -- the reference collate's tuple, every tensor on `device`."""
     device = torch.device(device)
     if device.type != "cuda":
@@ -457,6 +510,8 @@ def to_device(planned, device):
         meta = planned.meta.to(device, non_blocking=True)
         image = planned.image.to(device, non_blocking=True)
         masks = planned.mask.to(device, non_blocking=True)
+        if planned.segm is not None and N:
+            masks = _segm_decode(planned, device)
         out_image = torch.empty((B, 3, H, W), dtype=torch.float32, device=device)
         out_mask = torch.empty((N, H, W), dtype=torch.bool, device=device)
         ws = None
@@ -482,6 +537,28 @@ def to_device(planned, device):
     if planned.info is not None:
         return out_image, anno, planned.info
     return out_image, anno
+
+
+def _segm_decode(planned, device):
+    """the packed masks of a 'segm' batch, decoded on the current stream into a fresh scratch"""
+    L = _lib.load()
+    c = planned.segm_counts
+    tables = planned.segm.to(device, non_blocking=True)
+    scratch = torch.empty(c["mask_bytes"], dtype=torch.uint8, device=device)
+    ws_bytes = int(L.om_segm_decode_workspace_bytes(c["bitmap_words"], planned.N))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
+
+    def ptr(name):
+        off, nbytes = planned.segm_layout[name]
+        return ctypes.c_void_p(tables.data_ptr() + off) if nbytes else None
+
+    rc = L.om_segm_decode(planned.N, ptr("mask_hw"), ptr("mask_src_first"), ptr("mask_src_word_off"), ptr("mask_out_off"),
+                          c["n_poly"], c["n_srcs"], ptr("src_kind"), ptr("src_mask"), ptr("src_data_off"), ptr("src_len"),
+                          ptr("src_word_off"), ptr("poly"), ptr("counts"), ptr("strings"), c["bitmap_words"],
+                          ctypes.c_void_p(ws.data_ptr() if ws_bytes else None), ws_bytes, ctypes.c_void_p(scratch.data_ptr()),
+                          _lib.current_stream_ptr(device))
+    _lib.check(rc, "om_segm_decode")
+    return scratch
 
 
 def device_batches(loader, device):

@@ -30,6 +30,7 @@ import numpy as np
 import torch
 
 from . import lib as _lib
+from .segm import COUNTS as _COUNTS, MAX_POLY_VERTICES, POLY as _POLY, STRING as _STRING, sources as _sources  # noqa: F401
 
 IOU_THRS = np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True)
 REC_THRS = np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=True)
@@ -37,40 +38,7 @@ MAX_DETS = [1, 10, 100]
 AREA_RNG = [[0 ** 2, 1e5 ** 2], [0 ** 2, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e5 ** 2]]
 AREA_LBL = ["all", "small", "medium", "large"]
 METRIC_KEYS = ["AP", "AP50", "AP75", "APS", "APM", "APL", "AR1", "AR10", "AR100", "ARS", "ARM", "ARL"]
-MAX_POLY_VERTICES = 4096        # csrc/cocoeval.hip: COCO_MAX_POLY
 DEFAULT_MAX_BYTES = 1 << 30
-
-_POLY, _COUNTS, _STRING = 0, 1, 2
-
-
-def _sources(segm, h, w):
-    """One annotation's segmentation -> (mask h, mask w, [(kind, data)]) as pycocotools' annToRLE reads it."""
-    if isinstance(segm, list):
-        if len(segm) == 0:
-            raise ValueError("empty segmentation list")
-        if len(segm[0]) == 4:                       # frPyObjects: a list of boxes -> rleFrBbox
-            out = []
-            for b in segm:
-                xs, ys, bw, bh = (float(v) for v in b)
-                xe, ye = xs + bw, ys + bh
-                out.append((_POLY, np.array([xs, ys, xs, ye, xe, ye, xe, ys], dtype=np.float64)))
-            return h, w, out
-        if len(segm[0]) < 4:
-            raise ValueError("segmentation polygon with fewer than 4 numbers")
-        out = []
-        for p in segm:
-            a = np.asarray(p, dtype=np.float64)
-            if a.size // 2 > MAX_POLY_VERTICES:
-                raise ValueError("polygon with %d vertices (at most %d)" % (a.size // 2, MAX_POLY_VERTICES))
-            out.append((_POLY, a))
-        return h, w, out
-    rh, rw = int(segm["size"][0]), int(segm["size"][1])
-    counts = segm["counts"]
-    if isinstance(counts, list):
-        return rh, rw, [(_COUNTS, np.asarray(counts, dtype=np.uint32))]
-    if isinstance(counts, bytes):
-        counts = counts.decode("ascii")
-    return rh, rw, [(_STRING, counts.encode("ascii"))]
 
 
 class COCOGroundTruth:

@@ -330,6 +330,33 @@ __global__ __launch_bounds__(64) void coco_match_kernel(int n_groups, const int3
     }
 }
 
+// Stage 1 of every mask builder (om_cocoeval_masks here, om_segm_decode in segm_decode.hip): the bitmaps zeroed, every source's
+// toggles XORed in, then the prefix XOR -- after it the bitmap at src_word_off[s] is source s's mask.  Sources [0, n_poly) are the
+// polygons.  The caller has checked the tables' pointers.
+int launch_coco_raster(const char* who, int n_poly, int n_srcs, const int32_t* src_kind, const int32_t* src_mask,
+                       const int64_t* src_data_off, const int32_t* src_len, const int64_t* src_word_off, const int32_t* mask_hw,
+                       const double* poly, const uint32_t* counts, const uint8_t* strings, uint32_t* bitmaps, long long bitmap_words,
+                       hipStream_t st) {
+    OM_CHECK_HIP(hipMemsetAsync(bitmaps, 0, (size_t)bitmap_words * 4, st));
+    if (n_poly > 0) {
+        OM_REQUIRE(poly, OM_EINVAL, "%s: polygons without coordinates", who);
+        hipLaunchKernelGGL(coco_poly_toggle_kernel, dim3(n_poly), dim3(64), 0, st, src_mask, src_data_off, src_len, src_word_off,
+                           mask_hw, poly, bitmaps);
+        OM_CHECK_HIP(hipGetLastError());
+    }
+    if (n_srcs > n_poly) {
+        const int n = n_srcs - n_poly;
+        hipLaunchKernelGGL(coco_seq_toggle_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n_poly, n, src_kind, src_mask,
+                           src_data_off, src_len, src_word_off, mask_hw, counts, strings, bitmaps);
+        OM_CHECK_HIP(hipGetLastError());
+    }
+    if (n_srcs > 0) {
+        hipLaunchKernelGGL(coco_scan_kernel, dim3(n_srcs), dim3(COCO_SCAN_THREADS), 0, st, src_mask, src_word_off, mask_hw, bitmaps);
+        OM_CHECK_HIP(hipGetLastError());
+    }
+    return OM_OK;
+}
+
 }  // namespace om
 
 
@@ -355,24 +382,9 @@ int om_cocoeval_masks(int n_masks, const int32_t* mask_hw, const int64_t* mask_w
     hipStream_t st = static_cast<hipStream_t>(stream);
     uint32_t* bitmaps = static_cast<uint32_t*>(workspace);
     int32_t* stats = reinterpret_cast<int32_t*>(static_cast<char*>(workspace) + om::align_up((size_t)bitmap_words * 4, 256));
-    OM_CHECK_HIP(hipMemsetAsync(bitmaps, 0, (size_t)bitmap_words * 4, st));
-    if (n_poly > 0) {
-        OM_REQUIRE(poly, OM_EINVAL, "om_cocoeval_masks: polygons without coordinates");
-        hipLaunchKernelGGL(om::coco_poly_toggle_kernel, dim3(n_poly), dim3(64), 0, st, src_mask, src_data_off, src_len,
-                           src_word_off, mask_hw, poly, bitmaps);
-        OM_CHECK_HIP(hipGetLastError());
-    }
-    if (n_srcs > n_poly) {
-        const int n = n_srcs - n_poly;
-        hipLaunchKernelGGL(om::coco_seq_toggle_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n_poly, n, src_kind, src_mask,
-                           src_data_off, src_len, src_word_off, mask_hw, counts, strings, bitmaps);
-        OM_CHECK_HIP(hipGetLastError());
-    }
-    if (n_srcs > 0) {
-        hipLaunchKernelGGL(om::coco_scan_kernel, dim3(n_srcs), dim3(om::COCO_SCAN_THREADS), 0, st, src_mask, src_word_off, mask_hw,
-                           bitmaps);
-        OM_CHECK_HIP(hipGetLastError());
-    }
+    const int rc = om::launch_coco_raster("om_cocoeval_masks", n_poly, n_srcs, src_kind, src_mask, src_data_off, src_len, src_word_off,
+                                          mask_hw, poly, counts, strings, bitmaps, bitmap_words, st);
+    if (rc != OM_OK) return rc;
     hipLaunchKernelGGL(om::coco_merge_kernel, dim3(n_masks), dim3(om::COCO_MERGE_THREADS), 0, st, mask_hw, mask_word_off,
                        mask_src_first, mask_src_word_off, bitmaps, stats);
     OM_CHECK_HIP(hipGetLastError());

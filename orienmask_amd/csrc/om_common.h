@@ -170,6 +170,12 @@ bool wino_fused_for(int cin);     // true: the input transform is fused into the
 // Clears n 32-bit words with a kernel.  The library never uses hipMemsetAsync: a memset node captured
 // into a hipGraph was observed (ROCm 7.2, DESIGN.md "hipGraph") to leave part of the range uncleared on replay.
 int launch_zero_words(void* ptr, size_t n_words, hipStream_t stream);
+// cocoeval.hip: stage 1 of the COCO mask builders, shared with segm_decode.hip -- zero the bitmaps, XOR every source's toggles in
+// (polygons: sources [0, n_poly); counts and strings behind them), prefix XOR.  `who` names the caller in error messages.
+int launch_coco_raster(const char* who, int n_poly, int n_srcs, const int32_t* src_kind, const int32_t* src_mask,
+                       const int64_t* src_data_off, const int32_t* src_len, const int64_t* src_word_off, const int32_t* mask_hw,
+                       const double* poly, const uint32_t* counts, const uint8_t* strings, uint32_t* bitmaps, long long bitmap_words,
+                       hipStream_t stream);
 int launch_conv_stem(const float* in_nchw, int B, int H, int W, const float* w, const float* scale,
                      const float* shift, int cout, float* out_nhwc, hipStream_t stream);
 

@@ -180,6 +180,8 @@ SIGNATURES = {
     "om_cocoeval_mask_iou": (_i, [_i, _vp, _vp, _i, _vp, _vp, ctypes.c_longlong, _vp, _vp, _vp]),
     "om_cocoeval_bbox_iou": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "om_cocoeval_match": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "om_segm_decode_workspace_bytes": (_sz, [ctypes.c_longlong, _i]),
+    "om_segm_decode": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _vp, _sz, _vp, _vp]),
     "om_post_kernel_occupancy": (_i, [_i, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "om_nms_workspace_bytes": (_sz, [_i]),
     "om_nms": (_i, [_vp, _i, _f, _vp, _vp, _vp, _sz, _vp]),

@@ -478,3 +478,60 @@ def synth_coco_sample(seed, height, width, n_gt, border=False, with_info=True, i
     if with_info:
         sample["info"] = {"id": image_id, "height": height, "width": width}
     return sample
+
+
+def synth_segm_sample(seed, height, width, n_gt, crowd=False, with_info=True, image_id=0):
+    """synth_coco_sample's sample with its masks as the annotation json would hold them ('segm', no pixel): each GT is 1-3
+    polygons of 20-200 vertices (wobbly ellipses, coordinates rounded to 2 decimals as COCO's are), except that with crowd=True
+    the last GT is an uncompressed RLE ({'size', 'counts'}) of a few blobs, as COCO stores iscrowd annotations.  The image is
+    uint8; bbox is the polygons' extent clipped to the image."""
+    rng = _rng(seed)
+    image = rng.integers(0, 256, (height, width, 3), dtype=np.uint8)
+    boxes, segm = [], []
+    for k in range(n_gt):
+        cx, cy = rng.uniform(0.15, 0.85) * width, rng.uniform(0.15, 0.85) * height
+        rx, ry = rng.uniform(0.05, 0.3) * width, rng.uniform(0.05, 0.3) * height
+        if crowd and k == n_gt - 1:
+            yy, xx = np.mgrid[0:height, 0:width]
+            m = np.zeros((height, width), bool)
+            for _ in range(4):
+                ox, oy = rng.uniform(-rx, rx), rng.uniform(-ry, ry)
+                m |= ((xx - cx - ox) / (rx / 2)) ** 2 + ((yy - cy - oy) / (ry / 2)) ** 2 <= 1.0
+            flat = m.T.ravel()
+            edges = np.flatnonzero(np.diff(flat)) + 1
+            runs = np.diff(np.concatenate([[0], edges, [flat.size]])).tolist()
+            segm.append({"size": [height, width], "counts": ([0] if flat[0] else []) + [int(r) for r in runs]})
+            ys, xs = np.nonzero(m)
+            x0, x1, y0, y1 = (xs.min(), xs.max() + 1, ys.min(), ys.max() + 1) if len(xs) else (0, 1, 0, 1)
+        else:
+            polys = []
+            for _ in range(int(rng.integers(1, 4))):
+                n = int(rng.integers(20, 201))
+                a = np.sort(rng.uniform(0, 2 * np.pi, n))
+                r = 1 + 0.25 * np.sin(3 * a + rng.uniform(0, 6)) + rng.uniform(-0.1, 0.1, n)
+                ox, oy = rng.uniform(-0.5, 0.5) * rx, rng.uniform(-0.5, 0.5) * ry
+                x = np.clip(cx + ox + 0.6 * rx * r * np.cos(a), 0, width)
+                y = np.clip(cy + oy + 0.6 * ry * r * np.sin(a), 0, height)
+                polys.append(np.round(np.stack([x, y], 1).ravel(), 2).tolist())
+            segm.append(polys)
+            allx = np.concatenate([np.asarray(p)[0::2] for p in polys])
+            ally = np.concatenate([np.asarray(p)[1::2] for p in polys])
+            x0, x1, y0, y1 = allx.min(), allx.max(), ally.min(), ally.max()
+        boxes.append([(x0 + x1) / 2 / width, (y0 + y1) / 2 / height, max(x1 - x0, 1) / width, max(y1 - y0, 1) / height])
+    sample = {"image": image, "bbox": np.array(boxes, np.float32).reshape(-1, 4),
+              "cls": rng.integers(0, 80, n_gt).astype(np.int64), "segm": segm}
+    if with_info:
+        sample["info"] = {"id": image_id, "height": height, "width": width}
+    return sample
+
+
+def synth_segm_batch(seed=0, batch=32, height=480, width=640, mean_gt=7, crowd_every=4):
+    """A batch of COCO-like proportions for tools/bench_segm_decode.py: `batch` sources of height x width with about mean_gt GTs
+    each (Poisson, at least 0) and one crowd RLE in every crowd_every-th image."""
+    rng = _rng(seed)
+    out = []
+    for b in range(batch):
+        n = int(rng.poisson(mean_gt))
+        crowd = crowd_every > 0 and b % crowd_every == crowd_every - 1 and n > 0
+        out.append(synth_segm_sample(1000 * seed + b, height, width, n, crowd=crowd, image_id=b))
+    return out

@@ -1,5 +1,6 @@
 """Drop-in for the reference's GPU preprocessing and, from augment.py, its training / validation
-data pipeline (COCOTransform, collate, to_device, device_batches: SURVEY.md row 14).
+data pipeline (COCOTransform, collate, to_device, device_batches: SURVEY.md row 14) and, from dataset.py, the datasets that feed it
+(BaseDataset, COCODataset, VOCDataset; DataLoader is torch's): what trainer/builder.py:91-105 resolves against its data module.
 
   FastCOCOTransform(pipeline, use_cuda)   /root/reference/data/transform.py:444-510
   pad(image, size_divisor=32, pad_value=0) /root/reference/infer.py:21-32
@@ -18,6 +19,8 @@ import torch
 
 from . import lib as _lib
 from .augment import COCOTransform, collate, device_batches, to_device  # noqa: F401  (build_transform resolves names here)
+from .dataset import BaseDataset, COCODataset, VOCDataset  # noqa: F401  (build(dataset_config, module) resolves names here)
+from torch.utils.data import DataLoader  # noqa: F401  (as the reference's data/__init__.py exports it)
 
 
 def _pair(v):
