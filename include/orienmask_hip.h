@@ -661,6 +661,41 @@ int om_loss_backward(const om_loss_cfg* cfg, const float* const* bbox, const flo
                      const float* grad_out, const float* scales_weight, float* const* grad_bbox, float* const* grad_orien,
                      om_stream stream);
 
+/* ---- The loop's per-step bookkeeping on the device: what orienmask_amd/loss.py's _finish (eval/base.py:90-121) and
+ *      EvalCounter.update (eval/counter.py) do on the host after every om_loss, as ONE launch of one wave, so a training step
+ *      holds no device-to-host copy.  Call it after om_loss on the same stream with that call's `result`.
+ *
+ * Per-step values, float32, every operation rounded once (no fused multiply-add), t = a scale's 7 terms, m = its 8 (numerator,
+ * count) pairs, w = scales_weight, S = num_scales; sums over scales run over s < S only, left to right from the first scale:
+ *      s_k               = (((((t0 + t1) + t2) + t3) + t4) + t5) + t6             the scale sum of scale k
+ *      cross row j       = ((w0 * v0j) + (w1 * v1j)) + (w2 * v2j)                 v_kj = t_kj for j < 7, s_k for j = 7
+ *      loss_sum          = ((w0 * s0) + (w1 * s1)) + (w2 * s2)                    (= cross row 7)
+ *      cross metric j    = ((n0j + n1j) + n2j, (c0j + c1j) + c2j)                 numerators and counts summed separately
+ *
+ * The counter block (device, OM_COUNTER_BLOCK_DOUBLES float64, caller-owned, zeroed by the caller before the first call): one
+ * (sum, items) pair per key at OM_COUNTER_STAGE_OFF + 2 * key; the keys are 'loss', then per scale its 7 terms and scale sum,
+ * then the 8 cross-scale rows, then per scale its 8 metrics, then the 8 cross-scale metrics: 1 + 16 * (S + 1) keys, packed.
+ * 'loss' and the loss keys add (double(value), 1); the metric keys add (double(numerator), double(count)) and only when
+ * with_metrics != 0 (the reference's metric_log is empty for training=True).  The pairs at OM_COUNTER_EPOCH_OFF belong to the
+ * caller (orienmask_amd.loss.DeviceEvalCounter folds the stage into them); the kernel never touches them.
+ * Two int64 words behind the pairs latch status: at OM_COUNTER_FLAG_OFF the OR of every call's OM_LOSS_FLAG_* bits and of
+ * OM_COUNTER_FLAG_NONFINITE_LOSS (this call's loss_sum is not finite); at OM_COUNTER_STEP_OFF the `step` argument of the first
+ * call that set any bit, which later calls never overwrite.  The sums are added whatever the flags say.
+ * `loss_sum` (device float, caller-owned) receives this call's loss_sum.  No allocation, no host synchronisation, no atomics;
+ * bit-identical from run to run.
+ * Pointers: `result`, `counter` and `loss_sum` are DEVICE pointers (4-, 8- and 4-byte aligned).  `scales_weight` is a HOST
+ * array of num_scales floats: the launcher reads it before the launch and passes the values to the kernel by value, so the
+ * caller may free or change it as soon as the call returns. */
+#define OM_COUNTER_MAX_KEYS (1 + 2 * (OM_MAX_SCALES + 1) * OM_LOSS_METRICS)
+#define OM_COUNTER_STAGE_OFF 0
+#define OM_COUNTER_EPOCH_OFF (2 * OM_COUNTER_MAX_KEYS)
+#define OM_COUNTER_FLAG_OFF (4 * OM_COUNTER_MAX_KEYS)
+#define OM_COUNTER_STEP_OFF (OM_COUNTER_FLAG_OFF + 1)
+#define OM_COUNTER_BLOCK_DOUBLES (OM_COUNTER_FLAG_OFF + 2)
+#define OM_COUNTER_FLAG_NONFINITE_LOSS 256
+int om_loss_accumulate(const float* result, int num_scales, const float* scales_weight, int with_metrics, long long step,
+                       double* counter, float* loss_sum, om_stream stream);
+
 /* ---- Training / validation augmentation: COCOTransform + collate (data/transform.py:65-441, data/collate.py:13-30 of the
  *      reference; orienmask_amd/augment.py plans every random draw on the host, these kernels do the pixel work).
  *      One record per image, in DEVICE memory; every offset and window in it was checked by the host planner.  Per output pixel:

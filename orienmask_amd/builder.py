@@ -1,4 +1,4 @@
-"""The reference's type-keyed registry for the inference path, and the optimizer of the training path.
+"""The reference's type-keyed registry for the inference path, and the builders of the training path up to ``build_trainer``.
 
 Mirrors /root/reference/trainer/builder.py:61-77: ``build(cfg, module)`` looks ``cfg['type']`` up in a
 module and calls it with the remaining keys; ``build_postprocess`` pops ``nms`` and injects the bound
@@ -115,3 +115,68 @@ def build_train_model(config, is_distributed=False, ignore_pretrained=False):
         from torch.nn.parallel import DistributedDataParallel
         net = DistributedDataParallel(_train.convert_sync_batchnorm(net), device_ids=[dev.index])
     return net
+
+
+class DeviceLoader:
+    """A DataLoader whose collate is orienmask_amd.transform.collate, seen as the loader the epoch loops expect: iterating it
+    yields the reference collate's tuples on `device` (transform.device_batches); ``len``, ``dataset``, ``sampler`` and
+    ``batch_size`` are the DataLoader's."""
+
+    def __init__(self, loader, device):
+        self.loader, self.device = loader, device
+        self.dataset, self.sampler, self.batch_size = loader.dataset, getattr(loader, "sampler", None), loader.batch_size
+
+    def __len__(self):
+        return len(self.loader)
+
+    def __iter__(self):
+        from . import transform as _transform
+        return _transform.device_batches(self.loader, self.device)
+
+
+def build_dataloader(config, device, is_distributed=False):
+    """trainer/builder.py:91-105 against orienmask_amd.transform: the transform (COCOTransform), the dataset (COCODataset /
+    VOCDataset), the collate (`collate`, the default) and torch's DataLoader, wrapped in a DeviceLoader; with is_distributed a
+    DistributedSampler replaces `shuffle`.  The caller's dicts are not mutated."""
+    import copy
+    from . import transform as _transform
+    cfg = copy.deepcopy(config)
+    dataset_cfg = cfg.pop("dataset")
+    dataset = build(dataset_cfg, _transform, transform=_transform.build_transform(cfg.pop("transform")))
+    collate_fn = build_func_partial(cfg.pop("collate", {"type": "collate"}), _transform)
+    if is_distributed:
+        from torch.utils.data.distributed import DistributedSampler
+        cfg["sampler"] = DistributedSampler(dataset, shuffle=cfg.pop("shuffle", False))
+    return DeviceLoader(build(cfg, _transform, dataset=dataset, collate_fn=collate_fn), device)
+
+
+def build_trainer(config, args, device, train_loader=None, sync_free=None):
+    """trainer/builder.py:22-40 on the HIP path: seeds, loaders, postprocess, the training model, the loss with a backward
+    (orienmask_amd.train), the optimizer (lr / accumulate), the scheduler and ``orienmask_amd.trainer.<config['trainer']>``.
+    `args` carries ``resume`` and ``weights`` (either makes the model ignore ``pretrained``).  `train_loader`: use this
+    loader instead of building config['train_loader'] (tools/train.py --synthetic); a config without a 'val_loader' entry trains
+    without validation; `sync_free` is passed to the trainer."""
+    import random
+    import numpy as np
+    import torch
+    from . import optim as _optim
+    from . import train as _train
+    from . import trainer as _trainer
+    from .dist import world_info
+    random.seed(config["seed"])
+    np.random.seed(config["seed"])
+    torch.manual_seed(config["seed"])
+    torch.cuda.manual_seed_all(config["seed"])
+    is_distributed = world_info()[1] > 1
+    if train_loader is None:
+        train_loader = build_dataloader(config["train_loader"], device, is_distributed)
+    val_loader = build_dataloader(config["val_loader"], device, is_distributed) if config.get("val_loader") else None
+    postprocess = build_postprocess(config["postprocess"], device=device) if config.get("postprocess") else None
+    ignore_pretrained = bool(getattr(args, "resume", None) or getattr(args, "weights", None))
+    model = build_train_model(config["model"], is_distributed, ignore_pretrained)
+    loss = build(config["loss"], _train)
+    optimizer = build_optimizer(config["optimizer"], config["accumulate"], model, is_distributed)
+    lr_scheduler = build(config["lr_scheduler"], _optim, optimizer=optimizer)
+    trainer_type = getattr(_trainer, config.get("trainer", "Trainer"))
+    return trainer_type(model, loss, optimizer, lr_scheduler, config, train_loader, val_loader, postprocess, device, args,
+                        sync_free=sync_free)

@@ -70,6 +70,14 @@ OM_LOSS_RESULT_FLOATS = OM_LOSS_FLAG_OFF + 1
 OM_LOSS_FLAG_NONFINITE_WH = 1
 OM_LOSS_FLAG_TOO_MANY_GT = 2
 OM_LOSS_FLAG_BAD_CLASS = 4
+# include/orienmask_hip.h: the counter block of om_loss_accumulate, in float64 elements (the two status words are int64)
+OM_COUNTER_MAX_KEYS = 1 + 2 * (OM_MAX_SCALES + 1) * OM_LOSS_METRICS
+OM_COUNTER_STAGE_OFF = 0
+OM_COUNTER_EPOCH_OFF = 2 * OM_COUNTER_MAX_KEYS
+OM_COUNTER_FLAG_OFF = 4 * OM_COUNTER_MAX_KEYS
+OM_COUNTER_STEP_OFF = OM_COUNTER_FLAG_OFF + 1
+OM_COUNTER_BLOCK_DOUBLES = OM_COUNTER_FLAG_OFF + 2
+OM_COUNTER_FLAG_NONFINITE_LOSS = 256
 
 
 class LossCfg(ctypes.Structure):
@@ -191,6 +199,7 @@ SIGNATURES = {
     "om_loss": (_i, [ctypes.POINTER(LossCfg), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
     "om_loss_targets": (_i, [ctypes.POINTER(LossCfg), ctypes.POINTER(_vp), _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,
                              _vp, _vp, _vp, _vp, _sz, _vp]),
+    "om_loss_accumulate": (_i, [_vp, _i, ctypes.POINTER(_f), _i, ctypes.c_longlong, _vp, _vp, _vp]),
     "om_augment_workspace_bytes": (_sz, [_i]),
     "om_augment": (_i, [_vp, _i, _vp, _i, ctypes.POINTER(_f), ctypes.POINTER(_f), _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _sz, _vp]),
     "om_loss_backward": (_i, [ctypes.POINTER(LossCfg), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _i, _vp, _vp, _i, _vp, _vp, _sz, _vp,

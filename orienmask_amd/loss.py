@@ -3,6 +3,8 @@
   OrienMaskYOLOMultiScaleLoss  same constructor, attributes and call contract as
                                the reference's eval/orienmask_yolo_loss.py:259-325 with eval/base.py's aggregation
   EvalCounter                  the counter semantics of the reference's eval/counter.py
+  DeviceEvalCounter            the same counter on a device block: ``enqueue`` (below) adds a call's values to it with
+                               ``om_loss_accumulate`` (csrc/loss_counter.hip) and the host reads it when it wants the means
 
 The values come from ``om_loss`` (csrc/loss.hip): four kernel launches for all scales and ONE device-to-host copy per call,
 against the reference's per-image, per-instance Python loops over full-image tensors and dozens of ``.item()`` calls.  The
@@ -16,6 +18,8 @@ Deliberate departures from the reference:
     orientation maps are exactly image / 4 per side.  The GT limit is exercised: tests/test_loss_crowd.py checks values,
     targets and gradients of images with 63 .. 1024 GTs (1025 is refused, tests/test_loss.py);
   * scales_weight=None means ones (the reference reads num_scales before setting it and fails).
+``enqueue(predict, target, counter, step)`` is the deferred form of a call, for a loop that must not stall: om_loss, then
+om_loss_accumulate into a DeviceEvalCounter, and the device scalar loss_sum comes back; nothing is copied to the host.
 Duplicate positives (two GTs on one cell) follow torch-CPU's answer: box targets from the highest GT index, tcls the union of
 their classes (csrc/loss.hip).
 """
@@ -100,6 +104,192 @@ class EvalCounter:
         for key in self.keys:
             self.items_epoch[key] += counter_dict["items_epoch"][key]
             self.counter_epoch[key] += counter_dict["counter_epoch"][key]
+
+
+def _accumulate_torch(block, result, num_scales, scales_weight, with_metrics, step, out):
+    """om_loss_accumulate (include/orienmask_hip.h) in torch ops on the tensors' own device: the comparator of the kernel and
+    what a counter on the CPU runs.  float32 throughout, one rounding per operation, sums left to right."""
+    S, T, SF = num_scales, _lib.OM_LOSS_TERMS, _lib.OM_LOSS_SCALE_FLOATS
+    r = result[:_lib.OM_LOSS_FLAG_OFF].view(_lib.OM_MAX_SCALES, SF)[:S]
+    t = r[:, :T]
+    ssum = t[:, 0]
+    for j in range(1, T):
+        ssum = ssum + t[:, j]
+    v = torch.cat([t, ssum.unsqueeze(1)], 1)                               # [S, 8]: the terms and the scale sum
+    w = torch.tensor(scales_weight[:S], dtype=torch.float32, device=result.device)
+    wv = v * w.unsqueeze(1)
+    cross = wv[0]
+    for s in range(1, S):
+        cross = cross + wv[s]
+    loss_sum = cross[T]
+    values = torch.cat([loss_sum.reshape(1), v.reshape(-1), cross]).double()
+    n_loss = values.numel()
+    pairs = block[_lib.OM_COUNTER_STAGE_OFF:_lib.OM_COUNTER_STAGE_OFF + 2 * n_loss].view(n_loss, 2)
+    pairs[:, 0] += values
+    pairs[:, 1] += 1.0
+    if with_metrics:
+        m = r[:, T:].reshape(S, _lib.OM_LOSS_METRICS, 2)
+        cm = m[0]
+        for s in range(1, S):
+            cm = cm + m[s]
+        mets = torch.cat([m.reshape(-1, 2), cm]).double()
+        off = _lib.OM_COUNTER_STAGE_OFF + 2 * n_loss
+        block[off:off + 2 * mets.shape[0]].view(-1, 2).add_(mets)
+    status = block[_lib.OM_COUNTER_FLAG_OFF:_lib.OM_COUNTER_FLAG_OFF + 2].view(torch.int64)
+    bits = result[_lib.OM_LOSS_FLAG_OFF:].view(torch.int32)[0].to(torch.int64)
+    bits = bits | (~torch.isfinite(loss_sum)).to(torch.int64) * _lib.OM_COUNTER_FLAG_NONFINITE_LOSS
+    first = (status[0] == 0) & (bits != 0)
+    status[1] = torch.where(first, torch.full_like(bits, int(step)), status[1])
+    status[0] |= bits
+    out.copy_(loss_sum)
+    return out
+
+
+class DeviceEvalCounter:
+    """EvalCounter (``average``, ``average_epoch``, ``reset``, ``reset_epoch``, ``keys``) for the keys of one loss, living in a
+    block on `device` (include/orienmask_hip.h: OM_COUNTER_*).  ``accumulate`` -- what ``loss.enqueue`` calls -- adds a call's
+    values on the device (om_loss_accumulate; on a CPU device the same arithmetic in torch ops); the keys are
+    ['loss'] + loss.loss_id + loss.metric_id.
+
+    Every reading method (``average``, ``average_epoch`` and their plural forms ``averages`` / ``averages_epoch``, which answer
+    for many keys from the same copy) does ONE device-to-host copy of the block, calls ``check`` on it and answers with
+    EvalCounter's arithmetic (-1 when there are no items).  ``reset`` / ``reset_epoch`` and the fold of ``average_epoch`` are
+    asynchronous torch ops on the current stream.  The status words are sticky: ``check`` raises what the host path would have
+    raised at the step that latched them, and names that step; ``reset_epoch`` clears them."""
+
+    def __init__(self, loss, device):
+        self.keys = ["loss"] + list(loss.loss_id) + list(loss.metric_id)
+        self.num_scales = int(loss.num_scales)
+        if len(self.keys) != 1 + 2 * (self.num_scales + 1) * _lib.OM_LOSS_METRICS:
+            raise ValueError("a loss of %d scales has %d keys, not %d" % (self.num_scales, 1 + 2 * (self.num_scales + 1)
+                                                                            * _lib.OM_LOSS_METRICS, len(self.keys)))
+        self.num_classes = loss.num_classes
+        self.scales_weight = [float(v) for v in loss.scales_weight]
+        self._w = (ctypes.c_float * _lib.OM_MAX_SCALES)(*(self.scales_weight + [0.0] * (_lib.OM_MAX_SCALES - self.num_scales)))
+        self._index = {k: i for i, k in enumerate(self.keys)}
+        self.device = torch.device(device)
+        self.block = torch.zeros(_lib.OM_COUNTER_BLOCK_DOUBLES, dtype=torch.float64, device=self.device)
+        self.flags, self.first_bad_step = 0, None
+
+    # -- the device side
+    def accumulate(self, result, step, with_metrics=False, out=None):
+        """Add one om_loss result vector (on the counter's device) as step `step`; returns loss_sum, a 0-dim float32 tensor on
+        the device (`out` if given).  No host synchronisation."""
+        if result.device != self.block.device or result.dtype != torch.float32 or result.numel() != _lib.OM_LOSS_RESULT_FLOATS \
+                or not result.is_contiguous():
+            raise ValueError("result must be om_loss's %d contiguous float32 on %s" % (_lib.OM_LOSS_RESULT_FLOATS, self.block.device))
+        if out is None:
+            out = torch.empty((), dtype=torch.float32, device=self.block.device)
+        if not self.block.is_cuda:
+            return _accumulate_torch(self.block, result, self.num_scales, self.scales_weight, with_metrics, step, out)
+        dev = self.block.device
+        with torch.cuda.device(dev):
+            rc = _lib.load().om_loss_accumulate(ctypes.c_void_p(result.data_ptr()), self.num_scales, self._w, int(bool(with_metrics)),
+                                                int(step), ctypes.c_void_p(self.block.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+                                                _lib.current_stream_ptr(dev))
+        _lib.check(rc, "om_loss_accumulate")
+        return out
+
+    def _stage(self):
+        return self.block[_lib.OM_COUNTER_STAGE_OFF:_lib.OM_COUNTER_STAGE_OFF + 2 * len(self.keys)]
+
+    def _epoch(self):
+        return self.block[_lib.OM_COUNTER_EPOCH_OFF:_lib.OM_COUNTER_EPOCH_OFF + 2 * len(self.keys)]
+
+    def reset(self):
+        self._epoch().add_(self._stage())
+        self._stage().zero_()
+
+    def reset_epoch(self):
+        self.block.zero_()
+
+    def gather(self, group=None):
+        """All-gather the block and replace this rank's STAGE pairs by the sum of every rank's, added in rank order on every rank
+        (the reference's _temp_counter_<rank>.pth merge, trainer/trainer.py:78-81,113-116,175-178, which merges the stage pairs:
+        "not merge_epoch"); the status words become the OR of the ranks' flags and the smallest latched step.  The epoch pairs
+        stay: a loop that gathers before every reset has the merged totals in them already.  No host synchronisation."""
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+            return self
+        blocks = [torch.empty_like(self.block) for _ in range(dist.get_world_size(group))]
+        dist.all_gather(blocks, self.block, group=group)
+        n = 2 * len(self.keys)
+        total = blocks[0][:n].clone()
+        for b in blocks[1:]:
+            total += b[:n]
+        status = torch.stack([b[_lib.OM_COUNTER_FLAG_OFF:].view(torch.int64) for b in blocks])        # [world, 2]
+        flags = status[0, 0].clone()
+        for f in status[1:, 0]:
+            flags |= f
+        big = torch.iinfo(torch.int64).max
+        first = torch.where(status[:, 0] != 0, status[:, 1], torch.full_like(status[:, 1], big)).min()
+        self._stage().copy_(total)
+        mine = self.block[_lib.OM_COUNTER_FLAG_OFF:].view(torch.int64)
+        mine[0] = flags
+        mine[1] = torch.where(flags != 0, first, torch.zeros_like(first))
+        return self
+
+    # -- the host side
+    def _host(self):
+        host = self.block.cpu() if self.block.is_cuda else self.block.clone()            # the read's one device-to-host copy
+        self.check(host)
+        return host.tolist()
+
+    def check(self, host=None):
+        """Raise from the latched status words: FloatingPointError for a non-finite pred_wh or loss, ValueError for the GT flags
+        (the errors of the host path's _finish); the message names the step that latched first.  `host`: a host copy of the
+        block (one is made when it is not given)."""
+        if host is None:
+            host = self.block.cpu()
+        flags, step = host[_lib.OM_COUNTER_FLAG_OFF:].view(torch.int64).tolist()
+        self.flags, self.first_bad_step = flags, (step if flags else None)
+        if not flags:
+            return
+        where = " (first at step %d)" % step
+        if flags & _lib.OM_LOSS_FLAG_NONFINITE_WH:
+            raise FloatingPointError("pred_wh not finite" + where)
+        if flags & _lib.OM_LOSS_FLAG_TOO_MANY_GT:
+            raise ValueError("gt_index is not a prefix of the GTs or an image has more than %d GTs (the HIP loss's limit)"
+                             % _lib.OM_LOSS_MAX_GT + where)
+        if flags & _lib.OM_LOSS_FLAG_BAD_CLASS:
+            raise ValueError("a gt_cls value lies outside [0, %d)" % self.num_classes + where)
+        if flags & _lib.OM_COUNTER_FLAG_NONFINITE_LOSS:
+            raise FloatingPointError("loss not finite" + where)
+        raise RuntimeError("unknown counter flags 0x%x" % flags + where)
+
+    def averages(self, keys=None):
+        """{key: stage mean} for `keys` (default: all) from one copy of the block."""
+        host = self._host()
+        out = {}
+        for key in (self.keys if keys is None else keys):
+            i = _lib.OM_COUNTER_STAGE_OFF + 2 * self._index[key]
+            out[key] = EvalCounter._mean(host[i], host[i + 1])
+        return out
+
+    def averages_epoch(self, keys=None):
+        """{key: epoch mean} for `keys` (default: all) from one copy of the block; like EvalCounter.average_epoch it folds the
+        stage pairs of the keys it answers for into the epoch pairs (on the device, asynchronously)."""
+        host = self._host()
+        out = {}
+        for key in (self.keys if keys is None else keys):
+            s = _lib.OM_COUNTER_STAGE_OFF + 2 * self._index[key]
+            e = _lib.OM_COUNTER_EPOCH_OFF + 2 * self._index[key]
+            out[key] = EvalCounter._mean(host[e] + host[s], host[e + 1] + host[s + 1])
+        if keys is None:
+            self.reset()
+        else:
+            for key in keys:
+                s = _lib.OM_COUNTER_STAGE_OFF + 2 * self._index[key]
+                e = _lib.OM_COUNTER_EPOCH_OFF + 2 * self._index[key]
+                self.block[e:e + 2] += self.block[s:s + 2]
+                self.block[s:s + 2].zero_()
+        return out
+
+    def average(self, key):
+        return self.averages([key])[key]
+
+    def average_epoch(self, key):
+        return self.averages_epoch([key])[key]
 
 
 class OrienMaskYOLOMultiScaleLoss:
@@ -296,6 +486,12 @@ class OrienMaskYOLOMultiScaleLoss:
         eval/base.py:90-121's keys in its order; metric_log is empty when training is True (orienmask_yolo_loss.py:148)."""
         result = self.launch(predict, target)
         return self._finish(result, training, result.device)
+
+    def enqueue(self, predict, target, counter, step, training=True):
+        """The deferred call: om_loss, then om_loss_accumulate of its result into `counter` (a DeviceEvalCounter of this loss on
+        the heads' device) as step `step`; with training=False the metric keys are counted too.  Returns loss_sum as a 0-dim
+        device tensor.  Nothing is copied to the host: a bad input shows at the counter's next read (DeviceEvalCounter.check)."""
+        return counter.accumulate(self.launch(predict, target), step, with_metrics=training is not True)
 
     def _finish(self, result, training, dev):
         """The host side of a call: the flag word, then aggregate."""

@@ -247,14 +247,22 @@ def _model_device(model):
     return torch.device("cuda", torch.cuda.current_device())
 
 
-def validate(model, loss, postprocess, loader, coco_metrics=None):
+def validate(model, loss, postprocess, loader, coco_metrics=None, counter=None, group=None):
     """Trainer._val_epoch (the reference's trainer/trainer.py:135-209) for ONE rank: forward, loss(training=False), and -- when a
     cocoeval.COCOMetrics is given -- postprocess, to_coco_format / update_results and coco_eval.  The image and the targets
     are moved to the device of the model's parameters, as _val_epoch moves them to the trainer's.  Returns its val_log:
-    val_loss, val_<loss_id>, val_<metric_id> (EvalCounter epoch averages) and val_<coco key>.  Merging the counters and COCO
-    results of several ranks (the reference's _temp_counter_*.pth / _temp_coco_eval_*.json exchange) is not done here; the
-    tensorboard writes are left out.  Without coco_metrics the postprocess is not run (its output would go nowhere)."""
+    val_loss, val_<loss_id>, val_<metric_id> (EvalCounter epoch averages) and val_<coco key>.  The tensorboard writes are left
+    out.  Without coco_metrics the postprocess is not run (its output would go nowhere).
+
+    Without `counter` the counters and COCO results of several ranks (the reference's _temp_counter_*.pth /
+    _temp_coco_eval_*.json exchange) are not merged.  With `counter` (a loss.DeviceEvalCounter of `loss` on the model's device;
+    it is reset) the loop is the deferred one -- ``loss.enqueue`` per batch, no device-to-host copy of the loss values, ONE read
+    of the counter at the end -- and the ranks of `group` (None: the default process group, when there is one) merge: the
+    counters by ``counter.gather`` (rank order), the COCO results in rank order as dist.gather_detections merges them; every
+    rank returns the merged val_log."""
     from .loss import EvalCounter
+    if counter is not None:
+        return _validate_deferred(model, loss, postprocess, loader, coco_metrics, counter, group)
     if coco_metrics is not None:
         coco_metrics.reset()
     counter = EvalCounter()
@@ -281,6 +289,45 @@ def validate(model, loss, postprocess, loader, coco_metrics=None):
     for key in loss.metric_id:
         val_log["val_%s" % key] = counter.average_epoch(key)
     if coco_metrics is not None:
+        for key, value in coco_metrics.coco_eval().items():
+            val_log["val_%s" % key] = value
+    counter.reset_epoch()
+    return val_log
+
+
+def _validate_deferred(model, loss, postprocess, loader, coco_metrics, counter, group):
+    import torch.distributed as dist
+    from .dist import gather_detections
+    if coco_metrics is not None:
+        coco_metrics.reset()
+    counter.reset_epoch()
+    dev = _model_device(model)
+    with torch.no_grad():
+        for step, sample in enumerate(loader, 1):
+            image = sample[0].to(dev)
+            target = [anno.to(dev) for anno in sample[1]]
+            predict = model(image)
+            loss.enqueue(predict, target, counter, step, training=False)
+            if coco_metrics is not None:
+                coco_metrics.update_results(coco_metrics.to_coco_format(sample[2], postprocess(predict)))
+    many = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
+    if many:
+        counter.gather(group)
+    means = counter.averages_epoch()
+    val_log = {"val_loss": means["loss"]}
+    for key in list(loss.loss_id) + list(loss.metric_id):
+        val_log["val_%s" % key] = means[key]
+    if coco_metrics is not None:
+        if many:
+            mine = [dict(bbox=coco_metrics.bbox_results, segm=coco_metrics.segm_results)]
+            if group is None:
+                parts = gather_detections(mine)
+            else:
+                parts = [None] * dist.get_world_size(group)
+                dist.all_gather_object(parts, mine, group=group)
+                parts = [d for part in parts for d in part]
+            coco_metrics.bbox_results = [r for part in parts for r in part["bbox"]]
+            coco_metrics.segm_results = [r for part in parts for r in part["segm"]]
         for key, value in coco_metrics.coco_eval().items():
             val_log["val_%s" % key] = value
     counter.reset_epoch()

@@ -1,7 +1,8 @@
 """The reference's training loss on the HIP path: ``builder.build(config["loss"], orienmask_amd.train)``.
 
   OrienMaskYOLOMultiScaleLoss  orienmask_amd.loss's class with the same constructor; when a head requires grad, ``forward``
-                               returns a ``loss_sum`` with a ``grad_fn`` whose backward is ``om_loss_backward`` (csrc/loss.hip)
+                               returns a ``loss_sum`` with a ``grad_fn`` whose backward is ``om_loss_backward`` (csrc/loss.hip);
+                               ``enqueue`` is the same call without the host copy (the values go to a DeviceEvalCounter)
 
 This is the one-line swap of the reference's trainer/builder.py:34 (``build(config['loss'], evaluation_module)``): the trainer
 then does ``loss, loss_log, _ = self.loss(predict, label, training=True)`` and ``loss.backward()`` as before, without the
@@ -52,9 +53,9 @@ from torch.nn.modules.batchnorm import _BatchNorm
 from . import lib as _lib
 from . import pack as _pack
 from .arch import DARKNET_STAGES, LEAKY_SLOPE, model_convs
-from .loss import EvalCounter, OrienMaskYOLOMultiScaleLoss as _ValuesLoss
+from .loss import DeviceEvalCounter, EvalCounter, OrienMaskYOLOMultiScaleLoss as _ValuesLoss
 
-__all__ = ["OrienMaskYOLOMultiScaleLoss", "EvalCounter", "ConvBNLeaky", "bn_leaky", "conv2d", "OrienMaskYOLOFPNPlus", "OrienMaskYOLO",
+__all__ = ["OrienMaskYOLOMultiScaleLoss", "EvalCounter", "DeviceEvalCounter", "ConvBNLeaky", "bn_leaky", "conv2d", "OrienMaskYOLOFPNPlus", "OrienMaskYOLO",
            "convert_sync_batchnorm", "upsample_concat", "split_channels"]
 
 BACKENDS = ("hip", "torch")
@@ -140,15 +141,39 @@ class OrienMaskYOLOMultiScaleLoss(_ValuesLoss):
     def forward(self, predict, target, training=True):
         """Returns (loss_sum, loss_log, metric_log) as the values-only class does; loss_sum has a grad_fn when any head requires
         grad (and grad mode is on)."""
+        flat = self._wants_graph(predict)
+        if flat is None:
+            # no graph to build (no head requires grad, or grad mode is off): the values-only path
+            return super().forward([(b.detach(), o.detach()) for b, o in predict], target, training)
+        run = self._bind_own(predict, target)
+        loss_sum, loss_log, metric_log = self._finish(run(), training, run.result.device)
+        return self._attach(predict, flat, run, loss_sum), loss_log, metric_log
+
+    def enqueue(self, predict, target, counter, step, training=True):
+        """The values-only class's deferred call (om_loss, om_loss_accumulate into `counter`, no host copy); the device scalar it
+        returns has the same grad_fn as forward's loss_sum when any head requires grad, so ``enqueue(...).backward()`` is
+        ``forward(...)[0].backward()``."""
+        flat = self._wants_graph(predict)
+        if flat is None:
+            return super().enqueue([(b.detach(), o.detach()) for b, o in predict], target, counter, step, training)
+        run = self._bind_own(predict, target)
+        loss_sum = counter.accumulate(run(), step, with_metrics=training is not True)
+        return self._attach(predict, flat, run, loss_sum)
+
+    def _wants_graph(self, predict):
+        """The heads as a flat list when a graph is to be built (a head requires grad and grad mode is on), else None."""
         if len(predict) != self.num_scales:
             raise ValueError("predict has %d scales, the loss was built for %d" % (len(predict), self.num_scales))
         flat = [t for pair in predict for t in pair]
         if not (torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in flat)):
-            # no graph to build (no head requires grad, or grad mode is off): the values-only path
-            return super().forward([(b.detach(), o.detach()) for b, o in predict], target, training)
+            return None
         for t in flat:
             if isinstance(t, torch.Tensor) and t.requires_grad and t.dtype != torch.float32:
                 raise _lib.OrienMaskHipError("the HIP loss takes float32 heads, got %s" % t.dtype)
+        return flat
+
+    def _bind_own(self, predict, target):
+        """prepare() on dense detached heads with a workspace of this call's own."""
         dense = []
         for b, o in predict:
             # the gradient is written through the strides the kernels read: heads that are not dense are read from a copy
@@ -162,12 +187,12 @@ class OrienMaskYOLOMultiScaleLoss(_ValuesLoss):
         N = int(target[0].shape[0])
         # a workspace of this call's own: a later call must not overwrite the match records this graph's backward reads
         ws = torch.empty(self.workspace_bytes(B, N), dtype=torch.uint8, device=dev)
-        run = self.prepare(dense, target, workspace=ws)
-        loss_sum, loss_log, metric_log = self._finish(run(), training, dev)
+        return self.prepare(dense, target, workspace=ws)
+
+    def _attach(self, predict, flat, run, loss_sum):
         call = _Call(self, [(b.requires_grad, o.requires_grad) for b, o in predict], run)
         call.loss_sum = loss_sum
-        out = _LossBackward.apply(call, *flat)
-        return out, loss_log, metric_log
+        return _LossBackward.apply(call, *flat)
 
 
 # ---------------------------------------------------------------------------------------------------------------- the model

@@ -1,0 +1,90 @@
+"""Steps per second of the training loop, sync-free against the reference's per-step host bookkeeping, on the same build.
+
+    python tools/bench_train_step.py [--batch 8] [--size 544] [--steps 30] [--warmup 5] [--rounds 3] [--out profiles/train_step_bench.json]
+
+Both loops are orienmask_amd.trainer.Trainer._train_epoch over the same SyntheticLossLoader batches (made once, on the device),
+the trainable OrienMaskYOLOFPNPlus with every HIP backend, the HIP SGD step, accumulate 1 and log_freq = steps, so the sync-free
+loop reads its counter twice per timed epoch (at the last batch, where step % writer_freq == 0, and at the end of the epoch): the
+only difference is ``sync_free``.  An epoch of `warmup` batches runs first; then `rounds` timed epochs of
+`steps` batches per loop, alternating, each between two device synchronisations.  Prints one JSON line: per loop the median,
+minimum and maximum steps per second over the rounds, and the spread that any comparison of the two has to clear.
+"""
+import argparse
+import json
+import os
+import shutil
+import statistics
+import sys
+import tempfile
+import time
+import types
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--size", type=int, default=544)
+    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--out", default=None, help="also write the JSON line to this file")
+    args = ap.parse_args(argv)
+
+    import torch
+    from orienmask_amd import builder
+    from orienmask_amd.tester import SyntheticLossLoader
+    if not torch.cuda.is_available():
+        raise SystemExit("needs an MI355X")
+    dev = torch.device("cuda", 0)
+    s = args.size
+    anchors = [[12, 16], [19, 36], [40, 28], [36, 75], [76, 55], [72, 146], [142, 110], [192, 243], [459, 401]]
+    log_dir = tempfile.mkdtemp(prefix="om_train_bench_")
+    config = dict(seed=0, n_gpu=1, accumulate=1, epochs=1, val_freq=1000, save_freq=1000, monitor="loss", monitor_mode="off",
+                  log_freq=args.steps, log_dir=log_dir, name="bench",
+                  model=dict(type="OrienMaskYOLOFPNPlus", num_anchors=3, num_classes=80, backend="hip", conv_backend="hip",
+                             conv_forward="hip", route_backend="hip"),
+                  loss=dict(type="OrienMaskYOLOMultiScaleLoss", grid_size=[[s // 32] * 2, [s // 16] * 2, [s // 8] * 2],
+                            image_size=[s, s], anchors=anchors, anchor_mask=[[6, 7, 8], [3, 4, 5], [0, 1, 2]], num_classes=80,
+                            weight=[1, 1, 1, 1, 1, 20, 20], scales_weight=[1, 1, 1]),
+                  optimizer=dict(type="SGD", lr=1e-4, momentum=0.9, weight_decay=5e-4),
+                  lr_scheduler=dict(type="StepWarmUpLR", warmup_type="linear", warmup_iter=1000, warmup_ratio=0.1,
+                                    milestones=[100000], gamma=0.1))
+
+    def loader(n):
+        return SyntheticLossLoader(n * args.batch, args.batch, size=(s, s), seed=1, device=dev)
+
+    warm, timed = loader(args.warmup), loader(args.steps)
+    trainers = {}
+    for name, sync_free in (("sync_free", True), ("host_loop", False)):
+        t = builder.build_trainer(dict(config, name="bench_" + name), types.SimpleNamespace(resume=None, weights=None), dev,
+                                  train_loader=warm, sync_free=sync_free)
+        t._train_epoch(1)
+        t.train_loader = timed
+        trainers[name] = t
+    rates = {name: [] for name in trainers}
+    for _ in range(args.rounds):
+        for name, t in trainers.items():
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            t._train_epoch(2)
+            torch.cuda.synchronize(dev)
+            rates[name].append(args.steps / (time.perf_counter() - t0))
+    shutil.rmtree(log_dir, ignore_errors=True)          # the trainers' run directories: nothing in them is a result
+    out = dict(bench="train_step", batch=args.batch, size=s, steps=args.steps, warmup=args.warmup, rounds=args.rounds,
+               device=torch.cuda.get_device_name(0), torch=torch.__version__)
+    for name, r in rates.items():
+        out[name] = dict(steps_per_s_median=round(statistics.median(r), 3), steps_per_s_min=round(min(r), 3),
+                         steps_per_s_max=round(max(r), 3), images_per_s_median=round(statistics.median(r) * args.batch, 2))
+    out["ratio_of_medians"] = round(out["sync_free"]["steps_per_s_median"] / out["host_loop"]["steps_per_s_median"], 4)
+    out["spread"] = round(max((max(r) - min(r)) / statistics.median(r) for r in rates.values()), 4)
+    line = json.dumps(out)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as handle:
+            handle.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

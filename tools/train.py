@@ -1,0 +1,66 @@
+"""Train an OrienMask model on the MI355X: the reference's train.py against orienmask_amd.
+
+    python tools/train.py --config CONFIG [--resume CHECKPOINT | --weights WEIGHTS] [--synthetic N]
+
+CONFIG is a JSON file -- the ``config.json`` a trainer writes into its checkpoint directory is one -- or, where a ``config``
+package with the reference's ``get_config`` is importable, a config name.  ``--synthetic N`` trains on N seeded synthetic images
+(tester.SyntheticLossLoader) of the loss's image size instead of config['train_loader'], so the tool runs without a dataset; no
+validation then.  With several processes (torchrun), each uses the GPU of its LOCAL_RANK.
+"""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def load_config(name):
+    if os.path.isfile(name):
+        with open(name) as handle:
+            return json.load(handle)
+    try:
+        from config import get_config
+    except ImportError:
+        raise SystemExit("--config %r is not a file, and no `config` package with get_config is importable" % name)
+    return get_config(name)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("-c", "--config", required=True, help="a config JSON file (or a config name, see above)")
+    ap.add_argument("-r", "--resume", default=None, help="checkpoint to resume from")
+    ap.add_argument("-w", "--weights", default=None, help="weights to start from (strict=False)")
+    ap.add_argument("--synthetic", type=int, default=0, metavar="N", help="train on N synthetic images")
+    args = ap.parse_args(argv)
+    assert not (args.resume and args.weights), "--resume and --weights exclude each other"
+
+    import torch
+    from orienmask_amd import builder
+    config = load_config(args.config)
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    if not torch.cuda.is_available():
+        raise SystemExit("training needs an MI355X")
+    torch.cuda.set_device(local_rank)
+    device = torch.device("cuda", local_rank)
+    if world > 1:
+        torch.distributed.init_process_group("nccl")
+    train_loader = None
+    if args.synthetic:
+        from orienmask_amd.tester import SyntheticLossLoader
+        loss_cfg = config["loss"]
+        size = loss_cfg["image_size"]
+        size = (size, size) if isinstance(size, int) else tuple(size)
+        batch = config.get("train_loader", {}).get("batch_size", 8)
+        train_loader = SyntheticLossLoader(args.synthetic, batch, size=size, seed=config.get("seed", 0),
+                                           num_classes=loss_cfg["num_classes"], device=device)
+        config = dict(config, val_loader=None)
+    trainer = builder.build_trainer(config, args, device, train_loader=train_loader)
+    trainer.train()
+    if world > 1:
+        torch.distributed.destroy_process_group()
+
+
+if __name__ == "__main__":
+    main()
