@@ -21,7 +21,8 @@
 //   conv_dw_kernel   dw[co,ci,kh,kw] = sum_{b,oy,ox} dy[b,co,oy,ox] * x[b,ci,oy*s+kh-pad,ox*s+kw-pad]
 //       GEMM: rows = co (dy), columns = ci, one 32x32 accumulator per tap, k = the flat output pixel (b, oy, ox); both operands are
 //       contiguous along k in NCHW.  k is split over workgroups (blockIdx.x), at most CG_SPLIT_PIX pixels each.  Three levels of
-//       sums: the matrix-instruction accumulator takes CG_CHAIN_PIX pixels, then is added into a second fp32 accumulator and
+//       sums: the matrix-instruction accumulator takes CG_CHAIN_PIX pixels (1x1: four accumulators take every fourth pixel pair of
+//       them, 8 pixels each, and are summed pairwise), then is added into a second fp32 accumulator and
 //       cleared (at most 64 such additions per workgroup); with more than one split the workgroup writes its tile to
 //       partial[split][co][ci][tap] in the caller's workspace and conv_dw_reduce_kernel sums the splits of an element in split order
 //       in double and rounds once.  The number of splits depends on the shape and the device's compute-unit count only.  No
@@ -184,9 +185,16 @@ __global__ void __launch_bounds__(CG_THREADS) conv_dw_kernel(const DwArgs a) {
 
     constexpr int CHAIN_STEPS = CG_CHAIN_PIX / KP;
     static_assert(CG_CHAIN_PIX % KP == 0, "a chain is a whole number of steps");
-    f32x16 acc[TAPS], tot[TAPS];
+    // 1x1: NCH interleaved accumulators share the pixels of a chain (pixel pair kk goes to accumulator kk % NCH) and are summed
+    // pairwise where the chain ends, so no fmaf chain is longer than CG_CHAIN_PIX / NCH products.  One chain over the 18 pixels of
+    // a 3 x 3 map at B = 2 measured 2.12 x torch-CPU-float32's error over the tensor's scale on in-network operands.
+    constexpr int NCH = TAPS == 1 ? 4 : 1;
+    static_assert((KP / 2) % NCH == 0, "every step gives each accumulator the same number of pixel pairs");
+    f32x16 acc[TAPS * NCH], tot[TAPS];
 #pragma unroll
-    for (int tp = 0; tp < TAPS; ++tp) { clear16(acc[tp]); clear16(tot[tp]); }
+    for (int tp = 0; tp < TAPS; ++tp) clear16(tot[tp]);
+#pragma unroll
+    for (int i = 0; i < TAPS * NCH; ++i) clear16(acc[i]);
 
     int step = 0;
     for (int k0 = k_begin; k0 < k_end; k0 += KP) {
@@ -226,15 +234,19 @@ __global__ void __launch_bounds__(CG_THREADS) conv_dw_kernel(const DwArgs a) {
                 const float av = ap[2 * kk];
 #pragma unroll
                 for (int tp = 0; tp < TAPS; ++tp)
-                    acc[tp] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bp[tp * CIT * LD + 2 * kk], acc[tp], 0, 0, 0);
+                    acc[tp * NCH + kk % NCH] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bp[tp * CIT * LD + 2 * kk], acc[tp * NCH + kk % NCH], 0, 0, 0);
             }
             if (++step == CHAIN_STEPS) {            // the chain ends
                 step = 0;
 #pragma unroll
                 for (int tp = 0; tp < TAPS; ++tp) {
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) tot[tp][r] += acc[tp][r];
-                    clear16(acc[tp]);
+                    for (int r = 0; r < 16; ++r) {
+                        if constexpr (NCH == 4) tot[tp][r] += (acc[tp * 4][r] + acc[tp * 4 + 1][r]) + (acc[tp * 4 + 2][r] + acc[tp * 4 + 3][r]);
+                        else tot[tp][r] += acc[tp][r];
+                    }
+#pragma unroll
+                    for (int c = 0; c < NCH; ++c) clear16(acc[tp * NCH + c]);
                 }
             }
         }
@@ -249,7 +261,11 @@ __global__ void __launch_bounds__(CG_THREADS) conv_dw_kernel(const DwArgs a) {
         const int co = co0 + wco * 32 + 8 * (r >> 2) + 4 * fk + (r & 3);
         if (co >= a.cout) continue;
 #pragma unroll
-        for (int tp = 0; tp < TAPS; ++tp) o[((size_t)co * a.cin + ci) * TAPS + tp] = tot[tp][r] + acc[tp][r];
+        for (int tp = 0; tp < TAPS; ++tp) {
+            float rest = acc[tp * NCH][r];          // an unfinished chain
+            if constexpr (NCH == 4) rest = (acc[tp * 4][r] + acc[tp * 4 + 1][r]) + (acc[tp * 4 + 2][r] + acc[tp * 4 + 3][r]);
+            o[((size_t)co * a.cin + ci) * TAPS + tp] = tot[tp][r] + rest;
+        }
     }
 }
 
