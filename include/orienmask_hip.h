@@ -862,6 +862,24 @@ int om_conv2d_grad_weight(const float* x, const float* dy, int B, int cin, int H
 int om_conv2d_forward(const float* x, const float* w, const float* bias, int B, int cin, int H, int W, int cout, int ksize, int stride,
                       float* y, om_stream stream);
 
+/* ---- A FROZEN Conv -> BatchNorm -> LeakyReLU (+ residual) block in one kernel (orienmask_amd.train.conv_bn_leaky_frozen; the
+ *      models' frozen_stages with conv_forward='hip'): the bias-free convolution above with another epilogue, so the convolution
+ *      output never reaches memory and nothing is saved for a backward.  x, w, the geometries, layouts and size limits are
+ *      om_conv2d_forward's; gamma, beta, running_mean, running_var [cout]; residual [B,cout,Ho,Wo] or null; y [B,cout,Ho,Wo].
+ *      Per output element, with h the element's double sum (om_conv2d_forward's chains in its order):
+ *          z = fma(h - mean, gamma * invstd, beta),   y = (float)((z > 0 ? z : z * slope) + residual)
+ *      in double, rounded once; without a residual nothing is added.  mean = (double)running_mean and invstd = 1/sqrt((double)
+ *      running_var + eps), carried through a float32 (value, remainder) pair, are the doubles om_bn_act_forward(training=0) builds
+ *      (one definition, csrc/bn_channel.h): where every convolution sum is an exact float32, y has the bits of that call on
+ *      om_conv2d_forward's output.  The statistics are read only; eps > 0.
+ *      The channel records are built once per workgroup.  Enqueued on `stream`; no workspace, no allocation, no host synchronisation,
+ *      no atomics, bit-identical from run to run, and an image's y has the same bits alone and in any batch.  A null x / w / y /
+ *      gamma / beta / running_mean / running_var, y aliasing x, w or the residual, another geometry, sizes outside the limits or
+ *      eps <= 0 return OM_EINVAL and nothing is written. */
+int om_conv2d_frozen_forward(const float* x, const float* w, int B, int cin, int H, int W, int cout, int ksize, int stride,
+                             const float* gamma, const float* beta, const float* running_mean, const float* running_var, double eps,
+                             float slope, const float* residual, float* y, om_stream stream);
+
 /* ---- The training models' plumbing between the convolutions (model/orienmask_yolo_fpnplus.py:74-90, model/orienmask_yolo.py:71-86:
  *      F.interpolate(mode='nearest'), torch.cat and torch.split, with autograd's backward of the three; orienmask_amd.train's
  *      upsample_concat / split_channels, the models with route_backend='hip').  All tensors fp32 NCHW contiguous: y, dy

@@ -18,6 +18,7 @@
 // channel: no atomics, the same bits on every run.  Compiled with -ffp-contract=off: z = fma(x - mean, gamma * invstd, beta) is
 // written out once and is the SAME expression, on the same doubles, in the forward and in the backward's mask.
 #include "om_common.h"
+#include "bn_channel.h"
 
 namespace om {
 
@@ -111,28 +112,8 @@ __device__ __forceinline__ void sum_partials(const double* __restrict__ partial,
     block_sum2(a, b, lds);
 }
 
-// What the element-wise passes know about a channel, in double.  mean and invstd are carried as float32 pairs (value, remainder) in
-// the save vectors, so the backward rebuilds exactly the doubles the forward used and z has the same bits in both.
-struct BnChannel {
-    double mean, invstd, w, beta;      // w = gamma * invstd
-};
-
-__device__ __forceinline__ void split_hi_lo(double v, float& hi, float& lo) {
-    hi = (float)v;
-    lo = (float)(v - (double)hi);
-}
-
-__device__ __forceinline__ BnChannel bn_channel(float mean_hi, float mean_lo, float invstd_hi, float invstd_lo, float gamma, float beta) {
-    BnChannel ch;
-    ch.mean = (double)mean_hi + (double)mean_lo;
-    ch.invstd = (double)invstd_hi + (double)invstd_lo;
-    ch.w = (double)gamma * ch.invstd;
-    ch.beta = (double)beta;
-    return ch;
-}
-
-// z = gamma * xhat + beta: THE expression of the forward and of the backward's mask (one fma on exact operands)
-__device__ __forceinline__ double bn_z(float x, const BnChannel& ch) { return fma((double)x - ch.mean, ch.w, ch.beta); }
+// BnChannel, split_hi_lo, bn_channel and bn_z (THE expression of z, in the forward and in the backward's mask): bn_channel.h,
+// shared with the frozen block's epilogue in conv_fwd.hip.
 
 // ---------------------------------------------------------------------------------------------------------------- forward
 template <int V>

@@ -26,9 +26,19 @@
 //       most 32 products: 8 x 3 at 3x3, 32 at 1x1), then is added into a double per element and cleared; y is that double plus
 //       the bias (as double), rounded once.  Chunks in ci order, row taps in kh order: the order for an element depends on the
 //       geometry only, not on the tile, the image or B.  k is never split; no workspace, no atomics: the same bits on every run.
+//   EPI_FROZEN        the same kernel with the frozen Conv -> BatchNorm -> LeakyReLU (+ residual) block's epilogue instead of the
+//       bias (om_conv2d_frozen_forward): the convolution output never reaches memory.  At the start, beside the position table,
+//       thread t of the first NT writes the record of channel co0 + t to LDS: exactly the doubles bn_fwd_kernel's EVAL phase
+//       builds (bn_channel.h; invstd = 1/sqrt((double)running_var + eps) through split_hi_lo, mean = (double)running_mean), zeros
+//       where co0 + t >= cout.  One record per channel and workgroup, not one per lane: the double sqrt and division of 32 records
+//       per lane would cost more than the matrix instructions of a 64-channel 1x1 layer.  Per element, with h the double sum:
+//       z = fma(h - mean, gamma * invstd, beta), y = (float)((z > 0 ? z : z * slope) + residual), all double, rounded once, with
+//       contraction switched off for the function (this file is not built with -ffp-contract=off).  The 16 residuals of a
+//       32-channel block are loaded before the block's first store.
 // Every load and store is bounds-checked per element (any B, cin, cout, H, W >= 1; no alignment is assumed); rows and columns of a
 // tile that lie outside the tensor are staged as zeros and never stored.
 #include "om_common.h"
+#include "bn_channel.h"
 
 namespace om {
 
@@ -37,14 +47,32 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int CF_THREADS = 256;
 constexpr int CF_MT = 128;              // pixels of a tile: four waves of 32
 
+enum { EPI_BIAS = 0, EPI_FROZEN = 1 };
+
 struct FwdArgs {
     const float* x; const float* w; const float* bias; float* y;
     int cin, cout, H, W, Ho, Wo, HoWo;
     int P;                      // B * Ho * Wo
+    // EPI_FROZEN only
+    const float* gamma; const float* beta; const float* running_mean; const float* running_var; const float* residual;
+    double eps;
+    float slope;
 };
 
+// the frozen block's output for one element: fwd_apply's expressions (bn_act.hip, built with -ffp-contract=off) on the double sum.
+// This file is built with contraction on, and z * slope + res must stay a rounded product and a rounded sum: the pragma takes the
+// contract flag off the operations written in this function (the __dmul_rn / __dadd_rn intrinsics are plain operators in the
+// toolchain's header, which a later inlining pass could still fuse); bn_z's only fused operation is its explicit fma.
+__device__ __forceinline__ float frozen_out(double h, const BnAffine& ch, double slope, bool has_res, float res) {
+#pragma clang fp contract(off)
+    const double z = bn_z(h, ch);
+    double y = z > 0.0 ? z : z * slope;
+    if (has_res) y = y + (double)res;
+    return (float)y;                                        // the only rounding to float32
+}
+
 // TN blocks of 32 output channels per wave (every wave takes the tile's whole co range and 32 of its pixels)
-template <int TN, int KS, int S>
+template <int TN, int KS, int S, int EPI>
 __global__ void __launch_bounds__(CF_THREADS) conv_fwd_kernel(const FwdArgs a) {
     constexpr int TAPS = KS * KS, NT = TN * 32;
     constexpr int KC = KS == 1 ? 32 : 8;                    // input channels per staged chunk
@@ -58,6 +86,7 @@ __global__ void __launch_bounds__(CF_THREADS) conv_fwd_kernel(const FwdArgs a) {
     __shared__ long long s_off[POSN];
     __shared__ float s_x[2][XE];                            // [ci][row][position]
     __shared__ float s_w[2][NT * LDW];                      // [co][ci][tap]
+    __shared__ BnAffine s_ch[EPI == EPI_FROZEN ? NT : 1];   // the record of channel co0 + t
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int fi = lane & 31, fk = lane >> 5;
@@ -81,6 +110,19 @@ __global__ void __launch_bounds__(CF_THREADS) conv_fwd_kernel(const FwdArgs a) {
             if ((unsigned)iy < (unsigned)a.H && ix < a.W) off = (long long)((size_t)b * a.cin * hw + (size_t)iy * a.W + ix);
         }
         s_off[p] = off;
+    }
+
+    if constexpr (EPI == EPI_FROZEN) {
+        if (tid < NT) {
+            const int co = co0 + tid;
+            BnChannel ch = {};
+            if (co < a.cout) {
+                float invstd_hi, invstd_lo;
+                split_hi_lo(1.0 / sqrt((double)a.running_var[co] + a.eps), invstd_hi, invstd_lo);
+                ch = bn_channel(a.running_mean[co], 0.f, invstd_hi, invstd_lo, a.gamma[co], a.beta[co]);
+            }
+            s_ch[tid] = BnAffine{ch.mean, ch.w, ch.beta};
+        }
     }
 
     // this lane's pixel and the column taps that stay in its row
@@ -179,14 +221,43 @@ __global__ void __launch_bounds__(CF_THREADS) conv_fwd_kernel(const FwdArgs a) {
     }
     // D layout: column (pixel) = lane & 31, row (co) = 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3)
     if (!live) return;
-    float* o = a.y + (size_t)b * a.cout * a.HoWo + q;
+    const size_t base = (size_t)b * a.cout * a.HoWo + q;
+    float* o = a.y + base;
+    if constexpr (EPI == EPI_FROZEN) {
+        const bool has_res = a.residual != nullptr;
+        const float* rp = has_res ? a.residual + base : nullptr;
+        const double slope = (double)a.slope;
 #pragma unroll
-    for (int n = 0; n < TN; ++n)
+        for (int n = 0; n < TN; ++n) {
+            // 16 loads in flight, under one uniform branch and none per element: a channel beyond cout reads the last channel's
+            // plane (in bounds) and is never stored
+            float res[16];
+            if (has_res) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int co = co0 + n * 32 + 8 * (r >> 2) + 4 * fk + (r & 3);
-            if (co < a.cout) o[(size_t)co * a.HoWo] = (float)(tot[n][r] + (a.bias ? (double)a.bias[co] : 0.0));
+                for (int r = 0; r < 16; ++r) {
+                    const int co = co0 + n * 32 + 8 * (r >> 2) + 4 * fk + (r & 3);
+                    res[r] = rp[(size_t)(co < a.cout ? co : a.cout - 1) * a.HoWo];
+                }
+            } else {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) res[r] = 0.f;
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int cl = n * 32 + 8 * (r >> 2) + 4 * fk + (r & 3);
+                const BnAffine ch = s_ch[cl];
+                if (co0 + cl < a.cout) o[(size_t)(co0 + cl) * a.HoWo] = frozen_out(tot[n][r], ch, slope, has_res, res[r]);
+            }
         }
+    } else {
+#pragma unroll
+        for (int n = 0; n < TN; ++n)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int co = co0 + n * 32 + 8 * (r >> 2) + 4 * fk + (r & 3);
+                if (co < a.cout) o[(size_t)co * a.HoWo] = (float)(tot[n][r] + (a.bias ? (double)a.bias[co] : 0.0));
+            }
+    }
 }
 
 // compute units of the current device (0 when there is none to ask)
@@ -200,19 +271,47 @@ static int cf_compute_units() {
     return n;
 }
 
-template <int TN, int KS, int S>
+template <int TN, int KS, int S, int EPI>
 static void launch_fwd(const FwdArgs& a, hipStream_t st) {
     const dim3 grid((a.P + CF_MT - 1) / CF_MT, (a.cout + TN * 32 - 1) / (TN * 32));
-    hipLaunchKernelGGL((conv_fwd_kernel<TN, KS, S>), grid, dim3(CF_THREADS), 0, st, a);
+    hipLaunchKernelGGL((conv_fwd_kernel<TN, KS, S, EPI>), grid, dim3(CF_THREADS), 0, st, a);
 }
 
-template <int KS, int S>
+template <int KS, int S, int EPI>
 static void launch_fwd_geometry(const FwdArgs& a, hipStream_t st) {
     // 64 output channels per workgroup; 32 where there are no more, or where 64 would leave compute units without a workgroup
     // (k is never split)
     const long long tiles = ((long long)a.P + CF_MT - 1) / CF_MT * ((a.cout + 63) / 64);
-    if (a.cout > 32 && tiles >= cf_compute_units()) launch_fwd<2, KS, S>(a, st);
-    else launch_fwd<1, KS, S>(a, st);
+    if (a.cout > 32 && tiles >= cf_compute_units()) launch_fwd<2, KS, S, EPI>(a, st);
+    else launch_fwd<1, KS, S, EPI>(a, st);
+}
+
+// the geometries and size limits of both entry points (those of the gradients, conv_grad.hip: 32-bit pixel and element counts, grid
+// dimension y below 65536)
+static bool fwd_shape_ok(int B, int cin, int H, int W, int cout, int ksize, int stride) {
+    const bool geometry = (ksize == 1 && stride == 1) || (ksize == 3 && (stride == 1 || stride == 2));
+    const bool sizes = B >= 1 && cin >= 1 && cout >= 1 && H >= 1 && W >= 1 && B <= 16383 && (long long)B * H * W < (1ll << 30) &&
+                       (long long)cout * cin * ksize * ksize < (1ll << 31) && cin <= (1 << 20) && cout <= (1 << 20);
+    return geometry && sizes;
+}
+
+static FwdArgs fwd_args(const float* x, const float* w, float* y, int B, int cin, int H, int W, int cout, int ksize, int stride) {
+    const int pad = ksize / 2;
+    FwdArgs a = {};
+    a.x = x; a.w = w; a.y = y;
+    a.cin = cin; a.cout = cout; a.H = H; a.W = W;
+    a.Ho = (H + 2 * pad - ksize) / stride + 1;
+    a.Wo = (W + 2 * pad - ksize) / stride + 1;
+    a.HoWo = a.Ho * a.Wo;
+    a.P = B * a.HoWo;
+    return a;
+}
+
+template <int EPI>
+static void launch_fwd_any(const FwdArgs& a, int ksize, int stride, hipStream_t st) {
+    if (ksize == 1) launch_fwd_geometry<1, 1, EPI>(a, st);
+    else if (stride == 1) launch_fwd_geometry<3, 1, EPI>(a, st);
+    else launch_fwd_geometry<3, 2, EPI>(a, st);
 }
 
 }  // namespace om
@@ -220,25 +319,31 @@ static void launch_fwd_geometry(const FwdArgs& a, hipStream_t st) {
 extern "C" int om_conv2d_forward(const float* x, const float* w, const float* bias, int B, int cin, int H, int W, int cout, int ksize,
                                  int stride, float* y, om_stream stream) {
     OM_REQUIRE(x && w && y, OM_EINVAL, "om_conv2d_forward: null pointer");
-    const bool geometry = (ksize == 1 && stride == 1) || (ksize == 3 && (stride == 1 || stride == 2));
-    // the limits of the gradients (conv_grad.hip): 32-bit pixel and element counts, grid dimension y below 65536
-    const bool sizes = B >= 1 && cin >= 1 && cout >= 1 && H >= 1 && W >= 1 && B <= 16383 && (long long)B * H * W < (1ll << 30) &&
-                       (long long)cout * cin * ksize * ksize < (1ll << 31) && cin <= (1 << 20) && cout <= (1 << 20);
-    OM_REQUIRE(geometry && sizes, OM_EINVAL,
+    OM_REQUIRE(om::fwd_shape_ok(B, cin, H, W, cout, ksize, stride), OM_EINVAL,
                "om_conv2d_forward: [%d,%d,%d,%d] -> %d channels, ksize %d stride %d: the geometries are 1x1 stride 1, 3x3 stride 1 "
                "and 3x3 stride 2 (B <= 16383, B*H*W below 2^30, cout*cin*ksize^2 below 2^31)", B, cin, H, W, cout, ksize, stride);
-    const int pad = ksize / 2;
-    om::FwdArgs a = {};
-    a.x = x; a.w = w; a.bias = bias; a.y = y;
-    a.cin = cin; a.cout = cout; a.H = H; a.W = W;
-    a.Ho = (H + 2 * pad - ksize) / stride + 1;
-    a.Wo = (W + 2 * pad - ksize) / stride + 1;
-    a.HoWo = a.Ho * a.Wo;
-    a.P = B * a.HoWo;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (ksize == 1) om::launch_fwd_geometry<1, 1>(a, st);
-    else if (stride == 1) om::launch_fwd_geometry<3, 1>(a, st);
-    else om::launch_fwd_geometry<3, 2>(a, st);
+    om::FwdArgs a = om::fwd_args(x, w, y, B, cin, H, W, cout, ksize, stride);
+    a.bias = bias;
+    om::launch_fwd_any<om::EPI_BIAS>(a, ksize, stride, static_cast<hipStream_t>(stream));
+    OM_CHECK_HIP(hipGetLastError());
+    return OM_OK;
+}
+
+extern "C" int om_conv2d_frozen_forward(const float* x, const float* w, int B, int cin, int H, int W, int cout, int ksize, int stride,
+                                        const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                                        double eps, float slope, const float* residual, float* y, om_stream stream) {
+    OM_REQUIRE(x && w && y && gamma && beta && running_mean && running_var, OM_EINVAL, "om_conv2d_frozen_forward: null pointer");
+    OM_REQUIRE(y != x && y != w && y != residual, OM_EINVAL,
+               "om_conv2d_frozen_forward: y must not alias x, w or the residual (a workgroup reads what another has written)");
+    OM_REQUIRE(om::fwd_shape_ok(B, cin, H, W, cout, ksize, stride), OM_EINVAL,
+               "om_conv2d_frozen_forward: [%d,%d,%d,%d] -> %d channels, ksize %d stride %d: the geometries are 1x1 stride 1, 3x3 "
+               "stride 1 and 3x3 stride 2 (B <= 16383, B*H*W below 2^30, cout*cin*ksize^2 below 2^31)", B, cin, H, W, cout, ksize,
+               stride);
+    OM_REQUIRE(eps > 0.0, OM_EINVAL, "om_conv2d_frozen_forward: eps %g", eps);
+    om::FwdArgs a = om::fwd_args(x, w, y, B, cin, H, W, cout, ksize, stride);
+    a.gamma = gamma; a.beta = beta; a.running_mean = running_mean; a.running_var = running_var; a.residual = residual;
+    a.eps = eps; a.slope = slope;
+    om::launch_fwd_any<om::EPI_FROZEN>(a, ksize, stride, static_cast<hipStream_t>(stream));
     OM_CHECK_HIP(hipGetLastError());
     return OM_OK;
 }

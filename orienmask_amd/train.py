@@ -34,6 +34,10 @@ The forward convolution is torch's with conv_forward='torch' (the default) and o
 needs conv_backend='hip'.  Its gradients are torch's with conv_backend='torch' (the default) and the HIP kernels of
 csrc/conv_grad.hip with conv_backend='hip'.
 
+  conv_bn_leaky_frozen         a frozen block (the models' frozen_stages) as one kernel: the convolution with the fixed affine of the
+                               running statistics, LeakyReLU and the residual add in its epilogue (om_conv2d_frozen_forward); no
+                               autograd node, nothing saved
+
   upsample_concat              torch.cat of nearest-up-sampled tensors (the models' three cat sites) as om_route_concat_forward, with
                                om_route_concat_backward (csrc/route.hip) as its backward
   split_channels               torch.split along the channels into dense tensors: the same two kernels with the roles swapped
@@ -56,7 +60,7 @@ from .arch import DARKNET_STAGES, LEAKY_SLOPE, model_convs
 from .loss import DeviceEvalCounter, EvalCounter, OrienMaskYOLOMultiScaleLoss as _ValuesLoss
 
 __all__ = ["OrienMaskYOLOMultiScaleLoss", "EvalCounter", "DeviceEvalCounter", "ConvBNLeaky", "bn_leaky", "conv2d", "OrienMaskYOLOFPNPlus", "OrienMaskYOLO",
-           "convert_sync_batchnorm", "upsample_concat", "split_channels"]
+           "convert_sync_batchnorm", "upsample_concat", "split_channels", "conv_bn_leaky_frozen"]
 
 BACKENDS = ("hip", "torch")
 CONV_BACKENDS = ("torch", "hip")
@@ -356,6 +360,65 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, forward="torch"):
     return _Conv2d.apply(x, weight, bias, s, forward == "hip")
 
 
+def _require_no_grad(what, **tensors):
+    """A frozen layer has no backward: under grad mode nothing it reads may require grad."""
+    if not torch.is_grad_enabled():
+        return
+    for name, t in tensors.items():
+        if t is not None and t.requires_grad:
+            raise _lib.OrienMaskHipError("%s: %s requires grad, but a frozen layer has no backward (frozen layers are a prefix of the "
+                                         "network: freeze what feeds them, or run under torch.no_grad())" % (what, name))
+
+
+def conv_bn_leaky_frozen(x, weight, bn, residual=None, stride=1, padding=0, slope=LEAKY_SLOPE):
+    """A frozen Conv -> BatchNorm -> LeakyReLU (+ residual) block as ONE kernel, om_conv2d_frozen_forward (csrc/conv_fwd.hip):
+    leaky_relu(batch_norm(conv2d(x, weight), bn's running statistics), slope) + residual, where the convolution output is never
+    stored.  x, weight and the geometries as conv2d; `bn` an nn.BatchNorm2d with affine parameters and running statistics, whose
+    weight, bias, running_mean, running_var and eps are read (its mode is not asked: the running statistics are used, no buffer is
+    touched); residual None or NCHW-contiguous with the output's shape.  Returns a tensor without a grad_fn.  Under grad mode, x,
+    residual, the weight or bn's parameters requiring grad raise; so does anything else that is off: there is no fallback."""
+    what = "conv_bn_leaky_frozen"
+    _lib.require_cuda_tensor(x, "the frozen block's input", torch.float32)
+    _lib.require_cuda_tensor(weight, "the frozen block's convolution weight", torch.float32)
+    if x.dim() != 4 or not x.is_contiguous():
+        raise _lib.OrienMaskHipError("%s takes NCHW-contiguous [B,C,H,W] activations, got strides %s for shape %s"
+                                     % (what, x.stride(), tuple(x.shape)))
+    if weight.dim() != 4 or not weight.is_contiguous() or weight.shape[1] != x.shape[1] or weight.shape[2] != weight.shape[3]:
+        raise _lib.OrienMaskHipError("%s: weight must be contiguous [cout,%d,k,k], got %s strides %s"
+                                     % (what, x.shape[1], tuple(weight.shape), weight.stride()))
+    ks, s, p = int(weight.shape[2]), _pair_of(stride, "stride"), _pair_of(padding, "padding")
+    if (ks, s, p) not in ((1, 1, 0), (3, 1, 1), (3, 2, 1)):
+        raise _lib.OrienMaskHipError("%s: kernel %d stride %d padding %d; the geometries are 1x1 stride 1 padding 0, 3x3 stride 1 "
+                                     "padding 1 and 3x3 stride 2 padding 1" % (what, ks, s, p))
+    cout = int(weight.shape[0])
+    if bn.running_mean is None or bn.running_var is None:
+        raise _lib.OrienMaskHipError("%s: the BatchNorm has no running statistics (track_running_stats=False)" % what)
+    if bn.weight is None or bn.bias is None:
+        raise _lib.OrienMaskHipError("%s: the BatchNorm has no affine parameters" % what)
+    for name, t in (("weight", bn.weight), ("bias", bn.bias), ("running_mean", bn.running_mean), ("running_var", bn.running_var)):
+        _lib.require_cuda_tensor(t, "the frozen block's BatchNorm " + name, torch.float32)
+        if tuple(t.shape) != (cout,) or not t.is_contiguous() or t.device != x.device:
+            raise _lib.OrienMaskHipError("%s: BatchNorm %s must be contiguous [%d] on %s, got %s on %s"
+                                         % (what, name, cout, x.device, tuple(t.shape), t.device))
+    if weight.device != x.device:
+        raise _lib.OrienMaskHipError("%s: weight on %s, x on %s" % (what, weight.device, x.device))
+    B, cin, H, W = x.shape
+    shape = (B, cout, (H + 2 * p - ks) // s + 1, (W + 2 * p - ks) // s + 1)
+    if residual is not None:
+        _lib.require_cuda_tensor(residual, "residual", torch.float32)
+        if tuple(residual.shape) != shape or not residual.is_contiguous() or residual.device != x.device:
+            raise _lib.OrienMaskHipError("residual must be NCHW-contiguous with the block's output shape %s on %s, got %s strides %s on %s"
+                                         % (shape, x.device, tuple(residual.shape), residual.stride(), residual.device))
+    _require_no_grad(what, x=x, residual=residual, weight=weight, **{"bn.weight": bn.weight, "bn.bias": bn.bias})
+    dev = x.device
+    y = torch.empty(shape, dtype=torch.float32, device=dev)
+    with _device(dev):
+        _lib.check(_lib.load().om_conv2d_frozen_forward(
+            _vp(x), _vp(weight), B, cin, H, W, cout, ks, s, _vp(bn.weight), _vp(bn.bias), _vp(bn.running_mean), _vp(bn.running_var),
+            float(bn.eps), float(slope), _vp(residual), _vp(y), _lib.current_stream_ptr(dev)), "om_conv2d_frozen_forward")
+    return y
+
+
 def _route_call(fn, what, ptrs, chans, scales, B, H, W, whole, dev):
     """One om_route_concat_* call on the current stream: `ptrs` the per-source tensors (None: null), `whole` y or dy."""
     n = len(chans)
@@ -576,10 +639,17 @@ class ConvBNLeaky(nn.Module):
     through conv2d, whose gradients are the HIP kernels of csrc/conv_grad.hip; CUDA float32 NCHW-contiguous tensors only.
 
     conv_forward 'torch' (default): the forward convolution is F.conv2d.  conv_forward 'hip' (needs conv_backend 'hip'): it is
-    om_conv2d_forward (csrc/conv_fwd.hip)."""
+    om_conv2d_forward (csrc/conv_fwd.hip).
+
+    frozen=True: the block's three parameters have requires_grad False; its BatchNorm normalises with the running statistics in
+    every mode, never touches a buffer, stays in eval mode across train() calls and is left alone by convert_sync_batchnorm.  No
+    autograd node is made, and an input that requires grad raises (frozen blocks are a prefix of the network).  The forward is
+    F.conv2d -> F.batch_norm(training=False) -> leaky (+ residual) with backend 'torch'; F.conv2d -> bn_leaky's eval kernel with
+    backend 'hip'; and with conv_forward 'hip' the single kernel of conv_bn_leaky_frozen.  The keys and buffers are an unfrozen
+    block's; load_state_dict tolerates a missing num_batches_tracked (the reference's FrozenBatchNorm2d has none)."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, backend="hip", conv_backend="torch",
-                 conv_forward="torch"):
+                 conv_forward="torch", frozen=False):
         super().__init__()
         if backend not in BACKENDS:
             raise ValueError("backend must be one of %s, got %r" % (BACKENDS, backend))
@@ -594,8 +664,46 @@ class ConvBNLeaky(nn.Module):
             nn.Conv2d(in_channels, out_channels, kernel_size, stride=stride, padding=padding, bias=False),
             nn.BatchNorm2d(out_channels),
             nn.LeakyReLU(negative_slope=LEAKY_SLOPE, inplace=True))
+        self.frozen = bool(frozen)
+        if self.frozen:
+            for p in self.parameters():
+                p.requires_grad_(False)
+            bn = self.conv_block[1]
+            bn.eval()
+            bn.register_load_state_dict_pre_hook(self._keep_num_batches_tracked)
+
+    def _keep_num_batches_tracked(self, module, state_dict, prefix, *_):
+        """A frozen block's counter is never read: where a checkpoint lacks it, the module keeps its own."""
+        key = prefix + "num_batches_tracked"
+        if key not in state_dict:
+            state_dict[key] = self.conv_block[1].num_batches_tracked
+
+    def train(self, mode=True):
+        super().train(mode)
+        if self.frozen:
+            self.conv_block[1].eval()
+        return self
+
+    def _frozen_forward(self, x, residual):
+        conv, bn, act = self.conv_block[0], self.conv_block[1], self.conv_block[2]
+        if bn.training:
+            bn.eval()                       # set by hand on the sub-module: .training tells what the block does
+        if bn.running_mean is None or bn.running_var is None:
+            raise ValueError("ConvBNLeaky: a frozen block needs the BatchNorm's running statistics")
+        _require_no_grad("ConvBNLeaky(frozen=True)", x=x, residual=residual, **{n: p for n, p in self.named_parameters()})
+        if self.backend == "hip" and self.conv_forward == "hip":
+            return conv_bn_leaky_frozen(x, conv.weight, bn, residual=residual, stride=conv.stride, padding=conv.padding,
+                                        slope=act.negative_slope)
+        h = F.conv2d(x, conv.weight, None, conv.stride, conv.padding)
+        if self.backend == "hip":
+            return bn_leaky(h, bn, residual=residual, slope=act.negative_slope)
+        y = F.batch_norm(h, bn.running_mean, bn.running_var, bn.weight, bn.bias, False, 0.0, bn.eps)
+        y = F.leaky_relu(y, act.negative_slope, inplace=True)
+        return y if residual is None else y + residual
 
     def forward(self, x, residual=None):
+        if self.frozen:
+            return self._frozen_forward(x, residual)
         conv, bn, act = self.conv_block[0], self.conv_block[1], self.conv_block[2]
         if bn.momentum is None:
             raise ValueError("ConvBNLeaky: momentum=None (a cumulative moving average) is not supported")
@@ -621,8 +729,9 @@ def convert_sync_batchnorm(model, process_group=None):
     ConvBNLeaky so that, in training mode and with more than one rank in `process_group` (None: the default group), its batch
     statistics are taken over every rank's batch.  The module tree, the state_dict keys and the parameters() order are unchanged.
     Blocks in eval mode (model.eval(), backbone_batchnorm_eval) and a world of one rank exchange nothing, as torch's SyncBatchNorm.
+    Frozen blocks (ConvBNLeaky(frozen=True), the models' frozen_stages) have no batch statistics and are left unsynchronised.
     Backend 'torch' is refused: F.batch_norm cannot synchronise.  Returns `model`."""
-    blocks = [m for m in model.modules() if isinstance(m, ConvBNLeaky)]
+    blocks = [m for m in model.modules() if isinstance(m, ConvBNLeaky) and not m.frozen]
     for m in blocks:
         if m.backend != "hip":
             raise ValueError("convert_sync_batchnorm: backend %r cannot synchronise its batch statistics (F.batch_norm); build the "
@@ -660,14 +769,24 @@ class OrienMaskYOLOFPNPlus(nn.Module):
     / 'hip': whose up-sampling, cat and split between the convolutions: torch's ops, or upsample_concat and split_channels
     (csrc/route.hip), CUDA float32 tensors only; independent of the other three), the same state_dict keys and parameters() order as the reference and as
     orienmask_amd.model (checkpoints and optimizer state move in both directions), trainable parameters, and a forward that
-    returns the reference's ((bbox32, orien32), (bbox16, orien16), (bbox8, orien8)) with a graph behind it."""
+    returns the reference's ((bbox32, orien32), (bbox16, orien16), (bbox8, orien8)) with a graph behind it.
+
+    frozen_stages (int 0...6, default 0): freezes backbone.conv1 ... backbone.conv{k} (conv1 the stem layer, conv2-conv6 a
+    down-sampling layer plus its blocks each) as ConvBNLeaky(frozen=True): no gradients, running statistics in every mode, untouched
+    buffers, and with conv_forward 'hip' one kernel per layer.  What the reference's freeze_backbone stage count means to do
+    (model/backbone/darknet.py:31-38, model/base.py:210-266) under an unambiguous name: bools raise.  The keys, the parameters()
+    order and the buffers are those of frozen_stages=0, which builds the model as before; independent of backbone_batchnorm_eval."""
 
     def __init__(self, num_anchors, num_classes, pretrained=None, freeze_backbone=False, backbone_batchnorm_eval=False,
-                 backend="hip", conv_backend="torch", conv_forward="torch", route_backend="torch"):
+                 backend="hip", conv_backend="torch", conv_forward="torch", route_backend="torch", frozen_stages=0):
         super().__init__()
         if freeze_backbone is not False:
             # the reference's DarkNet53._freeze_network calls self._freeze_module, which does not exist (darknet.py:31-38)
-            raise NotImplementedError("freeze_backbone=%r: the reference's own _freeze_network cannot run; not supported" % (freeze_backbone,))
+            raise NotImplementedError("freeze_backbone=%r: the reference's own _freeze_network cannot run; not supported.  Use "
+                                      "frozen_stages=k (0...6) to freeze backbone.conv1 ... backbone.conv{k}" % (freeze_backbone,))
+        if isinstance(frozen_stages, bool) or not isinstance(frozen_stages, int) or not 0 <= frozen_stages <= len(DARKNET_STAGES) + 1:
+            raise ValueError("frozen_stages must be an int from 0 to %d (the number of backbone stages conv1 ... conv%d to freeze), "
+                             "got %r" % (len(DARKNET_STAGES) + 1, len(DARKNET_STAGES) + 1, frozen_stages))
         if backend not in BACKENDS:
             raise ValueError("backend must be one of %s, got %r" % (BACKENDS, backend))
         if conv_backend not in CONV_BACKENDS:
@@ -684,6 +803,7 @@ class OrienMaskYOLOFPNPlus(nn.Module):
         self.conv_backend = conv_backend
         self.conv_forward = conv_forward
         self.route_backend = route_backend
+        self.frozen_stages = frozen_stages
         self.backbone = _Backbone(backbone_batchnorm_eval)
         self._plus = type(self).__name__ == "OrienMaskYOLOFPNPlus"
         self._by_name = {}
@@ -696,8 +816,10 @@ class OrienMaskYOLOFPNPlus(nn.Module):
                 node = node._modules[p]
             pad = spec.ksize // 2
             if spec.bn:
+                # backbone.conv{i}[...]: frozen where i <= frozen_stages
+                frozen = spec.name.startswith("backbone.conv") and int(spec.name.split(".")[1][len("conv"):]) <= frozen_stages
                 m = ConvBNLeaky(spec.cin, spec.cout, spec.ksize, stride=spec.stride, padding=pad, backend=backend,
-                                conv_backend=conv_backend, conv_forward=conv_forward)
+                                conv_backend=conv_backend, conv_forward=conv_forward, frozen=frozen)
             else:
                 m = nn.Conv2d(spec.cin, spec.cout, spec.ksize, stride=spec.stride, padding=pad)
             node.add_module(leaf, m)

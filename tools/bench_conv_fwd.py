@@ -10,7 +10,15 @@ divides.  Reported: median / min / max per call, TFLOP/s at the median (2 * B*Ho
 step (forward + backward, median of interleaved rounds) with its peak memory for (conv_backend, conv_forward) = ('torch', 'torch'),
 ('hip', 'torch') and ('hip', 'hip'), all in this run.
 
-    python tools/bench_conv_fwd.py [--batches 8 32] [--rounds 5] [--inner 3] [--warmup 2] [--out profiles/conv_fwd_bench.json]
+The frozen column: on the geometries the backbone contains (what frozen_stages can freeze), om_conv2d_frozen_forward (hip_frozen:
+the convolution with the fixed BatchNorm affine, LeakyReLU and, on a DarkNet block's second layer, the residual add in its epilogue)
+against the two kernels it replaces, om_conv2d_forward followed by om_bn_act_forward(training=0) (hip_fwd_bn), in the same
+interleaved rounds; the geometries where the fused kernel is slower by more than the rounds' own min-max spread are listed.  A row's
+`backbone_layers` counts the backbone's layers of the geometry (52 in all; `layers` counts the whole model's, which also has the
+geometry in its necks, where nothing can be frozen), and the two frozen columns' sums over layers are weighted by it.
+--only-frozen times these two on the backbone's geometries and nothing else.
+
+    python tools/bench_conv_fwd.py [--batches 8 32] [--rounds 5] [--inner 3] [--warmup 2] [--only-frozen] [--out profiles/conv_fwd_bench.json]
 
 prints one JSON line (and writes it to --out); a progress line per geometry goes to stderr.
 """
@@ -43,6 +51,20 @@ def layer_table(size):
     return table
 
 
+def backbone_table(size):
+    """The backbone's geometries (what frozen_stages=6 fuses) -> (number of BACKBONE layers, residual): residual True for a DarkNet
+    block's second layer.  Within the backbone a geometry is either always or never such a layer."""
+    table = {}
+    for spec in arch.fpnplus_convs():
+        if spec.name.startswith("backbone."):
+            d = arch.layer_div(spec)
+            key = (spec.cin, spec.cout, spec.ksize, spec.stride, size // d * spec.stride, size // d * spec.stride)
+            count, residual = table.get(key, (0, spec.name.endswith(".conv.1")))
+            assert residual == spec.name.endswith(".conv.1"), key
+            table[key] = (count + 1, residual)
+    return table
+
+
 def time_calls(fn, inner):
     start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     torch.cuda.synchronize()
@@ -54,7 +76,7 @@ def time_calls(fn, inner):
     return start.elapsed_time(stop) / inner
 
 
-def bench_geometry(dev, B, key, args):
+def bench_geometry(dev, B, key, args, frozen=None):
     cin, cout, ks, stride, H, W = key
     L = omlib.load()
     gen = torch.Generator(device=dev).manual_seed(cin + cout + H)
@@ -72,6 +94,23 @@ def bench_geometry(dev, B, key, args):
         "torch_fwd": lambda: F.conv2d(x, w, None, stride, pad),
         "hip_dx": lambda: omlib.check(L.om_conv2d_grad_input(vp(dy), vp(w), *geom, vp(dx), None, 0, st), "dx"),
     }
+    if frozen is not None:
+        gamma, beta, mean = (torch.randn(cout, device=dev, generator=gen) for _ in range(3))
+        var = torch.rand(cout, device=dev, generator=gen) + 0.5
+        res = torch.randn(B, cout, Ho, Wo, device=dev, generator=gen) if frozen else None
+        h, save = torch.empty_like(dy), torch.empty(4 * cout, device=dev)
+        rp = vp(res) if frozen else None
+
+        def two_kernels():
+            omlib.check(L.om_conv2d_forward(vp(x), vp(w), None, *geom, vp(h), st), "fwd")
+            omlib.check(L.om_bn_act_forward(vp(h), B, cout, Ho, Wo, vp(gamma), vp(beta), vp(mean), vp(var), None, 0, 0.1, 1e-5, 0.1, rp,
+                                            vp(y), save.data_ptr(), save.data_ptr() + 8 * cout, None, 0, st), "bn")
+
+        calls["hip_frozen"] = lambda: omlib.check(L.om_conv2d_frozen_forward(vp(x), vp(w), *geom, vp(gamma), vp(beta), vp(mean), vp(var),
+                                                                             1e-5, 0.1, rp, vp(y), st), "frozen")
+        calls["hip_fwd_bn"] = two_kernels
+        if args.only_frozen:
+            calls = {k: calls[k] for k in ("hip_frozen", "hip_fwd_bn")}
     for fn in calls.values():
         for _ in range(args.warmup):
             fn()
@@ -130,32 +169,45 @@ def main():
     ap.add_argument("--inner", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--step-batch", type=int, default=8)
+    ap.add_argument("--only-frozen", action="store_true", help="only the frozen column, on the backbone's geometries")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_conv_fwd.py needs an MI355X: there is nothing to time on a CPU")
     dev = torch.device("cuda:0")
     table = layer_table(args.size)
+    backbone = backbone_table(args.size)
+    if args.only_frozen:
+        table = {k: backbone[k][0] for k in table if k in backbone}
     result = {"bench": "conv_fwd", "size": args.size, "rounds": args.rounds, "inner": args.inner, "warmup": args.warmup,
               "device": torch.cuda.get_device_name(0), "torch": torch.__version__, "batches": {}}
     for B in args.batches:
         rows, sums = [], {}
         for key, count in sorted(table.items(), key=lambda kv: -kv[0][0] * kv[0][1] * kv[0][2] ** 2 * kv[0][4] * kv[0][5]):
-            r = bench_geometry(dev, B, key, args)
+            r = bench_geometry(dev, B, key, args, backbone[key][1] if key in backbone else None)
             rows.append(dict(zip(("cin", "cout", "ksize", "stride", "H", "W"), key), layers=count, **r))
+            if key in backbone:
+                rows[-1].update(backbone_layers=backbone[key][0], residual=backbone[key][1])
             print("B=%d %s x%d: %s" % (B, key, count, {k: v["ms_median"] for k, v in r.items()}), file=sys.stderr, flush=True)
             for k, v in r.items():
                 s = sums.setdefault(k, {"ms_median": 0.0, "ms_min": 0.0, "ms_max": 0.0})
                 for f in s:
-                    s[f] += count * v[f]
+                    s[f] += (backbone[key][0] if k in ("hip_frozen", "hip_fwd_bn") else count) * v[f]
             torch.cuda.empty_cache()
         slower = [dict(zip(("cin", "cout", "ksize", "stride", "H"), (r["cin"], r["cout"], r["ksize"], r["stride"], r["H"])),
                        hip_ms=r["hip_fwd"]["ms_median"], torch_ms=r["torch_fwd"]["ms_median"], hip_dx_ms=r["hip_dx"]["ms_median"])
-                  for r in rows if r["hip_fwd"]["ms_median"] > r["torch_fwd"]["ms_median"]]
+                  for r in rows if not args.only_frozen and r["hip_fwd"]["ms_median"] > r["torch_fwd"]["ms_median"]]
+        # slower by more than the rounds' own spread: the fused kernel's fastest round is above the two kernels' slowest
+        fused_slower = [dict(zip(("cin", "cout", "ksize", "stride", "H"), (r["cin"], r["cout"], r["ksize"], r["stride"], r["H"])),
+                             frozen_ms=r["hip_frozen"], two_kernels_ms=r["hip_fwd_bn"])
+                        for r in rows if "hip_frozen" in r and r["hip_frozen"]["ms_min"] > r["hip_fwd_bn"]["ms_max"]]
         result["batches"][str(B)] = {"geometries": rows, "layers": sum(table.values()),
+                                     "backbone_layers": sum(n for n, _ in backbone.values()),
                                      "sum_over_layers_ms": {k: {f: round(x, 4) for f, x in v.items()} for k, v in sums.items()},
-                                     "geometries_where_hip_is_slower": slower}
-    result["training_step"] = step_times_and_memory(dev, args.step_batch, args.size, args.rounds)
+                                     "geometries_where_hip_is_slower": slower,
+                                     "geometries_where_the_fused_frozen_kernel_is_slower_beyond_spread": fused_slower}
+    if not args.only_frozen:
+        result["training_step"] = step_times_and_memory(dev, args.step_batch, args.size, args.rounds)
     line = json.dumps(result)
     print(line)
     if args.out:

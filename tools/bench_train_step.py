@@ -1,13 +1,16 @@
 """Steps per second of the training loop, sync-free against the reference's per-step host bookkeeping, on the same build.
 
-    python tools/bench_train_step.py [--batch 8] [--size 544] [--steps 30] [--warmup 5] [--rounds 3] [--out profiles/train_step_bench.json]
+    python tools/bench_train_step.py [--batch 8] [--size 544] [--steps 30] [--warmup 5] [--rounds 3] [--frozen-stages K]
+                                     [--default-backends] [--out profiles/train_step_bench.json]
 
 Both loops are orienmask_amd.trainer.Trainer._train_epoch over the same SyntheticLossLoader batches (made once, on the device),
 the trainable OrienMaskYOLOFPNPlus with every HIP backend, the HIP SGD step, accumulate 1 and log_freq = steps, so the sync-free
 loop reads its counter twice per timed epoch (at the last batch, where step % writer_freq == 0, and at the end of the epoch): the
 only difference is ``sync_free``.  An epoch of `warmup` batches runs first; then `rounds` timed epochs of
 `steps` batches per loop, alternating, each between two device synchronisations.  Prints one JSON line: per loop the median,
-minimum and maximum steps per second over the rounds, and the spread that any comparison of the two has to clear.
+minimum and maximum steps per second over the rounds, and the spread that any comparison of the two has to clear, and the peak
+device memory of the timed epochs.  --frozen-stages K builds the model with frozen_stages=K (0, the default, leaves the model
+dict as it was); --default-backends leaves the four backend options at the model's defaults instead of every HIP backend.
 """
 import argparse
 import json
@@ -29,6 +32,8 @@ def main(argv=None):
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--frozen-stages", type=int, default=0, help="freeze backbone.conv1 ... conv{K} (0: none)")
+    ap.add_argument("--default-backends", action="store_true", help="the model's default backends instead of every HIP backend")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     args = ap.parse_args(argv)
 
@@ -52,6 +57,11 @@ def main(argv=None):
                   lr_scheduler=dict(type="StepWarmUpLR", warmup_type="linear", warmup_iter=1000, warmup_ratio=0.1,
                                     milestones=[100000], gamma=0.1))
 
+    if args.default_backends:
+        config["model"] = dict(type="OrienMaskYOLOFPNPlus", num_anchors=3, num_classes=80)
+    if args.frozen_stages:
+        config["model"]["frozen_stages"] = args.frozen_stages
+
     def loader(n):
         return SyntheticLossLoader(n * args.batch, args.batch, size=(s, s), seed=1, device=dev)
 
@@ -64,6 +74,8 @@ def main(argv=None):
         t.train_loader = timed
         trainers[name] = t
     rates = {name: [] for name in trainers}
+    torch.cuda.synchronize(dev)
+    torch.cuda.reset_peak_memory_stats(dev)
     for _ in range(args.rounds):
         for name, t in trainers.items():
             torch.cuda.synchronize(dev)
@@ -73,7 +85,8 @@ def main(argv=None):
             rates[name].append(args.steps / (time.perf_counter() - t0))
     shutil.rmtree(log_dir, ignore_errors=True)          # the trainers' run directories: nothing in them is a result
     out = dict(bench="train_step", batch=args.batch, size=s, steps=args.steps, warmup=args.warmup, rounds=args.rounds,
-               device=torch.cuda.get_device_name(0), torch=torch.__version__)
+               device=torch.cuda.get_device_name(0), torch=torch.__version__, frozen_stages=args.frozen_stages,
+               backends="default" if args.default_backends else "hip", peak_bytes=int(torch.cuda.max_memory_allocated(dev)))
     for name, r in rates.items():
         out[name] = dict(steps_per_s_median=round(statistics.median(r), 3), steps_per_s_min=round(min(r), 3),
                          steps_per_s_max=round(max(r), 3), images_per_s_median=round(statistics.median(r) * args.batch, 2))

@@ -1,11 +1,12 @@
 """Train an OrienMask model on the MI355X: the reference's train.py against orienmask_amd.
 
-    python tools/train.py --config CONFIG [--resume CHECKPOINT | --weights WEIGHTS] [--synthetic N]
+    python tools/train.py --config CONFIG [--resume CHECKPOINT | --weights WEIGHTS] [--synthetic N] [--frozen-stages K]
 
 CONFIG is a JSON file -- the ``config.json`` a trainer writes into its checkpoint directory is one -- or, where a ``config``
 package with the reference's ``get_config`` is importable, a config name.  ``--synthetic N`` trains on N seeded synthetic images
 (tester.SyntheticLossLoader) of the loss's image size instead of config['train_loader'], so the tool runs without a dataset; no
-validation then.  With several processes (torchrun), each uses the GPU of its LOCAL_RANK.
+validation then.  ``--frozen-stages K`` (0...6) overrides the model's ``frozen_stages``: backbone.conv1 ... conv{K} are frozen
+(orienmask_amd.train), the usual way to fine-tune a pretrained backbone.  With several processes (torchrun), each uses the GPU of its LOCAL_RANK.
 """
 import argparse
 import json
@@ -32,12 +33,16 @@ def main(argv=None):
     ap.add_argument("-r", "--resume", default=None, help="checkpoint to resume from")
     ap.add_argument("-w", "--weights", default=None, help="weights to start from (strict=False)")
     ap.add_argument("--synthetic", type=int, default=0, metavar="N", help="train on N synthetic images")
+    ap.add_argument("--frozen-stages", type=int, default=None, metavar="K",
+                    help="freeze backbone.conv1 ... conv{K} (0...6), overriding the config's model.frozen_stages")
     args = ap.parse_args(argv)
     assert not (args.resume and args.weights), "--resume and --weights exclude each other"
 
     import torch
     from orienmask_amd import builder
     config = load_config(args.config)
+    if args.frozen_stages is not None:
+        config = dict(config, model=dict(config["model"], frozen_stages=args.frozen_stages))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if not torch.cuda.is_available():
