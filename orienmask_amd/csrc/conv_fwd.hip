@@ -37,12 +37,10 @@
 //       32-channel block are loaded before the block's first store.
 // Every load and store is bounds-checked per element (any B, cin, cout, H, W >= 1; no alignment is assumed); rows and columns of a
 // tile that lie outside the tensor are staged as zeros and never stored.
-#include "om_common.h"
+#include "conv_train.h"
 #include "bn_channel.h"
 
 namespace om {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int CF_THREADS = 256;
 constexpr int CF_MT = 128;              // pixels of a tile: four waves of 32
@@ -260,17 +258,6 @@ __global__ void __launch_bounds__(CF_THREADS) conv_fwd_kernel(const FwdArgs a) {
     }
 }
 
-// compute units of the current device (0 when there is none to ask)
-static int cf_compute_units() {
-    static int cached[64] = {};
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    if (dev >= 0 && dev < 64 && cached[dev] > 0) return cached[dev];
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) { (void)hipGetLastError(); return 0; }
-    if (dev >= 0 && dev < 64) cached[dev] = n;
-    return n;
-}
-
 template <int TN, int KS, int S, int EPI>
 static void launch_fwd(const FwdArgs& a, hipStream_t st) {
     const dim3 grid((a.P + CF_MT - 1) / CF_MT, (a.cout + TN * 32 - 1) / (TN * 32));
@@ -282,28 +269,14 @@ static void launch_fwd_geometry(const FwdArgs& a, hipStream_t st) {
     // 64 output channels per workgroup; 32 where there are no more, or where 64 would leave compute units without a workgroup
     // (k is never split)
     const long long tiles = ((long long)a.P + CF_MT - 1) / CF_MT * ((a.cout + 63) / 64);
-    if (a.cout > 32 && tiles >= cf_compute_units()) launch_fwd<2, KS, S, EPI>(a, st);
+    if (a.cout > 32 && tiles >= device_compute_units()) launch_fwd<2, KS, S, EPI>(a, st);
     else launch_fwd<1, KS, S, EPI>(a, st);
 }
 
-// the geometries and size limits of both entry points (those of the gradients, conv_grad.hip: 32-bit pixel and element counts, grid
-// dimension y below 65536)
-static bool fwd_shape_ok(int B, int cin, int H, int W, int cout, int ksize, int stride) {
-    const bool geometry = (ksize == 1 && stride == 1) || (ksize == 3 && (stride == 1 || stride == 2));
-    const bool sizes = B >= 1 && cin >= 1 && cout >= 1 && H >= 1 && W >= 1 && B <= 16383 && (long long)B * H * W < (1ll << 30) &&
-                       (long long)cout * cin * ksize * ksize < (1ll << 31) && cin <= (1 << 20) && cout <= (1 << 20);
-    return geometry && sizes;
-}
-
-static FwdArgs fwd_args(const float* x, const float* w, float* y, int B, int cin, int H, int W, int cout, int ksize, int stride) {
-    const int pad = ksize / 2;
+static FwdArgs make_fwd(const ConvGeom& g, const float* x, const float* w, float* y) {
     FwdArgs a = {};
     a.x = x; a.w = w; a.y = y;
-    a.cin = cin; a.cout = cout; a.H = H; a.W = W;
-    a.Ho = (H + 2 * pad - ksize) / stride + 1;
-    a.Wo = (W + 2 * pad - ksize) / stride + 1;
-    a.HoWo = a.Ho * a.Wo;
-    a.P = B * a.HoWo;
+    a.cin = g.cin; a.cout = g.cout; a.H = g.H; a.W = g.W; a.Ho = g.Ho; a.Wo = g.Wo; a.HoWo = g.HoWo; a.P = g.K;
     return a;
 }
 
@@ -319,10 +292,10 @@ static void launch_fwd_any(const FwdArgs& a, int ksize, int stride, hipStream_t 
 extern "C" int om_conv2d_forward(const float* x, const float* w, const float* bias, int B, int cin, int H, int W, int cout, int ksize,
                                  int stride, float* y, om_stream stream) {
     OM_REQUIRE(x && w && y, OM_EINVAL, "om_conv2d_forward: null pointer");
-    OM_REQUIRE(om::fwd_shape_ok(B, cin, H, W, cout, ksize, stride), OM_EINVAL,
-               "om_conv2d_forward: [%d,%d,%d,%d] -> %d channels, ksize %d stride %d: the geometries are 1x1 stride 1, 3x3 stride 1 "
-               "and 3x3 stride 2 (B <= 16383, B*H*W below 2^30, cout*cin*ksize^2 below 2^31)", B, cin, H, W, cout, ksize, stride);
-    om::FwdArgs a = om::fwd_args(x, w, y, B, cin, H, W, cout, ksize, stride);
+    om::ConvGeom g;
+    if (!om::conv_geometry(B, cin, H, W, cout, ksize, stride, &g))
+        return om::conv_geometry_refused("om_conv2d_forward", B, cin, H, W, cout, ksize, stride);
+    om::FwdArgs a = om::make_fwd(g, x, w, y);
     a.bias = bias;
     om::launch_fwd_any<om::EPI_BIAS>(a, ksize, stride, static_cast<hipStream_t>(stream));
     OM_CHECK_HIP(hipGetLastError());
@@ -335,12 +308,11 @@ extern "C" int om_conv2d_frozen_forward(const float* x, const float* w, int B, i
     OM_REQUIRE(x && w && y && gamma && beta && running_mean && running_var, OM_EINVAL, "om_conv2d_frozen_forward: null pointer");
     OM_REQUIRE(y != x && y != w && y != residual, OM_EINVAL,
                "om_conv2d_frozen_forward: y must not alias x, w or the residual (a workgroup reads what another has written)");
-    OM_REQUIRE(om::fwd_shape_ok(B, cin, H, W, cout, ksize, stride), OM_EINVAL,
-               "om_conv2d_frozen_forward: [%d,%d,%d,%d] -> %d channels, ksize %d stride %d: the geometries are 1x1 stride 1, 3x3 "
-               "stride 1 and 3x3 stride 2 (B <= 16383, B*H*W below 2^30, cout*cin*ksize^2 below 2^31)", B, cin, H, W, cout, ksize,
-               stride);
+    om::ConvGeom g;
+    if (!om::conv_geometry(B, cin, H, W, cout, ksize, stride, &g))
+        return om::conv_geometry_refused("om_conv2d_frozen_forward", B, cin, H, W, cout, ksize, stride);
     OM_REQUIRE(eps > 0.0, OM_EINVAL, "om_conv2d_frozen_forward: eps %g", eps);
-    om::FwdArgs a = om::fwd_args(x, w, y, B, cin, H, W, cout, ksize, stride);
+    om::FwdArgs a = om::make_fwd(g, x, w, y);
     a.gamma = gamma; a.beta = beta; a.running_mean = running_mean; a.running_var = running_var; a.residual = residual;
     a.eps = eps; a.slope = slope;
     om::launch_fwd_any<om::EPI_FROZEN>(a, ksize, stride, static_cast<hipStream_t>(stream));

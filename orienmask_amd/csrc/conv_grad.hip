@@ -30,11 +30,9 @@
 //   conv_dbias_kernel   db[co] = sum dy[b,co,:,:] in double, one workgroup per channel, fixed order.
 // Every load and store is bounds-checked per element (any B, cin, cout, H, W >= 1; no alignment is assumed); rows and columns of a
 // tile that lie outside the tensor are staged as zeros and never stored.
-#include "om_common.h"
+#include "conv_train.h"
 
 namespace om {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int CG_THREADS = 256;
 constexpr int CG_CHAIN_PIX = 32;        // dw: pixels (= products) of a first-level chain
@@ -65,11 +63,6 @@ struct DwArgs {
     int chunk;                  // pixels per split
     size_t n;                   // cout * cin * taps
 };
-
-__device__ __forceinline__ void clear16(f32x16& v) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) v[r] = 0.f;
-}
 
 // ---------------------------------------------------------------------------------------------------------------- data gradient
 // WM waves along the pixels (32 each), 4 / WM along ci (TN blocks of 32 each).
@@ -297,48 +290,15 @@ __global__ void __launch_bounds__(CG_THREADS) conv_dbias_kernel(const float* __r
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host
-struct CgGeom {
-    int B, cin, cout, H, W, Ho, Wo, HoWo, ks, stride, pad, taps;
-    int K;              // B * Ho * Wo
-    size_t n;           // cout * cin * taps
-};
-
-static bool cg_geometry(int B, int cin, int H, int W, int cout, int ksize, int stride, CgGeom* g) {
-    if (!((ksize == 1 && stride == 1) || (ksize == 3 && (stride == 1 || stride == 2)))) return false;
-    if (B < 1 || cin < 1 || cout < 1 || H < 1 || W < 1) return false;
-    g->B = B; g->cin = cin; g->cout = cout; g->H = H; g->W = W; g->ks = ksize; g->stride = stride;
-    g->pad = ksize / 2; g->taps = ksize * ksize;
-    g->Ho = (H + 2 * g->pad - ksize) / stride + 1;
-    g->Wo = (W + 2 * g->pad - ksize) / stride + 1;
-    const long long howo = (long long)g->Ho * g->Wo, n = (long long)cout * cin * g->taps;
-    // 32-bit pixel and element counts (split * chunk stays below 2^31), and grid dimensions y / z below 65536
-    if ((long long)B * H * W >= (1ll << 30) || n >= (1ll << 31) || B > 16383 || cin > (1 << 20) || cout > (1 << 20)) return false;
-    g->HoWo = (int)howo;
-    g->K = (int)(howo * B);
-    g->n = (size_t)n;
-    return true;
-}
-
-// compute units of the current device (0 when there is none to ask)
-static int cg_compute_units() {
-    static int cached[64] = {};
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    if (dev >= 0 && dev < 64 && cached[dev] > 0) return cached[dev];
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) { (void)hipGetLastError(); return 0; }
-    if (dev >= 0 && dev < 64) cached[dev] = n;
-    return n;
-}
-
 static int cg_dw_wco(int cout) { return cout > 64 ? 4 : cout > 32 ? 2 : 1; }
 
 // splits of the weight gradient's k: at most CG_SPLIT_PIX pixels each; more, down to CG_MIN_PIX pixels each, while the launch
 // has fewer than two workgroups per compute unit
-static int cg_dw_splits(const CgGeom& g, int* chunk) {
+static int cg_dw_splits(const ConvGeom& g, int* chunk) {
     const int wco = cg_dw_wco(g.cout), wci = 4 / wco;
     const long long tiles = (long long)((g.cout + 32 * wco - 1) / (32 * wco)) * ((g.cin + 32 * wci - 1) / (32 * wci));
     long long s = ((long long)g.K + CG_SPLIT_PIX - 1) / CG_SPLIT_PIX;
-    const long long want = (2ll * cg_compute_units() + tiles - 1) / tiles;
+    const long long want = (2ll * device_compute_units() + tiles - 1) / tiles;
     const long long most = ((long long)g.K + CG_MIN_PIX - 1) / CG_MIN_PIX;
     if (s < want) s = want < most ? want : most;
     if (s < 1) s = 1;
@@ -384,8 +344,8 @@ static void launch_dw(const DwArgs& a, int splits, hipStream_t st) {
 extern "C" {
 
 size_t om_conv2d_grad_workspace_bytes(int B, int cin, int H, int W, int cout, int ksize, int stride) {
-    om::CgGeom g;
-    if (!om::cg_geometry(B, cin, H, W, cout, ksize, stride, &g)) return 0;
+    om::ConvGeom g;
+    if (!om::conv_geometry(B, cin, H, W, cout, ksize, stride, &g)) return 0;
     int chunk;
     const int splits = om::cg_dw_splits(g, &chunk);
     return splits > 1 ? (size_t)splits * g.n * sizeof(float) : 0;
@@ -395,10 +355,9 @@ int om_conv2d_grad_input(const float* dy, const float* w, int B, int cin, int H,
                          void* workspace, size_t ws_bytes, om_stream stream) {
     (void)workspace; (void)ws_bytes;                // the data gradient needs no scratch
     OM_REQUIRE(dy && w && dx, OM_EINVAL, "om_conv2d_grad_input: null pointer");
-    om::CgGeom g;
-    OM_REQUIRE(om::cg_geometry(B, cin, H, W, cout, ksize, stride, &g), OM_EINVAL,
-               "om_conv2d_grad_input: [%d,%d,%d,%d] -> %d channels, ksize %d stride %d: the geometries are 1x1 stride 1, 3x3 stride 1 "
-               "and 3x3 stride 2 (B <= 16383, B*H*W below 2^30, cout*cin*ksize^2 below 2^31)", B, cin, H, W, cout, ksize, stride);
+    om::ConvGeom g;
+    if (!om::conv_geometry(B, cin, H, W, cout, ksize, stride, &g))
+        return om::conv_geometry_refused("om_conv2d_grad_input", B, cin, H, W, cout, ksize, stride);
     hipStream_t st = static_cast<hipStream_t>(stream);
     om::DxArgs a = {};
     a.dy = dy; a.w = w; a.dx = dx;
@@ -425,10 +384,9 @@ int om_conv2d_grad_input(const float* dy, const float* w, int B, int cin, int H,
 int om_conv2d_grad_weight(const float* x, const float* dy, int B, int cin, int H, int W, int cout, int ksize, int stride, float* dw,
                           float* dbias, void* workspace, size_t ws_bytes, om_stream stream) {
     OM_REQUIRE(x && dy && (dw || dbias), OM_EINVAL, "om_conv2d_grad_weight: null pointer");
-    om::CgGeom g;
-    OM_REQUIRE(om::cg_geometry(B, cin, H, W, cout, ksize, stride, &g), OM_EINVAL,
-               "om_conv2d_grad_weight: [%d,%d,%d,%d] -> %d channels, ksize %d stride %d: the geometries are 1x1 stride 1, 3x3 stride 1 "
-               "and 3x3 stride 2 (B <= 16383, B*H*W below 2^30, cout*cin*ksize^2 below 2^31)", B, cin, H, W, cout, ksize, stride);
+    om::ConvGeom g;
+    if (!om::conv_geometry(B, cin, H, W, cout, ksize, stride, &g))
+        return om::conv_geometry_refused("om_conv2d_grad_weight", B, cin, H, W, cout, ksize, stride);
     int chunk;
     const int splits = om::cg_dw_splits(g, &chunk);
     const size_t need = dw && splits > 1 ? (size_t)splits * g.n * sizeof(float) : 0;

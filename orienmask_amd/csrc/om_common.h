@@ -10,6 +10,8 @@
 namespace om {
 
 void set_error(const char* fmt, ...);
+// compute units of the current device, cached per device (0 when there is none to ask; HIP's sticky error is cleared)
+int device_compute_units();
 
 #define OM_CHECK_HIP(expr)                                                              \
     do {                                                                                \

@@ -35,6 +35,16 @@ void set_error(const char* fmt, ...) {
     va_end(ap);
 }
 
+int device_compute_units() {
+    static int cached[64] = {};
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    if (dev >= 0 && dev < 64 && cached[dev] > 0) return cached[dev];
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) { (void)hipGetLastError(); return 0; }
+    if (dev >= 0 && dev < 64) cached[dev] = n;
+    return n;
+}
+
 enum : int { BUF_INPUT = -1, BUF_BBOX32 = -2, BUF_BBOX16 = -3, BUF_BBOX8 = -4, BUF_ORIENS = -5 };
 constexpr int HEAD_PIX_STRIDE = 256;
 

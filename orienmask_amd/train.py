@@ -70,9 +70,12 @@ ROUTE_SCALES = (1, 2, 4, 8)
 ROUTE_MAX = 4
 
 
-def _check_conv_forward(conv_backend, conv_forward):
-    if conv_forward not in CONV_FORWARDS:
-        raise ValueError("conv_forward must be one of %s, got %r" % (CONV_FORWARDS, conv_forward))
+def _check_backends(backend, conv_backend, conv_forward, route_backend="torch"):
+    """The option strings of a block and of a model (a block has no route_backend: the default passes)."""
+    for name, value, known in (("backend", backend, BACKENDS), ("conv_backend", conv_backend, CONV_BACKENDS),
+                               ("conv_forward", conv_forward, CONV_FORWARDS), ("route_backend", route_backend, ROUTE_BACKENDS)):
+        if value not in known:
+            raise ValueError("%s must be one of %s, got %r" % (name, known, value))
     if conv_forward == "hip" and conv_backend != "hip":
         raise ValueError("conv_forward 'hip' requires conv_backend 'hip', got conv_backend %r: torch's gradient node under the HIP "
                          "forward is not supported" % (conv_backend,))
@@ -224,6 +227,30 @@ def _workspace(dev, stream, nbytes):
     return ws
 
 
+def _bn_scratch(x):
+    """(library, stream, workspace) of an om_bn_act_* / om_bn_sync_* call on x's device and current stream."""
+    L = _lib.load()
+    stream = _lib.current_stream_ptr(x.device)
+    return L, stream, _workspace(x.device, stream, L.om_bn_act_workspace_bytes(*x.shape))
+
+
+def _bn_forward_buffers(x):
+    """y, and save_mean | save_invstd (include/orienmask_hip.h) as one buffer of 4C floats."""
+    return torch.empty_like(x), torch.empty(4 * x.shape[1], dtype=torch.float32, device=x.device)
+
+
+def _bn_backward_buffers(ctx, x, dy):
+    """dy contiguous, dx where the input needs a gradient, and dgamma | dbeta as one [2, C] buffer."""
+    dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+    return dy.contiguous(), dx, torch.empty((2, x.shape[1]), dtype=torch.float32, device=x.device)
+
+
+def _bn_grads(ctx, dx, dgb, dy):
+    """The gradients of (x, gamma, beta, residual) and None for the rest of forward's arguments."""
+    return (dx, dgb[0] if ctx.needs_input_grad[1] else None, dgb[1] if ctx.needs_input_grad[2] else None,
+            dy if ctx.has_residual and ctx.needs_input_grad[3] else None) + (None,) * (len(ctx.needs_input_grad) - 4)
+
+
 class _BNAct(torch.autograd.Function):
     """forward(ctx, x, gamma, beta, residual, bn, slope) -> leaky(batch_norm(x)) (+ residual): om_bn_act_forward.  `bn` is the
     nn.BatchNorm2d whose buffers the kernel updates in training mode and reads in eval mode.  Saved for the backward: x, gamma, beta
@@ -233,15 +260,11 @@ class _BNAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, residual, bn, slope):
         B, C, H, W = x.shape
-        dev = x.device
-        L = _lib.load()
         training = bool(bn.training or bn.running_mean is None)
-        y = torch.empty_like(x)
-        save = torch.empty(4 * C, dtype=torch.float32, device=dev)      # save_mean | save_invstd (include/orienmask_hip.h)
+        y, save = _bn_forward_buffers(x)
         track = training and bn.running_mean is not None
-        stream = _lib.current_stream_ptr(dev)
-        ws = _workspace(dev, stream, L.om_bn_act_workspace_bytes(B, C, H, W))
-        with _device(dev):
+        L, stream, ws = _bn_scratch(x)
+        with _device(x.device):
             _lib.check(L.om_bn_act_forward(
                 _vp(x), B, C, H, W, _vp(gamma), _vp(beta), _vp(bn.running_mean), _vp(bn.running_var),
                 _vp(bn.num_batches_tracked) if track else None, 1 if training else 0, float(bn.momentum), float(bn.eps),
@@ -256,19 +279,13 @@ class _BNAct(torch.autograd.Function):
     def backward(ctx, dy):
         x, gamma, beta, save = ctx.saved_tensors
         B, C, H, W = x.shape
-        dev = x.device
-        L = _lib.load()
-        dy = dy.contiguous()
-        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        dgb = torch.empty((2, C), dtype=torch.float32, device=dev)
-        stream = _lib.current_stream_ptr(dev)
-        ws = _workspace(dev, stream, L.om_bn_act_workspace_bytes(B, C, H, W))
-        with _device(dev):
+        dy, dx, dgb = _bn_backward_buffers(ctx, x, dy)
+        L, stream, ws = _bn_scratch(x)
+        with _device(x.device):
             _lib.check(L.om_bn_act_backward(
                 _vp(x), _vp(dy), B, C, H, W, _vp(gamma), _vp(beta), save.data_ptr(), save.data_ptr() + 8 * C, 1 if ctx.training else 0,
                 ctx.slope, _vp(dx), dgb.data_ptr(), dgb.data_ptr() + 4 * C, ws.data_ptr(), ws.numel(), stream), "om_bn_act_backward")
-        return (dx, dgb[0] if ctx.needs_input_grad[1] else None, dgb[1] if ctx.needs_input_grad[2] else None,
-                dy if ctx.has_residual and ctx.needs_input_grad[3] else None, None, None)
+        return _bn_grads(ctx, dx, dgb, dy)
 
 
 class _Conv2d(torch.autograd.Function):
@@ -320,9 +337,22 @@ class _Conv2d(torch.autograd.Function):
         return dx, dw, db, None, None
 
 
-def _forward_kw(conv_forward):
-    """conv2d's keyword for a model's conv_forward: none for the default, so the call is the one it was before the argument."""
-    return {} if conv_forward == "torch" else {"forward": conv_forward}
+def _require_nchw(t, who, what):
+    """`what` (as lib.require_cuda_tensor names it) is a CUDA float32 NCHW-contiguous [B,C,H,W] tensor, or `who` refuses it."""
+    _lib.require_cuda_tensor(t, what, torch.float32)
+    if t.dim() != 4 or not t.is_contiguous():
+        raise _lib.OrienMaskHipError("%s takes NCHW-contiguous [B,C,H,W] activations, got strides %s for shape %s"
+                                     % (who, t.stride(), tuple(t.shape)))
+
+
+def _require_residual(residual, shape, dev):
+    """None, or a CUDA float32 NCHW-contiguous tensor of the block's output shape on the block's device."""
+    if residual is None:
+        return
+    _lib.require_cuda_tensor(residual, "residual", torch.float32)
+    if tuple(residual.shape) != tuple(shape) or not residual.is_contiguous() or residual.device != dev:
+        raise _lib.OrienMaskHipError("residual must be NCHW-contiguous with the block's output shape %s on %s, got %s strides %s on %s"
+                                     % (tuple(shape), dev, tuple(residual.shape), residual.stride(), residual.device))
 
 
 def _pair_of(v, what):
@@ -330,6 +360,18 @@ def _pair_of(v, what):
     if a != b:
         raise _lib.OrienMaskHipError("conv2d: %s %r must be the same along both axes" % (what, v))
     return int(a)
+
+
+def _conv_geometry(who, x, weight, stride, padding):
+    """(ksize, stride, padding) of a convolution of x with a contiguous [cout,cin,k,k] weight, one of the three geometries."""
+    if weight.dim() != 4 or not weight.is_contiguous() or weight.shape[1] != x.shape[1] or weight.shape[2] != weight.shape[3]:
+        raise _lib.OrienMaskHipError("%s: weight must be contiguous [cout,%d,k,k], got %s strides %s"
+                                     % (who, x.shape[1], tuple(weight.shape), weight.stride()))
+    ks, s, p = int(weight.shape[2]), _pair_of(stride, "stride"), _pair_of(padding, "padding")
+    if (ks, s, p) not in ((1, 1, 0), (3, 1, 1), (3, 2, 1)):
+        raise _lib.OrienMaskHipError("%s: kernel %d stride %d padding %d; the geometries are 1x1 stride 1 padding 0, 3x3 stride 1 "
+                                     "padding 1 and 3x3 stride 2 padding 1" % (who, ks, s, p))
+    return ks, s, p
 
 
 def conv2d(x, weight, bias=None, stride=1, padding=0, forward="torch"):
@@ -341,22 +383,13 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, forward="torch"):
     dy) the gradients have the same bits under either forward."""
     if forward not in CONV_FORWARDS:
         raise ValueError("forward must be one of %s, got %r" % (CONV_FORWARDS, forward))
-    _lib.require_cuda_tensor(x, "the convolution input (conv_backend 'hip')", torch.float32)
+    _require_nchw(x, "conv_backend 'hip'", "the convolution input (conv_backend 'hip')")
     _lib.require_cuda_tensor(weight, "the convolution weight (conv_backend 'hip')", torch.float32)
     if bias is not None:
         _lib.require_cuda_tensor(bias, "the convolution bias (conv_backend 'hip')", torch.float32)
-    if x.dim() != 4 or not x.is_contiguous():
-        raise _lib.OrienMaskHipError("conv_backend 'hip' takes NCHW-contiguous [B,C,H,W] activations, got strides %s for shape %s"
-                                     % (x.stride(), tuple(x.shape)))
-    if weight.dim() != 4 or not weight.is_contiguous() or weight.shape[1] != x.shape[1] or weight.shape[2] != weight.shape[3]:
-        raise _lib.OrienMaskHipError("conv2d: weight must be contiguous [cout,%d,k,k], got %s strides %s"
-                                     % (x.shape[1], tuple(weight.shape), weight.stride()))
+    ks, s, p = _conv_geometry("conv2d", x, weight, stride, padding)
     if bias is not None and (tuple(bias.shape) != (weight.shape[0],) or not bias.is_contiguous()):
         raise _lib.OrienMaskHipError("conv2d: bias must be contiguous [%d], got %s" % (weight.shape[0], tuple(bias.shape)))
-    ks, s, p = int(weight.shape[2]), _pair_of(stride, "stride"), _pair_of(padding, "padding")
-    if (ks, s, p) not in ((1, 1, 0), (3, 1, 1), (3, 2, 1)):
-        raise _lib.OrienMaskHipError("conv2d: kernel %d stride %d padding %d; the HIP gradients cover 1x1 stride 1 padding 0, 3x3 "
-                                     "stride 1 padding 1 and 3x3 stride 2 padding 1" % (ks, s, p))
     return _Conv2d.apply(x, weight, bias, s, forward == "hip")
 
 
@@ -378,18 +411,9 @@ def conv_bn_leaky_frozen(x, weight, bn, residual=None, stride=1, padding=0, slop
     touched); residual None or NCHW-contiguous with the output's shape.  Returns a tensor without a grad_fn.  Under grad mode, x,
     residual, the weight or bn's parameters requiring grad raise; so does anything else that is off: there is no fallback."""
     what = "conv_bn_leaky_frozen"
-    _lib.require_cuda_tensor(x, "the frozen block's input", torch.float32)
+    _require_nchw(x, what, "the frozen block's input")
     _lib.require_cuda_tensor(weight, "the frozen block's convolution weight", torch.float32)
-    if x.dim() != 4 or not x.is_contiguous():
-        raise _lib.OrienMaskHipError("%s takes NCHW-contiguous [B,C,H,W] activations, got strides %s for shape %s"
-                                     % (what, x.stride(), tuple(x.shape)))
-    if weight.dim() != 4 or not weight.is_contiguous() or weight.shape[1] != x.shape[1] or weight.shape[2] != weight.shape[3]:
-        raise _lib.OrienMaskHipError("%s: weight must be contiguous [cout,%d,k,k], got %s strides %s"
-                                     % (what, x.shape[1], tuple(weight.shape), weight.stride()))
-    ks, s, p = int(weight.shape[2]), _pair_of(stride, "stride"), _pair_of(padding, "padding")
-    if (ks, s, p) not in ((1, 1, 0), (3, 1, 1), (3, 2, 1)):
-        raise _lib.OrienMaskHipError("%s: kernel %d stride %d padding %d; the geometries are 1x1 stride 1 padding 0, 3x3 stride 1 "
-                                     "padding 1 and 3x3 stride 2 padding 1" % (what, ks, s, p))
+    ks, s, p = _conv_geometry(what, x, weight, stride, padding)
     cout = int(weight.shape[0])
     if bn.running_mean is None or bn.running_var is None:
         raise _lib.OrienMaskHipError("%s: the BatchNorm has no running statistics (track_running_stats=False)" % what)
@@ -404,11 +428,7 @@ def conv_bn_leaky_frozen(x, weight, bn, residual=None, stride=1, padding=0, slop
         raise _lib.OrienMaskHipError("%s: weight on %s, x on %s" % (what, weight.device, x.device))
     B, cin, H, W = x.shape
     shape = (B, cout, (H + 2 * p - ks) // s + 1, (W + 2 * p - ks) // s + 1)
-    if residual is not None:
-        _lib.require_cuda_tensor(residual, "residual", torch.float32)
-        if tuple(residual.shape) != shape or not residual.is_contiguous() or residual.device != x.device:
-            raise _lib.OrienMaskHipError("residual must be NCHW-contiguous with the block's output shape %s on %s, got %s strides %s on %s"
-                                         % (shape, x.device, tuple(residual.shape), residual.stride(), residual.device))
+    _require_residual(residual, shape, x.device)
     _require_no_grad(what, x=x, residual=residual, weight=weight, **{"bn.weight": bn.weight, "bn.bias": bn.bias})
     dev = x.device
     y = torch.empty(shape, dtype=torch.float32, device=dev)
@@ -489,13 +509,6 @@ class _SplitChannels(torch.autograd.Function):
         return dx, None
 
 
-def _require_route_tensor(t, what):
-    _lib.require_cuda_tensor(t, "%s (route_backend 'hip')" % what, torch.float32)
-    if t.dim() != 4 or not t.is_contiguous():
-        raise _lib.OrienMaskHipError("route_backend 'hip' takes NCHW-contiguous [B,C,H,W] activations, got strides %s for shape %s"
-                                     % (t.stride(), tuple(t.shape)))
-
-
 def upsample_concat(tensors, scales):
     """torch.cat([F.interpolate(t, scale_factor=s, mode='nearest') for t, s in zip(tensors, scales)], dim=1) as one HIP kernel
     (csrc/route.hip), bit-identical to it, with the backward as one kernel too: the gradient of a source is the s x s block sum of
@@ -505,7 +518,7 @@ def upsample_concat(tensors, scales):
     if not 1 <= len(tensors) <= ROUTE_MAX or len(scales) != len(tensors):
         raise ValueError("upsample_concat takes 1 to %d tensors and as many scales, got %d and %d" % (ROUTE_MAX, len(tensors), len(scales)))
     for i, t in enumerate(tensors):
-        _require_route_tensor(t, "input %d of upsample_concat" % i)
+        _require_nchw(t, "route_backend 'hip'", "input %d of upsample_concat (route_backend 'hip')" % i)
     for s in scales:
         if isinstance(s, bool) or not isinstance(s, int) or s not in ROUTE_SCALES:
             raise _lib.OrienMaskHipError("upsample_concat: scale %r; the scales are the integers %s" % (s, ROUTE_SCALES))
@@ -524,7 +537,7 @@ def split_channels(x, sizes):
     sizes = [int(c) for c in sizes]
     if not 1 <= len(sizes) <= ROUTE_MAX:
         raise ValueError("split_channels takes 1 to %d sizes, got %d" % (ROUTE_MAX, len(sizes)))
-    _require_route_tensor(x, "the input of split_channels")
+    _require_nchw(x, "route_backend 'hip'", "the input of split_channels (route_backend 'hip')")
     if min(sizes) < 1 or sum(sizes) != x.shape[1] or min(x.shape) < 1:
         raise _lib.OrienMaskHipError("split_channels: sizes %s do not split the %d channels of shape %s" % (sizes, x.shape[1], tuple(x.shape)))
     return _SplitChannels.apply(x, tuple(sizes))
@@ -543,16 +556,13 @@ class _SyncBNAct(torch.autograd.Function):
         import torch.distributed as dist
         B, C, H, W = x.shape
         dev = x.device
-        L = _lib.load()
         R = dist.get_world_size(group)
-        y = torch.empty_like(x)
-        save = torch.empty(4 * C, dtype=torch.float32, device=dev)      # save_mean | save_invstd (include/orienmask_hip.h)
+        y, save = _bn_forward_buffers(x)
         record = torch.empty(3 * C, dtype=torch.float64, device=dev)
         records = torch.empty(R * 3 * C, dtype=torch.float64, device=dev)
         n_total = torch.empty(1, dtype=torch.float64, device=dev)
         track = bn.running_mean is not None
-        stream = _lib.current_stream_ptr(dev)
-        ws = _workspace(dev, stream, L.om_bn_act_workspace_bytes(B, C, H, W))
+        L, stream, ws = _bn_scratch(x)
         with _device(dev):
             _lib.check(L.om_bn_sync_stats(_vp(x), B, C, H, W, _vp(record), ws.data_ptr(), ws.numel(), stream), "om_bn_sync_stats")
             dist.all_gather_into_tensor(records, record, group=group)
@@ -571,14 +581,10 @@ class _SyncBNAct(torch.autograd.Function):
         x, gamma, beta, save, n_total = ctx.saved_tensors
         B, C, H, W = x.shape
         dev = x.device
-        L = _lib.load()
         R = ctx.R
-        dy = dy.contiguous()
-        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        dgb = torch.empty((2, C), dtype=torch.float32, device=dev)
+        dy, dx, dgb = _bn_backward_buffers(ctx, x, dy)
         sums = torch.empty(2 * C, dtype=torch.float64, device=dev)
-        stream = _lib.current_stream_ptr(dev)
-        ws = _workspace(dev, stream, L.om_bn_act_workspace_bytes(B, C, H, W))
+        L, stream, ws = _bn_scratch(x)
         with _device(dev):
             _lib.check(L.om_bn_sync_backward_sums(
                 _vp(x), _vp(dy), B, C, H, W, _vp(gamma), _vp(beta), save.data_ptr(), save.data_ptr() + 8 * C, ctx.slope, _vp(sums),
@@ -589,8 +595,7 @@ class _SyncBNAct(torch.autograd.Function):
                 _lib.check(L.om_bn_sync_backward_dx(
                     _vp(x), _vp(dy), B, C, H, W, _vp(gamma), _vp(beta), save.data_ptr(), save.data_ptr() + 8 * C, ctx.slope,
                     _vp(sums_all), R, _vp(n_total), _vp(dx), stream), "om_bn_sync_backward_dx")
-        return (dx, dgb[0] if ctx.needs_input_grad[1] else None, dgb[1] if ctx.needs_input_grad[2] else None,
-                dy if ctx.has_residual and ctx.needs_input_grad[3] else None, None, None, None)
+        return _bn_grads(ctx, dx, dgb, dy)
 
 
 def _sync_world_size(group):
@@ -601,24 +606,22 @@ def _sync_world_size(group):
     return dist.get_world_size(group)
 
 
+def _check_bn_batch(bn, h, synced):
+    """What F.batch_norm refuses too: a cumulative moving average, and one value per channel in training mode on one rank."""
+    if bn.momentum is None:
+        raise ValueError("BatchNorm momentum=None (a cumulative moving average) is not supported")
+    if (bn.training or bn.running_mean is None) and h.numel() // h.shape[1] <= 1 and not synced:
+        raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(h.shape),))
+
+
 def bn_leaky(x, bn, residual=None, slope=LEAKY_SLOPE, sync=False, process_group=None):
     """leaky_relu(bn(x), slope) (+ residual) as the HIP block: `bn` is an nn.BatchNorm2d in training or eval mode, x (and residual)
     CUDA float32 NCHW-contiguous; anything else raises.  sync=True: in training mode and with more than one rank in `process_group`
     (None: the default group) the batch statistics are those of every rank's batch (_SyncBNAct); otherwise nothing is exchanged."""
     synced = sync and bn.training and _sync_world_size(process_group) > 1
-    _lib.require_cuda_tensor(x, "the BatchNorm input (backend 'hip')", torch.float32)
-    if bn.momentum is None:
-        raise ValueError("bn_leaky: momentum=None (a cumulative moving average) is not supported")
-    if x.dim() != 4 or not x.is_contiguous():
-        raise _lib.OrienMaskHipError("backend 'hip' takes NCHW-contiguous [B,C,H,W] activations, got strides %s for shape %s"
-                                     % (x.stride(), tuple(x.shape)))
-    if (bn.training or bn.running_mean is None) and x.numel() // x.shape[1] <= 1 and not synced:
-        raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(x.shape),))
-    if residual is not None:
-        _lib.require_cuda_tensor(residual, "residual", torch.float32)
-        if residual.shape != x.shape or not residual.is_contiguous():
-            raise _lib.OrienMaskHipError("residual must be NCHW-contiguous with the block's output shape %s, got %s strides %s"
-                                         % (tuple(x.shape), tuple(residual.shape), residual.stride()))
+    _require_nchw(x, "backend 'hip'", "the BatchNorm input (backend 'hip')")
+    _check_bn_batch(bn, x, synced)
+    _require_residual(residual, x.shape, x.device)
     if synced:
         return _SyncBNAct.apply(x, bn.weight, bn.bias, residual, bn, slope, process_group)
     return _BNAct.apply(x, bn.weight, bn.bias, residual, bn, slope)
@@ -651,11 +654,7 @@ class ConvBNLeaky(nn.Module):
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, backend="hip", conv_backend="torch",
                  conv_forward="torch", frozen=False):
         super().__init__()
-        if backend not in BACKENDS:
-            raise ValueError("backend must be one of %s, got %r" % (BACKENDS, backend))
-        if conv_backend not in CONV_BACKENDS:
-            raise ValueError("conv_backend must be one of %s, got %r" % (CONV_BACKENDS, conv_backend))
-        _check_conv_forward(conv_backend, conv_forward)
+        _check_backends(backend, conv_backend, conv_forward)
         self.backend = backend
         self.conv_backend = conv_backend
         self.conv_forward = conv_forward
@@ -705,17 +704,13 @@ class ConvBNLeaky(nn.Module):
         if self.frozen:
             return self._frozen_forward(x, residual)
         conv, bn, act = self.conv_block[0], self.conv_block[1], self.conv_block[2]
-        if bn.momentum is None:
-            raise ValueError("ConvBNLeaky: momentum=None (a cumulative moving average) is not supported")
         if self.conv_backend == "hip":
-            h = conv2d(x, conv.weight, None, conv.stride, conv.padding, **_forward_kw(self.conv_forward))
+            h = conv2d(x, conv.weight, None, conv.stride, conv.padding, forward=self.conv_forward)
         else:
             h = F.conv2d(x, conv.weight, None, conv.stride, conv.padding)
-        training = bn.training or bn.running_mean is None
-        synced = self.sync and bn.training and _sync_world_size(self.process_group) > 1
-        if training and h.numel() // h.shape[1] <= 1 and not synced:
-            raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(h.shape),))
+        _check_bn_batch(bn, h, self.sync and bn.training and _sync_world_size(self.process_group) > 1)
         if self.backend == "torch":
+            training = bn.training or bn.running_mean is None
             y = F.batch_norm(h, bn.running_mean, bn.running_var, bn.weight, bn.bias, training, bn.momentum, bn.eps)
             if training and bn.num_batches_tracked is not None:
                 bn.num_batches_tracked.add_(1)
@@ -787,13 +782,7 @@ class OrienMaskYOLOFPNPlus(nn.Module):
         if isinstance(frozen_stages, bool) or not isinstance(frozen_stages, int) or not 0 <= frozen_stages <= len(DARKNET_STAGES) + 1:
             raise ValueError("frozen_stages must be an int from 0 to %d (the number of backbone stages conv1 ... conv%d to freeze), "
                              "got %r" % (len(DARKNET_STAGES) + 1, len(DARKNET_STAGES) + 1, frozen_stages))
-        if backend not in BACKENDS:
-            raise ValueError("backend must be one of %s, got %r" % (BACKENDS, backend))
-        if conv_backend not in CONV_BACKENDS:
-            raise ValueError("conv_backend must be one of %s, got %r" % (CONV_BACKENDS, conv_backend))
-        _check_conv_forward(conv_backend, conv_forward)
-        if route_backend not in ROUTE_BACKENDS:
-            raise ValueError("route_backend must be one of %s, got %r" % (ROUTE_BACKENDS, route_backend))
+        _check_backends(backend, conv_backend, conv_forward, route_backend)
         self.num_anchors = num_anchors
         self.num_classes = num_classes
         self.pretrained = pretrained
@@ -896,7 +885,7 @@ class OrienMaskYOLOFPNPlus(nn.Module):
         """A head's nn.Conv2d: the module itself, or conv2d on its parameters (conv_backend 'hip')."""
         m = self._by_name[name]
         if self.conv_backend == "hip":
-            return conv2d(x, m.weight, m.bias, m.stride, m.padding, **_forward_kw(self.conv_forward))
+            return conv2d(x, m.weight, m.bias, m.stride, m.padding, forward=self.conv_forward)
         return m(x)
 
     def _bbox_head(self, s, x):

@@ -59,7 +59,8 @@ import pytest
 import torch
 
 import backward_audit as A
-from conftest import ANCHOR_MASK, ANCHORS_YOLOV4, GOLDEN, fixture_weights_and_input
+from conftest import GOLDEN, fixture_weights_and_input
+import train_step as T
 from orienmask_amd import builder, synth, train
 
 pytestmark = pytest.mark.gpu
@@ -91,11 +92,7 @@ def dev(built):
 
 
 def _loss_backward(dev, B, H, W):
-    cfg = dict(type="OrienMaskYOLOMultiScaleLoss", grid_size=[[H // 32, W // 32], [H // 16, W // 16], [H // 8, W // 8]],
-               image_size=[H, W], anchors=ANCHORS_YOLOV4, anchor_mask=ANCHOR_MASK, num_classes=80, center_region=0.6,
-               valid_region=0.6, label_smooth=False, obj_ignore_threshold=0.7, weight=[1, 1, 1, 1, 1, 20, 20],
-               scales_weight=[1, 1, 1], scales_id=["S32", "S16", "S08"])
-    loss_fn = builder.build(cfg, train)
+    loss_fn = builder.build(T.loss_cfg(H, W), train)
     target = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in synth.synth_targets(51, B, H, W, 6))
 
     def backward(heads):

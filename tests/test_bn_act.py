@@ -16,10 +16,10 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from conftest import ANCHOR_MASK, ANCHORS_YOLOV4, GOLDEN, fixture_weights_and_input
+from conftest import GOLDEN, fixture_weights_and_input
 import bn_act_np as N
-from orienmask_amd import arch, builder, lib as omlib, train
-from orienmask_amd import optim as O
+import train_step as T
+from orienmask_amd import arch, lib as omlib, train
 
 pytestmark = pytest.mark.gpu
 
@@ -321,43 +321,25 @@ def test_saved_tensors_of_one_block(dev):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the model
-def _step(net, x, cot):
-    out = net(x)
-    heads = [t for pair in out for t in pair]
-    torch.autograd.backward(heads, cot)
-    return heads
-
-
 @pytest.mark.parametrize("fixture", ["train_step_f96_b2", "train_step_bneval_f96_b2"])
 def test_model_against_the_torch_backend_and_the_reference_step(dev, fixture):
     """'hip' against 'torch' on the same GPU: heads within 1e-4 of scale.  Against the reference's recorded step (CPU): the 'hip'
     model's relative-L2 gradient error (root mean square over the recorded tensors, each relative to its own norm) is at most twice
     the 'torch' model's on this GPU -- the convolutions' error is common to both."""
     g = np.load(os.path.join(GOLDEN, fixture + ".npz"))
-    sd, x = fixture_weights_and_input(g)
-    x = x.to(dev)
     errs, heads_of, nets = {}, {}, {}
     for backend in ("hip", "torch"):
-        net = train.OrienMaskYOLOFPNPlus(3, 80, backbone_batchnorm_eval=bool(int(g["bneval"])), backend=backend)
-        net.load_state_dict(sd, strict=True)
-        net = net.to(dev).train()
-        shapes = [g[k].shape for k in N.HEAD_KEYS]
-        cot = [torch.from_numpy(c).to(dev) for c in N.cotangents(int(g["gseed"]), shapes)]
-        heads_of[backend] = [t.detach() for t in _step(net, x, cot)]
-        params = dict(net.named_parameters())
-        errs[backend] = [N.rel_l2(params[n].grad.cpu().numpy(), g["grad_%d" % i]) for i, n in enumerate(N.GRAD_NAMES)]
-        l2 = np.array([p.grad.double().norm().item() for p in params.values()])
+        heads_of[backend], grads, _, errs[backend], nets[backend] = T.recorded_step(dev, g, backend=backend)
+        l2 = np.array([v.double().norm().item() for v in grads.values()])
         errs[backend + "_l2"] = float(np.abs(l2 / g["grad_l2"] - 1).max())
-        nets[backend] = net
     for k, a, b in zip(N.HEAD_KEYS, heads_of["hip"], heads_of["torch"]):
         assert (a - b).abs().max().item() <= 1e-4 * b.abs().max().item(), k
         print("%-8s against the reference's CPU heads: %.3g of scale" % (k, N.rel_max(a.cpu().numpy(), g[k])))
     for i, n in enumerate(N.GRAD_NAMES):
         print("%-50s hip %.3g  torch %.3g" % (n, errs["hip"][i], errs["torch"][i]))
-    rms = {b: float(np.sqrt(np.mean(np.square(errs[b])))) for b in ("hip", "torch")}
     print("gradient error, rms over tensors: hip %.3g  torch %.3g; norms of all parameters: hip %.3g  torch %.3g"
-          % (rms["hip"], rms["torch"], errs["hip_l2"], errs["torch_l2"]))
-    assert rms["hip"] <= 2 * rms["torch"]
+          % (T.rms(errs["hip"]), T.rms(errs["torch"]), errs["hip_l2"], errs["torch_l2"]))
+    assert T.rms(errs["hip"]) <= 2 * T.rms(errs["torch"])
     after = nets["hip"].state_dict()
     layers = [str(k) for k in g["bn_layers"]]
     assert N.rel_l2(np.concatenate([after[k + ".running_mean"].cpu().numpy() for k in layers]), g["running_mean"]) <= 1e-4
@@ -381,29 +363,6 @@ def test_eval_forward_matches_the_inference_fixture(dev):
 
 def test_one_trainer_step_changes_every_parameter(dev):
     """trainer/trainer.py:42-55 with this package's pieces: build_train_model -> the HIP loss -> backward -> the HIP SGD step."""
-    h = w = 96
-    loss_cfg = dict(type="OrienMaskYOLOMultiScaleLoss", grid_size=[[h // 32, w // 32], [h // 16, w // 16], [h // 8, w // 8]],
-                    image_size=[h, w], anchors=ANCHORS_YOLOV4, anchor_mask=ANCHOR_MASK, num_classes=80, center_region=0.6,
-                    valid_region=0.6, label_smooth=False, obj_ignore_threshold=0.7, weight=[1, 1, 1, 1, 1, 20, 20],
-                    scales_weight=[1, 1, 1], scales_id=["S32", "S16", "S08"])
-    from orienmask_amd import synth
-    torch.manual_seed(3)
-    with torch.cuda.device(dev):
-        net = builder.build_train_model(dict(type="OrienMaskYOLOFPNPlus", num_anchors=3, num_classes=80, pretrained=None,
-                                             freeze_backbone=False, backbone_batchnorm_eval=False))
+    _, _, net = T.trainer_steps(dev, {}, 1)
     assert net.training and net.backend == "hip" and next(net.parameters()).device == dev
-    loss_fn = builder.build(loss_cfg, train)
-    optimizer = builder.build_optimizer(dict(type="SGD", lr=1e-3, momentum=0.9, weight_decay=5e-4), 1, net)
-    assert type(optimizer) is O.SGD
-    before = [p.detach().clone() for p in net.parameters()]
-    target = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in synth.synth_targets(51, 2, h, w, 6))
-    x = synth.synth_image_batch(8, 2, h, w).to(dev)
-    loss, _, _ = loss_fn(net(x), target, training=True)
-    assert torch.isfinite(loss)
-    loss.backward()
-    assert all(p.grad is not None and torch.isfinite(p.grad).all() for p in net.parameters())
-    optimizer.step()
-    torch.cuda.synchronize(dev)
-    unchanged = [n for (n, p), b in zip(net.named_parameters(), before) if torch.equal(p.detach(), b)]
-    assert not unchanged, unchanged[:5]
     assert all(int(v) == 1 for k, v in net.state_dict().items() if k.endswith("num_batches_tracked"))

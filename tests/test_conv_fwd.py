@@ -7,18 +7,16 @@ be at most TWICE torch-CPU-float32's on the same inputs, with a floor of 2e-7 (t
 pre-filled with NaN, so "every element finite" is "every element written".
 
 Worst kernel / torch-CPU ratios measured on an MI355X are recorded in DESIGN.md 3.21."""
-import ctypes
 import os
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import ANCHOR_MASK, ANCHORS_YOLOV4, GOLDEN, fixture_weights_and_input
-import bn_act_np as N
+from conftest import GOLDEN
 import conv_fwd_np as C
-from orienmask_amd import arch, builder, lib as omlib, train
-from orienmask_amd import optim as O
+import train_step as T
+from orienmask_amd import arch, lib as omlib, train
 
 pytestmark = pytest.mark.gpu
 
@@ -33,18 +31,6 @@ def dev(built):
     return torch.device("cuda:0")
 
 
-def _layer_cases(size):
-    """Every distinct (cin, cout, ksize, stride, H, W) of the two models' convolutions at this image size; H, W are the input's."""
-    out = []
-    for spec in list(arch.fpnplus_convs()) + list(arch.yolo_convs()):
-        d = arch.layer_div(spec)
-        case = (spec.cin, spec.cout, spec.ksize, spec.stride, size[0] // d * spec.stride, size[1] // d * spec.stride)
-        if case not in out:
-            out.append(case)
-    return out
-
-
-SWEEP = [(2,) + c for c in _layer_cases((96, 96))] + [(2,) + c for c in _layer_cases((160, 128)) if c not in _layer_cases((96, 96))]
 # the plain head convolutions are the ones with a bias
 _HEADS = {(s.cin, s.cout, s.ksize, s.stride) for s in list(arch.fpnplus_convs()) + list(arch.yolo_convs()) if not s.bn}
 # (B, cin, cout, ksize, stride, H, W)
@@ -83,14 +69,10 @@ def _reference(case, seed, bias=None):
     return _REFERENCES[key]
 
 
-def _vp(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
 def _call(dev, x, w, b, ks, stride, y):
     L = omlib.load()
     B, cin, H, W = x.shape
-    return L.om_conv2d_forward(_vp(x), _vp(w), _vp(b), B, cin, H, W, w.shape[0], ks, stride, _vp(y), omlib.current_stream_ptr(dev))
+    return L.om_conv2d_forward(T.vp(x), T.vp(w), T.vp(b), B, cin, H, W, w.shape[0], ks, stride, T.vp(y), omlib.current_stream_ptr(dev))
 
 
 def _hip(dev, d):
@@ -117,18 +99,14 @@ def _judge(dev, case, seed):
     return ratio
 
 
-def _id(case):
-    return "x".join(map(str, case))
-
-
 # ---------------------------------------------------------------------------------------------------------------- C ABI
-@pytest.mark.parametrize("case", SWEEP, ids=_id)
+@pytest.mark.parametrize("case", T.SWEEP, ids=T.case_id)
 def test_every_layer_geometry_against_float64(dev, case):
     """Every distinct convolution of the two models at 96 x 96 and 160 x 128, B = 2; the head convolutions with a bias."""
     _judge(dev, case, sum(case) * 5 + 1)
 
 
-@pytest.mark.parametrize("case", SPECIAL, ids=_id)
+@pytest.mark.parametrize("case", SPECIAL, ids=T.case_id)
 def test_special_shapes_against_float64(dev, case):
     """The smallest shape, channel counts that are no tile multiple (3, 5, 7, 18, 255), planes of 289 floats, odd and even stride-2
     inputs, tiny maps with deep channels (tiles that span several images and end mid-image; at 1 x 1 every cell is at an image
@@ -136,14 +114,14 @@ def test_special_shapes_against_float64(dev, case):
     _judge(dev, case, sum(case) * 3 + 2)
 
 
-@pytest.mark.parametrize("case", LARGE, ids=_id)
+@pytest.mark.parametrize("case", LARGE, ids=T.case_id)
 def test_full_size_shapes_against_float64(dev, case):
     """B = 2 at 544 x 544: many tiles, and the workload's own k (4608 for the 512 -> 1024 3x3 layer)."""
     _judge(dev, case, 17)
 
 
 @pytest.mark.parametrize("case", [(5, 16, 32, 3, 1, 3, 5), (3, 5, 7, 3, 1, 17, 17), (5, 32, 64, 3, 2, 8, 8), (4, 64, 32, 1, 1, 17, 17)],
-                         ids=_id)
+                         ids=T.case_id)
 def test_batch_independence(dev, case):
     """The tiles run over the flat (image, cell) index: an image's y must not depend on its neighbours in the batch or its place
     in it.  The batch equals, bit for bit, every image run alone, and the reversed batch reversed back."""
@@ -157,7 +135,7 @@ def test_batch_independence(dev, case):
     assert np.array_equal(back.view(np.uint32), whole.view(np.uint32)), case
 
 
-@pytest.mark.parametrize("case", [(3, 5, 7, 3, 2, 17, 17), (2, 64, 255, 1, 1, 17, 17)], ids=_id)
+@pytest.mark.parametrize("case", [(3, 5, 7, 3, 2, 17, 17), (2, 64, 255, 1, 1, 17, 17)], ids=T.case_id)
 def test_neighbours_untouched(dev, case):
     """y is a view in the middle of a larger buffer: the sentinel on both sides is intact after the call."""
     d, truth, _ = _reference(case, 43)
@@ -175,7 +153,7 @@ def test_neighbours_untouched(dev, case):
     assert C.rel_max(got, truth) <= 1e-5
 
 
-@pytest.mark.parametrize("case", [(2, 512, 1024, 3, 1, 3, 3), (2, 32, 64, 3, 2, 48, 48), (2, 3, 32, 3, 1, 544, 544)], ids=_id)
+@pytest.mark.parametrize("case", [(2, 512, 1024, 3, 1, 3, 3), (2, 32, 64, 3, 2, 48, 48), (2, 3, 32, 3, 1, 544, 544)], ids=T.case_id)
 def test_rerun_is_bit_identical(dev, case):
     """The same call twice; the first case is the shape on which MIOpen's forward does not repeat its bits."""
     d = _reference(case, 23)[0]
@@ -206,10 +184,10 @@ def test_refusals_on_the_device(dev):
         assert b"ksize" in L.om_last_error()
     w = torch.randn(cout, cin, 3, 3, device=dev)
     st = omlib.current_stream_ptr(dev)
-    assert L.om_conv2d_forward(_vp(x), _vp(w), None, 0, cin, H, W, cout, 3, 1, _vp(y), st) == OM_EINVAL
-    assert L.om_conv2d_forward(None, _vp(w), None, B, cin, H, W, cout, 3, 1, _vp(y), st) == OM_EINVAL
-    assert L.om_conv2d_forward(_vp(x), None, None, B, cin, H, W, cout, 3, 1, _vp(y), st) == OM_EINVAL
-    assert L.om_conv2d_forward(_vp(x), _vp(w), None, B, cin, H, W, cout, 3, 1, None, st) == OM_EINVAL
+    assert L.om_conv2d_forward(T.vp(x), T.vp(w), None, 0, cin, H, W, cout, 3, 1, T.vp(y), st) == OM_EINVAL
+    assert L.om_conv2d_forward(None, T.vp(w), None, B, cin, H, W, cout, 3, 1, T.vp(y), st) == OM_EINVAL
+    assert L.om_conv2d_forward(T.vp(x), None, None, B, cin, H, W, cout, 3, 1, T.vp(y), st) == OM_EINVAL
+    assert L.om_conv2d_forward(T.vp(x), T.vp(w), None, B, cin, H, W, cout, 3, 1, None, st) == OM_EINVAL
     torch.cuda.synchronize(dev)
     assert torch.isnan(y).all()
     omlib.check(_call(dev, x, w, None, 3, 1, y), "om_conv2d_forward")
@@ -259,13 +237,6 @@ def test_module_function_refusals(dev):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the model
-def _step(net, x, cot):
-    out = net(x)
-    heads = [t for pair in out for t in pair]
-    torch.autograd.backward(heads, cot)
-    return heads
-
-
 @pytest.mark.parametrize("fixture", ["train_step_f96_b2", "train_step_bneval_f96_b2"])
 def test_model_against_the_torch_forward_and_the_reference_step(dev, fixture):
     """conv_forward 'hip' against 'torch' (both models with backend 'hip' and conv_backend 'hip') on the same GPU, the 'torch' run
@@ -273,70 +244,25 @@ def test_model_against_the_torch_forward_and_the_reference_step(dev, fixture):
     over tensors of the relative-L2 error of the heads, and of the parameter gradients, is for 'hip' at most twice that of 'torch'
     measured here -- both are float32 evaluations in another summation order than the recording's."""
     g = np.load(os.path.join(GOLDEN, fixture + ".npz"))
-    sd, x = fixture_weights_and_input(g)
-    x = x.to(dev)
     herr, gerr = {}, {}
     for cf in ("torch", "hip"):
-        net = train.OrienMaskYOLOFPNPlus(3, 80, backbone_batchnorm_eval=bool(int(g["bneval"])), backend="hip", conv_backend="hip",
-                                         conv_forward=cf)
-        net.load_state_dict(sd, strict=True)
-        net = net.to(dev).train()
-        shapes = [g[k].shape for k in N.HEAD_KEYS]
-        cot = [torch.from_numpy(c).to(dev) for c in N.cotangents(int(g["gseed"]), shapes)]
-        if cf == "torch":
-            with torch.backends.cudnn.flags(deterministic=True):
-                heads = _step(net, x, cot)
-        else:
-            assert not torch.backends.cudnn.deterministic
-            heads = _step(net, x, cot)
-        heads = [t.detach().cpu().numpy() for t in heads]
-        params = dict(net.named_parameters())
-        assert all(np.isfinite(h).all() for h in heads), cf
-        assert all(p.grad is not None and torch.isfinite(p.grad).all() for p in params.values()), cf
-        herr[cf] = [N.rel_l2(h, g[k]) for k, h in zip(N.HEAD_KEYS, heads)]
-        gerr[cf] = [N.rel_l2(params[n].grad.cpu().numpy(), g["grad_%d" % i]) for i, n in enumerate(N.GRAD_NAMES)]
-    rms = lambda v: float(np.sqrt(np.mean(np.square(v))))      # noqa: E731
-    print("%s: head error, rms over tensors: conv_forward hip %.3g  torch %.3g" % (fixture, rms(herr["hip"]), rms(herr["torch"])))
-    print("%s: gradient error, rms over tensors: conv_forward hip %.3g  torch %.3g" % (fixture, rms(gerr["hip"]), rms(gerr["torch"])))
-    assert rms(herr["hip"]) <= 2 * rms(herr["torch"])
-    assert rms(gerr["hip"]) <= 2 * rms(gerr["torch"])
+        assert not torch.backends.cudnn.deterministic      # the flag of the 'torch' run ends with its step
+        _, _, herr[cf], gerr[cf], _ = T.recorded_step(dev, g, deterministic=cf == "torch", backend="hip", conv_backend="hip",
+                                                      conv_forward=cf)
+    print("%s: head error, rms over tensors: conv_forward hip %.3g  torch %.3g" % (fixture, T.rms(herr["hip"]), T.rms(herr["torch"])))
+    print("%s: gradient error, rms over tensors: conv_forward hip %.3g  torch %.3g" % (fixture, T.rms(gerr["hip"]), T.rms(gerr["torch"])))
+    assert T.rms(herr["hip"]) <= 2 * T.rms(herr["torch"])
+    assert T.rms(gerr["hip"]) <= 2 * T.rms(gerr["torch"])
 
 
 def test_one_trainer_step_repeats_its_bits_without_the_deterministic_flag(dev):
     """build_train_model with conv_backend and conv_forward 'hip' -> the HIP loss -> backward -> the HIP SGD step, twice from the
     same seed with torch.backends.cudnn.deterministic left False: the loss and every parameter are bit-identical."""
     assert not torch.backends.cudnn.deterministic
-    h = w = 96
-    loss_cfg = dict(type="OrienMaskYOLOMultiScaleLoss", grid_size=[[h // 32, w // 32], [h // 16, w // 16], [h // 8, w // 8]],
-                    image_size=[h, w], anchors=ANCHORS_YOLOV4, anchor_mask=ANCHOR_MASK, num_classes=80, center_region=0.6,
-                    valid_region=0.6, label_smooth=False, obj_ignore_threshold=0.7, weight=[1, 1, 1, 1, 1, 20, 20],
-                    scales_weight=[1, 1, 1], scales_id=["S32", "S16", "S08"])
-    from orienmask_amd import synth
-    target = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in synth.synth_targets(51, 2, h, w, 6))
-    x = synth.synth_image_batch(8, 2, h, w).to(dev)
-    results, losses = [], []
-    for _ in range(2):
-        torch.manual_seed(3)
-        with torch.cuda.device(dev):
-            net = builder.build_train_model(dict(type="OrienMaskYOLOFPNPlus", num_anchors=3, num_classes=80, pretrained=None,
-                                                 freeze_backbone=False, backbone_batchnorm_eval=False, conv_backend="hip",
-                                                 conv_forward="hip"))
-        assert net.training and net.backend == "hip" and net.conv_backend == "hip" and net.conv_forward == "hip"
+    runs = [T.trainer_steps(dev, dict(conv_backend="hip", conv_forward="hip"), 1) for _ in range(2)]
+    for _, _, net in runs:
+        assert net.backend == "hip" and net.conv_backend == "hip" and net.conv_forward == "hip"
         assert all(m.conv_forward == "hip" for m in net.modules() if isinstance(m, train.ConvBNLeaky))
-        loss_fn = builder.build(loss_cfg, train)
-        optimizer = builder.build_optimizer(dict(type="SGD", lr=1e-3, momentum=0.9, weight_decay=5e-4), 1, net)
-        assert type(optimizer) is O.SGD
-        before = [p.detach().clone() for p in net.parameters()]
-        loss, _, _ = loss_fn(net(x), target, training=True)
-        assert torch.isfinite(loss)
-        loss.backward()
-        assert all(p.grad is not None and torch.isfinite(p.grad).all() for p in net.parameters())
-        optimizer.step()
-        torch.cuda.synchronize(dev)
-        unchanged = [n for (n, p), b in zip(net.named_parameters(), before) if torch.equal(p.detach(), b)]
-        assert not unchanged, unchanged[:5]
-        losses.append(loss.detach().cpu().numpy().view(np.uint32).copy())
-        results.append([p.detach().clone() for p in net.parameters()])
-    assert np.array_equal(losses[0], losses[1])
-    differ = [n for (n, _), a, b in zip(net.named_parameters(), *results) if not torch.equal(a, b)]
+    assert np.array_equal(runs[0][0][0], runs[1][0][0])
+    differ = [n for (n, _), a, b in zip(runs[0][2].named_parameters(), runs[0][1][0], runs[1][1][0]) if not torch.equal(a, b)]
     assert not differ, differ[:5]

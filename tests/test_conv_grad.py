@@ -7,7 +7,6 @@ dx, dw and dbias the kernel's maximum error over the truth's scale may be at mos
 a floor of 2e-7 (about three half-units in the last place of the scale).
 
 Worst kernel / torch-CPU ratios measured on an MI355X are recorded in DESIGN.md 3.19."""
-import ctypes
 import os
 
 import numpy as np
@@ -15,11 +14,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from conftest import ANCHOR_MASK, ANCHORS_YOLOV4, GOLDEN, fixture_weights_and_input
+from conftest import GOLDEN
 import bn_act_np as N
 import conv_grad_np as G
-from orienmask_amd import arch, builder, lib as omlib, train
-from orienmask_amd import optim as O
+import train_step as T
+from orienmask_amd import lib as omlib, train
 
 pytestmark = pytest.mark.gpu
 
@@ -34,18 +33,6 @@ def dev(built):
     return torch.device("cuda:0")
 
 
-def _layer_cases(size):
-    """Every distinct (cin, cout, ksize, stride, H, W) of the two models' convolutions at this image size; H, W are the input's."""
-    out = []
-    for spec in list(arch.fpnplus_convs()) + list(arch.yolo_convs()):
-        d = arch.layer_div(spec)
-        case = (spec.cin, spec.cout, spec.ksize, spec.stride, size[0] // d * spec.stride, size[1] // d * spec.stride)
-        if case not in out:
-            out.append(case)
-    return out
-
-
-SWEEP = [(2,) + c for c in _layer_cases((96, 96))] + [(2,) + c for c in _layer_cases((160, 128)) if c not in _layer_cases((96, 96))]
 # (B, cin, cout, ksize, stride, H, W)
 SPECIAL = [(1, 1, 1, 1, 1, 1, 1),
            (3, 5, 7, 1, 1, 17, 17), (3, 5, 7, 3, 1, 17, 17), (3, 5, 7, 3, 2, 17, 17),
@@ -74,10 +61,6 @@ def _reference(case, seed, want=ALL):
     return _REFERENCES[key]
 
 
-def _vp(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
 def _hip(dev, d, want=ALL, ws=None):
     """The gradients through the C ABI: outputs pre-filled with NaN, the workspace with 0xFF.  -> dict of numpy arrays."""
     L = omlib.load()
@@ -96,9 +79,9 @@ def _hip(dev, d, want=ALL, ws=None):
     dw = nan(w) if "dw" in want else None
     db = torch.full((cout,), float("nan"), device=dev) if "db" in want else None
     if dx is not None:
-        omlib.check(L.om_conv2d_grad_input(_vp(dy), _vp(w), *geom, _vp(dx), _vp(ws), ws.numel(), st), "om_conv2d_grad_input")
+        omlib.check(L.om_conv2d_grad_input(T.vp(dy), T.vp(w), *geom, T.vp(dx), T.vp(ws), ws.numel(), st), "om_conv2d_grad_input")
     if dw is not None or db is not None:
-        omlib.check(L.om_conv2d_grad_weight(_vp(x), _vp(dy), *geom, _vp(dw), _vp(db), _vp(ws), ws.numel(), st), "om_conv2d_grad_weight")
+        omlib.check(L.om_conv2d_grad_weight(T.vp(x), T.vp(dy), *geom, T.vp(dw), T.vp(db), T.vp(ws), ws.numel(), st), "om_conv2d_grad_weight")
     torch.cuda.synchronize(dev)
     return {k: v.cpu().numpy() for k, v in (("dx", dx), ("dw", dw), ("db", db)) if v is not None}
 
@@ -120,31 +103,27 @@ def _judge(dev, case, seed, want=ALL):
     return ratios
 
 
-def _id(case):
-    return "x".join(map(str, case))
-
-
 # ---------------------------------------------------------------------------------------------------------------- C ABI
-@pytest.mark.parametrize("case", SWEEP, ids=_id)
+@pytest.mark.parametrize("case", T.SWEEP, ids=T.case_id)
 def test_every_layer_geometry_against_float64(dev, case):
     """Every distinct convolution of the two models at 96 x 96 and 160 x 128, B = 2."""
     _judge(dev, case, sum(case) * 5 + 1)
 
 
-@pytest.mark.parametrize("case", SPECIAL, ids=_id)
+@pytest.mark.parametrize("case", SPECIAL, ids=T.case_id)
 def test_special_shapes_against_float64(dev, case):
     """The smallest shape, channel counts that are no tile multiple (3, 5, 7, 18, 255), planes of 289 floats, odd stride-2 inputs,
     tiny maps with deep channels, a batch that is no power of two."""
     _judge(dev, case, sum(case) * 3 + 2)
 
 
-@pytest.mark.parametrize("case,want", LARGE, ids=[_id(c) for c, _ in LARGE])
+@pytest.mark.parametrize("case,want", LARGE, ids=[T.case_id(c) for c, _ in LARGE])
 def test_full_size_shapes_against_float64(dev, case, want):
     """B = 2 at 544 x 544: the split-k and multi-tile paths at the workload's own k."""
     _judge(dev, case, 17, want)
 
 
-@pytest.mark.parametrize("case", [(2, 32, 64, 3, 2, 48, 48), (2, 128, 64, 1, 1, 24, 24), (2, 3, 32, 3, 1, 544, 544)], ids=_id)
+@pytest.mark.parametrize("case", [(2, 32, 64, 3, 2, 48, 48), (2, 128, 64, 1, 1, 24, 24), (2, 3, 32, 3, 1, 544, 544)], ids=T.case_id)
 def test_rerun_is_bit_identical(dev, case):
     """The same call twice, and once more after another call has used the same workspace."""
     want = ("dw", "db") if case[-1] == 544 else ALL
@@ -185,29 +164,29 @@ def test_refusals_on_the_device(dev):
         w = torch.randn(cout, cin, ks, ks, device=dev)
         dx, dw = torch.full_like(x, float("nan")), torch.full_like(w, float("nan"))
         assert L.om_conv2d_grad_workspace_bytes(B, cin, H, W, cout, ks, stride) == 0
-        assert L.om_conv2d_grad_input(_vp(dy), _vp(w), B, cin, H, W, cout, ks, stride, _vp(dx), _vp(ws), ws.numel(), st) == OM_EINVAL
+        assert L.om_conv2d_grad_input(T.vp(dy), T.vp(w), B, cin, H, W, cout, ks, stride, T.vp(dx), T.vp(ws), ws.numel(), st) == OM_EINVAL
         assert b"ksize" in L.om_last_error()
-        assert L.om_conv2d_grad_weight(_vp(x), _vp(dy), B, cin, H, W, cout, ks, stride, _vp(dw), None, _vp(ws), ws.numel(), st) == OM_EINVAL
+        assert L.om_conv2d_grad_weight(T.vp(x), T.vp(dy), B, cin, H, W, cout, ks, stride, T.vp(dw), None, T.vp(ws), ws.numel(), st) == OM_EINVAL
         torch.cuda.synchronize(dev)
         assert torch.isnan(dx).all() and torch.isnan(dw).all()
     geom = (B, cin, H, W, cout, 3, 1)
     dy = torch.randn(B, cout, H, W, device=dev)
     w = torch.randn(cout, cin, 3, 3, device=dev)
     dx, dw = torch.full_like(x, float("nan")), torch.full_like(w, float("nan"))
-    assert L.om_conv2d_grad_input(None, _vp(w), *geom, _vp(dx), _vp(ws), ws.numel(), st) == OM_EINVAL
-    assert L.om_conv2d_grad_input(_vp(dy), None, *geom, _vp(dx), _vp(ws), ws.numel(), st) == OM_EINVAL
-    assert L.om_conv2d_grad_input(_vp(dy), _vp(w), *geom, None, _vp(ws), ws.numel(), st) == OM_EINVAL
-    assert L.om_conv2d_grad_weight(None, _vp(dy), *geom, _vp(dw), None, _vp(ws), ws.numel(), st) == OM_EINVAL
-    assert L.om_conv2d_grad_weight(_vp(x), None, *geom, _vp(dw), None, _vp(ws), ws.numel(), st) == OM_EINVAL
-    assert L.om_conv2d_grad_weight(_vp(x), _vp(dy), *geom, None, None, _vp(ws), ws.numel(), st) == OM_EINVAL
+    assert L.om_conv2d_grad_input(None, T.vp(w), *geom, T.vp(dx), T.vp(ws), ws.numel(), st) == OM_EINVAL
+    assert L.om_conv2d_grad_input(T.vp(dy), None, *geom, T.vp(dx), T.vp(ws), ws.numel(), st) == OM_EINVAL
+    assert L.om_conv2d_grad_input(T.vp(dy), T.vp(w), *geom, None, T.vp(ws), ws.numel(), st) == OM_EINVAL
+    assert L.om_conv2d_grad_weight(None, T.vp(dy), *geom, T.vp(dw), None, T.vp(ws), ws.numel(), st) == OM_EINVAL
+    assert L.om_conv2d_grad_weight(T.vp(x), None, *geom, T.vp(dw), None, T.vp(ws), ws.numel(), st) == OM_EINVAL
+    assert L.om_conv2d_grad_weight(T.vp(x), T.vp(dy), *geom, None, None, T.vp(ws), ws.numel(), st) == OM_EINVAL
     need = L.om_conv2d_grad_workspace_bytes(*geom)
     assert 0 < need <= ws.numel()                 # k = 18432: several splits
-    assert L.om_conv2d_grad_weight(_vp(x), _vp(dy), *geom, _vp(dw), None, _vp(ws), need - 1, st) == OM_ENOMEM
+    assert L.om_conv2d_grad_weight(T.vp(x), T.vp(dy), *geom, T.vp(dw), None, T.vp(ws), need - 1, st) == OM_ENOMEM
     assert b"workspace" in L.om_last_error()
-    assert L.om_conv2d_grad_weight(_vp(x), _vp(dy), *geom, _vp(dw), None, None, need, st) == OM_ENOMEM
+    assert L.om_conv2d_grad_weight(T.vp(x), T.vp(dy), *geom, T.vp(dw), None, None, need, st) == OM_ENOMEM
     torch.cuda.synchronize(dev)
     assert torch.isnan(dx).all() and torch.isnan(dw).all()
-    omlib.check(L.om_conv2d_grad_weight(_vp(x), _vp(dy), *geom, _vp(dw), None, _vp(ws), need, st), "om_conv2d_grad_weight")
+    omlib.check(L.om_conv2d_grad_weight(T.vp(x), T.vp(dy), *geom, T.vp(dw), None, T.vp(ws), need, st), "om_conv2d_grad_weight")
     torch.cuda.synchronize(dev)
     assert torch.isfinite(dw).all()
 
@@ -296,72 +275,29 @@ def reproducible_forward():
         yield
 
 
-def _step(net, x, cot):
-    out = net(x)
-    heads = [t for pair in out for t in pair]
-    torch.autograd.backward(heads, cot)
-    return heads
-
-
 @pytest.mark.parametrize("fixture", ["train_step_f96_b2", "train_step_bneval_f96_b2"])
 def test_model_against_the_torch_conv_backend_and_the_reference_step(dev, reproducible_forward, fixture):
     """conv_backend 'hip' against 'torch' (both with backend 'hip') on the same GPU: the heads are bit-identical (the forward is
     shared).  Against the reference's recorded step (CPU float32): the 'hip' model's relative-L2 gradient error (root mean square
     over the recorded tensors) is at most twice the 'torch' model's -- both are float32 against a CPU float32 recording."""
     g = np.load(os.path.join(GOLDEN, fixture + ".npz"))
-    sd, x = fixture_weights_and_input(g)
-    x = x.to(dev)
     errs, heads_of = {}, {}
     for cb in ("hip", "torch"):
-        net = train.OrienMaskYOLOFPNPlus(3, 80, backbone_batchnorm_eval=bool(int(g["bneval"])), backend="hip", conv_backend=cb)
-        net.load_state_dict(sd, strict=True)
-        net = net.to(dev).train()
-        shapes = [g[k].shape for k in N.HEAD_KEYS]
-        cot = [torch.from_numpy(c).to(dev) for c in N.cotangents(int(g["gseed"]), shapes)]
-        heads_of[cb] = [t.detach() for t in _step(net, x, cot)]
-        params = dict(net.named_parameters())
-        assert all(p.grad is not None and torch.isfinite(p.grad).all() for p in params.values()), cb
-        errs[cb] = [N.rel_l2(params[n].grad.cpu().numpy(), g["grad_%d" % i]) for i, n in enumerate(N.GRAD_NAMES)]
+        heads_of[cb], _, _, errs[cb], _ = T.recorded_step(dev, g, backend="hip", conv_backend=cb)
     for k, a, b in zip(N.HEAD_KEYS, heads_of["hip"], heads_of["torch"]):
         assert torch.equal(a, b), k
     for i, n in enumerate(N.GRAD_NAMES):
         print("%-50s hip %.3g  torch %.3g" % (n, errs["hip"][i], errs["torch"][i]))
-    rms = {b: float(np.sqrt(np.mean(np.square(errs[b])))) for b in ("hip", "torch")}
-    print("%s: gradient error, rms over tensors: conv_backend hip %.3g  torch %.3g" % (fixture, rms["hip"], rms["torch"]))
-    assert rms["hip"] <= 2 * rms["torch"]
+    print("%s: gradient error, rms over tensors: conv_backend hip %.3g  torch %.3g" % (fixture, T.rms(errs["hip"]), T.rms(errs["torch"])))
+    assert T.rms(errs["hip"]) <= 2 * T.rms(errs["torch"])
 
 
 def test_one_trainer_step_with_hip_convolution_gradients(dev, reproducible_forward):
     """build_train_model with conv_backend 'hip' -> the HIP loss -> backward -> the HIP SGD step: every parameter changes, and two
     such steps from the same seed leave bit-identical parameters."""
-    h = w = 96
-    loss_cfg = dict(type="OrienMaskYOLOMultiScaleLoss", grid_size=[[h // 32, w // 32], [h // 16, w // 16], [h // 8, w // 8]],
-                    image_size=[h, w], anchors=ANCHORS_YOLOV4, anchor_mask=ANCHOR_MASK, num_classes=80, center_region=0.6,
-                    valid_region=0.6, label_smooth=False, obj_ignore_threshold=0.7, weight=[1, 1, 1, 1, 1, 20, 20],
-                    scales_weight=[1, 1, 1], scales_id=["S32", "S16", "S08"])
-    from orienmask_amd import synth
-    target = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in synth.synth_targets(51, 2, h, w, 6))
-    x = synth.synth_image_batch(8, 2, h, w).to(dev)
-    results = []
-    for _ in range(2):
-        torch.manual_seed(3)
-        with torch.cuda.device(dev):
-            net = builder.build_train_model(dict(type="OrienMaskYOLOFPNPlus", num_anchors=3, num_classes=80, pretrained=None,
-                                                 freeze_backbone=False, backbone_batchnorm_eval=False, conv_backend="hip"))
-        assert net.training and net.backend == "hip" and net.conv_backend == "hip"
+    runs = [T.trainer_steps(dev, dict(conv_backend="hip"), 1) for _ in range(2)]
+    for _, _, net in runs:
+        assert net.backend == "hip" and net.conv_backend == "hip"
         assert all(m.conv_backend == "hip" for m in net.modules() if isinstance(m, train.ConvBNLeaky))
-        loss_fn = builder.build(loss_cfg, train)
-        optimizer = builder.build_optimizer(dict(type="SGD", lr=1e-3, momentum=0.9, weight_decay=5e-4), 1, net)
-        assert type(optimizer) is O.SGD
-        before = [p.detach().clone() for p in net.parameters()]
-        loss, _, _ = loss_fn(net(x), target, training=True)
-        assert torch.isfinite(loss)
-        loss.backward()
-        assert all(p.grad is not None and torch.isfinite(p.grad).all() for p in net.parameters())
-        optimizer.step()
-        torch.cuda.synchronize(dev)
-        unchanged = [n for (n, p), b in zip(net.named_parameters(), before) if torch.equal(p.detach(), b)]
-        assert not unchanged, unchanged[:5]
-        results.append([p.detach().clone() for p in net.parameters()])
-    differ = [n for (n, _), a, b in zip(net.named_parameters(), *results) if not torch.equal(a, b)]
+    differ = [n for (n, _), a, b in zip(runs[0][2].named_parameters(), runs[0][1][0], runs[1][1][0]) if not torch.equal(a, b)]
     assert not differ, differ[:5]

@@ -5,20 +5,17 @@ import re
 import pytest
 import torch
 
+import train_step as T
 from orienmask_amd import lib as omlib, train
-
-
-def _models(**kw):
-    return [train.OrienMaskYOLOFPNPlus(3, 80, **kw), train.OrienMaskYOLO(3, 80, **kw)]
 
 
 def test_conv_backend_is_accepted_and_defaults_to_torch():
     assert train.ConvBNLeaky(4, 8, 3, padding=1).conv_backend == "torch"
     assert train.ConvBNLeaky(4, 8, 3, padding=1, conv_backend="hip").conv_backend == "hip"
-    for net in _models():
+    for net in T.models():
         assert net.conv_backend == "torch"
         assert all(m.conv_backend == "torch" for m in net.modules() if isinstance(m, train.ConvBNLeaky))
-    for net in _models(conv_backend="hip"):
+    for net in T.models(conv_backend="hip"):
         assert net.conv_backend == "hip" and net.backend == "hip"
         blocks = [m for m in net.modules() if isinstance(m, train.ConvBNLeaky)]
         assert len(blocks) in (83, 86) and all(m.conv_backend == "hip" for m in blocks)
@@ -33,7 +30,7 @@ def test_unknown_conv_backend_is_refused():
 
 
 def test_hip_conv_backend_leaves_the_module_tree_alone():
-    for a, b in zip(_models(conv_backend="hip"), _models()):
+    for a, b in zip(T.models(conv_backend="hip"), T.models()):
         assert list(a.state_dict().keys()) == list(b.state_dict().keys())
         assert [(n, tuple(p.shape)) for n, p in a.named_parameters()] == [(n, tuple(p.shape)) for n, p in b.named_parameters()]
         assert [(n, type(m)) for n, m in a.named_modules()] == [(n, type(m)) for n, m in b.named_modules()]
@@ -43,7 +40,7 @@ def test_hip_conv_backend_leaves_the_module_tree_alone():
 
 def test_hip_conv_backend_has_no_cpu_fallback():
     x = torch.zeros(2, 3, 32, 32)
-    for net in _models(conv_backend="hip") + _models(conv_backend="hip", backend="torch"):
+    for net in T.models(conv_backend="hip") + T.models(conv_backend="hip", backend="torch"):
         with pytest.raises(omlib.OrienMaskHipError, match="no CPU fallback"):
             net(x)
     with pytest.raises(omlib.OrienMaskHipError, match="no CPU fallback"):

@@ -9,9 +9,9 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import ANCHOR_MASK, ANCHORS_YOLOV4
 import bn_act_np as N
 import loss_counter_cases as cases
+import train_step as T
 from orienmask_amd import arch, builder, synth, train
 from orienmask_amd import optim as O
 
@@ -62,12 +62,6 @@ def _model(dev, weights, k, **kw):
     net = train.OrienMaskYOLOFPNPlus(3, 80, frozen_stages=k, **kw)
     net.load_state_dict(weights, strict=True)
     return net.to(dev).train()
-
-
-def _step(net, x, cot):
-    heads = [t for pair in net(x) for t in pair]
-    torch.autograd.backward(heads, cot)
-    return heads
 
 
 # ---------------------------------------------------------------------------------------------------------------- the prefix
@@ -187,7 +181,7 @@ def test_heads_and_gradients_against_float64(dev, weights, image, monkeypatch):
     truth_net.load_state_dict(weights, strict=True)
     truth_net = truth_net.double().train()
     monkeypatch.setattr(train.F, "batch_norm", recording)
-    want_heads = [h.detach().numpy() for h in _step(truth_net, image.double(), [c.double() for c in cot])]
+    want_heads = [h.detach().numpy() for h in T.step(truth_net, image.double(), [c.double() for c in cot])]
     monkeypatch.undo()
     want_grads = {n: p.grad.numpy() for n, p in truth_net.named_parameters() if p.grad is not None}
     assert sorted(want_grads) == sorted(got["hip"][1]) == sorted(got["torch"][1]) and len(want_grads) == 266 - 3 * len(frozen)
@@ -232,21 +226,13 @@ def test_heads_and_gradients_against_float64(dev, weights, image, monkeypatch):
 
 
 # ---------------------------------------------------------------------------------------------------------------- a whole step
-def _loss_cfg():
-    h = w = SIZE
-    return dict(type="OrienMaskYOLOMultiScaleLoss", grid_size=[[h // 32, w // 32], [h // 16, w // 16], [h // 8, w // 8]],
-                image_size=[h, w], anchors=ANCHORS_YOLOV4, anchor_mask=ANCHOR_MASK, num_classes=80, center_region=0.6,
-                valid_region=0.6, label_smooth=False, obj_ignore_threshold=0.7, weight=[1, 1, 1, 1, 1, 20, 20],
-                scales_weight=[1, 1, 1], scales_id=["S32", "S16", "S08"])
-
-
 def _train_step(dev, k, x, target):
     """build_train_model -> the HIP loss -> backward -> the HIP SGD step.  -> (net, optimizer, loss bits, peak bytes of the step)."""
     torch.manual_seed(3)
     with torch.cuda.device(dev):
         net = builder.build_train_model(dict(type="OrienMaskYOLOFPNPlus", num_anchors=3, num_classes=80, pretrained=None,
                                              freeze_backbone=False, backbone_batchnorm_eval=False, frozen_stages=k, **HIP))
-    loss_fn = builder.build(_loss_cfg(), train)
+    loss_fn = builder.build(T.loss_cfg(SIZE, SIZE), train)
     optimizer = builder.build_optimizer(dict(type="SGD", lr=1e-3, momentum=0.9, weight_decay=5e-4), 1, net)
     assert type(optimizer) is O.SGD
     torch.cuda.synchronize(dev)

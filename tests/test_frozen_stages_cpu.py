@@ -5,6 +5,7 @@ builder.build_optimizer, train.convert_sync_batchnorm and builder.build_train_mo
 import pytest
 import torch
 
+import train_step as T
 from orienmask_amd import arch, builder, train
 from orienmask_amd import optim as O
 
@@ -46,12 +47,6 @@ def _pair(name, k):
     return net, hand
 
 
-def _step(net, x, cot):
-    heads = [t for pair in net(x) for t in pair]
-    torch.autograd.backward(heads, cot)
-    return heads
-
-
 @pytest.fixture(scope="module")
 def batch():
     g = torch.Generator().manual_seed(5)
@@ -75,7 +70,7 @@ def test_equals_the_model_frozen_by_hand(batch, name, k):
             assert m.conv_block[1].training == (not m.frozen), mod_name
     before = {n: b.clone() for n, b in net.named_buffers()}
 
-    heads, want = _step(net, x, cot), _step(hand, x, cot)
+    heads, want = T.step(net, x, cot), T.step(hand, x, cot)
     for h, w in zip(heads, want):
         assert torch.isfinite(h).all() and torch.equal(h, w)
     theirs = dict(hand.named_parameters())
@@ -133,7 +128,7 @@ def test_frozen_stages_is_orthogonal_to_backbone_batchnorm_eval(batch):
     torch.manual_seed(3)
     net = train.OrienMaskYOLO(3, 80, backend="torch", frozen_stages=2, backbone_batchnorm_eval=True).train()
     before = {n: b.clone() for n, b in net.named_buffers()}
-    _step(net, x, cot)
+    T.step(net, x, cot)
     for n, p in net.named_parameters():
         assert (p.grad is None) == (_stage(n) <= 2), n
     for n, b in net.named_buffers():

@@ -9,8 +9,9 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import ANCHOR_MASK, ANCHORS_YOLOV4, GOLDEN
+from conftest import GOLDEN
 import optim_np as N
+import train_step as T
 from orienmask_amd import builder, lib as omlib
 from orienmask_amd import optim as O
 
@@ -407,12 +408,8 @@ def test_training_step_with_hip_loss_and_optimizer(dev):
     split) and StepWarmUpLR from config dicts: the step applied to those gradients is the yardstick's, for two iterations."""
     from orienmask_amd import synth, train
     h = w = 96
-    loss_cfg = dict(type="OrienMaskYOLOMultiScaleLoss", grid_size=[[h // 32, w // 32], [h // 16, w // 16], [h // 8, w // 8]],
-                    image_size=[h, w], anchors=ANCHORS_YOLOV4, anchor_mask=ANCHOR_MASK, num_classes=80, center_region=0.6,
-                    valid_region=0.6, label_smooth=False, obj_ignore_threshold=0.7, weight=[1, 1, 1, 1, 1, 20, 20],
-                    scales_weight=[1, 1, 1], scales_id=["S32", "S16", "S08"])
     net = _Heads().to(dev)
-    loss_fn = builder.build(loss_cfg, train)
+    loss_fn = builder.build(T.loss_cfg(h, w), train)
     opt_cfg = dict(type="SGD", lr=4e-3, momentum=0.9, weight_decay=5e-4,
                    param_groups=dict(norm_weight_decay=0.0, bias_lr_factor=2.0, bias_weight_decay=1e-4))
     optimizer = builder.build_optimizer(opt_cfg, 2, net)

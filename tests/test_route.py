@@ -15,11 +15,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from conftest import ANCHOR_MASK, ANCHORS_YOLOV4, GOLDEN, fixture_weights_and_input
+from conftest import GOLDEN
 import bn_act_np as N
 import route_np as R
-from orienmask_amd import builder, lib as omlib, synth, train
-from orienmask_amd import optim as O
+import train_step as T
+from orienmask_amd import lib as omlib, synth, train
 
 pytestmark = pytest.mark.gpu
 
@@ -42,10 +42,6 @@ def _reference(case):
         chans, scales = R.chans_scales(case)
         _REFERENCES[key] = (srcs, dy, R.forward(srcs, chans, scales, *case[:3]), R.backward(dy, chans, scales))
     return _REFERENCES[key]
-
-
-def _vp(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def _carve(dev, shape, offset, fill=float("nan")):
@@ -73,13 +69,13 @@ def _ptrs(ts):
 
 def _call_fwd(dev, srcs, chans, scales, B, H, W, y, n=None):
     c, s = _arrays(chans, scales)
-    return omlib.load().om_route_concat_forward(_ptrs(srcs), c, s, len(chans) if n is None else n, B, H, W, _vp(y),
+    return omlib.load().om_route_concat_forward(_ptrs(srcs), c, s, len(chans) if n is None else n, B, H, W, T.vp(y),
                                                 omlib.current_stream_ptr(dev))
 
 
 def _call_bwd(dev, dy, chans, scales, B, H, W, dsrc, n=None):
     c, s = _arrays(chans, scales)
-    return omlib.load().om_route_concat_backward(_vp(dy), c, s, len(chans) if n is None else n, B, H, W, _ptrs(dsrc),
+    return omlib.load().om_route_concat_backward(T.vp(dy), c, s, len(chans) if n is None else n, B, H, W, _ptrs(dsrc),
                                                  omlib.current_stream_ptr(dev))
 
 
@@ -367,13 +363,6 @@ def test_function_refusals(dev):
 ALL_HIP = dict(backend="hip", conv_backend="hip", conv_forward="hip")
 
 
-def _step(net, x, cot):
-    out = net(x)
-    heads = [t for pair in out for t in pair]
-    torch.autograd.backward(heads, cot)
-    return heads
-
-
 @pytest.mark.parametrize("fixture", ["train_step_f96_b2", "train_step_bneval_f96_b2"])
 def test_model_against_the_torch_routes_and_the_reference_step(dev, fixture):
     """route_backend 'hip' against 'torch', everything else HIP in both so that it repeats its bits.  The forward is copies: the six
@@ -381,27 +370,15 @@ def test_model_against_the_torch_routes_and_the_reference_step(dev, fixture):
     reference's recorded step (CPU float32) the rms over tensors of the parameter gradients' relative-L2 error is for 'hip' at
     most twice that of 'torch' measured here."""
     g = np.load(os.path.join(GOLDEN, fixture + ".npz"))
-    sd, x = fixture_weights_and_input(g)
-    x = x.to(dev)
     heads, grads, gerr = {}, {}, {}
     for rb in ("torch", "hip"):
-        net = train.OrienMaskYOLOFPNPlus(3, 80, backbone_batchnorm_eval=bool(int(g["bneval"])), route_backend=rb, **ALL_HIP)
-        net.load_state_dict(sd, strict=True)
-        net = net.to(dev).train()
-        cot = [torch.from_numpy(c).to(dev) for c in N.cotangents(int(g["gseed"]), [g[k].shape for k in N.HEAD_KEYS])]
-        heads[rb] = [t.detach() for t in _step(net, x, cot)]
-        params = dict(net.named_parameters())
-        assert all(torch.isfinite(h).all() for h in heads[rb]), rb
-        assert all(p.grad is not None and torch.isfinite(p.grad).all() for p in params.values()), rb
-        grads[rb] = {n: p.grad.detach().clone() for n, p in params.items()}
-        gerr[rb] = [N.rel_l2(params[n].grad.cpu().numpy(), g["grad_%d" % i]) for i, n in enumerate(N.GRAD_NAMES)]
+        heads[rb], grads[rb], _, gerr[rb], _ = T.recorded_step(dev, g, route_backend=rb, **ALL_HIP)
     for k, a, b in zip(N.HEAD_KEYS, heads["hip"], heads["torch"]):
         assert torch.equal(a, b), k
-    rms = lambda v: float(np.sqrt(np.mean(np.square(v))))      # noqa: E731
     same = sum(torch.equal(grads["hip"][n], grads["torch"][n]) for n in grads["hip"])
     print("%s: gradient error, rms over tensors: route_backend hip %.6g  torch %.6g; %d of %d gradients bit-equal"
-          % (fixture, rms(gerr["hip"]), rms(gerr["torch"]), same, len(grads["hip"])))
-    assert rms(gerr["hip"]) <= 2 * rms(gerr["torch"])
+          % (fixture, T.rms(gerr["hip"]), T.rms(gerr["torch"]), same, len(grads["hip"])))
+    assert T.rms(gerr["hip"]) <= 2 * T.rms(gerr["torch"])
 
 
 def test_the_non_plus_model_has_the_torch_routes_heads(dev):
@@ -424,37 +401,12 @@ def test_the_non_plus_model_has_the_torch_routes_heads(dev):
 def test_one_trainer_step_repeats_its_bits(dev):
     """build_train_model with all four options 'hip' -> the HIP loss -> backward -> the HIP SGD step, twice from one seed: the loss
     and every parameter are bit-identical, and no parameter is left unchanged."""
-    h = w = 96
-    loss_cfg = dict(type="OrienMaskYOLOMultiScaleLoss", grid_size=[[h // 32, w // 32], [h // 16, w // 16], [h // 8, w // 8]],
-                    image_size=[h, w], anchors=ANCHORS_YOLOV4, anchor_mask=ANCHOR_MASK, num_classes=80, center_region=0.6,
-                    valid_region=0.6, label_smooth=False, obj_ignore_threshold=0.7, weight=[1, 1, 1, 1, 1, 20, 20],
-                    scales_weight=[1, 1, 1], scales_id=["S32", "S16", "S08"])
-    target = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in synth.synth_targets(51, 2, h, w, 6))
-    x = synth.synth_image_batch(8, 2, h, w).to(dev)
-    results, losses = [], []
-    for _ in range(2):
-        torch.manual_seed(3)
-        with torch.cuda.device(dev):
-            net = builder.build_train_model(dict(type="OrienMaskYOLOFPNPlus", num_anchors=3, num_classes=80, pretrained=None,
-                                                 freeze_backbone=False, backbone_batchnorm_eval=False, conv_backend="hip",
-                                                 conv_forward="hip", route_backend="hip"))
-        assert net.training and (net.backend, net.conv_backend, net.conv_forward, net.route_backend) == ("hip",) * 4
-        loss_fn = builder.build(loss_cfg, train)
-        optimizer = builder.build_optimizer(dict(type="SGD", lr=1e-3, momentum=0.9, weight_decay=5e-4), 1, net)
-        assert type(optimizer) is O.SGD
-        before = [p.detach().clone() for p in net.parameters()]
-        out = net(x)
+    def dense(out):
         assert all(o.is_contiguous() for _, o in out)      # the split's outputs are dense: the loss reads them as they are
-        loss, _, _ = loss_fn(out, target, training=True)
-        assert torch.isfinite(loss)
-        loss.backward()
-        assert all(p.grad is not None and torch.isfinite(p.grad).all() for p in net.parameters())
-        optimizer.step()
-        torch.cuda.synchronize(dev)
-        unchanged = [n for (n, p), b in zip(net.named_parameters(), before) if torch.equal(p.detach(), b)]
-        assert not unchanged, unchanged[:5]
-        losses.append(loss.detach().cpu().numpy().view(np.uint32).copy())
-        results.append([p.detach().clone() for p in net.parameters()])
-    assert np.array_equal(losses[0], losses[1])
-    differ = [n for (n, _), a, b in zip(net.named_parameters(), *results) if not torch.equal(a, b)]
+
+    runs = [T.trainer_steps(dev, dict(conv_backend="hip", conv_forward="hip", route_backend="hip"), 1, on_output=dense) for _ in range(2)]
+    for _, _, net in runs:
+        assert (net.backend, net.conv_backend, net.conv_forward, net.route_backend) == ("hip",) * 4
+    assert np.array_equal(runs[0][0][0], runs[1][0][0])
+    differ = [n for (n, _), a, b in zip(runs[0][2].named_parameters(), runs[0][1][0], runs[1][1][0]) if not torch.equal(a, b)]
     assert not differ, differ[:5]
