@@ -903,6 +903,42 @@ int om_route_concat_forward(const float* const src[4], const int chans[4], const
 int om_route_concat_backward(const float* dy, const int chans[4], const int scales[4], int n, int B, int H, int W, float* const dsrc[4],
                              om_stream stream);
 
+/* ---- bf16 activations (orienmask_amd.train's models with amp='bf16').  The _bf16 form of each entry point above takes the same
+ *      arguments and returns the same codes; only the ACTIVATION tensors change type: x, residual, y, dy, dx, the route sources, the
+ *      route output and their gradients are bf16 (uint16_t bits) NCHW contiguous.  gamma, beta, the running buffers, save_mean /
+ *      save_invstd, dgamma / dbeta stay float32, workspace partials and SyncBatchNorm records stay doubles, in the layouts above; the
+ *      workspace size is om_bn_act_workspace_bytes'.
+ *      Arithmetic: a bf16 input is widened exactly, every intermediate is the fp32 entry point's expression on the same doubles in
+ *      the same order, and a bf16 output is the float32 that entry point would have stored, rounded to bf16 to nearest even.  So
+ *      f_bf16(X) == rne_bf16(f(float(X))) bit for bit, and the float32 and double outputs (save vectors, running buffers, dgamma,
+ *      dbeta, records, sums) have f(float(X))'s bits.  om_route_concat_forward_bf16 is a copy; om_route_concat_backward_bf16 sums a
+ *      block in float32 in the order above and rounds once.
+ *      The 4-element unit of the fp32 kernels is kept (8 bytes of bf16: where H*W, or W for the routes, is a multiple of 4 and the
+ *      tensors are 8-byte aligned; one element per lane otherwise), because the unit fixes the order of the per-channel sums. */
+int om_bn_act_forward_bf16(const uint16_t* x, int B, int C, int H, int W, const float* gamma, const float* beta, float* running_mean,
+                           float* running_var, int64_t* num_batches_tracked, int training, double momentum, double eps, float slope,
+                           const uint16_t* residual, uint16_t* y, float* save_mean, float* save_invstd, void* workspace,
+                           size_t ws_bytes, om_stream stream);
+int om_bn_act_backward_bf16(const uint16_t* x, const uint16_t* dy, int B, int C, int H, int W, const float* gamma, const float* beta,
+                            const float* save_mean, const float* save_invstd, int training, float slope, uint16_t* dx, float* dgamma,
+                            float* dbeta, void* workspace, size_t ws_bytes, om_stream stream);
+int om_bn_sync_stats_bf16(const uint16_t* x, int B, int C, int H, int W, double* record, void* workspace, size_t ws_bytes,
+                          om_stream stream);
+int om_bn_sync_forward_bf16(const uint16_t* x, int B, int C, int H, int W, const double* records, int R, const float* gamma,
+                            const float* beta, float* running_mean, float* running_var, int64_t* num_batches_tracked, double momentum,
+                            double eps, float slope, const uint16_t* residual, uint16_t* y, float* save_mean, float* save_invstd,
+                            double* n_total_out, om_stream stream);
+int om_bn_sync_backward_sums_bf16(const uint16_t* x, const uint16_t* dy, int B, int C, int H, int W, const float* gamma,
+                                  const float* beta, const float* save_mean, const float* save_invstd, float slope, double* sums,
+                                  float* dgamma, float* dbeta, void* workspace, size_t ws_bytes, om_stream stream);
+int om_bn_sync_backward_dx_bf16(const uint16_t* x, const uint16_t* dy, int B, int C, int H, int W, const float* gamma,
+                                const float* beta, const float* save_mean, const float* save_invstd, float slope,
+                                const double* sums_all, int R, const double* n_total, uint16_t* dx, om_stream stream);
+int om_route_concat_forward_bf16(const uint16_t* const src[4], const int chans[4], const int scales[4], int n, int B, int H, int W,
+                                 uint16_t* y, om_stream stream);
+int om_route_concat_backward_bf16(const uint16_t* dy, const int chans[4], const int scales[4], int n, int B, int H, int W,
+                                  uint16_t* const dsrc[4], om_stream stream);
+
 /* ---- Several batches in flight.  Every entry point only enqueues kernels on the caller's stream and keeps no per-call state in
  *      the model handle (profiling apart): om_forward / om_forward_f16 / om_postprocess may be issued for different batches
  *      on different HIP streams at the same time, provided each batch in flight has its OWN workspace (and output buffers);

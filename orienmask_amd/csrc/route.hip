@@ -4,21 +4,24 @@
 //   route_concat_backward_kernel   dsrc_i[b, c, sy, sx] = the s_i x s_i block of dy summed sequentially in fp32, rows top to
 //                                  bottom and left to right within a row, the accumulator starting as the block's first element
 //                                  (torch-CPU's upsample_nearest2d backward order); at s = 1 a copy.  A null dsrc is skipped.
+// The tensors are fp32, or bf16 through the _bf16 entry points (the kernels' element type T).
 // Both kernels walk ONE flat item list with a grid-stride loop: the items of source 0, then of source 1, ...  An item's place in
 // its source's list is decoded into (b, c, row, k) with k fastest, so a wave's lanes run along W.  The divisors are fixed per
 // launch, so the host turns each into a multiply and a shift (RouteDiv).
 // Two forms of each kernel, chosen by the ENTRY POINT from the arguments (route_vector_form), never inside the kernel:
-//   vector   W % 4 == 0 and y / dy and every non-null source tensor 16-byte aligned.  Forward: an item is 4 output pixels of a row,
+//   vector   W % 4 == 0 and y / dy and every non-null source tensor aligned to 4 elements (16 bytes of fp32, 8 of bf16; the byte
+//            counts below are fp32's, bf16's are half).  Forward: an item is 4 output pixels of a row,
 //            one 16-byte store; the source side is one 16-byte load (s = 1), two elements (s = 2) or one (s = 4, 8).  Backward: an
 //            item is a strip of 4 dy columns (8 at s = 8) by s rows, read as 16-byte loads; it writes 4 (s = 1), 2 (s = 2) or 1
 //            (s = 4, 8) elements of dsrc in one store.
-//   scalar   anything else (a tensor that starts at an odd float, W % 4 != 0): an item is one element of y / of dsrc.
+//   scalar   anything else (a tensor that starts at an odd element, W % 4 != 0): an item is one element of y / of dsrc.
 // The table (pointers, channel offsets, scales, divisors) is a kernel argument by value; its rows are picked with constant indices
 // (route_pick), so nothing is indexed dynamically and nothing goes to scratch.  Built with -ffp-contract=off and without SLP
 // vectorisation: the block sum's adds stay single fp32 adds in the order written.
 #include <climits>
 
 #include "om_common.h"
+#include "bf16.h"
 
 namespace om {
 
@@ -28,9 +31,42 @@ constexpr int ROUTE_MAX_SRC = 4;
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) float gfloat;
-typedef __attribute__((address_space(1))) f32x2 gfloat2;
-typedef __attribute__((address_space(1))) f32x4 gfloat4;
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+
+// The element type T of a launch is float or bf16_t; the kernels see floats through these.  A bf16 is widened exactly and a float
+// is rounded to bf16 to nearest even (bf16.h), so the forward stays a copy and the backward's block sum, taken in fp32 in the order
+// below, is rounded once.  GROUP accesses are 4 elements: 16 bytes of fp32, 8 of bf16.
+
+#define OM_GLOBAL __attribute__((address_space(1)))
+template <typename T>
+__device__ __forceinline__ float route_load1(const OM_GLOBAL T* p) {
+    if constexpr (sizeof(T) == 4) return *p;
+    else return bf16_widen(*p);
+}
+template <typename T>
+__device__ __forceinline__ void route_store1(OM_GLOBAL T* p, float v) {
+    if constexpr (sizeof(T) == 4) *p = v;
+    else *p = (bf16_t)bf16_round(v);
+}
+template <typename T>
+__device__ __forceinline__ f32x4 route_load4(const OM_GLOBAL T* p) {
+    if constexpr (sizeof(T) == 4) {
+        return *(const OM_GLOBAL f32x4*)p;
+    } else {
+        const u32x2 t = *(const OM_GLOBAL u32x2*)p;
+        return f32x4{bf16_widen(t[0] & 0xffffu), bf16_widen(t[0] >> 16), bf16_widen(t[1] & 0xffffu), bf16_widen(t[1] >> 16)};
+    }
+}
+template <typename T>
+__device__ __forceinline__ void route_store4(OM_GLOBAL T* p, f32x4 v) {
+    if constexpr (sizeof(T) == 4) *(OM_GLOBAL f32x4*)p = v;
+    else *(OM_GLOBAL u32x2*)p = u32x2{bf16_round(v[0]) | (bf16_round(v[1]) << 16), bf16_round(v[2]) | (bf16_round(v[3]) << 16)};
+}
+template <typename T>
+__device__ __forceinline__ void route_store2(OM_GLOBAL T* p, f32x2 v) {
+    if constexpr (sizeof(T) == 4) *(OM_GLOBAL f32x2*)p = v;
+    else *(OM_GLOBAL uint32_t*)p = bf16_round(v[0]) | (bf16_round(v[1]) << 16);
+}
 
 // n / d for every n < 2^31 as (n * mul) >> shift: shift = 31 + ceil(log2 d), mul = ceil(2^shift / d) < 2^32 (Granlund & Montgomery
 // 1994, theorem 4.2 with N = 31)
@@ -97,15 +133,15 @@ __device__ __forceinline__ RouteItem route_decode(const RouteSeg& s, uint32_t lo
     return it;
 }
 
-template <bool VEC>
+template <typename T, bool VEC>
 __global__ void __launch_bounds__(ROUTE_THREADS)
-route_concat_forward_kernel(const RouteTable t, float* __restrict__ y_) {
-    gfloat* __restrict__ y = (gfloat*)y_;
+route_concat_forward_kernel(const RouteTable t, T* __restrict__ y_) {
+    OM_GLOBAL T* __restrict__ y = (OM_GLOBAL T*)y_;
     const uint32_t stride = gridDim.x * ROUTE_THREADS;
     for (uint32_t idx = blockIdx.x * ROUTE_THREADS + threadIdx.x; idx < t.total; idx += stride) {
         const RouteSeg s = route_pick(t, idx);
         const RouteItem it = route_decode(s, idx - s.start);       // row = oy, k = the item's place in the output row
-        const gfloat* __restrict__ src = (const gfloat*)s.ptr;
+        const OM_GLOBAL T* __restrict__ src = (const OM_GLOBAL T*)s.ptr;
         const uint32_t ws = t.W >> s.sh;
         // first source element of the item: source row oy >> sh of plane (b, c)
         const uint32_t srow = ((it.b * s.chans + it.c) * (t.H >> s.sh) + (it.row >> s.sh)) * ws;
@@ -115,77 +151,77 @@ route_concat_forward_kernel(const RouteTable t, float* __restrict__ y_) {
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
             if (src) {
                 if (s.sh == 0) {
-                    v = *(const gfloat4*)(src + srow + ox);
+                    v = route_load4<T>(src + srow + ox);
                 } else if (s.sh == 1) {
-                    const float a = src[srow + (ox >> 1)], c = src[srow + (ox >> 1) + 1];
+                    const float a = route_load1<T>(src + srow + (ox >> 1)), c = route_load1<T>(src + srow + (ox >> 1) + 1);
                     v = f32x4{a, a, c, c};
                 } else {
-                    const float a = src[srow + (ox >> s.sh)];
+                    const float a = route_load1<T>(src + srow + (ox >> s.sh));
                     v = f32x4{a, a, a, a};
                 }
             }
-            *(gfloat4*)(y + yrow + ox) = v;
+            route_store4<T>(y + yrow + ox, v);
         } else {
-            y[yrow + it.k] = src ? src[srow + (it.k >> s.sh)] : 0.f;
+            route_store1<T>(y + yrow + it.k, src ? route_load1<T>(src + srow + (it.k >> s.sh)) : 0.f);
         }
     }
 }
 
-template <bool VEC>
+template <typename T, bool VEC>
 __global__ void __launch_bounds__(ROUTE_THREADS)
-route_concat_backward_kernel(const RouteTable t, const float* __restrict__ dy_) {
-    const gfloat* __restrict__ dy = (const gfloat*)dy_;
+route_concat_backward_kernel(const RouteTable t, const T* __restrict__ dy_) {
+    const OM_GLOBAL T* __restrict__ dy = (const OM_GLOBAL T*)dy_;
     const uint32_t stride = gridDim.x * ROUTE_THREADS;
     for (uint32_t idx = blockIdx.x * ROUTE_THREADS + threadIdx.x; idx < t.total; idx += stride) {
         const RouteSeg s = route_pick(t, idx);
         const uint32_t local = idx - s.start;
         const RouteItem it = route_decode(s, local);      // row = sy, k = the item's place in the source row
-        gfloat* __restrict__ dst = (gfloat*)s.ptr;
+        OM_GLOBAL T* __restrict__ dst = (OM_GLOBAL T*)s.ptr;
         const uint32_t W = t.W;
         // first dy element of the item's top row: row sy << sh of plane (b, off + c)
-        const gfloat* __restrict__ top = dy + ((it.b * t.ctot + s.off + it.c) * t.H + (it.row << s.sh)) * W;
+        const OM_GLOBAL T* __restrict__ top = dy + ((it.b * t.ctot + s.off + it.c) * t.H + (it.row << s.sh)) * W;
         if (VEC) {
             // dsrc is contiguous in item order: item `local` owns elements [local * g, local * g + g), g = 4, 2, 1, 1
             if (s.sh == 0) {
-                *(gfloat4*)(dst + (size_t)local * 4) = *(const gfloat4*)(top + it.k * 4);
+                route_store4<T>(dst + (size_t)local * 4, route_load4<T>(top + it.k * 4));
             } else if (s.sh == 1) {
-                const f32x4 r0 = *(const gfloat4*)(top + it.k * 4), r1 = *(const gfloat4*)(top + W + it.k * 4);
+                const f32x4 r0 = route_load4<T>(top + it.k * 4), r1 = route_load4<T>(top + W + it.k * 4);
                 f32x2 o;
                 o[0] = ((r0[0] + r0[1]) + r1[0]) + r1[1];
                 o[1] = ((r0[2] + r0[3]) + r1[2]) + r1[3];
-                *(gfloat2*)(dst + (size_t)local * 2) = o;
+                route_store2<T>(dst + (size_t)local * 2, o);
             } else if (s.sh == 2) {
-                const gfloat* p = top + it.k * 4;
-                f32x4 r = *(const gfloat4*)p;
+                const OM_GLOBAL T* p = top + it.k * 4;
+                f32x4 r = route_load4<T>(p);
                 float acc = ((r[0] + r[1]) + r[2]) + r[3];
 #pragma unroll
                 for (int j = 1; j < 4; ++j) {
-                    r = *(const gfloat4*)(p + j * W);
+                    r = route_load4<T>(p + j * W);
                     acc = (((acc + r[0]) + r[1]) + r[2]) + r[3];
                 }
-                dst[local] = acc;
+                route_store1<T>(dst + local, acc);
             } else {
-                const gfloat* p = top + it.k * 8;
-                f32x4 r = *(const gfloat4*)p, q = *(const gfloat4*)(p + 4);
+                const OM_GLOBAL T* p = top + it.k * 8;
+                f32x4 r = route_load4<T>(p), q = route_load4<T>(p + 4);
                 float acc = ((((((r[0] + r[1]) + r[2]) + r[3]) + q[0]) + q[1]) + q[2]) + q[3];
 #pragma unroll
                 for (int j = 1; j < 8; ++j) {
-                    r = *(const gfloat4*)(p + j * W);
-                    q = *(const gfloat4*)(p + j * W + 4);
+                    r = route_load4<T>(p + j * W);
+                    q = route_load4<T>(p + j * W + 4);
                     acc = (((((((acc + r[0]) + r[1]) + r[2]) + r[3]) + q[0]) + q[1]) + q[2]) + q[3];
                 }
-                dst[local] = acc;
+                route_store1<T>(dst + local, acc);
             }
         } else {
             const uint32_t sc = 1u << s.sh;
-            const gfloat* p = top + (it.k << s.sh);
-            float acc = p[0];
-            for (uint32_t i = 1; i < sc; ++i) acc += p[i];
+            const OM_GLOBAL T* p = top + (it.k << s.sh);
+            float acc = route_load1<T>(p);
+            for (uint32_t i = 1; i < sc; ++i) acc += route_load1<T>(p + i);
             for (uint32_t j = 1; j < sc; ++j) {
                 p += W;
-                for (uint32_t i = 0; i < sc; ++i) acc += p[i];
+                for (uint32_t i = 0; i < sc; ++i) acc += route_load1<T>(p + i);
             }
-            dst[local] = acc;
+            route_store1<T>(dst + local, acc);
         }
     }
 }
@@ -214,12 +250,12 @@ static int route_check(const char* who, const int* chans, const int* scales, int
     return OM_OK;
 }
 
-// The vector form's conditions, from the arguments alone: rows of whole 16-byte groups, and every tensor the kernel touches starting
-// on a 16-byte boundary (every plane and row of a contiguous tensor then does, at every scale: W / s is even or the access scalar).
-static bool route_vector_form(const void* whole, void* const* parts, int n, int W) {
-    if (W % 4 != 0 || align_bytes(whole) < 16) return false;
+// The vector form's conditions, from the arguments alone: rows of whole 4-element groups (group_bytes: 16 of fp32, 8 of bf16), and
+// every tensor the kernel touches starting on a group boundary (every plane and row of a contiguous tensor then does, at every scale: W / s is even or the access scalar).
+static bool route_vector_form(const void* whole, void* const* parts, int n, int W, int group_bytes) {
+    if (W % 4 != 0 || align_bytes(whole) < group_bytes) return false;
     for (int i = 0; i < n; ++i)
-        if (parts[i] && align_bytes(parts[i]) < 16) return false;
+        if (parts[i] && align_bytes(parts[i]) < group_bytes) return false;
     return true;
 }
 
@@ -263,55 +299,82 @@ static void route_table(RouteTable& t, void* const* ptrs, const int* chans, cons
     t.W = (uint32_t)W;
 }
 
+// The entry points' bodies for the element type T; `who` is the entry point's name in the messages.
+template <typename T>
+static int route_concat_forward(const char* who, const void* const* src, const int* chans, const int* scales, int n, int B, int H, int W,
+                                T* y, om_stream stream) {
+    int ctot = 0;
+    const int rc = route_check(who, chans, scales, n, B, H, W, &ctot);
+    if (rc != OM_OK) return rc;
+    OM_REQUIRE(src && y, OM_EINVAL, "%s: null src table or y", who);
+    void* ptrs[ROUTE_MAX_SRC] = {nullptr, nullptr, nullptr, nullptr};
+    for (int i = 0; i < n; ++i) ptrs[i] = const_cast<void*>(src[i]);
+    const bool vec = route_vector_form(y, ptrs, n, W, 4 * (int)sizeof(T));
+    RouteTable t;
+    route_table(t, ptrs, chans, scales, n, B, ctot, H, W, vec, false);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid(route_blocks(t.total)), block(ROUTE_THREADS);
+    if (vec)
+        hipLaunchKernelGGL((route_concat_forward_kernel<T, true>), grid, block, 0, st, t, y);
+    else
+        hipLaunchKernelGGL((route_concat_forward_kernel<T, false>), grid, block, 0, st, t, y);
+    OM_CHECK_HIP(hipGetLastError());
+    return OM_OK;
+}
+
+template <typename T>
+static int route_concat_backward(const char* who, const T* dy, const int* chans, const int* scales, int n, int B, int H, int W,
+                                 void* const* dsrc, om_stream stream) {
+    int ctot = 0;
+    const int rc = route_check(who, chans, scales, n, B, H, W, &ctot);
+    if (rc != OM_OK) return rc;
+    OM_REQUIRE(dy && dsrc, OM_EINVAL, "%s: null dy or dsrc table", who);
+    void* ptrs[ROUTE_MAX_SRC] = {nullptr, nullptr, nullptr, nullptr};
+    bool any = false;
+    for (int i = 0; i < n; ++i) {
+        ptrs[i] = dsrc[i];
+        any = any || dsrc[i];
+    }
+    OM_REQUIRE(any, OM_EINVAL, "%s: every dsrc is null, there is nothing to compute", who);
+    const bool vec = route_vector_form(dy, ptrs, n, W, 4 * (int)sizeof(T));
+    RouteTable t;
+    route_table(t, ptrs, chans, scales, n, B, ctot, H, W, vec, true);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid(route_blocks(t.total)), block(ROUTE_THREADS);
+    if (vec)
+        hipLaunchKernelGGL((route_concat_backward_kernel<T, true>), grid, block, 0, st, t, dy);
+    else
+        hipLaunchKernelGGL((route_concat_backward_kernel<T, false>), grid, block, 0, st, t, dy);
+    OM_CHECK_HIP(hipGetLastError());
+    return OM_OK;
+}
+
 }  // namespace om
 
 extern "C" {
 
 int om_route_concat_forward(const float* const src[4], const int chans[4], const int scales[4], int n, int B, int H, int W, float* y,
                             om_stream stream) {
-    int ctot = 0;
-    const int rc = om::route_check("om_route_concat_forward", chans, scales, n, B, H, W, &ctot);
-    if (rc != OM_OK) return rc;
-    OM_REQUIRE(src && y, OM_EINVAL, "om_route_concat_forward: null src table or y");
-    void* ptrs[om::ROUTE_MAX_SRC] = {nullptr, nullptr, nullptr, nullptr};
-    for (int i = 0; i < n; ++i) ptrs[i] = const_cast<float*>(src[i]);
-    const bool vec = om::route_vector_form(y, ptrs, n, W);
-    om::RouteTable t;
-    om::route_table(t, ptrs, chans, scales, n, B, ctot, H, W, vec, false);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const dim3 grid(om::route_blocks(t.total)), block(om::ROUTE_THREADS);
-    if (vec)
-        hipLaunchKernelGGL(om::route_concat_forward_kernel<true>, grid, block, 0, st, t, y);
-    else
-        hipLaunchKernelGGL(om::route_concat_forward_kernel<false>, grid, block, 0, st, t, y);
-    OM_CHECK_HIP(hipGetLastError());
-    return OM_OK;
+    return om::route_concat_forward<float>("om_route_concat_forward", reinterpret_cast<const void* const*>(src), chans, scales, n, B, H,
+                                           W, y, stream);
+}
+
+int om_route_concat_forward_bf16(const uint16_t* const src[4], const int chans[4], const int scales[4], int n, int B, int H, int W,
+                                 uint16_t* y, om_stream stream) {
+    return om::route_concat_forward<om::bf16_t>("om_route_concat_forward_bf16", reinterpret_cast<const void* const*>(src), chans, scales,
+                                                n, B, H, W, y, stream);
 }
 
 int om_route_concat_backward(const float* dy, const int chans[4], const int scales[4], int n, int B, int H, int W, float* const dsrc[4],
                              om_stream stream) {
-    int ctot = 0;
-    const int rc = om::route_check("om_route_concat_backward", chans, scales, n, B, H, W, &ctot);
-    if (rc != OM_OK) return rc;
-    OM_REQUIRE(dy && dsrc, OM_EINVAL, "om_route_concat_backward: null dy or dsrc table");
-    void* ptrs[om::ROUTE_MAX_SRC] = {nullptr, nullptr, nullptr, nullptr};
-    bool any = false;
-    for (int i = 0; i < n; ++i) {
-        ptrs[i] = dsrc[i];
-        any = any || dsrc[i];
-    }
-    OM_REQUIRE(any, OM_EINVAL, "om_route_concat_backward: every dsrc is null, there is nothing to compute");
-    const bool vec = om::route_vector_form(dy, ptrs, n, W);
-    om::RouteTable t;
-    om::route_table(t, ptrs, chans, scales, n, B, ctot, H, W, vec, true);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const dim3 grid(om::route_blocks(t.total)), block(om::ROUTE_THREADS);
-    if (vec)
-        hipLaunchKernelGGL(om::route_concat_backward_kernel<true>, grid, block, 0, st, t, dy);
-    else
-        hipLaunchKernelGGL(om::route_concat_backward_kernel<false>, grid, block, 0, st, t, dy);
-    OM_CHECK_HIP(hipGetLastError());
-    return OM_OK;
+    return om::route_concat_backward<float>("om_route_concat_backward", dy, chans, scales, n, B, H, W,
+                                            reinterpret_cast<void* const*>(dsrc), stream);
+}
+
+int om_route_concat_backward_bf16(const uint16_t* dy, const int chans[4], const int scales[4], int n, int B, int H, int W,
+                                  uint16_t* const dsrc[4], om_stream stream) {
+    return om::route_concat_backward<om::bf16_t>("om_route_concat_backward_bf16", dy, chans, scales, n, B, H, W,
+                                                 reinterpret_cast<void* const*>(dsrc), stream);
 }
 
 }  // extern "C"

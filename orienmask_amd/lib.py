@@ -222,6 +222,10 @@ SIGNATURES = {
     "om_route_concat_forward": (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i, _i, _i, _vp, _vp]),
     "om_route_concat_backward": (_i, [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i, _i, _i, ctypes.POINTER(_vp), _vp]),
 }
+# the bf16-activation forms: the same arguments, the activation pointers bf16
+for _name in ("om_bn_act_forward", "om_bn_act_backward", "om_bn_sync_stats", "om_bn_sync_forward", "om_bn_sync_backward_sums",
+              "om_bn_sync_backward_dx", "om_route_concat_forward", "om_route_concat_backward"):
+    SIGNATURES[_name + "_bf16"] = SIGNATURES[_name]
 
 _lib = None
 

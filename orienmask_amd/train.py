@@ -44,6 +44,12 @@ csrc/conv_grad.hip with conv_backend='hip'.
 
 The up-sampling, cat and split are torch ops with route_backend='torch' (the default) and these two functions with
 route_backend='hip', which is independent of the other three options.
+
+Mixed precision: amp='bf16' on a model or a block (default None: float32 throughout).  The forward then runs under
+torch.autocast(dtype=torch.bfloat16): torch's convolutions produce bf16, and bn_leaky, upsample_concat and split_channels take and
+return bf16 through the _bf16 entry points of csrc/bn_act.hip and csrc/route.hip (the saved x, dy and dx are bf16 too).  Parameters,
+their gradients, the BatchNorm statistics and buffers, the heads the model returns, the loss and the optimizer stay float32, so
+state_dicts move freely between amp and float32 models.  amp excludes conv_backend / conv_forward 'hip' (float32 operands only).
 """
 import contextlib
 import ctypes
@@ -68,10 +74,17 @@ CONV_FORWARDS = ("torch", "hip")
 ROUTE_BACKENDS = ("torch", "hip")
 ROUTE_SCALES = (1, 2, 4, 8)
 ROUTE_MAX = 4
+AMP = (None, "bf16")
+ACT_DTYPES = (torch.float32, torch.bfloat16)       # what the BatchNorm block and the routes take
 
 
-def _check_backends(backend, conv_backend, conv_forward, route_backend="torch"):
+def _check_backends(backend, conv_backend, conv_forward, route_backend="torch", amp=None):
     """The option strings of a block and of a model (a block has no route_backend: the default passes)."""
+    if amp not in AMP:
+        raise ValueError("amp must be one of %s, got %r" % (AMP, amp))
+    if amp is not None and (conv_backend == "hip" or conv_forward == "hip"):
+        raise ValueError("amp %r needs torch's convolutions: conv_backend %r / conv_forward %r take float32 operands only"
+                         % (amp, conv_backend, conv_forward))
     for name, value, known in (("backend", backend, BACKENDS), ("conv_backend", conv_backend, CONV_BACKENDS),
                                ("conv_forward", conv_forward, CONV_FORWARDS), ("route_backend", route_backend, ROUTE_BACKENDS)):
         if value not in known:
@@ -227,6 +240,19 @@ def _workspace(dev, stream, nbytes):
     return ws
 
 
+def _sfx(t):
+    """The entry points' suffix for t's element type: the float32 ones have none."""
+    return "_bf16" if t.dtype == torch.bfloat16 else ""
+
+
+def _autocast(amp, x):
+    """The context a forward with `amp` runs under: torch.autocast to bf16 on x's device type, nothing without amp or inside one."""
+    kind = x.device.type
+    if amp is None or (torch.is_autocast_enabled(kind) and torch.get_autocast_dtype(kind) == torch.bfloat16):
+        return _NO_SWITCH
+    return torch.autocast(kind, dtype=torch.bfloat16)
+
+
 def _bn_scratch(x):
     """(library, stream, workspace) of an om_bn_act_* / om_bn_sync_* call on x's device and current stream."""
     L = _lib.load()
@@ -241,6 +267,8 @@ def _bn_forward_buffers(x):
 
 def _bn_backward_buffers(ctx, x, dy):
     """dy contiguous, dx where the input needs a gradient, and dgamma | dbeta as one [2, C] buffer."""
+    if dy.dtype != x.dtype:
+        raise _lib.OrienMaskHipError("the BatchNorm block's output gradient is %s, its input %s: there is no cast" % (dy.dtype, x.dtype))
     dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
     return dy.contiguous(), dx, torch.empty((2, x.shape[1]), dtype=torch.float32, device=x.device)
 
@@ -253,7 +281,8 @@ def _bn_grads(ctx, dx, dgb, dy):
 
 class _BNAct(torch.autograd.Function):
     """forward(ctx, x, gamma, beta, residual, bn, slope) -> leaky(batch_norm(x)) (+ residual): om_bn_act_forward.  `bn` is the
-    nn.BatchNorm2d whose buffers the kernel updates in training mode and reads in eval mode.  Saved for the backward: x, gamma, beta
+    nn.BatchNorm2d whose buffers the kernel updates in training mode and reads in eval mode.  x (and residual) float32, or bf16
+    through the _bf16 entry points: y, dy and dx then are bf16, everything else stays float32.  Saved for the backward: x, gamma, beta
     and one per-channel buffer the forward wrote (save_mean and save_invstd, 2C floats each); the LeakyReLU mask is recomputed from
     x (om_bn_act_backward)."""
 
@@ -265,7 +294,7 @@ class _BNAct(torch.autograd.Function):
         track = training and bn.running_mean is not None
         L, stream, ws = _bn_scratch(x)
         with _device(x.device):
-            _lib.check(L.om_bn_act_forward(
+            _lib.check(getattr(L, "om_bn_act_forward" + _sfx(x))(
                 _vp(x), B, C, H, W, _vp(gamma), _vp(beta), _vp(bn.running_mean), _vp(bn.running_var),
                 _vp(bn.num_batches_tracked) if track else None, 1 if training else 0, float(bn.momentum), float(bn.eps),
                 float(slope), _vp(residual), _vp(y), save.data_ptr(), save.data_ptr() + 8 * C, ws.data_ptr(), ws.numel(), stream),
@@ -282,7 +311,7 @@ class _BNAct(torch.autograd.Function):
         dy, dx, dgb = _bn_backward_buffers(ctx, x, dy)
         L, stream, ws = _bn_scratch(x)
         with _device(x.device):
-            _lib.check(L.om_bn_act_backward(
+            _lib.check(getattr(L, "om_bn_act_backward" + _sfx(x))(
                 _vp(x), _vp(dy), B, C, H, W, _vp(gamma), _vp(beta), save.data_ptr(), save.data_ptr() + 8 * C, 1 if ctx.training else 0,
                 ctx.slope, _vp(dx), dgb.data_ptr(), dgb.data_ptr() + 4 * C, ws.data_ptr(), ws.numel(), stream), "om_bn_act_backward")
         return _bn_grads(ctx, dx, dgb, dy)
@@ -337,19 +366,20 @@ class _Conv2d(torch.autograd.Function):
         return dx, dw, db, None, None
 
 
-def _require_nchw(t, who, what):
-    """`what` (as lib.require_cuda_tensor names it) is a CUDA float32 NCHW-contiguous [B,C,H,W] tensor, or `who` refuses it."""
-    _lib.require_cuda_tensor(t, what, torch.float32)
+def _require_nchw(t, who, what, dtypes=(torch.float32,)):
+    """`what` (as lib.require_cuda_tensor names it) is a CUDA NCHW-contiguous [B,C,H,W] tensor of one of `dtypes`, or `who` refuses
+    it."""
+    _lib.require_cuda_tensor(t, what, t.dtype if isinstance(t, torch.Tensor) and t.dtype in dtypes else dtypes[0])
     if t.dim() != 4 or not t.is_contiguous():
         raise _lib.OrienMaskHipError("%s takes NCHW-contiguous [B,C,H,W] activations, got strides %s for shape %s"
                                      % (who, t.stride(), tuple(t.shape)))
 
 
-def _require_residual(residual, shape, dev):
-    """None, or a CUDA float32 NCHW-contiguous tensor of the block's output shape on the block's device."""
+def _require_residual(residual, shape, dev, dtype=torch.float32):
+    """None, or a CUDA NCHW-contiguous tensor of the block's element type and output shape on the block's device."""
     if residual is None:
         return
-    _lib.require_cuda_tensor(residual, "residual", torch.float32)
+    _lib.require_cuda_tensor(residual, "residual", dtype)
     if tuple(residual.shape) != tuple(shape) or not residual.is_contiguous() or residual.device != dev:
         raise _lib.OrienMaskHipError("residual must be NCHW-contiguous with the block's output shape %s on %s, got %s strides %s on %s"
                                      % (tuple(shape), dev, tuple(residual.shape), residual.stride(), residual.device))
@@ -440,17 +470,21 @@ def conv_bn_leaky_frozen(x, weight, bn, residual=None, stride=1, padding=0, slop
 
 
 def _route_call(fn, what, ptrs, chans, scales, B, H, W, whole, dev):
-    """One om_route_concat_* call on the current stream: `ptrs` the per-source tensors (None: null), `whole` y or dy."""
+    """One om_route_concat_* call on the current stream: `ptrs` the per-source tensors (None: null), `whole` y or dy; the entry
+    point is the one of their element type."""
     n = len(chans)
     table = (ctypes.c_void_p * ROUTE_MAX)(*[t.data_ptr() if t is not None else None for t in ptrs] + [None] * (ROUTE_MAX - n))
     c = (ctypes.c_int * ROUTE_MAX)(*list(chans) + [0] * (ROUTE_MAX - n))
     s = (ctypes.c_int * ROUTE_MAX)(*list(scales) + [0] * (ROUTE_MAX - n))
     stream = _lib.current_stream_ptr(dev)
+    for t in ptrs:
+        if t is not None and t.dtype != whole.dtype:
+            raise _lib.OrienMaskHipError("%s: tensors of %s and %s in one call: there is no cast" % (what, t.dtype, whole.dtype))
     with _device(dev):
         if fn == "forward":
-            rc = _lib.load().om_route_concat_forward(table, c, s, n, B, H, W, _vp(whole), stream)
+            rc = getattr(_lib.load(), "om_route_concat_forward" + _sfx(whole))(table, c, s, n, B, H, W, _vp(whole), stream)
         else:
-            rc = _lib.load().om_route_concat_backward(_vp(whole), c, s, n, B, H, W, table, stream)
+            rc = getattr(_lib.load(), "om_route_concat_backward" + _sfx(whole))(_vp(whole), c, s, n, B, H, W, table, stream)
     _lib.check(rc, what)
 
 
@@ -465,7 +499,7 @@ class _UpsampleConcat(torch.autograd.Function):
         H, W = tensors[0].shape[2] * scales[0], tensors[0].shape[3] * scales[0]
         chans = [int(t.shape[1]) for t in tensors]
         dev = tensors[0].device
-        y = torch.empty((B, sum(chans), H, W), dtype=torch.float32, device=dev)
+        y = torch.empty((B, sum(chans), H, W), dtype=tensors[0].dtype, device=dev)
         _route_call("forward", "om_route_concat_forward", tensors, chans, scales, B, H, W, y, dev)
         ctx.geom = (chans, tuple(scales), B, H, W)
         return y
@@ -476,7 +510,7 @@ class _UpsampleConcat(torch.autograd.Function):
         chans, scales, B, H, W = ctx.geom
         dev = dy.device
         dy = dy.contiguous()
-        grads = [torch.empty((B, c, H // s, W // s), dtype=torch.float32, device=dev) if need else None
+        grads = [torch.empty((B, c, H // s, W // s), dtype=dy.dtype, device=dev) if need else None
                  for c, s, need in zip(chans, scales, ctx.needs_input_grad[1:])]
         if any(g is not None for g in grads):
             _route_call("backward", "om_route_concat_backward", grads, chans, scales, B, H, W, dy, dev)
@@ -491,20 +525,20 @@ class _SplitChannels(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, sizes):
         B, C, H, W = x.shape
-        outs = [torch.empty((B, c, H, W), dtype=torch.float32, device=x.device) for c in sizes]
+        outs = [torch.empty((B, c, H, W), dtype=x.dtype, device=x.device) for c in sizes]
         _route_call("backward", "om_route_concat_backward", outs, sizes, [1] * len(sizes), B, H, W, x, x.device)
-        ctx.geom = (tuple(sizes), B, H, W, x.device)
+        ctx.geom = (tuple(sizes), B, H, W, x.device, x.dtype)
         ctx.set_materialize_grads(False)
         return tuple(outs)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, *grads):
-        sizes, B, H, W, dev = ctx.geom
+        sizes, B, H, W, dev, dtype = ctx.geom
         if all(g is None for g in grads):
             return None, None
         grads = [g.contiguous() if g is not None else None for g in grads]
-        dx = torch.empty((B, sum(sizes), H, W), dtype=torch.float32, device=dev)
+        dx = torch.empty((B, sum(sizes), H, W), dtype=dtype, device=dev)
         _route_call("forward", "om_route_concat_forward", grads, sizes, [1] * len(sizes), B, H, W, dx, dev)
         return dx, None
 
@@ -512,18 +546,21 @@ class _SplitChannels(torch.autograd.Function):
 def upsample_concat(tensors, scales):
     """torch.cat([F.interpolate(t, scale_factor=s, mode='nearest') for t, s in zip(tensors, scales)], dim=1) as one HIP kernel
     (csrc/route.hip), bit-identical to it, with the backward as one kernel too: the gradient of a source is the s x s block sum of
-    its channels' dy in torch-CPU's order.  1 to 4 CUDA float32 NCHW-contiguous tensors of one batch size whose up-sampled sizes
-    agree, and their integer scales, each 1, 2, 4 or 8.  Anything else raises: there is no fallback."""
+    its channels' dy in torch-CPU's order.  1 to 4 CUDA NCHW-contiguous tensors, all float32 or all bf16 (the output and the
+    gradients have their type; a bf16 gradient is the float32 block sum rounded once), of one batch size whose up-sampled sizes
+    agree, and their integer scales, each 1, 2, 4 or 8.  Anything else raises: there is no fallback and no cast."""
     tensors, scales = list(tensors), list(scales)
     if not 1 <= len(tensors) <= ROUTE_MAX or len(scales) != len(tensors):
         raise ValueError("upsample_concat takes 1 to %d tensors and as many scales, got %d and %d" % (ROUTE_MAX, len(tensors), len(scales)))
     for i, t in enumerate(tensors):
-        _require_nchw(t, "route_backend 'hip'", "input %d of upsample_concat (route_backend 'hip')" % i)
+        _require_nchw(t, "route_backend 'hip'", "input %d of upsample_concat (route_backend 'hip')" % i, ACT_DTYPES)
     for s in scales:
         if isinstance(s, bool) or not isinstance(s, int) or s not in ROUTE_SCALES:
             raise _lib.OrienMaskHipError("upsample_concat: scale %r; the scales are the integers %s" % (s, ROUTE_SCALES))
     B, H, W = tensors[0].shape[0], tensors[0].shape[2] * scales[0], tensors[0].shape[3] * scales[0]
     for t, s in zip(tensors, scales):
+        if t.dtype != tensors[0].dtype:
+            raise _lib.OrienMaskHipError("upsample_concat: inputs of %s and %s: there is no cast" % (tensors[0].dtype, t.dtype))
         if t.device != tensors[0].device or t.shape[0] != B or t.shape[2] * s != H or t.shape[3] * s != W or min(t.shape) < 1:
             raise _lib.OrienMaskHipError("upsample_concat: shapes %s at scales %s do not give one [%d,*,%d,%d] tensor on one device"
                                          % ([tuple(t.shape) for t in tensors], scales, B, H, W))
@@ -532,12 +569,12 @@ def upsample_concat(tensors, scales):
 
 def split_channels(x, sizes):
     """torch.split(x, sizes, dim=1) as dense tensors, one HIP kernel (csrc/route.hip); the backward is one kernel that writes the
-    whole gradient of x, zeros for an output that took no part in the loss.  x CUDA float32 NCHW-contiguous, 1 to 4 sizes >= 1
+    whole gradient of x, zeros for an output that took no part in the loss.  x CUDA float32 or bf16 NCHW-contiguous, 1 to 4 sizes >= 1
     that sum to its channels.  Anything else raises: there is no fallback."""
     sizes = [int(c) for c in sizes]
     if not 1 <= len(sizes) <= ROUTE_MAX:
         raise ValueError("split_channels takes 1 to %d sizes, got %d" % (ROUTE_MAX, len(sizes)))
-    _require_nchw(x, "route_backend 'hip'", "the input of split_channels (route_backend 'hip')")
+    _require_nchw(x, "route_backend 'hip'", "the input of split_channels (route_backend 'hip')", ACT_DTYPES)
     if min(sizes) < 1 or sum(sizes) != x.shape[1] or min(x.shape) < 1:
         raise _lib.OrienMaskHipError("split_channels: sizes %s do not split the %d channels of shape %s" % (sizes, x.shape[1], tuple(x.shape)))
     return _SplitChannels.apply(x, tuple(sizes))
@@ -564,9 +601,9 @@ class _SyncBNAct(torch.autograd.Function):
         track = bn.running_mean is not None
         L, stream, ws = _bn_scratch(x)
         with _device(dev):
-            _lib.check(L.om_bn_sync_stats(_vp(x), B, C, H, W, _vp(record), ws.data_ptr(), ws.numel(), stream), "om_bn_sync_stats")
+            _lib.check(getattr(L, "om_bn_sync_stats" + _sfx(x))(_vp(x), B, C, H, W, _vp(record), ws.data_ptr(), ws.numel(), stream), "om_bn_sync_stats")
             dist.all_gather_into_tensor(records, record, group=group)
-            _lib.check(L.om_bn_sync_forward(
+            _lib.check(getattr(L, "om_bn_sync_forward" + _sfx(x))(
                 _vp(x), B, C, H, W, _vp(records), R, _vp(gamma), _vp(beta), _vp(bn.running_mean), _vp(bn.running_var),
                 _vp(bn.num_batches_tracked) if track else None, float(bn.momentum), float(bn.eps), float(slope), _vp(residual),
                 _vp(y), save.data_ptr(), save.data_ptr() + 8 * C, _vp(n_total), stream), "om_bn_sync_forward")
@@ -586,13 +623,13 @@ class _SyncBNAct(torch.autograd.Function):
         sums = torch.empty(2 * C, dtype=torch.float64, device=dev)
         L, stream, ws = _bn_scratch(x)
         with _device(dev):
-            _lib.check(L.om_bn_sync_backward_sums(
+            _lib.check(getattr(L, "om_bn_sync_backward_sums" + _sfx(x))(
                 _vp(x), _vp(dy), B, C, H, W, _vp(gamma), _vp(beta), save.data_ptr(), save.data_ptr() + 8 * C, ctx.slope, _vp(sums),
                 dgb.data_ptr(), dgb.data_ptr() + 4 * C, ws.data_ptr(), ws.numel(), stream), "om_bn_sync_backward_sums")
             if dx is not None:
                 sums_all = torch.empty(R * 2 * C, dtype=torch.float64, device=dev)
                 dist.all_gather_into_tensor(sums_all, sums, group=ctx.group)
-                _lib.check(L.om_bn_sync_backward_dx(
+                _lib.check(getattr(L, "om_bn_sync_backward_dx" + _sfx(x))(
                     _vp(x), _vp(dy), B, C, H, W, _vp(gamma), _vp(beta), save.data_ptr(), save.data_ptr() + 8 * C, ctx.slope,
                     _vp(sums_all), R, _vp(n_total), _vp(dx), stream), "om_bn_sync_backward_dx")
         return _bn_grads(ctx, dx, dgb, dy)
@@ -616,15 +653,23 @@ def _check_bn_batch(bn, h, synced):
 
 def bn_leaky(x, bn, residual=None, slope=LEAKY_SLOPE, sync=False, process_group=None):
     """leaky_relu(bn(x), slope) (+ residual) as the HIP block: `bn` is an nn.BatchNorm2d in training or eval mode, x (and residual)
-    CUDA float32 NCHW-contiguous; anything else raises.  sync=True: in training mode and with more than one rank in `process_group`
+    CUDA NCHW-contiguous, both float32 or both bf16 (the output has their type; bn's parameters and buffers are float32 either
+    way); anything else raises.  sync=True: in training mode and with more than one rank in `process_group`
     (None: the default group) the batch statistics are those of every rank's batch (_SyncBNAct); otherwise nothing is exchanged."""
     synced = sync and bn.training and _sync_world_size(process_group) > 1
-    _require_nchw(x, "backend 'hip'", "the BatchNorm input (backend 'hip')")
+    _require_nchw(x, "backend 'hip'", "the BatchNorm input (backend 'hip')", ACT_DTYPES)
     _check_bn_batch(bn, x, synced)
-    _require_residual(residual, x.shape, x.device)
+    _require_residual(residual, x.shape, x.device, x.dtype)
     if synced:
         return _SyncBNAct.apply(x, bn.weight, bn.bias, residual, bn, slope, process_group)
     return _BNAct.apply(x, bn.weight, bn.bias, residual, bn, slope)
+
+
+def _same_type(residual, y):
+    """The residual of a backend-'torch' block, refused where torch's add would promote it or the block's output silently."""
+    if residual.dtype != y.dtype:
+        raise ValueError("residual is %s, the block's output %s: there is no cast" % (residual.dtype, y.dtype))
+    return residual
 
 
 class ConvBNLeaky(nn.Module):
@@ -649,12 +694,19 @@ class ConvBNLeaky(nn.Module):
     autograd node is made, and an input that requires grad raises (frozen blocks are a prefix of the network).  The forward is
     F.conv2d -> F.batch_norm(training=False) -> leaky (+ residual) with backend 'torch'; F.conv2d -> bn_leaky's eval kernel with
     backend 'hip'; and with conv_forward 'hip' the single kernel of conv_bn_leaky_frozen.  The keys and buffers are an unfrozen
-    block's; load_state_dict tolerates a missing num_batches_tracked (the reference's FrozenBatchNorm2d has none)."""
+    block's; load_state_dict tolerates a missing num_batches_tracked (the reference's FrozenBatchNorm2d has none).
+
+    amp None (default): float32.  amp 'bf16': the forward runs under torch.autocast(dtype=torch.bfloat16), so the convolution is
+    torch's in bf16 and the output is bf16: from the _bf16 kernels with backend 'hip' (a frozen block: their eval phase), from
+    torch's own bf16 batch_norm and leaky_relu with backend 'torch' (the comparator; CPU tensors too).  The parameters, their
+    gradients and the buffers stay float32.  A residual must have the block's element type.  Needs conv_backend and conv_forward
+    'torch'."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, backend="hip", conv_backend="torch",
-                 conv_forward="torch", frozen=False):
+                 conv_forward="torch", frozen=False, amp=None):
         super().__init__()
-        _check_backends(backend, conv_backend, conv_forward)
+        _check_backends(backend, conv_backend, conv_forward, amp=amp)
+        self.amp = amp
         self.backend = backend
         self.conv_backend = conv_backend
         self.conv_forward = conv_forward
@@ -698,9 +750,13 @@ class ConvBNLeaky(nn.Module):
             return bn_leaky(h, bn, residual=residual, slope=act.negative_slope)
         y = F.batch_norm(h, bn.running_mean, bn.running_var, bn.weight, bn.bias, False, 0.0, bn.eps)
         y = F.leaky_relu(y, act.negative_slope, inplace=True)
-        return y if residual is None else y + residual
+        return y if residual is None else y + _same_type(residual, y)
 
     def forward(self, x, residual=None):
+        with _autocast(self.amp, x):
+            return self._forward(x, residual)
+
+    def _forward(self, x, residual):
         if self.frozen:
             return self._frozen_forward(x, residual)
         conv, bn, act = self.conv_block[0], self.conv_block[1], self.conv_block[2]
@@ -715,7 +771,7 @@ class ConvBNLeaky(nn.Module):
             if training and bn.num_batches_tracked is not None:
                 bn.num_batches_tracked.add_(1)
             y = F.leaky_relu(y, act.negative_slope, inplace=True)
-            return y if residual is None else y + residual
+            return y if residual is None else y + _same_type(residual, y)
         return bn_leaky(h, bn, residual=residual, slope=act.negative_slope, sync=self.sync, process_group=self.process_group)
 
 
@@ -770,10 +826,16 @@ class OrienMaskYOLOFPNPlus(nn.Module):
     down-sampling layer plus its blocks each) as ConvBNLeaky(frozen=True): no gradients, running statistics in every mode, untouched
     buffers, and with conv_forward 'hip' one kernel per layer.  What the reference's freeze_backbone stage count means to do
     (model/backbone/darknet.py:31-38, model/base.py:210-266) under an unambiguous name: bools raise.  The keys, the parameters()
-    order and the buffers are those of frozen_stages=0, which builds the model as before; independent of backbone_batchnorm_eval."""
+    order and the buffers are those of frozen_stages=0, which builds the model as before; independent of backbone_batchnorm_eval.
+
+    amp (None / 'bf16', default None): mixed precision.  With 'bf16' the forward runs under torch.autocast(dtype=torch.bfloat16):
+    every convolution is torch's in bf16 (conv_backend / conv_forward 'hip' raise), the activations between them are bf16 through
+    the blocks (ConvBNLeaky) and, with route_backend 'hip', through upsample_concat; the head convolutions' outputs are returned
+    as float32, so the loss, the counters and the optimizer see what they see without amp.  Parameters, gradients, buffers and
+    the state_dict (keys and dtypes) are those of amp=None: checkpoints move freely between the two and to the inference model."""
 
     def __init__(self, num_anchors, num_classes, pretrained=None, freeze_backbone=False, backbone_batchnorm_eval=False,
-                 backend="hip", conv_backend="torch", conv_forward="torch", route_backend="torch", frozen_stages=0):
+                 backend="hip", conv_backend="torch", conv_forward="torch", route_backend="torch", frozen_stages=0, amp=None):
         super().__init__()
         if freeze_backbone is not False:
             # the reference's DarkNet53._freeze_network calls self._freeze_module, which does not exist (darknet.py:31-38)
@@ -782,7 +844,8 @@ class OrienMaskYOLOFPNPlus(nn.Module):
         if isinstance(frozen_stages, bool) or not isinstance(frozen_stages, int) or not 0 <= frozen_stages <= len(DARKNET_STAGES) + 1:
             raise ValueError("frozen_stages must be an int from 0 to %d (the number of backbone stages conv1 ... conv%d to freeze), "
                              "got %r" % (len(DARKNET_STAGES) + 1, len(DARKNET_STAGES) + 1, frozen_stages))
-        _check_backends(backend, conv_backend, conv_forward, route_backend)
+        _check_backends(backend, conv_backend, conv_forward, route_backend, amp)
+        self.amp = amp
         self.num_anchors = num_anchors
         self.num_classes = num_classes
         self.pretrained = pretrained
@@ -808,7 +871,7 @@ class OrienMaskYOLOFPNPlus(nn.Module):
                 # backbone.conv{i}[...]: frozen where i <= frozen_stages
                 frozen = spec.name.startswith("backbone.conv") and int(spec.name.split(".")[1][len("conv"):]) <= frozen_stages
                 m = ConvBNLeaky(spec.cin, spec.cout, spec.ksize, stride=spec.stride, padding=pad, backend=backend,
-                                conv_backend=conv_backend, conv_forward=conv_forward, frozen=frozen)
+                                conv_backend=conv_backend, conv_forward=conv_forward, frozen=frozen, amp=amp)
             else:
                 m = nn.Conv2d(spec.cin, spec.cout, spec.ksize, stride=spec.stride, padding=pad)
             node.add_module(leaf, m)
@@ -886,7 +949,7 @@ class OrienMaskYOLOFPNPlus(nn.Module):
         m = self._by_name[name]
         if self.conv_backend == "hip":
             return conv2d(x, m.weight, m.bias, m.stride, m.padding, forward=self.conv_forward)
-        return m(x)
+        return m(x).float() if self.amp else m(x)        # the heads leave the model as float32
 
     def _bbox_head(self, s, x):
         return self._plain("bbox_head%d.1" % s, self._by_name["bbox_head%d.0" % s](x))
@@ -894,6 +957,10 @@ class OrienMaskYOLOFPNPlus(nn.Module):
     def forward(self, x):
         if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] % 32 or x.shape[3] % 32:
             raise ValueError("x must be [B,3,H,W] with H and W multiples of 32, got %s" % (tuple(x.shape),))
+        with _autocast(self.amp, x):
+            return self._forward(x)
+
+    def _forward(self, x):
         x32, x16, x8, x4 = self._backbone_forward(x)
         neck32 = self._run("neck32", x32)
         neck16 = self._run("neck16", self._cat([self._route("route32.0", neck32, 2), x16]))

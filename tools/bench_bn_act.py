@@ -10,7 +10,12 @@ median against the fused pass counts (forward 3 passes over the activation tenso
 over the BatchNorm layers (median x multiplicity; 86 in the FPNPlus model) with the sum of the per-shape minima and maxima as its run-to-run range, and the peak
 memory of one full training step (forward + backward of the whole model) for both backends.
 
-    python tools/bench_bn_act.py [--batches 8 32] [--rounds 7] [--inner 5] [--warmup 3] [--out profiles/bn_act_bench.json]
+--dtype fp32 (default) times float32 activations; --dtype bf16 the bf16 entry points (the models' amp='bf16') against torch's bf16
+batch_norm + leaky_relu, under the names hip_bf16 / torch_bf16; --dtype both times all four in the same interleaved rounds, which
+is what a comparison of the two types needs.  Bytes are counted with the type's element size; the passes are the same.
+
+    python tools/bench_bn_act.py [--batches 8 32] [--rounds 7] [--inner 5] [--warmup 3] [--dtype fp32|bf16|both]
+                                 [--out profiles/bn_act_bench.json]
 
 prints one JSON line (and writes it to --out).
 """
@@ -66,20 +71,35 @@ def time_calls(fn, inner):
     return start.elapsed_time(stop) / inner, (t1 - t0) * 1e3 / inner
 
 
+DTYPES = {"fp32": (torch.float32, ""), "bf16": (torch.bfloat16, "_bf16")}
+
+
+def variants(dtype):
+    """name -> (block, tensor dtype): hip / torch for float32, hip_bf16 / torch_bf16 for bf16."""
+    kinds = ("fp32", "bf16") if dtype == "both" else (dtype,)
+    return {name + DTYPES[k][1]: (fn, DTYPES[k][0]) for k in kinds for name, fn in (("hip", hip_block), ("torch", torch_block))}
+
+
 def bench_shape(dev, B, C, H, W, residual, args):
     gen = torch.Generator(device=dev).manual_seed(C + H)
-    h = torch.randn(B, C, H, W, device=dev, generator=gen).requires_grad_(True)
-    res = torch.randn(B, C, H, W, device=dev, generator=gen) if residual else None
-    gy = torch.randn(B, C, H, W, device=dev, generator=gen)
+    blocks = variants(args.dtype)
+    data = {}
+    for dt in {d for _, d in blocks.values()}:          # the same values in either type, up to bf16's rounding
+        gen.manual_seed(C + H)
+        data[dt] = (torch.randn(B, C, H, W, device=dev, generator=gen).to(dt).requires_grad_(True),
+                    torch.randn(B, C, H, W, device=dev, generator=gen).to(dt) if residual else None,
+                    torch.randn(B, C, H, W, device=dev, generator=gen).to(dt))
     bn = torch.nn.BatchNorm2d(C).to(dev).train()
-    blocks = {"hip": hip_block, "torch": torch_block}
     out = {}
     state = {}
 
     def fwd(name):
-        state[name] = blocks[name](h, bn, res)
+        fn, dt = blocks[name]
+        h, res, _ = data[dt]
+        state[name] = fn(h, bn, res)
 
     def bwd(name):
+        h, _, gy = data[blocks[name][1]]
         h.grad = None
         state[name].backward(gy, retain_graph=True)
 
@@ -95,22 +115,23 @@ def bench_shape(dev, B, C, H, W, residual, args):
             samples[(name, "fwd")].append(d); host[(name, "fwd")].append(hst)
             d, hst = time_calls(lambda: bwd(name), args.inner)
             samples[(name, "bwd")].append(d); host[(name, "bwd")].append(hst)
-    tensor_bytes = 4 * B * C * H * W
     passes = {("hip", "fwd"): 3 + (1 if residual else 0), ("hip", "bwd"): 5, ("torch", "fwd"): 5 + (3 if residual else 0), ("torch", "bwd"): 8}
     for key, v in samples.items():
         v = sorted(v)
         med = statistics.median(v)
         hm = statistics.median(host[key])
+        tensor_bytes = blocks[key[0]][1].itemsize * B * C * H * W
+        n_pass = passes[(key[0].split("_")[0], key[1])]
         out["%s_%s" % key] = {"ms_median": round(med, 5), "ms_min": round(v[0], 5), "ms_max": round(v[-1], 5),
-                              "passes_counted": passes[key], "GBps_at_median": round(passes[key] * tensor_bytes / med / 1e6, 1),
-                              "share_of_6.3TBps": round(passes[key] * tensor_bytes / (med * 1e-3) / HBM_BYTES_PER_S, 3),
+                              "passes_counted": n_pass, "GBps_at_median": round(n_pass * tensor_bytes / med / 1e6, 1),
+                              "share_of_6.3TBps": round(n_pass * tensor_bytes / (med * 1e-3) / HBM_BYTES_PER_S, 3),
                               "host_ms_median": round(hm, 5), "host_bound": hm > 0.9 * med}
     return out
 
 
-def step_peak_memory(dev, backend, B, size):
+def step_peak_memory(dev, backend, B, size, amp=None):
     torch.manual_seed(0)
-    net = train.OrienMaskYOLOFPNPlus(3, 80, backend=backend).to(dev).train()
+    net = train.OrienMaskYOLOFPNPlus(3, 80, backend=backend, amp=amp).to(dev).train()
     x = torch.rand(B, 3, size, size, device=dev)
     for _ in range(2):                    # the second step is the steady state (gradients exist, the allocator is warm)
         torch.cuda.synchronize()
@@ -133,13 +154,15 @@ def main():
     ap.add_argument("--inner", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--memory-batch", type=int, default=8)
+    ap.add_argument("--dtype", choices=["fp32", "bf16", "both"], default="fp32", help="the activations' type (see above)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_bn_act.py needs an MI355X: there is nothing to time on a CPU")
     dev = torch.device("cuda:0")
     table = layer_table(args.size)
-    result = {"bench": "bn_act", "size": args.size, "rounds": args.rounds, "inner": args.inner, "warmup": args.warmup,
+    names = list(variants(args.dtype))
+    result = {"bench": "bn_act", "dtype": args.dtype, "size": args.size, "rounds": args.rounds, "inner": args.inner, "warmup": args.warmup,
               "device": torch.cuda.get_device_name(0), "torch": torch.__version__, "batches": {}}
     for B in args.batches:
         rows, sums = [], {}
@@ -151,12 +174,20 @@ def main():
                 for f in s:
                     s[f] += count * v[f]
             torch.cuda.empty_cache()
-        slower = [{"C": r["C"], "H": r["H"], "residual": r["residual"], "pass": p, "hip_ms": r["hip_" + p]["ms_median"],
-                   "torch_ms": r["torch_" + p]["ms_median"]} for r in rows for p in ("fwd", "bwd")
-                  if r["hip_" + p]["ms_median"] > r["torch_" + p]["ms_median"]]
-        result["batches"][str(B)] = {"shapes": rows, "layers": sum(table.values()), "sum_over_layers_ms": {k: {f: round(x, 4) for f, x in v.items()} for k, v in sums.items()},
-                                     "shapes_where_hip_is_slower": slower}
-    result["training_step_peak_memory"] = {b: step_peak_memory(dev, b, args.memory_batch, args.size) for b in ("hip", "torch")}
+        slower = [{"C": r["C"], "H": r["H"], "residual": r["residual"], "pass": p, "sfx": sfx, "hip_ms": r["hip%s_%s" % (sfx, p)]["ms_median"],
+                   "torch_ms": r["torch%s_%s" % (sfx, p)]["ms_median"]} for r in rows for p in ("fwd", "bwd")
+                  for sfx in ("", "_bf16") if "hip" + sfx in names
+                  if r["hip%s_%s" % (sfx, p)]["ms_median"] > r["torch%s_%s" % (sfx, p)]["ms_median"]]
+        batch = {"shapes": rows, "layers": sum(table.values()), "sum_over_layers_ms": {k: {f: round(x, 4) for f, x in v.items()} for k, v in sums.items()},
+                 "shapes_where_hip_is_slower": slower}
+        if args.dtype == "both":
+            batch["shapes_where_hip_bf16_is_slower_than_hip_fp32"] = [
+                {"C": r["C"], "H": r["H"], "residual": r["residual"], "pass": p, "bf16_ms": r["hip_bf16_" + p]["ms_median"],
+                 "fp32_ms": r["hip_" + p]["ms_median"]} for r in rows for p in ("fwd", "bwd")
+                if r["hip_bf16_" + p]["ms_median"] > r["hip_" + p]["ms_median"]]
+        result["batches"][str(B)] = batch
+    result["training_step_peak_memory"] = {n: step_peak_memory(dev, n.split("_")[0], args.memory_batch, args.size,
+                                                               "bf16" if n.endswith("_bf16") else None) for n in names}
     line = json.dumps(result)
     print(line)
     if args.out:

@@ -1,7 +1,7 @@
 """Steps per second of the training loop, sync-free against the reference's per-step host bookkeeping, on the same build.
 
     python tools/bench_train_step.py [--batch 8] [--size 544] [--steps 30] [--warmup 5] [--rounds 3] [--frozen-stages K]
-                                     [--default-backends] [--out profiles/train_step_bench.json]
+                                     [--default-backends] [--amp bf16] [--out profiles/train_step_bench.json]
 
 Both loops are orienmask_amd.trainer.Trainer._train_epoch over the same SyntheticLossLoader batches (made once, on the device),
 the trainable OrienMaskYOLOFPNPlus with every HIP backend, the HIP SGD step, accumulate 1 and log_freq = steps, so the sync-free
@@ -11,6 +11,10 @@ only difference is ``sync_free``.  An epoch of `warmup` batches runs first; then
 minimum and maximum steps per second over the rounds, and the spread that any comparison of the two has to clear, and the peak
 device memory of the timed epochs.  --frozen-stages K builds the model with frozen_stages=K (0, the default, leaves the model
 dict as it was); --default-backends leaves the four backend options at the model's defaults instead of every HIP backend.
+
+--amp bf16 compares precisions instead of loops: both loops are sync-free and use the model's default backends (amp needs torch's
+convolutions), one with the float32 model ("fp32") and one with amp='bf16' ("amp_bf16"), in the same alternating rounds; each
+loop's peak device memory is that of its own timed epochs (both models stay resident, so subtract nothing: compare the two).
 """
 import argparse
 import json
@@ -34,6 +38,7 @@ def main(argv=None):
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--frozen-stages", type=int, default=0, help="freeze backbone.conv1 ... conv{K} (0: none)")
     ap.add_argument("--default-backends", action="store_true", help="the model's default backends instead of every HIP backend")
+    ap.add_argument("--amp", choices=["bf16"], default=None, help="time the float32 model against amp (see above)")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     args = ap.parse_args(argv)
 
@@ -57,7 +62,7 @@ def main(argv=None):
                   lr_scheduler=dict(type="StepWarmUpLR", warmup_type="linear", warmup_iter=1000, warmup_ratio=0.1,
                                     milestones=[100000], gamma=0.1))
 
-    if args.default_backends:
+    if args.default_backends or args.amp:
         config["model"] = dict(type="OrienMaskYOLOFPNPlus", num_anchors=3, num_classes=80)
     if args.frozen_stages:
         config["model"]["frozen_stages"] = args.frozen_stages
@@ -67,30 +72,45 @@ def main(argv=None):
 
     warm, timed = loader(args.warmup), loader(args.steps)
     trainers = {}
-    for name, sync_free in (("sync_free", True), ("host_loop", False)):
-        t = builder.build_trainer(dict(config, name="bench_" + name), types.SimpleNamespace(resume=None, weights=None), dev,
-                                  train_loader=warm, sync_free=sync_free)
+    if args.amp:
+        loops = (("fp32", True, {}), ("amp_" + args.amp, True, dict(amp=args.amp)))
+    else:
+        loops = (("sync_free", True, {}), ("host_loop", False, {}))
+    for name, sync_free, model_kw in loops:
+        t = builder.build_trainer(dict(config, name="bench_" + name, model=dict(config["model"], **model_kw)),
+                                  types.SimpleNamespace(resume=None, weights=None), dev, train_loader=warm, sync_free=sync_free)
         t._train_epoch(1)
         t.train_loader = timed
         trainers[name] = t
     rates = {name: [] for name in trainers}
+    peaks = {name: 0 for name in trainers}
     torch.cuda.synchronize(dev)
     torch.cuda.reset_peak_memory_stats(dev)
     for _ in range(args.rounds):
         for name, t in trainers.items():
             torch.cuda.synchronize(dev)
+            if args.amp:
+                torch.cuda.reset_peak_memory_stats(dev)
             t0 = time.perf_counter()
             t._train_epoch(2)
             torch.cuda.synchronize(dev)
             rates[name].append(args.steps / (time.perf_counter() - t0))
+            peaks[name] = max(peaks[name], int(torch.cuda.max_memory_allocated(dev)))
     shutil.rmtree(log_dir, ignore_errors=True)          # the trainers' run directories: nothing in them is a result
     out = dict(bench="train_step", batch=args.batch, size=s, steps=args.steps, warmup=args.warmup, rounds=args.rounds,
                device=torch.cuda.get_device_name(0), torch=torch.__version__, frozen_stages=args.frozen_stages,
-               backends="default" if args.default_backends else "hip", peak_bytes=int(torch.cuda.max_memory_allocated(dev)))
+               backends="default" if args.default_backends or args.amp else "hip", amp=args.amp,
+               peak_bytes=max(peaks.values()))
     for name, r in rates.items():
         out[name] = dict(steps_per_s_median=round(statistics.median(r), 3), steps_per_s_min=round(min(r), 3),
-                         steps_per_s_max=round(max(r), 3), images_per_s_median=round(statistics.median(r) * args.batch, 2))
-    out["ratio_of_medians"] = round(out["sync_free"]["steps_per_s_median"] / out["host_loop"]["steps_per_s_median"], 4)
+                         steps_per_s_max=round(max(r), 3), images_per_s_median=round(statistics.median(r) * args.batch, 2),
+                         ms_per_step_median=round(1e3 / statistics.median(r), 3))
+        if args.amp:
+            out[name]["peak_bytes"] = peaks[name]
+    first, second = [n for n, _, _ in loops]
+    # sync_free over host_loop; with --amp, amp over fp32
+    out["ratio_of_medians"] = round(out[second if args.amp else first]["steps_per_s_median"]
+                                    / out[first if args.amp else second]["steps_per_s_median"], 4)
     out["spread"] = round(max((max(r) - min(r)) / statistics.median(r) for r in rates.values()), 4)
     line = json.dumps(out)
     print(line)

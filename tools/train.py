@@ -1,12 +1,14 @@
 """Train an OrienMask model on the MI355X: the reference's train.py against orienmask_amd.
 
-    python tools/train.py --config CONFIG [--resume CHECKPOINT | --weights WEIGHTS] [--synthetic N] [--frozen-stages K]
+    python tools/train.py --config CONFIG [--resume CHECKPOINT | --weights WEIGHTS] [--synthetic N] [--frozen-stages K] [--amp bf16]
 
 CONFIG is a JSON file -- the ``config.json`` a trainer writes into its checkpoint directory is one -- or, where a ``config``
 package with the reference's ``get_config`` is importable, a config name.  ``--synthetic N`` trains on N seeded synthetic images
 (tester.SyntheticLossLoader) of the loss's image size instead of config['train_loader'], so the tool runs without a dataset; no
 validation then.  ``--frozen-stages K`` (0...6) overrides the model's ``frozen_stages``: backbone.conv1 ... conv{K} are frozen
-(orienmask_amd.train), the usual way to fine-tune a pretrained backbone.  With several processes (torchrun), each uses the GPU of its LOCAL_RANK.
+(orienmask_amd.train), the usual way to fine-tune a pretrained backbone.  ``--amp bf16`` sets the model's ``amp``: bf16 activations
+under torch.autocast, float32 parameters, statistics, loss and optimizer (resuming a checkpoint that was trained with another ``amp``
+fails the trainer's model-config check, as any other change of the model does).  With several processes (torchrun), each uses the GPU of its LOCAL_RANK.
 """
 import argparse
 import json
@@ -27,7 +29,7 @@ def load_config(name):
     return get_config(name)
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("-c", "--config", required=True, help="a config JSON file (or a config name, see above)")
     ap.add_argument("-r", "--resume", default=None, help="checkpoint to resume from")
@@ -35,14 +37,28 @@ def main(argv=None):
     ap.add_argument("--synthetic", type=int, default=0, metavar="N", help="train on N synthetic images")
     ap.add_argument("--frozen-stages", type=int, default=None, metavar="K",
                     help="freeze backbone.conv1 ... conv{K} (0...6), overriding the config's model.frozen_stages")
+    ap.add_argument("--amp", choices=["bf16"], default=None,
+                    help="mixed precision: bf16 activations (the model's amp), overriding the config's model.amp")
     args = ap.parse_args(argv)
     assert not (args.resume and args.weights), "--resume and --weights exclude each other"
+    return args
+
+
+def apply_overrides(config, args):
+    """The config with the command line's model options in config['model']; the caller's dicts are not mutated."""
+    if args.frozen_stages is not None:
+        config = dict(config, model=dict(config["model"], frozen_stages=args.frozen_stages))
+    if args.amp is not None:
+        config = dict(config, model=dict(config["model"], amp=args.amp))
+    return config
+
+
+def main(argv=None):
+    args = parse_args(argv)
 
     import torch
     from orienmask_amd import builder
-    config = load_config(args.config)
-    if args.frozen_stages is not None:
-        config = dict(config, model=dict(config["model"], frozen_stages=args.frozen_stages))
+    config = apply_overrides(load_config(args.config), args)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if not torch.cuda.is_available():
