@@ -9,7 +9,7 @@ Reference structure this table restates (not copied; rebuilt from the shapes):
   * necks / routes / heads / skips            /root/reference/model/orienmask_yolo_fpnplus.py:9-72
   * conv -> BN(eps=1e-5) -> LeakyReLU(0.1)    /root/reference/model/base.py:104-137,278-279
 
-The C++ side (``csrc/om_graph.cpp``) builds the same graph independently;
+The C++ side (``csrc/om_model.cpp``) builds the same graph independently;
 ``pack.py`` cross-checks the two through ``om_model_layer_info``.
 """
 from collections import namedtuple

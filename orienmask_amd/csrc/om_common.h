@@ -106,6 +106,15 @@ struct ConvArgsH {
     const void* seg_ptr[4] = {nullptr, nullptr, nullptr, nullptr};
     int seg_channels[4] = {0, 0, 0, 0}, seg_pix_stride[4] = {0, 0, 0, 0}, seg_up[4] = {1, 1, 1, 1};
 };
+// The shape, stride and mode fields of one launch (ConvArgs or ConvArgsH)
+template <class Args>
+static void fill_conv_shape(Args& a, int B, int H, int W, int cin, int in_pix_stride, int cout, int cout_pad, int ks, int stride, int leaky,
+                            int res_pix_stride, int out_pix_stride, int out_mode = 0, int up = 1) {
+    a.B = B; a.H = H; a.W = W; a.cin = cin; a.in_pix_stride = in_pix_stride;
+    a.Ho = H / stride; a.Wo = W / stride; a.cout = cout; a.cout_pad = cout_pad;
+    a.ks = ks; a.stride = stride; a.leaky = leaky; a.res_pix_stride = res_pix_stride;
+    a.out_pix_stride = out_pix_stride; a.out_mode = out_mode; a.up = up;
+}
 int launch_conv_igemm_f16(const ConvArgsH& a, hipStream_t stream);     // dispatches stride-1 3x3 layers to conv3x3_f16.hip
 int launch_conv3x3_f16(const ConvArgsH& a, hipStream_t stream);
 bool conv3x3_f16_supported(const ConvArgsH& a);

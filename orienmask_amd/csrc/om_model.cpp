@@ -116,16 +116,6 @@ static int algo_code(Form f, bool f16) {
     return -1;
 }
 
-// The shape, stride and mode fields of one launch (ConvArgs or ConvArgsH)
-template <class Args>
-static void fill_conv_shape(Args& a, int B, int H, int W, int cin, int in_pix_stride, int cout, int cout_pad, int ks, int stride, int leaky,
-                            int res_pix_stride, int out_pix_stride, int out_mode = 0, int up = 1) {
-    a.B = B; a.H = H; a.W = W; a.cin = cin; a.in_pix_stride = in_pix_stride;
-    a.Ho = H / stride; a.Wo = W / stride; a.cout = cout; a.cout_pad = cout_pad;
-    a.ks = ks; a.stride = stride; a.leaky = leaky; a.res_pix_stride = res_pix_stride;
-    a.out_pix_stride = out_pix_stride; a.out_mode = out_mode; a.up = up;
-}
-
 }  // namespace om
 
 // Process-wide A/B switches, default on; each is off while its environment variable (read once, by the first call that asks) is 1, or
@@ -834,16 +824,6 @@ struct ForwardRun {
     }
 };
 
-// The om_conv2d_* unit-test entries: ONE library-owned block of sync words, zeroed before every launch, so that the persistent tile
-// queue (what om_forward uses, with tickets carved from the caller's workspace) is what gets tested and benchmarked.
-int unit_ticket(hipStream_t stream, int** out) {
-    static int* g_ticket = nullptr;
-    if (!g_ticket) OM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&g_ticket), om::SYNC_WORDS * sizeof(int)));
-    if (int rc = om::launch_zero_words(g_ticket, om::SYNC_WORDS, stream)) return rc;
-    *out = g_ticket;
-    return OM_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -1142,225 +1122,12 @@ int om_profile_read(om_model* m, float* layer_ms, float* layer_pre_ms, int n_lay
     return OM_OK;
 }
 
-int om_conv2d_mode(const float* in, int B, int H, int W, int cin, int in_pix_stride, const float* w, const float* scale,
-                   const float* shift, int cout, int ksize, int stride, int leaky, const float* res, int res_pix_stride,
-                   float* out, int out_pix_stride, int out_mode, int up, om_stream stream) {
-    OM_REQUIRE(B > 0 && H > 0 && W > 0 && stride >= 1 && H % stride == 0 && W % stride == 0, OM_EINVAL,
-               "om_conv2d: bad shape");
-    OM_REQUIRE(out_mode >= 0 && out_mode <= 2 && up >= 1 && (out_mode == 1 || up == 1), OM_EINVAL,
-               "om_conv2d_mode: out_mode=%d up=%d (0 NHWC, 1 NHWC replicated up x up, 2 NCHW)", out_mode, up);
-    om::ConvArgs a;
-    a.in = in; a.w = w; a.scale = scale; a.shift = shift; a.res = res; a.out = out;
-    om::fill_conv_shape(a, B, H, W, cin, in_pix_stride, cout, om::round_up(cout, 32), ksize, stride, leaky, res_pix_stride, out_pix_stride, out_mode, up);
-    if (int rc = unit_ticket(static_cast<hipStream_t>(stream), &a.ticket)) return rc;
-    return om::launch_conv_igemm(a, static_cast<hipStream_t>(stream));
-}
-
-int om_conv2d_split(const float* in, int B, int H, int W, int cin, int in_pix_stride, const void* w_split,
-                    const float* scale_split, const float* shift, int cout, int ksize, int stride, int leaky, const float* res,
-                    int res_pix_stride, float* out, int out_pix_stride, int out_mode, int up, int tile_bm, int tile_bn,
-                    int32_t* status_dev, om_stream stream) {
-    OM_REQUIRE(B > 0 && H > 0 && W > 0 && stride >= 1 && H % stride == 0 && W % stride == 0, OM_EINVAL,
-               "om_conv2d_split: bad shape");
-    OM_REQUIRE(out_mode >= 0 && out_mode <= 2 && up >= 1 && (out_mode == 1 || up == 1), OM_EINVAL,
-               "om_conv2d_split: out_mode=%d up=%d (0 NHWC, 1 NHWC replicated up x up, 2 NCHW)", out_mode, up);
-    om::ConvArgs a;
-    a.in = in; a.w = static_cast<const float*>(w_split); a.scale = scale_split; a.shift = shift; a.res = res; a.out = out;
-    om::fill_conv_shape(a, B, H, W, cin, in_pix_stride, cout, om::round_up(cout, 32), ksize, stride, leaky, res_pix_stride, out_pix_stride, out_mode, up);
-    a.force_bm = tile_bm; a.force_bn = tile_bn; a.status = status_dev;
-    if (int rc = unit_ticket(static_cast<hipStream_t>(stream), &a.ticket)) return rc;
-    return om::launch_conv_igemm_split(a, static_cast<hipStream_t>(stream));
-}
-
-int om_conv2d_split_k(const float* in, int B, int H, int W, int cin, int in_pix_stride, const void* w_split,
-                      const float* scale_split, const float* shift, int cout, int ksize, int stride, int leaky, const float* res,
-                      int res_pix_stride, float* out, int out_pix_stride, int out_mode, int up, int tile_bm, int tile_bn,
-                      int max_parts, int32_t* status_dev, om_stream stream) {
-    OM_REQUIRE(B > 0 && H > 0 && W > 0 && stride >= 1 && H % stride == 0 && W % stride == 0, OM_EINVAL,
-               "om_conv2d_split_k: bad shape");
-    OM_REQUIRE(out_mode >= 0 && out_mode <= 2 && up >= 1 && (out_mode == 1 || up == 1), OM_EINVAL,
-               "om_conv2d_split_k: out_mode=%d up=%d (0 NHWC, 1 NHWC replicated up x up, 2 NCHW)", out_mode, up);
-    OM_REQUIRE(max_parts >= 1 && max_parts <= 8, OM_EINVAL, "om_conv2d_split_k: max_parts=%d (1 .. 8)", max_parts);
-    om::ConvArgs a;
-    a.in = in; a.w = static_cast<const float*>(w_split); a.scale = scale_split; a.shift = shift; a.res = res; a.out = out;
-    om::fill_conv_shape(a, B, H, W, cin, in_pix_stride, cout, om::round_up(cout, 32), ksize, stride, leaky, res_pix_stride, out_pix_stride, out_mode, up);
-    a.force_bm = tile_bm; a.force_bn = tile_bn; a.status = status_dev;
-    a.ksplit_max = max_parts;
-    // unit-test entry only: room of the library's own for 512 parts of 128 x 64 floats
-    static float* g_partial = nullptr;
-    if (!g_partial) OM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&g_partial), (size_t)512 * 128 * 64 * sizeof(float)));
-    if (int rc = unit_ticket(static_cast<hipStream_t>(stream), &a.ticket)) return rc;
-    a.sk_partial = g_partial;
-    return om::launch_conv_igemm_split(a, static_cast<hipStream_t>(stream));
-}
-
-int om_conv2d_split_gather(int nseg, const float* const* seg_ptr, const int* seg_channels, const int* seg_pix_stride,
-                           const int* seg_up, int B, int H, int W, const void* w_split, const float* scale_split, const float* shift,
-                           int cout, int leaky, float* out, int out_pix_stride, int32_t* status_dev, om_stream stream) {
-    OM_REQUIRE(B > 0 && H > 0 && W > 0 && nseg >= 1 && nseg <= 4 && seg_ptr && seg_channels && seg_pix_stride && seg_up, OM_EINVAL,
-               "om_conv2d_split_gather: bad shape / null segment table (nseg=%d)", nseg);
-    om::ConvArgs a;
-    a.in = nullptr; a.w = static_cast<const float*>(w_split); a.scale = scale_split; a.shift = shift; a.res = nullptr; a.out = out;
-    a.nseg = nseg;
-    int cin = 0;
-    for (int g = 0; g < nseg; ++g) {
-        a.seg_ptr[g] = seg_ptr[g]; a.seg_channels[g] = seg_channels[g]; a.seg_pix_stride[g] = seg_pix_stride[g]; a.seg_up[g] = seg_up[g];
-        cin += seg_channels[g];
-    }
-    OM_REQUIRE(cin > 0 && cin % 32 == 0, OM_EINVAL, "om_conv2d_split_gather: %d input channels", cin);
-    om::fill_conv_shape(a, B, H, W, cin, 0, cout, om::round_up(cout, 32), 1, 1, leaky, 0, out_pix_stride);
-    a.status = status_dev;
-    if (int rc = unit_ticket(static_cast<hipStream_t>(stream), &a.ticket)) return rc;
-    return om::launch_conv_igemm_split(a, static_cast<hipStream_t>(stream));
-}
-
-int om_conv2d(const float* in, int B, int H, int W, int cin, int in_pix_stride, const float* w, const float* scale,
-              const float* shift, int cout, int ksize, int stride, int leaky, const float* res, int res_pix_stride,
-              float* out, int out_pix_stride, om_stream stream) {
-    return om_conv2d_mode(in, B, H, W, cin, in_pix_stride, w, scale, shift, cout, ksize, stride, leaky, res, res_pix_stride, out,
-                          out_pix_stride, 0, 1, stream);
-}
-
-size_t om_conv2d_winograd_scratch_bytes(int B, int H, int W, int cin) {
-    if (B <= 0 || H <= 0 || W <= 0 || cin <= 0) return 0;
-    return om::align_up(om::wino_scratch_floats(B, H, W, cin) * sizeof(float), 256);
-}
-
-int om_conv2d_winograd(const float* in, int B, int H, int W, int cin, int in_pix_stride, const float* u,
-                       const float* scale, const float* shift, int cout, int leaky, const float* res,
-                       int res_pix_stride, float* out, int out_pix_stride, void* scratch, size_t scratch_bytes,
-                       om_stream stream) {
-    OM_REQUIRE(B > 0 && H > 0 && W > 0, OM_EINVAL, "om_conv2d_winograd: bad shape");
-    OM_REQUIRE(scratch && scratch_bytes >= om_conv2d_winograd_scratch_bytes(B, H, W, cin), OM_ENOMEM,
-               "om_conv2d_winograd: scratch too small");
-    om::ConvArgs a;
-    a.in = in; a.w = u; a.scale = scale; a.shift = shift; a.res = res; a.out = out;
-    om::fill_conv_shape(a, B, H, W, cin, in_pix_stride, cout, om::round_up(cout, 64), 3, 1, leaky, res_pix_stride, out_pix_stride);
-    if (int rc = unit_ticket(static_cast<hipStream_t>(stream), &a.ticket)) return rc;
-    return om::launch_conv_winograd(a, static_cast<float*>(scratch), static_cast<hipStream_t>(stream));
-}
-
-int om_conv2d_f16(const void* in, int B, int H, int W, int cin, int in_pix_stride, const void* w, const float* scale,
-                  const float* shift, int cout, int ksize, int stride, int leaky, const void* res, int res_pix_stride,
-                  void* out, int out_pix_stride, int out_f32, om_stream stream) {
-    OM_REQUIRE(B > 0 && H > 0 && W > 0 && stride >= 1 && H % stride == 0 && W % stride == 0, OM_EINVAL,
-               "om_conv2d_f16: bad shape");
-    om::ConvArgsH a;
-    a.in = in; a.w = w; a.scale = scale; a.shift = shift; a.res = res; a.out = out;
-    om::fill_conv_shape(a, B, H, W, cin, in_pix_stride, cout, om::round_up(cout, 32), ksize, stride, leaky, res_pix_stride, out_pix_stride);
-    a.out_f32 = out_f32;
-    if (int rc = unit_ticket(static_cast<hipStream_t>(stream), &a.ticket)) return rc;
-    return om::launch_conv_igemm_f16(a, static_cast<hipStream_t>(stream));
-}
-
-int om_conv2d_stem_f16(const float* in, int B, int H, int W, const float* w, const float* scale, const float* shift,
-                       int cout, void* out, om_stream stream) {
-    return om::launch_conv_stem_f16(in, B, H, W, w, scale, shift, cout, out, static_cast<hipStream_t>(stream));
-}
-
-size_t om_conv2d_winograd24_scratch_bytes(int B, int H, int W, int cin) {
-    if (B <= 0 || H <= 0 || W <= 0 || cin <= 0) return 0;
-    return om::align_up(om::wino24_scratch_floats(B, H, W, cin) * sizeof(float), 256) + om::SK_PARTIAL_BYTES;
-}
-
-static int conv2d_winograd24_impl(const float* in, int B, int H, int W, int cin, int in_pix_stride, const float* u,
-                                  const float* scale, const float* shift, int cout, int leaky, const float* res,
-                                  int res_pix_stride, float* out, int out_pix_stride, void* scratch, size_t scratch_bytes,
-                                  om_stream stream, int split, int32_t* status_dev) {
-    OM_REQUIRE(B > 0 && H > 0 && W > 0, OM_EINVAL, "om_conv2d_winograd24: bad shape");
-    OM_REQUIRE(scratch && scratch_bytes >= om_conv2d_winograd24_scratch_bytes(B, H, W, cin), OM_ENOMEM,
-               "om_conv2d_winograd24: scratch too small");
-    om::ConvArgs a;
-    a.in = in; a.w = u; a.scale = scale; a.shift = shift; a.res = res; a.out = out;
-    om::fill_conv_shape(a, B, H, W, cin, in_pix_stride, cout, om::round_up(cout, 64), 3, 1, leaky, res_pix_stride, out_pix_stride);
-    a.split = split; a.status = status_dev;
-    if (int rc = unit_ticket(static_cast<hipStream_t>(stream), &a.ticket)) return rc;
-    a.sk_partial = reinterpret_cast<float*>(static_cast<char*>(scratch) + om::align_up(om::wino24_scratch_floats(B, H, W, cin) * sizeof(float), 256));
-    return om::launch_conv_winograd24(a, static_cast<float*>(scratch), static_cast<hipStream_t>(stream));
-}
-
-int om_conv2d_winograd24(const float* in, int B, int H, int W, int cin, int in_pix_stride, const float* u,
-                         const float* scale, const float* shift, int cout, int leaky, const float* res,
-                         int res_pix_stride, float* out, int out_pix_stride, void* scratch, size_t scratch_bytes,
-                         om_stream stream) {
-    return conv2d_winograd24_impl(in, B, H, W, cin, in_pix_stride, u, scale, shift, cout, leaky, res, res_pix_stride, out,
-                                  out_pix_stride, scratch, scratch_bytes, stream, 0, nullptr);
-}
-
-int om_conv2d_winograd24_split(const float* in, int B, int H, int W, int cin, int in_pix_stride, const void* u_split,
-                               const float* scale_split, const float* shift, int cout, int leaky, const float* res,
-                               int res_pix_stride, float* out, int out_pix_stride, void* scratch, size_t scratch_bytes,
-                               int32_t* status_dev, om_stream stream) {
-    return conv2d_winograd24_impl(in, B, H, W, cin, in_pix_stride, static_cast<const float*>(u_split), scale_split, shift, cout,
-                                  leaky, res, res_pix_stride, out, out_pix_stride, scratch, scratch_bytes, stream, 1, status_dev);
-}
-
-int om_conv2d_wino14_split(const float* in, int B, int H, int W, int cin, int in_pix_stride, const void* u14_split,
-                           const float* scale_split, const float* shift, int cout, int leaky, const float* res,
-                           int res_pix_stride, float* out, int out_pix_stride, int32_t* status_dev, om_stream stream) {
-    OM_REQUIRE(B > 0 && H > 0 && W > 0, OM_EINVAL, "om_conv2d_wino14_split: bad shape");
-    om::ConvArgs a;
-    a.in = in; a.w = static_cast<const float*>(u14_split); a.scale = scale_split; a.shift = shift; a.res = res; a.out = out;
-    om::fill_conv_shape(a, B, H, W, cin, in_pix_stride, cout, om::round_up(cout, 64), 3, 1, leaky, res_pix_stride, out_pix_stride);
-    a.split = 1; a.status = status_dev;
-    if (int rc = unit_ticket(static_cast<hipStream_t>(stream), &a.ticket)) return rc;
-    return om::launch_conv_wino14_split(a, static_cast<hipStream_t>(stream));
-}
-
-int om_conv2d_wino14_blocks(int B, int H, int W, int* classes, int* row_pitch, long long* m_tiles) {
-    OM_REQUIRE(B > 0 && H > 0 && W > 0 && classes && row_pitch && m_tiles, OM_EINVAL, "om_conv2d_wino14_blocks: bad argument");
-    om::Wino14Class cls[om::W14_MAXCLS];
-    long long gtot = 0;
-    const int n = om::wino14_blocks(B, H, W, cls, row_pitch, &gtot, m_tiles);
-    for (int k = 0; k < n; ++k) {
-        const int v[5] = {cls[k].t0, cls[k].Ct, cls[k].ncb, cls[k].R, cls[k].nrb};
-        for (int i = 0; i < 5; ++i) classes[5 * k + i] = v[i];
-    }
-    return n;
-}
-
-size_t om_conv2d_wino14_wide_scratch_bytes(int B, int H, int W, int cin) {
-    if (B <= 0 || H <= 0 || W <= 0 || cin <= 0 || cin % 16) return 0;
-    return om::align_up(om::wino14_wide_scratch_floats(B, H, W, cin) * sizeof(float), 256);
-}
-
-int om_conv2d_wino14_wide(const float* in, int B, int H, int W, int cin, int in_pix_stride, const void* u14_split,
-                          const float* scale_split, const float* shift, int cout, int leaky, const float* res,
-                          int res_pix_stride, float* out, int out_pix_stride, void* scratch, size_t scratch_bytes,
-                          int32_t* status_dev, om_stream stream) {
-    OM_REQUIRE(B > 0 && H > 0 && W > 0, OM_EINVAL, "om_conv2d_wino14_wide: bad shape");
-    OM_REQUIRE(scratch && scratch_bytes >= om_conv2d_wino14_wide_scratch_bytes(B, H, W, cin), OM_ENOMEM,
-               "om_conv2d_wino14_wide: scratch too small");
-    om::ConvArgs a;
-    a.in = in; a.w = static_cast<const float*>(u14_split); a.scale = scale_split; a.shift = shift; a.res = res; a.out = out;
-    om::fill_conv_shape(a, B, H, W, cin, in_pix_stride, cout, om::round_up(cout, 64), 3, 1, leaky, res_pix_stride, out_pix_stride);
-    a.split = 1; a.status = status_dev;
-    if (int rc = unit_ticket(static_cast<hipStream_t>(stream), &a.ticket)) return rc;
-    return om::launch_conv_wino14_wide(a, static_cast<float*>(scratch), static_cast<hipStream_t>(stream));
-}
-
 int om_set_wino14_wide(int on) {
     OM_REQUIRE(on == 0 || on == 1, OM_EINVAL, "om_set_wino14_wide: %d", on);
     switch_flag(SW_W14_WIDE).store(on, std::memory_order_relaxed);
     return OM_OK;
 }
 int om_get_wino14_wide(void) { return switch_on(SW_W14_WIDE) ? 1 : 0; }
-
-int om_conv2d_stem3_split(const float* in, int B, int H, int W, const float* w1, const float* scale1, const float* shift1,
-                          const void* w2_split, const float* scale2_split, const float* shift2, int cout2, int leaky2, float* out,
-                          int out_pix_stride, const void* w3_split, const float* scale3_split, const float* shift3, int cout3, int leaky3,
-                          float* out3, int out3_pix_stride, int32_t* status_dev, om_stream stream) {
-    om::Stem2Third third{w3_split, scale3_split, shift3, out3, cout3, leaky3, out3_pix_stride};
-    return om::launch_conv_stem2_split(in, B, H, W, w1, scale1, shift1, w2_split, scale2_split, shift2, cout2, leaky2, out,
-                                       out_pix_stride, status_dev, static_cast<hipStream_t>(stream), &third);
-}
-
-int om_conv2d_stem2_f16(const float* in, int B, int H, int W, const float* w1, const float* scale1, const float* shift1,
-                        const void* w2_f16, const float* scale2, const float* shift2, int cout2, int leaky2, void* out, int out_pix_stride,
-                        om_stream stream) {
-    return om::launch_conv_stem2_f16(in, B, H, W, w1, scale1, shift1, w2_f16, scale2, shift2, cout2, leaky2, out, out_pix_stride,
-                                     static_cast<hipStream_t>(stream));
-}
 
 int om_set_stem_fusion(int which, int on) {
     OM_REQUIRE((which == 0 || which == 1) && (on == 0 || on == 1), OM_EINVAL, "om_set_stem_fusion: which=%d on=%d", which, on);
@@ -1379,18 +1146,6 @@ int om_set_conv3x3_f16_variant(int mode) {
     OM_REQUIRE(mode >= 0 && mode <= 2, OM_EINVAL, "om_set_conv3x3_f16_variant: %d", mode);
     om::conv3x3_f16_set_tall(mode);
     return OM_OK;
-}
-
-int om_conv2d_stem(const float* in, int B, int H, int W, const float* w, const float* scale, const float* shift,
-                   int cout, float* out, om_stream stream) {
-    return om::launch_conv_stem(in, B, H, W, w, scale, shift, cout, out, static_cast<hipStream_t>(stream));
-}
-
-int om_conv2d_stem2_split(const float* in, int B, int H, int W, const float* w1, const float* scale1, const float* shift1,
-                          const void* w2_split, const float* scale2_split, const float* shift2, int cout2, int leaky2, float* out,
-                          int out_pix_stride, int32_t* status_dev, om_stream stream) {
-    return om::launch_conv_stem2_split(in, B, H, W, w1, scale1, shift1, w2_split, scale2_split, shift2, cout2, leaky2, out,
-                                       out_pix_stride, status_dev, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN, REPO, fixture_weights_and_input, golden_files, post_cfg
+from conv_cases import LayerCase
 from oracle import orienmask_ref as R
 from orienmask_amd import lib as omlib
 from orienmask_amd import synth
@@ -213,27 +214,14 @@ CONV_CASES = [
 def test_conv_layer_matches_torch(dev, case):
     B, H, W, cin, cout, k, stride, leaky, use_res = case
     L = omlib.load()
-    g = torch.Generator().manual_seed(sum(case))
-    x = torch.randn(B, cin, H, W, generator=g)
-    w = torch.randn(cout, cin, k, k, generator=g) / (cin * k * k) ** 0.5
-    scale = torch.rand(cout, generator=g) + 0.5
-    shift = torch.randn(cout, generator=g) * 0.2
-    Ho, Wo = H // stride, W // stride
-    res = torch.randn(B, cout, Ho, Wo, generator=g) if use_res else None
-    want = torch.nn.functional.conv2d(x.double(), w.double(), None, stride, k // 2)
-    want = want * scale.double().view(1, -1, 1, 1) + shift.double().view(1, -1, 1, 1)
-    if leaky:
-        want = torch.where(want > 0, want, want * 0.1)
-    if use_res:
-        want = want + res.double()
+    c = LayerCase(sum(case), case)
+    want, Ho, Wo = c.want, c.Ho, c.Wo
     cpad = (cout + 31) // 32 * 32
     wp = torch.zeros(cpad, k * k * cin)
-    wp[:cout] = w.permute(0, 2, 3, 1).reshape(cout, -1)
-    sp = torch.zeros(cpad); sp[:cout] = scale
-    hp = torch.zeros(cpad); hp[:cout] = shift
-    xd = x.permute(0, 2, 3, 1).contiguous().to(dev)
+    wp[:cout] = c.w.permute(0, 2, 3, 1).reshape(cout, -1)
+    sp, hp = c.padded(cpad)
+    xd, rd = c.nhwc(c.x, dev), c.nhwc(c.res, dev)
     wd, sd_, hd = wp.to(dev), sp.to(dev), hp.to(dev)
-    rd = res.permute(0, 2, 3, 1).contiguous().to(dev) if use_res else None
     out = torch.full((B, Ho, Wo, cout), float("nan"), device=dev)
     rc = L.om_conv2d(_p(xd), B, H, W, cin, cin, _p(wd), _p(sd_), _p(hd), cout, k, stride, leaky,
                      _p(rd) if use_res else None, cout if use_res else 0, _p(out), cout,
@@ -252,19 +240,12 @@ def test_conv_upsample_epilogue_matches_torch(dev, up, cin, cout, hw, cstride, c
     L = omlib.load()
     H, W = hw
     B = 2
-    g = torch.Generator().manual_seed(up * 100 + cout)
-    x = torch.randn(B, cin, H, W, generator=g)
-    w = torch.randn(cout, cin, 1, 1, generator=g) / cin ** 0.5
-    scale = torch.rand(cout, generator=g) + 0.5
-    shift = torch.randn(cout, generator=g) * 0.2
-    want = torch.nn.functional.conv2d(x.double(), w.double()) * scale.double().view(1, -1, 1, 1) + shift.double().view(1, -1, 1, 1)
-    want = torch.where(want > 0, want, want * 0.1)
-    want = torch.nn.functional.interpolate(want, scale_factor=float(up), mode="nearest")
+    c = LayerCase(up * 100 + cout, (B, H, W, cin, cout, 1, 1, 1, False))
+    want = torch.nn.functional.interpolate(c.want, scale_factor=float(up), mode="nearest")
     cpad = (cout + 31) // 32 * 32
-    wp = torch.zeros(cpad, cin); wp[:cout] = w.reshape(cout, cin)
-    sp = torch.zeros(cpad); sp[:cout] = scale
-    hp = torch.zeros(cpad); hp[:cout] = shift
-    xd = x.permute(0, 2, 3, 1).contiguous().to(dev)
+    wp = torch.zeros(cpad, cin); wp[:cout] = c.w.reshape(cout, cin)
+    sp, hp = c.padded(cpad)
+    xd = c.nhwc(c.x, dev)
     wd, sd_, hd = wp.to(dev), sp.to(dev), hp.to(dev)
     buf = torch.full((B, H * up, W * up, cstride), 7.0, device=dev)          # the concat buffer
     view = buf[..., coff:]
@@ -291,27 +272,13 @@ def test_conv_split_layer_matches_torch(dev, case):
     from orienmask_amd.pack import conv_weights_split
     B, H, W, cin, cout, k, stride, leaky, use_res = case
     L = omlib.load()
-    g = torch.Generator().manual_seed(sum(case))
-    x = torch.randn(B, cin, H, W, generator=g)
-    w = torch.randn(cout, cin, k, k, generator=g) / (cin * k * k) ** 0.5
-    scale = torch.rand(cout, generator=g) + 0.5
-    shift = torch.randn(cout, generator=g) * 0.2
-    Ho, Wo = H // stride, W // stride
-    res = torch.randn(B, cout, Ho, Wo, generator=g) if use_res else None
-    want = torch.nn.functional.conv2d(x.double(), w.double(), None, stride, k // 2)
-    want = want * scale.double().view(1, -1, 1, 1) + shift.double().view(1, -1, 1, 1)
-    if leaky:
-        want = torch.where(want > 0, want, want * 0.1)
-    if use_res:
-        want = want + res.double()
+    c = LayerCase(sum(case), case)
+    want, Ho, Wo = c.want, c.Ho, c.Wo
     cpad = (cout + 31) // 32 * 32
-    ws, e = conv_weights_split(w, cpad)
-    sp = torch.zeros(cpad); sp[:cout] = scale
-    sp = (sp.double() * torch.pow(torch.tensor(2.0, dtype=torch.float64), -e.double())).float()
-    hp = torch.zeros(cpad); hp[:cout] = shift
-    xd = x.permute(0, 2, 3, 1).contiguous().to(dev)
+    ws, e = conv_weights_split(c.w, cpad)
+    sp, hp = c.padded(cpad, e)
+    xd, rd = c.nhwc(c.x, dev), c.nhwc(c.res, dev)
     wd, sd_, hd = ws.to(dev), sp.to(dev), hp.to(dev)
-    rd = res.permute(0, 2, 3, 1).contiguous().to(dev) if use_res else None
     out = torch.full((B, Ho, Wo, cout), float("nan"), device=dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     rc = L.om_conv2d_split(_p(xd), B, H, W, cin, cin, _p(wd), _p(sd_), _p(hd), cout, k, stride, leaky,
@@ -344,27 +311,13 @@ def test_conv_split_k_parts(dev, case):
     from orienmask_amd.pack import conv_weights_split
     B, H, W, cin, cout, k, stride, leaky, use_res, out_mode, (bm, bn), parts = case
     L = omlib.load()
-    g = torch.Generator().manual_seed(B + H + W + cin + cout + k + parts)
-    x = torch.randn(B, cin, H, W, generator=g)
-    w = torch.randn(cout, cin, k, k, generator=g) / (cin * k * k) ** 0.5
-    scale = torch.rand(cout, generator=g) + 0.5
-    shift = torch.randn(cout, generator=g) * 0.2
-    Ho, Wo = H // stride, W // stride
-    res = torch.randn(B, cout, Ho, Wo, generator=g) if use_res else None
-    want = torch.nn.functional.conv2d(x.double(), w.double(), None, stride, k // 2)
-    want = want * scale.double().view(1, -1, 1, 1) + shift.double().view(1, -1, 1, 1)
-    if leaky:
-        want = torch.where(want > 0, want, want * 0.1)
-    if use_res:
-        want = want + res.double()
+    c = LayerCase(B + H + W + cin + cout + k + parts, case[:9])
+    want, Ho, Wo = c.want, c.Ho, c.Wo
     cpad = (cout + 31) // 32 * 32
-    ws, e = conv_weights_split(w, cpad)
-    sp = torch.zeros(cpad); sp[:cout] = scale
-    sp = (sp.double() * torch.pow(torch.tensor(2.0, dtype=torch.float64), -e.double())).float()
-    hp = torch.zeros(cpad); hp[:cout] = shift
-    xd = x.permute(0, 2, 3, 1).contiguous().to(dev)
+    ws, e = conv_weights_split(c.w, cpad)
+    sp, hp = c.padded(cpad, e)
+    xd, rd = c.nhwc(c.x, dev), c.nhwc(c.res, dev)
     wd, sd_, hd = ws.to(dev), sp.to(dev), hp.to(dev)
-    rd = res.permute(0, 2, 3, 1).contiguous().to(dev) if use_res else None
     status = torch.zeros(1, dtype=torch.int32, device=dev)
 
     def run(max_parts):
@@ -391,15 +344,9 @@ def test_conv_split_k_parts(dev, case):
     # other data through the same partial-tile area: nothing of the previous launch's parts may be read (a stale line in this
     # XCD's L2 or this CU's L1 would be exactly that)
     for rep in range(3):
-        x2 = torch.randn(B, cin, H, W, generator=g)
-        want2 = torch.nn.functional.conv2d(x2.double(), w.double(), None, stride, k // 2)
-        want2 = want2 * scale.double().view(1, -1, 1, 1) + shift.double().view(1, -1, 1, 1)
-        if leaky:
-            want2 = torch.where(want2 > 0, want2, want2 * 0.1)
-        if use_res:
-            want2 = want2 + res.double()
+        x2 = torch.randn(B, cin, H, W, generator=c.g)
         xd.copy_(x2.permute(0, 2, 3, 1))
-        assert _rel_err(run(parts).double(), want2) < 2e-6, (case, rep)
+        assert _rel_err(run(parts).double(), c.expected(x2)) < 2e-6, (case, rep)
 
 
 @pytest.mark.parametrize("case", [(8, 68, 68, 256, 128, 1, 1), (4, 68, 68, 128, 256, 3, 2), (2, 34, 34, 96, 128, 3, 2)])
@@ -509,22 +456,14 @@ def test_conv_split_output_modes(dev, mode):
     NCHW orientation head (18 channels, no activation)."""
     from orienmask_amd.pack import conv_weights_split
     L = omlib.load()
-    g = torch.Generator().manual_seed(77)
     B, H, W = 2, 6, 5
     cin, cout, up, leaky = (256, 64, 4, 1) if mode == "upsample" else (256, 18, 1, 0)
-    x = torch.randn(B, cin, H, W, generator=g)
-    w = torch.randn(cout, cin, 1, 1, generator=g) / cin ** 0.5
-    scale = torch.rand(cout, generator=g) + 0.5
-    shift = torch.randn(cout, generator=g) * 0.2
-    want = torch.nn.functional.conv2d(x.double(), w.double()) * scale.double().view(1, -1, 1, 1) + shift.double().view(1, -1, 1, 1)
-    if leaky:
-        want = torch.where(want > 0, want, want * 0.1)
+    c = LayerCase(77, (B, H, W, cin, cout, 1, 1, leaky, False))
+    want = c.want
     cpad = (cout + 31) // 32 * 32
-    ws, e = conv_weights_split(w, cpad)
-    sp = torch.zeros(cpad); sp[:cout] = scale
-    sp = (sp.double() * torch.pow(torch.tensor(2.0, dtype=torch.float64), -e.double())).float()
-    hp = torch.zeros(cpad); hp[:cout] = shift
-    xd = x.permute(0, 2, 3, 1).contiguous().to(dev)
+    ws, e = conv_weights_split(c.w, cpad)
+    sp, hp = c.padded(cpad, e)
+    xd = c.nhwc(c.x, dev)
     wd, sd_, hd = ws.to(dev), sp.to(dev), hp.to(dev)
     if mode == "upsample":
         want = torch.nn.functional.interpolate(want, scale_factor=float(up), mode="nearest")
@@ -562,25 +501,13 @@ def test_winograd_layer_matches_torch(dev, case):
     from orienmask_amd.pack import winograd_weights
     B, H, W, cin, cout, leaky, use_res = case
     L = omlib.load()
-    g = torch.Generator().manual_seed(sum(case) + 7)
-    x = torch.randn(B, cin, H, W, generator=g)
-    w = torch.randn(cout, cin, 3, 3, generator=g) / (cin * 9) ** 0.5
-    scale = torch.rand(cout, generator=g) + 0.5
-    shift = torch.randn(cout, generator=g) * 0.2
-    res = torch.randn(B, cout, H, W, generator=g) if use_res else None
-    want = torch.nn.functional.conv2d(x.double(), w.double(), None, 1, 1)
-    want = want * scale.double().view(1, -1, 1, 1) + shift.double().view(1, -1, 1, 1)
-    if leaky:
-        want = torch.where(want > 0, want, want * 0.1)
-    if use_res:
-        want = want + res.double()
+    c = LayerCase(sum(case) + 7, (B, H, W, cin, cout, 3, 1, leaky, use_res))
+    want = c.want
     cpad = (cout + 63) // 64 * 64
-    ud = winograd_weights(w, cpad).contiguous().to(dev)
-    sp = torch.zeros(cpad); sp[:cout] = scale
-    hp = torch.zeros(cpad); hp[:cout] = shift
-    xd = x.permute(0, 2, 3, 1).contiguous().to(dev)
+    ud = winograd_weights(c.w, cpad).contiguous().to(dev)
+    sp, hp = c.padded(cpad)
+    xd, rd = c.nhwc(c.x, dev), c.nhwc(c.res, dev)
     sd_, hd = sp.to(dev), hp.to(dev)
-    rd = res.permute(0, 2, 3, 1).contiguous().to(dev) if use_res else None
     out = torch.full((B, H, W, cout), float("nan"), device=dev)
     scratch = torch.empty(L.om_conv2d_winograd_scratch_bytes(B, H, W, cin), dtype=torch.uint8, device=dev)
     rc = L.om_conv2d_winograd(_p(xd), B, H, W, cin, cin, _p(ud), _p(sd_), _p(hd), cout, leaky,
@@ -606,25 +533,13 @@ def test_winograd24_layer_matches_torch(dev, case):
     from orienmask_amd.pack import winograd_weights
     B, H, W, cin, cout, leaky, use_res = case
     L = omlib.load()
-    g = torch.Generator().manual_seed(sum(case) + 17)
-    x = torch.randn(B, cin, H, W, generator=g)
-    w = torch.randn(cout, cin, 3, 3, generator=g) / (cin * 9) ** 0.5
-    scale = torch.rand(cout, generator=g) + 0.5
-    shift = torch.randn(cout, generator=g) * 0.2
-    res = torch.randn(B, cout, H, W, generator=g) if use_res else None
-    want = torch.nn.functional.conv2d(x.double(), w.double(), None, 1, 1)
-    want = want * scale.double().view(1, -1, 1, 1) + shift.double().view(1, -1, 1, 1)
-    if leaky:
-        want = torch.where(want > 0, want, want * 0.1)
-    if use_res:
-        want = want + res.double()
+    c = LayerCase(sum(case) + 17, (B, H, W, cin, cout, 3, 1, leaky, use_res))
+    want = c.want
     cpad = (cout + 63) // 64 * 64
-    ud = winograd_weights(w, cpad, 24).contiguous().to(dev)
-    sp = torch.zeros(cpad); sp[:cout] = scale
-    hp = torch.zeros(cpad); hp[:cout] = shift
-    xd = x.permute(0, 2, 3, 1).contiguous().to(dev)
+    ud = winograd_weights(c.w, cpad, 24).contiguous().to(dev)
+    sp, hp = c.padded(cpad)
+    xd, rd = c.nhwc(c.x, dev), c.nhwc(c.res, dev)
     sd_, hd = sp.to(dev), hp.to(dev)
-    rd = res.permute(0, 2, 3, 1).contiguous().to(dev) if use_res else None
     out = torch.full((B, H, W, cout), float("nan"), device=dev)
     scratch = torch.empty(L.om_conv2d_winograd24_scratch_bytes(B, H, W, cin), dtype=torch.uint8, device=dev)
     rc = L.om_conv2d_winograd24(_p(xd), B, H, W, cin, cin, _p(ud), _p(sd_), _p(hd), cout, leaky,
@@ -644,25 +559,12 @@ def test_winograd24_split_layer_matches_torch(dev, case):
     from orienmask_amd.pack import winograd_weights, winograd_weights_split
     B, H, W, cin, cout, leaky, use_res = case
     L = omlib.load()
-    g = torch.Generator().manual_seed(sum(case) + 17)
-    x = torch.randn(B, cin, H, W, generator=g)
-    w = torch.randn(cout, cin, 3, 3, generator=g) / (cin * 9) ** 0.5
-    scale = torch.rand(cout, generator=g) + 0.5
-    shift = torch.randn(cout, generator=g) * 0.2
-    res = torch.randn(B, cout, H, W, generator=g) if use_res else None
-    want = torch.nn.functional.conv2d(x.double(), w.double(), None, 1, 1)
-    want = want * scale.double().view(1, -1, 1, 1) + shift.double().view(1, -1, 1, 1)
-    if leaky:
-        want = torch.where(want > 0, want, want * 0.1)
-    if use_res:
-        want = want + res.double()
+    c = LayerCase(sum(case) + 17, (B, H, W, cin, cout, 3, 1, leaky, use_res))
+    want, w = c.want, c.w
     cpad = (cout + 63) // 64 * 64
-    sp = torch.zeros(cpad); sp[:cout] = scale
-    hp = torch.zeros(cpad); hp[:cout] = shift
     us, e = winograd_weights_split(w, cpad)
-    sps = (sp.double() * torch.pow(torch.tensor(2.0, dtype=torch.float64), -e.double())).float()
-    xd = x.permute(0, 2, 3, 1).contiguous().to(dev)
-    rd = res.permute(0, 2, 3, 1).contiguous().to(dev) if use_res else None
+    (sp, hp), sps = c.padded(cpad), c.padded(cpad, e)[0]
+    xd, rd = c.nhwc(c.x, dev), c.nhwc(c.res, dev)
     scratch = torch.empty(L.om_conv2d_winograd24_scratch_bytes(B, H, W, cin), dtype=torch.uint8, device=dev)
     errs = {}
     for mode in ("f32", "split"):
@@ -703,29 +605,16 @@ def test_wino14_split_layer_matches_torch(dev, case):
     from orienmask_amd.pack import winograd14_weights_split
     B, H, W, cin, cout, leaky, use_res = case
     L = omlib.load()
-    g = torch.Generator().manual_seed(sum(case) + 23)
-    x = torch.randn(B, cin, H, W, generator=g)
-    w = torch.randn(cout, cin, 3, 3, generator=g) / (cin * 9) ** 0.5
-    scale = torch.rand(cout, generator=g) + 0.5
-    shift = torch.randn(cout, generator=g) * 0.2
-    res = torch.randn(B, cout, H, W, generator=g) if use_res else None
-    want = torch.nn.functional.conv2d(x.double(), w.double(), None, 1, 1)
-    want = want * scale.double().view(1, -1, 1, 1) + shift.double().view(1, -1, 1, 1)
-    if leaky:
-        want = torch.where(want > 0, want, want * 0.1)
-    if use_res:
-        want = want + res.double()
+    c = LayerCase(sum(case) + 23, (B, H, W, cin, cout, 3, 1, leaky, use_res))
+    want = c.want
     cpad = (cout + 63) // 64 * 64
-    us, e = winograd14_weights_split(w, cpad)
-    sp = torch.zeros(cpad); sp[:cout] = scale
-    sps = (sp.double() * torch.pow(torch.tensor(2.0, dtype=torch.float64), -e.double())).float().to(dev)
-    hp = torch.zeros(cpad); hp[:cout] = shift
-    hd = hp.to(dev)
+    us, e = winograd14_weights_split(c.w, cpad)
+    sps, hd = (t.to(dev) for t in c.padded(cpad, e))
     # the input as a channel slice of a wider buffer (concat views), the output with a pixel stride of its own
     xbuf = torch.full((B, H, W, cin + 16), 9.0, device=dev)
-    xbuf[..., 8:8 + cin] = x.permute(0, 2, 3, 1).to(dev)
+    xbuf[..., 8:8 + cin] = c.x.permute(0, 2, 3, 1).to(dev)
     xv = xbuf[..., 8:]
-    rd = res.permute(0, 2, 3, 1).contiguous().to(dev) if use_res else None
+    rd = c.nhwc(c.res, dev)
     ostride = cout + (4 - cout % 4) % 4 + 4
     out = torch.full((B, H, W, ostride), float("nan"), device=dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -1108,9 +997,6 @@ def test_forward_matches_reference_golden(dev, fname, precision):
     torch.cuda.synchronize()
     assert out.flags() == 0, "a fixture must not need the fp32-operand fallback (it would test nothing of the split kernels)"
     _check_forward_fixture(out, g, fname, precision, dev, size, batch)
-
-
-_ORACLE_CACHE = {}
 
 
 def _oracle_once(key, fn):
@@ -1883,26 +1769,13 @@ def test_conv_f16_layer_matches_torch(dev, case, variant):
     L = omlib.load()
     previous = L.om_get_conv3x3_f16_variant()       # OM_C3_TALL of the environment, or the default: restored below
     omlib.check(L.om_set_conv3x3_f16_variant(variant), "om_set_conv3x3_f16_variant")
-    g = torch.Generator().manual_seed(sum(case) + 11)
-    x = torch.randn(B, cin, H, W, generator=g).half()
-    w = (torch.randn(cout, cin, k, k, generator=g) / (cin * k * k) ** 0.5).half()
-    scale = torch.rand(cout, generator=g) + 0.5
-    shift = torch.randn(cout, generator=g) * 0.2
-    Ho, Wo = H // stride, W // stride
-    res = torch.randn(B, cout, Ho, Wo, generator=g).half() if use_res else None
-    want = torch.nn.functional.conv2d(x.double(), w.double(), None, stride, k // 2)
-    want = want * scale.double().view(1, -1, 1, 1) + shift.double().view(1, -1, 1, 1)
-    if leaky:
-        want = torch.where(want > 0, want, want * 0.1)
-    if use_res:
-        want = want + res.double()
+    c = LayerCase(sum(case) + 11, case[:9], half=True)
+    want, Ho, Wo = c.want, c.Ho, c.Wo
     cpad = (cout + 31) // 32 * 32
-    wd = conv_weights_f16(w.float(), cpad).contiguous().to(dev)
-    sp = torch.zeros(cpad); sp[:cout] = scale
-    hp = torch.zeros(cpad); hp[:cout] = shift
-    xd = x.permute(0, 2, 3, 1).contiguous().to(dev)
+    wd = conv_weights_f16(c.w.float(), cpad).contiguous().to(dev)
+    sp, hp = c.padded(cpad)
+    xd, rd = c.nhwc(c.x, dev), c.nhwc(c.res, dev)
     sd_, hd = sp.to(dev), hp.to(dev)
-    rd = res.permute(0, 2, 3, 1).contiguous().to(dev) if use_res else None
     ostride = 256 if out_f32 else cout
     out = torch.full((B, Ho, Wo, ostride), float("nan"), device=dev, dtype=torch.float32 if out_f32 else torch.float16)
     try:
