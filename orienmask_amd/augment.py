@@ -506,7 +506,7 @@ def to_device(planned, device):
     planned.pin_memory()
     B, N = planned.B, planned.N
     H, W = planned.out_hw
-    with torch.cuda.device(device):
+    with _lib.on_device(device):
         meta = planned.meta.to(device, non_blocking=True)
         image = planned.image.to(device, non_blocking=True)
         masks = planned.mask.to(device, non_blocking=True)
@@ -515,21 +515,15 @@ def to_device(planned, device):
         out_image = torch.empty((B, 3, H, W), dtype=torch.float32, device=device)
         out_mask = torch.empty((N, H, W), dtype=torch.bool, device=device)
         ws = None
-        L = _lib.load()
         if planned.any_contrast:
-            ws = torch.empty(L.om_augment_workspace_bytes(B), dtype=torch.uint8, device=device)
+            ws = torch.empty(_lib.load().om_augment_workspace_bytes(B), dtype=torch.uint8, device=device)
         samples = meta[planned.layout["samples"][0]:]
         gt = meta[planned.layout["gt"][0]:]
         mean = (ctypes.c_float * 3)(*planned.mean)
         std = (ctypes.c_float * 3)(*planned.std)
-        rc = L.om_augment(ctypes.c_void_p(samples.data_ptr()), B, ctypes.c_void_p(image.data_ptr()),
-                          int(planned.image.dtype == torch.uint8), mean, std, H, W, ctypes.c_void_p(out_image.data_ptr()),
-                          ctypes.c_void_p(masks.data_ptr() if N and planned.has_mask else None),
-                          ctypes.c_void_p(gt.data_ptr()), N if planned.has_mask else 0,
-                          ctypes.c_void_p(out_mask.data_ptr() if N and planned.has_mask else None), int(planned.any_contrast),
-                          ctypes.c_void_p(ws.data_ptr() if ws is not None else None), ws.numel() if ws is not None else 0,
-                          _lib.current_stream_ptr(device))
-        _lib.check(rc, "om_augment")
+        _lib.launch("om_augment", device, samples, B, image, int(planned.image.dtype == torch.uint8), mean, std, H, W, out_image,
+                    masks if N and planned.has_mask else None, gt, N if planned.has_mask else 0,
+                    out_mask if N and planned.has_mask else None, int(planned.any_contrast), ws, ws.numel() if ws is not None else 0)
     bbox = _meta_view(meta, planned.layout, "bbox", torch.float32, (N, 4))
     cls = _meta_view(meta, planned.layout, "cls", torch.int64, (N,))
     index = _meta_view(meta, planned.layout, "index", torch.int64, (B + 1,))
@@ -541,23 +535,20 @@ def to_device(planned, device):
 
 def _segm_decode(planned, device):
     """the packed masks of a 'segm' batch, decoded on the current stream into a fresh scratch"""
-    L = _lib.load()
     c = planned.segm_counts
     tables = planned.segm.to(device, non_blocking=True)
     scratch = torch.empty(c["mask_bytes"], dtype=torch.uint8, device=device)
-    ws_bytes = int(L.om_segm_decode_workspace_bytes(c["bitmap_words"], planned.N))
+    ws_bytes = int(_lib.load().om_segm_decode_workspace_bytes(c["bitmap_words"], planned.N))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
 
-    def ptr(name):
+    def at(name):
+        """the address of table `name` inside `tables`, null for an empty one"""
         off, nbytes = planned.segm_layout[name]
-        return ctypes.c_void_p(tables.data_ptr() + off) if nbytes else None
+        return tables.data_ptr() + off if nbytes else None
 
-    rc = L.om_segm_decode(planned.N, ptr("mask_hw"), ptr("mask_src_first"), ptr("mask_src_word_off"), ptr("mask_out_off"),
-                          c["n_poly"], c["n_srcs"], ptr("src_kind"), ptr("src_mask"), ptr("src_data_off"), ptr("src_len"),
-                          ptr("src_word_off"), ptr("poly"), ptr("counts"), ptr("strings"), c["bitmap_words"],
-                          ctypes.c_void_p(ws.data_ptr() if ws_bytes else None), ws_bytes, ctypes.c_void_p(scratch.data_ptr()),
-                          _lib.current_stream_ptr(device))
-    _lib.check(rc, "om_segm_decode")
+    _lib.launch("om_segm_decode", device, planned.N, at("mask_hw"), at("mask_src_first"), at("mask_src_word_off"), at("mask_out_off"),
+                c["n_poly"], c["n_srcs"], at("src_kind"), at("src_mask"), at("src_data_off"), at("src_len"), at("src_word_off"),
+                at("poly"), at("counts"), at("strings"), c["bitmap_words"], ws if ws_bytes else None, ws_bytes, scratch)
     return scratch
 
 

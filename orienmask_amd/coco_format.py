@@ -71,12 +71,8 @@ def recover_shape_bbox(bbox, sample_info):
     pd = sample_info.get("pad")
     cp_arr = (ctypes.c_int32 * 6)(*[int(v) for v in cp]) if cp is not None else None
     pd_arr = (ctypes.c_int32 * 6)(*[int(v) for v in pd]) if pd is not None else None
-    with torch.cuda.device(b.device):
-        rc = _lib.load().om_recover_bbox(ctypes.c_void_p(b.data_ptr()), K, b.shape[1], cp_arr, pd_arr,
-                                         int(bool(sample_info.get("hflip", False))), int(bool(sample_info.get("vflip", False))),
-                                         int(sample_info["height"]), int(sample_info["width"]),
-                                         ctypes.c_void_p(out.data_ptr()), _lib.current_stream_ptr(b.device))
-    _lib.check(rc, "om_recover_bbox")
+    _lib.launch("om_recover_bbox", b.device, b, K, b.shape[1], cp_arr, pd_arr, int(bool(sample_info.get("hflip", False))),
+                int(bool(sample_info.get("vflip", False))), int(sample_info["height"]), int(sample_info["width"]), out)
     return out
 
 
@@ -93,18 +89,11 @@ def recover_masks_rle(mask, sample_info, max_runs=None, return_resized=False):
     top, down, left, right = _crop_of(sample_info)
     full = oh * ow + 1
     max_runs = min(full, max_runs or 16384)
-    L = _lib.load()
     while True:
         counts = torch.empty((K, max_runs), dtype=torch.int32, device=mask.device)
         n_runs = torch.empty((K,), dtype=torch.int32, device=mask.device)
-        with torch.cuda.device(mask.device):
-            rc = L.om_recover_masks_rle(ctypes.c_void_p(m.data_ptr()), K, H, W, top, down, left, right,
-                                        int(bool(sample_info.get("hflip", False))), int(bool(sample_info.get("vflip", False))),
-                                        oh, ow, ctypes.c_void_p(counts.data_ptr()), max_runs,
-                                        ctypes.c_void_p(n_runs.data_ptr()),
-                                        ctypes.c_void_p(resized.data_ptr()) if return_resized else None,
-                                        _lib.current_stream_ptr(mask.device))
-        _lib.check(rc, "om_recover_masks_rle")
+        _lib.launch("om_recover_masks_rle", mask.device, m, K, H, W, top, down, left, right, int(bool(sample_info.get("hflip", False))),
+                    int(bool(sample_info.get("vflip", False))), oh, ow, counts, max_runs, n_runs, resized if return_resized else None)
         n = n_runs.cpu().tolist()
         if max(n) <= max_runs or max_runs >= full:
             break
@@ -151,7 +140,6 @@ class COCOFormatter:
 
     @staticmethod
     def _worst_case_chunk(items):
-        L = _lib.load()
         dev = items[0][0].device
         n = len(items)
         full = max(int(i["height"]) * int(i["width"]) for _, i in items) + 1
@@ -161,11 +149,8 @@ class COCOFormatter:
         sbytes = torch.empty(cap, dtype=torch.uint8, device=dev)
         masks = [m.contiguous().view(torch.uint8) for m, _ in items]
         imgs = (_lib.RleImage * n)(*[_rle_image(m, i) for m, (_, i) in zip(masks, items)])
-        with torch.cuda.device(dev):
-            _lib.check(L.om_recover_masks_rle_strings(
-                imgs, n, ctypes.c_void_p(counts.data_ptr()), full, ctypes.c_void_p(hdr.data_ptr() + (2 + 2 * n) * 4),
-                ctypes.c_void_p(sbytes.data_ptr()), cap, ctypes.c_void_p(hdr.data_ptr()), ctypes.c_void_p(hdr.data_ptr() + 8),
-                ctypes.c_void_p(hdr.data_ptr() + (2 + n) * 4), _lib.current_stream_ptr(dev)), "om_recover_masks_rle_strings")
+        _lib.launch("om_recover_masks_rle_strings", dev, imgs, n, counts, full, hdr.data_ptr() + (2 + 2 * n) * 4, sbytes, cap, hdr,
+                    hdr.data_ptr() + 8, hdr.data_ptr() + (2 + n) * 4)
         h = hdr.cpu().tolist()
         if h[1] or any(o < 0 for o in h[2:2 + n]):
             raise _lib.OrienMaskHipError("RLE strings of %d masks do not fit %d bytes" % (n, cap))
@@ -183,7 +168,6 @@ class COCOFormatter:
             return out
         dev = pairs[0][1]["bbox"].device
         _lib.require_cuda_tensor(pairs[0][1]["bbox"], "bbox", torch.float32)
-        L = _lib.load()
         Ks = [int(det["bbox"].shape[0]) for _, det in pairs]
         N = sum(Ks)
         starts = [0]
@@ -191,16 +175,15 @@ class COCOFormatter:
             starts.append(starts[-1] + k)
         xywh = torch.empty((N, 4), dtype=torch.float32, device=dev)
         st = _lib.current_stream_ptr(dev)
-        with torch.cuda.device(dev):
+        with _lib.on_device(dev):
             for (info, det), s0, K in zip(pairs, starts, Ks):
                 b = det["bbox"].contiguous()
                 cp, pd = info.get("collate_pad"), info.get("pad")
                 cp_arr = (ctypes.c_int32 * 6)(*[int(v) for v in cp]) if cp is not None else None
                 pd_arr = (ctypes.c_int32 * 6)(*[int(v) for v in pd]) if pd is not None else None
-                _lib.check(L.om_recover_bbox(ctypes.c_void_p(b.data_ptr()), K, b.shape[1], cp_arr, pd_arr,
-                                             int(bool(info.get("hflip", False))), int(bool(info.get("vflip", False))),
-                                             int(info["height"]), int(info["width"]),
-                                             ctypes.c_void_p(xywh.data_ptr() + s0 * 16), st), "om_recover_bbox")
+                _lib.launch("om_recover_bbox", dev, b, K, b.shape[1], cp_arr, pd_arr, int(bool(info.get("hflip", False))),
+                            int(bool(info.get("vflip", False))), int(info["height"]), int(info["width"]), xywh.data_ptr() + s0 * 16,
+                            stream=st)
             if self.with_mask:
                 cap = N * self.BYTES_PER_MASK
                 hdr = self._buffer(dev, "hdr", 2 + 3 * N, torch.int32)        # cursor, overflow | off[N] | len[N] | n_runs[N]
@@ -213,10 +196,8 @@ class COCOFormatter:
                     _lib.require_cuda_tensor(det["mask"], "mask")
                     masks.append(det["mask"].contiguous().view(torch.uint8))
                     imgs[i] = _rle_image(masks[-1], info)
-                _lib.check(L.om_recover_masks_rle_strings(
-                    imgs, len(pairs), ctypes.c_void_p(counts.data_ptr()), self.MAX_RUNS, ctypes.c_void_p(hdr.data_ptr() + (2 + 2 * N) * 4),
-                    ctypes.c_void_p(sbytes.data_ptr()), cap, ctypes.c_void_p(hdr.data_ptr()), ctypes.c_void_p(hdr.data_ptr() + 8),
-                    ctypes.c_void_p(hdr.data_ptr() + (2 + N) * 4), st), "om_recover_masks_rle_strings")
+                _lib.launch("om_recover_masks_rle_strings", dev, imgs, len(pairs), counts, self.MAX_RUNS, hdr.data_ptr() + (2 + 2 * N) * 4,
+                            sbytes, cap, hdr, hdr.data_ptr() + 8, hdr.data_ptr() + (2 + N) * 4, stream=st)
         # ---- the batch's host reads
         meta = torch.cat([xywh, torch.cat([det["bbox"][:, -1:] for _, det in pairs]),
                           torch.cat([det["cls"].reshape(-1, 1).to(torch.float32) for _, det in pairs])], dim=1).cpu()

@@ -21,7 +21,6 @@ Kept pycocotools behaviours: a GT segmentation that is a list whose first entry 
 (``frPyObjects``); GT ``ignore`` is ``iscrowd`` whatever the json says; a det's area is ``w * h`` when the first result has
 a ``bbox`` and the mask area otherwise (``loadRes``); "matched" means "GT id != 0", so a GT with id 0 counts as unmatched.
 """
-import ctypes
 import itertools
 import json
 import os
@@ -222,11 +221,11 @@ class COCOEvaluator:
         pairs = np.concatenate(pairs).astype(np.int32) if pairs else np.zeros((0, 2), np.int32)
         crowd = np.concatenate(crowd) if crowd else np.zeros(0, np.uint8)
         tt = lambda a, dtype=None: torch.from_numpy(np.ascontiguousarray(a if dtype is None else a.astype(dtype))).to(dev)
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+        ptr = _or_null
         ious = torch.zeros(max(n_pairs, 1), dtype=torch.float64, device=dev)
         d_pairs, d_crowd = tt(pairs), tt(crowd)
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-        with torch.cuda.device(dev):
+        with _lib.on_device(dev):
             ev[0].record()
             if self.iou_type == "segm":
                 mask_stats = self._build_masks(L, gts + dts, st)     # gts are masks [0, ng), dets [ng, ng + nd)
@@ -235,9 +234,8 @@ class COCOEvaluator:
                     pr = pairs.copy()
                     pr[:, 0] += ng
                     pr_t = tt(pr)
-                    _lib.check(L.om_cocoeval_mask_iou(n_pairs, ptr(pr_t), ptr(d_crowd), ng + nd, ptr(self._m_hw),
-                                                      ptr(self._m_off), self._m_words, ptr(self._ws), ptr(ious), st),
-                               "om_cocoeval_mask_iou")
+                    _lib.launch("om_cocoeval_mask_iou", dev, n_pairs, ptr(pr_t), ptr(d_crowd), ng + nd, ptr(self._m_hw), ptr(self._m_off),
+                                self._m_words, self._ws.data_ptr(), ptr(ious), stream=st)
                 dt_area = mask_stats[ng:, 0].astype(np.float64) if not self._box_branch else \
                     np.array([float(d["area"]) for d in dts], dtype=np.float64)
             else:
@@ -245,8 +243,7 @@ class COCOEvaluator:
                 dbox = tt(np.array([[float(v) for v in d["bbox"]] for d in dts], dtype=np.float64).reshape(-1, 4))
                 gbox = tt(np.array([[float(v) for v in g["bbox"]] for g in gts], dtype=np.float64).reshape(-1, 4))
                 if n_pairs:
-                    _lib.check(L.om_cocoeval_bbox_iou(n_pairs, ptr(d_pairs), ptr(d_crowd), ptr(dbox), ptr(gbox), ptr(ious), st),
-                               "om_cocoeval_bbox_iou")
+                    _lib.launch("om_cocoeval_bbox_iou", dev, n_pairs, ptr(d_pairs), ptr(d_crowd), ptr(dbox), ptr(gbox), ptr(ious), stream=st)
                 dt_area = np.array([float(d["area"]) for d in dts], dtype=np.float64)
             ev[2].record()
             lanes = T * A
@@ -260,9 +257,8 @@ class COCOEvaluator:
             rng = tt(np.array(self.areaRng, dtype=np.float64))
             thr = tt(np.asarray(self.iouThrs, dtype=np.float64))
             d_dtf, d_gtf, d_off = tt(l_dt_first), tt(l_gt_first), tt(iou_off)
-            _lib.check(L.om_cocoeval_match(len(gidx), ptr(d_dtf), ptr(d_gtf), ptr(d_off), ptr(ious), ptr(d_area), ptr(g_area),
-                                           ptr(g_crowd), ptr(g_id), ptr(rng), ptr(thr), nd, ng, ptr(gtm), ptr(dtm), ptr(dti), st),
-                       "om_cocoeval_match")
+            _lib.launch("om_cocoeval_match", dev, len(gidx), ptr(d_dtf), ptr(d_gtf), ptr(d_off), ptr(ious), ptr(d_area), ptr(g_area),
+                        ptr(g_crowd), ptr(g_id), ptr(rng), ptr(thr), nd, ng, ptr(gtm), ptr(dtm), ptr(dti), stream=st)
             ev[3].record()
             h_dtm, h_dti = dtm.cpu().numpy(), dti.cpu().numpy().astype(bool)
             h_iou = ious.cpu().numpy()
@@ -327,7 +323,7 @@ class COCOEvaluator:
                 sdata.append(data); ns_off += len(data)
         merge_woff = swoff[order]
         tt = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+        ptr = _or_null
         d_hw, d_moff, d_sf = tt(hw), tt(m_off), tt(src_first)
         d_kind, d_smask, d_slen, d_sdoff, d_swoff = tt(kind), tt(smask), tt(slen), tt(sdoff), tt(swoff)
         d_merge = tt(merge_woff)
@@ -337,11 +333,10 @@ class COCOEvaluator:
         need = int(L.om_cocoeval_workspace_bytes(words, n))
         ws = torch.empty(need + 256, dtype=torch.uint8, device=dev)
         base = (ws.data_ptr() + 255) // 256 * 256
-        _lib.check(L.om_cocoeval_masks(n, ptr(d_hw), ptr(d_moff), ptr(d_sf), ptr(d_merge), n_poly, len(srcs_all), ptr(d_kind), ptr(d_smask),
-                                       ptr(d_sdoff), ptr(d_slen), ptr(d_swoff), ptr(d_poly), ptr(d_cnt), ptr(d_str), words,
-                                       ctypes.c_void_p(base), need, st), "om_cocoeval_masks")
+        _lib.launch("om_cocoeval_masks", dev, n, ptr(d_hw), ptr(d_moff), ptr(d_sf), ptr(d_merge), n_poly, len(srcs_all), ptr(d_kind),
+                    ptr(d_smask), ptr(d_sdoff), ptr(d_slen), ptr(d_swoff), ptr(d_poly), ptr(d_cnt), ptr(d_str), words, base, need, stream=st)
         stats = torch.empty((n, 3), dtype=torch.int32, device=dev)
-        _lib.check(L.om_cocoeval_mask_stats(n, words, ctypes.c_void_p(base), ptr(stats), st), "om_cocoeval_mask_stats")
+        _lib.launch("om_cocoeval_mask_stats", dev, n, words, base, ptr(stats), stream=st)
         self._ws_keep = ws
         self._ws = _Ptr(base)
         self._m_hw, self._m_off, self._m_words = d_hw, d_moff, words
@@ -375,7 +370,7 @@ class COCOEvaluator:
 
 
 class _Ptr:
-    """A raw device address handed to ctypes (the workspace is over-allocated and aligned to 256 bytes)."""
+    """A raw device address (the workspace is over-allocated and aligned to 256 bytes)."""
 
     def __init__(self, addr):
         self.addr = addr
@@ -385,6 +380,11 @@ class _Ptr:
 
     def numel(self):
         return 1
+
+
+def _or_null(t):
+    """The launch argument of a table that may be absent or empty: the tensor, or None (a null pointer) when it has no elements."""
+    return t if t is not None and t.numel() else None
 
 
 def accumulate_records(K, grp_cat, dt_cat, dt_rank, dt_score, dt_matched, dt_ignore, gt_cat, gt_ignore, iou_thrs, rec_thrs,

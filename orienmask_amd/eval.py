@@ -74,21 +74,16 @@ def _nms_keep(dets, threshold, backend=None):
     if dets.size(0) == 0:
         return dets.new_zeros(0, dtype=torch.long)
     _lib.require_cuda_tensor(dets, "dets")
-    L = _lib.load()
     d = dets.detach().to(torch.float32).contiguous()
     n = d.shape[0]
     dev = d.device
     keep = torch.empty(n, dtype=torch.long, device=dev)
     n_keep = torch.zeros(1, dtype=torch.int32, device=dev)
-    nbytes = L.om_nms_workspace_bytes(n)
+    nbytes = _lib.load().om_nms_workspace_bytes(n)
     if nbytes == 0:
         raise _lib.OrienMaskHipError("om_nms: %d boxes exceed the library's limit of 65536" % n)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.om_nms_ex(ctypes.c_void_p(d.data_ptr()), n, float(threshold), NMS_BACKENDS[backend],
-                         ctypes.c_void_p(keep.data_ptr()), ctypes.c_void_p(n_keep.data_ptr()), ctypes.c_void_p(ws.data_ptr()),
-                         ws.numel(), _lib.current_stream_ptr(dev))
-    _lib.check(rc, "om_nms_ex")
+    _lib.launch("om_nms_ex", dev, d, n, float(threshold), NMS_BACKENDS[backend], keep, n_keep, ws, ws.numel())
     return keep[:int(n_keep.item())]
 
 
@@ -227,7 +222,6 @@ class OrienMaskYOLOPostProcess:
         for p in predict:
             _lib.require_cuda_tensor(p[0], "bbox head", torch.float32)
             _lib.require_cuda_tensor(p[1], "orientation head", torch.float32)
-        L = _lib.load()
         bboxes, pix_stride = self._bbox_nhwc(predict)
         oriens = self._oriens_nchw(predict)
         B = bboxes[0].shape[0]
@@ -237,15 +231,7 @@ class OrienMaskYOLOPostProcess:
             return self._launch_foreign(predict, bboxes, oriens, cfg, B, dev)
         while len(bboxes) < 3:
             bboxes = bboxes + [bboxes[0]]        # unused scales: never read
-        key = (dev, B, pix_stride)
-        ws = self._ws.get(key)
-        if ws is None:
-            nbytes = L.om_postprocess_workspace_bytes(ctypes.byref(cfg), B)
-            if nbytes == 0:
-                _lib.check(-1, "om_postprocess_workspace_bytes")
-            self._ws.clear()
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            self._ws[key] = ws
+        ws = self._workspace(cfg, B, dev, pix_stride)
         out_bbox = torch.empty((B, self.nms_post, 5), dtype=torch.float32, device=dev)
         out_cls = torch.empty((B, self.nms_post), dtype=torch.long, device=dev)
         out_mask = torch.empty((B, self.nms_post, self.image_h, self.image_w), dtype=torch.uint8, device=dev)
@@ -257,14 +243,8 @@ class OrienMaskYOLOPostProcess:
         if n_status:
             out_count[B:].copy_(status)
         out_keep = torch.empty((B, self.nms_post), dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            rc = L.om_postprocess(ctypes.byref(cfg), ctypes.c_void_p(bboxes[0].data_ptr()),
-                                  ctypes.c_void_p(bboxes[1].data_ptr()), ctypes.c_void_p(bboxes[2].data_ptr()),
-                                  ctypes.c_void_p(oriens.data_ptr()), B, ctypes.c_void_p(out_bbox.data_ptr()),
-                                  ctypes.c_void_p(out_cls.data_ptr()), ctypes.c_void_p(out_mask.data_ptr()),
-                                  ctypes.c_void_p(out_count.data_ptr()), ctypes.c_void_p(out_keep.data_ptr()),
-                                  ctypes.c_void_p(ws.data_ptr()), ws.numel(), _lib.current_stream_ptr(dev))
-        _lib.check(rc, "om_postprocess")
+        _lib.launch("om_postprocess", dev, ctypes.byref(cfg), bboxes[0], bboxes[1], bboxes[2], oriens, B, out_bbox, out_cls, out_mask,
+                    out_count, out_keep, ws, ws.numel())
         return out_bbox, out_cls, out_mask, out_count, out_keep, (bboxes, oriens), predict     # keep the inputs alive
 
     def launch_step(self, model, image):
@@ -281,7 +261,6 @@ class OrienMaskYOLOPostProcess:
                  and (self.image_h, self.image_w) == tuple(image.shape[2:]))
         if not fused:
             return self.launch(model(image))
-        L = _lib.load()
         B, dev = image.shape[0], image.device
         cfg = self.cfg_struct(HEAD_PIX_STRIDE)
         ws = self._workspace(cfg, B, dev, HEAD_PIX_STRIDE)
@@ -292,15 +271,12 @@ class OrienMaskYOLOPostProcess:
         out_count = torch.empty((B + n_status,), dtype=torch.int32, device=dev)
         out_keep = torch.empty((B, self.nms_post), dtype=torch.int32, device=dev)
         h = model._ensure_handle()
-        with torch.cuda.device(dev):
-            _lib.check(L.om_model_attach_postprocess(h, ctypes.byref(cfg), ctypes.c_void_p(out_bbox.data_ptr()),
-                                                     ctypes.c_void_p(out_cls.data_ptr()), ctypes.c_void_p(out_mask.data_ptr()),
-                                                     ctypes.c_void_p(out_count.data_ptr()), ctypes.c_void_p(out_keep.data_ptr()),
-                                                     ctypes.c_void_p(ws.data_ptr()), ws.numel()), "om_model_attach_postprocess")
+        with _lib.on_device(dev):
+            _lib.call("om_model_attach_postprocess", h, ctypes.byref(cfg), out_bbox, out_cls, out_mask, out_count, out_keep, ws, ws.numel())
             try:
                 predict = model(image)
             finally:
-                _lib.check(L.om_model_attach_postprocess(h, None, None, None, None, None, None, None, 0), "om_model_attach_postprocess")
+                _lib.call("om_model_attach_postprocess", h, None, None, None, None, None, None, None, 0)
         status = getattr(predict, "status", None)
         if status is None or int(status.numel()) != n_status:
             raise _lib.OrienMaskHipError("launch_step: the forward returned %s status words" % (None if status is None else status.numel()))
@@ -309,13 +285,10 @@ class OrienMaskYOLOPostProcess:
         return out_bbox, out_cls, out_mask, out_count, out_keep, (bboxes, self._oriens_nchw(predict)), predict
 
     def _workspace(self, cfg, B, dev, pix_stride):
-        L = _lib.load()
         key = (dev, B, pix_stride)
         ws = self._ws.get(key)
         if ws is None:
-            nbytes = L.om_postprocess_workspace_bytes(ctypes.byref(cfg), B)
-            if nbytes == 0:
-                _lib.check(-1, "om_postprocess_workspace_bytes")
+            nbytes = _lib.workspace_bytes("om_postprocess_workspace_bytes", ctypes.byref(cfg), B)
             self._ws.clear()
             ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             self._ws[key] = ws
@@ -325,19 +298,15 @@ class OrienMaskYOLOPostProcess:
         """A caller-supplied nms_func (postprocess.py:9-11,146-154): candidates on the device (om_postprocess_candidates), the
         callable per image on device tensors -- this step reads the candidate counts, so it synchronises, like the reference's
         own per-image loop -- then the survivors' masks on the device (om_postprocess_masks).  Returns the same tuple as launch."""
-        L = _lib.load()
         st = _lib.current_stream_ptr(dev)
         ws = self._workspace(cfg, B, dev, cfg.bbox_pix_stride)
-        heads = [ctypes.c_void_p(t.data_ptr()) for t in bboxes] + [None] * (3 - len(bboxes))
+        heads = list(bboxes) + [None] * (3 - len(bboxes))
         cd = torch.empty((B, self.nms_pre, 5), dtype=torch.float32, device=dev)
         cc = torch.empty((B, self.nms_pre), dtype=torch.long, device=dev)
         cf = torch.empty((B, self.nms_pre), dtype=torch.int32, device=dev)
         cn = torch.empty((B,), dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(L.om_postprocess_candidates(ctypes.byref(cfg), heads[0], heads[1], heads[2], B, ctypes.c_void_p(cd.data_ptr()),
-                                                   ctypes.c_void_p(cc.data_ptr()), ctypes.c_void_p(cf.data_ptr()),
-                                                   ctypes.c_void_p(cn.data_ptr()), ctypes.c_void_p(ws.data_ptr()), ws.numel(), st),
-                       "om_postprocess_candidates")
+        _lib.launch("om_postprocess_candidates", dev, ctypes.byref(cfg), heads[0], heads[1], heads[2], B, cd, cc, cf, cn, ws, ws.numel(),
+                    stream=st)
         out_bbox = torch.zeros((B, self.nms_post, 5), dtype=torch.float32, device=dev)
         out_cls = torch.zeros((B, self.nms_post), dtype=torch.long, device=dev)
         out_field = torch.zeros((B, self.nms_post), dtype=torch.int32, device=dev)
@@ -364,11 +333,8 @@ class OrienMaskYOLOPostProcess:
         if n_status:
             out_count[B:].copy_(status)
         out_mask = torch.empty((B, self.nms_post, self.image_h, self.image_w), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(L.om_postprocess_masks(ctypes.byref(cfg), ctypes.c_void_p(oriens.data_ptr()), B, ctypes.c_void_p(out_bbox.data_ptr()),
-                                              ctypes.c_void_p(out_field.data_ptr()), ctypes.c_void_p(out_count.data_ptr()),
-                                              ctypes.c_void_p(out_mask.data_ptr()), ctypes.c_void_p(ws.data_ptr()), ws.numel(), st),
-                       "om_postprocess_masks")
+        _lib.launch("om_postprocess_masks", dev, ctypes.byref(cfg), oriens, B, out_bbox, out_field, out_count, out_mask, ws, ws.numel(),
+                    stream=st)
         return out_bbox, out_cls, out_mask, out_count, out_keep, (bboxes, oriens, out_field), predict
 
     def collect(self, outs):

@@ -3,8 +3,11 @@
 The HIP library IS the product: there is no CPU or eager-PyTorch fallback.  If the shared
 object is missing or does not export a declared symbol, loading raises immediately.
 """
+import contextlib
 import ctypes
 import os
+
+import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "liborienmask_hip.so")
@@ -243,10 +246,9 @@ def load():
         raise OrienMaskHipError(
             "%s not found: the HIP extension is not built (run `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C orienmask_amd/csrc`). There is no CPU fallback." % LIB_PATH)
-    # torch first: its wheel bundles a HIP runtime, and the process must end up with ONE runtime -- the one whose streams and device
+    # torch first (this module's own import): its wheel bundles a HIP runtime, and the process must end up with ONE runtime -- the one whose streams and device
     # pointers the callers hand to this library.  Loaded the other way round (this library before torch) the library binds to
     # /opt/rocm's runtime, torch initialises its own, and every launch fails with "no ROCm-capable device is detected".
-    import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in SIGNATURES.items():
         try:
@@ -266,7 +268,6 @@ def check(rc, what):
 
 
 def require_cuda_tensor(t, name, dtype=None):
-    import torch
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
         raise OrienMaskHipError("%s must be a tensor on an MI355X device (got %s); this path has no CPU fallback"
                                 % (name, getattr(t, "device", type(t))))
@@ -275,5 +276,52 @@ def require_cuda_tensor(t, name, dtype=None):
 
 
 def current_stream_ptr(device):
-    import torch
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+# ------------------------------------------------------------------------------------------------- the one call path
+_NO_SWITCH = contextlib.nullcontext()
+
+
+def on_device(dev):
+    """The launches go to the tensors' device: switch only when it is not the current one (the switch costs as much as a
+    launch).  Also the guard of a block of several launches with events or copies; `launch` inside it then switches nothing."""
+    return _NO_SWITCH if torch.cuda.current_device() == dev.index else torch.cuda.device(dev)
+
+
+def raw_args(args):
+    """The arguments as ctypes takes them under argtypes: a tensor becomes its data_ptr() (a view's own address); ints, floats,
+    None, ctypes objects and addresses computed by the caller pass through untouched.  Nothing is validated."""
+    return [a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args]
+
+
+def _entry(name):
+    if name not in SIGNATURES:
+        raise OrienMaskHipError("%s is not an entry point of %s" % (name, LIB_PATH))
+    return getattr(load(), name)
+
+
+def launch(name, dev, *args, stream=None):
+    """Call entry point `name`, whose last parameter is om_stream, with `dev` current: `args` through raw_args, then the stream --
+    `dev`'s current torch stream, or `stream` (a torch.cuda.Stream or a raw pointer).  A nonzero status raises check(rc, name)."""
+    fn = _entry(name)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    elif isinstance(stream, torch.cuda.Stream):
+        stream = stream.cuda_stream
+    with on_device(dev):
+        rc = fn(*raw_args(args), stream)
+    check(rc, name)
+
+
+def call(name, *args):
+    """launch without a device or a stream: the host-side entry points that return a status."""
+    check(_entry(name)(*raw_args(args)), name)
+
+
+def workspace_bytes(name, *args):
+    """A size query whose 0 means refusal: raises with the library's message, as check(-1, name) does."""
+    n = _entry(name)(*args)
+    if n == 0:
+        check(-1, name)
+    return n

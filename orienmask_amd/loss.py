@@ -182,12 +182,8 @@ class DeviceEvalCounter:
             out = torch.empty((), dtype=torch.float32, device=self.block.device)
         if not self.block.is_cuda:
             return _accumulate_torch(self.block, result, self.num_scales, self.scales_weight, with_metrics, step, out)
-        dev = self.block.device
-        with torch.cuda.device(dev):
-            rc = _lib.load().om_loss_accumulate(ctypes.c_void_p(result.data_ptr()), self.num_scales, self._w, int(bool(with_metrics)),
-                                                int(step), ctypes.c_void_p(self.block.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-                                                _lib.current_stream_ptr(dev))
-        _lib.check(rc, "om_loss_accumulate")
+        _lib.launch("om_loss_accumulate", self.block.device, result, self.num_scales, self._w, int(bool(with_metrics)), int(step),
+                    self.block, out)
         return out
 
     def _stage(self):
@@ -431,10 +427,7 @@ class OrienMaskYOLOMultiScaleLoss:
         return gt_bbox.contiguous(), gt_cls.contiguous(), gt_index.contiguous(), gt_mask, N
 
     def workspace_bytes(self, B, N):
-        n = _lib.load().om_loss_workspace_bytes(ctypes.byref(self.cfg_struct()), int(B), int(N))
-        if n == 0:
-            _lib.check(-1, "om_loss_workspace_bytes")
-        return n
+        return _lib.workspace_bytes("om_loss_workspace_bytes", ctypes.byref(self.cfg_struct()), int(B), int(N))
 
     def _workspace(self, nbytes, dev):
         if self._ws is None or self._ws.device != dev or self._ws.numel() < nbytes:
@@ -450,7 +443,6 @@ class OrienMaskYOLOMultiScaleLoss:
         heads = self._heads(predict)
         B, dev = heads[0][0].shape[0], heads[0][0].device
         gt_bbox, gt_cls, gt_index, gt_mask, N = self._targets(target, B, dev)
-        L = _lib.load()
         cfg = self.cfg_struct(heads)
         if workspace is None:
             ws = self._workspace(self.workspace_bytes(B, N), dev)
@@ -461,14 +453,12 @@ class OrienMaskYOLOMultiScaleLoss:
         result = torch.empty(_lib.OM_LOSS_RESULT_FLOATS, dtype=torch.float32, device=dev)
         bb = (ctypes.c_void_p * 3)(*[h[0].data_ptr() for h in heads] + [None] * (3 - len(heads)))
         oo = (ctypes.c_void_p * 3)(*[h[1].data_ptr() for h in heads] + [None] * (3 - len(heads)))
-        args = (ctypes.byref(cfg), bb, oo, B, ctypes.c_void_p(gt_bbox.data_ptr()), ctypes.c_void_p(gt_cls.data_ptr()),
-                ctypes.c_void_p(gt_index.data_ptr()), ctypes.c_void_p(gt_mask.data_ptr()), N, ctypes.c_void_p(result.data_ptr()),
-                ctypes.c_void_p(ws.data_ptr()), ws.numel())
+        args = (ctypes.byref(cfg), bb, oo, B, gt_bbox.data_ptr(), gt_cls.data_ptr(), gt_index.data_ptr(), gt_mask.data_ptr(), N,
+                result.data_ptr(), ws.data_ptr(), ws.numel())
         keep = (cfg, heads, gt_bbox, gt_cls, gt_index, gt_mask, ws)        # alive as long as the callable
 
         def run():
-            with torch.cuda.device(dev):
-                _lib.check(L.om_loss(*args, _lib.current_stream_ptr(dev)), "om_loss")
+            _lib.launch("om_loss", dev, *args)
             run.keep = keep
             return result
         run.heads, run.target, run.B, run.N, run.ws, run.result = heads, (gt_bbox, gt_cls, gt_index, gt_mask), B, N, ws, result
@@ -563,15 +553,9 @@ class OrienMaskYOLOMultiScaleLoss:
         for s, b in enumerate(predict_bbox):
             for i, v in enumerate(b.stride()):
                 cfg.bbox_stride[s][i] = v
-        L = _lib.load()
         ws = torch.empty(self.workspace_bytes(B, N) + 512, dtype=torch.uint8, device=dev)
         bb = (ctypes.c_void_p * 3)(*[t.data_ptr() for t in predict_bbox] + [None] * (3 - len(predict_bbox)))
-        ptr = lambda k: ctypes.c_void_p(out[k].data_ptr())     # noqa: E731
-        with torch.cuda.device(dev):
-            rc = L.om_loss_targets(ctypes.byref(cfg), bb, B, ctypes.c_void_p(gt_bbox.data_ptr()), ctypes.c_void_p(gt_cls.data_ptr()),
-                                   ctypes.c_void_p(gt_index.data_ptr()), ctypes.c_void_p(gt_mask.data_ptr()), N, scale,
-                                   ptr("bbox_pos_mask"), ptr("bbox_neg_mask"), ptr("bbox_pos_scale"), ptr("txy"), ptr("twh"),
-                                   ptr("tiou"), ptr("tcls"), ptr("orien_mask"), ptr("torien"), ctypes.c_void_p(ws.data_ptr()),
-                                   ws.numel(), _lib.current_stream_ptr(dev))
-        _lib.check(rc, "om_loss_targets")
+        _lib.launch("om_loss_targets", dev, ctypes.byref(cfg), bb, B, gt_bbox, gt_cls, gt_index, gt_mask, N, scale,
+                    *[out[k] for k in ("bbox_pos_mask", "bbox_neg_mask", "bbox_pos_scale", "txy", "twh", "tiou", "tcls", "orien_mask",
+                                       "torien")], ws, ws.numel())
         return out

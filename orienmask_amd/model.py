@@ -189,10 +189,8 @@ class OrienMaskYOLOFPNPlus(nn.Module):
 
     def _ensure_handle(self):
         if self._handle is None:
-            L = _lib.load()
             h = ctypes.c_void_p()
-            _lib.check(L.om_model_create_variant(ctypes.byref(h), self.VARIANT, self.num_anchors, self.num_classes),
-                       "om_model_create_variant")
+            _lib.call("om_model_create_variant", ctypes.byref(h), self.VARIANT, self.num_anchors, self.num_classes)
             self._handle = h
             self._layers = _pack.graph_layers(h)
             _pack.check_graph_matches_arch(self._layers, self.num_anchors, self.num_classes, type(self).__name__)
@@ -218,8 +216,7 @@ class OrienMaskYOLOFPNPlus(nn.Module):
         """Device blob in the library's layout (built lazily, cached until weights change)."""
         h = self._ensure_handle()
         if self._packed is None or self._packed_device != device:
-            L = _lib.load()
-            total = L.om_model_weight_floats(h)
+            total = _lib.load().om_model_weight_floats(h)
             blob = _pack.pack_state_dict(self.state_dict(), self._layers, total).to(device)
             self.bind_packed(blob)
         return self._packed
@@ -249,9 +246,8 @@ class OrienMaskYOLOFPNPlus(nn.Module):
     def bind_packed_split(self, blob):
         h = self._ensure_handle()
         _lib.require_cuda_tensor(blob, "packed split weights", torch.float32)
-        with torch.cuda.device(blob.device):
-            _lib.check(_lib.load().om_model_load_weights_split(h, ctypes.c_void_p(blob.data_ptr()), blob.numel() * 4),
-                       "om_model_load_weights_split")
+        with _lib.on_device(blob.device):
+            _lib.call("om_model_load_weights_split", h, blob, blob.numel() * 4)
         self._packed_split = blob
 
     LATENCY_CELLS = 3500          # about twelve 544 x 544 images (289 cells each): set_latency_mode(True)
@@ -267,9 +263,9 @@ class OrienMaskYOLOFPNPlus(nn.Module):
         than whole tiles (same 1e-4 bar against the reference; ~1e-6 of scale apart; run-to-run identical), so outputs are no
         longer independent of the batch size: off by default, on in tester.infer_loop (the reference's bs = 1 loop)."""
         self.latency_cells = int(cells if cells is not None else self.LATENCY_CELLS) if enable else 0
-        _lib.check(_lib.load().om_model_set_latency_cells(self._ensure_handle(), self.latency_cells), "om_model_set_latency_cells")
+        _lib.call("om_model_set_latency_cells", self._ensure_handle(), self.latency_cells)
         if ksplit is not None:      # most parts a small launch's k loop is cut into (om_model_set_latency_ksplit; default 8, 1 = whole tiles)
-            _lib.check(_lib.load().om_model_set_latency_ksplit(self._ensure_handle(), int(ksplit)), "om_model_set_latency_ksplit")
+            _lib.call("om_model_set_latency_ksplit", self._ensure_handle(), int(ksplit))
         return self
 
     def set_upsample_on_read(self, enable=True):
@@ -277,7 +273,7 @@ class OrienMaskYOLOFPNPlus(nn.Module):
         layer behind each concat (neck16.0 / neck8.0 / neck4.0) reads them up-sampled; False = they store their output replicated
         into the concat buffer (what 'f32' does).  Bit-identical outputs; for A/B measurements and the test of that claim.
         Drops the cached workspaces (their layout differs)."""
-        _lib.check(_lib.load().om_model_set_upsample_on_read(self._ensure_handle(), 1 if enable else 0), "om_model_set_upsample_on_read")
+        _lib.call("om_model_set_upsample_on_read", self._ensure_handle(), 1 if enable else 0)
         self._workspace.clear()
         self._slot_workspaces.clear()
         return self
@@ -315,19 +311,16 @@ class OrienMaskYOLOFPNPlus(nn.Module):
     def bind_packed_f16(self, blob):
         h = self._ensure_handle()
         _lib.require_cuda_tensor(blob, "packed fp16 weights", torch.float16)
-        with torch.cuda.device(blob.device):
-            _lib.check(_lib.load().om_model_load_weights_f16(h, ctypes.c_void_p(blob.data_ptr()), blob.numel() * 2),
-                       "om_model_load_weights_f16")
+        with _lib.on_device(blob.device):
+            _lib.call("om_model_load_weights_f16", h, blob, blob.numel() * 2)
         self._packed16 = blob
 
     def bind_packed(self, blob):
         """Bind an already packed device blob (used after an RCCL broadcast of rank 0's blob)."""
         h = self._ensure_handle()
         _lib.require_cuda_tensor(blob, "packed weights", torch.float32)
-        L = _lib.load()
-        with torch.cuda.device(blob.device):
-            _lib.check(L.om_model_load_weights(h, ctypes.c_void_p(blob.data_ptr()), blob.numel() * 4, 0),
-                       "om_model_load_weights")
+        with _lib.on_device(blob.device):
+            _lib.call("om_model_load_weights", h, blob, blob.numel() * 4, 0)
         self._packed = blob
         self._packed_device = blob.device
 
@@ -352,7 +345,7 @@ class OrienMaskYOLOFPNPlus(nn.Module):
         split = precision == "f32_split"
         if split:
             self.packed_weights_split(dev)
-        _lib.check(L.om_model_set_precision(h, 1 if split else 0), "om_model_set_precision")
+        _lib.call("om_model_set_precision", h, 1 if split else 0)
         # sub-batches: n_streams > 1 runs B / n_streams images on each of n side streams (own workspace each) and joins
         # them on the caller's stream; images are independent, so the results are bit-identical to one launch
         n_sub = self.n_streams if (self.n_streams > 1 and B % self.n_streams == 0) else 1
@@ -374,17 +367,15 @@ class OrienMaskYOLOFPNPlus(nn.Module):
         bbox_dim = A * (5 + self.num_classes)
         heads = [torch.empty((B, H // s, W // s, HEAD_PIX_STRIDE), dtype=torch.float32, device=dev) for s in (32, 16, 8)]
         oriens = torch.empty((B, 6 * A, H // 4, W // 4), dtype=torch.float32, device=dev)
-        fwd = L.om_forward_f16 if f16 else L.om_forward
+        fwd = "om_forward_f16" if f16 else "om_forward"
 
-        def launch(i, stream_ptr):
+        def launch(i, stream=None):
             xs, hs, os_ = x[i * Bs:], [t[i * Bs:] for t in heads], oriens[i * Bs:]
-            return fwd(h, ctypes.c_void_p(xs.data_ptr()), Bs, H, W, ctypes.c_void_p(hs[0].data_ptr()),
-                       ctypes.c_void_p(hs[1].data_ptr()), ctypes.c_void_p(hs[2].data_ptr()), ctypes.c_void_p(os_.data_ptr()),
-                       ctypes.c_void_p(ws.data_ptr() + i * ws_each), ws_each, stream_ptr)
+            _lib.launch(fwd, dev, h, xs, Bs, H, W, hs[0], hs[1], hs[2], os_, ws.data_ptr() + i * ws_each, ws_each, stream=stream)
 
-        with torch.cuda.device(dev):
+        with _lib.on_device(dev):
             if n_sub == 1:
-                _lib.check(launch(0, _lib.current_stream_ptr(dev)), "om_forward")
+                launch(0)
             else:
                 cur = torch.cuda.current_stream(dev)
                 side = self._side_streams.setdefault(dev, [])
@@ -392,7 +383,7 @@ class OrienMaskYOLOFPNPlus(nn.Module):
                     side.append(torch.cuda.Stream(device=dev))
                 for i in range(n_sub):
                     side[i].wait_stream(cur)
-                    _lib.check(launch(i, ctypes.c_void_p(side[i].cuda_stream)), "om_forward")
+                    launch(i, side[i])
                 for i in range(n_sub):
                     cur.wait_stream(side[i])
             # the status word of every launched sub-batch, copied out of the workspace (which the next forward in this slot
@@ -409,12 +400,12 @@ class OrienMaskYOLOFPNPlus(nn.Module):
     # ------------------------------------------------------------------ measurement
     def profile_enable(self, enable=True):
         """Record one HIP event pair per layer on the launch stream during forward()."""
-        _lib.check(_lib.load().om_profile_enable(self._ensure_handle(), 1 if enable else 0), "om_profile_enable")
+        _lib.call("om_profile_enable", self._ensure_handle(), 1 if enable else 0)
 
     def keep_activations(self, keep=True):
         """Give every activation its own workspace slab (no reuse by live range) so that layer_output() can be read after a
         forward.  Drops the cached workspaces: the next forward sizes a new one."""
-        _lib.check(_lib.load().om_model_keep_activations(self._ensure_handle(), 1 if keep else 0), "om_model_keep_activations")
+        _lib.call("om_model_keep_activations", self._ensure_handle(), 1 if keep else 0)
         self._workspace.clear()
         self._slot_workspaces.clear()
         return self
@@ -429,8 +420,8 @@ class OrienMaskYOLOFPNPlus(nn.Module):
         f16 = self.precision == "f16"
         ws = next(iter(self._workspace.values()))
         off, ch, ps, div = ctypes.c_size_t(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
-        _lib.check(_lib.load().om_layer_output_view(h, idx, B, H, W, 1 if f16 else 0, ctypes.byref(off), ctypes.byref(ch),
-                                                    ctypes.byref(ps), ctypes.byref(div)), "om_layer_output_view")
+        _lib.call("om_layer_output_view", h, idx, B, H, W, 1 if f16 else 0, ctypes.byref(off), ctypes.byref(ch), ctypes.byref(ps),
+                  ctypes.byref(div))
         dt = torch.float16 if f16 else torch.float32
         esz = 2 if f16 else 4
         hh, ww = H // div.value, W // div.value
@@ -441,7 +432,7 @@ class OrienMaskYOLOFPNPlus(nn.Module):
         """Like profile_enable(True), but events are recorded only around the named layers (cheaper inside a timed region)."""
         h = self._ensure_handle()
         mask = bytes(1 if l["name"] in set(names) else 0 for l in self._layers)
-        _lib.check(_lib.load().om_profile_enable_layers(h, mask, len(mask)), "om_profile_enable_layers")
+        _lib.call("om_profile_enable_layers", h, mask, len(mask))
 
     def layer_kernels(self, B, H, W):
         """Kernel instantiation that runs each layer at this size: 'conv_stem_kernel' or
@@ -451,18 +442,16 @@ class OrienMaskYOLOFPNPlus(nn.Module):
         if self.precision == "f16":
             for i, l in enumerate(self._layers):
                 bm, bn, algo = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
-                _lib.check(_lib.load().om_layer_tile_f16(h, i, B, H, W, ctypes.byref(bm), ctypes.byref(bn),
-                                                         ctypes.byref(algo)), "om_layer_tile_f16")
+                _lib.call("om_layer_tile_f16", h, i, B, H, W, ctypes.byref(bm), ctypes.byref(bn), ctypes.byref(algo))
                 fmt = {0: "conv_stem_kernel<f16>", 1: "conv_igemm_f16_kernel<%d,%d>", 4: "conv3x3_f16_kernel<%d,%d>",
                        5: "conv_igemm_f16_kernel<%d,%d,gather>", 6: "conv3x3_f16_tall_kernel<%d,%d>",
                        7: "conv_stem2_f16_kernel<%d,%d>", 8: "(in the previous layer's kernel)"}[algo.value]
                 out.append((l["name"], fmt % (bm.value, bn.value) if algo.value not in (0, 8) else fmt))
             return out
-        _lib.check(_lib.load().om_model_set_precision(h, 1 if self.precision == "f32_split" else 0), "om_model_set_precision")
+        _lib.call("om_model_set_precision", h, 1 if self.precision == "f32_split" else 0)
         for i, l in enumerate(self._layers):
             bm, bn, algo = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
-            _lib.check(_lib.load().om_layer_tile(h, i, B, H, W, ctypes.byref(bm), ctypes.byref(bn), ctypes.byref(algo)),
-                       "om_layer_tile")
+            _lib.call("om_layer_tile", h, i, B, H, W, ctypes.byref(bm), ctypes.byref(bn), ctypes.byref(algo))
             fmt = {0: "conv_stem_kernel", 1: "conv_igemm_f32_kernel<%d,%d>", 2: "wino_gemm_kernel<%d,%d>",
                    3: "wino_fused_kernel<%d,%d>", 5: "wino24_gemm_kernel<%d,%d>",
                    7: "conv_igemm_split_kernel<%d,%d>", 8: "wino14_split_kernel<%d,%d>",
@@ -479,7 +468,7 @@ class OrienMaskYOLOFPNPlus(nn.Module):
         ms = (ctypes.c_float * n)()
         pre = (ctypes.c_float * n)()
         nf = ctypes.c_int(0)
-        _lib.check(_lib.load().om_profile_read(h, ms, pre, n, ctypes.byref(nf)), "om_profile_read")
+        _lib.call("om_profile_read", h, ms, pre, n, ctypes.byref(nf))
         return [(self._layers[i]["name"], float(ms[i]), float(pre[i])) for i in range(n)], nf.value
 
     def __del__(self):

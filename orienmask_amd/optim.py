@@ -23,8 +23,6 @@ pinned staging buffers and hands that to om_sgd_step, which enqueues the host-to
 stream.  A staging buffer is reused only after the event recorded behind its copy has completed.  After a parameter's first step
 nothing is allocated and nothing is read back from the device.
 """
-import ctypes as _ctypes
-
 import numpy as _np
 import torch as _torch
 from torch.optim import *                   # noqa: F401,F403  (the reference's optim/__init__.py:1)
@@ -218,7 +216,7 @@ class SGD(_TorchSGD):
             b = nb
         return b
 
-    def _step_plan(self, plan, L):
+    def _step_plan(self, plan):
         groups = self.param_groups
         for gi in plan.group_slots:
             g = groups[gi]
@@ -279,15 +277,9 @@ class SGD(_TorchSGD):
         plan.staging_rows[k][:] = rows
         dev = plan.device
         stream = _torch.cuda.current_stream(dev)
-        args = (_ctypes.c_void_p(plan.staging[k].data_ptr()), _ctypes.c_void_p(plan.table.data_ptr()), plan.n,
-                _ctypes.c_void_p(plan.chunks.data_ptr()), plan.n_chunks, _ctypes.c_void_p(stream.cuda_stream))
-        if _torch.cuda.current_device() == dev.index:
-            _lib.check(L.om_sgd_step(*args), "om_sgd_step")
+        with _lib.on_device(dev):
+            _lib.launch("om_sgd_step", dev, plan.staging[k], plan.table, plan.n, plan.chunks, plan.n_chunks, stream=stream)
             ev.record(stream)
-        else:
-            with _torch.cuda.device(dev):
-                _lib.check(L.om_sgd_step(*args), "om_sgd_step")
-                ev.record(stream)
         del keep
 
     def step(self, closure=None):
@@ -296,12 +288,12 @@ class SGD(_TorchSGD):
         if closure is not None:
             with _torch.enable_grad():
                 loss = closure()
-        L = _lib.load()
+        _lib.load()
         if getattr(self, "_plans", None) is None or self._built_for != self._structure():
             self._build_plans()
         with _torch.no_grad():
             for plan in self._plans:
-                self._step_plan(plan, L)
+                self._step_plan(plan)
         return loss
 
 

@@ -25,7 +25,7 @@ def graph_layers(handle):
     out = []
     for i in range(L.om_model_num_layers(handle)):
         info = _lib.LayerInfo()
-        _lib.check(L.om_model_layer_info(handle, i, ctypes.byref(info)), "om_model_layer_info")
+        _lib.call("om_model_layer_info", handle, i, ctypes.byref(info))
         out.append(dict(name=info.name.decode(), cin=info.cin, cout=info.cout, cout_pad=info.cout_pad,
                         ksize=info.ksize, stride=info.stride, has_bn=bool(info.has_bn), leaky=bool(info.leaky),
                         w_off=info.w_off, scale_off=info.scale_off, shift_off=info.shift_off,

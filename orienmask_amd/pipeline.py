@@ -93,7 +93,7 @@ class InFlightPipeline:
         cur.wait_event(done)
         for t in outs[:5]:
             t.record_stream(cur)                               # the caller goes on using them on its own stream
-        with torch.cuda.device(dev):
+        with _lib.on_device(dev):
             return self._posts[slot].collect(outs)
 
     def map(self, batches):

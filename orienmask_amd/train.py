@@ -134,14 +134,11 @@ class _Call:
         ptrs = lambda ts: (ctypes.c_void_p * 3)(*[t.data_ptr() for t in ts] + [None] * (3 - S))      # noqa: E731
         _, _, gt_index, gt_mask = self.target
         args = (ctypes.byref(cfg), ptrs([b for b, _ in self.read]), ptrs([o for _, o in self.read]), self.B,
-                ctypes.c_void_p(gt_index.data_ptr()), ctypes.c_void_p(gt_mask.data_ptr()), self.N,
-                ctypes.c_void_p(self.result.data_ptr()), ctypes.c_void_p(self.ws.data_ptr()), self.ws.numel(),
-                ctypes.c_void_p(g.data_ptr()), (ctypes.c_float * 3)(*self.sw + [0.0] * (3 - S)), ptrs(gb), ptrs(go))
-        L = _lib.load()
+                gt_index.data_ptr(), gt_mask.data_ptr(), self.N, self.result.data_ptr(), self.ws.data_ptr(), self.ws.numel(),
+                g.data_ptr(), (ctypes.c_float * 3)(*self.sw + [0.0] * (3 - S)), ptrs(gb), ptrs(go))
 
         def run():
-            with torch.cuda.device(dev):
-                _lib.check(L.om_loss_backward(*args, _lib.current_stream_ptr(dev)), "om_loss_backward")
+            _lib.launch("om_loss_backward", dev, *args)
             run.keep = (cfg, g)
         return run, gb, go
 
@@ -216,17 +213,8 @@ class OrienMaskYOLOMultiScaleLoss(_ValuesLoss):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the model
-def _vp(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
 _WORKSPACES = {}
 _NO_SWITCH = contextlib.nullcontext()
-
-
-def _device(dev):
-    """The launches go to the tensors' device: switch only when it is not the current one (the switch costs as much as a launch)."""
-    return _NO_SWITCH if torch.cuda.current_device() == dev.index else torch.cuda.device(dev)
 
 
 def _workspace(dev, stream, nbytes):
@@ -254,10 +242,9 @@ def _autocast(amp, x):
 
 
 def _bn_scratch(x):
-    """(library, stream, workspace) of an om_bn_act_* / om_bn_sync_* call on x's device and current stream."""
-    L = _lib.load()
+    """(stream, workspace) of an om_bn_act_* / om_bn_sync_* call on x's device and current stream."""
     stream = _lib.current_stream_ptr(x.device)
-    return L, stream, _workspace(x.device, stream, L.om_bn_act_workspace_bytes(*x.shape))
+    return stream, _workspace(x.device, stream, _lib.load().om_bn_act_workspace_bytes(*x.shape))
 
 
 def _bn_forward_buffers(x):
@@ -292,13 +279,10 @@ class _BNAct(torch.autograd.Function):
         training = bool(bn.training or bn.running_mean is None)
         y, save = _bn_forward_buffers(x)
         track = training and bn.running_mean is not None
-        L, stream, ws = _bn_scratch(x)
-        with _device(x.device):
-            _lib.check(getattr(L, "om_bn_act_forward" + _sfx(x))(
-                _vp(x), B, C, H, W, _vp(gamma), _vp(beta), _vp(bn.running_mean), _vp(bn.running_var),
-                _vp(bn.num_batches_tracked) if track else None, 1 if training else 0, float(bn.momentum), float(bn.eps),
-                float(slope), _vp(residual), _vp(y), save.data_ptr(), save.data_ptr() + 8 * C, ws.data_ptr(), ws.numel(), stream),
-                "om_bn_act_forward")
+        stream, ws = _bn_scratch(x)
+        _lib.launch("om_bn_act_forward" + _sfx(x), x.device, x, B, C, H, W, gamma, beta, bn.running_mean, bn.running_var,
+                    bn.num_batches_tracked if track else None, 1 if training else 0, float(bn.momentum), float(bn.eps),
+                    float(slope), residual, y, save.data_ptr(), save.data_ptr() + 8 * C, ws, ws.numel(), stream=stream)
         ctx.save_for_backward(x, gamma, beta, save)
         ctx.training, ctx.slope, ctx.has_residual = training, float(slope), residual is not None
         return y
@@ -309,11 +293,9 @@ class _BNAct(torch.autograd.Function):
         x, gamma, beta, save = ctx.saved_tensors
         B, C, H, W = x.shape
         dy, dx, dgb = _bn_backward_buffers(ctx, x, dy)
-        L, stream, ws = _bn_scratch(x)
-        with _device(x.device):
-            _lib.check(getattr(L, "om_bn_act_backward" + _sfx(x))(
-                _vp(x), _vp(dy), B, C, H, W, _vp(gamma), _vp(beta), save.data_ptr(), save.data_ptr() + 8 * C, 1 if ctx.training else 0,
-                ctx.slope, _vp(dx), dgb.data_ptr(), dgb.data_ptr() + 4 * C, ws.data_ptr(), ws.numel(), stream), "om_bn_act_backward")
+        stream, ws = _bn_scratch(x)
+        _lib.launch("om_bn_act_backward" + _sfx(x), x.device, x, dy, B, C, H, W, gamma, beta, save.data_ptr(), save.data_ptr() + 8 * C,
+                    1 if ctx.training else 0, ctx.slope, dx, dgb.data_ptr(), dgb.data_ptr() + 4 * C, ws, ws.numel(), stream=stream)
         return _bn_grads(ctx, dx, dgb, dy)
 
 
@@ -335,9 +317,7 @@ class _Conv2d(torch.autograd.Function):
         pad = ks // 2
         dev = x.device
         y = torch.empty((B, cout, (H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1), dtype=torch.float32, device=dev)
-        with _device(dev):
-            _lib.check(_lib.load().om_conv2d_forward(_vp(x), _vp(weight), _vp(bias), B, cin, H, W, cout, ks, stride, _vp(y),
-                                                     _lib.current_stream_ptr(dev)), "om_conv2d_forward")
+        _lib.launch("om_conv2d_forward", dev, x, weight, bias, B, cin, H, W, cout, ks, stride, y)
         return y
 
     @staticmethod
@@ -347,7 +327,6 @@ class _Conv2d(torch.autograd.Function):
         B, cin, H, W = x.shape
         cout, ks = weight.shape[0], weight.shape[2]
         dev = x.device
-        L = _lib.load()
         dy = dy.contiguous()
         need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
         dx = torch.empty_like(x) if need_x else None
@@ -355,14 +334,12 @@ class _Conv2d(torch.autograd.Function):
         db = torch.empty(cout, dtype=torch.float32, device=dev) if need_b else None
         stream = _lib.current_stream_ptr(dev)
         geom = (B, cin, H, W, cout, ks, ctx.stride)
-        with _device(dev):
-            ws = _workspace(dev, stream, L.om_conv2d_grad_workspace_bytes(*geom))
+        with _lib.on_device(dev):
+            ws = _workspace(dev, stream, _lib.load().om_conv2d_grad_workspace_bytes(*geom))
             if need_x:
-                _lib.check(L.om_conv2d_grad_input(_vp(dy), _vp(weight), *geom, _vp(dx), ws.data_ptr(), ws.numel(), stream),
-                           "om_conv2d_grad_input")
+                _lib.launch("om_conv2d_grad_input", dev, dy, weight, *geom, dx, ws, ws.numel(), stream=stream)
             if need_w or need_b:
-                _lib.check(L.om_conv2d_grad_weight(_vp(x), _vp(dy), *geom, _vp(dw), _vp(db), ws.data_ptr(), ws.numel(), stream),
-                           "om_conv2d_grad_weight")
+                _lib.launch("om_conv2d_grad_weight", dev, x, dy, *geom, dw, db, ws, ws.numel(), stream=stream)
         return dx, dw, db, None, None
 
 
@@ -462,30 +439,25 @@ def conv_bn_leaky_frozen(x, weight, bn, residual=None, stride=1, padding=0, slop
     _require_no_grad(what, x=x, residual=residual, weight=weight, **{"bn.weight": bn.weight, "bn.bias": bn.bias})
     dev = x.device
     y = torch.empty(shape, dtype=torch.float32, device=dev)
-    with _device(dev):
-        _lib.check(_lib.load().om_conv2d_frozen_forward(
-            _vp(x), _vp(weight), B, cin, H, W, cout, ks, s, _vp(bn.weight), _vp(bn.bias), _vp(bn.running_mean), _vp(bn.running_var),
-            float(bn.eps), float(slope), _vp(residual), _vp(y), _lib.current_stream_ptr(dev)), "om_conv2d_frozen_forward")
+    _lib.launch("om_conv2d_frozen_forward", dev, x, weight, B, cin, H, W, cout, ks, s, bn.weight, bn.bias, bn.running_mean,
+                bn.running_var, float(bn.eps), float(slope), residual, y)
     return y
 
 
-def _route_call(fn, what, ptrs, chans, scales, B, H, W, whole, dev):
-    """One om_route_concat_* call on the current stream: `ptrs` the per-source tensors (None: null), `whole` y or dy; the entry
+def _route_call(fn, ptrs, chans, scales, B, H, W, whole, dev):
+    """One om_route_concat_<fn> call on the current stream: `ptrs` the per-source tensors (None: null), `whole` y or dy; the entry
     point is the one of their element type."""
     n = len(chans)
     table = (ctypes.c_void_p * ROUTE_MAX)(*[t.data_ptr() if t is not None else None for t in ptrs] + [None] * (ROUTE_MAX - n))
     c = (ctypes.c_int * ROUTE_MAX)(*list(chans) + [0] * (ROUTE_MAX - n))
     s = (ctypes.c_int * ROUTE_MAX)(*list(scales) + [0] * (ROUTE_MAX - n))
-    stream = _lib.current_stream_ptr(dev)
     for t in ptrs:
         if t is not None and t.dtype != whole.dtype:
-            raise _lib.OrienMaskHipError("%s: tensors of %s and %s in one call: there is no cast" % (what, t.dtype, whole.dtype))
-    with _device(dev):
-        if fn == "forward":
-            rc = getattr(_lib.load(), "om_route_concat_forward" + _sfx(whole))(table, c, s, n, B, H, W, _vp(whole), stream)
-        else:
-            rc = getattr(_lib.load(), "om_route_concat_backward" + _sfx(whole))(_vp(whole), c, s, n, B, H, W, table, stream)
-    _lib.check(rc, what)
+            raise _lib.OrienMaskHipError("om_route_concat_%s: tensors of %s and %s in one call: there is no cast" % (fn, t.dtype, whole.dtype))
+    if fn == "forward":
+        _lib.launch("om_route_concat_forward" + _sfx(whole), dev, table, c, s, n, B, H, W, whole)
+    else:
+        _lib.launch("om_route_concat_backward" + _sfx(whole), dev, whole, c, s, n, B, H, W, table)
 
 
 class _UpsampleConcat(torch.autograd.Function):
@@ -500,7 +472,7 @@ class _UpsampleConcat(torch.autograd.Function):
         chans = [int(t.shape[1]) for t in tensors]
         dev = tensors[0].device
         y = torch.empty((B, sum(chans), H, W), dtype=tensors[0].dtype, device=dev)
-        _route_call("forward", "om_route_concat_forward", tensors, chans, scales, B, H, W, y, dev)
+        _route_call("forward", tensors, chans, scales, B, H, W, y, dev)
         ctx.geom = (chans, tuple(scales), B, H, W)
         return y
 
@@ -513,7 +485,7 @@ class _UpsampleConcat(torch.autograd.Function):
         grads = [torch.empty((B, c, H // s, W // s), dtype=dy.dtype, device=dev) if need else None
                  for c, s, need in zip(chans, scales, ctx.needs_input_grad[1:])]
         if any(g is not None for g in grads):
-            _route_call("backward", "om_route_concat_backward", grads, chans, scales, B, H, W, dy, dev)
+            _route_call("backward", grads, chans, scales, B, H, W, dy, dev)
         return (None,) + tuple(grads)
 
 
@@ -526,7 +498,7 @@ class _SplitChannels(torch.autograd.Function):
     def forward(ctx, x, sizes):
         B, C, H, W = x.shape
         outs = [torch.empty((B, c, H, W), dtype=x.dtype, device=x.device) for c in sizes]
-        _route_call("backward", "om_route_concat_backward", outs, sizes, [1] * len(sizes), B, H, W, x, x.device)
+        _route_call("backward", outs, sizes, [1] * len(sizes), B, H, W, x, x.device)
         ctx.geom = (tuple(sizes), B, H, W, x.device, x.dtype)
         ctx.set_materialize_grads(False)
         return tuple(outs)
@@ -539,7 +511,7 @@ class _SplitChannels(torch.autograd.Function):
             return None, None
         grads = [g.contiguous() if g is not None else None for g in grads]
         dx = torch.empty((B, sum(sizes), H, W), dtype=dtype, device=dev)
-        _route_call("forward", "om_route_concat_forward", grads, sizes, [1] * len(sizes), B, H, W, dx, dev)
+        _route_call("forward", grads, sizes, [1] * len(sizes), B, H, W, dx, dev)
         return dx, None
 
 
@@ -599,14 +571,13 @@ class _SyncBNAct(torch.autograd.Function):
         records = torch.empty(R * 3 * C, dtype=torch.float64, device=dev)
         n_total = torch.empty(1, dtype=torch.float64, device=dev)
         track = bn.running_mean is not None
-        L, stream, ws = _bn_scratch(x)
-        with _device(dev):
-            _lib.check(getattr(L, "om_bn_sync_stats" + _sfx(x))(_vp(x), B, C, H, W, _vp(record), ws.data_ptr(), ws.numel(), stream), "om_bn_sync_stats")
+        stream, ws = _bn_scratch(x)
+        with _lib.on_device(dev):
+            _lib.launch("om_bn_sync_stats" + _sfx(x), dev, x, B, C, H, W, record, ws, ws.numel(), stream=stream)
             dist.all_gather_into_tensor(records, record, group=group)
-            _lib.check(getattr(L, "om_bn_sync_forward" + _sfx(x))(
-                _vp(x), B, C, H, W, _vp(records), R, _vp(gamma), _vp(beta), _vp(bn.running_mean), _vp(bn.running_var),
-                _vp(bn.num_batches_tracked) if track else None, float(bn.momentum), float(bn.eps), float(slope), _vp(residual),
-                _vp(y), save.data_ptr(), save.data_ptr() + 8 * C, _vp(n_total), stream), "om_bn_sync_forward")
+            _lib.launch("om_bn_sync_forward" + _sfx(x), dev, x, B, C, H, W, records, R, gamma, beta, bn.running_mean, bn.running_var,
+                        bn.num_batches_tracked if track else None, float(bn.momentum), float(bn.eps), float(slope), residual,
+                        y, save.data_ptr(), save.data_ptr() + 8 * C, n_total, stream=stream)
         ctx.save_for_backward(x, gamma, beta, save, n_total)
         ctx.slope, ctx.has_residual, ctx.group, ctx.R = float(slope), residual is not None, group, R
         return y
@@ -621,17 +592,15 @@ class _SyncBNAct(torch.autograd.Function):
         R = ctx.R
         dy, dx, dgb = _bn_backward_buffers(ctx, x, dy)
         sums = torch.empty(2 * C, dtype=torch.float64, device=dev)
-        L, stream, ws = _bn_scratch(x)
-        with _device(dev):
-            _lib.check(getattr(L, "om_bn_sync_backward_sums" + _sfx(x))(
-                _vp(x), _vp(dy), B, C, H, W, _vp(gamma), _vp(beta), save.data_ptr(), save.data_ptr() + 8 * C, ctx.slope, _vp(sums),
-                dgb.data_ptr(), dgb.data_ptr() + 4 * C, ws.data_ptr(), ws.numel(), stream), "om_bn_sync_backward_sums")
+        stream, ws = _bn_scratch(x)
+        with _lib.on_device(dev):
+            _lib.launch("om_bn_sync_backward_sums" + _sfx(x), dev, x, dy, B, C, H, W, gamma, beta, save.data_ptr(),
+                        save.data_ptr() + 8 * C, ctx.slope, sums, dgb.data_ptr(), dgb.data_ptr() + 4 * C, ws, ws.numel(), stream=stream)
             if dx is not None:
                 sums_all = torch.empty(R * 2 * C, dtype=torch.float64, device=dev)
                 dist.all_gather_into_tensor(sums_all, sums, group=ctx.group)
-                _lib.check(getattr(L, "om_bn_sync_backward_dx" + _sfx(x))(
-                    _vp(x), _vp(dy), B, C, H, W, _vp(gamma), _vp(beta), save.data_ptr(), save.data_ptr() + 8 * C, ctx.slope,
-                    _vp(sums_all), R, _vp(n_total), _vp(dx), stream), "om_bn_sync_backward_dx")
+                _lib.launch("om_bn_sync_backward_dx" + _sfx(x), dev, x, dy, B, C, H, W, gamma, beta, save.data_ptr(),
+                            save.data_ptr() + 8 * C, ctx.slope, sums_all, R, n_total, dx, stream=stream)
         return _bn_grads(ctx, dx, dgb, dy)
 
 

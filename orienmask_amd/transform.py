@@ -85,11 +85,7 @@ class FastCOCOTransform:
         mean = (ctypes.c_float * 3)(*(self._norm.mean if self._norm else [0.0] * 3))
         std = (ctypes.c_float * 3)(*(self._norm.std if self._norm else [1.0] * 3))
         out = torch.empty((n, 3, oh, ow), dtype=torch.float32, device=image.device)
-        L = _lib.load()
-        with torch.cuda.device(image.device):
-            rc = L.om_preprocess(ctypes.c_void_p(image.data_ptr()), n, h, w, rh, rw, mean, std, top, left, oh, ow,
-                                 float(pad_value), ctypes.c_void_p(out.data_ptr()), _lib.current_stream_ptr(image.device))
-        _lib.check(rc, "om_preprocess")
+        _lib.launch("om_preprocess", image.device, image, n, h, w, rh, rw, mean, std, top, left, oh, ow, float(pad_value), out)
         return out, [left, right, top, down, oh, ow]
 
     def __call__(self, image):
@@ -116,12 +112,7 @@ def pad(image, size_divisor=32, pad_value=0):
     src = image.contiguous()
     planes = src.numel() // (height * width)
     out = torch.empty(tuple(src.shape[:-2]) + (new_height, new_width), dtype=torch.float32, device=src.device)
-    L = _lib.load()
-    with torch.cuda.device(src.device):
-        rc = L.om_pad_nchw(ctypes.c_void_p(src.data_ptr()), planes, height, width, pad_top, pad_left, new_height,
-                           new_width, float(pad_value), ctypes.c_void_p(out.data_ptr()),
-                           _lib.current_stream_ptr(src.device))
-    _lib.check(rc, "om_pad_nchw")
+    _lib.launch("om_pad_nchw", src.device, src, planes, height, width, pad_top, pad_left, new_height, new_width, float(pad_value), out)
     return out, pad_info
 
 

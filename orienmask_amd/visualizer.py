@@ -207,7 +207,6 @@ class InferenceVisualizer:
         return item
 
     def _launch(self, items, outs, draw_boxes, out_floats=None):
-        L = _lib.load()
         imgs = (_lib.VisImage * len(items))()
         alive = []                      # tensors whose pointers the descriptors hold, until the launch is enqueued
         dev = items[0]["image"].device
@@ -232,9 +231,8 @@ class InferenceVisualizer:
                 if it["mask"] is not None:
                     m = it["mask"]
                     d.mask, d.Hn, d.Wn = m.data_ptr(), int(m.shape[1]), int(m.shape[2])
-        ws = torch.empty(int(L.om_visualize_workspace_bytes(imgs, len(items))), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(L.om_visualize(imgs, len(items), ctypes_ptr(ws), ws.numel(), _lib.current_stream_ptr(dev)), "om_visualize")
+        ws = torch.empty(int(_lib.load().om_visualize_workspace_bytes(imgs, len(items))), dtype=torch.uint8, device=dev)
+        _lib.launch("om_visualize", dev, imgs, len(items), ws, ws.numel())
         del alive
         return ws
 
@@ -278,8 +276,3 @@ class InferenceVisualizer:
         mask = mask[:, top:-down if down else None, left:-right if right else None]
         mask = F.interpolate(mask.float().unsqueeze(0), size=(height, width), mode='bilinear', align_corners=False)
         return mask.squeeze(0)
-
-
-def ctypes_ptr(t):
-    import ctypes
-    return ctypes.c_void_p(t.data_ptr())
