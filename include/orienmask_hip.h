@@ -880,6 +880,35 @@ int om_conv2d_frozen_forward(const float* x, const float* w, int B, int cin, int
                              const float* gamma, const float* beta, const float* running_mean, const float* running_var, double eps,
                              float slope, const float* residual, float* y, om_stream stream);
 
+/* ---- The same forward on bf16 activations (orienmask_amd.train.conv2d_bf16; the models with amp='bf16', conv_forward='hip'):
+ *      x [B,cin,H,W] bf16 (uint16_t bits), w [cout,cin,ksize,ksize] the FLOAT32 master weight, bias [cout] float32 or null; the
+ *      geometries, layouts and size limits of om_conv2d_forward.  y [B,cout,Ho,Wo]: float32 where y_is_f32 != 0, bf16 otherwise.
+ *      One kernel (csrc/conv_fwd_bf16.hip) with om_conv2d_forward's tiles (128 consecutive output pixels of the flat (b, oy, ox)
+ *      index by 64 or 32 output channels, the whole k in one workgroup: no split, no workspace) on v_mfma_f32_32x32x16_bf16.
+ *      Arithmetic: x is widened exactly; every weight is rounded to bf16 (nearest, ties to even: csrc/bf16.h, torch's
+ *      .to(torch.bfloat16)) while it is staged -- no cast kernel, no bf16 copy.  Every product is exact in float32; an element's sum
+ *      is ONE float32 chain in the matrix instruction's accumulators, 16 input channels of one tap per step, in the order input
+ *      channels (blocks of 16) > kh > kw (at 1x1: input channels), channels beyond cin as zeros.  That order is a function of the
+ *      geometry only -- not of the tile, the image index, B or the co tile width -- so an image's y has the same bits alone, in any
+ *      batch and on every run.  y32 = sum + bias (one float32 add; none without a bias); the float32 output is y32, the bf16 output
+ *      its rounding to nearest even: bf16 y == rne(float32 y) bit for bit.
+ *      No alignment beyond the element's own is required (a bf16 tensor may start at any uint16_t).  Enqueued on `stream`; no
+ *      allocation, no host synchronisation, no atomics.  A null x / w / y, another geometry or sizes outside the limits return
+ *      OM_EINVAL and nothing is written. */
+int om_conv2d_bf16_forward(const uint16_t* x, const float* w, const float* bias, int B, int cin, int H, int W, int cout, int ksize,
+                           int stride, void* y, int y_is_f32, om_stream stream);
+
+/* ---- The FROZEN block on bf16 activations (orienmask_amd.train.conv_bn_leaky_frozen on a bf16 x; the models' frozen_stages with
+ *      amp='bf16', conv_forward='hip'): om_conv2d_bf16_forward without a bias, with om_conv2d_frozen_forward's epilogue on its
+ *      float32 sum h:  y = rne_bf16((float)((z > 0 ? z : z * slope) + residual)),  z = fma((double)h - mean, gamma * invstd, beta),
+ *      the same per-channel doubles (csrc/bn_channel.h).  x, residual and y bf16; w and the statistics float32.  So y equals, bit
+ *      for bit, om_conv2d_bf16_forward(y_is_f32 = 1), then om_bn_act_forward(training=0) on that tensor with the residual widened,
+ *      then the rounding to bf16.  Refusals as om_conv2d_frozen_forward's (null pointers, y aliasing x, w or the residual, the
+ *      geometry, eps <= 0): OM_EINVAL and nothing is written. */
+int om_conv2d_bf16_frozen_forward(const uint16_t* x, const float* w, int B, int cin, int H, int W, int cout, int ksize, int stride,
+                                  const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                                  double eps, float slope, const uint16_t* residual, uint16_t* y, om_stream stream);
+
 /* ---- The training models' plumbing between the convolutions (model/orienmask_yolo_fpnplus.py:74-90, model/orienmask_yolo.py:71-86:
  *      F.interpolate(mode='nearest'), torch.cat and torch.split, with autograd's backward of the three; orienmask_amd.train's
  *      upsample_concat / split_channels, the models with route_backend='hip').  All tensors fp32 NCHW contiguous: y, dy

@@ -57,17 +57,7 @@ struct FwdArgs {
     float slope;
 };
 
-// the frozen block's output for one element: fwd_apply's expressions (bn_act.hip, built with -ffp-contract=off) on the double sum.
-// This file is built with contraction on, and z * slope + res must stay a rounded product and a rounded sum: the pragma takes the
-// contract flag off the operations written in this function (the __dmul_rn / __dadd_rn intrinsics are plain operators in the
-// toolchain's header, which a later inlining pass could still fuse); bn_z's only fused operation is its explicit fma.
-__device__ __forceinline__ float frozen_out(double h, const BnAffine& ch, double slope, bool has_res, float res) {
-#pragma clang fp contract(off)
-    const double z = bn_z(h, ch);
-    double y = z > 0.0 ? z : z * slope;
-    if (has_res) y = y + (double)res;
-    return (float)y;                                        // the only rounding to float32
-}
+// (the frozen block's output for one element is bn_channel.h's frozen_out, shared with conv_fwd_bf16.hip)
 
 // TN blocks of 32 output channels per wave (every wave takes the tile's whole co range and 32 of its pixels)
 template <int TN, int KS, int S, int EPI>
@@ -113,13 +103,9 @@ __global__ void __launch_bounds__(CF_THREADS) conv_fwd_kernel(const FwdArgs a) {
     if constexpr (EPI == EPI_FROZEN) {
         if (tid < NT) {
             const int co = co0 + tid;
-            BnChannel ch = {};
-            if (co < a.cout) {
-                float invstd_hi, invstd_lo;
-                split_hi_lo(1.0 / sqrt((double)a.running_var[co] + a.eps), invstd_hi, invstd_lo);
-                ch = bn_channel(a.running_mean[co], 0.f, invstd_hi, invstd_lo, a.gamma[co], a.beta[co]);
-            }
-            s_ch[tid] = BnAffine{ch.mean, ch.w, ch.beta};
+            BnAffine ch = {};
+            if (co < a.cout) ch = bn_affine_eval(a.running_mean[co], a.running_var[co], a.eps, a.gamma[co], a.beta[co]);
+            s_ch[tid] = ch;
         }
     }
 

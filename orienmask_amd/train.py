@@ -30,13 +30,17 @@ And the reference's model in training mode: ``builder.build(config["model"], ori
                                (csrc/conv_grad.hip); the models use it with conv_backend='hip'.  With forward='hip' the forward
                                is om_conv2d_forward (csrc/conv_fwd.hip) too; the models pass it with conv_forward='hip'
 
+  conv2d_bf16                  the bf16 forward: om_conv2d_bf16_forward (csrc/conv_fwd_bf16.hip) on a bf16 x and the float32 master
+                               weight, bf16 or float32 out; the backward is torch's bf16 gradient (conv2d_bf16_backward).  The
+                               models use it with amp='bf16', conv_forward='hip'
+
 The forward convolution is torch's with conv_forward='torch' (the default) and om_conv2d_forward with conv_forward='hip', which
-needs conv_backend='hip'.  Its gradients are torch's with conv_backend='torch' (the default) and the HIP kernels of
-csrc/conv_grad.hip with conv_backend='hip'.
+needs conv_backend='hip' -- or, under amp='bf16', om_conv2d_bf16_forward with conv_backend='torch'.  Its gradients are torch's with
+conv_backend='torch' (the default) and the HIP kernels of csrc/conv_grad.hip with conv_backend='hip' (float32 only).
 
   conv_bn_leaky_frozen         a frozen block (the models' frozen_stages) as one kernel: the convolution with the fixed affine of the
-                               running statistics, LeakyReLU and the residual add in its epilogue (om_conv2d_frozen_forward); no
-                               autograd node, nothing saved
+                               running statistics, LeakyReLU and the residual add in its epilogue (om_conv2d_frozen_forward; on a
+                               bf16 x om_conv2d_bf16_frozen_forward); no autograd node, nothing saved
 
   upsample_concat              torch.cat of nearest-up-sampled tensors (the models' three cat sites) as om_route_concat_forward, with
                                om_route_concat_backward (csrc/route.hip) as its backward
@@ -49,7 +53,10 @@ Mixed precision: amp='bf16' on a model or a block (default None: float32 through
 torch.autocast(dtype=torch.bfloat16): torch's convolutions produce bf16, and bn_leaky, upsample_concat and split_channels take and
 return bf16 through the _bf16 entry points of csrc/bn_act.hip and csrc/route.hip (the saved x, dy and dx are bf16 too).  Parameters,
 their gradients, the BatchNorm statistics and buffers, the heads the model returns, the loss and the optimizer stay float32, so
-state_dicts move freely between amp and float32 models.  amp excludes conv_backend / conv_forward 'hip' (float32 operands only).
+state_dicts move freely between amp and float32 models.  With amp, conv_forward='hip' (and conv_backend='torch') makes every forward
+convolution this package's: conv2d_bf16 in the blocks and the heads (the heads float32 straight from the accumulators), the fused
+bf16 kernel in frozen blocks; the first layer's float32 image is cast to bf16 once, as autocast does.  The forward then repeats bit
+for bit without cudnn.deterministic.  amp excludes conv_backend='hip': the gradient kernels take float32 operands only.
 """
 import contextlib
 import ctypes
@@ -66,7 +73,7 @@ from .arch import DARKNET_STAGES, LEAKY_SLOPE, model_convs
 from .loss import DeviceEvalCounter, EvalCounter, OrienMaskYOLOMultiScaleLoss as _ValuesLoss
 
 __all__ = ["OrienMaskYOLOMultiScaleLoss", "EvalCounter", "DeviceEvalCounter", "ConvBNLeaky", "bn_leaky", "conv2d", "OrienMaskYOLOFPNPlus", "OrienMaskYOLO",
-           "convert_sync_batchnorm", "upsample_concat", "split_channels", "conv_bn_leaky_frozen"]
+           "convert_sync_batchnorm", "upsample_concat", "split_channels", "conv_bn_leaky_frozen", "conv2d_bf16"]
 
 BACKENDS = ("hip", "torch")
 CONV_BACKENDS = ("torch", "hip")
@@ -82,16 +89,19 @@ def _check_backends(backend, conv_backend, conv_forward, route_backend="torch", 
     """The option strings of a block and of a model (a block has no route_backend: the default passes)."""
     if amp not in AMP:
         raise ValueError("amp must be one of %s, got %r" % (AMP, amp))
-    if amp is not None and (conv_backend == "hip" or conv_forward == "hip"):
-        raise ValueError("amp %r needs torch's convolutions: conv_backend %r / conv_forward %r take float32 operands only"
-                         % (amp, conv_backend, conv_forward))
+    if amp is not None and conv_backend == "hip":
+        raise ValueError("amp %r with conv_backend 'hip' (conv_forward %r): the gradient kernels take float32 operands only.  With "
+                         "amp the available combinations are conv_backend 'torch' with conv_forward 'torch' (torch's bf16 "
+                         "convolutions) or conv_forward 'hip' (the bf16 forward kernel, torch's bf16 gradients)"
+                         % (amp, conv_forward))
     for name, value, known in (("backend", backend, BACKENDS), ("conv_backend", conv_backend, CONV_BACKENDS),
                                ("conv_forward", conv_forward, CONV_FORWARDS), ("route_backend", route_backend, ROUTE_BACKENDS)):
         if value not in known:
             raise ValueError("%s must be one of %s, got %r" % (name, known, value))
-    if conv_forward == "hip" and conv_backend != "hip":
-        raise ValueError("conv_forward 'hip' requires conv_backend 'hip', got conv_backend %r: torch's gradient node under the HIP "
-                         "forward is not supported" % (conv_backend,))
+    if conv_forward == "hip" and conv_backend != "hip" and amp is None:
+        raise ValueError("conv_forward 'hip' requires conv_backend 'hip' (float32) or amp 'bf16' with conv_backend 'torch' (the bf16 "
+                         "forward kernel), got conv_backend %r without amp: torch's gradient node under the float32 HIP forward is "
+                         "not supported" % (conv_backend,))
 
 
 class _LossBackward(torch.autograd.Function):
@@ -400,6 +410,71 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, forward="torch"):
     return _Conv2d.apply(x, weight, bias, s, forward == "hip")
 
 
+def _out_shape(x, cout, ks, s, p):
+    B, _, H, W = x.shape
+    return (B, cout, (H + 2 * p - ks) // s + 1, (W + 2 * p - ks) // s + 1)
+
+
+def conv2d_bf16_backward(dy, x, weight, stride, padding, has_bias, needs):
+    """The gradients of conv2d_bf16: torch's bf16 convolution gradient, aten.convolution_backward(dy, x, weight.to(bfloat16)), which
+    is what F.conv2d under torch.autocast(dtype=bfloat16) leaves behind its weight cast.  dy and x bf16, weight the float32 master
+    weight; `needs` = (x, weight, bias) as ctx.needs_input_grad gives them.  Returns (dx bf16, dw float32, db float32), None for a
+    gradient that is not needed (or a bias that does not exist): it is not computed.  Runs on CPU tensors too.  This is the one
+    place bf16 forms of om_conv2d_grad_input / om_conv2d_grad_weight will drop into."""
+    need_x, need_w, need_b = bool(needs[0]), bool(needs[1]), bool(has_bias and needs[2])
+    if not (need_x or need_w or need_b):
+        return None, None, None
+    cout = weight.shape[0]
+    dx, dw, db = torch.ops.aten.convolution_backward(dy, x, weight.to(torch.bfloat16), [cout] if has_bias else None, [stride, stride],
+                                                     [padding, padding], [1, 1], False, [0, 0], 1, [need_x, need_w, need_b])
+    return (dx if need_x else None, dw.float() if need_w else None, db.float() if need_b else None)
+
+
+class _Conv2dBf16(torch.autograd.Function):
+    """forward(ctx, x, weight, bias, stride, padding, f32_out) -> om_conv2d_bf16_forward (csrc/conv_fwd_bf16.hip) into a torch.empty
+    output of bf16 or float32.  Saved: x and the float32 weight (the kernel rounds it while staging; nothing else exists to save).
+    The backward is conv2d_bf16_backward on a bf16 dy (a float32 output's gradient is rounded to bf16 once, as autocast's cast node
+    does behind a .float())."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride, padding, f32_out):
+        ctx.save_for_backward(x, weight)
+        ctx.stride, ctx.padding, ctx.has_bias = stride, padding, bias is not None
+        cout, ks = int(weight.shape[0]), int(weight.shape[2])
+        B, cin, H, W = x.shape
+        y = torch.empty(_out_shape(x, cout, ks, stride, padding), dtype=torch.float32 if f32_out else torch.bfloat16, device=x.device)
+        _lib.launch("om_conv2d_bf16_forward", x.device, x, weight, bias, B, cin, H, W, cout, ks, stride, y, 1 if f32_out else 0)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        dy = dy.to(torch.bfloat16).contiguous()
+        return conv2d_bf16_backward(dy, x, weight, ctx.stride, ctx.padding, ctx.has_bias, ctx.needs_input_grad[:3]) + (None, None, None)
+
+
+def conv2d_bf16(x, weight, bias=None, stride=1, padding=0, out_dtype=torch.bfloat16):
+    """F.conv2d(x, weight.to(bfloat16), bias, stride, padding) with float32 accumulation as om_conv2d_bf16_forward
+    (csrc/conv_fwd_bf16.hip): x CUDA bf16 NCHW-contiguous, weight (contiguous [cout,cin,k,k]) and bias CUDA float32 -- the master
+    parameters, which the kernel rounds to bf16 (nearest even) while staging, as autocast's cast does; the geometries of conv2d.
+    out_dtype torch.bfloat16 (default) or torch.float32: both are the same float32 accumulators plus the bias, the bf16 output
+    rounded once.  Bit-identical from run to run and independent of the batch.  The backward is torch's bf16 gradient
+    (conv2d_bf16_backward): dx bf16, dw and db float32, only those that are needed.  Anything else raises: there is no fallback."""
+    if out_dtype not in ACT_DTYPES:
+        raise ValueError("out_dtype must be one of %s, got %r" % (ACT_DTYPES, out_dtype))
+    _require_nchw(x, "conv2d_bf16", "the convolution input (conv2d_bf16)", (torch.bfloat16,))
+    _lib.require_cuda_tensor(weight, "the convolution weight (conv2d_bf16)", torch.float32)
+    if bias is not None:
+        _lib.require_cuda_tensor(bias, "the convolution bias (conv2d_bf16)", torch.float32)
+    ks, s, p = _conv_geometry("conv2d_bf16", x, weight, stride, padding)
+    if bias is not None and (tuple(bias.shape) != (weight.shape[0],) or not bias.is_contiguous()):
+        raise _lib.OrienMaskHipError("conv2d_bf16: bias must be contiguous [%d], got %s" % (weight.shape[0], tuple(bias.shape)))
+    if weight.device != x.device or (bias is not None and bias.device != x.device):
+        raise _lib.OrienMaskHipError("conv2d_bf16: x on %s, weight on %s" % (x.device, weight.device))
+    return _Conv2dBf16.apply(x, weight, bias, s, p, out_dtype == torch.float32)
+
+
 def _require_no_grad(what, **tensors):
     """A frozen layer has no backward: under grad mode nothing it reads may require grad."""
     if not torch.is_grad_enabled():
@@ -415,10 +490,12 @@ def conv_bn_leaky_frozen(x, weight, bn, residual=None, stride=1, padding=0, slop
     leaky_relu(batch_norm(conv2d(x, weight), bn's running statistics), slope) + residual, where the convolution output is never
     stored.  x, weight and the geometries as conv2d; `bn` an nn.BatchNorm2d with affine parameters and running statistics, whose
     weight, bias, running_mean, running_var and eps are read (its mode is not asked: the running statistics are used, no buffer is
-    touched); residual None or NCHW-contiguous with the output's shape.  Returns a tensor without a grad_fn.  Under grad mode, x,
-    residual, the weight or bn's parameters requiring grad raise; so does anything else that is off: there is no fallback."""
+    touched); residual None or NCHW-contiguous with the output's shape.  x (and the residual) float32, or both bf16: then the kernel
+    is om_conv2d_bf16_frozen_forward (csrc/conv_fwd_bf16.hip), the weight and bn stay float32 and the output is bf16; a mixed pair
+    raises.  Returns a tensor without a grad_fn.  Under grad mode, x, residual, the weight or bn's parameters requiring grad raise;
+    so does anything else that is off: there is no fallback."""
     what = "conv_bn_leaky_frozen"
-    _require_nchw(x, what, "the frozen block's input")
+    _require_nchw(x, what, "the frozen block's input", ACT_DTYPES)
     _lib.require_cuda_tensor(weight, "the frozen block's convolution weight", torch.float32)
     ks, s, p = _conv_geometry(what, x, weight, stride, padding)
     cout = int(weight.shape[0])
@@ -434,13 +511,14 @@ def conv_bn_leaky_frozen(x, weight, bn, residual=None, stride=1, padding=0, slop
     if weight.device != x.device:
         raise _lib.OrienMaskHipError("%s: weight on %s, x on %s" % (what, weight.device, x.device))
     B, cin, H, W = x.shape
-    shape = (B, cout, (H + 2 * p - ks) // s + 1, (W + 2 * p - ks) // s + 1)
-    _require_residual(residual, shape, x.device)
+    shape = _out_shape(x, cout, ks, s, p)
+    _require_residual(residual, shape, x.device, x.dtype)
     _require_no_grad(what, x=x, residual=residual, weight=weight, **{"bn.weight": bn.weight, "bn.bias": bn.bias})
     dev = x.device
-    y = torch.empty(shape, dtype=torch.float32, device=dev)
-    _lib.launch("om_conv2d_frozen_forward", dev, x, weight, B, cin, H, W, cout, ks, s, bn.weight, bn.bias, bn.running_mean,
-                bn.running_var, float(bn.eps), float(slope), residual, y)
+    y = torch.empty(shape, dtype=x.dtype, device=dev)
+    entry = "om_conv2d_bf16_frozen_forward" if x.dtype == torch.bfloat16 else "om_conv2d_frozen_forward"
+    _lib.launch(entry, dev, x, weight, B, cin, H, W, cout, ks, s, bn.weight, bn.bias, bn.running_mean, bn.running_var, float(bn.eps),
+                float(slope), residual, y)
     return y
 
 
@@ -634,6 +712,12 @@ def bn_leaky(x, bn, residual=None, slope=LEAKY_SLOPE, sync=False, process_group=
     return _BNAct.apply(x, bn.weight, bn.bias, residual, bn, slope)
 
 
+def _as_bf16(x):
+    """The bf16 forward's input: a float32 tensor (the first layer's image) is cast once, as autocast casts it in front of a
+    convolution; a bf16 tensor passes."""
+    return x.to(torch.bfloat16) if x.dtype == torch.float32 else x
+
+
 def _same_type(residual, y):
     """The residual of a backend-'torch' block, refused where torch's add would promote it or the block's output silently."""
     if residual.dtype != y.dtype:
@@ -655,8 +739,9 @@ class ConvBNLeaky(nn.Module):
     conv_backend 'torch' (default): the convolution is F.conv2d with torch's gradients.  conv_backend 'hip': the same forward
     through conv2d, whose gradients are the HIP kernels of csrc/conv_grad.hip; CUDA float32 NCHW-contiguous tensors only.
 
-    conv_forward 'torch' (default): the forward convolution is F.conv2d.  conv_forward 'hip' (needs conv_backend 'hip'): it is
-    om_conv2d_forward (csrc/conv_fwd.hip).
+    conv_forward 'torch' (default): the forward convolution is F.conv2d.  conv_forward 'hip': without amp (needs conv_backend
+    'hip') it is om_conv2d_forward (csrc/conv_fwd.hip); with amp 'bf16' (needs conv_backend 'torch') it is conv2d_bf16
+    (csrc/conv_fwd_bf16.hip), whose gradients are torch's bf16 ones.
 
     frozen=True: the block's three parameters have requires_grad False; its BatchNorm normalises with the running statistics in
     every mode, never touches a buffer, stays in eval mode across train() calls and is left alone by convert_sync_batchnorm.  No
@@ -668,8 +753,9 @@ class ConvBNLeaky(nn.Module):
     amp None (default): float32.  amp 'bf16': the forward runs under torch.autocast(dtype=torch.bfloat16), so the convolution is
     torch's in bf16 and the output is bf16: from the _bf16 kernels with backend 'hip' (a frozen block: their eval phase), from
     torch's own bf16 batch_norm and leaky_relu with backend 'torch' (the comparator; CPU tensors too).  The parameters, their
-    gradients and the buffers stay float32.  A residual must have the block's element type.  Needs conv_backend and conv_forward
-    'torch'."""
+    gradients and the buffers stay float32.  A residual must have the block's element type.  Needs conv_backend 'torch'.  With
+    conv_forward 'hip' the convolution is conv2d_bf16 on the float32 master weight (a float32 x is cast to bf16 once, as autocast
+    does), and a frozen block with backend 'hip' is the one bf16 kernel of conv_bn_leaky_frozen."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, backend="hip", conv_backend="torch",
                  conv_forward="torch", frozen=False, amp=None):
@@ -711,10 +797,15 @@ class ConvBNLeaky(nn.Module):
         if bn.running_mean is None or bn.running_var is None:
             raise ValueError("ConvBNLeaky: a frozen block needs the BatchNorm's running statistics")
         _require_no_grad("ConvBNLeaky(frozen=True)", x=x, residual=residual, **{n: p for n, p in self.named_parameters()})
+        if self.amp and self.conv_forward == "hip":
+            x = _as_bf16(x)
         if self.backend == "hip" and self.conv_forward == "hip":
             return conv_bn_leaky_frozen(x, conv.weight, bn, residual=residual, stride=conv.stride, padding=conv.padding,
                                         slope=act.negative_slope)
-        h = F.conv2d(x, conv.weight, None, conv.stride, conv.padding)
+        if self.amp and self.conv_forward == "hip":
+            h = conv2d_bf16(x, conv.weight, None, conv.stride, conv.padding)
+        else:
+            h = F.conv2d(x, conv.weight, None, conv.stride, conv.padding)
         if self.backend == "hip":
             return bn_leaky(h, bn, residual=residual, slope=act.negative_slope)
         y = F.batch_norm(h, bn.running_mean, bn.running_var, bn.weight, bn.bias, False, 0.0, bn.eps)
@@ -731,6 +822,8 @@ class ConvBNLeaky(nn.Module):
         conv, bn, act = self.conv_block[0], self.conv_block[1], self.conv_block[2]
         if self.conv_backend == "hip":
             h = conv2d(x, conv.weight, None, conv.stride, conv.padding, forward=self.conv_forward)
+        elif self.amp and self.conv_forward == "hip":
+            h = conv2d_bf16(_as_bf16(x), conv.weight, None, conv.stride, conv.padding)
         else:
             h = F.conv2d(x, conv.weight, None, conv.stride, conv.padding)
         _check_bn_batch(bn, h, self.sync and bn.training and _sync_world_size(self.process_group) > 1)
@@ -785,7 +878,7 @@ class OrienMaskYOLOFPNPlus(nn.Module):
     """The reference's OrienMaskYOLOFPNPlus (model/orienmask_yolo_fpnplus.py:9-90) for training: the same constructor arguments
     plus `backend` ('hip' / 'torch') and `conv_backend` ('torch' / 'hip': whose convolution gradients, see ConvBNLeaky; with 'hip'
     the plain head convolutions go through conv2d on the nn.Conv2d modules' parameters) and `conv_forward` ('torch' / 'hip': whose
-    forward convolution, for the blocks and the four head convolutions; 'hip' needs conv_backend 'hip') and `route_backend` ('torch'
+    forward convolution, for the blocks and the four head convolutions; 'hip' needs conv_backend 'hip', or amp 'bf16') and `route_backend` ('torch'
     / 'hip': whose up-sampling, cat and split between the convolutions: torch's ops, or upsample_concat and split_channels
     (csrc/route.hip), CUDA float32 tensors only; independent of the other three), the same state_dict keys and parameters() order as the reference and as
     orienmask_amd.model (checkpoints and optimizer state move in both directions), trainable parameters, and a forward that
@@ -798,7 +891,9 @@ class OrienMaskYOLOFPNPlus(nn.Module):
     order and the buffers are those of frozen_stages=0, which builds the model as before; independent of backbone_batchnorm_eval.
 
     amp (None / 'bf16', default None): mixed precision.  With 'bf16' the forward runs under torch.autocast(dtype=torch.bfloat16):
-    every convolution is torch's in bf16 (conv_backend / conv_forward 'hip' raise), the activations between them are bf16 through
+    every convolution is torch's in bf16 (conv_backend 'hip' raises) or, with conv_forward 'hip', this package's: conv2d_bf16 in the
+    unfrozen blocks, one fused bf16 kernel per frozen block (backend 'hip'), and the four head convolutions as conv2d_bf16 with a
+    float32 output; the first layer's image is cast to bf16 once.  The activations between them are bf16 through
     the blocks (ConvBNLeaky) and, with route_backend 'hip', through upsample_concat; the head convolutions' outputs are returned
     as float32, so the loss, the counters and the optimizer see what they see without amp.  Parameters, gradients, buffers and
     the state_dict (keys and dtypes) are those of amp=None: checkpoints move freely between the two and to the inference model."""
@@ -918,6 +1013,8 @@ class OrienMaskYOLOFPNPlus(nn.Module):
         m = self._by_name[name]
         if self.conv_backend == "hip":
             return conv2d(x, m.weight, m.bias, m.stride, m.padding, forward=self.conv_forward)
+        if self.amp and self.conv_forward == "hip":      # float32 straight from the accumulators: no .float() pass
+            return conv2d_bf16(_as_bf16(x), m.weight, m.bias, m.stride, m.padding, out_dtype=torch.float32)
         return m(x).float() if self.amp else m(x)        # the heads leave the model as float32
 
     def _bbox_head(self, s, x):

@@ -18,7 +18,15 @@ interleaved rounds; the geometries where the fused kernel is slower by more than
 geometry in its necks, where nothing can be frozen), and the two frozen columns' sums over layers are weighted by it.
 --only-frozen times these two on the backbone's geometries and nothing else.
 
-    python tools/bench_conv_fwd.py [--batches 8 32] [--rounds 5] [--inner 3] [--warmup 2] [--only-frozen] [--out profiles/conv_fwd_bench.json]
+--dtype bf16 times the bf16 forward instead (csrc/conv_fwd_bf16.hip, what amp='bf16' with conv_forward='hip' enqueues), per
+geometry and in the same interleaved rounds: om_conv2d_bf16_forward on a bf16 x and the float32 master weight, bf16 out (hip_bf16),
+against F.conv2d on bf16 tensors (MIOpen: torch_bf16) and om_conv2d_forward on the float32 tensors (hip_f32); and on the backbone's
+geometries om_conv2d_bf16_frozen_forward (hip_bf16_frozen) against torch's bf16 convolution followed by om_bn_act_forward_bf16 in
+eval mode (torch_bf16_conv_bn: what a frozen block runs under amp with conv_forward='torch').  No training step (that is
+tools/bench_train_step.py --amp bf16 --conv-forward hip).  Default --out: profiles/conv_fwd_bf16_bench.json.
+
+    python tools/bench_conv_fwd.py [--batches 8 32] [--rounds 5] [--inner 3] [--warmup 2] [--only-frozen] [--dtype {f32,bf16}]
+                                   [--out profiles/conv_fwd_bench.json]
 
 prints one JSON line (and writes it to --out); a progress line per geometry goes to stderr.
 """
@@ -38,6 +46,7 @@ import torch.nn.functional as F  # noqa: E402
 
 from orienmask_amd import arch, lib as omlib, train  # noqa: E402
 
+BACKBONE_COLUMNS = ("hip_frozen", "hip_fwd_bn", "hip_bf16_frozen", "torch_bf16_conv_bn")   # summed over the backbone's layers
 STEP_CONFIGS = (("torch", "torch"), ("hip", "torch"), ("hip", "hip"))      # (conv_backend, conv_forward)
 
 
@@ -94,7 +103,29 @@ def bench_geometry(dev, B, key, args, frozen=None):
         "torch_fwd": lambda: F.conv2d(x, w, None, stride, pad),
         "hip_dx": lambda: omlib.check(L.om_conv2d_grad_input(vp(dy), vp(w), *geom, vp(dx), None, 0, st), "dx"),
     }
-    if frozen is not None:
+    if args.dtype == "bf16":
+        xb, wb, yb = x.to(torch.bfloat16), w.to(torch.bfloat16), torch.empty_like(dy, dtype=torch.bfloat16)
+        calls = {
+            "hip_bf16": lambda: omlib.check(L.om_conv2d_bf16_forward(vp(xb), vp(w), None, *geom, vp(yb), 0, st), "bf16 fwd"),
+            "torch_bf16": lambda: F.conv2d(xb, wb, None, stride, pad),
+            "hip_f32": calls["hip_fwd"],
+        }
+        if frozen is not None:
+            gamma, beta, mean = (torch.randn(cout, device=dev, generator=gen) for _ in range(3))
+            var = torch.rand(cout, device=dev, generator=gen) + 0.5
+            res = torch.randn(B, cout, Ho, Wo, device=dev, generator=gen).to(torch.bfloat16) if frozen else None
+            save = torch.empty(4 * cout, device=dev)
+            rp = vp(res) if frozen else None
+
+            def torch_conv_bn():
+                h = F.conv2d(xb, wb, None, stride, pad)
+                omlib.check(L.om_bn_act_forward_bf16(vp(h), B, cout, Ho, Wo, vp(gamma), vp(beta), vp(mean), vp(var), None, 0, 0.1, 1e-5,
+                                                     0.1, rp, vp(yb), save.data_ptr(), save.data_ptr() + 8 * cout, None, 0, st), "bn")
+
+            calls["hip_bf16_frozen"] = lambda: omlib.check(L.om_conv2d_bf16_frozen_forward(
+                vp(xb), vp(w), *geom, vp(gamma), vp(beta), vp(mean), vp(var), 1e-5, 0.1, rp, vp(yb), st), "bf16 frozen")
+            calls["torch_bf16_conv_bn"] = torch_conv_bn
+    elif frozen is not None:
         gamma, beta, mean = (torch.randn(cout, device=dev, generator=gen) for _ in range(3))
         var = torch.rand(cout, device=dev, generator=gen) + 0.5
         res = torch.randn(B, cout, Ho, Wo, device=dev, generator=gen) if frozen else None
@@ -170,8 +201,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--step-batch", type=int, default=8)
     ap.add_argument("--only-frozen", action="store_true", help="only the frozen column, on the backbone's geometries")
+    ap.add_argument("--dtype", choices=["f32", "bf16"], default="f32", help="bf16: the bf16 forward's columns (see above)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    bf16 = args.dtype == "bf16"
+    if bf16 and args.only_frozen:
+        raise SystemExit("--only-frozen is a float32 column")
+    if bf16 and args.out is None:
+        args.out = os.path.join(REPO, "profiles", "conv_fwd_bf16_bench.json")
     if not torch.cuda.is_available():
         raise SystemExit("bench_conv_fwd.py needs an MI355X: there is nothing to time on a CPU")
     dev = torch.device("cuda:0")
@@ -179,7 +216,7 @@ def main():
     backbone = backbone_table(args.size)
     if args.only_frozen:
         table = {k: backbone[k][0] for k in table if k in backbone}
-    result = {"bench": "conv_fwd", "size": args.size, "rounds": args.rounds, "inner": args.inner, "warmup": args.warmup,
+    result = {"bench": "conv_fwd_bf16" if bf16 else "conv_fwd", "size": args.size, "rounds": args.rounds, "inner": args.inner, "warmup": args.warmup,
               "device": torch.cuda.get_device_name(0), "torch": torch.__version__, "batches": {}}
     for B in args.batches:
         rows, sums = [], {}
@@ -192,21 +229,34 @@ def main():
             for k, v in r.items():
                 s = sums.setdefault(k, {"ms_median": 0.0, "ms_min": 0.0, "ms_max": 0.0})
                 for f in s:
-                    s[f] += (backbone[key][0] if k in ("hip_frozen", "hip_fwd_bn") else count) * v[f]
+                    s[f] += (backbone[key][0] if k in BACKBONE_COLUMNS else count) * v[f]
             torch.cuda.empty_cache()
         slower = [dict(zip(("cin", "cout", "ksize", "stride", "H"), (r["cin"], r["cout"], r["ksize"], r["stride"], r["H"])),
                        hip_ms=r["hip_fwd"]["ms_median"], torch_ms=r["torch_fwd"]["ms_median"], hip_dx_ms=r["hip_dx"]["ms_median"])
-                  for r in rows if not args.only_frozen and r["hip_fwd"]["ms_median"] > r["torch_fwd"]["ms_median"]]
+                  for r in rows if not args.only_frozen and not bf16 and r["hip_fwd"]["ms_median"] > r["torch_fwd"]["ms_median"]]
         # slower by more than the rounds' own spread: the fused kernel's fastest round is above the two kernels' slowest
         fused_slower = [dict(zip(("cin", "cout", "ksize", "stride", "H"), (r["cin"], r["cout"], r["ksize"], r["stride"], r["H"])),
                              frozen_ms=r["hip_frozen"], two_kernels_ms=r["hip_fwd_bn"])
                         for r in rows if "hip_frozen" in r and r["hip_frozen"]["ms_min"] > r["hip_fwd_bn"]["ms_max"]]
+        if bf16:
+            geo = lambda r: "%dx%d s%d %d->%d @%d" % (r["ksize"], r["ksize"], r["stride"], r["cin"], r["cout"], r["H"])      # noqa: E731
+            for r in rows:
+                r["hip_bf16_over_torch_bf16"] = round(r["hip_bf16"]["ms_median"] / r["torch_bf16"]["ms_median"], 3)
+                r["hip_bf16_over_hip_f32"] = round(r["hip_bf16"]["ms_median"] / r["hip_f32"]["ms_median"], 3)
+            result["batches"][str(B)] = {"geometries": rows, "layers": sum(table.values()),
+                                         "backbone_layers": sum(n for n, _ in backbone.values()),
+                                         "sum_over_layers_ms": {k: {f: round(x, 4) for f, x in v.items()} for k, v in sums.items()},
+                                         "geometries_where_bf16_is_not_faster_than_the_f32_kernel":
+                                             [geo(r) for r in rows if r["hip_bf16"]["ms_median"] >= r["hip_f32"]["ms_median"]],
+                                         "geometries_where_bf16_is_slower_than_torch_bf16":
+                                             [geo(r) for r in rows if r["hip_bf16"]["ms_median"] > r["torch_bf16"]["ms_median"]]}
+            continue
         result["batches"][str(B)] = {"geometries": rows, "layers": sum(table.values()),
                                      "backbone_layers": sum(n for n, _ in backbone.values()),
                                      "sum_over_layers_ms": {k: {f: round(x, 4) for f, x in v.items()} for k, v in sums.items()},
                                      "geometries_where_hip_is_slower": slower,
                                      "geometries_where_the_fused_frozen_kernel_is_slower_beyond_spread": fused_slower}
-    if not args.only_frozen:
+    if not args.only_frozen and not bf16:
         result["training_step"] = step_times_and_memory(dev, args.step_batch, args.size, args.rounds)
     line = json.dumps(result)
     print(line)

@@ -1,7 +1,8 @@
 """Steps per second of the training loop, sync-free against the reference's per-step host bookkeeping, on the same build.
 
     python tools/bench_train_step.py [--batch 8] [--size 544] [--steps 30] [--warmup 5] [--rounds 3] [--frozen-stages K]
-                                     [--default-backends] [--amp bf16] [--out profiles/train_step_bench.json]
+                                     [--default-backends] [--amp bf16] [--conv-forward {torch,hip}]
+                                     [--out profiles/train_step_bench.json]
 
 Both loops are orienmask_amd.trainer.Trainer._train_epoch over the same SyntheticLossLoader batches (made once, on the device),
 the trainable OrienMaskYOLOFPNPlus with every HIP backend, the HIP SGD step, accumulate 1 and log_freq = steps, so the sync-free
@@ -15,6 +16,11 @@ dict as it was); --default-backends leaves the four backend options at the model
 --amp bf16 compares precisions instead of loops: both loops are sync-free and use the model's default backends (amp needs torch's
 convolutions), one with the float32 model ("fp32") and one with amp='bf16' ("amp_bf16"), in the same alternating rounds; each
 loop's peak device memory is that of its own timed epochs (both models stay resident, so subtract nothing: compare the two).
+
+--amp bf16 --conv-forward hip compares the forward convolutions under amp instead: both loops are sync-free amp='bf16' models with
+the default backends, one with torch's bf16 convolutions ("amp_bf16_conv_torch") and one with conv_forward='hip'
+("amp_bf16_conv_hip": csrc/conv_fwd_bf16.hip, frozen stages one fused kernel per layer), in the same alternating rounds; default
+--out profiles/train_step_amp_conv_bench.json.
 """
 import argparse
 import json
@@ -39,8 +45,15 @@ def main(argv=None):
     ap.add_argument("--frozen-stages", type=int, default=0, help="freeze backbone.conv1 ... conv{K} (0: none)")
     ap.add_argument("--default-backends", action="store_true", help="the model's default backends instead of every HIP backend")
     ap.add_argument("--amp", choices=["bf16"], default=None, help="time the float32 model against amp (see above)")
+    ap.add_argument("--conv-forward", choices=["torch", "hip"], default="torch",
+                    help="with --amp: 'hip' times amp with torch's convolutions against amp with conv_forward='hip' (see above)")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     args = ap.parse_args(argv)
+    conv_ab = args.conv_forward == "hip"
+    if conv_ab and not args.amp:
+        raise SystemExit("--conv-forward hip compares the forward convolutions under amp: add --amp bf16")
+    if conv_ab and args.out is None:
+        args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "train_step_amp_conv_bench.json")
 
     import torch
     from orienmask_amd import builder
@@ -72,7 +85,10 @@ def main(argv=None):
 
     warm, timed = loader(args.warmup), loader(args.steps)
     trainers = {}
-    if args.amp:
+    if conv_ab:
+        loops = (("amp_%s_conv_torch" % args.amp, True, dict(amp=args.amp)),
+                 ("amp_%s_conv_hip" % args.amp, True, dict(amp=args.amp, conv_forward="hip")))
+    elif args.amp:
         loops = (("fp32", True, {}), ("amp_" + args.amp, True, dict(amp=args.amp)))
     else:
         loops = (("sync_free", True, {}), ("host_loop", False, {}))
@@ -99,7 +115,7 @@ def main(argv=None):
     shutil.rmtree(log_dir, ignore_errors=True)          # the trainers' run directories: nothing in them is a result
     out = dict(bench="train_step", batch=args.batch, size=s, steps=args.steps, warmup=args.warmup, rounds=args.rounds,
                device=torch.cuda.get_device_name(0), torch=torch.__version__, frozen_stages=args.frozen_stages,
-               backends="default" if args.default_backends or args.amp else "hip", amp=args.amp,
+               backends="default" if args.default_backends or args.amp else "hip", amp=args.amp, conv_forward=args.conv_forward,
                peak_bytes=max(peaks.values()))
     for name, r in rates.items():
         out[name] = dict(steps_per_s_median=round(statistics.median(r), 3), steps_per_s_min=round(min(r), 3),
@@ -108,7 +124,7 @@ def main(argv=None):
         if args.amp:
             out[name]["peak_bytes"] = peaks[name]
     first, second = [n for n, _, _ in loops]
-    # sync_free over host_loop; with --amp, amp over fp32
+    # sync_free over host_loop; with --amp, amp over fp32; with --conv-forward hip, conv_forward 'hip' over 'torch'
     out["ratio_of_medians"] = round(out[second if args.amp else first]["steps_per_s_median"]
                                     / out[first if args.amp else second]["steps_per_s_median"], 4)
     out["spread"] = round(max((max(r) - min(r)) / statistics.median(r) for r in rates.values()), 4)
