@@ -909,6 +909,36 @@ int om_conv2d_bf16_frozen_forward(const uint16_t* x, const float* w, int B, int 
                                   const float* gamma, const float* beta, const float* running_mean, const float* running_var,
                                   double eps, float slope, const uint16_t* residual, uint16_t* y, om_stream stream);
 
+/* ---- The gradients of om_conv2d_bf16_forward (orienmask_amd.train.conv2d_bf16 with backward='hip'; the models with amp='bf16',
+ *      conv_forward='hip', conv_grad='hip'; csrc/conv_grad_bf16.hip): dy [B,cout,Ho,Wo] and x [B,cin,H,W] bf16 (uint16_t bits), w
+ *      [cout,cin,ksize,ksize] the FLOAT32 master weight; dx [B,cin,H,W] float32 where dx_is_f32 != 0, bf16 otherwise; dw
+ *      [cout,cin,ksize,ksize] and dbias [cout] float32.  The geometries, layouts and size limits of om_conv2d_grad_*; H and W are
+ *      the INPUT's.  On v_mfma_f32_32x32x16_bf16.
+ *      Arithmetic: dy and x are widened exactly; every weight is rounded to bf16 (nearest, ties to even: csrc/bf16.h) while it is
+ *      staged, which is what the forward multiplied by -- no cast kernel, no bf16 copy.  Every product is exact in float32; all
+ *      accumulation is float32 or wider.
+ *      om_conv2d_bf16_grad_input: an element's sum is ONE float32 chain over the output channels (blocks of 16) and the taps that
+ *      reach the pixel, in an order that is a function of the geometry only -- not of B, the tile or the device -- so an image's dx
+ *      has the same bits alone and in any batch; the bf16 output is the rounding of the float32 one, bit for bit.  Stride 1 is the
+ *      forward kernel on dy with the weight read transposed and flipped; stride 2 takes the four parity classes of the input pixel
+ *      (1, 2, 2 and 4 taps, no product with an absent tap) and writes every element of dx.  Needs no workspace (the arguments are
+ *      accepted and ignored).  dx aliasing dy or w returns OM_EINVAL.
+ *      om_conv2d_bf16_grad_weight: dw = sum over b and the output pixels of dy * x, the pixels split over workgroups by
+ *      om_conv2d_grad_weight's rule (at most 2048 each; a function of the shape and the device's compute-unit count): a chain of
+ *      the matrix instruction holds 32 pixels, a workgroup sums its chains in float32 (at most 64), and with more than one split the
+ *      partial tiles go to `workspace` and a second kernel sums them in split order in double.  dbias = the sum of dy over b and the
+ *      plane in double, rounded once.  dw or dbias may be null (not computed); both null returns OM_EINVAL.  workspace:
+ *      om_conv2d_bf16_grad_workspace_bytes for the shape on the current device (0 where one split suffices or the geometry is
+ *      refused), undefined on entry; too small: OM_ENOMEM.
+ *      No alignment beyond the element's own is required.  Everything is enqueued on `stream`; no allocation, no host
+ *      synchronisation, no atomics, bit-identical from run to run.  A null dy / w / x / dx, another geometry or sizes outside the
+ *      limits return OM_EINVAL and nothing is written. */
+size_t om_conv2d_bf16_grad_workspace_bytes(int B, int cin, int H, int W, int cout, int ksize, int stride);
+int om_conv2d_bf16_grad_input(const uint16_t* dy, const float* w, int B, int cin, int H, int W, int cout, int ksize, int stride,
+                              void* dx, int dx_is_f32, void* workspace, size_t ws_bytes, om_stream stream);
+int om_conv2d_bf16_grad_weight(const uint16_t* x, const uint16_t* dy, int B, int cin, int H, int W, int cout, int ksize, int stride,
+                               float* dw, float* dbias, void* workspace, size_t ws_bytes, om_stream stream);
+
 /* ---- The training models' plumbing between the convolutions (model/orienmask_yolo_fpnplus.py:74-90, model/orienmask_yolo.py:71-86:
  *      F.interpolate(mode='nearest'), torch.cat and torch.split, with autograd's backward of the three; orienmask_amd.train's
  *      upsample_concat / split_channels, the models with route_backend='hip').  All tensors fp32 NCHW contiguous: y, dy

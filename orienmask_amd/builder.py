@@ -94,7 +94,7 @@ def build_optimizer(config, accumulate, model, is_distributed=False):
 
 def build_train_model(config, is_distributed=False, ignore_pretrained=False):
     """trainer/builder.py:80-88 against orienmask_amd.train: the model of config (a reference `model` dict, optionally with
-    `backend`, `conv_backend`, `conv_forward`, `route_backend`, `frozen_stages` and `amp`, which are passed on to the model class) on the current device, in training mode as a freshly built nn.Module is.  The caller's dict is not mutated.
+    `backend`, `conv_backend`, `conv_forward`, `route_backend`, `frozen_stages`, `amp` and `conv_grad`, which are passed on to the model class) on the current device, in training mode as a freshly built nn.Module is.  The caller's dict is not mutated.
     is_distributed=True is the reference's lines 85-87: the blocks are converted to synchronised batch statistics
     (train.convert_sync_batchnorm, the default process group) and the model is returned inside DistributedDataParallel on the
     current device.  It needs an initialised default process group and raises NotImplementedError without one."""

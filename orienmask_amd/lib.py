@@ -225,6 +225,9 @@ SIGNATURES = {
     "om_conv2d_bf16_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
     "om_conv2d_bf16_frozen_forward": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_double, _f, _vp, _vp,
                                            _vp]),
+    "om_conv2d_bf16_grad_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
+    "om_conv2d_bf16_grad_input": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _sz, _vp]),
+    "om_conv2d_bf16_grad_weight": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "om_route_concat_forward": (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i, _i, _i, _vp, _vp]),
     "om_route_concat_backward": (_i, [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i, _i, _i, ctypes.POINTER(_vp), _vp]),
 }

@@ -31,8 +31,9 @@ And the reference's model in training mode: ``builder.build(config["model"], ori
                                is om_conv2d_forward (csrc/conv_fwd.hip) too; the models pass it with conv_forward='hip'
 
   conv2d_bf16                  the bf16 forward: om_conv2d_bf16_forward (csrc/conv_fwd_bf16.hip) on a bf16 x and the float32 master
-                               weight, bf16 or float32 out; the backward is torch's bf16 gradient (conv2d_bf16_backward).  The
-                               models use it with amp='bf16', conv_forward='hip'
+                               weight, bf16 or float32 out; the backward is conv2d_bf16_backward: torch's bf16 gradient, or with
+                               backward='hip' om_conv2d_bf16_grad_input / om_conv2d_bf16_grad_weight (csrc/conv_grad_bf16.hip).
+                               The models use it with amp='bf16', conv_forward='hip' (and conv_grad='hip' for the latter)
 
 The forward convolution is torch's with conv_forward='torch' (the default) and om_conv2d_forward with conv_forward='hip', which
 needs conv_backend='hip' -- or, under amp='bf16', om_conv2d_bf16_forward with conv_backend='torch'.  Its gradients are torch's with
@@ -56,7 +57,10 @@ their gradients, the BatchNorm statistics and buffers, the heads the model retur
 state_dicts move freely between amp and float32 models.  With amp, conv_forward='hip' (and conv_backend='torch') makes every forward
 convolution this package's: conv2d_bf16 in the blocks and the heads (the heads float32 straight from the accumulators), the fused
 bf16 kernel in frozen blocks; the first layer's float32 image is cast to bf16 once, as autocast does.  The forward then repeats bit
-for bit without cudnn.deterministic.  amp excludes conv_backend='hip': the gradient kernels take float32 operands only.
+for bit without cudnn.deterministic.  amp excludes conv_backend='hip': the float32 gradient kernels take float32 operands only.
+conv_grad='hip' (default 'torch'; needs amp='bf16', conv_forward='hip', conv_backend='torch') makes the gradients of those
+convolutions the bf16 kernels of csrc/conv_grad_bf16.hip: every convolution node of a step is then this package's, and a whole
+trainer step repeats bit for bit without cudnn.deterministic, as the float32 path (conv_backend='hip', conv_forward='hip') does.
 """
 import contextlib
 import ctypes
@@ -78,6 +82,7 @@ __all__ = ["OrienMaskYOLOMultiScaleLoss", "EvalCounter", "DeviceEvalCounter", "C
 BACKENDS = ("hip", "torch")
 CONV_BACKENDS = ("torch", "hip")
 CONV_FORWARDS = ("torch", "hip")
+CONV_GRADS = ("torch", "hip")
 ROUTE_BACKENDS = ("torch", "hip")
 ROUTE_SCALES = (1, 2, 4, 8)
 ROUTE_MAX = 4
@@ -85,23 +90,28 @@ AMP = (None, "bf16")
 ACT_DTYPES = (torch.float32, torch.bfloat16)       # what the BatchNorm block and the routes take
 
 
-def _check_backends(backend, conv_backend, conv_forward, route_backend="torch", amp=None):
-    """The option strings of a block and of a model (a block has no route_backend: the default passes)."""
+def _check_backends(backend, conv_backend, conv_forward, route_backend="torch", amp=None, conv_grad="torch"):
+    """The option strings of a block and of a model (a block has no route_backend: the default passes).  conv_grad is a key of its
+    own, not a meaning of conv_backend 'hip' under amp, because that combination is pinned to raise."""
     if amp not in AMP:
         raise ValueError("amp must be one of %s, got %r" % (AMP, amp))
     if amp is not None and conv_backend == "hip":
         raise ValueError("amp %r with conv_backend 'hip' (conv_forward %r): the gradient kernels take float32 operands only.  With "
                          "amp the available combinations are conv_backend 'torch' with conv_forward 'torch' (torch's bf16 "
-                         "convolutions) or conv_forward 'hip' (the bf16 forward kernel, torch's bf16 gradients)"
-                         % (amp, conv_forward))
+                         "convolutions) or conv_forward 'hip' (the bf16 forward kernel, torch's bf16 gradients; with conv_grad "
+                         "'hip' the bf16 gradient kernels)" % (amp, conv_forward))
     for name, value, known in (("backend", backend, BACKENDS), ("conv_backend", conv_backend, CONV_BACKENDS),
-                               ("conv_forward", conv_forward, CONV_FORWARDS), ("route_backend", route_backend, ROUTE_BACKENDS)):
+                               ("conv_forward", conv_forward, CONV_FORWARDS), ("route_backend", route_backend, ROUTE_BACKENDS),
+                               ("conv_grad", conv_grad, CONV_GRADS)):
         if value not in known:
             raise ValueError("%s must be one of %s, got %r" % (name, known, value))
     if conv_forward == "hip" and conv_backend != "hip" and amp is None:
         raise ValueError("conv_forward 'hip' requires conv_backend 'hip' (float32) or amp 'bf16' with conv_backend 'torch' (the bf16 "
                          "forward kernel), got conv_backend %r without amp: torch's gradient node under the float32 HIP forward is "
                          "not supported" % (conv_backend,))
+    if conv_grad == "hip" and not (amp == "bf16" and conv_forward == "hip" and conv_backend == "torch"):
+        raise ValueError("conv_grad 'hip' (the bf16 gradient kernels) requires amp 'bf16' with conv_forward 'hip' and conv_backend "
+                         "'torch', got amp %r, conv_forward %r, conv_backend %r" % (amp, conv_forward, conv_backend))
 
 
 class _LossBackward(torch.autograd.Function):
@@ -415,31 +425,60 @@ def _out_shape(x, cout, ks, s, p):
     return (B, cout, (H + 2 * p - ks) // s + 1, (W + 2 * p - ks) // s + 1)
 
 
-def conv2d_bf16_backward(dy, x, weight, stride, padding, has_bias, needs):
-    """The gradients of conv2d_bf16: torch's bf16 convolution gradient, aten.convolution_backward(dy, x, weight.to(bfloat16)), which
-    is what F.conv2d under torch.autocast(dtype=bfloat16) leaves behind its weight cast.  dy and x bf16, weight the float32 master
-    weight; `needs` = (x, weight, bias) as ctx.needs_input_grad gives them.  Returns (dx bf16, dw float32, db float32), None for a
-    gradient that is not needed (or a bias that does not exist): it is not computed.  Runs on CPU tensors too.  This is the one
-    place bf16 forms of om_conv2d_grad_input / om_conv2d_grad_weight will drop into."""
+def conv2d_bf16_backward(dy, x, weight, stride, padding, has_bias, needs, backend="torch"):
+    """The gradients of conv2d_bf16.  dy and x bf16, weight the float32 master weight; `needs` = (x, weight, bias) as
+    ctx.needs_input_grad gives them.  Returns (dx bf16, dw float32, db float32), None for a gradient that is not needed (or a bias
+    that does not exist): it is not computed.
+    backend 'torch' (default): torch's bf16 convolution gradient, aten.convolution_backward(dy, x, weight.to(bfloat16)), which is
+    what F.conv2d under torch.autocast(dtype=bfloat16) leaves behind its weight cast.  Runs on CPU tensors too.
+    backend 'hip': om_conv2d_bf16_grad_input / om_conv2d_bf16_grad_weight (csrc/conv_grad_bf16.hip) on the current stream, into
+    torch.empty outputs, with the grow-only workspace of the device and stream; CUDA NCHW-contiguous tensors only.  The weight is
+    rounded to bf16 inside the kernel, as the forward rounds it; the same bits on every run."""
+    if backend not in CONV_GRADS:
+        raise ValueError("backend must be one of %s, got %r" % (CONV_GRADS, backend))
     need_x, need_w, need_b = bool(needs[0]), bool(needs[1]), bool(has_bias and needs[2])
     if not (need_x or need_w or need_b):
         return None, None, None
     cout = weight.shape[0]
+    if backend == "hip":
+        _require_nchw(dy, "conv2d_bf16_backward", "the output gradient (conv2d_bf16_backward)", (torch.bfloat16,))
+        _require_nchw(x, "conv2d_bf16_backward", "the convolution input (conv2d_bf16_backward)", (torch.bfloat16,))
+        _lib.require_cuda_tensor(weight, "the convolution weight (conv2d_bf16_backward)", torch.float32)
+        ks, s, p = _conv_geometry("conv2d_bf16_backward", x, weight, stride, padding)
+        dev = x.device
+        if dy.dtype != torch.bfloat16 or x.dtype != torch.bfloat16 or tuple(dy.shape) != _out_shape(x, cout, ks, s, p) \
+                or dy.device != dev or weight.device != dev:
+            raise _lib.OrienMaskHipError("conv2d_bf16_backward: dy %s %s on %s for x %s %s on %s, weight %s on %s"
+                                         % (tuple(dy.shape), dy.dtype, dy.device, tuple(x.shape), x.dtype, dev, tuple(weight.shape),
+                                            weight.device))
+        B, cin, H, W = x.shape
+        dx = torch.empty_like(x) if need_x else None
+        dw = torch.empty_like(weight) if need_w else None
+        db = torch.empty(cout, dtype=torch.float32, device=dev) if need_b else None
+        stream = _lib.current_stream_ptr(dev)
+        geom = (B, cin, H, W, cout, ks, s)
+        with _lib.on_device(dev):
+            ws = _workspace(dev, stream, _lib.load().om_conv2d_bf16_grad_workspace_bytes(*geom))
+            if need_x:
+                _lib.launch("om_conv2d_bf16_grad_input", dev, dy, weight, *geom, dx, 0, ws, ws.numel(), stream=stream)
+            if need_w or need_b:
+                _lib.launch("om_conv2d_bf16_grad_weight", dev, x, dy, *geom, dw, db, ws, ws.numel(), stream=stream)
+        return dx, dw, db
     dx, dw, db = torch.ops.aten.convolution_backward(dy, x, weight.to(torch.bfloat16), [cout] if has_bias else None, [stride, stride],
                                                      [padding, padding], [1, 1], False, [0, 0], 1, [need_x, need_w, need_b])
     return (dx if need_x else None, dw.float() if need_w else None, db.float() if need_b else None)
 
 
 class _Conv2dBf16(torch.autograd.Function):
-    """forward(ctx, x, weight, bias, stride, padding, f32_out) -> om_conv2d_bf16_forward (csrc/conv_fwd_bf16.hip) into a torch.empty
-    output of bf16 or float32.  Saved: x and the float32 weight (the kernel rounds it while staging; nothing else exists to save).
-    The backward is conv2d_bf16_backward on a bf16 dy (a float32 output's gradient is rounded to bf16 once, as autocast's cast node
-    does behind a .float())."""
+    """forward(ctx, x, weight, bias, stride, padding, f32_out, backward) -> om_conv2d_bf16_forward (csrc/conv_fwd_bf16.hip) into a
+    torch.empty output of bf16 or float32.  Saved: x and the float32 weight (the kernel rounds it while staging; nothing else exists
+    to save).  The backward is conv2d_bf16_backward (backend `backward`) on a bf16 dy (a float32 output's gradient is rounded to bf16 once, as
+    autocast's cast node does behind a .float())."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, stride, padding, f32_out):
+    def forward(ctx, x, weight, bias, stride, padding, f32_out, backward="torch"):
         ctx.save_for_backward(x, weight)
-        ctx.stride, ctx.padding, ctx.has_bias = stride, padding, bias is not None
+        ctx.stride, ctx.padding, ctx.has_bias, ctx.backward_backend = stride, padding, bias is not None, backward
         cout, ks = int(weight.shape[0]), int(weight.shape[2])
         B, cin, H, W = x.shape
         y = torch.empty(_out_shape(x, cout, ks, stride, padding), dtype=torch.float32 if f32_out else torch.bfloat16, device=x.device)
@@ -451,16 +490,24 @@ class _Conv2dBf16(torch.autograd.Function):
     def backward(ctx, dy):
         x, weight = ctx.saved_tensors
         dy = dy.to(torch.bfloat16).contiguous()
-        return conv2d_bf16_backward(dy, x, weight, ctx.stride, ctx.padding, ctx.has_bias, ctx.needs_input_grad[:3]) + (None, None, None)
+        if ctx.backward_backend == "torch":         # positional only: unchanged for callers that wrap the function with (*args)
+            grads = conv2d_bf16_backward(dy, x, weight, ctx.stride, ctx.padding, ctx.has_bias, ctx.needs_input_grad[:3])
+        else:
+            grads = conv2d_bf16_backward(dy, x, weight, ctx.stride, ctx.padding, ctx.has_bias, ctx.needs_input_grad[:3],
+                                         backend=ctx.backward_backend)
+        return grads + (None, None, None, None)
 
 
-def conv2d_bf16(x, weight, bias=None, stride=1, padding=0, out_dtype=torch.bfloat16):
+def conv2d_bf16(x, weight, bias=None, stride=1, padding=0, out_dtype=torch.bfloat16, backward="torch"):
     """F.conv2d(x, weight.to(bfloat16), bias, stride, padding) with float32 accumulation as om_conv2d_bf16_forward
     (csrc/conv_fwd_bf16.hip): x CUDA bf16 NCHW-contiguous, weight (contiguous [cout,cin,k,k]) and bias CUDA float32 -- the master
     parameters, which the kernel rounds to bf16 (nearest even) while staging, as autocast's cast does; the geometries of conv2d.
     out_dtype torch.bfloat16 (default) or torch.float32: both are the same float32 accumulators plus the bias, the bf16 output
-    rounded once.  Bit-identical from run to run and independent of the batch.  The backward is torch's bf16 gradient
-    (conv2d_bf16_backward): dx bf16, dw and db float32, only those that are needed.  Anything else raises: there is no fallback."""
+    rounded once.  Bit-identical from run to run and independent of the batch.  The backward is conv2d_bf16_backward with backend
+    `backward`: 'torch' (default) torch's bf16 gradient, 'hip' the kernels of csrc/conv_grad_bf16.hip (bit-identical from run to
+    run); dx bf16, dw and db float32, only those that are needed.  Anything else raises: there is no fallback."""
+    if backward not in CONV_GRADS:
+        raise ValueError("backward must be one of %s, got %r" % (CONV_GRADS, backward))
     if out_dtype not in ACT_DTYPES:
         raise ValueError("out_dtype must be one of %s, got %r" % (ACT_DTYPES, out_dtype))
     _require_nchw(x, "conv2d_bf16", "the convolution input (conv2d_bf16)", (torch.bfloat16,))
@@ -472,7 +519,7 @@ def conv2d_bf16(x, weight, bias=None, stride=1, padding=0, out_dtype=torch.bfloa
         raise _lib.OrienMaskHipError("conv2d_bf16: bias must be contiguous [%d], got %s" % (weight.shape[0], tuple(bias.shape)))
     if weight.device != x.device or (bias is not None and bias.device != x.device):
         raise _lib.OrienMaskHipError("conv2d_bf16: x on %s, weight on %s" % (x.device, weight.device))
-    return _Conv2dBf16.apply(x, weight, bias, s, p, out_dtype == torch.float32)
+    return _Conv2dBf16.apply(x, weight, bias, s, p, out_dtype == torch.float32, backward)
 
 
 def _require_no_grad(what, **tensors):
@@ -755,13 +802,18 @@ class ConvBNLeaky(nn.Module):
     torch's own bf16 batch_norm and leaky_relu with backend 'torch' (the comparator; CPU tensors too).  The parameters, their
     gradients and the buffers stay float32.  A residual must have the block's element type.  Needs conv_backend 'torch'.  With
     conv_forward 'hip' the convolution is conv2d_bf16 on the float32 master weight (a float32 x is cast to bf16 once, as autocast
-    does), and a frozen block with backend 'hip' is the one bf16 kernel of conv_bn_leaky_frozen."""
+    does), and a frozen block with backend 'hip' is the one bf16 kernel of conv_bn_leaky_frozen.
+
+    conv_grad 'torch' (default): conv2d_bf16's gradients are torch's bf16 ones.  conv_grad 'hip' (needs amp 'bf16', conv_forward
+    'hip', conv_backend 'torch'): they are om_conv2d_bf16_grad_input / om_conv2d_bf16_grad_weight (csrc/conv_grad_bf16.hip).  A key
+    of its own because amp with conv_backend 'hip' is pinned to raise.  A frozen block has no backward and ignores it."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, backend="hip", conv_backend="torch",
-                 conv_forward="torch", frozen=False, amp=None):
+                 conv_forward="torch", frozen=False, amp=None, conv_grad="torch"):
         super().__init__()
-        _check_backends(backend, conv_backend, conv_forward, amp=amp)
+        _check_backends(backend, conv_backend, conv_forward, amp=amp, conv_grad=conv_grad)
         self.amp = amp
+        self.conv_grad = conv_grad
         self.backend = backend
         self.conv_backend = conv_backend
         self.conv_forward = conv_forward
@@ -823,7 +875,7 @@ class ConvBNLeaky(nn.Module):
         if self.conv_backend == "hip":
             h = conv2d(x, conv.weight, None, conv.stride, conv.padding, forward=self.conv_forward)
         elif self.amp and self.conv_forward == "hip":
-            h = conv2d_bf16(_as_bf16(x), conv.weight, None, conv.stride, conv.padding)
+            h = conv2d_bf16(_as_bf16(x), conv.weight, None, conv.stride, conv.padding, backward=self.conv_grad)
         else:
             h = F.conv2d(x, conv.weight, None, conv.stride, conv.padding)
         _check_bn_batch(bn, h, self.sync and bn.training and _sync_world_size(self.process_group) > 1)
@@ -896,10 +948,16 @@ class OrienMaskYOLOFPNPlus(nn.Module):
     float32 output; the first layer's image is cast to bf16 once.  The activations between them are bf16 through
     the blocks (ConvBNLeaky) and, with route_backend 'hip', through upsample_concat; the head convolutions' outputs are returned
     as float32, so the loss, the counters and the optimizer see what they see without amp.  Parameters, gradients, buffers and
-    the state_dict (keys and dtypes) are those of amp=None: checkpoints move freely between the two and to the inference model."""
+    the state_dict (keys and dtypes) are those of amp=None: checkpoints move freely between the two and to the inference model.
+
+    conv_grad ('torch' / 'hip', default 'torch'): whose gradients behind conv2d_bf16, in the blocks and the four head convolutions.
+    'hip' needs amp 'bf16', conv_forward 'hip' and conv_backend 'torch' and makes them the bf16 kernels of csrc/conv_grad_bf16.hip:
+    every convolution node of a step is then this package's and a step repeats bit for bit without cudnn.deterministic.  (A key
+    of its own, because amp with conv_backend 'hip' is pinned to raise.)  Module tree, keys, parameter order and dtypes are unchanged."""
 
     def __init__(self, num_anchors, num_classes, pretrained=None, freeze_backbone=False, backbone_batchnorm_eval=False,
-                 backend="hip", conv_backend="torch", conv_forward="torch", route_backend="torch", frozen_stages=0, amp=None):
+                 backend="hip", conv_backend="torch", conv_forward="torch", route_backend="torch", frozen_stages=0, amp=None,
+                 conv_grad="torch"):
         super().__init__()
         if freeze_backbone is not False:
             # the reference's DarkNet53._freeze_network calls self._freeze_module, which does not exist (darknet.py:31-38)
@@ -908,8 +966,9 @@ class OrienMaskYOLOFPNPlus(nn.Module):
         if isinstance(frozen_stages, bool) or not isinstance(frozen_stages, int) or not 0 <= frozen_stages <= len(DARKNET_STAGES) + 1:
             raise ValueError("frozen_stages must be an int from 0 to %d (the number of backbone stages conv1 ... conv%d to freeze), "
                              "got %r" % (len(DARKNET_STAGES) + 1, len(DARKNET_STAGES) + 1, frozen_stages))
-        _check_backends(backend, conv_backend, conv_forward, route_backend, amp)
+        _check_backends(backend, conv_backend, conv_forward, route_backend, amp, conv_grad)
         self.amp = amp
+        self.conv_grad = conv_grad
         self.num_anchors = num_anchors
         self.num_classes = num_classes
         self.pretrained = pretrained
@@ -935,7 +994,7 @@ class OrienMaskYOLOFPNPlus(nn.Module):
                 # backbone.conv{i}[...]: frozen where i <= frozen_stages
                 frozen = spec.name.startswith("backbone.conv") and int(spec.name.split(".")[1][len("conv"):]) <= frozen_stages
                 m = ConvBNLeaky(spec.cin, spec.cout, spec.ksize, stride=spec.stride, padding=pad, backend=backend,
-                                conv_backend=conv_backend, conv_forward=conv_forward, frozen=frozen, amp=amp)
+                                conv_backend=conv_backend, conv_forward=conv_forward, frozen=frozen, amp=amp, conv_grad=conv_grad)
             else:
                 m = nn.Conv2d(spec.cin, spec.cout, spec.ksize, stride=spec.stride, padding=pad)
             node.add_module(leaf, m)
@@ -1014,7 +1073,7 @@ class OrienMaskYOLOFPNPlus(nn.Module):
         if self.conv_backend == "hip":
             return conv2d(x, m.weight, m.bias, m.stride, m.padding, forward=self.conv_forward)
         if self.amp and self.conv_forward == "hip":      # float32 straight from the accumulators: no .float() pass
-            return conv2d_bf16(_as_bf16(x), m.weight, m.bias, m.stride, m.padding, out_dtype=torch.float32)
+            return conv2d_bf16(_as_bf16(x), m.weight, m.bias, m.stride, m.padding, out_dtype=torch.float32, backward=self.conv_grad)
         return m(x).float() if self.amp else m(x)        # the heads leave the model as float32
 
     def _bbox_head(self, s, x):

@@ -11,8 +11,16 @@ geometries where 'hip' is slower, and one whole-model training step (forward + b
 memory for conv_backend 'hip' and 'torch'.
 
     python tools/bench_conv_grad.py [--batches 8 32] [--rounds 5] [--inner 3] [--warmup 2] [--out profiles/conv_grad_bench.json]
+                                    [--dtype {f32,bf16}]
 
 prints one JSON line (and writes it to --out); a progress line per geometry goes to stderr.
+
+--dtype bf16 times the bf16 gradients instead (csrc/conv_grad_bf16.hip, what amp='bf16' with conv_forward='hip', conv_grad='hip'
+enqueues), per geometry and in the same interleaved rounds: om_conv2d_bf16_grad_input (bf16 dx) and om_conv2d_bf16_grad_weight on
+bf16 dy and x and the float32 master weight (hip_bf16), aten.convolution_backward on bf16 tensors with one output selected
+(torch_bf16: what conv_grad='torch' runs), and om_conv2d_grad_* on the float32 tensors (hip_f32).  Reported besides: the geometries
+where hip_bf16 is slower than torch_bf16, and those where it is slower than hip_f32.  No whole-model step (that is
+tools/bench_train_step.py --amp bf16 --conv-forward hip --conv-grad hip).  Default --out: profiles/conv_grad_bf16_bench.json.
 """
 import argparse
 import ctypes
@@ -78,6 +86,23 @@ def bench_geometry(dev, B, key, args):
         ("hip", "dw"): lambda: omlib.check(L.om_conv2d_grad_weight(vp(x), vp(dy), *geom, vp(dw), None, vp(ws), ws.numel(), st), "dw"),
         ("torch", "dw"): lambda: torch_grad([False, True, False]),
     }
+    if args.dtype == "bf16":
+        xb, dyb, wb, dxb = x.to(torch.bfloat16), dy.to(torch.bfloat16), w.to(torch.bfloat16), torch.empty_like(x, dtype=torch.bfloat16)
+        wsb = torch.empty(max(L.om_conv2d_bf16_grad_workspace_bytes(*geom), 16), dtype=torch.uint8, device=dev)
+
+        def torch_bf16(mask):
+            return conv_bwd(dyb, xb, wb, None, [stride, stride], [pad, pad], [1, 1], False, [0, 0], 1, mask)
+
+        calls = {
+            ("hip_bf16", "dx"): lambda: omlib.check(L.om_conv2d_bf16_grad_input(vp(dyb), vp(w), *geom, vp(dxb), 0, vp(wsb), wsb.numel(),
+                                                                                st), "bf16 dx"),
+            ("torch_bf16", "dx"): lambda: torch_bf16([True, False, False]),
+            ("hip_f32", "dx"): calls[("hip", "dx")],
+            ("hip_bf16", "dw"): lambda: omlib.check(L.om_conv2d_bf16_grad_weight(vp(xb), vp(dyb), *geom, vp(dw), None, vp(wsb), wsb.numel(),
+                                                                                 st), "bf16 dw"),
+            ("torch_bf16", "dw"): lambda: torch_bf16([False, True, False]),
+            ("hip_f32", "dw"): calls[("hip", "dw")],
+        }
     for fn in calls.values():
         for _ in range(args.warmup):
             fn()
@@ -136,12 +161,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--step-batch", type=int, default=8)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--dtype", choices=["f32", "bf16"], default="f32")
     args = ap.parse_args()
+    bf16 = args.dtype == "bf16"
+    if bf16 and args.out is None:
+        args.out = os.path.join(REPO, "profiles", "conv_grad_bf16_bench.json")
     if not torch.cuda.is_available():
         raise SystemExit("bench_conv_grad.py needs an MI355X: there is nothing to time on a CPU")
     dev = torch.device("cuda:0")
     table = layer_table(args.size)
-    result = {"bench": "conv_grad", "size": args.size, "rounds": args.rounds, "inner": args.inner, "warmup": args.warmup,
+    result = {"bench": "conv_grad_bf16" if bf16 else "conv_grad", "size": args.size, "rounds": args.rounds, "inner": args.inner,
+              "warmup": args.warmup,
               "device": torch.cuda.get_device_name(0), "torch": torch.__version__, "batches": {}}
     for B in args.batches:
         rows, sums = [], {}
@@ -154,13 +184,24 @@ def main():
                 for f in s:
                     s[f] += (count_dx if k.endswith("dx") else count) * v[f]
             torch.cuda.empty_cache()
+        def slower_than(mine, other):
+            return [dict(zip(("cin", "cout", "ksize", "stride", "H"), (r["cin"], r["cout"], r["ksize"], r["stride"], r["H"])), gradient=g,
+                         **{mine + "_ms": r["%s_%s" % (mine, g)]["ms_median"], other + "_ms": r["%s_%s" % (other, g)]["ms_median"]})
+                    for r in rows for g in ("dx", "dw") if r["%s_%s" % (mine, g)]["ms_median"] > r["%s_%s" % (other, g)]["ms_median"]]
+        if bf16:
+            result["batches"][str(B)] = {"geometries": rows, "layers": sum(c for c, _ in table.values()),
+                                         "sum_over_layers_ms": {k: {f: round(x, 4) for f, x in v.items()} for k, v in sums.items()},
+                                         "geometries_where_hip_bf16_is_slower_than_torch_bf16": slower_than("hip_bf16", "torch_bf16"),
+                                         "geometries_where_hip_bf16_is_slower_than_hip_f32": slower_than("hip_bf16", "hip_f32")}
+            continue
         slower = [dict(zip(("cin", "cout", "ksize", "stride", "H"), (r["cin"], r["cout"], r["ksize"], r["stride"], r["H"])), gradient=g,
                        hip_ms=r["hip_" + g]["ms_median"], torch_ms=r["torch_" + g]["ms_median"])
                   for r in rows for g in ("dx", "dw") if r["hip_" + g]["ms_median"] > r["torch_" + g]["ms_median"]]
         result["batches"][str(B)] = {"geometries": rows, "layers": sum(c for c, _ in table.values()),
                                      "sum_over_layers_ms": {k: {f: round(x, 4) for f, x in v.items()} for k, v in sums.items()},
                                      "geometries_where_hip_is_slower": slower}
-    result["training_step"] = step_times_and_memory(dev, args.step_batch, args.size, args.rounds)
+    if not bf16:
+        result["training_step"] = step_times_and_memory(dev, args.step_batch, args.size, args.rounds)
     line = json.dumps(result)
     print(line)
     if args.out:

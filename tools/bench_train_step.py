@@ -1,7 +1,7 @@
 """Steps per second of the training loop, sync-free against the reference's per-step host bookkeeping, on the same build.
 
     python tools/bench_train_step.py [--batch 8] [--size 544] [--steps 30] [--warmup 5] [--rounds 3] [--frozen-stages K]
-                                     [--default-backends] [--amp bf16] [--conv-forward {torch,hip}]
+                                     [--default-backends] [--amp bf16] [--conv-forward {torch,hip}] [--conv-grad {torch,hip}]
                                      [--out profiles/train_step_bench.json]
 
 Both loops are orienmask_amd.trainer.Trainer._train_epoch over the same SyntheticLossLoader batches (made once, on the device),
@@ -21,6 +21,11 @@ loop's peak device memory is that of its own timed epochs (both models stay resi
 the default backends, one with torch's bf16 convolutions ("amp_bf16_conv_torch") and one with conv_forward='hip'
 ("amp_bf16_conv_hip": csrc/conv_fwd_bf16.hip, frozen stages one fused kernel per layer), in the same alternating rounds; default
 --out profiles/train_step_amp_conv_bench.json.
+
+--amp bf16 --conv-forward hip --conv-grad hip compares the convolution gradients behind that forward instead: both loops are
+sync-free amp='bf16', conv_forward='hip' models, one with torch's bf16 gradients ("amp_bf16_grad_torch") and one with
+conv_grad='hip' ("amp_bf16_grad_hip": csrc/conv_grad_bf16.hip), in the same alternating rounds; default --out
+profiles/train_step_amp_conv_grad_bench.json.
 """
 import argparse
 import json
@@ -47,9 +52,17 @@ def main(argv=None):
     ap.add_argument("--amp", choices=["bf16"], default=None, help="time the float32 model against amp (see above)")
     ap.add_argument("--conv-forward", choices=["torch", "hip"], default="torch",
                     help="with --amp: 'hip' times amp with torch's convolutions against amp with conv_forward='hip' (see above)")
+    ap.add_argument("--conv-grad", choices=["torch", "hip"], default="torch",
+                    help="with --amp and --conv-forward hip: 'hip' times conv_grad='torch' against conv_grad='hip' (see above)")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     args = ap.parse_args(argv)
     conv_ab = args.conv_forward == "hip"
+    grad_ab = args.conv_grad == "hip"
+    if grad_ab and not (args.amp and conv_ab):
+        raise SystemExit("--conv-grad hip compares the gradients behind the bf16 forward kernel: add --amp bf16 --conv-forward hip")
+    if grad_ab and args.out is None:
+        args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                "train_step_amp_conv_grad_bench.json")
     if conv_ab and not args.amp:
         raise SystemExit("--conv-forward hip compares the forward convolutions under amp: add --amp bf16")
     if conv_ab and args.out is None:
@@ -85,7 +98,10 @@ def main(argv=None):
 
     warm, timed = loader(args.warmup), loader(args.steps)
     trainers = {}
-    if conv_ab:
+    if grad_ab:
+        loops = (("amp_%s_grad_torch" % args.amp, True, dict(amp=args.amp, conv_forward="hip")),
+                 ("amp_%s_grad_hip" % args.amp, True, dict(amp=args.amp, conv_forward="hip", conv_grad="hip")))
+    elif conv_ab:
         loops = (("amp_%s_conv_torch" % args.amp, True, dict(amp=args.amp)),
                  ("amp_%s_conv_hip" % args.amp, True, dict(amp=args.amp, conv_forward="hip")))
     elif args.amp:
@@ -115,7 +131,7 @@ def main(argv=None):
     shutil.rmtree(log_dir, ignore_errors=True)          # the trainers' run directories: nothing in them is a result
     out = dict(bench="train_step", batch=args.batch, size=s, steps=args.steps, warmup=args.warmup, rounds=args.rounds,
                device=torch.cuda.get_device_name(0), torch=torch.__version__, frozen_stages=args.frozen_stages,
-               backends="default" if args.default_backends or args.amp else "hip", amp=args.amp, conv_forward=args.conv_forward,
+               backends="default" if args.default_backends or args.amp else "hip", amp=args.amp, conv_forward=args.conv_forward, conv_grad=args.conv_grad,
                peak_bytes=max(peaks.values()))
     for name, r in rates.items():
         out[name] = dict(steps_per_s_median=round(statistics.median(r), 3), steps_per_s_min=round(min(r), 3),

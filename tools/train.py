@@ -1,7 +1,7 @@
 """Train an OrienMask model on the MI355X: the reference's train.py against orienmask_amd.
 
     python tools/train.py --config CONFIG [--resume CHECKPOINT | --weights WEIGHTS] [--synthetic N] [--frozen-stages K] [--amp bf16]
-                          [--conv-forward {torch,hip}]
+                          [--conv-forward {torch,hip}] [--conv-grad {torch,hip}]
 
 CONFIG is a JSON file -- the ``config.json`` a trainer writes into its checkpoint directory is one -- or, where a ``config``
 package with the reference's ``get_config`` is importable, a config name.  ``--synthetic N`` trains on N seeded synthetic images
@@ -11,7 +11,9 @@ validation then.  ``--frozen-stages K`` (0...6) overrides the model's ``frozen_s
 under torch.autocast, float32 parameters, statistics, loss and optimizer (resuming a checkpoint that was trained with another ``amp``
 fails the trainer's model-config check, as any other change of the model does).  ``--conv-forward hip`` sets the model's
 ``conv_forward``: with ``--amp bf16`` every forward convolution is this package's bf16 kernel (csrc/conv_fwd_bf16.hip), frozen
-blocks one fused kernel each; without amp it needs the config's ``conv_backend`` to be 'hip'.  With several processes (torchrun), each uses the GPU of its LOCAL_RANK.
+blocks one fused kernel each; without amp it needs the config's ``conv_backend`` to be 'hip'.  ``--conv-grad hip`` sets the model's
+``conv_grad``: with ``--amp bf16 --conv-forward hip`` the gradients of those convolutions are this package's bf16 kernels too
+(csrc/conv_grad_bf16.hip), and a step repeats bit for bit.  With several processes (torchrun), each uses the GPU of its LOCAL_RANK.
 """
 import argparse
 import json
@@ -44,6 +46,9 @@ def parse_args(argv=None):
                     help="mixed precision: bf16 activations (the model's amp), overriding the config's model.amp")
     ap.add_argument("--conv-forward", choices=["torch", "hip"], default=None,
                     help="whose forward convolution (the model's conv_forward), overriding the config's model.conv_forward")
+    ap.add_argument("--conv-grad", choices=["torch", "hip"], default=None,
+                    help="whose bf16 convolution gradients under --amp bf16 --conv-forward hip (the model's conv_grad), overriding "
+                         "the config's model.conv_grad")
     args = ap.parse_args(argv)
     assert not (args.resume and args.weights), "--resume and --weights exclude each other"
     return args
@@ -57,6 +62,8 @@ def apply_overrides(config, args):
         config = dict(config, model=dict(config["model"], amp=args.amp))
     if args.conv_forward is not None:
         config = dict(config, model=dict(config["model"], conv_forward=args.conv_forward))
+    if args.conv_grad is not None:
+        config = dict(config, model=dict(config["model"], conv_grad=args.conv_grad))
     return config
 
 
