@@ -887,10 +887,12 @@ int om_conv2d_frozen_forward(const float* x, const float* w, int B, int cin, int
  *      index by 64 or 32 output channels, the whole k in one workgroup: no split, no workspace) on v_mfma_f32_32x32x16_bf16.
  *      Arithmetic: x is widened exactly; every weight is rounded to bf16 (nearest, ties to even: csrc/bf16.h, torch's
  *      .to(torch.bfloat16)) while it is staged -- no cast kernel, no bf16 copy.  Every product is exact in float32; an element's sum
- *      is ONE float32 chain in the matrix instruction's accumulators, 16 input channels of one tap per step, in the order input
- *      channels (blocks of 16) > kh > kw (at 1x1: input channels), channels beyond cin as zeros.  That order is a function of the
- *      geometry only -- not of the tile, the image index, B or the co tile width -- so an image's y has the same bits alone, in any
- *      batch and on every run.  y32 = sum + bias (one float32 add; none without a bias); the float32 output is y32, the bf16 output
+ *      has TWO float32 levels: a chain in the matrix instruction's accumulators, 16 input channels of one tap per step, holds one
+ *      block of input channels (16 at 3x3, in the order kh > kw: 144 products; 64 at 1x1), and the blocks' sums are added in block
+ *      order into a second float32 accumulator (one add per block; one block: the chain itself); channels beyond cin as zeros.
+ *      (One chain over the whole k was up to 4.6 x further from float64 than torch-CPU's float32 on in-network operands.)  That
+ *      order is a function of the geometry only -- not of the tile, the image index, B or the co tile width -- so an image's y has
+ *      the same bits alone, in any batch and on every run.  y32 = sum + bias (one float32 add; none without a bias); the float32 output is y32, the bf16 output
  *      its rounding to nearest even: bf16 y == rne(float32 y) bit for bit.
  *      No alignment beyond the element's own is required (a bf16 tensor may start at any uint16_t).  Enqueued on `stream`; no
  *      allocation, no host synchronisation, no atomics.  A null x / w / y, another geometry or sizes outside the limits return
@@ -917,8 +919,10 @@ int om_conv2d_bf16_frozen_forward(const uint16_t* x, const float* w, int B, int 
  *      Arithmetic: dy and x are widened exactly; every weight is rounded to bf16 (nearest, ties to even: csrc/bf16.h) while it is
  *      staged, which is what the forward multiplied by -- no cast kernel, no bf16 copy.  Every product is exact in float32; all
  *      accumulation is float32 or wider.
- *      om_conv2d_bf16_grad_input: an element's sum is ONE float32 chain over the output channels (blocks of 16) and the taps that
- *      reach the pixel, in an order that is a function of the geometry only -- not of B, the tile or the device -- so an image's dx
+ *      om_conv2d_bf16_grad_input: an element's sum has two float32 levels, as the forward's: a chain in the matrix instruction's
+ *      accumulators over a block of output channels (stride 1: 16 at 3x3, 64 at 1x1; stride 2: 64) and the taps that reach the
+ *      pixel, and the blocks' sums added in block order into a second float32 accumulator; an order that is a function of the
+ *      geometry only -- not of B, the tile or the device -- so an image's dx
  *      has the same bits alone and in any batch; the bf16 output is the rounding of the float32 one, bit for bit.  Stride 1 is the
  *      forward kernel on dy with the weight read transposed and flipped; stride 2 takes the four parity classes of the input pixel
  *      (1, 2, 2 and 4 taps, no product with an absent tap) and writes every element of dx.  Needs no workspace (the arguments are

@@ -86,9 +86,10 @@ __global__ void __launch_bounds__(CB_THREADS, 2) conv_bf16_kernel(const FwdBf16A
     const int ox = q % a.Wo;
     const bool ok0 = ox >= 1, ok2 = S == 2 || ox + 1 < a.Wo;
 
-    f32x16 acc[TN];
+    // two levels: the matrix instruction's chain holds one staged chunk (acc), the chunks are added in chunk order (tot)
+    f32x16 acc[TN], tot[TN];
 #pragma unroll
-    for (int n = 0; n < TN; ++n) clear16(acc[n]);
+    for (int n = 0; n < TN; ++n) { clear16(acc[n]); clear16(tot[n]); }
 
     uint4 px[NIX], pw[NIW];     // the chunk in flight, as it will lie in LDS
     auto load = [&](int ci0) {
@@ -174,6 +175,9 @@ __global__ void __launch_bounds__(CB_THREADS, 2) conv_bf16_kernel(const FwdBf16A
                 }
             }
         }
+        // the chunk's chain ends here: one float32 add per element into the second level (0 + acc is exact for the first chunk)
+#pragma unroll
+        for (int n = 0; n < TN; ++n) { tot[n] += acc[n]; clear16(acc[n]); }
         __syncthreads();        // the chunk is consumed: the next store may overwrite it
     }
     // D layout: column (pixel) = lane & 31, row (co) = 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3)
@@ -204,7 +208,7 @@ __global__ void __launch_bounds__(CB_THREADS, 2) conv_bf16_kernel(const FwdBf16A
                 const int cl = n * 32 + 8 * (r >> 2) + 4 * fk + (r & 3);
                 const BnAffine ch = s_ch[cl];
                 if (co0 + cl < a.cout)
-                    o[(size_t)(co0 + cl) * a.HoWo] = (bf16_t)bf16_round(frozen_out((double)acc[n][r], ch, slope, has_res, res[r]));
+                    o[(size_t)(co0 + cl) * a.HoWo] = (bf16_t)bf16_round(frozen_out((double)tot[n][r], ch, slope, has_res, res[r]));
             }
         }
     } else {
@@ -214,7 +218,7 @@ __global__ void __launch_bounds__(CB_THREADS, 2) conv_bf16_kernel(const FwdBf16A
             for (int r = 0; r < 16; ++r) {
                 const int co = co0 + n * 32 + 8 * (r >> 2) + 4 * fk + (r & 3);
                 if (co < a.cout) {
-                    float v = acc[n][r];
+                    float v = tot[n][r];
                     if (a.bias) v = v + a.bias[co];
                     const size_t at = base + (size_t)co * a.HoWo;
                     if (a.y_is_f32) static_cast<float*>(a.y)[at] = v;

@@ -21,16 +21,22 @@
 //       the chunk in LDS and written after the barrier that ends them (two barriers per chunk).
 //       INHERITED from conv_fwd.hip, knowingly: every wave reads the tile's whole weight block from LDS (a 2 x 2 wave grid would
 //       read (NT/2 + 64) rows per wave instead of (NT + 32): the same 96 at NT = 64).  NOT inherited: one wave per SIMD -- the
-//       kernel has no double level (32 accumulator registers at TN = 2), is held to 256 registers (__launch_bounds__(256, 2): 143
-//       to 256 are used, one spilled at 3x3 stride 2) and takes at most 51 KiB of LDS, so two workgroups share a CU.
+//       kernel has no double level (two float32 levels: 64 accumulator registers at TN = 2), is held to 256 registers
+//       (__launch_bounds__(256, 2): 154 to 256 are used, one spilled at 3x3 stride 2) and takes at most 51 KiB of LDS, so two
+//       workgroups share a CU.
 //       WHERE THE TIME GOES: in the staging, not in the matrix instructions.  Every global load moves one element
 //       per lane (128 bytes of x per wave instruction), as many load instructions per input channel as conv_fwd.hip issues.
-//       CHAIN: ONE float32 chain per output element over the whole k, in the matrix instruction's accumulators (k/16 steps; every
-//       product of two bf16 values is exact in float32).  No double level: the bound the tests hold (k * 2^-23 * S) is the chain's
-//       own, and a bf16 activation carries 2^-9 already.  Chunks in ci order, k-steps, kh, kw in order: the order for an element
-//       is a function of the geometry only, not of the tile, the image, B or TN.  k is never split; no workspace, no atomics.
-//   Epilogues         plain: y32 = acc + bias (one float32 add; none without a bias), stored as float32 or as bf16_round(y32).
-//       EPI_FROZEN: bn_channel.h's frozen_out on (double)acc with the bf16 residual widened, its float32 result through bf16_round:
+//       CHAIN: two float32 levels per output element.  The matrix instruction's accumulators hold the chain of ONE staged chunk (16
+//       input channels x 9 taps = 144 products at 3x3, 64 input channels at 1x1; every product of two bf16 values is exact in
+//       float32); where the chunk ends the chain is added into a second float32 accumulator and cleared, so the chunks' sums are
+//       added in ci order (a single chunk: 0 + chain, the chain itself).  One chain over the whole k held the tests' own bound
+//       (k * 2^-23 * S) but was up to 4.6 x further from float64 than torch-CPU's float32 on in-network operands, over the
+//       project's bar of 2 x in y and in the stride-1 dx of most 3x3 layers; a bf16 output hides that, the float32
+//       output and the frozen epilogue do not.  No double level.  Chunks in ci order, k-steps, kh, kw in order: the order for an
+//       element is a function of the geometry only, not of the tile, the image, B or TN.  k is never split; no workspace, no
+//       atomics.
+//   Epilogues         plain: y32 = sum + bias (one float32 add; none without a bias), stored as float32 or as bf16_round(y32).
+//       EPI_FROZEN: bn_channel.h's frozen_out on (double)sum with the bf16 residual widened, its float32 result through bf16_round:
 //       bit for bit om_bn_act_forward(training=0) on the float32 output of the plain entry, rounded to bf16.  The channel records
 //       (bn_affine_eval) are built once per channel and workgroup.
 // Every load and store is bounds-checked per element (any B, cin, cout, H, W >= 1); every global access is of one element (2 bytes

@@ -6,10 +6,13 @@
 //   dy and x are bf16 and are widened exactly.  w is rounded with bf16.h's bf16_round while it is staged: that is what the forward
 //   multiplied by, so the gradient is the gradient of the function that ran; there is no cast kernel and no bf16 copy of the weight.
 //   Every product of two bf16 values is exact in float32; all accumulation is float32 or wider.
-//   dx   the float32 output (dx_is_f32 = 1) is the sum, the bf16 output is bf16_round of the same sum.  ONE float32 chain per
-//        element in the matrix instruction's accumulators, over k = cout * (the taps that reach the pixel), in the order output
-//        channels (blocks of 16) > tap; that order is a function of the geometry only -- not of B, the tile or the device -- so an
-//        image's dx has the same bits alone and in any batch.
+//   dx   the float32 output (dx_is_f32 = 1) is the sum, the bf16 output is bf16_round of the same sum.  Two float32 levels per
+//        element over k = cout * (the taps that reach the pixel), in the order output channels (blocks of 16) > tap: a chain in the
+//        matrix instruction's accumulators holds a block of output channels (stride 1: a staged chunk of conv_bf16_tile.h, 16 at
+//        3x3 and 64 at 1x1; stride 2: CGB_DX2_FOLD = 64) and is then added into a second float32 accumulator and cleared.  (One
+//        chain over the whole k reached 4.3 x torch-CPU's error in the stride-2 dx of an in-network layer: DESIGN 3.30.)  The
+//        order is a function of the geometry only -- not of B, the tile or the device -- so an image's dx has the same bits alone
+//        and in any batch.
 //   dw   float32.  k is the flat output pixel (b, oy, ox), split over workgroups by conv_grad.hip's rule (a function of the shape and
 //        om::device_compute_units only).  Three levels: a matrix-instruction accumulator takes CGB_CHAIN_PIX = 32 pixels (two
 //        instructions; at 1x1 one instruction each in two accumulators that are then added), is added into a second float32
@@ -53,6 +56,7 @@ namespace om {
 
 constexpr int CGB_THREADS = 256;
 constexpr int CGB_MT = 128;             // dx stride 2: cells of a tile
+constexpr int CGB_DX2_FOLD = 64;        // dx stride 2: output channels of a first-level chain (four staged chunks of 16)
 constexpr int CGB_CHAIN_PIX = 32;       // dw: pixels of a first-level chain (two matrix instructions)
 constexpr int CGB_SPLIT_PIX = 2048;     // dw: most pixels of a workgroup: at most 64 first-level chains in its second-level sum
 constexpr int CGB_MIN_PIX = 256;        // dw: fewest pixels a split is cut down to when the launch would leave compute units idle
@@ -107,9 +111,10 @@ __global__ void __launch_bounds__(CGB_THREADS, 2) conv_dx2_bf16_kernel(const Dx2
         s_off[p] = off;
     }
 
-    f32x16 acc[TN];
+    // two levels: the matrix instruction's chain holds CGB_DX2_FOLD output channels (acc), the chains are added in order (tot)
+    f32x16 acc[TN], tot[TN];
 #pragma unroll
-    for (int n = 0; n < TN; ++n) clear16(acc[n]);
+    for (int n = 0; n < TN; ++n) { clear16(acc[n]); clear16(tot[n]); }
 
     uint4 px[NIX], pw[NIW];     // the chunk in flight, as it will lie in LDS
     auto load = [&](int co0) {
@@ -180,6 +185,11 @@ __global__ void __launch_bounds__(CGB_THREADS, 2) conv_dx2_bf16_kernel(const Dx2
             for (int n = 0; n < TN; ++n)
                 acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wp[n * 64]), bv, acc[n], 0, 0, 0);
         }
+        // a chain ends after CGB_DX2_FOLD output channels and at the last chunk: one float32 add per element into the second level
+        if ((co0 + 16) % CGB_DX2_FOLD == 0 || co0 + 16 >= a.cout) {
+#pragma unroll
+            for (int n = 0; n < TN; ++n) { tot[n] += acc[n]; clear16(acc[n]); }
+        }
         __syncthreads();        // the chunk is consumed: the next store may overwrite it
     }
     // D layout: column (cell) = lane & 31, row (ci) = 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3)
@@ -196,8 +206,8 @@ __global__ void __launch_bounds__(CGB_THREADS, 2) conv_dx2_bf16_kernel(const Dx2
             const int ci = ci0 + n * 32 + 8 * (r >> 2) + 4 * fk + (r & 3);
             if (ci < a.cin) {
                 const size_t at = base + (size_t)ci * hw;
-                if (a.dx_is_f32) static_cast<float*>(a.dx)[at] = acc[n][r];
-                else static_cast<bf16_t*>(a.dx)[at] = (bf16_t)bf16_round(acc[n][r]);
+                if (a.dx_is_f32) static_cast<float*>(a.dx)[at] = tot[n][r];
+                else static_cast<bf16_t*>(a.dx)[at] = (bf16_t)bf16_round(tot[n][r]);
             }
         }
 }
