@@ -768,6 +768,47 @@ typedef struct om_sgd_chunk {
 int om_sgd_step(const om_sgd_tensor* table_host, om_sgd_tensor* table, int n_tensors, const om_sgd_chunk* chunks, int n_chunks,
                 om_stream stream);
 
+/* ---- The same step behind global L2 gradient-norm clipping: torch.nn.utils.clip_grad_norm_(params, max_norm) followed by
+ *      SGD.step(), decided and applied on the device in THREE launches on `stream` (the table copy ahead of the first), without
+ *      atomics, allocation or host synchronisation; bit-identical from run to run.  table_host / table / chunks as om_sgd_step.
+ *        1. partials[c] = the float64 sum of g * g over chunk c (0 for a chunk of an OM_SGD_SKIP row).  Element j of a chunk belongs
+ *           to lane (j / 4) % 256 whatever the gradient's alignment; a lane adds its elements in ascending order; the 256 lanes
+ *           are summed by a fixed tree (lane l with l ^ 32, ^ 16, ... ^ 1 within a wave, then (w0 + w1) + (w2 + w3)).
+ *        2. one workgroup: lane l adds partials l, l + 256, ... in ascending order, the same tree gives S;
+ *               total_norm = (float)sqrt(S)
+ *               coef       = min(1, (1 / (total_norm + 1e-6f)) * max_norm)      (float32, each operation rounded once: torch
+ *                            2.10's `max_norm / (total_norm + 1e-6)` is reciprocal-then-multiply; a NaN stays a NaN)
+ *               skip       = (mode & OM_CLIP_SKIP_NONFINITE) && total_norm is not finite
+ *           and the state block is updated (below).
+ *        3. om_sgd_step's update with every gradient element read as g * coef (rounded once, ahead of OM_SGD_MAXIMIZE's negation
+ *           and of weight decay; the gradient in memory is NOT modified).  Under `skip` the launch returns without touching a
+ *           parameter or a momentum buffer.  A row flagged OM_SGD_DEVICE_FIRST decides "first step" on the device:
+ *           valid_since[tensor] is 0 until an update has been applied to the tensor, then the number of that step; the step is the
+ *           tensor's first (buf = d) when the word is 0 or equals `step`.  A skipped step so leaves "first" pending.
+ *      partials: n_chunks doubles, undefined on entry.  valid_since: n_tensors int64, zeroed by the caller once.  step: this call's
+ *      number, from 1, increasing.  state: OM_CLIP_STATE_DOUBLES 8-byte words, caller-owned, zeroed by the caller before the first
+ *      call: float64 at OM_CLIP_NORM_OFF / OM_CLIP_COEF_OFF (this call's total_norm and coef, float32 values), OM_CLIP_SUM_OFF and
+ *      OM_CLIP_MAX_OFF (sum and maximum of the finite norms); int64 at OM_CLIP_SKIP_OFF (this call's decision), OM_CLIP_STEPS_OFF
+ *      (calls), OM_CLIP_CLIPPED_OFF (finite norm and coef < 1), OM_CLIP_NONFINITE_OFF (norm not finite) and
+ *      OM_CLIP_FIRST_NONFINITE_OFF (the `step` of the first such call, latched as OM_COUNTER_STEP_OFF is: never overwritten).
+ *      The words from OM_CLIP_STEPS_OFF up to OM_CLIP_FIRST_NONFINITE_OFF may be zeroed by the caller between calls.
+ *      max_norm must be positive and finite. */
+#define OM_SGD_DEVICE_FIRST 64
+#define OM_CLIP_SKIP_NONFINITE 1
+#define OM_CLIP_NORM_OFF 0
+#define OM_CLIP_COEF_OFF 1
+#define OM_CLIP_SKIP_OFF 2
+#define OM_CLIP_STEPS_OFF 3
+#define OM_CLIP_SUM_OFF 4
+#define OM_CLIP_MAX_OFF 5
+#define OM_CLIP_CLIPPED_OFF 6
+#define OM_CLIP_NONFINITE_OFF 7
+#define OM_CLIP_FIRST_NONFINITE_OFF 8
+#define OM_CLIP_STATE_DOUBLES 9
+int om_sgd_clip_step(const om_sgd_tensor* table_host, om_sgd_tensor* table, int n_tensors, const om_sgd_chunk* chunks, int n_chunks,
+                     double* partials, double* state, long long* valid_since, float max_norm, int mode, long long step,
+                     om_stream stream);
+
 /* ---- The Conv -> BatchNorm2d -> LeakyReLU(0.1) block of the reference without its convolution (model/base.py:104-137,278-279: the
  *      nn.BatchNorm2d and nn.LeakyReLU of ConvBNRelu.conv_block), optionally with the residual add that closes a DarkNet block
  *      (model/backbone/darknet.py:14-15 `x + self.conv(x)`), for the training forward of trainer/trainer.py:47 and its backward (:52).

@@ -6,6 +6,18 @@
 //                     16-byte aligned, one element per lane otherwise (a view one element into a flat buffer) and for the last
 //                     n % 4 elements.  lr, weight_decay, momentum, dampening and the three pointers come from the tensor's row
 //                     of the DEVICE table: a scheduler step changes a row, never the launch.
+//   grad_sumsq_kernel   (clipping only) the same grid over the same chunk table: one float64 sum of squared gradient elements per
+//                     chunk into `partials`.  Element j of a chunk belongs to lane (j / 4) % 256 whatever the gradient's alignment
+//                     (16-byte loads where it is 16-byte aligned, 4-byte loads otherwise and for the last n % 4 elements); a lane
+//                     adds its elements in ascending order, the 256 lanes are combined by a fixed tree (block_tree_sum).  A float32
+//                     square is exact in float64, so the norm's bits depend on values and element counts alone.
+//   clip_finish_kernel  (clipping only) ONE workgroup: lane l adds partials l, l + 256, ... in ascending order, the same tree, then
+//                     total_norm = (float)sqrt(S), the coefficient min(1, (total_norm + 1e-6).reciprocal() * max_norm) in float32
+//                     with one rounding per operation (torch's clip_grad_norm_), the skip decision and the running statistics,
+//                     written into the state block with plain stores by lane 0.
+//   sgd_step_kernel<true>  reads coefficient and skip decision from the state block: every gradient element enters the update as
+//                     g * coef, rounded once; a skipped step returns before it touches a parameter.  No atomics anywhere: a step
+//                     repeats bit for bit.
 // Arithmetic: torch.optim.SGD's, in torch-CPU's float32 rounding: every x.add(y, alpha=a) of the update
 // is ONE fused multiply-add fma(y, float32(a), x); buf.mul_(momentum) is a product rounded on its own.  The fmas are written out
 // and the file is built with -ffp-contract=off, so the compiler neither splits them nor folds buf * momentum into the next one.
@@ -23,13 +35,22 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(1))) float gfloat;
 typedef __attribute__((address_space(1))) f32x4 gfloat4;
 
+// what the clipped form of the step reads beside the tables (unused by sgd_step_kernel<false>)
+struct SgdClip {
+    const double* state;        // the OM_CLIP_* block clip_finish_kernel wrote on this stream
+    long long* valid_since;     // per tensor: the step that first applied an update to an OM_SGD_DEVICE_FIRST row, 0 = none yet
+    long long step;             // this step's number (from 1)
+};
+
 struct SgdHyper {
     float neg_lr, wd, momentum, one_minus_damp;
     bool has_wd, has_mom, first, nesterov, maximize;
 };
 
 // one element of torch.optim.SGD's update; `buf` is read only when has_mom && !first, and is the value to store when has_mom
-__device__ __forceinline__ float sgd_element(const SgdHyper& h, float p, float g, float& buf) {
+template <bool CLIP>
+__device__ __forceinline__ float sgd_element(const SgdHyper& h, float coef, float p, float g, float& buf) {
+    if constexpr (CLIP) g = __fmul_rn(g, coef);             // the clipped gradient, rounded once, ahead of everything else
     float d = h.maximize ? -g : g;
     if (h.has_wd) d = fmaf(p, h.wd, d);
     if (h.has_mom) {
@@ -44,8 +65,98 @@ __device__ __forceinline__ float sgd_element(const SgdHyper& h, float p, float g
     return fmaf(d, h.neg_lr, p);
 }
 
+// the sum of one double per lane over the workgroup in a FIXED order: within a wave lane l takes l ^ 32, ^ 16, ... ^ 1 (after the
+// step with distance d, lanes l < d hold the sums of the pairs (l, l + d) of the step before), then (w0 + w1) + (w2 + w3) over the
+// four waves through LDS.  The result is valid in thread 0.  tests/clip_np.py restates this order.
+__device__ __forceinline__ double block_tree_sum(double v, double* wave_sums) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    __syncthreads();                                        // the previous use of wave_sums has been read
+    if ((threadIdx.x & 63) == 0) wave_sums[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (wave_sums[0] + wave_sums[1]) + (wave_sums[2] + wave_sums[3]);
+}
+static_assert(SGD_THREADS == 256, "block_tree_sum combines four waves of 64");
+
 __global__ void __launch_bounds__(SGD_THREADS)
-sgd_step_kernel(const om_sgd_tensor* __restrict__ tensors, int n_tensors, const om_sgd_chunk* __restrict__ chunks, int n_chunks) {
+grad_sumsq_kernel(const om_sgd_tensor* __restrict__ tensors, int n_tensors, const om_sgd_chunk* __restrict__ chunks, int n_chunks,
+                  double* __restrict__ partials) {
+    __shared__ double wave_sums[SGD_THREADS / 64];
+    for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {                 // c is the same for the whole workgroup
+        const om_sgd_chunk ck = chunks[c];
+        double acc = 0.0;
+        if ((unsigned)ck.tensor < (unsigned)n_tensors && ck.chunk >= 0) {
+            const om_sgd_tensor t = tensors[ck.tensor];
+            const long long n = t.n;
+            const long long start = (long long)ck.chunk * OM_SGD_CHUNK;
+            if (!(t.flags & OM_SGD_SKIP) && start < n) {
+                const gfloat* __restrict__ G = (const gfloat*)t.grad;
+                const long long stop = (start + OM_SGD_CHUNK < n) ? start + OM_SGD_CHUNK : n;
+                const bool aligned = (reinterpret_cast<uintptr_t>(t.grad) & 15) == 0;
+                const gfloat4* G4 = (const gfloat4*)G;
+                f32x4 g[SGD_VEC_PER_THREAD];
+                // group i of four elements [4 i, 4 i + 4) belongs to lane (i - start / 4) % 256 in both forms
+#pragma unroll
+                for (int k = 0; k < SGD_VEC_PER_THREAD; ++k) {
+                    const long long i = start / 4 + k * SGD_THREADS + threadIdx.x;
+                    if (aligned && 4 * i + 4 <= stop) {
+                        g[k] = G4[i];
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) g[k][e] = (4 * i + e < stop) ? G[4 * i + e] : 0.f;     // + 0.0 changes no sum
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < SGD_VEC_PER_THREAD; ++k)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const double x = (double)g[k][e];
+                        acc += x * x;                       // the square of a float32 is exact in float64
+                    }
+            }
+        }
+        const double total = block_tree_sum(acc, wave_sums);
+        if (threadIdx.x == 0) partials[c] = total;          // every chunk writes: a passed-over one writes 0
+    }
+}
+
+__global__ void __launch_bounds__(SGD_THREADS)
+clip_finish_kernel(const double* __restrict__ partials, int n_chunks, float max_norm, int mode, long long step,
+                   double* __restrict__ state) {
+    __shared__ double wave_sums[SGD_THREADS / 64];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n_chunks; i += SGD_THREADS) acc += partials[i];
+    const double S = block_tree_sum(acc, wave_sums);
+    if (threadIdx.x != 0) return;
+    const float norm = (float)__dsqrt_rn(S);
+    // torch: max_norm / (total_norm + 1e-6) is (total_norm + 1e-6).reciprocal() * max_norm, each operation rounded to float32
+    float coef = __fmul_rn(__fdiv_rn(1.0f, __fadd_rn(norm, 1e-6f)), max_norm);
+    if (coef > 1.0f) coef = 1.0f;                           // clamp(max=1): NaN stays NaN
+    const bool finite = isfinite(norm);
+    long long* words = reinterpret_cast<long long*>(state);
+    state[OM_CLIP_NORM_OFF] = (double)norm;
+    state[OM_CLIP_COEF_OFF] = (double)coef;
+    words[OM_CLIP_SKIP_OFF] = ((mode & OM_CLIP_SKIP_NONFINITE) && !finite) ? 1 : 0;
+    words[OM_CLIP_STEPS_OFF] += 1;
+    if (finite) {
+        state[OM_CLIP_SUM_OFF] += (double)norm;
+        if ((double)norm > state[OM_CLIP_MAX_OFF]) state[OM_CLIP_MAX_OFF] = (double)norm;
+        if (coef < 1.0f) words[OM_CLIP_CLIPPED_OFF] += 1;
+    } else {
+        words[OM_CLIP_NONFINITE_OFF] += 1;
+        if (words[OM_CLIP_FIRST_NONFINITE_OFF] == 0) words[OM_CLIP_FIRST_NONFINITE_OFF] = step;
+    }
+}
+
+template <bool CLIP>
+__global__ void __launch_bounds__(SGD_THREADS)
+sgd_step_kernel(const om_sgd_tensor* __restrict__ tensors, int n_tensors, const om_sgd_chunk* __restrict__ chunks, int n_chunks,
+                const SgdClip clip) {
+    float coef = 1.0f;
+    if constexpr (CLIP) {
+        if (reinterpret_cast<const long long*>(clip.state)[OM_CLIP_SKIP_OFF] != 0) return;      // nothing is touched
+        coef = (float)clip.state[OM_CLIP_COEF_OFF];
+    }
     for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {
         const om_sgd_chunk ck = chunks[c];
         if ((unsigned)ck.tensor >= (unsigned)n_tensors || ck.chunk < 0) continue;
@@ -57,6 +168,15 @@ sgd_step_kernel(const om_sgd_tensor* __restrict__ tensors, int n_tensors, const 
         h.neg_lr = t.neg_lr; h.wd = t.weight_decay; h.momentum = t.momentum; h.one_minus_damp = t.one_minus_dampening;
         h.has_wd = t.flags & OM_SGD_HAS_WD; h.has_mom = (t.flags & OM_SGD_HAS_MOMENTUM) && t.buf;
         h.first = t.flags & OM_SGD_FIRST; h.nesterov = t.flags & OM_SGD_NESTEROV; h.maximize = t.flags & OM_SGD_MAXIMIZE;
+        if constexpr (CLIP) {
+            if ((t.flags & OM_SGD_DEVICE_FIRST) && h.has_mom) {
+                // first = no step has been applied to this tensor yet.  Another chunk of the tensor may already have written this
+                // step's number: both values mean "first", and every writer stores the same value.
+                const long long since = clip.valid_since[ck.tensor];
+                h.first = since == 0 || since == clip.step;
+                if (since == 0 && threadIdx.x == 0) clip.valid_since[ck.tensor] = clip.step;
+            }
+        }
         const bool read_buf = h.has_mom && !h.first;
         // the pointers come out of the table: tell the compiler they are global memory (global_load, not flat_load)
         gfloat* __restrict__ P = (gfloat*)t.param;
@@ -89,7 +209,7 @@ sgd_step_kernel(const om_sgd_tensor* __restrict__ tensors, int n_tensors, const 
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         float bv = b[k][e];
-                        q[e] = sgd_element(h, p[k][e], g[k][e], bv);
+                        q[e] = sgd_element<CLIP>(h, coef, p[k][e], g[k][e], bv);
                         nb[e] = bv;
                     }
                     P4[i] = q;
@@ -99,13 +219,13 @@ sgd_step_kernel(const om_sgd_tensor* __restrict__ tensors, int n_tensors, const 
             const long long i = v1 * 4 + threadIdx.x;       // the tail of an element count that is not a multiple of 4
             if (i < stop) {
                 float bv = read_buf ? Bf[i] : 0.f;
-                P[i] = sgd_element(h, P[i], G[i], bv);
+                P[i] = sgd_element<CLIP>(h, coef, P[i], G[i], bv);
                 if (h.has_mom) Bf[i] = bv;
             }
         } else {
             for (long long i = start + threadIdx.x; i < stop; i += SGD_THREADS) {
                 float bv = read_buf ? Bf[i] : 0.f;
-                P[i] = sgd_element(h, P[i], G[i], bv);
+                P[i] = sgd_element<CLIP>(h, coef, P[i], G[i], bv);
                 if (h.has_mom) Bf[i] = bv;
             }
         }
@@ -131,7 +251,41 @@ int om_sgd_step(const om_sgd_tensor* table_host, om_sgd_tensor* table, int n_ten
         OM_CHECK_HIP(hipMemcpyAsync(table, table_host, (size_t)n_tensors * sizeof(om_sgd_tensor), hipMemcpyHostToDevice, st));
     }
     const int blocks = n_chunks < om::SGD_MAX_BLOCKS ? n_chunks : om::SGD_MAX_BLOCKS;
-    hipLaunchKernelGGL(om::sgd_step_kernel, dim3(blocks), dim3(om::SGD_THREADS), 0, st, table, n_tensors, chunks, n_chunks);
+    hipLaunchKernelGGL(om::sgd_step_kernel<false>, dim3(blocks), dim3(om::SGD_THREADS), 0, st, table, n_tensors, chunks, n_chunks,
+                       om::SgdClip{});
+    OM_CHECK_HIP(hipGetLastError());
+    return OM_OK;
+}
+
+int om_sgd_clip_step(const om_sgd_tensor* table_host, om_sgd_tensor* table, int n_tensors, const om_sgd_chunk* chunks, int n_chunks,
+                     double* partials, double* state, long long* valid_since, float max_norm, int mode, long long step,
+                     om_stream stream) {
+    OM_REQUIRE(table && chunks && partials && state && valid_since, OM_EINVAL, "om_sgd_clip_step: null pointer");
+    OM_REQUIRE(n_tensors > 0 && n_chunks > 0, OM_EINVAL, "om_sgd_clip_step: %d tensors in %d chunks", n_tensors, n_chunks);
+    OM_REQUIRE(max_norm > 0.f && std::isfinite(max_norm), OM_EINVAL, "om_sgd_clip_step: max_norm %g is not positive and finite",
+               (double)max_norm);
+    OM_REQUIRE((mode & ~OM_CLIP_SKIP_NONFINITE) == 0 && step >= 1, OM_EINVAL, "om_sgd_clip_step: mode %d, step %lld", mode, step);
+    OM_REQUIRE((reinterpret_cast<uintptr_t>(partials) | reinterpret_cast<uintptr_t>(state) |
+                reinterpret_cast<uintptr_t>(valid_since)) % 8 == 0, OM_EINVAL, "om_sgd_clip_step: misaligned pointer");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (table_host) {
+        for (int i = 0; i < n_tensors; ++i) {
+            const om_sgd_tensor& t = table_host[i];
+            if (t.flags & OM_SGD_SKIP) continue;
+            OM_REQUIRE(t.param && t.grad && t.n > 0 && (!(t.flags & OM_SGD_HAS_MOMENTUM) || t.buf), OM_EINVAL,
+                       "om_sgd_clip_step: row %d has a null pointer or no elements", i);
+        }
+        OM_CHECK_HIP(hipMemcpyAsync(table, table_host, (size_t)n_tensors * sizeof(om_sgd_tensor), hipMemcpyHostToDevice, st));
+    }
+    const int blocks = n_chunks < om::SGD_MAX_BLOCKS ? n_chunks : om::SGD_MAX_BLOCKS;
+    hipLaunchKernelGGL(om::grad_sumsq_kernel, dim3(blocks), dim3(om::SGD_THREADS), 0, st, table, n_tensors, chunks, n_chunks,
+                       partials);
+    OM_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(om::clip_finish_kernel, dim3(1), dim3(om::SGD_THREADS), 0, st, partials, n_chunks, max_norm, mode, step,
+                       state);
+    OM_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(om::sgd_step_kernel<true>, dim3(blocks), dim3(om::SGD_THREADS), 0, st, table, n_tensors, chunks, n_chunks,
+                       om::SgdClip{state, valid_since, step});
     OM_CHECK_HIP(hipGetLastError());
     return OM_OK;
 }

@@ -22,6 +22,18 @@ have been reallocated by ``zero_grad(set_to_none=True)``; a scheduler has usuall
 pinned staging buffers and hands that to om_sgd_step, which enqueues the host-to-device copy and the kernel on the current
 stream.  A staging buffer is reused only after the event recorded behind its copy has completed.  After a parameter's first step
 nothing is allocated and nothing is read back from the device.
+
+Gradient-norm clipping.  ``SGD(..., max_grad_norm=X, nonfinite="propagate" | "skip")`` (keyword-only; attributes of the optimizer,
+neither ``defaults`` nor param-group entries, so ``state_dict()`` keeps torch's keys) makes ``step()`` the three launches of
+om_sgd_clip_step: float64 partial sums of squares per chunk, one workgroup that finishes the float32 norm, torch's coefficient
+``min(1, (norm + 1e-6).reciprocal() * max_grad_norm)`` and the skip decision into a small device state block, and the update with
+every gradient element read as ``g * coef``.  That is ``torch.nn.utils.clip_grad_norm_(params, X)`` followed by ``step()``, bit for
+bit, except that ``p.grad`` is NOT modified.  With ``nonfinite="skip"`` a step whose norm is Inf or NaN leaves every parameter and
+momentum buffer bit-unchanged; the host never learns of it during the step.  New momentum buffers are then allocated with zeros
+and the device decides which applied step is a tensor's first (``buf = d``).  Known edge: resuming from a checkpoint taken before
+any APPLIED step (it holds zero buffers) with ``dampening != 0`` makes the first applied step ``buf = (1 - dampening) * d``, not
+torch's ``buf = d``.  ``grad_norm_stats()`` is one small device-to-host read of the block.  Under DistributedDataParallel every
+rank sees the same all-reduced gradients and so takes the same decision; no collective is added.  DESIGN.md section 3.16.1.
 """
 import numpy as _np
 import torch as _torch
@@ -34,6 +46,12 @@ from . import lib as _lib
 
 OM_SGD_CHUNK = 4096         # include/orienmask_hip.h
 OM_SGD_SKIP, OM_SGD_FIRST, OM_SGD_NESTEROV, OM_SGD_MAXIMIZE, OM_SGD_HAS_MOMENTUM, OM_SGD_HAS_WD = 1, 2, 4, 8, 16, 32
+OM_SGD_DEVICE_FIRST = 64    # "first step" is decided on the device (om_sgd_clip_step's valid_since)
+OM_CLIP_SKIP_NONFINITE = 1  # om_sgd_clip_step's mode bits
+# om_sgd_clip_step's state block, in 8-byte words (NORM, COEF, SUM, MAX are float64, the others int64)
+(OM_CLIP_NORM_OFF, OM_CLIP_COEF_OFF, OM_CLIP_SKIP_OFF, OM_CLIP_STEPS_OFF, OM_CLIP_SUM_OFF, OM_CLIP_MAX_OFF, OM_CLIP_CLIPPED_OFF,
+ OM_CLIP_NONFINITE_OFF, OM_CLIP_FIRST_NONFINITE_OFF, OM_CLIP_STATE_DOUBLES) = range(10)
+NONFINITE_MODES = ("propagate", "skip")
 # om_sgd_tensor / om_sgd_chunk as numpy records
 TENSOR_ROW = _np.dtype([("param", "<u8"), ("grad", "<u8"), ("buf", "<u8"), ("n", "<i8"), ("neg_lr", "<f4"), ("weight_decay", "<f4"),
                         ("momentum", "<f4"), ("one_minus_dampening", "<f4"), ("flags", "<u4"), ("reserved", "<u4", (3,))])
@@ -127,17 +145,50 @@ class _Plan:
         self.events = [_torch.cuda.Event() for _ in range(_RING)]
         self.turn = 0
         self.signature = [p.numel() for p in params]
+        self.device_first = [False] * n                   # rows whose first step the device decides (clipping, nonfinite="skip")
+        self.partials = self.valid_since = None           # om_sgd_clip_step's buffers, once a clipped step needs them
+
+    def clip_buffers(self):
+        if self.partials is None:
+            self.partials = _torch.empty(self.n_chunks, dtype=_torch.float64, device=self.device)
+            self.valid_since = _torch.zeros(self.n, dtype=_torch.int64, device=self.device)
+        return self.partials, self.valid_since
+
+
+def check_clip(max_grad_norm, nonfinite):
+    """The refusals of SGD's two clipping options."""
+    if nonfinite not in NONFINITE_MODES:
+        raise ValueError("orienmask_amd.optim.SGD: nonfinite must be one of %s, got %r" % (NONFINITE_MODES, nonfinite))
+    if max_grad_norm is None:
+        if nonfinite == "skip":
+            raise ValueError("orienmask_amd.optim.SGD: nonfinite='skip' needs max_grad_norm (the decision is taken from the "
+                             "gradient norm; a large bound such as 1e30 skips without clipping)")
+        return
+    if isinstance(max_grad_norm, _torch.Tensor):
+        raise _lib.OrienMaskHipError("orienmask_amd.optim.SGD: max_grad_norm is a tensor; the step takes a Python number (reading a "
+                                     "tensor back would synchronise)")
+    if isinstance(max_grad_norm, bool) or not isinstance(max_grad_norm, (int, float)):
+        raise ValueError("orienmask_amd.optim.SGD: max_grad_norm must be a positive finite number or None, got %r" % (max_grad_norm,))
+    as_f32 = float(_np.float32(max_grad_norm)) if abs(max_grad_norm) < 3.5e38 else float("inf")
+    if not (max_grad_norm > 0 and as_f32 > 0 and _np.isfinite(as_f32)):
+        raise ValueError("orienmask_amd.optim.SGD: max_grad_norm must be positive and finite in float32, got %r" % (max_grad_norm,))
 
 
 class SGD(_TorchSGD):
     """torch.optim.SGD (same constructor, same state, same state_dict) whose step is one HIP launch; see the module docstring."""
 
-    def __init__(self, params, *args, **kwargs):
+    def __init__(self, params, *args, max_grad_norm=None, nonfinite="propagate", **kwargs):
+        check_clip(max_grad_norm, nonfinite)
         super().__init__(params, *args, **kwargs)
         if self.defaults.get("differentiable"):
             raise _lib.OrienMaskHipError("orienmask_amd.optim.SGD: differentiable=True is not supported (the step is a HIP kernel "
                                          "outside autograd)")
         self._plans = None
+        # attributes, not defaults and not param-group entries: state_dict() keeps torch.optim.SGD's keys
+        self.max_grad_norm = max_grad_norm
+        self.nonfinite = nonfinite
+        self._clip_state = None                           # the device state block of om_sgd_clip_step, once a clipped step ran
+        self._clip_steps = 0                              # clipped step() calls so far: the step number the kernels latch
 
     def __setstate__(self, state):
         super().__setstate__(state)
@@ -173,8 +224,15 @@ class SGD(_TorchSGD):
                 params, group_of = per_device.setdefault(p.device, ([], []))
                 params.append(p)
                 group_of.append(gi)
+        if getattr(self, "max_grad_norm", None) is not None and len(per_device) > 1:
+            raise _lib.OrienMaskHipError("orienmask_amd.optim.SGD: max_grad_norm needs every parameter on one device (the norm is "
+                                         "global); got %s" % sorted(str(d) for d in per_device))
         self._plans = [_Plan(dev, params, group_of) for dev, (params, group_of) in per_device.items()]
         self._built_for = self._structure()
+        self._built_clip = self._clip_key()
+
+    def _clip_key(self):
+        return (getattr(self, "max_grad_norm", None) is not None, getattr(self, "nonfinite", "propagate"))
 
     @staticmethod
     def _write_hyper(plan, gi, key):
@@ -216,7 +274,8 @@ class SGD(_TorchSGD):
             b = nb
         return b
 
-    def _step_plan(self, plan):
+    def _step_plan(self, plan, clip=None, skip_mode=False):
+        """One device's step; ``clip``: None, or float max_grad_norm (then ``skip_mode``: nonfinite == "skip")."""
         groups = self.param_groups
         for gi in plan.group_slots:
             g = groups[gi]
@@ -253,11 +312,20 @@ class SGD(_TorchSGD):
                 if st is None:
                     st = states[i] = self.state[p]
                 b = st.get("momentum_buffer")
-                if b is None:
+                if b is None and skip_mode:
+                    # this step may be skipped: zeros (a checkpoint taken before an applied step holds no garbage), and from now
+                    # on the device decides which step is the tensor's first
+                    b = _torch.zeros_like(p, requires_grad=False)
+                    st["momentum_buffer"] = b
+                    plan.device_first[i] = True
+                    bufs[i] = None
+                elif b is None:
                     b = _torch.empty_like(p, requires_grad=False)      # written, not read, by this step (OM_SGD_FIRST)
                     st["momentum_buffer"] = b
                     flags[i] |= OM_SGD_FIRST
                     bufs[i] = None
+                if plan.device_first[i]:
+                    flags[i] |= OM_SGD_DEVICE_FIRST
                 if b is not bufs[i]:
                     nb = self._conform_buf(p, b)
                     if nb is not b:
@@ -278,7 +346,16 @@ class SGD(_TorchSGD):
         dev = plan.device
         stream = _torch.cuda.current_stream(dev)
         with _lib.on_device(dev):
-            _lib.launch("om_sgd_step", dev, plan.staging[k], plan.table, plan.n, plan.chunks, plan.n_chunks, stream=stream)
+            if clip is None:
+                _lib.launch("om_sgd_step", dev, plan.staging[k], plan.table, plan.n, plan.chunks, plan.n_chunks, stream=stream)
+            else:
+                partials, valid_since = plan.clip_buffers()
+                if self._clip_state is None or self._clip_state.device != dev:
+                    self._clip_state = _torch.zeros(OM_CLIP_STATE_DOUBLES, dtype=_torch.float64, device=dev)
+                self._clip_steps += 1
+                _lib.launch("om_sgd_clip_step", dev, plan.staging[k], plan.table, plan.n, plan.chunks, plan.n_chunks, partials,
+                            self._clip_state, valid_since, clip, OM_CLIP_SKIP_NONFINITE if skip_mode else 0, self._clip_steps,
+                            stream=stream)
             ev.record(stream)
         del keep
 
@@ -289,12 +366,38 @@ class SGD(_TorchSGD):
             with _torch.enable_grad():
                 loss = closure()
         _lib.load()
-        if getattr(self, "_plans", None) is None or self._built_for != self._structure():
+        max_norm, nonfinite = getattr(self, "max_grad_norm", None), getattr(self, "nonfinite", "propagate")
+        check_clip(max_norm, nonfinite)
+        if getattr(self, "_plans", None) is None or self._built_for != self._structure() or self._built_clip != self._clip_key():
             self._build_plans()
         with _torch.no_grad():
             for plan in self._plans:
-                self._step_plan(plan)
+                self._step_plan(plan, None if max_norm is None else float(max_norm), nonfinite == "skip")
         return loss
+
+    def grad_norm_stats(self, reset=True):
+        """What the clipped steps since the last reset saw, as ONE small device-to-host read of the state block the step kernels
+        keep (this synchronises; step() never does): ``steps`` (clipped step() calls), ``mean_norm`` and ``max_norm`` over the
+        steps whose norm was finite (nan where there was none), ``clipped_steps`` (finite norm, coefficient < 1),
+        ``nonfinite_steps`` (with nonfinite="skip": the steps that were skipped), ``first_nonfinite_step`` (the 1-based count of
+        this optimizer's clipped step() calls at the first non-finite norm, 0 = none; latched, never reset), ``last_norm`` and
+        ``last_coef`` (float32 values of the latest step).  ``reset``: the running counts start again."""
+        if getattr(self, "max_grad_norm", None) is None and getattr(self, "_clip_state", None) is None:
+            raise _lib.OrienMaskHipError("orienmask_amd.optim.SGD.grad_norm_stats: clipping is not enabled (max_grad_norm is None)")
+        if getattr(self, "_clip_state", None) is None:
+            block = _np.zeros(OM_CLIP_STATE_DOUBLES, dtype=_np.float64)
+        else:
+            block = self._clip_state.cpu().numpy()
+            if reset:
+                self._clip_state[OM_CLIP_STEPS_OFF:OM_CLIP_FIRST_NONFINITE_OFF].zero_()
+        words = block.view(_np.int64)
+        steps, nonfinite = int(words[OM_CLIP_STEPS_OFF]), int(words[OM_CLIP_NONFINITE_OFF])
+        finite = steps - nonfinite
+        return dict(steps=steps, mean_norm=float(block[OM_CLIP_SUM_OFF]) / finite if finite else float("nan"),
+                    max_norm=float(block[OM_CLIP_MAX_OFF]) if finite else float("nan"),
+                    clipped_steps=int(words[OM_CLIP_CLIPPED_OFF]), nonfinite_steps=nonfinite,
+                    first_nonfinite_step=int(words[OM_CLIP_FIRST_NONFINITE_OFF]),
+                    last_norm=float(block[OM_CLIP_NORM_OFF]), last_coef=float(block[OM_CLIP_COEF_OFF]))
 
 
 # ---- optim/param_groups.py ------------------------------------------------------------------------------------------------------

@@ -13,7 +13,12 @@ host EvalCounter, and ``isfinite(loss).item()`` / ``loss.item()`` on every batch
 values in a ``DeviceEvalCounter`` (om_loss_accumulate, csrc/loss_counter.hip) and the host reads that block every ``writer_freq``
 steps and at the end of the epoch.  The ONE deliberate difference in behaviour: the non-finite stop happens at that read, so up to
 ``log_freq * accumulate`` batches late; the block latches the first bad step, so the error still names the epoch and batch where
-it happened (the optimizer has stepped on the bad gradients by then; the run is lost either way, as in the reference).
+it happened (the optimizer has stepped on the bad gradients by then; the run is lost either way, as in the reference -- unless the
+optimizer is orienmask_amd.optim.SGD with ``max_grad_norm`` and ``nonfinite="skip"``: its step decides on the device to leave
+parameters and momentum buffers untouched when the gradient norm is not finite, so the weights at the stop are the last finite ones,
+and the error says so).  With ``max_grad_norm`` set, rank 0 also writes ``train/grad_norm``, ``train/grad_norm_max``,
+``train/clipped_steps`` and ``train/skipped_steps`` from ``optimizer.grad_norm_stats()`` at each of those reads; without it the
+scalars are unchanged.
 
 Other departures from the reference:
   * no ``exit()``: a non-finite loss raises FloatingPointError; reaching ``lr_scheduler.max_iter`` saves ``batch_<step>.pth`` and
@@ -351,8 +356,19 @@ class Trainer(BaseTrainer):
             self.tensorboard.add_scalar("lr/group%d" % i, group["lr"] * self.accumulate, at)
         for key, value in means.items():
             self.tensorboard.add_scalar("train/%s" % key, value, at)
+        if self._clipping():
+            # one small read of the optimizer's device block, at the counter's read: the norms of the steps since the last one
+            stats = self.optimizer.grad_norm_stats()
+            skipped = stats["nonfinite_steps"] if self.optimizer.nonfinite == "skip" else 0
+            for tag, value in (("grad_norm", stats["mean_norm"]), ("grad_norm_max", stats["max_norm"]),
+                               ("clipped_steps", stats["clipped_steps"]), ("skipped_steps", skipped)):
+                self.tensorboard.add_scalar("train/%s" % tag, value, at)
         if hasattr(bar, "set_postfix"):
             bar.set_postfix(lr="%.2e" % (groups[0]["lr"] * self.accumulate), loss="%.4f" % means["loss"])
+
+    def _clipping(self):
+        """The optimizer clips the gradient norm in its step (orienmask_amd.optim.SGD with max_grad_norm)."""
+        return getattr(self.optimizer, "max_grad_norm", None) is not None and hasattr(self.optimizer, "grad_norm_stats")
 
     def _save_at_max_iter(self, step):
         if self.device_rank == 0:
@@ -380,7 +396,12 @@ class Trainer(BaseTrainer):
         if isinstance(cause, ValueError):
             error = ValueError("%s; %s" % (cause, where))
         else:
-            error = FloatingPointError("non-finite loss%s; %s" % (" (%s)" % cause if cause is not None else "", where))
+            kept = ""
+            if self._clipping() and self.optimizer.nonfinite == "skip":
+                first = self.optimizer.grad_norm_stats(reset=False)["first_nonfinite_step"]
+                kept = ("; the optimizer skipped every step with a non-finite gradient norm (first at its step %d), so the "
+                        "parameters were left at their last finite state" % first)
+            error = FloatingPointError("non-finite loss%s; %s%s" % (" (%s)" % cause if cause is not None else "", where, kept))
         self.logger.error(str(error))
         if self.device_rank == 0:
             for key, value in loss_log.items():

@@ -10,9 +10,12 @@ and divides.  Reported per variant: median, min and max of the rounds' per-step 
 bytes per second at the median, and the host time per step (what the Python side of step() costs; where it exceeds the device
 time the event figure is host-bound and says so).  The device clock is read before and after where the runtime exposes it.
 
-    python tools/bench_optim.py [--rounds 15] [--inner 20] [--warmup 5]
+    python tools/bench_optim.py [--rounds 15] [--inner 20] [--warmup 5] [--max-grad-norm X]
 
-prints one JSON line.
+prints one JSON line.  ``--max-grad-norm X`` adds, per grouping, ``hip_clip_*`` -- the same class with ``max_grad_norm=X``: three
+launches of om_sgd_clip_step, one more read of the gradients -- and ``torch_clip_foreach_*``: torch.nn.utils.clip_grad_norm_ on the
+tensors followed by torch's default step (on gradients of its own: it scales them in place), and reports ``clip_over_plain``, the
+ratio of the medians of hip_clip_* and hip_* of the same run.
 """
 import argparse
 import json
@@ -46,6 +49,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=15)
     ap.add_argument("--inner", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--max-grad-norm", type=float, default=None, metavar="X",
+                    help="also time the step with gradient-norm clipping at X, and torch's clip_grad_norm_ + step")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_optim.py needs an MI355X: there is nothing to time on a CPU")
@@ -70,6 +75,19 @@ def main():
             p.grad = g
         return ps
 
+    class TorchClipped:
+        """torch.nn.utils.clip_grad_norm_ + torch.optim.SGD.step() as one step()."""
+
+        def __init__(self, ps, per_tensor, max_norm):
+            for p in ps:
+                p.grad = p.grad.clone()                       # clip_grad_norm_ scales in place
+            self.params, self.max_norm = ps, max_norm
+            self.opt = torch.optim.SGD(groups(ps, per_tensor), **HYPER)
+
+        def step(self):
+            torch.nn.utils.clip_grad_norm_(self.params, self.max_norm)
+            self.opt.step()
+
     def groups(ps, per_tensor):
         if not per_tensor:
             return ps
@@ -79,6 +97,9 @@ def main():
     skipped = {}
     for per_tensor, tag in ((False, "1group"), (True, "266groups")):
         variants["hip_" + tag] = O.SGD(groups(fresh_params(), per_tensor), **HYPER)
+        if args.max_grad_norm is not None:
+            variants["hip_clip_" + tag] = O.SGD(groups(fresh_params(), per_tensor), max_grad_norm=args.max_grad_norm, **HYPER)
+            variants["torch_clip_foreach_" + tag] = TorchClipped(fresh_params(), per_tensor, args.max_grad_norm)
         variants["torch_single_" + tag] = torch.optim.SGD(groups(fresh_params(), per_tensor), foreach=False, **HYPER)
         variants["torch_foreach_" + tag] = torch.optim.SGD(groups(fresh_params(), per_tensor), **HYPER)
         try:
@@ -122,6 +143,10 @@ def main():
                                  "spread_pct": round(100 * (v[-1] - v[0]) / med, 1), "GBps_at_median": round(nbytes / med / 1e6, 1),
                                  "host_ms_median": round(statistics.median(host_ms[name]), 4),
                                  "host_bound": statistics.median(host_ms[name]) > 0.9 * med}
+    if args.max_grad_norm is not None:
+        out["max_grad_norm"] = args.max_grad_norm
+        out["clip_over_plain"] = {tag: round(out["variants"]["hip_clip_" + tag]["ms_median"] /
+                                             out["variants"]["hip_" + tag]["ms_median"], 3) for tag in ("1group", "266groups")}
     print(json.dumps(out))
 
 

@@ -1,7 +1,7 @@
 """Train an OrienMask model on the MI355X: the reference's train.py against orienmask_amd.
 
     python tools/train.py --config CONFIG [--resume CHECKPOINT | --weights WEIGHTS] [--synthetic N] [--frozen-stages K] [--amp bf16]
-                          [--conv-forward {torch,hip}] [--conv-grad {torch,hip}]
+                          [--conv-forward {torch,hip}] [--conv-grad {torch,hip}] [--max-grad-norm X] [--nonfinite-grads {propagate,skip}]
 
 CONFIG is a JSON file -- the ``config.json`` a trainer writes into its checkpoint directory is one -- or, where a ``config``
 package with the reference's ``get_config`` is importable, a config name.  ``--synthetic N`` trains on N seeded synthetic images
@@ -13,7 +13,10 @@ fails the trainer's model-config check, as any other change of the model does). 
 ``conv_forward``: with ``--amp bf16`` every forward convolution is this package's bf16 kernel (csrc/conv_fwd_bf16.hip), frozen
 blocks one fused kernel each; without amp it needs the config's ``conv_backend`` to be 'hip'.  ``--conv-grad hip`` sets the model's
 ``conv_grad``: with ``--amp bf16 --conv-forward hip`` the gradients of those convolutions are this package's bf16 kernels too
-(csrc/conv_grad_bf16.hip), and a step repeats bit for bit.  With several processes (torchrun), each uses the GPU of its LOCAL_RANK.
+(csrc/conv_grad_bf16.hip), and a step repeats bit for bit.  ``--max-grad-norm X`` sets the optimizer's ``max_grad_norm`` (global L2
+gradient-norm clipping inside the HIP SGD step, orienmask_amd.optim.SGD) and ``--nonfinite-grads skip`` its ``nonfinite``: a step
+whose gradient norm is not finite leaves parameters and momentum buffers untouched, so a diverged run stops with its last finite
+weights.  With several processes (torchrun), each uses the GPU of its LOCAL_RANK.
 """
 import argparse
 import json
@@ -49,13 +52,20 @@ def parse_args(argv=None):
     ap.add_argument("--conv-grad", choices=["torch", "hip"], default=None,
                     help="whose bf16 convolution gradients under --amp bf16 --conv-forward hip (the model's conv_grad), overriding "
                          "the config's model.conv_grad")
+    ap.add_argument("--max-grad-norm", type=float, default=None, metavar="X",
+                    help="clip the global L2 gradient norm to X inside the SGD step (the optimizer's max_grad_norm), overriding "
+                         "the config's optimizer.max_grad_norm")
+    ap.add_argument("--nonfinite-grads", choices=["propagate", "skip"], default=None,
+                    help="with --max-grad-norm: what a step does whose gradient norm is not finite (the optimizer's nonfinite), "
+                         "overriding the config's optimizer.nonfinite")
     args = ap.parse_args(argv)
     assert not (args.resume and args.weights), "--resume and --weights exclude each other"
     return args
 
 
 def apply_overrides(config, args):
-    """The config with the command line's model options in config['model']; the caller's dicts are not mutated."""
+    """The config with the command line's model options in config['model'] and its optimizer options in config['optimizer']; the
+    caller's dicts are not mutated."""
     if args.frozen_stages is not None:
         config = dict(config, model=dict(config["model"], frozen_stages=args.frozen_stages))
     if args.amp is not None:
@@ -64,6 +74,10 @@ def apply_overrides(config, args):
         config = dict(config, model=dict(config["model"], conv_forward=args.conv_forward))
     if args.conv_grad is not None:
         config = dict(config, model=dict(config["model"], conv_grad=args.conv_grad))
+    if args.max_grad_norm is not None:
+        config = dict(config, optimizer=dict(config["optimizer"], max_grad_norm=args.max_grad_norm))
+    if args.nonfinite_grads is not None:
+        config = dict(config, optimizer=dict(config["optimizer"], nonfinite=args.nonfinite_grads))
     return config
 
 
