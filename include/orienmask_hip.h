@@ -809,6 +809,38 @@ int om_sgd_clip_step(const om_sgd_tensor* table_host, om_sgd_tensor* table, int 
                      double* partials, double* state, long long* valid_since, float max_norm, int mode, long long step,
                      om_stream stream);
 
+/* ---- The same two steps with an exponential moving average (EMA) of the weights kept inside the update kernel: one more float32
+ *      stream per tensor, its SHADOW, read and written beside parameter and momentum buffer (8 more bytes per element, no further
+ *      launch).  shadows: n_tensors pointers in DEVICE memory, one per row of the table; a shadow holds n floats in its parameter's
+ *      storage order; a null entry means the tensor is not averaged.  The shadow joins the alignment test of the 16-byte path.
+ *      Per element of a row that is stepped (not OM_SGD_SKIP), with p' the parameter's new value:
+ *          diff = p' - e                                  (rounded once)
+ *          e    = fma(diff, omd, e)                       (one rounding)
+ *      omd = float32(1 - d_k), d_k = decay, or with warm-up min(decay, (1 + k) / (10 + k)), evaluated in float64, k the number of
+ *      EMA updates applied before this one.  Parameter and momentum buffer get exactly the bits om_sgd_step / om_sgd_clip_step
+ *      give them.  A row under OM_SGD_SKIP keeps its shadow; k counts steps, not rows.  NaN and Inf propagate as the arithmetic
+ *      gives them.
+ *      om_sgd_ema_step: every step is applied, so the caller knows k and passes omd (0 < omd <= 1).
+ *      om_sgd_clip_ema_step: the single workgroup that takes the skip decision also keeps ema_state, OM_EMA_STATE_DOUBLES 8-byte
+ *      words, caller-owned, zeroed (or set to a resumed count) by the caller before the first call: int64 at OM_EMA_UPDATES_OFF
+ *      (EMA updates applied so far; never reset by the library) and float64 at OM_EMA_OMD_OFF (the float32 omd of the latest
+ *      applied step).  When the step is not skipped it computes omd from the count, `decay` (inside (0, 1)) and `warmup`, then
+ *      increments the count; a skipped step leaves the block, every shadow, parameter and buffer bit-unchanged.  The other
+ *      arguments are om_sgd_clip_step's, and the clip state block is OM_CLIP_STATE_DOUBLES words as there.
+ *      om_ema_swap exchanges parameter and shadow of every row with a shadow, element for element as 32-bit words (NaN payloads
+ *      survive; twice is the identity), over the same chunk table; it reads `param` and `n` of a row and none of its flags.
+ *      No atomics, no allocation, no host synchronisation in any of the three. */
+#define OM_EMA_UPDATES_OFF 0
+#define OM_EMA_OMD_OFF 1
+#define OM_EMA_STATE_DOUBLES 2
+int om_sgd_ema_step(const om_sgd_tensor* table_host, om_sgd_tensor* table, int n_tensors, const om_sgd_chunk* chunks, int n_chunks,
+                    float* const* shadows, float omd, om_stream stream);
+int om_sgd_clip_ema_step(const om_sgd_tensor* table_host, om_sgd_tensor* table, int n_tensors, const om_sgd_chunk* chunks,
+                         int n_chunks, double* partials, double* state, long long* valid_since, float max_norm, int mode,
+                         long long step, float* const* shadows, double* ema_state, double decay, int warmup, om_stream stream);
+int om_ema_swap(const om_sgd_tensor* table_host, om_sgd_tensor* table, int n_tensors, const om_sgd_chunk* chunks, int n_chunks,
+                float* const* shadows, om_stream stream);
+
 /* ---- The Conv -> BatchNorm2d -> LeakyReLU(0.1) block of the reference without its convolution (model/base.py:104-137,278-279: the
  *      nn.BatchNorm2d and nn.LeakyReLU of ConvBNRelu.conv_block), optionally with the residual add that closes a DarkNet block
  *      (model/backbone/darknet.py:14-15 `x + self.conv(x)`), for the training forward of trainer/trainer.py:47 and its backward (:52).

@@ -15,9 +15,16 @@
 //                     total_norm = (float)sqrt(S), the coefficient min(1, (total_norm + 1e-6).reciprocal() * max_norm) in float32
 //                     with one rounding per operation (torch's clip_grad_norm_), the skip decision and the running statistics,
 //                     written into the state block with plain stores by lane 0.
-//   sgd_step_kernel<true>  reads coefficient and skip decision from the state block: every gradient element enters the update as
+//   sgd_step_kernel<true, EMA>  reads coefficient and skip decision from the state block: every gradient element enters the update as
 //                     g * coef, rounded once; a skipped step returns before it touches a parameter.  No atomics anywhere: a step
 //                     repeats bit for bit.
+//   sgd_step_kernel<CLIP, true>  (weight EMA) a fourth stream, the tensor's float32 shadow: with the new parameter p' still in
+//                     registers, diff = p' - e rounded once, e' = fma(diff, omd, e).  The shadow pointers come from a device array of
+//                     their own (null = not averaged; om_sgd_tensor keeps its 64 bytes) and join the alignment test; omd = float32(1 -
+//                     decay_k) is an argument in the plain form and a word of the EMA state block in the clipped form, where
+//                     clip_finish_kernel<true> computes it from the count of APPLIED updates and advances that count only when the
+//                     step is not skipped.  Parameter and momentum buffer get the bits they get without it.
+//   ema_swap_kernel   the same grid over the same chunk table: parameter and shadow exchanged as raw 32-bit words.
 // Arithmetic: torch.optim.SGD's, in torch-CPU's float32 rounding: every x.add(y, alpha=a) of the update
 // is ONE fused multiply-add fma(y, float32(a), x); buf.mul_(momentum) is a product rounded on its own.  The fmas are written out
 // and the file is built with -ffp-contract=off, so the compiler neither splits them nor folds buf * momentum into the next one.
@@ -35,11 +42,20 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(1))) float gfloat;
 typedef __attribute__((address_space(1))) f32x4 gfloat4;
 
-// what the clipped form of the step reads beside the tables (unused by sgd_step_kernel<false>)
+// what the clipped form of the step reads beside the tables (unused by sgd_step_kernel<false, EMA>)
 struct SgdClip {
     const double* state;        // the OM_CLIP_* block clip_finish_kernel wrote on this stream
     long long* valid_since;     // per tensor: the step that first applied an update to an OM_SGD_DEVICE_FIRST row, 0 = none yet
     long long step;             // this step's number (from 1)
+};
+
+// what the averaging forms read beside the tables (unused by sgd_step_kernel<CLIP, false> and clip_finish_kernel<false>)
+struct SgdEma {
+    float* const* shadows;      // n_tensors device pointers, null = the tensor is not averaged
+    double* state;              // the OM_EMA_* block (clipped form; null in the plain form)
+    float omd;                  // float32(1 - decay_k) of this step (plain form: the host knows k)
+    double decay;               // clipped form: clip_finish_kernel<true> derives omd on the device
+    int warmup;
 };
 
 struct SgdHyper {
@@ -120,9 +136,10 @@ grad_sumsq_kernel(const om_sgd_tensor* __restrict__ tensors, int n_tensors, cons
     }
 }
 
+template <bool EMA>
 __global__ void __launch_bounds__(SGD_THREADS)
 clip_finish_kernel(const double* __restrict__ partials, int n_chunks, float max_norm, int mode, long long step,
-                   double* __restrict__ state) {
+                   double* __restrict__ state, const SgdEma ema) {
     __shared__ double wave_sums[SGD_THREADS / 64];
     double acc = 0.0;
     for (int i = threadIdx.x; i < n_chunks; i += SGD_THREADS) acc += partials[i];
@@ -146,17 +163,38 @@ clip_finish_kernel(const double* __restrict__ partials, int n_chunks, float max_
         words[OM_CLIP_NONFINITE_OFF] += 1;
         if (words[OM_CLIP_FIRST_NONFINITE_OFF] == 0) words[OM_CLIP_FIRST_NONFINITE_OFF] = step;
     }
+    if constexpr (EMA) {
+        // an applied step is one more EMA update: its decay from the count so far, in float64, rounded to float32 once
+        if (words[OM_CLIP_SKIP_OFF] == 0) {
+            long long* updates = reinterpret_cast<long long*>(ema.state) + OM_EMA_UPDATES_OFF;
+            const double k = (double)*updates;
+            double d = ema.decay;
+            if (ema.warmup) {
+                const double ramp = (1.0 + k) / (10.0 + k);
+                if (ramp < d) d = ramp;
+            }
+            ema.state[OM_EMA_OMD_OFF] = (double)(float)(1.0 - d);
+            *updates += 1;
+        }
+    }
 }
 
-template <bool CLIP>
+// the shadow's update with the parameter's new value: the difference rounded once, then ONE fused multiply-add
+__device__ __forceinline__ float ema_element(float p_new, float e, float omd) {
+    return fmaf(__fsub_rn(p_new, e), omd, e);
+}
+
+template <bool CLIP, bool EMA>
 __global__ void __launch_bounds__(SGD_THREADS)
 sgd_step_kernel(const om_sgd_tensor* __restrict__ tensors, int n_tensors, const om_sgd_chunk* __restrict__ chunks, int n_chunks,
-                const SgdClip clip) {
+                const SgdClip clip, const SgdEma ema) {
     float coef = 1.0f;
     if constexpr (CLIP) {
         if (reinterpret_cast<const long long*>(clip.state)[OM_CLIP_SKIP_OFF] != 0) return;      // nothing is touched
         coef = (float)clip.state[OM_CLIP_COEF_OFF];
     }
+    float omd = 0.f;
+    if constexpr (EMA) omd = CLIP ? (float)ema.state[OM_EMA_OMD_OFF] : ema.omd;
     for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {
         const om_sgd_chunk ck = chunks[c];
         if ((unsigned)ck.tensor >= (unsigned)n_tensors || ck.chunk < 0) continue;
@@ -182,16 +220,21 @@ sgd_step_kernel(const om_sgd_tensor* __restrict__ tensors, int n_tensors, const 
         gfloat* __restrict__ P = (gfloat*)t.param;
         const gfloat* __restrict__ G = (const gfloat*)t.grad;
         gfloat* __restrict__ Bf = (gfloat*)t.buf;
+        gfloat* __restrict__ E = nullptr;                   // the shadow; null: this tensor is not averaged
+        if constexpr (EMA) E = (gfloat*)ema.shadows[ck.tensor];
+        const bool has_ema = EMA && E != nullptr;
         const long long stop = (start + OM_SGD_CHUNK < n) ? start + OM_SGD_CHUNK : n;
         const bool aligned = ((reinterpret_cast<uintptr_t>(t.param) | reinterpret_cast<uintptr_t>(t.grad) |
-                               (h.has_mom ? reinterpret_cast<uintptr_t>(t.buf) : (uintptr_t)0)) & 15) == 0;
+                               (h.has_mom ? reinterpret_cast<uintptr_t>(t.buf) : (uintptr_t)0) |
+                               (has_ema ? reinterpret_cast<uintptr_t>(E) : (uintptr_t)0)) & 15) == 0;
         if (aligned) {
             // start is a multiple of 4, so the chunk's float4s are [start / 4, stop / 4) and at most 3 elements remain
             const long long v0 = start / 4, v1 = stop / 4;
             gfloat4* P4 = (gfloat4*)P;
             const gfloat4* G4 = (const gfloat4*)G;
             gfloat4* B4 = (gfloat4*)Bf;
-            f32x4 p[SGD_VEC_PER_THREAD], g[SGD_VEC_PER_THREAD], b[SGD_VEC_PER_THREAD];
+            gfloat4* E4 = (gfloat4*)E;
+            f32x4 p[SGD_VEC_PER_THREAD], g[SGD_VEC_PER_THREAD], b[SGD_VEC_PER_THREAD], e4[EMA ? SGD_VEC_PER_THREAD : 1];
 #pragma unroll
             for (int k = 0; k < SGD_VEC_PER_THREAD; ++k) {
                 const long long i = v0 + k * SGD_THREADS + threadIdx.x;
@@ -199,60 +242,158 @@ sgd_step_kernel(const om_sgd_tensor* __restrict__ tensors, int n_tensors, const 
                     p[k] = P4[i];
                     g[k] = G4[i];
                     b[k] = read_buf ? B4[i] : f32x4{0.f, 0.f, 0.f, 0.f};
+                    if constexpr (EMA) e4[k] = has_ema ? E4[i] : f32x4{0.f, 0.f, 0.f, 0.f};
                 }
             }
 #pragma unroll
             for (int k = 0; k < SGD_VEC_PER_THREAD; ++k) {
                 const long long i = v0 + k * SGD_THREADS + threadIdx.x;
                 if (i < v1) {
-                    f32x4 q, nb;
+                    f32x4 q, nb, ne;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         float bv = b[k][e];
                         q[e] = sgd_element<CLIP>(h, coef, p[k][e], g[k][e], bv);
                         nb[e] = bv;
+                        if constexpr (EMA) ne[e] = ema_element(q[e], e4[k][e], omd);
                     }
                     P4[i] = q;
                     if (h.has_mom) B4[i] = nb;
+                    if constexpr (EMA) {
+                        if (has_ema) E4[i] = ne;
+                    }
                 }
             }
             const long long i = v1 * 4 + threadIdx.x;       // the tail of an element count that is not a multiple of 4
             if (i < stop) {
                 float bv = read_buf ? Bf[i] : 0.f;
-                P[i] = sgd_element<CLIP>(h, coef, P[i], G[i], bv);
+                const float ev = has_ema ? E[i] : 0.f;
+                const float q = sgd_element<CLIP>(h, coef, P[i], G[i], bv);
+                P[i] = q;
                 if (h.has_mom) Bf[i] = bv;
+                if (has_ema) E[i] = ema_element(q, ev, omd);
             }
         } else {
             for (long long i = start + threadIdx.x; i < stop; i += SGD_THREADS) {
                 float bv = read_buf ? Bf[i] : 0.f;
-                P[i] = sgd_element<CLIP>(h, coef, P[i], G[i], bv);
+                const float ev = has_ema ? E[i] : 0.f;
+                const float q = sgd_element<CLIP>(h, coef, P[i], G[i], bv);
+                P[i] = q;
                 if (h.has_mom) Bf[i] = bv;
+                if (has_ema) E[i] = ema_element(q, ev, omd);
             }
+        }
+    }
+}
+
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(1))) unsigned int guint;
+typedef __attribute__((address_space(1))) u32x4 guint4;
+
+// parameter <-> shadow, element for element, as 32-bit words (a NaN keeps its payload); rows without a shadow are passed over, a
+// row's OM_SGD_* flags are not read (a tensor that had no gradient in the latest step is exchanged like any other)
+__global__ void __launch_bounds__(SGD_THREADS)
+ema_swap_kernel(const om_sgd_tensor* __restrict__ tensors, int n_tensors, const om_sgd_chunk* __restrict__ chunks, int n_chunks,
+                float* const* __restrict__ shadows) {
+    for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+        const om_sgd_chunk ck = chunks[c];
+        if ((unsigned)ck.tensor >= (unsigned)n_tensors || ck.chunk < 0) continue;
+        const om_sgd_tensor t = tensors[ck.tensor];
+        const long long n = t.n;
+        const long long start = (long long)ck.chunk * OM_SGD_CHUNK;
+        guint* __restrict__ P = (guint*)t.param;
+        guint* __restrict__ E = (guint*)shadows[ck.tensor];
+        if (!P || !E || start >= n) continue;
+        const long long stop = (start + OM_SGD_CHUNK < n) ? start + OM_SGD_CHUNK : n;
+        const bool aligned = ((reinterpret_cast<uintptr_t>(t.param) | reinterpret_cast<uintptr_t>(shadows[ck.tensor])) & 15) == 0;
+        long long scalar_from = start;
+        if (aligned) {
+            const long long v0 = start / 4, v1 = stop / 4;
+            guint4* P4 = (guint4*)P;
+            guint4* E4 = (guint4*)E;
+            u32x4 p[SGD_VEC_PER_THREAD], e[SGD_VEC_PER_THREAD];
+#pragma unroll
+            for (int k = 0; k < SGD_VEC_PER_THREAD; ++k) {
+                const long long i = v0 + k * SGD_THREADS + threadIdx.x;
+                if (i < v1) {
+                    p[k] = P4[i];
+                    e[k] = E4[i];
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < SGD_VEC_PER_THREAD; ++k) {
+                const long long i = v0 + k * SGD_THREADS + threadIdx.x;
+                if (i < v1) {
+                    P4[i] = e[k];
+                    E4[i] = p[k];
+                }
+            }
+            scalar_from = v1 * 4;                           // at most 3 elements remain
+        }
+        for (long long i = scalar_from + threadIdx.x; i < stop; i += SGD_THREADS) {
+            const unsigned int pv = P[i], ev = E[i];
+            P[i] = ev;
+            E[i] = pv;
         }
     }
 }
 
 }  // namespace om
 
+namespace {
+
+// the checks and the table copy every step entry shares; `who` names the entry in the message
+int stage_table(const char* who, const om_sgd_tensor* table_host, om_sgd_tensor* table, int n_tensors, const om_sgd_chunk* chunks,
+                int n_chunks, bool rows_are_stepped, hipStream_t st) {
+    OM_REQUIRE(table && chunks, OM_EINVAL, "%s: null table", who);
+    OM_REQUIRE(n_tensors > 0 && n_chunks > 0, OM_EINVAL, "%s: %d tensors in %d chunks", who, n_tensors, n_chunks);
+    if (table_host) {       // the rows are at hand: refuse a row the kernel could only pass over
+        for (int i = 0; i < n_tensors && rows_are_stepped; ++i) {
+            const om_sgd_tensor& t = table_host[i];
+            if (t.flags & OM_SGD_SKIP) continue;
+            OM_REQUIRE(t.param && t.grad && t.n > 0 && (!(t.flags & OM_SGD_HAS_MOMENTUM) || t.buf), OM_EINVAL,
+                       "%s: row %d has a null pointer or no elements", who, i);
+        }
+        OM_CHECK_HIP(hipMemcpyAsync(table, table_host, (size_t)n_tensors * sizeof(om_sgd_tensor), hipMemcpyHostToDevice, st));
+    }
+    return OM_OK;
+}
+
+int check_clip(const char* who, const double* partials, const double* state, const long long* valid_since, float max_norm,
+               int mode, long long step) {
+    OM_REQUIRE(partials && state && valid_since, OM_EINVAL, "%s: null pointer", who);
+    OM_REQUIRE(max_norm > 0.f && std::isfinite(max_norm), OM_EINVAL, "%s: max_norm %g is not positive and finite", who,
+               (double)max_norm);
+    OM_REQUIRE((mode & ~OM_CLIP_SKIP_NONFINITE) == 0 && step >= 1, OM_EINVAL, "%s: mode %d, step %lld", who, mode, step);
+    OM_REQUIRE((reinterpret_cast<uintptr_t>(partials) | reinterpret_cast<uintptr_t>(state) |
+                reinterpret_cast<uintptr_t>(valid_since)) % 8 == 0, OM_EINVAL, "%s: misaligned pointer", who);
+    return OM_OK;
+}
+
+inline int grid_of(int n_chunks) { return n_chunks < om::SGD_MAX_BLOCKS ? n_chunks : om::SGD_MAX_BLOCKS; }
+
+}  // namespace
+
 extern "C" {
 
 int om_sgd_step(const om_sgd_tensor* table_host, om_sgd_tensor* table, int n_tensors, const om_sgd_chunk* chunks, int n_chunks,
                 om_stream stream) {
-    OM_REQUIRE(table && chunks, OM_EINVAL, "om_sgd_step: null table");
-    OM_REQUIRE(n_tensors > 0 && n_chunks > 0, OM_EINVAL, "om_sgd_step: %d tensors in %d chunks", n_tensors, n_chunks);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (table_host) {       // the rows are at hand: refuse a row the kernel could only pass over
-        for (int i = 0; i < n_tensors; ++i) {
-            const om_sgd_tensor& t = table_host[i];
-            if (t.flags & OM_SGD_SKIP) continue;
-            OM_REQUIRE(t.param && t.grad && t.n > 0 && (!(t.flags & OM_SGD_HAS_MOMENTUM) || t.buf), OM_EINVAL,
-                       "om_sgd_step: row %d has a null pointer or no elements", i);
-        }
-        OM_CHECK_HIP(hipMemcpyAsync(table, table_host, (size_t)n_tensors * sizeof(om_sgd_tensor), hipMemcpyHostToDevice, st));
-    }
-    const int blocks = n_chunks < om::SGD_MAX_BLOCKS ? n_chunks : om::SGD_MAX_BLOCKS;
-    hipLaunchKernelGGL(om::sgd_step_kernel<false>, dim3(blocks), dim3(om::SGD_THREADS), 0, st, table, n_tensors, chunks, n_chunks,
-                       om::SgdClip{});
+    if (int rc = stage_table("om_sgd_step", table_host, table, n_tensors, chunks, n_chunks, true, st)) return rc;
+    hipLaunchKernelGGL((om::sgd_step_kernel<false, false>), dim3(grid_of(n_chunks)), dim3(om::SGD_THREADS), 0, st, table, n_tensors,
+                       chunks, n_chunks, om::SgdClip{}, om::SgdEma{});
+    OM_CHECK_HIP(hipGetLastError());
+    return OM_OK;
+}
+
+int om_sgd_ema_step(const om_sgd_tensor* table_host, om_sgd_tensor* table, int n_tensors, const om_sgd_chunk* chunks, int n_chunks,
+                    float* const* shadows, float omd, om_stream stream) {
+    OM_REQUIRE(shadows, OM_EINVAL, "om_sgd_ema_step: null shadows");
+    OM_REQUIRE(omd > 0.f && omd <= 1.f, OM_EINVAL, "om_sgd_ema_step: omd %g is not 1 - decay of a decay in [0, 1)", (double)omd);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rc = stage_table("om_sgd_ema_step", table_host, table, n_tensors, chunks, n_chunks, true, st)) return rc;
+    hipLaunchKernelGGL((om::sgd_step_kernel<false, true>), dim3(grid_of(n_chunks)), dim3(om::SGD_THREADS), 0, st, table, n_tensors,
+                       chunks, n_chunks, om::SgdClip{}, om::SgdEma{shadows, nullptr, omd, 0.0, 0});
     OM_CHECK_HIP(hipGetLastError());
     return OM_OK;
 }
@@ -260,32 +401,53 @@ int om_sgd_step(const om_sgd_tensor* table_host, om_sgd_tensor* table, int n_ten
 int om_sgd_clip_step(const om_sgd_tensor* table_host, om_sgd_tensor* table, int n_tensors, const om_sgd_chunk* chunks, int n_chunks,
                      double* partials, double* state, long long* valid_since, float max_norm, int mode, long long step,
                      om_stream stream) {
-    OM_REQUIRE(table && chunks && partials && state && valid_since, OM_EINVAL, "om_sgd_clip_step: null pointer");
-    OM_REQUIRE(n_tensors > 0 && n_chunks > 0, OM_EINVAL, "om_sgd_clip_step: %d tensors in %d chunks", n_tensors, n_chunks);
-    OM_REQUIRE(max_norm > 0.f && std::isfinite(max_norm), OM_EINVAL, "om_sgd_clip_step: max_norm %g is not positive and finite",
-               (double)max_norm);
-    OM_REQUIRE((mode & ~OM_CLIP_SKIP_NONFINITE) == 0 && step >= 1, OM_EINVAL, "om_sgd_clip_step: mode %d, step %lld", mode, step);
-    OM_REQUIRE((reinterpret_cast<uintptr_t>(partials) | reinterpret_cast<uintptr_t>(state) |
-                reinterpret_cast<uintptr_t>(valid_since)) % 8 == 0, OM_EINVAL, "om_sgd_clip_step: misaligned pointer");
+    OM_REQUIRE(table && chunks, OM_EINVAL, "om_sgd_clip_step: null pointer");
+    if (int rc = check_clip("om_sgd_clip_step", partials, state, valid_since, max_norm, mode, step)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (table_host) {
-        for (int i = 0; i < n_tensors; ++i) {
-            const om_sgd_tensor& t = table_host[i];
-            if (t.flags & OM_SGD_SKIP) continue;
-            OM_REQUIRE(t.param && t.grad && t.n > 0 && (!(t.flags & OM_SGD_HAS_MOMENTUM) || t.buf), OM_EINVAL,
-                       "om_sgd_clip_step: row %d has a null pointer or no elements", i);
-        }
-        OM_CHECK_HIP(hipMemcpyAsync(table, table_host, (size_t)n_tensors * sizeof(om_sgd_tensor), hipMemcpyHostToDevice, st));
-    }
-    const int blocks = n_chunks < om::SGD_MAX_BLOCKS ? n_chunks : om::SGD_MAX_BLOCKS;
+    if (int rc = stage_table("om_sgd_clip_step", table_host, table, n_tensors, chunks, n_chunks, true, st)) return rc;
+    const int blocks = grid_of(n_chunks);
     hipLaunchKernelGGL(om::grad_sumsq_kernel, dim3(blocks), dim3(om::SGD_THREADS), 0, st, table, n_tensors, chunks, n_chunks,
                        partials);
     OM_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(om::clip_finish_kernel, dim3(1), dim3(om::SGD_THREADS), 0, st, partials, n_chunks, max_norm, mode, step,
-                       state);
+    hipLaunchKernelGGL(om::clip_finish_kernel<false>, dim3(1), dim3(om::SGD_THREADS), 0, st, partials, n_chunks, max_norm, mode, step,
+                       state, om::SgdEma{});
     OM_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(om::sgd_step_kernel<true>, dim3(blocks), dim3(om::SGD_THREADS), 0, st, table, n_tensors, chunks, n_chunks,
-                       om::SgdClip{state, valid_since, step});
+    hipLaunchKernelGGL((om::sgd_step_kernel<true, false>), dim3(blocks), dim3(om::SGD_THREADS), 0, st, table, n_tensors, chunks,
+                       n_chunks, om::SgdClip{state, valid_since, step}, om::SgdEma{});
+    OM_CHECK_HIP(hipGetLastError());
+    return OM_OK;
+}
+
+int om_sgd_clip_ema_step(const om_sgd_tensor* table_host, om_sgd_tensor* table, int n_tensors, const om_sgd_chunk* chunks,
+                         int n_chunks, double* partials, double* state, long long* valid_since, float max_norm, int mode,
+                         long long step, float* const* shadows, double* ema_state, double decay, int warmup, om_stream stream) {
+    OM_REQUIRE(table && chunks && shadows && ema_state, OM_EINVAL, "om_sgd_clip_ema_step: null pointer");
+    if (int rc = check_clip("om_sgd_clip_ema_step", partials, state, valid_since, max_norm, mode, step)) return rc;
+    OM_REQUIRE(reinterpret_cast<uintptr_t>(ema_state) % 8 == 0, OM_EINVAL, "om_sgd_clip_ema_step: misaligned pointer");
+    OM_REQUIRE(decay > 0.0 && decay < 1.0, OM_EINVAL, "om_sgd_clip_ema_step: decay %g is not inside (0, 1)", decay);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rc = stage_table("om_sgd_clip_ema_step", table_host, table, n_tensors, chunks, n_chunks, true, st)) return rc;
+    const int blocks = grid_of(n_chunks);
+    const om::SgdEma ema{shadows, ema_state, 0.f, decay, warmup != 0};
+    hipLaunchKernelGGL(om::grad_sumsq_kernel, dim3(blocks), dim3(om::SGD_THREADS), 0, st, table, n_tensors, chunks, n_chunks,
+                       partials);
+    OM_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(om::clip_finish_kernel<true>, dim3(1), dim3(om::SGD_THREADS), 0, st, partials, n_chunks, max_norm, mode, step,
+                       state, ema);
+    OM_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL((om::sgd_step_kernel<true, true>), dim3(blocks), dim3(om::SGD_THREADS), 0, st, table, n_tensors, chunks,
+                       n_chunks, om::SgdClip{state, valid_since, step}, ema);
+    OM_CHECK_HIP(hipGetLastError());
+    return OM_OK;
+}
+
+int om_ema_swap(const om_sgd_tensor* table_host, om_sgd_tensor* table, int n_tensors, const om_sgd_chunk* chunks, int n_chunks,
+                float* const* shadows, om_stream stream) {
+    OM_REQUIRE(shadows, OM_EINVAL, "om_ema_swap: null shadows");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rc = stage_table("om_ema_swap", table_host, table, n_tensors, chunks, n_chunks, false, st)) return rc;
+    hipLaunchKernelGGL(om::ema_swap_kernel, dim3(grid_of(n_chunks)), dim3(om::SGD_THREADS), 0, st, table, n_tensors, chunks,
+                       n_chunks, shadows);
     OM_CHECK_HIP(hipGetLastError());
     return OM_OK;
 }

@@ -34,7 +34,23 @@ and the device decides which applied step is a tensor's first (``buf = d``).  Kn
 any APPLIED step (it holds zero buffers) with ``dampening != 0`` makes the first applied step ``buf = (1 - dampening) * d``, not
 torch's ``buf = d``.  ``grad_norm_stats()`` is one small device-to-host read of the block.  Under DistributedDataParallel every
 rank sees the same all-reduced gradients and so takes the same decision; no collective is added.  DESIGN.md section 3.16.1.
+
+Weight EMA.  ``SGD(..., ema_decay=D, ema_warmup=True)`` (keyword-only attributes like the two above; ``state_dict()`` keeps torch's
+keys) keeps a float32 SHADOW per parameter tensor, with the parameter's shape and strides, allocated as a bit copy of the parameter
+when the device plan is built -- at the first ``step()``, so weights loaded before it are what gets copied.  Every APPLIED step
+updates it inside the step kernel (om_sgd_ema_step / om_sgd_clip_ema_step: 8 more bytes per element, no further launch), with the
+parameter's new value ``p'``:  ``diff = p' - e`` rounded once, ``e = fma(diff, omd, e)``, ``omd = float32(1 - d_k)``,
+``d_k = ema_decay`` or with warm-up ``min(ema_decay, (1 + k) / (10 + k))`` in float64, ``k`` the number of EMA updates this
+optimizer has applied.  Parameters and momentum buffers get exactly the bits they get without it.  With ``nonfinite="skip"`` the
+device keeps ``k`` and a skipped step leaves every shadow and ``k`` unchanged -- a host-side average cannot know that.  A parameter
+without a gradient in a step keeps its shadow while ``k``, which is global, still advances.  NaN and Inf propagate as the arithmetic
+gives them.  ``ema_updates()`` is the host's count, or one small device-to-host read in skip mode; ``ema_swap()`` / ``with
+ema_applied():`` exchange parameters and shadows in place (om_ema_swap: pointers stay, no plan is rebuilt, nothing is allocated);
+``ema_state_dict(model)`` / ``load_ema_state_dict(model, state_dict, updates)`` are the checkpoint's side.  Every parameter must
+be on one device.  Under DistributedDataParallel every rank starts from the same weights and sees the same gradients, so the
+shadows agree without a collective.  DESIGN.md section 3.16.2.
 """
+import contextlib as _contextlib
 import numpy as _np
 import torch as _torch
 from torch.optim import *                   # noqa: F401,F403  (the reference's optim/__init__.py:1)
@@ -52,6 +68,8 @@ OM_CLIP_SKIP_NONFINITE = 1  # om_sgd_clip_step's mode bits
 (OM_CLIP_NORM_OFF, OM_CLIP_COEF_OFF, OM_CLIP_SKIP_OFF, OM_CLIP_STEPS_OFF, OM_CLIP_SUM_OFF, OM_CLIP_MAX_OFF, OM_CLIP_CLIPPED_OFF,
  OM_CLIP_NONFINITE_OFF, OM_CLIP_FIRST_NONFINITE_OFF, OM_CLIP_STATE_DOUBLES) = range(10)
 NONFINITE_MODES = ("propagate", "skip")
+# om_sgd_clip_ema_step's EMA state block, in 8-byte words (UPDATES is int64, OMD float64)
+OM_EMA_UPDATES_OFF, OM_EMA_OMD_OFF, OM_EMA_STATE_DOUBLES = range(3)
 # om_sgd_tensor / om_sgd_chunk as numpy records
 TENSOR_ROW = _np.dtype([("param", "<u8"), ("grad", "<u8"), ("buf", "<u8"), ("n", "<i8"), ("neg_lr", "<f4"), ("weight_decay", "<f4"),
                         ("momentum", "<f4"), ("one_minus_dampening", "<f4"), ("flags", "<u4"), ("reserved", "<u4", (3,))])
@@ -147,6 +165,24 @@ class _Plan:
         self.signature = [p.numel() for p in params]
         self.device_first = [False] * n                   # rows whose first step the device decides (clipping, nonfinite="skip")
         self.partials = self.valid_since = None           # om_sgd_clip_step's buffers, once a clipped step needs them
+        self.shadows = None                               # the EMA shadows, slot by slot (None: not averaged), and the device
+        self.shadow_ptrs = None                           # array of their addresses om_sgd_ema_step reads
+
+    def set_shadows(self, shadows):
+        """The plan's shadows, one per slot; their addresses go to the device once (again only if one is replaced)."""
+        self.shadows = list(shadows)
+        ptrs = _np.asarray([0 if e is None else e.data_ptr() for e in self.shadows], dtype=_np.uint64).view(_np.int64)
+        self.shadow_ptrs = _torch.from_numpy(ptrs).to(self.device)
+
+    def stage(self):
+        """The host rows into the next pinned staging buffer -> (buffer, the event to record behind its copy)."""
+        k = self.turn
+        self.turn = (k + 1) % _RING
+        ev = self.events[k]
+        if not ev.query():
+            ev.synchronize()                              # the copy out of this staging buffer, _RING steps ago, has not run yet
+        self.staging_rows[k][:] = self.rows
+        return self.staging[k], ev
 
     def clip_buffers(self):
         if self.partials is None:
@@ -174,11 +210,31 @@ def check_clip(max_grad_norm, nonfinite):
         raise ValueError("orienmask_amd.optim.SGD: max_grad_norm must be positive and finite in float32, got %r" % (max_grad_norm,))
 
 
+def check_ema(ema_decay, ema_warmup=True):
+    """The refusals of SGD's two EMA options."""
+    if ema_decay is None:
+        return
+    if isinstance(ema_decay, _torch.Tensor):
+        raise _lib.OrienMaskHipError("orienmask_amd.optim.SGD: ema_decay is a tensor; the step takes a Python number (reading a "
+                                     "tensor back would synchronise)")
+    if isinstance(ema_decay, bool) or not isinstance(ema_decay, (int, float)) or not 0.0 < ema_decay < 1.0:
+        raise ValueError("orienmask_amd.optim.SGD: ema_decay must be a number inside (0, 1) or None, got %r" % (ema_decay,))
+    if not isinstance(ema_warmup, (bool, int)):
+        raise ValueError("orienmask_amd.optim.SGD: ema_warmup must be True or False, got %r" % (ema_warmup,))
+
+
+def ema_decay_at(k, decay, warmup=True):
+    """d_k, the decay of EMA update number k (from 0), in float64: ``decay``, or with warm-up min(decay, (1 + k) / (10 + k))."""
+    d = float(decay)
+    return min(d, (1.0 + k) / (10.0 + k)) if warmup else d
+
+
 class SGD(_TorchSGD):
     """torch.optim.SGD (same constructor, same state, same state_dict) whose step is one HIP launch; see the module docstring."""
 
-    def __init__(self, params, *args, max_grad_norm=None, nonfinite="propagate", **kwargs):
+    def __init__(self, params, *args, max_grad_norm=None, nonfinite="propagate", ema_decay=None, ema_warmup=True, **kwargs):
         check_clip(max_grad_norm, nonfinite)
+        check_ema(ema_decay, ema_warmup)
         super().__init__(params, *args, **kwargs)
         if self.defaults.get("differentiable"):
             raise _lib.OrienMaskHipError("orienmask_amd.optim.SGD: differentiable=True is not supported (the step is a HIP kernel "
@@ -189,6 +245,13 @@ class SGD(_TorchSGD):
         self.nonfinite = nonfinite
         self._clip_state = None                           # the device state block of om_sgd_clip_step, once a clipped step ran
         self._clip_steps = 0                              # clipped step() calls so far: the step number the kernels latch
+        self.ema_decay = ema_decay
+        self.ema_warmup = ema_warmup
+        self._ema_shadows = {}                            # parameter -> shadow; survives a rebuilt plan (load_state_dict)
+        self._ema_state = None                            # the device block of om_sgd_clip_ema_step, once such a step ran
+        self._ema_k = 0                                   # EMA updates applied so far, as far as the host knows:
+        self._ema_on_device = False                       # True after a step that may have been skipped: the device word counts
+        self._ema_word_valid = False                      # the device word holds _ema_k (or, _ema_on_device, the count itself)
 
     def __setstate__(self, state):
         super().__setstate__(state)
@@ -227,12 +290,47 @@ class SGD(_TorchSGD):
         if getattr(self, "max_grad_norm", None) is not None and len(per_device) > 1:
             raise _lib.OrienMaskHipError("orienmask_amd.optim.SGD: max_grad_norm needs every parameter on one device (the norm is "
                                          "global); got %s" % sorted(str(d) for d in per_device))
+        averaging = getattr(self, "ema_decay", None) is not None
+        if averaging and len(per_device) > 1:
+            raise _lib.OrienMaskHipError("orienmask_amd.optim.SGD: ema_decay needs every parameter on one device (one count of "
+                                         "updates, one swap); got %s" % sorted(str(d) for d in per_device))
         self._plans = [_Plan(dev, params, group_of) for dev, (params, group_of) in per_device.items()]
+        if averaging:
+            for plan in self._plans:
+                plan.set_shadows([self._shadow_of(p) for p in plan.params])
         self._built_for = self._structure()
         self._built_clip = self._clip_key()
 
     def _clip_key(self):
-        return (getattr(self, "max_grad_norm", None) is not None, getattr(self, "nonfinite", "propagate"))
+        return (getattr(self, "max_grad_norm", None) is not None, getattr(self, "nonfinite", "propagate"),
+                getattr(self, "ema_decay", None) is not None)
+
+    def _shadow_of(self, p):
+        """The parameter's shadow: kept if it still fits the parameter, else a bit copy of the parameter as it is now."""
+        e = self._ema_shadows.get(p)
+        if e is None or e.shape != p.shape or e.device != p.device:
+            e = _torch.empty_like(p, requires_grad=False)                   # dense parameter: same strides
+            e.copy_(p.detach())
+        elif _layout(e) != _layout(p):
+            old, e = e, _torch.empty_like(p, requires_grad=False)
+            e.copy_(old)
+        self._ema_shadows[p] = e
+        return e
+
+    def _param_moved(self, plan, i, p, ptr):
+        """The parameter's data was replaced (p.data = ..., module.to(...)): the row follows it."""
+        _check_param(p)
+        if p.numel() != plan.signature[i]:
+            self._plans = None
+            raise _lib.OrienMaskHipError("orienmask_amd.optim.SGD: a parameter changed its element count; step again")
+        plan.layouts[i] = _layout(p)
+        plan.strides[i] = p.stride()
+        plan.param_ptrs[i] = ptr
+        plan.rows["param"][i] = ptr
+        if plan.shadows is not None and plan.shadows[i] is not None and _layout(plan.shadows[i]) != plan.layouts[i]:
+            shadows = list(plan.shadows)
+            shadows[i] = self._shadow_of(p)                                 # the same values in the new storage order
+            plan.set_shadows(shadows)
 
     @staticmethod
     def _write_hyper(plan, gi, key):
@@ -274,8 +372,9 @@ class SGD(_TorchSGD):
             b = nb
         return b
 
-    def _step_plan(self, plan, clip=None, skip_mode=False):
-        """One device's step; ``clip``: None, or float max_grad_norm (then ``skip_mode``: nonfinite == "skip")."""
+    def _step_plan(self, plan, clip=None, skip_mode=False, ema=None):
+        """One device's step; ``clip``: None, or float max_grad_norm (then ``skip_mode``: nonfinite == "skip"); ``ema``: None, or
+        (ema_decay, ema_warmup)."""
         groups = self.param_groups
         for gi in plan.group_slots:
             g = groups[gi]
@@ -294,15 +393,8 @@ class SGD(_TorchSGD):
                 flags[i] = OM_SGD_SKIP
                 continue
             ptr = p.data_ptr()
-            if ptr != plan.param_ptrs[i]:                 # the parameter's data was replaced (p.data = ..., module.to(...))
-                _check_param(p)
-                if p.numel() != plan.signature[i]:
-                    self._plans = None
-                    raise _lib.OrienMaskHipError("orienmask_amd.optim.SGD: a parameter changed its element count; step again")
-                layouts[i] = _layout(p)
-                strides[i] = p.stride()
-                plan.param_ptrs[i] = ptr
-                rows["param"][i] = ptr
+            if ptr != plan.param_ptrs[i]:
+                self._param_moved(plan, i, p, ptr)
             if g.layout is not _torch.strided or (g.stride() != strides[i] and _layout(g) != layouts[i]):
                 g = self._conform_grad(p, g)
                 keep.append(g)
@@ -337,27 +429,48 @@ class SGD(_TorchSGD):
             return
         rows["grad"] = grad_ptrs
         rows["flags"] = flags
-        k = plan.turn
-        plan.turn = (k + 1) % _RING
-        ev = plan.events[k]
-        if not ev.query():
-            ev.synchronize()                              # the copy out of this staging buffer, _RING steps ago, has not run yet
-        plan.staging_rows[k][:] = rows
+        staging, ev = plan.stage()
         dev = plan.device
         stream = _torch.cuda.current_stream(dev)
+        tables = (staging, plan.table, plan.n, plan.chunks, plan.n_chunks)
         with _lib.on_device(dev):
-            if clip is None:
-                _lib.launch("om_sgd_step", dev, plan.staging[k], plan.table, plan.n, plan.chunks, plan.n_chunks, stream=stream)
+            if clip is None and ema is None:
+                _lib.launch("om_sgd_step", dev, *tables, stream=stream)
+            elif clip is None:
+                if self._ema_on_device:                   # the step form changed after skip mode: the count comes back, once
+                    self.ema_updates()
+                omd = float(_np.float32(1.0 - ema_decay_at(self._ema_k, *ema)))
+                _lib.launch("om_sgd_ema_step", dev, *tables, plan.shadow_ptrs, omd, stream=stream)
+                self._ema_k += 1
+                self._ema_word_valid = False
             else:
                 partials, valid_since = plan.clip_buffers()
                 if self._clip_state is None or self._clip_state.device != dev:
                     self._clip_state = _torch.zeros(OM_CLIP_STATE_DOUBLES, dtype=_torch.float64, device=dev)
                 self._clip_steps += 1
-                _lib.launch("om_sgd_clip_step", dev, plan.staging[k], plan.table, plan.n, plan.chunks, plan.n_chunks, partials,
-                            self._clip_state, valid_since, clip, OM_CLIP_SKIP_NONFINITE if skip_mode else 0, self._clip_steps,
-                            stream=stream)
+                clip_args = (partials, self._clip_state, valid_since, clip, OM_CLIP_SKIP_NONFINITE if skip_mode else 0,
+                             self._clip_steps)
+                if ema is None:
+                    _lib.launch("om_sgd_clip_step", dev, *tables, *clip_args, stream=stream)
+                else:
+                    _lib.launch("om_sgd_clip_ema_step", dev, *tables, *clip_args, plan.shadow_ptrs, self._ema_block(dev),
+                                float(ema[0]), int(bool(ema[1])), stream=stream)
+                    if skip_mode:
+                        self._ema_on_device = True        # only the device knows whether this step was applied
+                    elif not self._ema_on_device:
+                        self._ema_k += 1                  # the device word does the same
             ev.record(stream)
         del keep
+
+    def _ema_block(self, dev):
+        """The device block of om_sgd_clip_ema_step with its count word in step with the host's (a fill, no read)."""
+        if self._ema_state is None or self._ema_state.device != dev:
+            self._ema_state = _torch.zeros(OM_EMA_STATE_DOUBLES, dtype=_torch.int64, device=dev)
+            self._ema_word_valid = self._ema_k == 0 and not self._ema_on_device
+        if not self._ema_word_valid:
+            self._ema_state[OM_EMA_UPDATES_OFF:OM_EMA_UPDATES_OFF + 1].fill_(self._ema_k)
+            self._ema_word_valid = True
+        return self._ema_state
 
     def step(self, closure=None):
         """One optimization step; ``closure`` (optional) re-evaluates the model and returns the loss, as torch's does."""
@@ -368,12 +481,110 @@ class SGD(_TorchSGD):
         _lib.load()
         max_norm, nonfinite = getattr(self, "max_grad_norm", None), getattr(self, "nonfinite", "propagate")
         check_clip(max_norm, nonfinite)
+        decay, warmup = getattr(self, "ema_decay", None), getattr(self, "ema_warmup", True)
+        check_ema(decay, warmup)
         if getattr(self, "_plans", None) is None or self._built_for != self._structure() or self._built_clip != self._clip_key():
             self._build_plans()
         with _torch.no_grad():
             for plan in self._plans:
-                self._step_plan(plan, None if max_norm is None else float(max_norm), nonfinite == "skip")
+                self._step_plan(plan, None if max_norm is None else float(max_norm), nonfinite == "skip",
+                                None if decay is None else (decay, warmup))
         return loss
+
+    # ---- weight EMA -----------------------------------------------------------------------------------------------------------
+    def _ema_plan(self, what):
+        """The one plan of an averaging optimizer, built if need be (its shadows are then bit copies of the parameters)."""
+        if getattr(self, "ema_decay", None) is None:
+            raise _lib.OrienMaskHipError("orienmask_amd.optim.SGD.%s: averaging is not enabled (ema_decay is None)" % what)
+        check_ema(self.ema_decay, self.ema_warmup)
+        if getattr(self, "_plans", None) is None or self._built_for != self._structure() or self._built_clip != self._clip_key():
+            self._build_plans()
+        return self._plans[0]
+
+    def ema_updates(self):
+        """The number of EMA updates applied so far: the host's count, or with nonfinite="skip" (only the device knows which
+        steps were applied) one small device-to-host read of the count word.  That read synchronises; step() never does.  The
+        count carries over when the form of the step changes between steps."""
+        if self._ema_on_device:
+            self._ema_k = int(self._ema_state[OM_EMA_UPDATES_OFF:OM_EMA_UPDATES_OFF + 1].cpu().numpy()[0])
+            self._ema_on_device = False                   # until the next step that may be skipped
+        return self._ema_k
+
+    def ema_shadow(self, p):
+        """The shadow tensor of parameter ``p`` (the live tensor the step kernel updates), or None where ``p`` is not averaged."""
+        plan = self._ema_plan("ema_shadow")
+        for q, e in zip(plan.params, plan.shadows):
+            if q is p:
+                return e
+        return None
+
+    def ema_swap(self):
+        """Exchange every averaged parameter with its shadow, in place, in one launch on the current stream (om_ema_swap).  The
+        tensors keep their addresses: nothing is allocated and no plan is rebuilt.  Twice restores both, bit for bit."""
+        _lib.load()
+        plan = self._ema_plan("ema_swap")
+        for i, p in enumerate(plan.params):
+            ptr = p.data_ptr()
+            if ptr != plan.param_ptrs[i]:
+                self._param_moved(plan, i, p, ptr)
+        staging, ev = plan.stage()
+        dev = plan.device
+        stream = _torch.cuda.current_stream(dev)
+        with _lib.on_device(dev):
+            _lib.launch("om_ema_swap", dev, staging, plan.table, plan.n, plan.chunks, plan.n_chunks, plan.shadow_ptrs, stream=stream)
+            ev.record(stream)
+
+    @_contextlib.contextmanager
+    def ema_applied(self):
+        """``with optimizer.ema_applied():`` the parameters hold the averaged weights inside the block and their own again after it
+        (ema_swap on entry and on exit)."""
+        self.ema_swap()
+        try:
+            yield self
+        finally:
+            self.ema_swap()
+
+    def _ema_names(self, model):
+        """[(state_dict key, shadow)] of the parameters of ``model`` this optimizer averages, matched by tensor identity; a
+        parameter shared by two modules appears under both names."""
+        plan = self._ema_plan("ema_state_dict")
+        shadow = {id(p): e for p, e in zip(plan.params, plan.shadows)}
+        return [(name, shadow[id(p)]) for name, p in model.named_parameters(remove_duplicate=False) if id(p) in shadow]
+
+    def ema_state_dict(self, model):
+        """``model.state_dict()`` with every parameter this optimizer averages replaced by a copy of its shadow.  Buffers (the
+        BatchNorm running statistics are moving averages already) and parameters the optimizer does not hold (frozen stages)
+        are the live tensors."""
+        named = self._ema_names(model)
+        out = model.state_dict()
+        with _torch.no_grad():
+            for name, e in named:
+                if name in out:
+                    out[name] = e.clone()
+        return out
+
+    def load_ema_state_dict(self, model, state_dict, updates):
+        """The inverse of ema_state_dict: the shadows from ``state_dict`` (keys and shapes of the averaged parameters of ``model``
+        must be there; other entries are not read) and the count of applied updates."""
+        if isinstance(updates, bool) or not isinstance(updates, int) or updates < 0:
+            raise ValueError("orienmask_amd.optim.SGD.load_ema_state_dict: updates must be a non-negative int, got %r" % (updates,))
+        named = self._ema_names(model)
+        for name, e in named:
+            if name not in state_dict:
+                raise _lib.OrienMaskHipError("orienmask_amd.optim.SGD.load_ema_state_dict: no entry %r in the state dict" % name)
+            if tuple(state_dict[name].shape) != tuple(e.shape):
+                raise _lib.OrienMaskHipError("orienmask_amd.optim.SGD.load_ema_state_dict: %r has shape %s, the parameter %s"
+                                             % (name, tuple(state_dict[name].shape), tuple(e.shape)))
+        with _torch.no_grad():
+            for name, e in named:
+                e.copy_(state_dict[name])
+        self._ema_k, self._ema_on_device, self._ema_word_valid = updates, False, False
+
+    def ema_reset(self):
+        """Forget the shadows and the count: the next plan copies the parameters as they are then."""
+        self._ema_shadows = {}
+        self._ema_k, self._ema_on_device, self._ema_word_valid = 0, False, False
+        self._plans = None
 
     def grad_norm_stats(self, reset=True):
         """What the clipped steps since the last reset saw, as ONE small device-to-host read of the state block the step kernels

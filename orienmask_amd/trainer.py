@@ -20,6 +20,14 @@ and the error says so).  With ``max_grad_norm`` set, rank 0 also writes ``train/
 ``train/clipped_steps`` and ``train/skipped_steps`` from ``optimizer.grad_norm_stats()`` at each of those reads; without it the
 scalars are unchanged.
 
+Weight EMA.  When the optimizer averages the weights (orienmask_amd.optim.SGD with ``ema_decay``), ``_val_epoch`` runs inside
+``optimizer.ema_applied()``: validation, the monitored value and ``best_*`` refer to the AVERAGED weights (the BatchNorm running
+statistics are the live ones: they are moving averages already), and the parameters are their own again after it.  Every checkpoint,
+``batch_<step>.pth`` included, then has one more key, ``ema = {"state_dict": optimizer.ema_state_dict(model), "updates": n}``, beside
+the reference's, which are unchanged, so the reference still resumes from the file; resuming restores shadows and count, and an
+averaging run resumed from a file without the key starts its average again from the loaded weights and logs that.  Rank 0 writes
+``train/ema_updates`` at the counter's read.  Without ``ema_decay`` files and scalars are what they were.
+
 Other departures from the reference:
   * no ``exit()``: a non-finite loss raises FloatingPointError; reaching ``lr_scheduler.max_iter`` saves ``batch_<step>.pth`` and
     ends ``train()`` (``self.reached_max_iter``);
@@ -30,6 +38,7 @@ Other departures from the reference:
     to ``scalars.jsonl`` in the checkpoint directory; the tables are plain text; without tqdm there is no progress bar;
   * ``COCOMetrics`` is built only when the config has ``val_gt_file`` and there is a validation loader.
 """
+import contextlib
 import datetime
 import json
 import logging
@@ -201,9 +210,20 @@ class BaseTrainer:
             self.logger.info("%s: %s", key, value)
 
     # ---- checkpoints
+    def _averaging(self):
+        """The optimizer keeps an EMA of the weights in its step (orienmask_amd.optim.SGD with ema_decay)."""
+        return getattr(self.optimizer, "ema_decay", None) is not None and hasattr(self.optimizer, "ema_applied")
+
+    def _ema_entry(self, model):
+        """{"ema": ...} of a checkpoint whose state_dict is `model`'s; nothing without averaging: the file is then today's."""
+        if not self._averaging():
+            return {}
+        return dict(ema=dict(state_dict=self.optimizer.ema_state_dict(model), updates=self.optimizer.ema_updates()))
+
     def _checkpoint_state(self, epoch):
         return dict(epoch=epoch, state_dict=self._bare_model().state_dict(), optimizer=self.optimizer.state_dict(),
-                    lr_scheduler=self.lr_scheduler.state_dict(), monitor_best=self.monitor_best, config=self.config)
+                    lr_scheduler=self.lr_scheduler.state_dict(), monitor_best=self.monitor_best, config=self.config,
+                    **self._ema_entry(self._bare_model()))
 
     def _save_checkpoint(self, epoch, save_best=False, temp=False):
         names = []
@@ -242,6 +262,13 @@ class BaseTrainer:
         self._bare_model().load_state_dict(checkpoint["state_dict"], strict=True)
         self.optimizer.load_state_dict(checkpoint["optimizer"])
         self.lr_scheduler.load_state_dict(checkpoint["lr_scheduler"])
+        if self._averaging():
+            if "ema" in checkpoint:
+                self.optimizer.load_ema_state_dict(self._bare_model(), checkpoint["ema"]["state_dict"], checkpoint["ema"]["updates"])
+                self.logger.info("restored the averaged weights after %d updates", checkpoint["ema"]["updates"])
+            else:
+                self.optimizer.ema_reset()
+                self.logger.info("%s holds no averaged weights: the average starts again from the loaded weights", path)
         self.monitor_best = checkpoint["monitor_best"]
         self.start_epoch = checkpoint["epoch"] + 1
         self.logger.info("resumed from %s: epoch %d is next", path, self.start_epoch)
@@ -363,6 +390,8 @@ class Trainer(BaseTrainer):
             for tag, value in (("grad_norm", stats["mean_norm"]), ("grad_norm_max", stats["max_norm"]),
                                ("clipped_steps", stats["clipped_steps"]), ("skipped_steps", skipped)):
                 self.tensorboard.add_scalar("train/%s" % tag, value, at)
+        if self._averaging():
+            self.tensorboard.add_scalar("train/ema_updates", self.optimizer.ema_updates(), at)
         if hasattr(bar, "set_postfix"):
             bar.set_postfix(lr="%.2e" % (groups[0]["lr"] * self.accumulate), loss="%.4f" % means["loss"])
 
@@ -373,7 +402,7 @@ class Trainer(BaseTrainer):
     def _save_at_max_iter(self, step):
         if self.device_rank == 0:
             path = os.path.join(self.checkpoint_dir, "batch_%d.pth" % step)
-            torch.save(dict(state_dict=self.model.state_dict(), config=self.config), path)
+            torch.save(dict(state_dict=self.model.state_dict(), config=self.config, **self._ema_entry(self.model)), path)
             self.logger.info("max_iter reached: wrote %s", path)
         if self.world_size > 1:
             torch.distributed.barrier()
@@ -417,7 +446,9 @@ class Trainer(BaseTrainer):
         if self.sync_free:
             from .loss import DeviceEvalCounter
             counter = DeviceEvalCounter(self.loss, self.device)
-        val_log = validate(self.model, self.loss, self.postprocess, self.val_loader, self.coco_metrics, counter=counter)
+        # an averaging optimizer's weights are validated: the shadows are swapped in for the pass and out again after it
+        with self.optimizer.ema_applied() if self._averaging() else contextlib.nullcontext():
+            val_log = validate(self.model, self.loss, self.postprocess, self.val_loader, self.coco_metrics, counter=counter)
         if self.device_rank != 0:
             return {}
         for key, value in val_log.items():

@@ -10,12 +10,16 @@ and divides.  Reported per variant: median, min and max of the rounds' per-step 
 bytes per second at the median, and the host time per step (what the Python side of step() costs; where it exceeds the device
 time the event figure is host-bound and says so).  The device clock is read before and after where the runtime exposes it.
 
-    python tools/bench_optim.py [--rounds 15] [--inner 20] [--warmup 5] [--max-grad-norm X]
+    python tools/bench_optim.py [--rounds 15] [--inner 20] [--warmup 5] [--max-grad-norm X] [--ema-decay X]
 
 prints one JSON line.  ``--max-grad-norm X`` adds, per grouping, ``hip_clip_*`` -- the same class with ``max_grad_norm=X``: three
 launches of om_sgd_clip_step, one more read of the gradients -- and ``torch_clip_foreach_*``: torch.nn.utils.clip_grad_norm_ on the
 tensors followed by torch's default step (on gradients of its own: it scales them in place), and reports ``clip_over_plain``, the
-ratio of the medians of hip_clip_* and hip_* of the same run.
+ratio of the medians of hip_clip_* and hip_* of the same run.  ``--ema-decay X`` adds ``hip_ema_*`` -- the same class with
+``ema_decay=X``: om_sgd_ema_step, one more stream read and written (7 x 4 bytes per element) -- with ``--max-grad-norm`` also
+``hip_clip_ema_*``, and ``torch_foreach_ema_*``: torch's default step followed by ``torch._foreach_lerp_(shadows, params, 1 - X)``
+(8 x 4 bytes per element, more launches), and reports ``ema_over_plain`` and ``ema_over_torch``.  GBps_at_median counts the bytes
+each variant's own arithmetic has to move.
 """
 import argparse
 import json
@@ -51,6 +55,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--max-grad-norm", type=float, default=None, metavar="X",
                     help="also time the step with gradient-norm clipping at X, and torch's clip_grad_norm_ + step")
+    ap.add_argument("--ema-decay", type=float, default=None, metavar="X",
+                    help="also time the step with the weight EMA fused in (decay X), and torch's step + _foreach_lerp_")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_optim.py needs an MI355X: there is nothing to time on a CPU")
@@ -88,6 +94,18 @@ def main():
             torch.nn.utils.clip_grad_norm_(self.params, self.max_norm)
             self.opt.step()
 
+    class TorchAveraged:
+        """torch.optim.SGD.step() + torch._foreach_lerp_ of the shadows towards the parameters as one step()."""
+
+        def __init__(self, ps, per_tensor, decay):
+            self.params, self.weight = [p.detach() for p in ps], 1.0 - decay
+            self.shadows = [p.detach().clone() for p in ps]
+            self.opt = torch.optim.SGD(groups(ps, per_tensor), **HYPER)
+
+        def step(self):
+            self.opt.step()
+            torch._foreach_lerp_(self.shadows, self.params, self.weight)
+
     def groups(ps, per_tensor):
         if not per_tensor:
             return ps
@@ -100,6 +118,12 @@ def main():
         if args.max_grad_norm is not None:
             variants["hip_clip_" + tag] = O.SGD(groups(fresh_params(), per_tensor), max_grad_norm=args.max_grad_norm, **HYPER)
             variants["torch_clip_foreach_" + tag] = TorchClipped(fresh_params(), per_tensor, args.max_grad_norm)
+        if args.ema_decay is not None:
+            variants["hip_ema_" + tag] = O.SGD(groups(fresh_params(), per_tensor), ema_decay=args.ema_decay, **HYPER)
+            if args.max_grad_norm is not None:
+                variants["hip_clip_ema_" + tag] = O.SGD(groups(fresh_params(), per_tensor), max_grad_norm=args.max_grad_norm,
+                                                        ema_decay=args.ema_decay, **HYPER)
+            variants["torch_foreach_ema_" + tag] = TorchAveraged(fresh_params(), per_tensor, args.ema_decay)
         variants["torch_single_" + tag] = torch.optim.SGD(groups(fresh_params(), per_tensor), foreach=False, **HYPER)
         variants["torch_foreach_" + tag] = torch.optim.SGD(groups(fresh_params(), per_tensor), **HYPER)
         try:
@@ -139,14 +163,28 @@ def main():
     for name in variants:
         v = sorted(dev_ms[name])
         med = statistics.median(v)
+        # 4-byte streams per element: p, g, buf read and p, buf written; + g again for the norm; + shadow read and written (torch's
+        # lerp reads the parameter once more)
+        streams = 5 + ("clip" in name) + (3 if name.startswith("torch_foreach_ema") else 2 if "ema" in name else 0)
+        moved = streams * 4 * elements
         out["variants"][name] = {"ms_median": round(med, 4), "ms_min": round(v[0], 4), "ms_max": round(v[-1], 4),
-                                 "spread_pct": round(100 * (v[-1] - v[0]) / med, 1), "GBps_at_median": round(nbytes / med / 1e6, 1),
+                                 "spread_pct": round(100 * (v[-1] - v[0]) / med, 1), "bytes": moved,
+                                 "GBps_at_median": round(moved / med / 1e6, 1),
                                  "host_ms_median": round(statistics.median(host_ms[name]), 4),
                                  "host_bound": statistics.median(host_ms[name]) > 0.9 * med}
     if args.max_grad_norm is not None:
         out["max_grad_norm"] = args.max_grad_norm
         out["clip_over_plain"] = {tag: round(out["variants"]["hip_clip_" + tag]["ms_median"] /
                                              out["variants"]["hip_" + tag]["ms_median"], 3) for tag in ("1group", "266groups")}
+    if args.ema_decay is not None:
+        def ratio(a, b):
+            return {tag: round(out["variants"][a + tag]["ms_median"] / out["variants"][b + tag]["ms_median"], 3)
+                    for tag in ("1group", "266groups")}
+        out["ema_decay"] = args.ema_decay
+        out["ema_over_plain"] = ratio("hip_ema_", "hip_")
+        out["ema_over_torch"] = ratio("hip_ema_", "torch_foreach_ema_")
+        if args.max_grad_norm is not None:
+            out["clip_ema_over_clip"] = ratio("hip_clip_ema_", "hip_clip_")
     print(json.dumps(out))
 
 

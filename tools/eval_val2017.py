@@ -2,6 +2,8 @@
 on val2017" needs (not runnable offline -- no checkpoint, no COCO, no pycocotools in this image).
 
     python tools/eval_val2017.py --ckpt checkpoints/OrienMaskAnchor4FPNPlus/orienmask_yolo.pth --coco-root /data/coco
+    python tools/eval_val2017.py --ckpt RUN/best_model.pth --ema --coco-root /data/coco      # the averaged weights of a run trained
+                                                                             # with optimizer.ema_decay (the checkpoint's "ema" entry)
     python tools/eval_val2017.py --synthetic 12 --out /tmp/val_dry          # this container / the GPU box: everything up to the
                                                                              # json files pycocotools would be handed
 
@@ -129,6 +131,16 @@ def coco_eval(gt_file, out_dir, with_mask=True, evaluator="pycocotools"):
     return out
 
 
+def ema_checkpoint(ckpt, use_ema, path="the checkpoint"):
+    """`ckpt` as it is, or with --ema a copy whose state_dict is its averaged weights; a file without them is refused."""
+    if not use_ema:
+        return ckpt
+    ema = ckpt.get("ema") if isinstance(ckpt, dict) else None
+    if not (isinstance(ema, dict) and "state_dict" in ema):
+        raise SystemExit("--ema: %s holds no averaged weights (no 'ema' entry: it was not trained with optimizer.ema_decay)" % path)
+    return dict(ckpt, state_dict=ema["state_dict"])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ckpt", "-w", default=None, help="reference checkpoint (.pth with 'state_dict' and 'config')")
@@ -143,6 +155,9 @@ def main():
                     help="who scores the json files: pycocotools (default) or orienmask_amd.cocoeval (HIP, no pycocotools)")
     ap.add_argument("--synthetic", type=int, default=0,
                     help="no data: N synthetic images through a seeded random checkpoint, up to the json files (no AP)")
+    ap.add_argument("--ema", action="store_true",
+                    help="evaluate the checkpoint's averaged weights (ckpt['ema']['state_dict'], written by a run trained with "
+                         "optimizer.ema_decay); a checkpoint without them is refused")
     args = ap.parse_args()
     from orienmask_amd.builder import build_tester
     from orienmask_amd.coco_format import COCOFormatter
@@ -160,12 +175,12 @@ def main():
     dev = torch.device("cuda", torch.cuda.current_device())
     os.makedirs(args.out, exist_ok=True)
     if args.synthetic:
-        ckpt = synthetic_checkpoint()
+        ckpt = ema_checkpoint(synthetic_checkpoint(), args.ema, "the synthetic checkpoint")
         loader = SyntheticLoader(args.synthetic, args.batch, seed=17, device=dev)
     else:
         if not args.ckpt:
             raise SystemExit("--ckpt is required (or --synthetic N)")
-        ckpt = torch.load(args.ckpt, map_location="cpu", weights_only=False)
+        ckpt = ema_checkpoint(torch.load(args.ckpt, map_location="cpu", weights_only=False), args.ema, args.ckpt)
         if not (isinstance(ckpt, dict) and isinstance(ckpt.get("config"), dict) and "model" in ckpt["config"]):
             sd = ckpt["state_dict"] if isinstance(ckpt, dict) and "state_dict" in ckpt else ckpt      # a bare state_dict: infer.py:81-83
             ckpt = {"state_dict": sd, "config": {"model": dict(DEFAULT_MODEL)}}

@@ -2,6 +2,7 @@
 
     python tools/train.py --config CONFIG [--resume CHECKPOINT | --weights WEIGHTS] [--synthetic N] [--frozen-stages K] [--amp bf16]
                           [--conv-forward {torch,hip}] [--conv-grad {torch,hip}] [--max-grad-norm X] [--nonfinite-grads {propagate,skip}]
+                          [--ema-decay X] [--no-ema-warmup]
 
 CONFIG is a JSON file -- the ``config.json`` a trainer writes into its checkpoint directory is one -- or, where a ``config``
 package with the reference's ``get_config`` is importable, a config name.  ``--synthetic N`` trains on N seeded synthetic images
@@ -16,7 +17,9 @@ blocks one fused kernel each; without amp it needs the config's ``conv_backend``
 (csrc/conv_grad_bf16.hip), and a step repeats bit for bit.  ``--max-grad-norm X`` sets the optimizer's ``max_grad_norm`` (global L2
 gradient-norm clipping inside the HIP SGD step, orienmask_amd.optim.SGD) and ``--nonfinite-grads skip`` its ``nonfinite``: a step
 whose gradient norm is not finite leaves parameters and momentum buffers untouched, so a diverged run stops with its last finite
-weights.  With several processes (torchrun), each uses the GPU of its LOCAL_RANK.
+weights.  ``--ema-decay X`` sets the optimizer's ``ema_decay``: an exponential moving average of the weights kept inside the same
+step kernel, which validation, the monitored value and the checkpoint's ``ema`` entry then use (``--no-ema-warmup`` sets
+``ema_warmup`` to False: the decay is X from the first update on).  With several processes (torchrun), each uses the GPU of its LOCAL_RANK.
 """
 import argparse
 import json
@@ -58,6 +61,12 @@ def parse_args(argv=None):
     ap.add_argument("--nonfinite-grads", choices=["propagate", "skip"], default=None,
                     help="with --max-grad-norm: what a step does whose gradient norm is not finite (the optimizer's nonfinite), "
                          "overriding the config's optimizer.nonfinite")
+    ap.add_argument("--ema-decay", type=float, default=None, metavar="X",
+                    help="average the weights inside the SGD step with decay X (the optimizer's ema_decay), overriding the "
+                         "config's optimizer.ema_decay")
+    ap.add_argument("--no-ema-warmup", action="store_true",
+                    help="with an averaging optimizer: no warm-up of the decay (the optimizer's ema_warmup=False), overriding the "
+                         "config's optimizer.ema_warmup")
     args = ap.parse_args(argv)
     assert not (args.resume and args.weights), "--resume and --weights exclude each other"
     return args
@@ -78,6 +87,10 @@ def apply_overrides(config, args):
         config = dict(config, optimizer=dict(config["optimizer"], max_grad_norm=args.max_grad_norm))
     if args.nonfinite_grads is not None:
         config = dict(config, optimizer=dict(config["optimizer"], nonfinite=args.nonfinite_grads))
+    if args.ema_decay is not None:
+        config = dict(config, optimizer=dict(config["optimizer"], ema_decay=args.ema_decay))
+    if args.no_ema_warmup:
+        config = dict(config, optimizer=dict(config["optimizer"], ema_warmup=False))
     return config
 
 
