@@ -9,7 +9,14 @@
  * kernel-choice switches (om_set_*_variant, om_set_stem_fusion: A/B runs and tests) and the unit-test entries at the end, which
  * own a hipMalloc'ed tile-queue word each.
  * Threading: forwards of one om_model may be enqueued from several host threads when every thread uses its own stream and its
- * own workspace.  The caller serialises (a) stream captures of one model (they share one second stream), (b) om_profile_* and
+ * own workspace.  WORKSPACES: a `workspace` / `scratch` / `partials` argument is memory the entry may use as it likes for the
+ * duration of the call and whose CONTENTS ARE UNDEFINED ON ENTRY: every entry clears, writes or masks what it later reads, on the
+ * stream it is handed, and its outputs do not depend on what the memory held (old activations, NaNs, stale tickets and counts:
+ * tests/test_workspace_contract.py fills it with 0x00 / 0xFF / 0x7C / 0x01 and compares the outputs bit for bit).  The same holds
+ * for every output buffer: an entry never reads an output element before writing it.  The ONLY words a caller must initialise are
+ * named where they are declared: om_sgd_clip_step's valid_since and clip state, om_sgd_clip_ema_step's EMA state (zeroed once),
+ * om_recover_masks_rle_strings' str_cursor (zeroed per call), om_conv2d_split*'s optional status_dev, and om_loss_accumulate's
+ * counter block.  The caller serialises (a) stream captures of one model (they share one second stream), (b) om_profile_* and
  * (c) more than 64 caller streams with an attached postprocess at once.  The reference's plugin surface is single-threaded
  * under the GIL and never leaves this contract.
  *
@@ -174,7 +181,10 @@ int om_model_get_precision(const om_model* m);
 int om_model_set_upsample_on_read(om_model* m, int enable);
 
 size_t om_forward_workspace_bytes(const om_model* m, int B, int H, int W);
-/* x: [B,3,H,W] float32 NCHW, H and W multiples of 32.
+/* workspace: om_forward_workspace_bytes bytes, 256-byte aligned, contents undefined on entry -- activations and Winograd scratch
+ * (shared by live range), the partial-tile area of the stream-K / split-K forms, one block of queue / flag / arrival words per
+ * layer and the status word; om_forward clears the words on `stream` before its first layer and nothing else needs clearing.
+ * x: [B,3,H,W] float32 NCHW, H and W multiples of 32.
  * bbox32/16/8: [B, H/s, W/s, 256] float32 NHWC, channels [0, A*(5+C)) valid  (the caller views
  *              them as [B, A*(5+C), H/s, W/s] with strides)
  * oriens:      [B, 6*A, H/4, W/4] float32 NCHW contiguous */
@@ -198,7 +208,7 @@ size_t om_forward_status_offset(const om_model* m, int B, int H, int W);
  * om_model_load_weights_f16 (the fp16 weights laid out per om_layer_info.w16_off, om_model_weight_halfs() halfs). */
 size_t om_model_weight_halfs(const om_model* m);
 int om_model_load_weights_f16(om_model* m, const void* packed_f16_dev, size_t bytes);
-size_t om_forward_f16_workspace_bytes(const om_model* m, int B, int H, int W);
+size_t om_forward_f16_workspace_bytes(const om_model* m, int B, int H, int W);      /* contents undefined on entry, as om_forward's */
 int om_forward_f16(om_model* m, const float* x, int B, int H, int W, float* bbox32, float* bbox16, float* bbox8,
                    float* oriens, void* workspace, size_t ws_bytes, om_stream stream);
 /* kernel that runs layer `index` in the fp16 configuration (6 = conv3x3_f16_tall_kernel<512,128>, 7 = conv_stem2_f16_kernel: the first
@@ -391,7 +401,11 @@ int om_preprocess(const float* in_nhwc, int N, int h, int w, int resize_h, int r
 int om_pad_nchw(const float* in, long long planes, int h, int w, int pad_top, int pad_left, int out_h, int out_w,
                 float pad_value, float* out, om_stream stream);
 
-/* ---- postprocess -------------------------------------------------------------------------- */
+/* ---- postprocess --------------------------------------------------------------------------
+ * workspace (every om_postprocess* entry and the buffer handed to om_model_attach_postprocess): om_postprocess_workspace_bytes
+ * bytes, 256-byte aligned, contents undefined on entry -- candidate keys, per-tile counts, the radix histograms and the list
+ * counter (cleared by the entry), the compacted candidate list, the detections' mask constants and, for nms_pre > 512, the
+ * suppression bit matrix.  om_postprocess_assemble reads what om_postprocess_detect left there; om_postprocess_masks nothing. */
 size_t om_postprocess_workspace_bytes(const om_post_cfg* cfg, int B);
 /* Limits of the fused path (the reference has none): nms_pre <= 1024; 1..3 scales of 1..3 anchors; conf_thresh >= 0 (the
  * decode skips a candidate whose sigmoid(objectness) is not above it before reading its class logits); num_classes such that
@@ -467,7 +481,8 @@ int om_recover_masks_rle(const uint8_t* mask, int K, int H, int W, int crop_top,
  *   image after image.  counts [sum K][max_runs] scratch for the run lengths, n_runs [sum K] (> max_runs: that mask needs a
  *   larger buffer, its str_off is -1).  Every mask appends its string to ONE byte buffer: str_cursor[0] = bytes reserved
  *   (zeroed by the caller), str_cursor[1] = masks whose string did not fit str_capacity; str_off / str_len [sum K].  The host
- *   then copies the cursor + offsets and bytes[0:cursor] once per batch instead of 30 MB of masks per image. */
+ *   then copies the cursor + offsets and bytes[0:cursor] once per batch instead of 30 MB of masks per image.  counts, n_runs,
+ *   str_bytes, str_off and str_len: contents undefined on entry; both str_cursor words are the caller's to zero. */
 typedef struct om_rle_image {
     const uint8_t* mask;        /* [K,H,W] u8 0/1, device */
     int32_t K, H, W;
@@ -580,7 +595,8 @@ int om_ref_math(const float* x, long long n, int func, int num_classes, float* y
  *      om_nms = om_nms_ex(semantics 0): the CPU backend (IoU >= thresh suppresses, areas from the corners cx +- w/2, keep
  *      in ascending input order, nms_cpu.cpp:4-63).  semantics 1: the CUDA backend (IoU > thresh, areas w*h, keep in
  *      score-descending order, nms_kernel.cu:13-140); score ties, which torch's CUDA sort leaves unspecified, are visited
- *      in ascending input order. */
+ *      in ascending input order.  workspace: om_nms_workspace_bytes(n) bytes, 256-byte aligned, contents undefined on entry (the
+ *      sorted boxes and the suppression bit matrix); keep is defined below *n_keep. */
 size_t om_nms_workspace_bytes(int n);
 int om_nms(const float* dets, int n, float thresh, int64_t* keep, int32_t* n_keep, void* workspace,
            size_t ws_bytes, om_stream stream);
@@ -603,7 +619,10 @@ int om_nms_ex(const float* dets, int n, float thresh, int semantics, int64_t* ke
  * om_loss writes `result` (device, OM_LOSS_RESULT_FLOATS floats): per scale s at s*OM_LOSS_SCALE_FLOATS the 7 weighted terms
  * (loss_xy, loss_wh, loss_obj, loss_noobj, loss_cls, loss_orien_pos, loss_orien_neg) then 8 (numerator, count) pairs
  * (cls_conf, obj_pos, obj_neg, avg_iou, recall50, recall75, orien_pos_acc, orien_neg_acc); at OM_LOSS_FLAG_OFF a flag word
- * (int32 bits, OM_LOSS_FLAG_*).  No host synchronisation, no allocation; workspace: om_loss_workspace_bytes(cfg, B, N).
+ * (int32 bits, OM_LOSS_FLAG_*).  No host synchronisation, no allocation; workspace: om_loss_workspace_bytes(cfg, B, N) bytes,
+ * 256-byte aligned, contents undefined on entry (the match records and the partial sums; the layout moves with N, and a larger
+ * workspace kept from another call is as good as a fresh one); `result` is cleared by the call.  N = 0 (a batch without a GT):
+ * gt_bbox, gt_cls and gt_mask are not addressed and may be null.
  * The result is bit-identical from call to call: every sum has a fixed order (workgroup partials, then one fixed-order pass).
  *
  * om_loss_targets (test entry): scale s's built targets.  Any output may be null.  [B][A][nH][nW](x2 / xC) f32: bbox_pos,
@@ -655,7 +674,8 @@ int om_loss_targets(const om_loss_cfg* cfg, const float* const* bbox, int B, con
  *      Call it after om_loss on the same cfg, heads and targets, with that call's `result` and `workspace` untouched since: it reads
  *      the match records from the workspace and the bbox_pos / orientation pos / neg counts from the result vector.  grad_bbox[s]
  *      and grad_orien[s] are written through the SAME strides as the heads (cfg->bbox_stride / orien_stride), every element exactly
- *      once, zeros included; the result is bit-identical from call to call.  Two launches; no atomics, no allocation. */
+ *      once, zeros included; the result is bit-identical from call to call.  Two launches; no atomics, no allocation.  (Like
+ *      om_postprocess_assemble, an entry whose workspace is an INPUT: what it held before om_loss does not matter.) */
 int om_loss_backward(const om_loss_cfg* cfg, const float* const* bbox, const float* const* orien, int B, const int64_t* gt_index,
                      const uint8_t* gt_mask, int N, const float* result, const void* workspace, size_t ws_bytes,
                      const float* grad_out, const float* scales_weight, float* const* grad_bbox, float* const* grad_orien,

@@ -337,7 +337,8 @@ int launch_coco_raster(const char* who, int n_poly, int n_srcs, const int32_t* s
                        const int64_t* src_data_off, const int32_t* src_len, const int64_t* src_word_off, const int32_t* mask_hw,
                        const double* poly, const uint32_t* counts, const uint8_t* strings, uint32_t* bitmaps, long long bitmap_words,
                        hipStream_t st) {
-    OM_CHECK_HIP(hipMemsetAsync(bitmaps, 0, (size_t)bitmap_words * 4, st));
+    if (bitmap_words > 0)
+        if (int rc = launch_zero_words(bitmaps, (size_t)bitmap_words, st)) return rc;
     if (n_poly > 0) {
         OM_REQUIRE(poly, OM_EINVAL, "%s: polygons without coordinates", who);
         hipLaunchKernelGGL(coco_poly_toggle_kernel, dim3(n_poly), dim3(64), 0, st, src_mask, src_data_off, src_len, src_word_off,

@@ -533,7 +533,8 @@ static int loss_run(const om_loss_cfg* cfg, const float* const* bbox, const floa
                "anchors, image sides divisible by 4)", what, OM_LOSS_MAX_CLASSES);
     OM_REQUIRE(B >= 1 && N >= 0 && N <= B * OM_LOSS_MAX_GT, OM_EINVAL, "%s: B = %d, N = %d (at most %d GTs per image)", what, B, N,
                OM_LOSS_MAX_GT);
-    OM_REQUIRE(bbox && gt_bbox && gt_cls && gt_index && gt_mask && workspace && result, OM_EINVAL, "%s: null pointer", what);
+    // N == 0 (a batch without a single GT): the GT arrays are never addressed and may be null, which is what an empty tensor hands over
+    OM_REQUIRE(bbox && gt_index && workspace && result && (N == 0 || (gt_bbox && gt_cls && gt_mask)), OM_EINVAL, "%s: null pointer", what);
     for (int s = 0; s < cfg->num_scales; ++s) OM_REQUIRE(bbox[s] && (!orien || orien[s]), OM_EINVAL, "%s: null head of scale %d", what, s);
     const LossLayout L = loss_layout(cfg, B, N);
     OM_REQUIRE(ws_bytes >= L.total, OM_ENOMEM, "%s: workspace of %zu bytes, %zu needed", what, ws_bytes, L.total);
@@ -557,7 +558,7 @@ static int loss_run(const om_loss_cfg* cfg, const float* const* bbox, const floa
     p.tiles = L.tiles;
     p.tiles_x = L.tiles_x;
     p.result = result;
-    OM_CHECK_HIP(hipMemsetAsync(result, 0, OM_LOSS_RESULT_FLOATS * sizeof(float), st));
+    if (int rc = launch_zero_words(result, OM_LOSS_RESULT_FLOATS, st)) return rc;
     const int S = cfg->num_scales;
     hipLaunchKernelGGL(loss_match_kernel, dim3((std::max(N, B + 1) + 255) / 256, S), dim3(256), 0, st, p);
     OM_CHECK_HIP(hipGetLastError());
@@ -900,7 +901,7 @@ int om_loss_backward(const om_loss_cfg* cfg, const float* const* bbox, const flo
                      om_stream stream) {
     OM_REQUIRE(om::loss_cfg_ok(cfg), OM_EINVAL, "om_loss_backward: unsupported configuration");
     OM_REQUIRE(B >= 1 && N >= 0 && N <= B * OM_LOSS_MAX_GT, OM_EINVAL, "om_loss_backward: B = %d, N = %d", B, N);
-    OM_REQUIRE(bbox && orien && grad_bbox && grad_orien && gt_index && gt_mask && result && workspace && grad_out && scales_weight,
+    OM_REQUIRE(bbox && orien && grad_bbox && grad_orien && gt_index && (N == 0 || gt_mask) && result && workspace && grad_out && scales_weight,
                OM_EINVAL, "om_loss_backward: null pointer");
     const om::LossLayout L = om::loss_layout(cfg, B, N);
     OM_REQUIRE(ws_bytes >= L.total, OM_ENOMEM, "om_loss_backward: workspace of %zu bytes, %zu needed", ws_bytes, L.total);

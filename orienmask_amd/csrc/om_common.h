@@ -179,7 +179,9 @@ bool wino_enabled();
 int wino_bn(long long T, int cout_pad);   // N tile of the Winograd GEMM behind a transform kernel of its own, at this size
 bool wino_fused_for(int cin);     // true: the input transform is fused into the GEMM's loader   // tile shape launch_conv_igemm picks
 // Clears n 32-bit words with a kernel.  The library never uses hipMemsetAsync: a memset node captured
-// into a hipGraph was observed (ROCm 7.2, DESIGN.md "hipGraph") to leave part of the range uncleared on replay.
+// into a hipGraph was observed (ROCm 7.2, DESIGN.md "hipGraph") to leave part of the range uncleared on replay.  Every clear an
+// entry owes its workspace or outputs goes through here: the forward's queue / flag / status words, the postprocess histograms,
+// om_loss's result vector, the COCO bitmaps (include/orienmask_hip.h: "contents undefined on entry").
 int launch_zero_words(void* ptr, size_t n_words, hipStream_t stream);
 // cocoeval.hip: stage 1 of the COCO mask builders, shared with segm_decode.hip -- zero the bitmaps, XOR every source's toggles in
 // (polygons: sources [0, n_poly); counts and strings behind them), prefix XOR.  `who` names the caller in error messages.
