@@ -861,6 +861,59 @@ int om_sgd_clip_ema_step(const om_sgd_tensor* table_host, om_sgd_tensor* table, 
 int om_ema_swap(const om_sgd_tensor* table_host, om_sgd_tensor* table, int n_tensors, const om_sgd_chunk* chunks, int n_chunks,
                 float* const* shadows, om_stream stream);
 
+/* ---- The Adam family: torch.optim.Adam / AdamW (amsgrad=False) for every tensor of every parameter group, with the SGD step's
+ *      chunk list, staging, clipping, skip decision and EMA; orienmask_amd/optim.py (HipAdam, HipAdamW) is the host side.  Per
+ *      element, float32, every operation rounded once, sqrt and / IEEE-correct, denormals kept:
+ *          g   = g * coef                                  (clipped form only; ahead of everything else; memory is not modified)
+ *          g   = -g                                        (OM_ADAM_MAXIMIZE)
+ *          p   = p * dm                                    (OM_ADAM_HAS_WD and OM_ADAM_DECOUPLED: AdamW)
+ *          g   = fma(p, weight_decay, g)                   (OM_ADAM_HAS_WD alone: Adam)
+ *          d   = g - m
+ *          m'  = |w| < 0.5 ? fma(w, d, m) : fma(w - 1, d, g)          (lerp; w - 1 in float32)
+ *          v'  = fma(omb2 * g, g, v * beta2)                          (both products rounded)
+ *          den = sqrt(v') / bc2s + eps
+ *          p'  = p + (nss * m') / den                                 (three roundings, no fma)
+ *      and, with shadows, the EMA of om_sgd_ema_step on p'.
+ *      table / table_host: n_tensors rows of 96 bytes (csrc/optim.hip: struct om_adam_tensor; optim.ADAM_ROW in Python), staged as
+ *      om_sgd_step stages its rows:
+ *          float* param; const float* grad; float* exp_avg; float* exp_avg_sq;   dense, n floats each, one storage order
+ *          int64_t n;
+ *          double lr;                the group's lr (read for OM_ADAM_DEVICE_COUNTED rows only)
+ *          float w, beta2, omb2, eps;                 float32(1 - beta1), float32(beta2), float32(1 - beta2), float32(eps)
+ *          float weight_decay, dm, nss, bc2s;         float32(wd), float32(1 - lr * wd), float32(-(lr / bc1)), float32(bc2s), with
+ *                                    bc1 = 1 - beta1**step and bc2s = (1 - beta2**step) ** 0.5 in the host's doubles
+ *          int32_t bias_table;       which bias table the row's betas use (OM_ADAM_DEVICE_COUNTED)
+ *          uint32_t flags;           OM_ADAM_*
+ *          uint32_t reserved[2];
+ *      chunks: om_sgd_step's work list.  16-byte accesses where all four (with shadows, five) streams are 16-byte aligned, 4-byte
+ *      accesses otherwise; every element is written exactly once; no atomics, no allocation, no host synchronisation.
+ *      om_adam_step: ONE launch.  shadows may be null (no EMA; omd is then not read); otherwise omd as in om_sgd_ema_step.  A row
+ *      flagged OM_ADAM_DEVICE_COUNTED is refused.
+ *      om_adam_clip_step: THREE launches as om_sgd_clip_step (partials, state, max_norm, mode, step as there; shadows may be null,
+ *      otherwise ema_state, decay and warmup as in om_sgd_clip_ema_step).  counts: n_tensors int64, caller-owned, the number of
+ *      steps APPLIED to each tensor.  The single workgroup that takes the skip decision adds 1 to the count of every row flagged
+ *      OM_ADAM_DEVICE_COUNTED and not OM_ADAM_SKIP when the step is not skipped; a skipped step leaves parameters, both moments,
+ *      every count, every shadow and the EMA block bit-unchanged.  The update of such a row takes its step number k from counts
+ *      and its corrections from the bias tables: bias holds (bc1, bc2s) pairs of doubles, table after table; bias_dir holds, per
+ *      table, int64 (first pair, pairs); pair k of a table is step k's, and for k at or beyond the table's length both are 1.0.
+ *      Then nss = float32(-(lr / bc1)) with one IEEE double division and bc2s = float32(bc2s).  Rows without the flag use the
+ *      row's own nss and bc2s and leave their count alone.
+ *      om_adam_ema_swap: om_ema_swap over om_adam_tensor rows. */
+#define OM_ADAM_SKIP 1
+#define OM_ADAM_MAXIMIZE 2
+#define OM_ADAM_HAS_WD 4
+#define OM_ADAM_DECOUPLED 8
+#define OM_ADAM_DEVICE_COUNTED 16
+#define OM_ADAM_ROW_BYTES 96
+int om_adam_step(const void* table_host, void* table, int n_tensors, const om_sgd_chunk* chunks, int n_chunks,
+                 float* const* shadows, float omd, om_stream stream);
+int om_adam_clip_step(const void* table_host, void* table, int n_tensors, const om_sgd_chunk* chunks, int n_chunks, double* partials,
+                      double* state, long long* counts, const double* bias, const long long* bias_dir, int n_bias_tables,
+                      float max_norm, int mode, long long step, float* const* shadows, double* ema_state, double decay, int warmup,
+                      om_stream stream);
+int om_adam_ema_swap(const void* table_host, void* table, int n_tensors, const om_sgd_chunk* chunks, int n_chunks,
+                     float* const* shadows, om_stream stream);
+
 /* ---- The Conv -> BatchNorm2d -> LeakyReLU(0.1) block of the reference without its convolution (model/base.py:104-137,278-279: the
  *      nn.BatchNorm2d and nn.LeakyReLU of ConvBNRelu.conv_block), optionally with the residual add that closes a DarkNet block
  *      (model/backbone/darknet.py:14-15 `x + self.conv(x)`), for the training forward of trainer/trainer.py:47 and its backward (:52).

@@ -75,8 +75,9 @@ def build_tester(config, checkpoint, test_loader, device=None, on_batch=None):
 def build_optimizer(config, accumulate, model, is_distributed=False):
     """trainer/builder.py:118-130 against orienmask_amd.optim: the learning rate is divided by `accumulate`; an optional
     `param_groups` entry is resolved by orienmask_amd.optim.param_groups with `base_lr` / `weight_decay` injected from the
-    optimizer's; a DistributedDataParallel wrapper is looked through (`.module`).  `config['type']` "SGD" is the HIP step, any
-    other torch.optim name is torch's.  The caller's dicts are not mutated."""
+    optimizer's; a DistributedDataParallel wrapper is looked through (`.module`).  `config['type']` "SGD", "HipAdam" and "HipAdamW" are
+    the HIP steps (with their `max_grad_norm` / `nonfinite` / `ema_decay` / `ema_warmup` keys), any other torch.optim name -- "Adam"
+    and "AdamW" included -- is torch's.  The caller's dicts are not mutated."""
     import copy
     from . import optim as _optim
     model = model.module if is_distributed else model

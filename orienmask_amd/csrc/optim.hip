@@ -28,7 +28,31 @@
 // Arithmetic: torch.optim.SGD's, in torch-CPU's float32 rounding: every x.add(y, alpha=a) of the update
 // is ONE fused multiply-add fma(y, float32(a), x); buf.mul_(momentum) is a product rounded on its own.  The fmas are written out
 // and the file is built with -ffp-contract=off, so the compiler neither splits them nor folds buf * momentum into the next one.
+// The Adam family (orienmask_amd.optim.HipAdam / HipAdamW) walks the same chunk table with a row of its
+// own, om_adam_tensor, and a kernel of its own, adam_step_kernel<CLIP, EMA>; the norm, the decision (clip_decide) and the swap are
+// the kernels above instantiated for its row.  adam_clip_finish_kernel is the single workgroup of the clipped Adam step: lane 0
+// decides as clip_finish_kernel does, then, when the step is not skipped, lane l adds 1 to the applied-step count of rows l,
+// l + 256, ... that are flagged OM_ADAM_DEVICE_COUNTED and not OM_ADAM_SKIP (one writer per word).  The update reads that count
+// and takes the two bias corrections of the step from a host-built table (CPython's doubles; no pow on the device).
 #include "om_common.h"
+
+// one tensor of the Adam step as orienmask_amd/optim.py packs it (ADAM_ROW); include/orienmask_hip.h documents the fields
+struct om_adam_tensor {
+    float* param;
+    const float* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    int64_t n;
+    double lr;
+    float w, beta2, omb2, eps;
+    float weight_decay, dm, nss, bc2s;
+    int32_t bias_table;
+    uint32_t flags;
+    uint32_t reserved[2];
+};
+static_assert(sizeof(om_adam_tensor) == 96 && offsetof(om_adam_tensor, lr) == 40 && offsetof(om_adam_tensor, flags) == 84,
+              "the Adam row as orienmask_amd/optim.py packs it");
+static_assert(OM_ADAM_SKIP == OM_SGD_SKIP, "the norm kernel tests one bit for both row types");
 
 namespace om {
 
@@ -94,15 +118,16 @@ __device__ __forceinline__ double block_tree_sum(double v, double* wave_sums) {
 }
 static_assert(SGD_THREADS == 256, "block_tree_sum combines four waves of 64");
 
+template <class Row>
 __global__ void __launch_bounds__(SGD_THREADS)
-grad_sumsq_kernel(const om_sgd_tensor* __restrict__ tensors, int n_tensors, const om_sgd_chunk* __restrict__ chunks, int n_chunks,
+grad_sumsq_kernel(const Row* __restrict__ tensors, int n_tensors, const om_sgd_chunk* __restrict__ chunks, int n_chunks,
                   double* __restrict__ partials) {
     __shared__ double wave_sums[SGD_THREADS / 64];
     for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {                 // c is the same for the whole workgroup
         const om_sgd_chunk ck = chunks[c];
         double acc = 0.0;
         if ((unsigned)ck.tensor < (unsigned)n_tensors && ck.chunk >= 0) {
-            const om_sgd_tensor t = tensors[ck.tensor];
+            const Row t = tensors[ck.tensor];
             const long long n = t.n;
             const long long start = (long long)ck.chunk * OM_SGD_CHUNK;
             if (!(t.flags & OM_SGD_SKIP) && start < n) {
@@ -136,15 +161,11 @@ grad_sumsq_kernel(const om_sgd_tensor* __restrict__ tensors, int n_tensors, cons
     }
 }
 
+// the decision of a clipped step, taken by ONE lane from the sum of squares S: norm, coefficient, skip and the running statistics
+// into the state block, and under EMA the decay of this update and its count.  Returns the skip decision.
 template <bool EMA>
-__global__ void __launch_bounds__(SGD_THREADS)
-clip_finish_kernel(const double* __restrict__ partials, int n_chunks, float max_norm, int mode, long long step,
-                   double* __restrict__ state, const SgdEma ema) {
-    __shared__ double wave_sums[SGD_THREADS / 64];
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < n_chunks; i += SGD_THREADS) acc += partials[i];
-    const double S = block_tree_sum(acc, wave_sums);
-    if (threadIdx.x != 0) return;
+__device__ __forceinline__ bool clip_decide(double S, float max_norm, int mode, long long step, double* __restrict__ state,
+                                            const SgdEma& ema) {
     const float norm = (float)__dsqrt_rn(S);
     // torch: max_norm / (total_norm + 1e-6) is (total_norm + 1e-6).reciprocal() * max_norm, each operation rounded to float32
     float coef = __fmul_rn(__fdiv_rn(1.0f, __fadd_rn(norm, 1e-6f)), max_norm);
@@ -176,6 +197,39 @@ clip_finish_kernel(const double* __restrict__ partials, int n_chunks, float max_
             ema.state[OM_EMA_OMD_OFF] = (double)(float)(1.0 - d);
             *updates += 1;
         }
+    }
+    return words[OM_CLIP_SKIP_OFF] != 0;
+}
+
+template <bool EMA>
+__global__ void __launch_bounds__(SGD_THREADS)
+clip_finish_kernel(const double* __restrict__ partials, int n_chunks, float max_norm, int mode, long long step,
+                   double* __restrict__ state, const SgdEma ema) {
+    __shared__ double wave_sums[SGD_THREADS / 64];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n_chunks; i += SGD_THREADS) acc += partials[i];
+    const double S = block_tree_sum(acc, wave_sums);
+    if (threadIdx.x != 0) return;
+    clip_decide<EMA>(S, max_norm, mode, step, state, ema);
+}
+
+// the same workgroup for the Adam rows: after the decision, the applied-step counts of the device-counted rows
+template <bool EMA>
+__global__ void __launch_bounds__(SGD_THREADS)
+adam_clip_finish_kernel(const double* __restrict__ partials, int n_chunks, float max_norm, int mode, long long step,
+                        double* __restrict__ state, const SgdEma ema, const om_adam_tensor* __restrict__ tensors, int n_tensors,
+                        long long* __restrict__ counts) {
+    __shared__ double wave_sums[SGD_THREADS / 64];
+    __shared__ int skipped;
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n_chunks; i += SGD_THREADS) acc += partials[i];
+    const double S = block_tree_sum(acc, wave_sums);
+    if (threadIdx.x == 0) skipped = clip_decide<EMA>(S, max_norm, mode, step, state, ema) ? 1 : 0;
+    __syncthreads();
+    if (skipped) return;                                    // every count stays
+    for (int i = threadIdx.x; i < n_tensors; i += SGD_THREADS) {
+        const unsigned f = tensors[i].flags;
+        if ((f & OM_ADAM_DEVICE_COUNTED) && !(f & OM_ADAM_SKIP)) counts[i] += 1;
     }
 }
 
@@ -286,19 +340,160 @@ sgd_step_kernel(const om_sgd_tensor* __restrict__ tensors, int n_tensors, const 
     }
 }
 
+// ---- the Adam family ---------------------------------------------------------------------------------------------------------
+// what the clipped Adam step reads beside the tables (unused by adam_step_kernel<false, EMA>)
+struct AdamClip {
+    const double* state;        // the OM_CLIP_* block adam_clip_finish_kernel wrote on this stream
+    const long long* counts;    // per tensor: applied steps INCLUDING this one (rows under OM_ADAM_DEVICE_COUNTED)
+    const double* bias;         // the bias tables, one after the other: row k = (1 - beta1**k, (1 - beta2**k) ** 0.5)
+    const long long* bias_dir;  // per table: (first row in `bias`, rows); from its last row on both corrections are 1.0
+    int n_bias;
+};
+
+struct AdamHyper {
+    float w, wm1, beta2, omb2, eps, wd, dm, nss, bc2s;
+    bool low, maximize, has_wd, decoupled;
+};
+
+// one element of torch.optim.Adam / AdamW (_single_tensor_adam, amsgrad=False); m and v are read and are the values to store
+template <bool CLIP>
+__device__ __forceinline__ float adam_element(const AdamHyper& h, float coef, float p, float g, float& m, float& v) {
+    if constexpr (CLIP) g = __fmul_rn(g, coef);             // the clipped gradient, rounded once, ahead of everything else
+    if (h.maximize) g = -g;
+    if (h.has_wd) {
+        if (h.decoupled) p = __fmul_rn(p, h.dm);            // param.mul_(1 - lr * weight_decay)
+        else g = fmaf(p, h.wd, g);                          // grad.add(param, alpha=weight_decay)
+    }
+    const float d = __fsub_rn(g, m);
+    m = h.low ? fmaf(h.w, d, m) : fmaf(h.wm1, d, g);        // exp_avg.lerp_(grad, 1 - beta1): both weight branches of lerp
+    v = fmaf(__fmul_rn(h.omb2, g), g, __fmul_rn(v, h.beta2));   // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
+    // sqrtf and / are hipcc's correctly rounded forms (its default); __fsqrt_rn would be the 1-ulp native instruction
+    const float den = __fadd_rn(sqrtf(v) / h.bc2s, h.eps);
+    return __fadd_rn(p, __fdiv_rn(__fmul_rn(h.nss, m), den));   // addcdiv_: three roundings, no fma
+}
+
+template <bool CLIP, bool EMA>
+__global__ void __launch_bounds__(SGD_THREADS)
+adam_step_kernel(const om_adam_tensor* __restrict__ tensors, int n_tensors, const om_sgd_chunk* __restrict__ chunks, int n_chunks,
+                 const AdamClip clip, const SgdEma ema) {
+    float coef = 1.0f;
+    if constexpr (CLIP) {
+        if (reinterpret_cast<const long long*>(clip.state)[OM_CLIP_SKIP_OFF] != 0) return;      // nothing is touched
+        coef = (float)clip.state[OM_CLIP_COEF_OFF];
+    }
+    float omd = 0.f;
+    if constexpr (EMA) omd = CLIP ? (float)ema.state[OM_EMA_OMD_OFF] : ema.omd;
+    for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+        const om_sgd_chunk ck = chunks[c];
+        if ((unsigned)ck.tensor >= (unsigned)n_tensors || ck.chunk < 0) continue;
+        const om_adam_tensor t = tensors[ck.tensor];
+        const long long n = t.n;
+        const long long start = (long long)ck.chunk * OM_SGD_CHUNK;
+        if ((t.flags & OM_ADAM_SKIP) || start >= n) continue;
+        AdamHyper h;
+        h.w = t.w; h.wm1 = __fsub_rn(t.w, 1.0f); h.beta2 = t.beta2; h.omb2 = t.omb2; h.eps = t.eps; h.wd = t.weight_decay;
+        h.dm = t.dm; h.nss = t.nss; h.bc2s = t.bc2s;
+        h.low = fabsf(t.w) < 0.5f; h.maximize = t.flags & OM_ADAM_MAXIMIZE; h.has_wd = t.flags & OM_ADAM_HAS_WD;
+        h.decoupled = t.flags & OM_ADAM_DECOUPLED;
+        if constexpr (CLIP) {
+            if (t.flags & OM_ADAM_DEVICE_COUNTED) {
+                // this step's number for this tensor is on the device alone: the corrections come from the host's table
+                const long long k = clip.counts[ck.tensor];
+                double bc1 = 1.0, bc2s = 1.0;
+                if ((unsigned)t.bias_table < (unsigned)clip.n_bias) {
+                    const long long first = clip.bias_dir[2 * t.bias_table], rows = clip.bias_dir[2 * t.bias_table + 1];
+                    if (k >= 0 && k < rows) {
+                        bc1 = clip.bias[2 * (first + k)];
+                        bc2s = clip.bias[2 * (first + k) + 1];
+                    }
+                }
+                h.nss = (float)(-__ddiv_rn(t.lr, bc1));
+                h.bc2s = (float)bc2s;
+            }
+        }
+        // the pointers come out of the table: tell the compiler they are global memory (global_load, not flat_load)
+        gfloat* __restrict__ P = (gfloat*)t.param;
+        const gfloat* __restrict__ G = (const gfloat*)t.grad;
+        gfloat* __restrict__ M = (gfloat*)t.exp_avg;
+        gfloat* __restrict__ V = (gfloat*)t.exp_avg_sq;
+        gfloat* __restrict__ E = nullptr;                   // the shadow; null: this tensor is not averaged
+        if constexpr (EMA) E = (gfloat*)ema.shadows[ck.tensor];
+        const bool has_ema = EMA && E != nullptr;
+        const long long stop = (start + OM_SGD_CHUNK < n) ? start + OM_SGD_CHUNK : n;
+        const bool aligned = ((reinterpret_cast<uintptr_t>(t.param) | reinterpret_cast<uintptr_t>(t.grad) |
+                               reinterpret_cast<uintptr_t>(t.exp_avg) | reinterpret_cast<uintptr_t>(t.exp_avg_sq) |
+                               (has_ema ? reinterpret_cast<uintptr_t>(E) : (uintptr_t)0)) & 15) == 0;
+        long long scalar_from = start;
+        if (aligned) {
+            // start is a multiple of 4, so the chunk's float4s are [start / 4, stop / 4) and at most 3 elements remain
+            const long long v0 = start / 4, v1 = stop / 4;
+            gfloat4* P4 = (gfloat4*)P;
+            const gfloat4* G4 = (const gfloat4*)G;
+            gfloat4* M4 = (gfloat4*)M;
+            gfloat4* V4 = (gfloat4*)V;
+            gfloat4* E4 = (gfloat4*)E;
+            f32x4 p[SGD_VEC_PER_THREAD], g[SGD_VEC_PER_THREAD], m[SGD_VEC_PER_THREAD], v[SGD_VEC_PER_THREAD],
+                e4[EMA ? SGD_VEC_PER_THREAD : 1];
+#pragma unroll
+            for (int k = 0; k < SGD_VEC_PER_THREAD; ++k) {
+                const long long i = v0 + k * SGD_THREADS + threadIdx.x;
+                if (i < v1) {
+                    p[k] = P4[i];
+                    g[k] = G4[i];
+                    m[k] = M4[i];
+                    v[k] = V4[i];
+                    if constexpr (EMA) e4[k] = has_ema ? E4[i] : f32x4{0.f, 0.f, 0.f, 0.f};
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < SGD_VEC_PER_THREAD; ++k) {
+                const long long i = v0 + k * SGD_THREADS + threadIdx.x;
+                if (i < v1) {
+                    f32x4 q, nm, nv, ne;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        float mv = m[k][e], vv = v[k][e];
+                        q[e] = adam_element<CLIP>(h, coef, p[k][e], g[k][e], mv, vv);
+                        nm[e] = mv;
+                        nv[e] = vv;
+                        if constexpr (EMA) ne[e] = ema_element(q[e], e4[k][e], omd);
+                    }
+                    P4[i] = q;
+                    M4[i] = nm;
+                    V4[i] = nv;
+                    if constexpr (EMA) {
+                        if (has_ema) E4[i] = ne;
+                    }
+                }
+            }
+            scalar_from = v1 * 4;                           // the tail of an element count that is not a multiple of 4
+        }
+        for (long long i = scalar_from + threadIdx.x; i < stop; i += SGD_THREADS) {
+            float mv = M[i], vv = V[i];
+            const float ev = has_ema ? E[i] : 0.f;
+            const float q = adam_element<CLIP>(h, coef, P[i], G[i], mv, vv);
+            P[i] = q;
+            M[i] = mv;
+            V[i] = vv;
+            if (has_ema) E[i] = ema_element(q, ev, omd);
+        }
+    }
+}
+
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(1))) unsigned int guint;
 typedef __attribute__((address_space(1))) u32x4 guint4;
 
 // parameter <-> shadow, element for element, as 32-bit words (a NaN keeps its payload); rows without a shadow are passed over, a
 // row's OM_SGD_* flags are not read (a tensor that had no gradient in the latest step is exchanged like any other)
+template <class Row>
 __global__ void __launch_bounds__(SGD_THREADS)
-ema_swap_kernel(const om_sgd_tensor* __restrict__ tensors, int n_tensors, const om_sgd_chunk* __restrict__ chunks, int n_chunks,
+ema_swap_kernel(const Row* __restrict__ tensors, int n_tensors, const om_sgd_chunk* __restrict__ chunks, int n_chunks,
                 float* const* __restrict__ shadows) {
     for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {
         const om_sgd_chunk ck = chunks[c];
         if ((unsigned)ck.tensor >= (unsigned)n_tensors || ck.chunk < 0) continue;
-        const om_sgd_tensor t = tensors[ck.tensor];
+        const Row t = tensors[ck.tensor];
         const long long n = t.n;
         const long long start = (long long)ck.chunk * OM_SGD_CHUNK;
         guint* __restrict__ P = (guint*)t.param;
@@ -342,19 +537,22 @@ ema_swap_kernel(const om_sgd_tensor* __restrict__ tensors, int n_tensors, const 
 
 namespace {
 
+inline bool row_ok(const om_sgd_tensor& t) { return t.param && t.grad && t.n > 0 && (!(t.flags & OM_SGD_HAS_MOMENTUM) || t.buf); }
+inline bool row_ok(const om_adam_tensor& t) { return t.param && t.grad && t.exp_avg && t.exp_avg_sq && t.n > 0; }
+
 // the checks and the table copy every step entry shares; `who` names the entry in the message
-int stage_table(const char* who, const om_sgd_tensor* table_host, om_sgd_tensor* table, int n_tensors, const om_sgd_chunk* chunks,
-                int n_chunks, bool rows_are_stepped, hipStream_t st) {
+template <class Row>
+int stage_table(const char* who, const Row* table_host, Row* table, int n_tensors, const om_sgd_chunk* chunks, int n_chunks,
+                bool rows_are_stepped, hipStream_t st) {
     OM_REQUIRE(table && chunks, OM_EINVAL, "%s: null table", who);
     OM_REQUIRE(n_tensors > 0 && n_chunks > 0, OM_EINVAL, "%s: %d tensors in %d chunks", who, n_tensors, n_chunks);
     if (table_host) {       // the rows are at hand: refuse a row the kernel could only pass over
         for (int i = 0; i < n_tensors && rows_are_stepped; ++i) {
-            const om_sgd_tensor& t = table_host[i];
+            const Row& t = table_host[i];
             if (t.flags & OM_SGD_SKIP) continue;
-            OM_REQUIRE(t.param && t.grad && t.n > 0 && (!(t.flags & OM_SGD_HAS_MOMENTUM) || t.buf), OM_EINVAL,
-                       "%s: row %d has a null pointer or no elements", who, i);
+            OM_REQUIRE(row_ok(t), OM_EINVAL, "%s: row %d has a null pointer or no elements", who, i);
         }
-        OM_CHECK_HIP(hipMemcpyAsync(table, table_host, (size_t)n_tensors * sizeof(om_sgd_tensor), hipMemcpyHostToDevice, st));
+        OM_CHECK_HIP(hipMemcpyAsync(table, table_host, (size_t)n_tensors * sizeof(Row), hipMemcpyHostToDevice, st));
     }
     return OM_OK;
 }
@@ -406,7 +604,7 @@ int om_sgd_clip_step(const om_sgd_tensor* table_host, om_sgd_tensor* table, int 
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (int rc = stage_table("om_sgd_clip_step", table_host, table, n_tensors, chunks, n_chunks, true, st)) return rc;
     const int blocks = grid_of(n_chunks);
-    hipLaunchKernelGGL(om::grad_sumsq_kernel, dim3(blocks), dim3(om::SGD_THREADS), 0, st, table, n_tensors, chunks, n_chunks,
+    hipLaunchKernelGGL(om::grad_sumsq_kernel<om_sgd_tensor>, dim3(blocks), dim3(om::SGD_THREADS), 0, st, table, n_tensors, chunks, n_chunks,
                        partials);
     OM_CHECK_HIP(hipGetLastError());
     hipLaunchKernelGGL(om::clip_finish_kernel<false>, dim3(1), dim3(om::SGD_THREADS), 0, st, partials, n_chunks, max_norm, mode, step,
@@ -429,7 +627,7 @@ int om_sgd_clip_ema_step(const om_sgd_tensor* table_host, om_sgd_tensor* table, 
     if (int rc = stage_table("om_sgd_clip_ema_step", table_host, table, n_tensors, chunks, n_chunks, true, st)) return rc;
     const int blocks = grid_of(n_chunks);
     const om::SgdEma ema{shadows, ema_state, 0.f, decay, warmup != 0};
-    hipLaunchKernelGGL(om::grad_sumsq_kernel, dim3(blocks), dim3(om::SGD_THREADS), 0, st, table, n_tensors, chunks, n_chunks,
+    hipLaunchKernelGGL(om::grad_sumsq_kernel<om_sgd_tensor>, dim3(blocks), dim3(om::SGD_THREADS), 0, st, table, n_tensors, chunks, n_chunks,
                        partials);
     OM_CHECK_HIP(hipGetLastError());
     hipLaunchKernelGGL(om::clip_finish_kernel<true>, dim3(1), dim3(om::SGD_THREADS), 0, st, partials, n_chunks, max_norm, mode, step,
@@ -446,8 +644,88 @@ int om_ema_swap(const om_sgd_tensor* table_host, om_sgd_tensor* table, int n_ten
     OM_REQUIRE(shadows, OM_EINVAL, "om_ema_swap: null shadows");
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (int rc = stage_table("om_ema_swap", table_host, table, n_tensors, chunks, n_chunks, false, st)) return rc;
-    hipLaunchKernelGGL(om::ema_swap_kernel, dim3(grid_of(n_chunks)), dim3(om::SGD_THREADS), 0, st, table, n_tensors, chunks,
+    hipLaunchKernelGGL(om::ema_swap_kernel<om_sgd_tensor>, dim3(grid_of(n_chunks)), dim3(om::SGD_THREADS), 0, st, table, n_tensors, chunks,
                        n_chunks, shadows);
+    OM_CHECK_HIP(hipGetLastError());
+    return OM_OK;
+}
+
+int om_adam_step(const void* table_host, void* table, int n_tensors, const om_sgd_chunk* chunks, int n_chunks,
+                 float* const* shadows, float omd, om_stream stream) {
+    OM_REQUIRE(!shadows || (omd > 0.f && omd <= 1.f), OM_EINVAL, "om_adam_step: omd %g is not 1 - decay of a decay in [0, 1)",
+               (double)omd);
+    if (table_host)         // ahead of the staging copy: a refused call leaves the device table as it was
+        for (int i = 0; i < n_tensors; ++i)
+            OM_REQUIRE(!(static_cast<const om_adam_tensor*>(table_host)[i].flags & OM_ADAM_DEVICE_COUNTED), OM_EINVAL,
+                       "om_adam_step: row %d is device-counted; that needs om_adam_clip_step", i);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    om_adam_tensor* rows = static_cast<om_adam_tensor*>(table);
+    if (int rc = stage_table("om_adam_step", static_cast<const om_adam_tensor*>(table_host), rows, n_tensors, chunks, n_chunks, true,
+                             st))
+        return rc;
+    if (shadows)
+        hipLaunchKernelGGL((om::adam_step_kernel<false, true>), dim3(grid_of(n_chunks)), dim3(om::SGD_THREADS), 0, st, rows, n_tensors,
+                           chunks, n_chunks, om::AdamClip{}, om::SgdEma{shadows, nullptr, omd, 0.0, 0});
+    else
+        hipLaunchKernelGGL((om::adam_step_kernel<false, false>), dim3(grid_of(n_chunks)), dim3(om::SGD_THREADS), 0, st, rows, n_tensors,
+                           chunks, n_chunks, om::AdamClip{}, om::SgdEma{});
+    OM_CHECK_HIP(hipGetLastError());
+    return OM_OK;
+}
+
+int om_adam_clip_step(const void* table_host, void* table, int n_tensors, const om_sgd_chunk* chunks, int n_chunks, double* partials,
+                      double* state, long long* counts, const double* bias, const long long* bias_dir, int n_bias_tables,
+                      float max_norm, int mode, long long step, float* const* shadows, double* ema_state, double decay, int warmup,
+                      om_stream stream) {
+    OM_REQUIRE(table && chunks, OM_EINVAL, "om_adam_clip_step: null pointer");
+    if (int rc = check_clip("om_adam_clip_step", partials, state, counts, max_norm, mode, step)) return rc;
+    OM_REQUIRE(n_bias_tables >= 0 && (n_bias_tables == 0 || (bias && bias_dir)), OM_EINVAL,
+               "om_adam_clip_step: %d bias tables without their rows", n_bias_tables);
+    OM_REQUIRE((reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(bias_dir)) % 8 == 0, OM_EINVAL,
+               "om_adam_clip_step: misaligned pointer");
+    if (shadows) {
+        OM_REQUIRE(ema_state && reinterpret_cast<uintptr_t>(ema_state) % 8 == 0, OM_EINVAL,
+                   "om_adam_clip_step: shadows without an aligned EMA state block");
+        OM_REQUIRE(decay > 0.0 && decay < 1.0, OM_EINVAL, "om_adam_clip_step: decay %g is not inside (0, 1)", decay);
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    om_adam_tensor* rows = static_cast<om_adam_tensor*>(table);
+    if (int rc = stage_table("om_adam_clip_step", static_cast<const om_adam_tensor*>(table_host), rows, n_tensors, chunks, n_chunks,
+                             true, st))
+        return rc;
+    const int blocks = grid_of(n_chunks);
+    const om::SgdEma ema = shadows ? om::SgdEma{shadows, ema_state, 0.f, decay, warmup != 0} : om::SgdEma{};
+    const om::AdamClip clip{state, counts, bias, bias_dir, n_bias_tables};
+    hipLaunchKernelGGL(om::grad_sumsq_kernel<om_adam_tensor>, dim3(blocks), dim3(om::SGD_THREADS), 0, st, rows, n_tensors, chunks,
+                       n_chunks, partials);
+    OM_CHECK_HIP(hipGetLastError());
+    if (shadows) {
+        hipLaunchKernelGGL(om::adam_clip_finish_kernel<true>, dim3(1), dim3(om::SGD_THREADS), 0, st, partials, n_chunks, max_norm, mode,
+                           step, state, ema, rows, n_tensors, counts);
+        OM_CHECK_HIP(hipGetLastError());
+        hipLaunchKernelGGL((om::adam_step_kernel<true, true>), dim3(blocks), dim3(om::SGD_THREADS), 0, st, rows, n_tensors, chunks,
+                           n_chunks, clip, ema);
+    } else {
+        hipLaunchKernelGGL(om::adam_clip_finish_kernel<false>, dim3(1), dim3(om::SGD_THREADS), 0, st, partials, n_chunks, max_norm, mode,
+                           step, state, ema, rows, n_tensors, counts);
+        OM_CHECK_HIP(hipGetLastError());
+        hipLaunchKernelGGL((om::adam_step_kernel<true, false>), dim3(blocks), dim3(om::SGD_THREADS), 0, st, rows, n_tensors, chunks,
+                           n_chunks, clip, ema);
+    }
+    OM_CHECK_HIP(hipGetLastError());
+    return OM_OK;
+}
+
+int om_adam_ema_swap(const void* table_host, void* table, int n_tensors, const om_sgd_chunk* chunks, int n_chunks,
+                     float* const* shadows, om_stream stream) {
+    OM_REQUIRE(shadows, OM_EINVAL, "om_adam_ema_swap: null shadows");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    om_adam_tensor* rows = static_cast<om_adam_tensor*>(table);
+    if (int rc = stage_table("om_adam_ema_swap", static_cast<const om_adam_tensor*>(table_host), rows, n_tensors, chunks, n_chunks,
+                             false, st))
+        return rc;
+    hipLaunchKernelGGL(om::ema_swap_kernel<om_adam_tensor>, dim3(grid_of(n_chunks)), dim3(om::SGD_THREADS), 0, st, rows, n_tensors,
+                       chunks, n_chunks, shadows);
     OM_CHECK_HIP(hipGetLastError());
     return OM_OK;
 }

@@ -213,6 +213,10 @@ SIGNATURES = {
     "om_sgd_clip_ema_step": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _f, _i, ctypes.c_longlong, _vp, _vp, ctypes.c_double, _i,
                                   _vp]),
     "om_ema_swap": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp]),
+    "om_adam_step": (_i, [_vp, _vp, _i, _vp, _i, _vp, _f, _vp]),
+    "om_adam_clip_step": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _f, _i, ctypes.c_longlong, _vp, _vp, ctypes.c_double,
+                               _i, _vp]),
+    "om_adam_ema_swap": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp]),
     "om_bn_act_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "om_bn_act_forward": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, ctypes.c_double, ctypes.c_double, _f, _vp, _vp, _vp, _vp,
                                _vp, _sz, _vp]),

@@ -10,7 +10,7 @@ and divides.  Reported per variant: median, min and max of the rounds' per-step 
 bytes per second at the median, and the host time per step (what the Python side of step() costs; where it exceeds the device
 time the event figure is host-bound and says so).  The device clock is read before and after where the runtime exposes it.
 
-    python tools/bench_optim.py [--rounds 15] [--inner 20] [--warmup 5] [--max-grad-norm X] [--ema-decay X]
+    python tools/bench_optim.py [--optimizer sgd|adamw] [--rounds 15] [--inner 20] [--warmup 5] [--max-grad-norm X] [--ema-decay X]
 
 prints one JSON line.  ``--max-grad-norm X`` adds, per grouping, ``hip_clip_*`` -- the same class with ``max_grad_norm=X``: three
 launches of om_sgd_clip_step, one more read of the gradients -- and ``torch_clip_foreach_*``: torch.nn.utils.clip_grad_norm_ on the
@@ -20,6 +20,10 @@ ratio of the medians of hip_clip_* and hip_* of the same run.  ``--ema-decay X``
 ``hip_clip_ema_*``, and ``torch_foreach_ema_*``: torch's default step followed by ``torch._foreach_lerp_(shadows, params, 1 - X)``
 (8 x 4 bytes per element, more launches), and reports ``ema_over_plain`` and ``ema_over_torch``.  GBps_at_median counts the bytes
 each variant's own arithmetic has to move.
+
+``--optimizer adamw`` times orienmask_amd.optim.HipAdamW (om_adam_step / om_adam_clip_step) against torch.optim.AdamW in the same
+variants: a step reads parameter, gradient and both moments and writes parameter and both moments (7 x 4 bytes per element =
+1.78 GB); with ``--max-grad-norm`` also ``hip_clip_skip_*``, the form whose step counts live on the device (nonfinite="skip").
 """
 import argparse
 import json
@@ -37,7 +41,8 @@ import torch  # noqa: E402
 from orienmask_amd import optim as O  # noqa: E402
 from orienmask_amd.model import OrienMaskYOLOFPNPlus  # noqa: E402
 
-HYPER = dict(lr=1e-3, momentum=0.9, weight_decay=5e-4)
+HYPERS = {"sgd": dict(lr=1e-3, momentum=0.9, weight_decay=5e-4), "adamw": dict(lr=1e-3, weight_decay=1e-2)}
+STREAMS = {"sgd": 5, "adamw": 7}                                  # 4-byte streams per element of the plain step
 SPLIT = dict(base_lr=1e-3, weight_decay=5e-4, norm_weight_decay=0.0, bias_lr_factor=2.0, bias_weight_decay=1e-4)
 
 
@@ -50,6 +55,8 @@ def clock_mhz():
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--optimizer", choices=sorted(HYPERS), default="sgd",
+                    help="sgd: orienmask_amd.optim.SGD against torch.optim.SGD; adamw: HipAdamW against torch.optim.AdamW")
     ap.add_argument("--rounds", type=int, default=15)
     ap.add_argument("--inner", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
@@ -61,6 +68,8 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("bench_optim.py needs an MI355X: there is nothing to time on a CPU")
     dev = torch.device("cuda:0")
+    HYPER = HYPERS[args.optimizer]
+    hip_cls, torch_cls = (O.SGD, torch.optim.SGD) if args.optimizer == "sgd" else (O.HipAdamW, torch.optim.AdamW)
     net = OrienMaskYOLOFPNPlus(num_anchors=3, num_classes=80, pretrained=None, freeze_backbone=False, backbone_batchnorm_eval=False)
     cpu_params = list(net.parameters())
     for p in cpu_params:
@@ -88,7 +97,7 @@ def main():
             for p in ps:
                 p.grad = p.grad.clone()                       # clip_grad_norm_ scales in place
             self.params, self.max_norm = ps, max_norm
-            self.opt = torch.optim.SGD(groups(ps, per_tensor), **HYPER)
+            self.opt = torch_cls(groups(ps, per_tensor), **HYPER)
 
         def step(self):
             torch.nn.utils.clip_grad_norm_(self.params, self.max_norm)
@@ -100,7 +109,7 @@ def main():
         def __init__(self, ps, per_tensor, decay):
             self.params, self.weight = [p.detach() for p in ps], 1.0 - decay
             self.shadows = [p.detach().clone() for p in ps]
-            self.opt = torch.optim.SGD(groups(ps, per_tensor), **HYPER)
+            self.opt = torch_cls(groups(ps, per_tensor), **HYPER)
 
         def step(self):
             self.opt.step()
@@ -114,24 +123,27 @@ def main():
     variants = {}
     skipped = {}
     for per_tensor, tag in ((False, "1group"), (True, "266groups")):
-        variants["hip_" + tag] = O.SGD(groups(fresh_params(), per_tensor), **HYPER)
+        variants["hip_" + tag] = hip_cls(groups(fresh_params(), per_tensor), **HYPER)
         if args.max_grad_norm is not None:
-            variants["hip_clip_" + tag] = O.SGD(groups(fresh_params(), per_tensor), max_grad_norm=args.max_grad_norm, **HYPER)
+            variants["hip_clip_" + tag] = hip_cls(groups(fresh_params(), per_tensor), max_grad_norm=args.max_grad_norm, **HYPER)
+            if args.optimizer == "adamw":
+                variants["hip_clip_skip_" + tag] = hip_cls(groups(fresh_params(), per_tensor), max_grad_norm=args.max_grad_norm,
+                                                           nonfinite="skip", **HYPER)
             variants["torch_clip_foreach_" + tag] = TorchClipped(fresh_params(), per_tensor, args.max_grad_norm)
         if args.ema_decay is not None:
-            variants["hip_ema_" + tag] = O.SGD(groups(fresh_params(), per_tensor), ema_decay=args.ema_decay, **HYPER)
+            variants["hip_ema_" + tag] = hip_cls(groups(fresh_params(), per_tensor), ema_decay=args.ema_decay, **HYPER)
             if args.max_grad_norm is not None:
-                variants["hip_clip_ema_" + tag] = O.SGD(groups(fresh_params(), per_tensor), max_grad_norm=args.max_grad_norm,
-                                                        ema_decay=args.ema_decay, **HYPER)
+                variants["hip_clip_ema_" + tag] = hip_cls(groups(fresh_params(), per_tensor), max_grad_norm=args.max_grad_norm,
+                                                          ema_decay=args.ema_decay, **HYPER)
             variants["torch_foreach_ema_" + tag] = TorchAveraged(fresh_params(), per_tensor, args.ema_decay)
-        variants["torch_single_" + tag] = torch.optim.SGD(groups(fresh_params(), per_tensor), foreach=False, **HYPER)
-        variants["torch_foreach_" + tag] = torch.optim.SGD(groups(fresh_params(), per_tensor), **HYPER)
+        variants["torch_single_" + tag] = torch_cls(groups(fresh_params(), per_tensor), foreach=False, **HYPER)
+        variants["torch_foreach_" + tag] = torch_cls(groups(fresh_params(), per_tensor), **HYPER)
         try:
-            opt = torch.optim.SGD(groups(fresh_params(), per_tensor), fused=True, **HYPER)
+            opt = torch_cls(groups(fresh_params(), per_tensor), fused=True, **HYPER)
             opt.step()
             torch.cuda.synchronize()
             variants["torch_fused_" + tag] = opt
-        except Exception as e:                                # this torch build has no fused SGD on this device
+        except Exception as e:                                # this torch build has no fused step on this device
             skipped["torch_fused_" + tag] = "%s: %s" % (type(e).__name__, str(e)[:200])
 
     for opt in variants.values():
@@ -155,17 +167,19 @@ def main():
             dev_ms[name].append(start.elapsed_time(stop) / args.inner)
             host_ms[name].append((t1 - t0) * 1e3 / args.inner)
     clock_after = clock_mhz()
-    nbytes = 5 * 4 * elements
-    out = {"bench": "optim_step", "tensors": len(shapes), "elements": elements, "bytes_per_step": nbytes, "rounds": args.rounds,
-           "inner": args.inner, "warmup": args.warmup, "device": torch.cuda.get_device_name(0), "torch": torch.__version__,
+    nbytes = STREAMS[args.optimizer] * 4 * elements
+    out = {"bench": "optim_step", "optimizer": args.optimizer, "tensors": len(shapes), "elements": elements,
+           "bytes_per_step": nbytes, "rounds": args.rounds, "inner": args.inner, "warmup": args.warmup,
+           "device": torch.cuda.get_device_name(0), "torch": torch.__version__,
            "clock_mhz_before": clock_before, "clock_mhz_after": clock_after, "floor_ms_at_6.3TBps": nbytes / 6.3e12 * 1e3,
            "variants": {}, "skipped": skipped}
     for name in variants:
         v = sorted(dev_ms[name])
         med = statistics.median(v)
-        # 4-byte streams per element: p, g, buf read and p, buf written; + g again for the norm; + shadow read and written (torch's
-        # lerp reads the parameter once more)
-        streams = 5 + ("clip" in name) + (3 if name.startswith("torch_foreach_ema") else 2 if "ema" in name else 0)
+        # 4-byte streams per element: p, g, buf (adamw: both moments) read and p, buf (both moments) written; + g again for the
+        # norm; + shadow read and written (torch's lerp reads the parameter once more)
+        ema_streams = 3 if name.startswith("torch_foreach_ema") else 2 if "ema" in name else 0
+        streams = STREAMS[args.optimizer] + ("clip" in name) + ema_streams
         moved = streams * 4 * elements
         out["variants"][name] = {"ms_median": round(med, 4), "ms_min": round(v[0], 4), "ms_max": round(v[-1], 4),
                                  "spread_pct": round(100 * (v[-1] - v[0]) / med, 1), "bytes": moved,

@@ -56,13 +56,13 @@ def parse_args(argv=None):
                     help="whose bf16 convolution gradients under --amp bf16 --conv-forward hip (the model's conv_grad), overriding "
                          "the config's model.conv_grad")
     ap.add_argument("--max-grad-norm", type=float, default=None, metavar="X",
-                    help="clip the global L2 gradient norm to X inside the SGD step (the optimizer's max_grad_norm), overriding "
+                    help="clip the global L2 gradient norm to X inside the optimizer's HIP step (max_grad_norm of SGD, HipAdam, HipAdamW), overriding "
                          "the config's optimizer.max_grad_norm")
     ap.add_argument("--nonfinite-grads", choices=["propagate", "skip"], default=None,
                     help="with --max-grad-norm: what a step does whose gradient norm is not finite (the optimizer's nonfinite), "
                          "overriding the config's optimizer.nonfinite")
     ap.add_argument("--ema-decay", type=float, default=None, metavar="X",
-                    help="average the weights inside the SGD step with decay X (the optimizer's ema_decay), overriding the "
+                    help="average the weights inside the optimizer's HIP step with decay X (ema_decay of SGD, HipAdam, HipAdamW), overriding the "
                          "config's optimizer.ema_decay")
     ap.add_argument("--no-ema-warmup", action="store_true",
                     help="with an averaging optimizer: no warm-up of the decay (the optimizer's ema_warmup=False), overriding the "
