@@ -397,6 +397,26 @@ int om_conv2d_stem2_f16(const float* in, int B, int H, int W, const float* w1, c
 int om_preprocess(const float* in_nhwc, int N, int h, int w, int resize_h, int resize_w, const float* mean3,
                   const float* std3, int pad_top, int pad_left, int out_h, int out_w, float pad_value, float* out_nchw,
                   om_stream stream);
+/* The same for n images of their OWN sizes and element types in one call: what an inference loop has after decoding a
+ * directory of photos (uint8, BGR from cv2).  One launch per OM_PRE_BATCH images; the table reaches the kernel by value, so the
+ * entry allocates nothing, copies nothing and does not synchronise.
+ *   images  HOST array of n DEVICE pointers, each to a dense [h,w,3] HWC image: uint8 at any byte address (images staged back
+ *           to back need no padding between or behind them: no byte outside [image, image + h*w*3*elem) is read), float32
+ *           4-byte aligned
+ *   geom    HOST int32 [n][8], row i = { h, w, resize_h, resize_w, pad_top, pad_left, flags, 0 } of image i:
+ *           flags = OM_PRE_U8 (the image is uint8; otherwise float32) | OM_PRE_BGR (output channel c reads source channel
+ *           2 - c; mean3 / std3 are indexed by the OUTPUT channel); the last element is reserved and must be 0
+ *   out     [n,3,out_h,out_w] float32: image i resized to resize_h x resize_w, normalised and placed at (pad_top, pad_left) of
+ *           plane set i, everything else of the plane set pad_value.  16-byte stores when out_w is a multiple of 4 and
+ *           out_nchw 16-byte aligned, 4-byte stores otherwise
+ * Every plane set has the bits om_preprocess writes for float32(image) in RGB order with the same geometry (uint8 -> float32
+ * is exact).  A null pointer, n <= 0, a row whose resized image does not fit the output or has an empty side, and unknown flag
+ * bits are refused before anything is launched, with a message naming the image index. */
+#define OM_PRE_BATCH 16         /* images per launch */
+#define OM_PRE_U8 1
+#define OM_PRE_BGR 2
+int om_preprocess_batch(const void* const* images, const int32_t* geom, int n, const float* mean3, const float* std3,
+                        int out_h, int out_w, float pad_value, float* out_nchw, om_stream stream);
 /* pad() alone on an NCHW tensor of `planes` = N*C planes. */
 int om_pad_nchw(const float* in, long long planes, int h, int w, int pad_top, int pad_left, int out_h, int out_w,
                 float pad_value, float* out, om_stream stream);

@@ -81,6 +81,125 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const PreParams p) {
     }
 }
 
+// ---- the batched form: OM_PRE_BATCH images of their own sizes and element types per launch -----------------------------------
+// One table entry per image, passed by value (the kernel argument block: no device table, no copy); blockIdx.y is the image, so
+// the entry is read with scalar loads and the uint8 / float32 and RGB / BGR decisions are uniform over a workgroup.  A lane
+// owns VEC consecutive output pixels of one row in all three planes: VEC = 4 stores 16 bytes per plane, 1 KiB per wave and
+// instruction (out_w a multiple of 4 and a 16-byte aligned output); VEC = 1 is the form for every other width.
+//
+// The arithmetic is preprocess_kernel's, operation for operation, and uint8 -> float32 is exact: the result has the bits
+// preprocess_kernel gives for float32(image) in RGB order.
+//
+// Reads: the two taps of a row are neighbouring pixels (x1 = x0 + 1) or the same one (x0 = w - 1).  Of a uint8 row the six
+// bytes of two neighbours are read as 4 + 2 bytes at the pixel's own (any) byte address, the three bytes of a single one byte
+// by byte: nothing outside [image, image + h * w * 3) is touched, wherever the image starts and whatever lies behind it.
+struct PreImg {
+    const void* src;     // [h,w,3] uint8 or float32
+    int h, w, rh, rw, pad_top, pad_left, flags;
+    int small_out;       // as PreParams.small_out, of this image's rh + rw
+    float scale_h, scale_w;
+};
+
+struct PreBatch {
+    PreImg img[OM_PRE_BATCH];
+    float* out;          // plane set of the group's first image
+    int n, out_h, out_w;
+    float mean[3], stdv[3], pad_value;
+};
+
+struct TapPair { float a0, a1, a2, b0, b1, b2; };            // channels 0..2 of the pixel at x0 (a) and at x1 (b)
+
+__device__ __forceinline__ TapPair load_pair(const uint8_t* p, bool two) {
+    TapPair r;
+    if (two) {
+        uint32_t lo;
+        uint16_t hi;
+        __builtin_memcpy(&lo, p, 4);                         // alignment 1: the compiler picks the widest load the target allows
+        __builtin_memcpy(&hi, p + 4, 2);
+        r.a0 = (float)(lo & 0xffu); r.a1 = (float)((lo >> 8) & 0xffu); r.a2 = (float)((lo >> 16) & 0xffu);
+        r.b0 = (float)(lo >> 24); r.b1 = (float)(hi & 0xffu); r.b2 = (float)(hi >> 8);
+    } else {
+        r.a0 = r.b0 = (float)p[0]; r.a1 = r.b1 = (float)p[1]; r.a2 = r.b2 = (float)p[2];
+    }
+    return r;
+}
+
+__device__ __forceinline__ TapPair load_pair(const float* p, bool two) {
+    const float* p1 = p + (two ? 3 : 0);
+    TapPair r;
+    r.a0 = p[0]; r.a1 = p[1]; r.a2 = p[2]; r.b0 = p1[0]; r.b1 = p1[1]; r.b2 = p1[2];
+    return r;
+}
+
+// one output pixel inside the resized image: v[c] for the three OUTPUT channels
+template <typename T>
+__device__ __forceinline__ void pre_pixel(const PreBatch& bt, const PreImg& q, int y0, int y1, float wy0, float wy1, int rx,
+                                          float v[3]) {
+    int x0, x1;
+    float wx0, wx1;
+    bilinear_tap(rx, q.scale_w, q.w, x0, x1, wx0, wx1);
+    const T* img = static_cast<const T*>(q.src);
+    TapPair t = load_pair(img + ((size_t)y0 * q.w + x0) * 3, x1 != x0);
+    TapPair u = load_pair(img + ((size_t)y1 * q.w + x0) * 3, x1 != x0);
+    if (q.flags & OM_PRE_BGR) {                               // output channel c reads source channel 2 - c
+        float s;
+        s = t.a0; t.a0 = t.a2; t.a2 = s; s = t.b0; t.b0 = t.b2; t.b2 = s;
+        s = u.a0; u.a0 = u.a2; u.a2 = s; s = u.b0; u.b0 = u.b2; u.b2 = s;
+    }
+    const float a00[3] = {t.a0, t.a1, t.a2}, a01[3] = {t.b0, t.b1, t.b2}, a10[3] = {u.a0, u.a1, u.a2}, a11[3] = {u.b0, u.b1, u.b2};
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float t00 = a00[c], t01 = a01[c], t10 = a10[c], t11 = a11[c];
+        float r;
+        if (q.small_out) {
+            r = bilinear_blend_small(t00, t01, t10, t11, wx0, wx1, wy0, wy1);
+        } else {
+            const float top = fmaf(t00, wx0, t01 * wx1);
+            const float bot = fmaf(t10, wx0, t11 * wx1);
+            r = fmaf(top, wy0, bot * wy1);
+        }
+        v[c] = (r - bt.mean[c]) / bt.stdv[c];
+    }
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void preprocess_batch_kernel(const PreBatch bt) {
+    const PreImg& q = bt.img[blockIdx.y];
+    const int per_row = bt.out_w / VEC;
+    const int item = (int)blockIdx.x * 256 + (int)threadIdx.x;          // out_h * out_w < 2^31 (the entry)
+    if (item >= bt.out_h * per_row) return;
+    const int y = item / per_row, x = (item - y * per_row) * VEC;
+    const size_t plane = (size_t)bt.out_h * bt.out_w;
+    float* o = bt.out + (size_t)blockIdx.y * 3 * plane + (size_t)y * bt.out_w + x;
+    const int ry = y - q.pad_top;
+    const bool row_in = (unsigned)ry < (unsigned)q.rh;
+    int y0 = 0, y1 = 0;
+    float wy0 = 0.f, wy1 = 0.f;
+    if (row_in) bilinear_tap(ry, q.scale_h, q.h, y0, y1, wy0, wy1);
+    const bool u8 = (q.flags & OM_PRE_U8) != 0;
+    float r[3][VEC];
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+        const int rx = x + e - q.pad_left;
+        float v[3] = {bt.pad_value, bt.pad_value, bt.pad_value};
+        if (row_in && (unsigned)rx < (unsigned)q.rw) {
+            if (u8) pre_pixel<uint8_t>(bt, q, y0, y1, wy0, wy1, rx, v);
+            else pre_pixel<float>(bt, q, y0, y1, wy0, wy1, rx, v);
+        }
+        r[0][e] = v[0]; r[1][e] = v[1]; r[2][e] = v[2];
+    }
+    if constexpr (VEC == 4) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            *reinterpret_cast<float4*>(o + c * plane) = make_float4(r[c][0], r[c][1], r[c][2], r[c][3]);
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) o[c * plane + e] = r[c][e];
+    }
+}
+
 __global__ __launch_bounds__(256) void pad_nchw_kernel(const float* __restrict__ in, float* __restrict__ out, long long planes,
                                                        int h, int w, int out_h, int out_w, int pad_top, int pad_left,
                                                        float pad_value) {
@@ -120,6 +239,55 @@ int om_preprocess(const float* in_nhwc, int N, int h, int w, int resize_h, int r
     hipLaunchKernelGGL(om::preprocess_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), p);
     OM_CHECK_HIP(hipGetLastError());
+    return OM_OK;
+}
+
+int om_preprocess_batch(const void* const* images, const int32_t* geom, int n, const float* mean3, const float* std3,
+                        int out_h, int out_w, float pad_value, float* out_nchw, om_stream stream) {
+    OM_REQUIRE(images && geom && mean3 && std3 && out_nchw, OM_EINVAL, "om_preprocess_batch: null argument");
+    OM_REQUIRE(n > 0, OM_EINVAL, "om_preprocess_batch: n = %d images", n);
+    OM_REQUIRE(out_h > 0 && out_w > 0 && (long long)out_h * out_w < (1ll << 31), OM_EINVAL,
+               "om_preprocess_batch: bad output size %dx%d", out_h, out_w);
+    OM_REQUIRE(reinterpret_cast<uintptr_t>(out_nchw) % 4 == 0, OM_EINVAL, "om_preprocess_batch: out_nchw not 4-byte aligned");
+    for (int i = 0; i < n; ++i) {                             // every row before the first launch: a refused call writes nothing
+        const int32_t* g = geom + 8 * (size_t)i;
+        OM_REQUIRE(images[i], OM_EINVAL, "om_preprocess_batch: image %d: null pointer", i);
+        OM_REQUIRE((g[6] & ~(OM_PRE_U8 | OM_PRE_BGR)) == 0 && g[7] == 0, OM_EINVAL,
+                   "om_preprocess_batch: image %d: unknown flag bits (flags 0x%x, reserved %d)", i, (unsigned)g[6], g[7]);
+        OM_REQUIRE(g[0] > 0 && g[1] > 0 && g[2] > 0 && g[3] > 0, OM_EINVAL,
+                   "om_preprocess_batch: image %d: bad shape (%dx%d resized to %dx%d)", i, g[0], g[1], g[2], g[3]);
+        OM_REQUIRE(g[4] >= 0 && g[5] >= 0 && (long long)g[4] + g[2] <= out_h && (long long)g[5] + g[3] <= out_w, OM_EINVAL,
+                   "om_preprocess_batch: image %d: the resized image (%dx%d at +%d,+%d) does not fit the output %dx%d", i, g[2],
+                   g[3], g[4], g[5], out_h, out_w);
+        OM_REQUIRE((g[6] & OM_PRE_U8) || reinterpret_cast<uintptr_t>(images[i]) % 4 == 0, OM_EINVAL,
+                   "om_preprocess_batch: image %d: a float32 image must be 4-byte aligned", i);
+    }
+    const bool vec = out_w % 4 == 0 && reinterpret_cast<uintptr_t>(out_nchw) % 16 == 0;
+    const long long items = (long long)out_h * (vec ? out_w / 4 : out_w);
+    const size_t plane = (size_t)out_h * out_w;
+    for (int i0 = 0; i0 < n; i0 += OM_PRE_BATCH) {
+        om::PreBatch bt;
+        bt.n = n - i0 < OM_PRE_BATCH ? n - i0 : OM_PRE_BATCH;
+        bt.out = out_nchw + (size_t)i0 * 3 * plane;
+        bt.out_h = out_h; bt.out_w = out_w; bt.pad_value = pad_value;
+        for (int c = 0; c < 3; ++c) { bt.mean[c] = mean3[c]; bt.stdv[c] = std3[c]; }
+        for (int k = 0; k < OM_PRE_BATCH; ++k) {
+            const int i = i0 + (k < bt.n ? k : 0);            // the unused entries repeat the first: no workgroup reads them
+            const int32_t* g = geom + 8 * (size_t)i;
+            om::PreImg& q = bt.img[k];
+            q.src = images[i];
+            q.h = g[0]; q.w = g[1]; q.rh = g[2]; q.rw = g[3]; q.pad_top = g[4]; q.pad_left = g[5]; q.flags = g[6];
+            q.small_out = g[2] + g[3] <= om::BILINEAR_SMALL_OUT ? 1 : 0;
+            q.scale_h = (float)g[0] / (float)g[2];            // area_pixel_compute_scale with size= given
+            q.scale_w = (float)g[1] / (float)g[3];
+        }
+        const dim3 grid((unsigned)((items + 255) / 256), (unsigned)bt.n);
+        if (vec)
+            hipLaunchKernelGGL(om::preprocess_batch_kernel<4>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), bt);
+        else
+            hipLaunchKernelGGL(om::preprocess_batch_kernel<1>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), bt);
+        OM_CHECK_HIP(hipGetLastError());
+    }
     return OM_OK;
 }
 

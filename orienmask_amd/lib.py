@@ -103,6 +103,9 @@ class LossCfg(ctypes.Structure):
 
 OM_VIS_MAX_KEPT = 512
 OM_VIS_BATCH = 16
+OM_PRE_BATCH = 16               # include/orienmask_hip.h: om_preprocess_batch, images per launch and the flags of a geom row
+OM_PRE_U8 = 1
+OM_PRE_BGR = 2
 
 _vp, _i, _f, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 
@@ -172,6 +175,8 @@ SIGNATURES = {
                                     _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp]),
     "om_preprocess": (_i, [_vp, _i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                            _i, _i, _i, _i, _f, _vp, _vp]),
+    "om_preprocess_batch": (_i, [ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_int32), _i, ctypes.POINTER(ctypes.c_float),
+                                 ctypes.POINTER(ctypes.c_float), _i, _i, _f, _vp, _vp]),
     "om_pad_nchw": (_i, [_vp, ctypes.c_longlong, _i, _i, _i, _i, _i, _i, _f, _vp, _vp]),
     "om_postprocess_workspace_bytes": (_sz, [ctypes.POINTER(PostCfg), _i]),
     "om_postprocess": (_i, [ctypes.POINTER(PostCfg), _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -140,9 +140,16 @@ class Tester:
 
 
 def infer_loop(model, transform, postprocess, images, device, warmup=10, size_divisor=32, use_graph=True, latency_mode=True,
-               visualizer=None):
+               visualizer=None, batch_size=1, channel_order="rgb"):
     """images: list of [h,w,3] float32 tensors (what cv2.imread + cvtColor give infer.py).
     Returns (list of per-image detections, list of pad_info, timer log in ms).
+
+    batch_size > 1 (or channel_order='bgr'): consecutive groups of batch_size images go through transform.batch -- the images
+    may then be uint8 or float32, of different sizes, numpy arrays or tensors on the host or the device, in RGB or (cv2.imread's)
+    BGR order: one staging copy and one preprocess launch per group, timed as 'Load data' -- and then through the network and
+    the postprocess as ONE batch ('Forward & Postprocess').  The last, shorter group is a second input shape (a second graph).
+    Detections and pad_infos come back per image in input order; the visualizer gets each image as float32 RGB, derived on the
+    device from the staged source.  The model's latency setting is left alone for batch_size > 1: it is a one-image device.
 
     visualizer (infer.py -v, :166-172): called as visualizer(detections, image on the device, pad_info) after each image's
     forward + postprocess and timed as 'Visualize'; the loop then returns a fourth element, the list of what it returned (for
@@ -163,7 +170,12 @@ def infer_loop(model, transform, postprocess, images, device, warmup=10, size_di
     results, pads, shows = [], [], []
     graphs = {}
     restore = None
-    if latency_mode and getattr(model, "precision", None) == "f32_split" and hasattr(model, "set_latency_mode"):
+    batch_size = int(batch_size)
+    if batch_size < 1:
+        raise ValueError("infer_loop: batch_size must be at least 1, got %d" % batch_size)
+    through_batch = batch_size > 1 or channel_order != "rgb"
+    if (latency_mode and batch_size == 1 and getattr(model, "precision", None) == "f32_split"
+            and hasattr(model, "set_latency_mode")):
         restore = model.latency_cells
         model.set_latency_mode(True)
     # Only this package's postprocess with its own NMS can be captured: capture needs the kernel-only `launch` / `collect` split
@@ -191,24 +203,50 @@ def infer_loop(model, transform, postprocess, images, device, warmup=10, size_di
             return postprocess(model(x))
         return [{k: v.clone() for k, v in d.items()} for d in g(x)]
 
+    def batched():
+        def load(group):
+            return transform._batch(group, size_divisor, 0, channel_order, device)
+
+        if warmup and images:
+            x = load(images[:batch_size])[0]
+            for _ in range(warmup):
+                run(x)
+        with _timer.timer("Main Loop"):
+            for s in range(0, len(images), batch_size):
+                with _timer.timer("Load data"):
+                    x, pad_infos, sources = load(images[s:s + batch_size])
+                with _timer.timer("Forward & Postprocess"):
+                    det = run(x)
+                results.extend(det)
+                pads.extend(pad_infos)
+                if visualizer is not None:
+                    for d, src, pad_info in zip(det, sources, pad_infos):
+                        with _timer.timer("Visualize"):
+                            # the visualiser's contract is a float32 RGB image on the device: derived there from the staged source
+                            src = src.to(torch.float32)
+                            shows.append(visualizer(d, src.flip(-1) if channel_order == "bgr" else src, pad_info))
+
+    def single():
+        if warmup and images:
+            x, _ = transform.padded(images[0].to(device).unsqueeze(0), size_divisor)
+            for _ in range(warmup):
+                run(x)
+        with _timer.timer("Main Loop"):
+            for img in images:
+                with _timer.timer("Load data"):
+                    src = img.to(device)
+                    x, pad_info = transform.padded(src.unsqueeze(0), size_divisor)
+                with _timer.timer("Forward & Postprocess"):
+                    det = run(x)
+                results.append(det[0])
+                pads.append(pad_info)
+                if visualizer is not None:
+                    with _timer.timer("Visualize"):
+                        shows.append(visualizer(det[0], src, pad_info))
+
     try:
         with torch.no_grad():
-            if warmup and images:
-                x, _ = transform.padded(images[0].to(device).unsqueeze(0), size_divisor)
-                for _ in range(warmup):
-                    run(x)
-            with _timer.timer("Main Loop"):
-                for img in images:
-                    with _timer.timer("Load data"):
-                        src = img.to(device)
-                        x, pad_info = transform.padded(src.unsqueeze(0), size_divisor)
-                    with _timer.timer("Forward & Postprocess"):
-                        det = run(x)
-                    results.append(det[0])
-                    pads.append(pad_info)
-                    if visualizer is not None:
-                        with _timer.timer("Visualize"):
-                            shows.append(visualizer(det[0], src, pad_info))
+            batched() if through_batch else single()
     finally:
         if restore is not None:
             model.set_latency_mode(restore > 0, restore or None)
