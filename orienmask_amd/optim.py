@@ -2,73 +2,36 @@
 
   SGD            torch.optim.SGD with the same constructor whose ``step()`` is ONE launch of om_sgd_step (csrc/optim.hip) over
                  every tensor of every parameter group
-  HipAdam, HipAdamW   torch.optim.Adam / AdamW with the same constructor whose ``step()`` is om_adam_step / om_adam_clip_step, with
-                 SGD's clipping, skip and EMA (below)
+  HipAdam, HipAdamW   torch.optim.Adam / AdamW in the same way (om_adam_step)
   param_groups   the reference's optim/param_groups.py: one group per parameter with its own lr / weight_decay
   WarmupLR, PolyLR, StepWarmUpLR    the reference's optim/lr_scheduler.py
   everything else of torch.optim and torch.optim.lr_scheduler, re-exported as the reference's package re-exports it, so any other
   optimizer or scheduler type named in a config resolves to torch's -- ``Adam`` and ``AdamW`` included: the HIP Adam step is
   reached as ``type="HipAdam"`` / ``"HipAdamW"``.
 
-This is the swap of trainer/builder.py:35-36 (``optim_module``); orienmask_amd.builder.build_optimizer is :118-130.
+The three classes subclass torch's: ``param_groups``, ``state``, ``state_dict()`` / ``load_state_dict()``, ``add_param_group``,
+``zero_grad`` and torch's schedulers work as they are, and a checkpoint moves both ways between them and torch's classes.  The
+arithmetic is torch's on the CPU in float32, bit for bit (Adam: except where torch's vectorised sqrt is not correctly rounded).
+``step()`` never synchronises and, after a parameter's first step, allocates nothing.  What the kernels do not take is refused:
+parameters that are not dense float32 tensors on a GPU, sparse gradients, ``differentiable=True``, tensor hyper-parameters, and for
+Adam ``amsgrad``, ``capturable``, ``foreach=True``, ``fused=True``.  There is no eager fallback.
 
-SGD is a subclass: ``param_groups``, ``state`` (``momentum_buffer`` per parameter), ``state_dict()`` / ``load_state_dict()``,
-``add_param_group``, ``zero_grad`` and torch's schedulers work as they are, and a checkpoint written by the reference's trainer
-resumes here and the other way round.  The arithmetic is torch.optim.SGD's in torch-CPU's float32 rounding, bit for bit
-(DESIGN.md section 3.16).  What the kernel does not take is refused: parameters that are not float32 tensors on a GPU, sparse
-gradients, ``differentiable=True``, a tensor ``lr``.  There is no eager fallback.
+Four keyword-only options, attributes of the optimizer (``state_dict()`` keeps torch's keys):
 
-How a step works.  Per device the optimizer keeps a table with one 64-byte row per parameter (pointers to parameter, gradient and
-momentum buffer, element count, float32 -lr / weight_decay / momentum / 1 - dampening, flags) and a chunk list built once from the
-element counts (``plan_chunks``), both resident on the device.  ``step()`` refreshes the host copy of the table (gradients may
-have been reallocated by ``zero_grad(set_to_none=True)``; a scheduler has usually changed lr), copies it into one of ``_RING``
-pinned staging buffers and hands that to om_sgd_step, which enqueues the host-to-device copy and the kernel on the current
-stream.  A staging buffer is reused only after the event recorded behind its copy has completed.  After a parameter's first step
-nothing is allocated and nothing is read back from the device.
+  max_grad_norm=X     ``torch.nn.utils.clip_grad_norm_(params, X)`` followed by ``step()``, bit for bit, in three launches, except
+                      that ``p.grad`` is NOT modified.  ``grad_norm_stats()`` reads what the steps saw (one small read; it
+                      synchronises).  Every parameter must be on one device.
+  nonfinite="skip"    (with max_grad_norm) a step whose gradient norm is Inf or NaN leaves parameters, state and shadows
+                      bit-unchanged; the host does not learn of it during the step.  Adam's ``state[p]["step"]`` then lives on the
+                      device and is read back by ``state_dict()``.  Known edge (SGD): resuming from a checkpoint taken before any
+                      APPLIED step with ``dampening != 0`` makes the first applied step ``buf = (1 - dampening) * d``.
+  ema_decay=D, ema_warmup=True    a float32 shadow per parameter, a bit copy of the parameter at the first ``step()``, updated inside
+                      the step kernel at every APPLIED step: ``e += (p' - e) * (1 - d_k)`` with ``d_k = D``, or with warm-up
+                      ``min(D, (1 + k) / (10 + k))``.  ``ema_swap()`` / ``with ema_applied():`` exchange parameters and shadows in
+                      place; ``ema_state_dict(model)`` / ``load_ema_state_dict(model, state_dict, updates)`` / ``ema_updates()`` are
+                      the checkpoint's side.  Every parameter must be on one device.
 
-Gradient-norm clipping.  ``SGD(..., max_grad_norm=X, nonfinite="propagate" | "skip")`` (keyword-only; attributes of the optimizer,
-neither ``defaults`` nor param-group entries, so ``state_dict()`` keeps torch's keys) makes ``step()`` the three launches of
-om_sgd_clip_step: float64 partial sums of squares per chunk, one workgroup that finishes the float32 norm, torch's coefficient
-``min(1, (norm + 1e-6).reciprocal() * max_grad_norm)`` and the skip decision into a small device state block, and the update with
-every gradient element read as ``g * coef``.  That is ``torch.nn.utils.clip_grad_norm_(params, X)`` followed by ``step()``, bit for
-bit, except that ``p.grad`` is NOT modified.  With ``nonfinite="skip"`` a step whose norm is Inf or NaN leaves every parameter and
-momentum buffer bit-unchanged; the host never learns of it during the step.  New momentum buffers are then allocated with zeros
-and the device decides which applied step is a tensor's first (``buf = d``).  Known edge: resuming from a checkpoint taken before
-any APPLIED step (it holds zero buffers) with ``dampening != 0`` makes the first applied step ``buf = (1 - dampening) * d``, not
-torch's ``buf = d``.  ``grad_norm_stats()`` is one small device-to-host read of the block.  Under DistributedDataParallel every
-rank sees the same all-reduced gradients and so takes the same decision; no collective is added.  DESIGN.md section 3.16.1.
-
-Weight EMA.  ``SGD(..., ema_decay=D, ema_warmup=True)`` (keyword-only attributes like the two above; ``state_dict()`` keeps torch's
-keys) keeps a float32 SHADOW per parameter tensor, with the parameter's shape and strides, allocated as a bit copy of the parameter
-when the device plan is built -- at the first ``step()``, so weights loaded before it are what gets copied.  Every APPLIED step
-updates it inside the step kernel (om_sgd_ema_step / om_sgd_clip_ema_step: 8 more bytes per element, no further launch), with the
-parameter's new value ``p'``:  ``diff = p' - e`` rounded once, ``e = fma(diff, omd, e)``, ``omd = float32(1 - d_k)``,
-``d_k = ema_decay`` or with warm-up ``min(ema_decay, (1 + k) / (10 + k))`` in float64, ``k`` the number of EMA updates this
-optimizer has applied.  Parameters and momentum buffers get exactly the bits they get without it.  With ``nonfinite="skip"`` the
-device keeps ``k`` and a skipped step leaves every shadow and ``k`` unchanged -- a host-side average cannot know that.  A parameter
-without a gradient in a step keeps its shadow while ``k``, which is global, still advances.  NaN and Inf propagate as the arithmetic
-gives them.  ``ema_updates()`` is the host's count, or one small device-to-host read in skip mode; ``ema_swap()`` / ``with
-ema_applied():`` exchange parameters and shadows in place (om_ema_swap: pointers stay, no plan is rebuilt, nothing is allocated);
-``ema_state_dict(model)`` / ``load_ema_state_dict(model, state_dict, updates)`` are the checkpoint's side.  Every parameter must
-be on one device.  Under DistributedDataParallel every rank starts from the same weights and sees the same gradients, so the
-shadows agree without a collective.  DESIGN.md section 3.16.2.
-
-The Adam family.  ``HipAdam`` / ``HipAdamW`` subclass torch.optim.Adam / AdamW: constructor, ``param_groups``, state (``step``,
-``exp_avg``, ``exp_avg_sq`` as torch allocates them), ``state_dict()`` / ``load_state_dict()`` and the schedulers are torch's, and a
-checkpoint moves both ways between them and torch's classes.  They take the four keyword-only options above with the same
-meaning, and plans, staging ring, chunk list, clip launches, shadows, ``ema_*`` methods and ``grad_norm_stats()`` are the SAME code
-(``_HipStep``); the row is 96 bytes (``ADAM_ROW``).  The arithmetic is torch's _single_tensor_adam per element in IEEE float32, one
-rounding per operation (tests/adam_np.py restates it): torch-CPU bit for bit except where torch's vectorised sqrt is not correctly
-rounded.  Refused: ``amsgrad``, ``capturable``, ``differentiable``, ``foreach=True``, ``fused=True``, a tensor ``lr`` or tensor betas,
-sparse gradients, parameters that are not float32 on the GPU.  Step counts: torch keeps one per parameter and a parameter
-without a gradient does not advance.  Where the host knows every count (no clipping, or ``nonfinite="propagate"``) it writes
-``float32(-(lr / bc1))`` and ``float32(bc2s)`` into the rows at each step, from torch's own double expressions, and advances
-``state[p]["step"]`` as torch does.  With ``nonfinite="skip"`` only the device knows which steps were applied: an int64 count per
-tensor lives on the device, the workgroup that takes the skip decision increments the counts of the rows with a gradient when the
-step is applied, and the update reads the two corrections of that count from a table built on the host (``adam_bias_table``: one
-per distinct betas, CPython's doubles, up to 2**20 rows) and divides ``lr`` by bc1 in double.  ``state_dict()`` reads the counts
-back (one small device-to-host copy) into ``state[p]["step"]``; ``load_state_dict`` and a rebuilt plan upload them.  Neither
-happens inside ``step()``.  DESIGN.md section 3.16.3.
+How a step works, the rounding of every operation and the protocols of the device-side words: DESIGN.md section 3.16.
 """
 import contextlib as _contextlib
 import numpy as _np
@@ -155,6 +118,21 @@ def _check_param(p, who="orienmask_amd.optim.SGD"):
     if not _is_dense(p):
         raise _lib.OrienMaskHipError("%s: a parameter must be dense in its storage (shape %s, strides %s)"
                                      % (who, tuple(p.shape), p.stride()))
+
+
+def _conform_state(p, b, who, what):
+    """State tensor ``b`` (``what``: its key in ``state[p]``) as the kernel walks it: checked against parameter ``p``, and copied
+    into the parameter's storage order where it has another."""
+    if not isinstance(b, _torch.Tensor) or b.shape != p.shape:
+        raise _lib.OrienMaskHipError("%s: %s does not match its parameter's shape" % (who, what))
+    if b.device != p.device or b.dtype != _torch.float32 or b.layout is not _torch.strided:
+        raise _lib.OrienMaskHipError("%s: %s must be float32 on the parameter's device; got %s on %s"
+                                     % (who, what, b.dtype, b.device))
+    if _layout(b) != _layout(p):
+        nb = _torch.empty_like(p, requires_grad=False)
+        nb.copy_(b)
+        b = nb
+    return b
 
 
 class _Plan:
@@ -371,6 +349,12 @@ class _HipStep:
         self._built_for = self._structure()
         self._built_clip = self._clip_key()
 
+    def _current_plans(self):
+        """The plans, built again where the groups or the form of the step changed since they were built."""
+        if getattr(self, "_plans", None) is None or self._built_for != self._structure() or self._built_clip != self._clip_key():
+            self._build_plans()
+        return self._plans
+
     def _clip_key(self):
         return (getattr(self, "max_grad_norm", None) is not None, getattr(self, "nonfinite", "propagate"),
                 getattr(self, "ema_decay", None) is not None)
@@ -431,10 +415,9 @@ class _HipStep:
         check_clip(max_norm, nonfinite, self._NAME)
         decay, warmup = getattr(self, "ema_decay", None), getattr(self, "ema_warmup", True)
         check_ema(decay, warmup, self._NAME)
-        if getattr(self, "_plans", None) is None or self._built_for != self._structure() or self._built_clip != self._clip_key():
-            self._build_plans()
+        plans = self._current_plans()
         with _torch.no_grad():
-            for plan in self._plans:
+            for plan in plans:
                 self._step_plan(plan, None if max_norm is None else float(max_norm), nonfinite == "skip",
                                 None if decay is None else (decay, warmup))
         return loss
@@ -445,9 +428,7 @@ class _HipStep:
         if getattr(self, "ema_decay", None) is None:
             raise _lib.OrienMaskHipError("%s.%s: averaging is not enabled (ema_decay is None)" % (self._NAME, what))
         check_ema(self.ema_decay, self.ema_warmup, self._NAME)
-        if getattr(self, "_plans", None) is None or self._built_for != self._structure() or self._built_clip != self._clip_key():
-            self._build_plans()
-        return self._plans[0]
+        return self._current_plans()[0]
 
     def ema_updates(self):
         """The number of EMA updates applied so far: the host's count, or with nonfinite="skip" (only the device knows which
@@ -591,18 +572,6 @@ class SGD(_HipStep, _TorchSGD):
             plan.has_mom[i] = momentum != 0
         plan.hyper[gi] = key
 
-    def _conform_buf(self, p, b):
-        if not isinstance(b, _torch.Tensor) or b.shape != p.shape:
-            raise _lib.OrienMaskHipError("orienmask_amd.optim.SGD: momentum_buffer does not match its parameter's shape")
-        if b.device != p.device or b.dtype != _torch.float32 or b.layout is not _torch.strided:
-            raise _lib.OrienMaskHipError("orienmask_amd.optim.SGD: momentum_buffer must be float32 on the parameter's device; got "
-                                         "%s on %s" % (b.dtype, b.device))
-        if _layout(b) != _layout(p):
-            nb = _torch.empty_like(p, requires_grad=False)
-            nb.copy_(b)
-            b = nb
-        return b
-
     def _step_plan(self, plan, clip=None, skip_mode=False, ema=None):
         """One device's step; ``clip``: None, or float max_grad_norm (then ``skip_mode``: nonfinite == "skip"); ``ema``: None, or
         (ema_decay, ema_warmup)."""
@@ -650,7 +619,7 @@ class SGD(_HipStep, _TorchSGD):
                 if plan.device_first[i]:
                     flags[i] |= OM_SGD_DEVICE_FIRST
                 if b is not bufs[i]:
-                    nb = self._conform_buf(p, b)
+                    nb = _conform_state(p, b, self._NAME, "momentum_buffer")
                     if nb is not b:
                         st["momentum_buffer"] = b = nb
                     bufs[i] = b
@@ -712,7 +681,12 @@ class _HipAdamStep(_HipStep):
     _ROW = ADAM_ROW
     _SWAP_ENTRY = "om_adam_ema_swap"
 
-    def _init_adam(self, max_grad_norm, nonfinite, ema_decay, ema_warmup):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), *args, max_grad_norm=None, nonfinite="propagate", ema_decay=None,
+                 ema_warmup=True, **kwargs):
+        check_clip(max_grad_norm, nonfinite, self._NAME)
+        check_ema(ema_decay, ema_warmup, self._NAME)
+        self._check_args(lr, betas)
+        super().__init__(params, lr, betas, *args, **kwargs)                # torch's constructor, next in the MRO
         for group in self.param_groups:
             self._check_group(group)
         self._init_hip(max_grad_norm, nonfinite, ema_decay, ema_warmup)
@@ -842,18 +816,6 @@ class _HipAdamStep(_HipStep):
         plan.hyper[gi] = key
         plan.scalars = {}                                 # (group, step) -> (nss, bc2s), as long as no group changes
 
-    def _conform_moment(self, p, b, what):
-        if not isinstance(b, _torch.Tensor) or b.shape != p.shape:
-            raise _lib.OrienMaskHipError("%s: %s does not match its parameter's shape" % (self._NAME, what))
-        if b.device != p.device or b.dtype != _torch.float32 or b.layout is not _torch.strided:
-            raise _lib.OrienMaskHipError("%s: %s must be float32 on the parameter's device; got %s on %s"
-                                         % (self._NAME, what, b.dtype, b.device))
-        if _layout(b) != _layout(p):
-            nb = _torch.empty_like(p, requires_grad=False)
-            nb.copy_(b)
-            b = nb
-        return b
-
     def _step_plan(self, plan, clip=None, skip_mode=False, ema=None):
         groups = self.param_groups
         for gi in plan.group_slots:
@@ -892,7 +854,7 @@ class _HipAdamStep(_HipStep):
                 moments[i] = None
             m, v = st["exp_avg"], st["exp_avg_sq"]
             if moments[i] is None or m is not moments[i][0] or v is not moments[i][1]:
-                nm, nv = self._conform_moment(p, m, "exp_avg"), self._conform_moment(p, v, "exp_avg_sq")
+                nm, nv = _conform_state(p, m, self._NAME, "exp_avg"), _conform_state(p, v, self._NAME, "exp_avg_sq")
                 if nm is not m:
                     st["exp_avg"] = m = nm
                 if nv is not v:
@@ -942,27 +904,11 @@ class HipAdam(_HipAdamStep, _TorchAdam):
 
     _NAME = "orienmask_amd.optim.HipAdam"
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), *args, max_grad_norm=None, nonfinite="propagate", ema_decay=None,
-                 ema_warmup=True, **kwargs):
-        check_clip(max_grad_norm, nonfinite, self._NAME)
-        check_ema(ema_decay, ema_warmup, self._NAME)
-        self._check_args(lr, betas)
-        super().__init__(params, lr, betas, *args, **kwargs)
-        self._init_adam(max_grad_norm, nonfinite, ema_decay, ema_warmup)
-
 
 class HipAdamW(_HipAdamStep, _TorchAdamW):
     """torch.optim.AdamW with the same step: the decay is ``p *= 1 - lr * weight_decay`` ahead of the update."""
 
     _NAME = "orienmask_amd.optim.HipAdamW"
-
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), *args, max_grad_norm=None, nonfinite="propagate", ema_decay=None,
-                 ema_warmup=True, **kwargs):
-        check_clip(max_grad_norm, nonfinite, self._NAME)
-        check_ema(ema_decay, ema_warmup, self._NAME)
-        self._check_args(lr, betas)
-        super().__init__(params, lr, betas, *args, **kwargs)
-        self._init_adam(max_grad_norm, nonfinite, ema_decay, ema_warmup)
 
 
 # ---- optim/param_groups.py ------------------------------------------------------------------------------------------------------

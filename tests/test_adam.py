@@ -16,26 +16,9 @@ import ema_np as E
 import loss_counter_cases as cases
 import optim_np as N
 from orienmask_amd import optim as O
+from optim_harness import dev, _param, _np, _np_grad, _set_grads  # noqa: F401  (dev is a fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev(built):
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    return torch.device("cuda:0")
-
-
-def _param(dev, a):
-    return torch.nn.Parameter(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev))
-
-
-def _np(t):
-    """The tensor's values in STORAGE order."""
-    t = t.detach()
-    flat = torch.as_strided(t, (t.numel(),), (1,)) if O._is_dense(t) and t.numel() else t.reshape(-1)
-    return flat.cpu().numpy()
 
 
 def _hyper_of(group):
@@ -79,18 +62,6 @@ def _assert_state(opt, params, ref, what, counts=True):
         assert N.same_bits(_np(st["exp_avg_sq"]), ref.v[i]), (what, "exp_avg_sq", i, tuple(p.shape))
         if counts:
             assert float(st["step"]) == ref.k[i], (what, "step", i, float(st["step"]), ref.k[i])
-
-
-def _np_grad(p):
-    g = p.grad.detach()
-    if g.stride() != p.stride():
-        g = torch.empty_like(p).copy_(g)
-    return _np(g)
-
-
-def _set_grads(dev, params, grads):
-    for p, g in zip(params, grads):
-        p.grad = None if g is None else (g if isinstance(g, torch.Tensor) else torch.from_numpy(np.asarray(g, np.float32)).to(dev).view_as(p))
 
 
 def _drive(dev, opt, params, grads_per_step, ref=None, what="", after_step=None):

@@ -13,25 +13,11 @@ import optim_np as N
 import train_step as T
 from orienmask_amd import builder, lib as omlib
 from orienmask_amd import optim as O
+from optim_harness import dev, _param, _np, _set_grads  # noqa: F401  (dev is a fixture)
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
 HYPER = dict(lr=1e-2, momentum=0.9, weight_decay=5e-4)
-
-
-@pytest.fixture(scope="module")
-def dev(built):
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    return torch.device("cuda:0")
-
-
-def _param(dev, a):
-    return torch.nn.Parameter(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev))
-
-
-def _np(t):
-    return t.detach().reshape(-1).cpu().numpy()
 
 
 def _hyper_of(group):
@@ -58,8 +44,7 @@ def _drive(dev, opt, params, grads_per_step, after_step=None, what=""):
     bufs = [None] * len(params)
     seen = []
     for s, grads in enumerate(grads_per_step):
-        for p, g in zip(params, grads):
-            p.grad = None if g is None else (g if isinstance(g, torch.Tensor) else torch.from_numpy(np.asarray(g, np.float32)).to(dev)).view_as(p)
+        _set_grads(dev, params, grads)
         hyper = _hyper_of(opt.param_groups[0])
         assert len(opt.param_groups) == 1
         opt.step()

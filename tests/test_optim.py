@@ -14,26 +14,9 @@ import optim_np as N
 import train_step as T
 from orienmask_amd import builder, lib as omlib
 from orienmask_amd import optim as O
+from optim_harness import dev, _param, _np, _np_grad, _set_grads  # noqa: F401  (dev is a fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev(built):
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    return torch.device("cuda:0")
-
-
-def _param(dev, a):
-    return torch.nn.Parameter(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev))
-
-
-def _np(t):
-    """The tensor's values in STORAGE order (a channels_last weight is updated in storage order)."""
-    t = t.detach()
-    flat = torch.as_strided(t, (t.numel(),), (1,)) if O._is_dense(t) and t.numel() else t.reshape(-1)
-    return flat.cpu().numpy()
 
 
 def _hyper_of(group):
@@ -62,8 +45,7 @@ def _drive(dev, opt, params, grads_per_step, after_step=None, what=""):
     cur = [_np(p).copy() for p in params]
     bufs = [None] * len(params)
     for s, grads in enumerate(grads_per_step):
-        for p, g in zip(params, grads):
-            p.grad = None if g is None else (g if isinstance(g, torch.Tensor) else torch.from_numpy(np.asarray(g, np.float32)).to(dev).view_as(p))
+        _set_grads(dev, params, grads)
         hypers = [_hyper_of(group_of[id(p)]) for p in params]
         opt.step()
         flat = [None if p.grad is None else _np_grad(p) for p in params]
@@ -72,14 +54,6 @@ def _drive(dev, opt, params, grads_per_step, after_step=None, what=""):
         if after_step is not None:
             after_step(s)
     return cur, bufs
-
-
-def _np_grad(p):
-    """The gradient in the parameter's storage order."""
-    g = p.grad.detach()
-    if g.stride() != p.stride():
-        g = torch.empty_like(p).copy_(g)
-    return _np(g)
 
 
 # ---- hyper-parameter sets, fixtures ---------------------------------------------------------------------------------------------
