@@ -1078,7 +1078,7 @@ int om_conv2d_bf16_frozen_forward(const uint16_t* x, const float* w, int B, int 
                                   double eps, float slope, const uint16_t* residual, uint16_t* y, om_stream stream);
 
 /* ---- The gradients of om_conv2d_bf16_forward (orienmask_amd.train.conv2d_bf16 with backward='hip'; the models with amp='bf16',
- *      conv_forward='hip', conv_grad='hip'; csrc/conv_grad_bf16.hip): dy [B,cout,Ho,Wo] and x [B,cin,H,W] bf16 (uint16_t bits), w
+ *      conv_forward='hip', conv_grad='hip'; csrc/conv_grad_bf16.hip, csrc/conv_dw.hip): dy [B,cout,Ho,Wo] and x [B,cin,H,W] bf16 (uint16_t bits), w
  *      [cout,cin,ksize,ksize] the FLOAT32 master weight; dx [B,cin,H,W] float32 where dx_is_f32 != 0, bf16 otherwise; dw
  *      [cout,cin,ksize,ksize] and dbias [cout] float32.  The geometries, layouts and size limits of om_conv2d_grad_*; H and W are
  *      the INPUT's.  On v_mfma_f32_32x32x16_bf16.

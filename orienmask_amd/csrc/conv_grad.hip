@@ -1,6 +1,7 @@
-// The gradients of the training model's convolutions (orienmask_amd/train.py: conv2d), for the three geometries the two models
+// The data gradient of the training model's convolutions (orienmask_amd/train.py: conv2d), for the three geometries the two models
 // contain: 1x1 stride 1 pad 0, 3x3 stride 1 pad 1, 3x3 stride 2 pad 1.  fp32 NCHW contiguous, as the training activations are;
 // fp32 operands on v_mfma_f32_32x32x2_f32 (an fmaf chain per output element), fp32 accumulation.  Ho = (H + 2*pad - ks)/s + 1.
+// The weight and bias gradients, and the workspace query, are conv_dw.hip.
 //
 //   conv_dx_kernel   dx[b,ci,iy,ix] = sum_{co,kh,kw} dy[b,co,oy,ox] * w[co,ci,kh,kw],   iy = oy*s + kh - pad, ix = ox*s + kw - pad
 //       GEMM: rows = ci (first operand: weights), columns = pixels (second operand: dy), k = (co, tap).  A lane owns one pixel, so
@@ -18,16 +19,6 @@
 //       Chains: a matrix-instruction accumulator takes the KC output channels of a chunk times the column taps of ONE row tap (at
 //       most 32 products: 8 x 3 at 3x3, 32 at 1x1), then is added into a double per element and cleared; dx is that double rounded
 //       once.  (One fp32 chain over k = 576 measured 1.1e-6 of the tensor's scale, four times torch-CPU-float32's error.)
-//   conv_dw_kernel   dw[co,ci,kh,kw] = sum_{b,oy,ox} dy[b,co,oy,ox] * x[b,ci,oy*s+kh-pad,ox*s+kw-pad]
-//       GEMM: rows = co (dy), columns = ci, one 32x32 accumulator per tap, k = the flat output pixel (b, oy, ox); both operands are
-//       contiguous along k in NCHW.  k is split over workgroups (blockIdx.x), at most CG_SPLIT_PIX pixels each.  Three levels of
-//       sums: the matrix-instruction accumulator takes CG_CHAIN_PIX pixels (1x1: four accumulators take every fourth pixel pair of
-//       them, 8 pixels each, and are summed pairwise), then is added into a second fp32 accumulator and
-//       cleared (at most 64 such additions per workgroup); with more than one split the workgroup writes its tile to
-//       partial[split][co][ci][tap] in the caller's workspace and conv_dw_reduce_kernel sums the splits of an element in split order
-//       in double and rounds once.  The number of splits depends on the shape and the device's compute-unit count only.  No
-//       atomics: the same bits on every run.
-//   conv_dbias_kernel   db[co] = sum dy[b,co,:,:] in double, one workgroup per channel, fixed order.
 // Every load and store is bounds-checked per element (any B, cin, cout, H, W >= 1; no alignment is assumed); rows and columns of a
 // tile that lie outside the tensor are staged as zeros and never stored.
 #include "conv_train.h"
@@ -35,9 +26,6 @@
 namespace om {
 
 constexpr int CG_THREADS = 256;
-constexpr int CG_CHAIN_PIX = 32;        // dw: pixels (= products) of a first-level chain
-constexpr int CG_SPLIT_PIX = 2048;      // dw: most pixels of a workgroup, i.e. at most 64 first-level chains in its second-level sum
-constexpr int CG_MIN_PIX = 256;         // dw: fewest pixels a split is cut down to when the launch would leave compute units idle
 constexpr int CG_DX_WIDE_CELLS = 512;   // dx: cells per image from which the 128-pixel tile is used
 
 // the row taps and column taps of one tile family: tap r reads dy at cell q + rshift[r] * Wo (weights row kh[r]), likewise columns
@@ -53,15 +41,6 @@ struct DxArgs {
     int cin, cout, H, W, Ho, Wo, HoWo, stride;
     int n_classes;
     CgTaps cls[4];
-};
-
-struct DwArgs {
-    const float* x; const float* dy;
-    float* out;                 // dw, or the partial tiles [splits][cout][cin][taps]
-    int cin, cout, H, W, Ho, Wo, HoWo, stride, pad;
-    int K;                      // B * Ho * Wo
-    int chunk;                  // pixels per split
-    size_t n;                   // cout * cin * taps
 };
 
 // ---------------------------------------------------------------------------------------------------------------- data gradient
@@ -156,156 +135,7 @@ __global__ void __launch_bounds__(CG_THREADS) conv_dx_kernel(const DxArgs a) {
         }
 }
 
-// ---------------------------------------------------------------------------------------------------------------- weight gradient
-// WCO waves along co (32 each), 4 / WCO along ci (32 each); KP pixels per staged step, LDS rows padded to KP + 1 floats.
-template <int WCO, int TAPS>
-__global__ void __launch_bounds__(CG_THREADS) conv_dw_kernel(const DwArgs a) {
-    constexpr int WCI = 4 / WCO, KP = 32 / WCI, LD = KP + 1, COT = 32 * WCO, CIT = 32 * WCI;
-    constexpr int G = CG_THREADS / KP;              // threads per pixel column of the staging
-    constexpr int KS = TAPS == 1 ? 1 : 3;
-    __shared__ float s_dy[COT * LD];                // [co][pixel]
-    __shared__ float s_x[TAPS * CIT * LD];          // [tap][ci][pixel]
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wco = wave / WCI, wci = wave % WCI;
-    const int fi = lane & 31, fk = lane >> 5;
-    const int split = blockIdx.x, co0 = blockIdx.y * COT, ci0 = blockIdx.z * CIT;
-    const int k_begin = split * a.chunk;
-    const int k_end = min(a.K, k_begin + a.chunk);
-    const int kp = tid % KP, g = tid / KP;
-    const size_t hw = (size_t)a.H * a.W;
-    const bool live = co0 + wco * 32 < a.cout && ci0 + wci * 32 < a.cin;      // this wave's block holds an element of dw
-
-    constexpr int CHAIN_STEPS = CG_CHAIN_PIX / KP;
-    static_assert(CG_CHAIN_PIX % KP == 0, "a chain is a whole number of steps");
-    // 1x1: NCH interleaved accumulators share the pixels of a chain (pixel pair kk goes to accumulator kk % NCH) and are summed
-    // pairwise where the chain ends, so no fmaf chain is longer than CG_CHAIN_PIX / NCH products.  One chain over the 18 pixels of
-    // a 3 x 3 map at B = 2 measured 2.12 x torch-CPU-float32's error over the tensor's scale on in-network operands.
-    constexpr int NCH = TAPS == 1 ? 4 : 1;
-    static_assert((KP / 2) % NCH == 0, "every step gives each accumulator the same number of pixel pairs");
-    f32x16 acc[TAPS * NCH], tot[TAPS];
-#pragma unroll
-    for (int tp = 0; tp < TAPS; ++tp) clear16(tot[tp]);
-#pragma unroll
-    for (int i = 0; i < TAPS * NCH; ++i) clear16(acc[i]);
-
-    int step = 0;
-    for (int k0 = k_begin; k0 < k_end; k0 += KP) {
-        const int k = k0 + kp;
-        const bool valid = k < k_end;
-        const int kb = valid ? k : k_end - 1;
-        const int b = kb / a.HoWo, qq = kb - b * a.HoWo;
-        const int oy = qq / a.Wo, ox = qq - oy * a.Wo;
-        __syncthreads();                            // the previous step's reads are done
-        {
-            const float* p = a.dy + (size_t)b * a.cout * a.HoWo + qq;
-            for (int cl = g; cl < COT; cl += G) {
-                const int co = co0 + cl;
-                float v = 0.f;
-                if (valid && co < a.cout) v = p[(size_t)co * a.HoWo];
-                s_dy[cl * LD + kp] = v;
-            }
-        }
-#pragma unroll
-        for (int tp = 0; tp < TAPS; ++tp) {
-            const int iy = oy * a.stride + tp / KS - a.pad, ix = ox * a.stride + tp % KS - a.pad;
-            const bool tv = valid && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-            const float* p = a.x + (size_t)b * a.cin * hw + (tv ? (size_t)iy * a.W + ix : 0);
-            for (int cl = g; cl < CIT; cl += G) {
-                const int ci = ci0 + cl;
-                float v = 0.f;
-                if (tv && ci < a.cin) v = p[(size_t)ci * hw];
-                s_x[(tp * CIT + cl) * LD + kp] = v;
-            }
-        }
-        __syncthreads();
-        if (live) {
-            const float* ap = s_dy + (wco * 32 + fi) * LD + fk;
-            const float* bp = s_x + (wci * 32 + fi) * LD + fk;
-#pragma unroll
-            for (int kk = 0; kk < KP / 2; ++kk) {
-                const float av = ap[2 * kk];
-#pragma unroll
-                for (int tp = 0; tp < TAPS; ++tp)
-                    acc[tp * NCH + kk % NCH] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bp[tp * CIT * LD + 2 * kk], acc[tp * NCH + kk % NCH], 0, 0, 0);
-            }
-            if (++step == CHAIN_STEPS) {            // the chain ends
-                step = 0;
-#pragma unroll
-                for (int tp = 0; tp < TAPS; ++tp) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        if constexpr (NCH == 4) tot[tp][r] += (acc[tp * 4][r] + acc[tp * 4 + 1][r]) + (acc[tp * 4 + 2][r] + acc[tp * 4 + 3][r]);
-                        else tot[tp][r] += acc[tp][r];
-                    }
-#pragma unroll
-                    for (int c = 0; c < NCH; ++c) clear16(acc[tp * NCH + c]);
-                }
-            }
-        }
-    }
-    if (!live) return;
-    // D layout: column (ci) = lane & 31, row (co) = 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3)
-    const int ci = ci0 + wci * 32 + fi;
-    if (ci >= a.cin) return;
-    float* o = a.out + (size_t)split * a.n;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int co = co0 + wco * 32 + 8 * (r >> 2) + 4 * fk + (r & 3);
-        if (co >= a.cout) continue;
-#pragma unroll
-        for (int tp = 0; tp < TAPS; ++tp) {
-            float rest = acc[tp * NCH][r];          // an unfinished chain
-            if constexpr (NCH == 4) rest = (acc[tp * 4][r] + acc[tp * 4 + 1][r]) + (acc[tp * 4 + 2][r] + acc[tp * 4 + 3][r]);
-            o[((size_t)co * a.cin + ci) * TAPS + tp] = tot[tp][r] + rest;
-        }
-    }
-}
-
-// dw[e] = the splits' partial[s][e] summed in split order, in double, rounded once
-__global__ void __launch_bounds__(CG_THREADS) conv_dw_reduce_kernel(const float* __restrict__ partial, float* __restrict__ dw, size_t n,
-                                                                    int splits) {
-    const size_t e = (size_t)blockIdx.x * CG_THREADS + threadIdx.x;
-    if (e >= n) return;
-    double s = 0.0;
-    for (int i = 0; i < splits; ++i) s += (double)partial[(size_t)i * n + e];
-    dw[e] = (float)s;
-}
-
-// db[co] = sum over b and the plane of dy[b,co]: per-thread sums over a fixed stride, wave shuffles, four LDS slots
-__global__ void __launch_bounds__(CG_THREADS) conv_dbias_kernel(const float* __restrict__ dy, float* __restrict__ db, int B, int cout,
-                                                                int HoWo) {
-    __shared__ double lds[CG_THREADS / 64];
-    const int co = blockIdx.x;
-    double s = 0.0;
-    for (int b = 0; b < B; ++b) {
-        const float* p = dy + ((size_t)b * cout + co) * HoWo;
-        for (int i = threadIdx.x; i < HoWo; i += CG_THREADS) s += (double)p[i];
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) db[co] = (float)((lds[0] + lds[1]) + (lds[2] + lds[3]));
-}
-
 // ---------------------------------------------------------------------------------------------------------------- host
-static int cg_dw_wco(int cout) { return cout > 64 ? 4 : cout > 32 ? 2 : 1; }
-
-// splits of the weight gradient's k: at most CG_SPLIT_PIX pixels each; more, down to CG_MIN_PIX pixels each, while the launch
-// has fewer than two workgroups per compute unit
-static int cg_dw_splits(const ConvGeom& g, int* chunk) {
-    const int wco = cg_dw_wco(g.cout), wci = 4 / wco;
-    const long long tiles = (long long)((g.cout + 32 * wco - 1) / (32 * wco)) * ((g.cin + 32 * wci - 1) / (32 * wci));
-    long long s = ((long long)g.K + CG_SPLIT_PIX - 1) / CG_SPLIT_PIX;
-    const long long want = (2ll * device_compute_units() + tiles - 1) / tiles;
-    const long long most = ((long long)g.K + CG_MIN_PIX - 1) / CG_MIN_PIX;
-    if (s < want) s = want < most ? want : most;
-    if (s < 1) s = 1;
-    *chunk = (int)(((long long)g.K + s - 1) / s);
-    return (int)(((long long)g.K + *chunk - 1) / *chunk);
-}
-
 static void cg_taps_stride1(int ks, CgTaps* t) {
     *t = CgTaps{};
     t->nr = t->nc = ks;
@@ -332,24 +162,9 @@ static void launch_dx(const DxArgs& a, int B, hipStream_t st) {
     hipLaunchKernelGGL((conv_dx_kernel<WM, TN, TAPS>), grid, dim3(CG_THREADS), 0, st, a);
 }
 
-template <int WCO, int TAPS>
-static void launch_dw(const DwArgs& a, int splits, hipStream_t st) {
-    constexpr int COT = 32 * WCO, CIT = 32 * (4 / WCO);
-    const dim3 grid(splits, (a.cout + COT - 1) / COT, (a.cin + CIT - 1) / CIT);
-    hipLaunchKernelGGL((conv_dw_kernel<WCO, TAPS>), grid, dim3(CG_THREADS), 0, st, a);
-}
-
 }  // namespace om
 
 extern "C" {
-
-size_t om_conv2d_grad_workspace_bytes(int B, int cin, int H, int W, int cout, int ksize, int stride) {
-    om::ConvGeom g;
-    if (!om::conv_geometry(B, cin, H, W, cout, ksize, stride, &g)) return 0;
-    int chunk;
-    const int splits = om::cg_dw_splits(g, &chunk);
-    return splits > 1 ? (size_t)splits * g.n * sizeof(float) : 0;
-}
 
 int om_conv2d_grad_input(const float* dy, const float* w, int B, int cin, int H, int W, int cout, int ksize, int stride, float* dx,
                          void* workspace, size_t ws_bytes, om_stream stream) {
@@ -377,44 +192,6 @@ int om_conv2d_grad_input(const float* dy, const float* w, int B, int cin, int H,
         if (wide) om::launch_dx<4, 2, 9>(a, B, st);
         else om::launch_dx<1, 1, 9>(a, B, st);
     }
-    OM_CHECK_HIP(hipGetLastError());
-    return OM_OK;
-}
-
-int om_conv2d_grad_weight(const float* x, const float* dy, int B, int cin, int H, int W, int cout, int ksize, int stride, float* dw,
-                          float* dbias, void* workspace, size_t ws_bytes, om_stream stream) {
-    OM_REQUIRE(x && dy && (dw || dbias), OM_EINVAL, "om_conv2d_grad_weight: null pointer");
-    om::ConvGeom g;
-    if (!om::conv_geometry(B, cin, H, W, cout, ksize, stride, &g))
-        return om::conv_geometry_refused("om_conv2d_grad_weight", B, cin, H, W, cout, ksize, stride);
-    int chunk;
-    const int splits = om::cg_dw_splits(g, &chunk);
-    const size_t need = dw && splits > 1 ? (size_t)splits * g.n * sizeof(float) : 0;
-    OM_REQUIRE(need == 0 || (workspace && ws_bytes >= need), OM_ENOMEM, "om_conv2d_grad_weight: workspace of %zu bytes, need %zu",
-               workspace ? ws_bytes : (size_t)0, need);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    om::DwArgs a = {};
-    a.x = x; a.dy = dy; a.out = splits > 1 ? static_cast<float*>(workspace) : dw;
-    a.cin = cin; a.cout = cout; a.H = H; a.W = W; a.Ho = g.Ho; a.Wo = g.Wo; a.HoWo = g.HoWo; a.stride = stride; a.pad = g.pad;
-    a.K = g.K; a.chunk = chunk; a.n = g.n;
-    const int wco = om::cg_dw_wco(cout);
-    if (!dw) {
-        // a frozen weight with a trainable bias: only the bias gradient below
-    } else if (ksize == 1) {
-        if (wco == 4) om::launch_dw<4, 1>(a, splits, st);
-        else if (wco == 2) om::launch_dw<2, 1>(a, splits, st);
-        else om::launch_dw<1, 1>(a, splits, st);
-    } else {
-        if (wco == 4) om::launch_dw<4, 9>(a, splits, st);
-        else if (wco == 2) om::launch_dw<2, 9>(a, splits, st);
-        else om::launch_dw<1, 9>(a, splits, st);
-    }
-    if (dw && splits > 1) {
-        const unsigned blocks = (unsigned)((g.n + om::CG_THREADS - 1) / om::CG_THREADS);
-        hipLaunchKernelGGL(om::conv_dw_reduce_kernel, dim3(blocks), dim3(om::CG_THREADS), 0, st, static_cast<const float*>(workspace), dw,
-                           g.n, splits);
-    }
-    if (dbias) hipLaunchKernelGGL(om::conv_dbias_kernel, dim3(cout), dim3(om::CG_THREADS), 0, st, dy, dbias, B, cout, g.HoWo);
     OM_CHECK_HIP(hipGetLastError());
     return OM_OK;
 }

@@ -1,9 +1,10 @@
-// The bf16 gradients of the training model's convolutions (orienmask_amd/train.py: conv2d_bf16_backward with backend 'hip'; the
-// models with amp='bf16', conv_forward='hip', conv_grad='hip'), for conv_train.h's three geometries.  NCHW contiguous; dy and x
-// bf16, w the float32 master weight, on v_mfma_f32_32x32x16_bf16.  What conv_grad.hip is to float32.
+// The bf16 data gradient of the training model's convolutions (orienmask_amd/train.py: conv2d_bf16_backward with backend 'hip'; the
+// models with amp='bf16', conv_forward='hip', conv_grad='hip'), for conv_train.h's three geometries.  NCHW contiguous; dy bf16, w
+// the float32 master weight, on v_mfma_f32_32x32x16_bf16.  What conv_grad.hip is to float32.  The weight and bias gradients, and the
+// workspace query, are conv_dw.hip.
 //
 // ARITHMETIC CONTRACT (tests/test_conv_grad_bf16.py pins it)
-//   dy and x are bf16 and are widened exactly.  w is rounded with bf16.h's bf16_round while it is staged: that is what the forward
+//   dy is bf16 and is widened exactly.  w is rounded with bf16.h's bf16_round while it is staged: that is what the forward
 //   multiplied by, so the gradient is the gradient of the function that ran; there is no cast kernel and no bf16 copy of the weight.
 //   Every product of two bf16 values is exact in float32; all accumulation is float32 or wider.
 //   dx   the float32 output (dx_is_f32 = 1) is the sum, the bf16 output is bf16_round of the same sum.  Two float32 levels per
@@ -13,19 +14,12 @@
 //        chain over the whole k reached 4.3 x torch-CPU's error in the stride-2 dx of an in-network layer: DESIGN 3.30.)  The
 //        order is a function of the geometry only -- not of B, the tile or the device -- so an image's dx has the same bits alone
 //        and in any batch.
-//   dw   float32.  k is the flat output pixel (b, oy, ox), split over workgroups by conv_grad.hip's rule (a function of the shape and
-//        om::device_compute_units only).  Three levels: a matrix-instruction accumulator takes CGB_CHAIN_PIX = 32 pixels (two
-//        instructions; at 1x1 one instruction each in two accumulators that are then added), is added into a second float32
-//        accumulator and cleared (at most 64 such additions per workgroup); with more than one split the workgroup's tile goes to
-//        partial[split][co][ci][tap] in the workspace and conv_dw_bf16_reduce_kernel sums the splits in split order in double and
-//        rounds once.  No atomics.
-//   db   the sum of dy over batch and plane in double, in a fixed order, rounded once to float32.
 //
 // STRUCTURE
-//   dx, stride 1   the forward convolution of dy (cout channels in) with w'[ci][co][2-kh][2-kw] (1x1: w transposed): conv_bf16_tile.h's
+//   stride 1   the forward convolution of dy (cout channels in) with w'[ci][co][2-kh][2-kw] (1x1: w transposed): conv_bf16_tile.h's
 //        kernel with its transposed weight gather (WT), nothing else: position table, halo row, column-tap masks, LDS images,
 //        budget are the forward's (the head of conv_fwd_bf16.hip).
-//   dx, stride 2   conv_dx2_bf16_kernel: conv_grad.hip's four PARITY CLASSES (py, px) = (iy & 1, ix & 1) of the input pixel, one
+//   stride 2   conv_dx2_bf16_kernel: conv_grad.hip's four PARITY CLASSES (py, px) = (iy & 1, ix & 1) of the input pixel, one
 //        launch each.  A class is a grid of Hc x Wc = ceil((H - py) / 2) x ceil((W - px) / 2) cells (sy, sx) with iy = 2 sy + py,
 //        ix = 2 sx + px, so every element of dx belongs to exactly one class and is written by it, the last row or column of an odd
 //        or even H, W included (a class without cells is not launched).  Parity 0 has the one tap kh = 1 at oy = sy; parity 1 the
@@ -35,18 +29,9 @@
 //        (-1 where oy = Ho or ox = Wo: staged as zero): a shift of one staged row cannot serve here, because the class grid may be
 //        one column narrower than dy's.  Weights as [tap][ci][16 co] bf16, gathered from w[co][ci][kh][kw] and rounded while packing.
 //        One LDS buffer, the chunk in flight in registers, as the forward.
-//   dw   conv_dw_bf16_kernel: rows = co (first operand: dy), columns = ci (second operand: x, one 32 x 32 accumulator per tap), k =
-//        pixels; both operands are contiguous along k in memory and lie in LDS as [channel][pixel] bf16, so a lane's 8 consecutive
-//        k are one 16-byte read.  WCO waves along co, 4 / WCO along ci.  x is staged per tap (each pixel's tap address computed,
-//        zero outside the map), as conv_grad.hip stages it: simple and exact, and 9 two-byte loads per pixel and channel at 3x3.
-//        Staging the rows with their halo once and reading taps as shifts would cut that to ~1.1; left for later.
-//   db   conv_dbias_bf16_kernel, one workgroup per channel.
 //
-// BUDGET (gfx950 code objects; VGPR + AGPR, spill, LDS bytes)
-//   dx stride 1: conv_bf16_tile.h, __launch_bounds__(256, 2).  dx stride 2: __launch_bounds__(256, 2), LDS at most 28.1 KiB.
-//   dw: 3x3 holds 9 x 16 accumulators twice (first and second level) = 288 registers before any operand, so it cannot fit the 256
-//   of __launch_bounds__(256, 2) without spilling inside the main loop; it is built with __launch_bounds__(256) (one workgroup per
-//   SIMD set, up to 512 registers) as conv_grad.hip's dw kernel is, for the same reason.  LDS at most 55.5 KiB.
+// BUDGET (gfx950 code objects)
+//   stride 1: conv_bf16_tile.h, __launch_bounds__(256, 2).  stride 2: __launch_bounds__(256, 2), LDS at most 28.1 KiB.
 //   The figures per instantiation are in DESIGN 3.29.
 // Every load and store is bounds-checked per element (any B, cin, cout, H, W >= 1); every global access is of one element, so no
 // alignment beyond the element's own is assumed and there is one path only.
@@ -57,9 +42,6 @@ namespace om {
 constexpr int CGB_THREADS = 256;
 constexpr int CGB_MT = 128;             // dx stride 2: cells of a tile
 constexpr int CGB_DX2_FOLD = 64;        // dx stride 2: output channels of a first-level chain (four staged chunks of 16)
-constexpr int CGB_CHAIN_PIX = 32;       // dw: pixels of a first-level chain (two matrix instructions)
-constexpr int CGB_SPLIT_PIX = 2048;     // dw: most pixels of a workgroup: at most 64 first-level chains in its second-level sum
-constexpr int CGB_MIN_PIX = 256;        // dw: fewest pixels a split is cut down to when the launch would leave compute units idle
 
 struct Dx2Args {
     const bf16_t* dy; const float* w; void* dx;
@@ -67,15 +49,6 @@ struct Dx2Args {
     int cin, cout, H, W, Ho, Wo, HoWo;
     int Hc, Wc, HcWc;           // the class grid
     int P;                      // B * Hc * Wc
-};
-
-struct DwBf16Args {
-    const bf16_t* x; const bf16_t* dy;
-    float* out;                 // dw, or the partial tiles [splits][cout][cin][taps]
-    int cin, cout, H, W, Ho, Wo, HoWo, stride, pad;
-    int K;                      // B * Ho * Wo
-    int chunk;                  // pixels per split
-    size_t n;                   // cout * cin * taps
 };
 
 // ---------------------------------------------------------------------------------------------------------------- dx, stride 2
@@ -212,157 +185,7 @@ __global__ void __launch_bounds__(CGB_THREADS, 2) conv_dx2_bf16_kernel(const Dx2
         }
 }
 
-// ---------------------------------------------------------------------------------------------------------------- weight gradient
-// WCO waves along co (32 each), 4 / WCO along ci (32 each); KP pixels per staged step, LDS rows of KP + 8 bf16 (16-byte aligned)
-template <int WCO, int TAPS>
-__global__ void __launch_bounds__(CGB_THREADS) conv_dw_bf16_kernel(const DwBf16Args a) {
-    constexpr int WCI = 4 / WCO, COT = 32 * WCO, CIT = 32 * WCI;
-    constexpr int KP = (TAPS == 9 && WCI == 4) ? 16 : 32;           // (9 taps of 128 input channels at 32 pixels would not fit)
-    constexpr int LD = KP + 8;
-    constexpr int G = CGB_THREADS / KP;             // threads per pixel column of the staging
-    constexpr int KS = TAPS == 1 ? 1 : 3;
-    constexpr int NCH = TAPS == 1 ? 2 : 1;          // 1x1: the two instructions of a chain go to two accumulators
-    static_assert(NCH == 1 || KP == 32, "two accumulators take the two k-steps of one staged step");
-    __shared__ __attribute__((aligned(16))) bf16_t s_dy[COT * LD];          // [co][pixel]
-    __shared__ __attribute__((aligned(16))) bf16_t s_x[TAPS * CIT * LD];    // [tap][ci][pixel]
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wco = wave / WCI, wci = wave % WCI;
-    const int fi = lane & 31, fk = lane >> 5;
-    const int split = blockIdx.x, co0 = blockIdx.y * COT, ci0 = blockIdx.z * CIT;
-    const int k_begin = split * a.chunk;
-    const int k_end = min(a.K, k_begin + a.chunk);
-    const int kp = tid % KP, g = tid / KP;
-    const size_t hw = (size_t)a.H * a.W;
-    const bool live = co0 + wco * 32 < a.cout && ci0 + wci * 32 < a.cin;      // this wave's block holds an element of dw
-
-    f32x16 acc[TAPS * NCH], tot[TAPS];
-#pragma unroll
-    for (int tp = 0; tp < TAPS; ++tp) clear16(tot[tp]);
-#pragma unroll
-    for (int i = 0; i < TAPS * NCH; ++i) clear16(acc[i]);
-
-    int kstep = 0;              // matrix instructions (16 pixels each) in the open chain
-    for (int k0 = k_begin; k0 < k_end; k0 += KP) {
-        const int k = k0 + kp;
-        const bool valid = k < k_end;
-        const int kb = valid ? k : k_end - 1;
-        const int b = kb / a.HoWo, qq = kb - b * a.HoWo;
-        const int oy = qq / a.Wo, ox = qq - oy * a.Wo;
-        __syncthreads();                            // the previous step's reads are done
-        {
-            const bf16_t* p = a.dy + (size_t)b * a.cout * a.HoWo + qq;
-            for (int cl = g; cl < COT; cl += G) {
-                const int co = co0 + cl;
-                bf16_t v = 0;
-                if (valid && co < a.cout) v = p[(size_t)co * a.HoWo];
-                s_dy[cl * LD + kp] = v;
-            }
-        }
-#pragma unroll
-        for (int tp = 0; tp < TAPS; ++tp) {
-            const int iy = oy * a.stride + tp / KS - a.pad, ix = ox * a.stride + tp % KS - a.pad;
-            const bool tv = valid && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-            const bf16_t* p = a.x + (size_t)b * a.cin * hw + (tv ? (size_t)iy * a.W + ix : 0);
-            for (int cl = g; cl < CIT; cl += G) {
-                const int ci = ci0 + cl;
-                bf16_t v = 0;
-                if (tv && ci < a.cin) v = p[(size_t)ci * hw];
-                s_x[(tp * CIT + cl) * LD + kp] = v;
-            }
-        }
-        __syncthreads();
-        if (live) {
-            const bf16_t* ap = s_dy + (wco * 32 + fi) * LD + fk * 8;
-            const bf16_t* bp = s_x + (wci * 32 + fi) * LD + fk * 8;
-#pragma unroll
-            for (int ks = 0; ks < KP / 16; ++ks) {
-                const bf16x8 av = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(ap + ks * 16));
-#pragma unroll
-                for (int tp = 0; tp < TAPS; ++tp) {
-                    const bf16x8 bv = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(bp + tp * CIT * LD + ks * 16));
-                    const int ai = tp * NCH + (NCH == 2 ? ks : 0);
-                    acc[ai] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, acc[ai], 0, 0, 0);
-                }
-            }
-            kstep += KP / 16;
-            if (kstep == CGB_CHAIN_PIX / 16) {      // the chain ends
-                kstep = 0;
-#pragma unroll
-                for (int tp = 0; tp < TAPS; ++tp) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        if constexpr (NCH == 2) tot[tp][r] += acc[tp * 2][r] + acc[tp * 2 + 1][r];
-                        else tot[tp][r] += acc[tp][r];
-                    }
-#pragma unroll
-                    for (int c = 0; c < NCH; ++c) clear16(acc[tp * NCH + c]);
-                }
-            }
-        }
-    }
-    if (!live) return;
-    // D layout: column (ci) = lane & 31, row (co) = 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3)
-    const int ci = ci0 + wci * 32 + fi;
-    if (ci >= a.cin) return;
-    float* o = a.out + (size_t)split * a.n;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int co = co0 + wco * 32 + 8 * (r >> 2) + 4 * fk + (r & 3);
-        if (co >= a.cout) continue;
-#pragma unroll
-        for (int tp = 0; tp < TAPS; ++tp) {
-            float rest = acc[tp * NCH][r];          // an unfinished chain (zeros after a finished one)
-            if constexpr (NCH == 2) rest = acc[tp * 2][r] + acc[tp * 2 + 1][r];
-            o[((size_t)co * a.cin + ci) * TAPS + tp] = tot[tp][r] + rest;
-        }
-    }
-}
-
-// dw[e] = the splits' partial[s][e] summed in split order, in double, rounded once
-__global__ void __launch_bounds__(CGB_THREADS) conv_dw_bf16_reduce_kernel(const float* __restrict__ partial, float* __restrict__ dw,
-                                                                          size_t n, int splits) {
-    const size_t e = (size_t)blockIdx.x * CGB_THREADS + threadIdx.x;
-    if (e >= n) return;
-    double s = 0.0;
-    for (int i = 0; i < splits; ++i) s += (double)partial[(size_t)i * n + e];
-    dw[e] = (float)s;
-}
-
-// db[co] = sum over b and the plane of dy[b,co]: per-thread sums over a fixed stride, wave shuffles, four LDS slots
-__global__ void __launch_bounds__(CGB_THREADS) conv_dbias_bf16_kernel(const bf16_t* __restrict__ dy, float* __restrict__ db, int B,
-                                                                      int cout, int HoWo) {
-    __shared__ double lds[CGB_THREADS / 64];
-    const int co = blockIdx.x;
-    double s = 0.0;
-    for (int b = 0; b < B; ++b) {
-        const bf16_t* p = dy + ((size_t)b * cout + co) * HoWo;
-        for (int i = threadIdx.x; i < HoWo; i += CGB_THREADS) s += (double)bf16_widen(p[i]);
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) db[co] = (float)((lds[0] + lds[1]) + (lds[2] + lds[3]));
-}
-
 // ---------------------------------------------------------------------------------------------------------------- host
-static int cgb_dw_wco(int cout) { return cout > 64 ? 4 : cout > 32 ? 2 : 1; }
-
-// conv_grad.hip's split rule on this file's tiles: at most CGB_SPLIT_PIX pixels each; more, down to CGB_MIN_PIX pixels each, while
-// the launch has fewer than two workgroups per compute unit
-static int cgb_dw_splits(const ConvGeom& g, int* chunk) {
-    const int wco = cgb_dw_wco(g.cout), wci = 4 / wco;
-    const long long tiles = (long long)((g.cout + 32 * wco - 1) / (32 * wco)) * ((g.cin + 32 * wci - 1) / (32 * wci));
-    long long s = ((long long)g.K + CGB_SPLIT_PIX - 1) / CGB_SPLIT_PIX;
-    const long long want = (2ll * device_compute_units() + tiles - 1) / tiles;
-    const long long most = ((long long)g.K + CGB_MIN_PIX - 1) / CGB_MIN_PIX;
-    if (s < want) s = want < most ? want : most;
-    if (s < 1) s = 1;
-    *chunk = (int)(((long long)g.K + s - 1) / s);
-    return (int)(((long long)g.K + *chunk - 1) / *chunk);
-}
-
 template <int NR, int NC>
 static void launch_dx2(Dx2Args a, int B, hipStream_t st) {
     a.Hc = (a.H - (NR - 1) + 1) / 2;
@@ -376,24 +199,9 @@ static void launch_dx2(Dx2Args a, int B, hipStream_t st) {
     else hipLaunchKernelGGL((conv_dx2_bf16_kernel<1, NR, NC>), dim3(tiles, 1), dim3(CGB_THREADS), 0, st, a);
 }
 
-template <int WCO, int TAPS>
-static void launch_dw_bf16(const DwBf16Args& a, int splits, hipStream_t st) {
-    constexpr int COT = 32 * WCO, CIT = 32 * (4 / WCO);
-    const dim3 grid(splits, (a.cout + COT - 1) / COT, (a.cin + CIT - 1) / CIT);
-    hipLaunchKernelGGL((conv_dw_bf16_kernel<WCO, TAPS>), grid, dim3(CGB_THREADS), 0, st, a);
-}
-
 }  // namespace om
 
 extern "C" {
-
-size_t om_conv2d_bf16_grad_workspace_bytes(int B, int cin, int H, int W, int cout, int ksize, int stride) {
-    om::ConvGeom g;
-    if (!om::conv_geometry(B, cin, H, W, cout, ksize, stride, &g)) return 0;
-    int chunk;
-    const int splits = om::cgb_dw_splits(g, &chunk);
-    return splits > 1 ? (size_t)splits * g.n * sizeof(float) : 0;
-}
 
 int om_conv2d_bf16_grad_input(const uint16_t* dy, const float* w, int B, int cin, int H, int W, int cout, int ksize, int stride,
                               void* dx, int dx_is_f32, void* workspace, size_t ws_bytes, om_stream stream) {
@@ -425,44 +233,6 @@ int om_conv2d_bf16_grad_input(const uint16_t* dy, const float* w, int B, int cin
         om::launch_dx2<2, 1>(a, B, st);
         om::launch_dx2<2, 2>(a, B, st);
     }
-    OM_CHECK_HIP(hipGetLastError());
-    return OM_OK;
-}
-
-int om_conv2d_bf16_grad_weight(const uint16_t* x, const uint16_t* dy, int B, int cin, int H, int W, int cout, int ksize, int stride,
-                               float* dw, float* dbias, void* workspace, size_t ws_bytes, om_stream stream) {
-    OM_REQUIRE(x && dy && (dw || dbias), OM_EINVAL, "om_conv2d_bf16_grad_weight: null pointer");
-    om::ConvGeom g;
-    if (!om::conv_geometry(B, cin, H, W, cout, ksize, stride, &g))
-        return om::conv_geometry_refused("om_conv2d_bf16_grad_weight", B, cin, H, W, cout, ksize, stride);
-    int chunk;
-    const int splits = om::cgb_dw_splits(g, &chunk);
-    const size_t need = dw && splits > 1 ? (size_t)splits * g.n * sizeof(float) : 0;
-    OM_REQUIRE(need == 0 || (workspace && ws_bytes >= need), OM_ENOMEM, "om_conv2d_bf16_grad_weight: workspace of %zu bytes, need %zu",
-               workspace ? ws_bytes : (size_t)0, need);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    om::DwBf16Args a = {};
-    a.x = x; a.dy = dy; a.out = splits > 1 ? static_cast<float*>(workspace) : dw;
-    a.cin = cin; a.cout = cout; a.H = H; a.W = W; a.Ho = g.Ho; a.Wo = g.Wo; a.HoWo = g.HoWo; a.stride = stride; a.pad = g.pad;
-    a.K = g.K; a.chunk = chunk; a.n = g.n;
-    const int wco = om::cgb_dw_wco(cout);
-    if (!dw) {
-        // a frozen weight with a trainable bias: only the bias gradient below
-    } else if (ksize == 1) {
-        if (wco == 4) om::launch_dw_bf16<4, 1>(a, splits, st);
-        else if (wco == 2) om::launch_dw_bf16<2, 1>(a, splits, st);
-        else om::launch_dw_bf16<1, 1>(a, splits, st);
-    } else {
-        if (wco == 4) om::launch_dw_bf16<4, 9>(a, splits, st);
-        else if (wco == 2) om::launch_dw_bf16<2, 9>(a, splits, st);
-        else om::launch_dw_bf16<1, 9>(a, splits, st);
-    }
-    if (dw && splits > 1) {
-        const unsigned blocks = (unsigned)((g.n + om::CGB_THREADS - 1) / om::CGB_THREADS);
-        hipLaunchKernelGGL(om::conv_dw_bf16_reduce_kernel, dim3(blocks), dim3(om::CGB_THREADS), 0, st,
-                           static_cast<const float*>(workspace), dw, g.n, splits);
-    }
-    if (dbias) hipLaunchKernelGGL(om::conv_dbias_bf16_kernel, dim3(cout), dim3(om::CGB_THREADS), 0, st, dy, dbias, B, cout, g.HoWo);
     OM_CHECK_HIP(hipGetLastError());
     return OM_OK;
 }

@@ -1,4 +1,4 @@
-// What the training convolutions share (conv_fwd.hip, conv_grad.hip): the geometries and size limits of their four entry points, the
+// What the training convolutions share (conv_fwd.hip, conv_grad.hip, conv_dw.hip): the geometries and size limits of their four entry points, the
 // text that refuses a shape outside them, and the matrix instruction's accumulator type with its clear (conv_fwd.hip clears its
 // accumulators lane by lane inside the loops that also touch the double sums).
 #pragma once

@@ -27,17 +27,17 @@ And the reference's model in training mode: ``builder.build(config["model"], ori
                                records between the block's two phases, merged in rank order on every rank)
 
   conv2d                       F.conv2d whose input, weight and bias gradients are om_conv2d_grad_input / om_conv2d_grad_weight
-                               (csrc/conv_grad.hip); the models use it with conv_backend='hip'.  With forward='hip' the forward
-                               is om_conv2d_forward (csrc/conv_fwd.hip) too; the models pass it with conv_forward='hip'
+                               (csrc/conv_grad.hip, conv_dw.hip); the models use it with conv_backend='hip'.  With forward='hip' the
+                               forward is om_conv2d_forward (csrc/conv_fwd.hip) too; the models pass it with conv_forward='hip'
 
   conv2d_bf16                  the bf16 forward: om_conv2d_bf16_forward (csrc/conv_fwd_bf16.hip) on a bf16 x and the float32 master
                                weight, bf16 or float32 out; the backward is conv2d_bf16_backward: torch's bf16 gradient, or with
-                               backward='hip' om_conv2d_bf16_grad_input / om_conv2d_bf16_grad_weight (csrc/conv_grad_bf16.hip).
+                               backward='hip' om_conv2d_bf16_grad_input / om_conv2d_bf16_grad_weight (conv_grad_bf16.hip, conv_dw.hip).
                                The models use it with amp='bf16', conv_forward='hip' (and conv_grad='hip' for the latter)
 
 The forward convolution is torch's with conv_forward='torch' (the default) and om_conv2d_forward with conv_forward='hip', which
 needs conv_backend='hip' -- or, under amp='bf16', om_conv2d_bf16_forward with conv_backend='torch'.  Its gradients are torch's with
-conv_backend='torch' (the default) and the HIP kernels of csrc/conv_grad.hip with conv_backend='hip' (float32 only).
+conv_backend='torch' (the default) and the HIP kernels of csrc/conv_grad.hip and conv_dw.hip with conv_backend='hip' (float32 only).
 
   conv_bn_leaky_frozen         a frozen block (the models' frozen_stages) as one kernel: the convolution with the fixed affine of the
                                running statistics, LeakyReLU and the residual add in its epilogue (om_conv2d_frozen_forward; on a
@@ -59,8 +59,8 @@ convolution this package's: conv2d_bf16 in the blocks and the heads (the heads f
 bf16 kernel in frozen blocks; the first layer's float32 image is cast to bf16 once, as autocast does.  The forward then repeats bit
 for bit without cudnn.deterministic.  amp excludes conv_backend='hip': the float32 gradient kernels take float32 operands only.
 conv_grad='hip' (default 'torch'; needs amp='bf16', conv_forward='hip', conv_backend='torch') makes the gradients of those
-convolutions the bf16 kernels of csrc/conv_grad_bf16.hip: every convolution node of a step is then this package's, and a whole
-trainer step repeats bit for bit without cudnn.deterministic, as the float32 path (conv_backend='hip', conv_forward='hip') does.
+convolutions the bf16 kernels of csrc/conv_grad_bf16.hip and conv_dw.hip: every convolution node of a step is then this package's, and a
+whole trainer step repeats bit for bit without cudnn.deterministic, as the float32 path (conv_backend='hip', conv_forward='hip') does.
 """
 import contextlib
 import ctypes
@@ -319,11 +319,34 @@ class _BNAct(torch.autograd.Function):
         return _bn_grads(ctx, dx, dgb, dy)
 
 
+def _conv_grads_hip(dy, x, weight, stride, need_x, need_w, need_b):
+    """(dx, dw, db) of a convolution of x (float32 or bf16: the entry points of _sfx(x)) with the float32 weight, on the current
+    stream, into torch.empty outputs, with the grow-only workspace of the device and stream; None for a gradient that is not
+    needed: no input-gradient launch for an input that needs none, no weight-gradient launch where neither dw nor db is needed.
+    dx has x's type, dw and db are float32."""
+    B, cin, H, W = x.shape
+    cout, ks = weight.shape[0], weight.shape[2]
+    dev, sfx = x.device, _sfx(x)
+    dx = torch.empty_like(x) if need_x else None
+    dw = torch.empty_like(weight) if need_w else None
+    db = torch.empty(cout, dtype=torch.float32, device=dev) if need_b else None
+    stream = _lib.current_stream_ptr(dev)
+    geom = (B, cin, H, W, cout, ks, stride)
+    dx_is_f32 = (0,) if sfx else ()                 # the bf16 entry's extra argument: dx is bf16
+    with _lib.on_device(dev):
+        ws = _workspace(dev, stream, getattr(_lib.load(), "om_conv2d%s_grad_workspace_bytes" % sfx)(*geom))
+        if need_x:
+            _lib.launch("om_conv2d%s_grad_input" % sfx, dev, dy, weight, *geom, dx, *dx_is_f32, ws, ws.numel(), stream=stream)
+        if need_w or need_b:
+            _lib.launch("om_conv2d%s_grad_weight" % sfx, dev, x, dy, *geom, dw, db, ws, ws.numel(), stream=stream)
+    return dx, dw, db
+
+
 class _Conv2d(torch.autograd.Function):
     """forward(ctx, x, weight, bias, stride, hip_forward) -> F.conv2d(x, weight, bias, stride, ksize // 2), or with hip_forward
     the same convolution as om_conv2d_forward (csrc/conv_fwd.hip) into a torch.empty output.  Saved for the backward either way: x
-    and the weight, what torch's own node saves.  The backward enqueues om_conv2d_grad_input and om_conv2d_grad_weight (csrc/conv_grad.hip)
-    on the current stream for the gradients that are needed: no input gradient for an input that needs none, no weight gradient for
+    and the weight, what torch's own node saves.  The backward enqueues om_conv2d_grad_input and om_conv2d_grad_weight (csrc/conv_grad.hip,
+    conv_dw.hip) on the current stream for the gradients that are needed: no input gradient for an input that needs none, no weight gradient for
     a frozen weight; the bias gradient comes from the weight-gradient call."""
 
     @staticmethod
@@ -344,23 +367,8 @@ class _Conv2d(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, dy):
         x, weight = ctx.saved_tensors
-        B, cin, H, W = x.shape
-        cout, ks = weight.shape[0], weight.shape[2]
-        dev = x.device
-        dy = dy.contiguous()
         need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
-        dx = torch.empty_like(x) if need_x else None
-        dw = torch.empty_like(weight) if need_w else None
-        db = torch.empty(cout, dtype=torch.float32, device=dev) if need_b else None
-        stream = _lib.current_stream_ptr(dev)
-        geom = (B, cin, H, W, cout, ks, ctx.stride)
-        with _lib.on_device(dev):
-            ws = _workspace(dev, stream, _lib.load().om_conv2d_grad_workspace_bytes(*geom))
-            if need_x:
-                _lib.launch("om_conv2d_grad_input", dev, dy, weight, *geom, dx, ws, ws.numel(), stream=stream)
-            if need_w or need_b:
-                _lib.launch("om_conv2d_grad_weight", dev, x, dy, *geom, dw, db, ws, ws.numel(), stream=stream)
-        return dx, dw, db, None, None
+        return _conv_grads_hip(dy.contiguous(), x, weight, ctx.stride, need_x, need_w, need_b) + (None, None)
 
 
 def _require_nchw(t, who, what, dtypes=(torch.float32,)):
@@ -402,8 +410,8 @@ def _conv_geometry(who, x, weight, stride, padding):
 
 
 def conv2d(x, weight, bias=None, stride=1, padding=0, forward="torch"):
-    """F.conv2d(x, weight, bias, stride, padding) with the gradients as HIP kernels (csrc/conv_grad.hip).  x, weight and bias CUDA
-    float32, x NCHW-contiguous [B,cin,H,W], weight contiguous [cout,cin,k,k]; the geometry one of 1x1 stride 1 padding 0, 3x3
+    """F.conv2d(x, weight, bias, stride, padding) with the gradients as HIP kernels (csrc/conv_grad.hip, conv_dw.hip).  x, weight and bias
+    CUDA float32, x NCHW-contiguous [B,cin,H,W], weight contiguous [cout,cin,k,k]; the geometry one of 1x1 stride 1 padding 0, 3x3
     stride 1 padding 1, 3x3 stride 2 padding 1, without dilation or groups.  Anything else raises: there is no fallback.
     forward 'torch' (default): the forward is F.conv2d.  forward 'hip': it is om_conv2d_forward (csrc/conv_fwd.hip), enqueued on
     the current stream and bit-identical from run to run; the backward and what it reads are the same, so for the same (x, weight,
@@ -431,8 +439,8 @@ def conv2d_bf16_backward(dy, x, weight, stride, padding, has_bias, needs, backen
     that does not exist): it is not computed.
     backend 'torch' (default): torch's bf16 convolution gradient, aten.convolution_backward(dy, x, weight.to(bfloat16)), which is
     what F.conv2d under torch.autocast(dtype=bfloat16) leaves behind its weight cast.  Runs on CPU tensors too.
-    backend 'hip': om_conv2d_bf16_grad_input / om_conv2d_bf16_grad_weight (csrc/conv_grad_bf16.hip) on the current stream, into
-    torch.empty outputs, with the grow-only workspace of the device and stream; CUDA NCHW-contiguous tensors only.  The weight is
+    backend 'hip': om_conv2d_bf16_grad_input / om_conv2d_bf16_grad_weight (csrc/conv_grad_bf16.hip, conv_dw.hip) on the current stream,
+    into torch.empty outputs, with the grow-only workspace of the device and stream; CUDA NCHW-contiguous tensors only.  The weight is
     rounded to bf16 inside the kernel, as the forward rounds it; the same bits on every run."""
     if backend not in CONV_GRADS:
         raise ValueError("backend must be one of %s, got %r" % (CONV_GRADS, backend))
@@ -451,19 +459,7 @@ def conv2d_bf16_backward(dy, x, weight, stride, padding, has_bias, needs, backen
             raise _lib.OrienMaskHipError("conv2d_bf16_backward: dy %s %s on %s for x %s %s on %s, weight %s on %s"
                                          % (tuple(dy.shape), dy.dtype, dy.device, tuple(x.shape), x.dtype, dev, tuple(weight.shape),
                                             weight.device))
-        B, cin, H, W = x.shape
-        dx = torch.empty_like(x) if need_x else None
-        dw = torch.empty_like(weight) if need_w else None
-        db = torch.empty(cout, dtype=torch.float32, device=dev) if need_b else None
-        stream = _lib.current_stream_ptr(dev)
-        geom = (B, cin, H, W, cout, ks, s)
-        with _lib.on_device(dev):
-            ws = _workspace(dev, stream, _lib.load().om_conv2d_bf16_grad_workspace_bytes(*geom))
-            if need_x:
-                _lib.launch("om_conv2d_bf16_grad_input", dev, dy, weight, *geom, dx, 0, ws, ws.numel(), stream=stream)
-            if need_w or need_b:
-                _lib.launch("om_conv2d_bf16_grad_weight", dev, x, dy, *geom, dw, db, ws, ws.numel(), stream=stream)
-        return dx, dw, db
+        return _conv_grads_hip(dy, x, weight, s, need_x, need_w, need_b)
     dx, dw, db = torch.ops.aten.convolution_backward(dy, x, weight.to(torch.bfloat16), [cout] if has_bias else None, [stride, stride],
                                                      [padding, padding], [1, 1], False, [0, 0], 1, [need_x, need_w, need_b])
     return (dx if need_x else None, dw.float() if need_w else None, db.float() if need_b else None)

@@ -1,4 +1,4 @@
-"""The truth, the scale and the yardstick for the bf16 convolution gradients of csrc/conv_grad_bf16.hip (tests/test_conv_grad_bf16.py).
+"""The truth, the scale and the yardstick for the bf16 convolution gradients of csrc/conv_grad_bf16.hip and csrc/conv_dw.hip (tests/test_conv_grad_bf16.py).
 
 Inputs: conv_grad_np.inputs' draw with x and dy quantised to bf16 (bf16_np), w left float32 (the master weight; the kernel rounds
 it).  Truth: conv_grad_np.gradients in float64 on widen(x), widen(dy), quantise(w).  S: the same gradients of the absolute values

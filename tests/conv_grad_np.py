@@ -1,4 +1,4 @@
-"""The truth and the yardstick for the convolution gradients of csrc/conv_grad.hip (tests/test_conv_grad.py).
+"""The truth and the yardstick for the convolution gradients of csrc/conv_grad.hip and csrc/conv_dw.hip (tests/test_conv_grad.py).
 
 Truth: torch.nn.grad.conv2d_input / conv2d_weight on the float32 inputs widened to float64 (CPU).  Yardstick: the same two functions
 in float32 on the CPU.  The bias gradient is the sum of dy over batch and plane, in float64 and in float32.  Errors are

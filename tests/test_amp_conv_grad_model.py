@@ -1,5 +1,5 @@
 """GPU tests of the training models with amp='bf16', conv_forward='hip' and conv_grad='hip': every convolution node of a step, forward
-and backward, is this package's (csrc/conv_fwd_bf16.hip, csrc/conv_grad_bf16.hip).
+and backward, is this package's (csrc/conv_fwd_bf16.hip, csrc/conv_grad_bf16.hip, csrc/conv_dw.hip).
 
 tests/test_amp_conv_model.py's setting: FPN-Plus and the non-Plus model at 2 x 3 x 96 x 96, truth = the same model in float64 on the
 CPU (backend 'torch', no amp).  The comparator is conv_grad='torch' (torch's bf16 gradients behind the same forward) on the same GPU,

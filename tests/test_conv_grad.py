@@ -1,4 +1,4 @@
-"""GPU tests of the convolution gradients (om_conv2d_grad_input / om_conv2d_grad_weight, csrc/conv_grad.hip) through the C ABI,
+"""GPU tests of the convolution gradients (om_conv2d_grad_input / om_conv2d_grad_weight; csrc/conv_grad.hip, csrc/conv_dw.hip) through the C ABI,
 through orienmask_amd.train.conv2d and through the training models built with conv_backend='hip'.
 
 Truth is tests/conv_grad_np.py: torch.nn.grad's two functions in float64 on the float32 inputs.  The yardstick is the same two

@@ -1,4 +1,4 @@
-"""GPU tests of the bf16 convolution gradients (om_conv2d_bf16_grad_input / om_conv2d_bf16_grad_weight, csrc/conv_grad_bf16.hip)
+"""GPU tests of the bf16 convolution gradients (om_conv2d_bf16_grad_input / om_conv2d_bf16_grad_weight; csrc/conv_grad_bf16.hip, csrc/conv_dw.hip)
 through the C ABI and through orienmask_amd.train.conv2d_bf16(..., backward='hip').
 
 The arithmetic contract (include/orienmask_hip.h): dy and x bf16 widened exactly, w the float32 master weight rounded to bf16 (nearest

@@ -1,5 +1,5 @@
 """Without a GPU: the C-ABI surface of the bf16 convolution gradients (om_conv2d_bf16_grad_workspace_bytes, om_conv2d_bf16_grad_input,
-om_conv2d_bf16_grad_weight; csrc/conv_grad_bf16.hip), the option conv_grad='hip' on the block, both models, the builder and
+om_conv2d_bf16_grad_weight; csrc/conv_grad_bf16.hip, csrc/conv_dw.hip), the option conv_grad='hip' on the block, both models, the builder and
 tools/train.py, conv2d_bf16_backward's 'torch' backend against its default, and the test helper's truth against torch.autograd in
 float64.  No GPU compute."""
 import importlib.util

@@ -1,5 +1,5 @@
 """Without a GPU: the four entry points of the training convolutions (om_conv2d_forward, om_conv2d_frozen_forward,
-om_conv2d_grad_input, om_conv2d_grad_weight; csrc/conv_fwd.hip, csrc/conv_grad.hip) refuse the same shapes by one rule
+om_conv2d_grad_input, om_conv2d_grad_weight; csrc/conv_fwd.hip, csrc/conv_grad.hip, csrc/conv_dw.hip) refuse the same shapes by one rule
 (csrc/conv_train.h), each under its own name, and the workspace query answers 0 for them.  Only refused shapes are given: an
 accepted one would launch."""
 import ctypes

@@ -1,5 +1,5 @@
 """Time the convolution gradients per distinct convolution geometry of the FPNPlus model at 544 x 544: om_conv2d_grad_input and
-om_conv2d_grad_weight (csrc/conv_grad.hip, what orienmask_amd.train.conv2d's backward enqueues) against torch's own convolution
+om_conv2d_grad_weight (csrc/conv_grad.hip and csrc/conv_dw.hip, what orienmask_amd.train.conv2d's backward enqueues) against torch's own convolution
 backward (aten.convolution_backward with one output selected) on the same GPU and the same tensors, the data gradient and the weight
 gradient separately.  torch is the baseline: it is what conv_backend='torch' runs.
 
@@ -15,7 +15,7 @@ memory for conv_backend 'hip' and 'torch'.
 
 prints one JSON line (and writes it to --out); a progress line per geometry goes to stderr.
 
---dtype bf16 times the bf16 gradients instead (csrc/conv_grad_bf16.hip, what amp='bf16' with conv_forward='hip', conv_grad='hip'
+--dtype bf16 times the bf16 gradients instead (csrc/conv_grad_bf16.hip and csrc/conv_dw.hip, what amp='bf16' with conv_forward='hip', conv_grad='hip'
 enqueues), per geometry and in the same interleaved rounds: om_conv2d_bf16_grad_input (bf16 dx) and om_conv2d_bf16_grad_weight on
 bf16 dy and x and the float32 master weight (hip_bf16), aten.convolution_backward on bf16 tensors with one output selected
 (torch_bf16: what conv_grad='torch' runs), and om_conv2d_grad_* on the float32 tensors (hip_f32).  Reported besides: the geometries
