@@ -421,6 +421,83 @@ int om_preprocess_batch(const void* const* images, const int32_t* geom, int n, c
 int om_pad_nchw(const float* in, long long planes, int h, int w, int pad_top, int pad_left, int out_h, int out_w,
                 float pad_value, float* out, om_stream stream);
 
+/* ---- JPEG decoding ---------------------------------------------------------------------------
+ * Baseline JPEG in two halves: the host parses the stream and undoes the Huffman coding (csrc/om_jpeg.cpp: plain C++, no HIP
+ * call, nothing that initialises the GPU -- a loader worker may call it), the device does the arithmetic (csrc/jpeg.hip:
+ * dequantise, accurate-integer IDCT, chroma up-sampling, YCbCr -> RGB).  The result is, bit for bit, what libjpeg(-turbo) gives
+ * with its defaults (ISLOW IDCT, fancy up-sampling): PIL's Image.open(...).convert('RGB').
+ *
+ * SUPPORTED: SOF0, 8-bit samples, 8-bit quantisation tables, Huffman coding, 1 component (sampling 1x1) or 3 components with
+ * ids 1,2,3, luma sampling 1x1, 2x1 or 2x2 with chroma 1x1 (4:4:4, 4:2:2, 4:2:0), one interleaved scan, restart intervals, any
+ * legal layout of the DQT / DHT / APPn / COM segments.  UNSUPPORTED (status OM_OK, supported = 0 and a reason OM_JPEG_R_*; the
+ * caller gives the bytes to a host reader): every other process, precision, component set or sampling, 16-bit quantisation
+ * tables, an Adobe APP14 segment, several scans, DNL or a height of 0, an Exif orientation other than 1 (host readers disagree
+ * on whether to rotate), an image of 2^31 / 3 pixels or more, and a dequantised coefficient beyond OM_JPEG_COEF_BOUND.  REJECTED
+ * (status OM_EINVAL and a message): a stream that is truncated, runs past its buffer, carries an undefined Huffman code or table
+ * reference, has a run past coefficient 63, a bad restart sequence, no EOI behind the scan, or a DC predictor that leaves int16.
+ * No byte outside [bytes, bytes + len) is read and none outside the given buffers written, for any byte string whatever.
+ *
+ * info: int32 [OM_JPEG_INFO_WORDS], written by both host entries:
+ *   [OM_JPEG_I_WIDTH] [OM_JPEG_I_HEIGHT] [OM_JPEG_I_NCOMP] [OM_JPEG_I_HMAX] [OM_JPEG_I_VMAX] [OM_JPEG_I_RESTART]
+ *   [OM_JPEG_I_SUPPORTED] 1 / 0, [OM_JPEG_I_REASON] OM_JPEG_R_*; and, for a supported stream,
+ *   [OM_JPEG_I_BLOCKS] 8x8 blocks of all components: the coefficient buffer is 128 bytes times this;
+ *   [OM_JPEG_I_COMP + OM_JPEG_COMP_WORDS * c + ...] of component c: 0 h, 1 v (sampling factors), 2 blocks per row and 3 block
+ *   rows of its plane (padded to whole MCUs), 4 real width ceil(W * h / hmax) and 5 real height ceil(H * v / vmax) in samples.
+ * OM_JPEG_COEF_BOUND: the device IDCT works in int32, libjpeg's C code in 64-bit long.  With every |coefficient * quantiser| at
+ * most this, every intermediate of both IDCT passes fits int32 (derivation: csrc/om_jpeg.cpp; proof by interval arithmetic:
+ * tests/test_jpeg_cpu.py), so the two agree.  An 8-bit image's own coefficients stay below 1024 + 127. */
+#define OM_JPEG_BATCH 16        /* images per launch set of om_jpeg_decode_batch */
+#define OM_JPEG_COEF_BOUND 1170
+#define OM_JPEG_INFO_WORDS 32
+#define OM_JPEG_I_WIDTH 0
+#define OM_JPEG_I_HEIGHT 1
+#define OM_JPEG_I_NCOMP 2
+#define OM_JPEG_I_SUPPORTED 3
+#define OM_JPEG_I_REASON 4
+#define OM_JPEG_I_HMAX 5
+#define OM_JPEG_I_VMAX 6
+#define OM_JPEG_I_RESTART 7
+#define OM_JPEG_I_BLOCKS 8
+#define OM_JPEG_I_COMP 10
+#define OM_JPEG_COMP_WORDS 6
+#define OM_JPEG_R_NONE 0
+#define OM_JPEG_R_PROGRESSIVE 1
+#define OM_JPEG_R_ARITHMETIC 2
+#define OM_JPEG_R_LOSSLESS 3
+#define OM_JPEG_R_PRECISION 4   /* 12- or 16-bit samples */
+#define OM_JPEG_R_FRAME 5       /* another frame type (extended sequential, differential) or sample precision */
+#define OM_JPEG_R_QUANT16 6
+#define OM_JPEG_R_COMPONENTS 7  /* 4 components, or ids other than 1,2,3 */
+#define OM_JPEG_R_ADOBE 8
+#define OM_JPEG_R_SAMPLING 9
+#define OM_JPEG_R_SCANS 10
+#define OM_JPEG_R_DNL 11
+#define OM_JPEG_R_ORIENTATION 12
+#define OM_JPEG_R_SIZE 13
+#define OM_JPEG_R_RANGE 14      /* a |coefficient * quantiser| beyond OM_JPEG_COEF_BOUND (found by om_jpeg_entropy_decode only) */
+#define OM_JPEG_DESC_WORDS 8
+/* The headers alone: geometry, supported or not and why.  Host only. */
+int om_jpeg_info(const uint8_t* bytes, size_t len, int32_t* info);
+/* Host only.  coef (cap_bytes >= 128 * info[OM_JPEG_I_BLOCKS], else OM_ENOMEM) receives the UNDEQUANTISED coefficients,
+ * de-zigzagged, [block][64] int16, component after component, each component's blocks in raster order of its padded plane;
+ * quant receives [ncomp][64] uint16, the quantisation table of each component in natural order.  info is written as by
+ * om_jpeg_info; of an unsupported stream nothing else is written.  A stream this entry finds to be unsupported only while
+ * decoding (OM_JPEG_R_RANGE, OM_JPEG_R_SCANS behind the first scan) has supported = 0 on return as well. */
+int om_jpeg_entropy_decode(const uint8_t* bytes, size_t len, int16_t* coef, size_t cap_bytes, uint16_t* quant, int32_t* info);
+/* Device side.  desc: HOST int64 [n][OM_JPEG_DESC_WORDS], row i = { width, height, ncomp, hmax, vmax, coef_off, quant_off,
+ * out_off } of image i: the geometry om_jpeg_info reported and where the image's data lie -- coef_off in int16 elements into
+ * coef (a multiple of 64), quant_off in uint16 elements into quant (a multiple of 64), out_off in bytes into out (a multiple of
+ * 16).  coef, quant, out and workspace are DEVICE memory, 16-byte aligned; coef and quant hold what om_jpeg_entropy_decode wrote.
+ * out receives, at out_off, the dense [height,width,3] uint8 RGB image (a grey stream replicated to three channels); no other
+ * byte of out is written.  Images of one call may differ in size and sampling; two launches per OM_JPEG_BATCH images
+ * (IDCT into component planes in the workspace, then up-sampling + colour), asynchronous on `stream`, no allocation, no
+ * synchronisation, no atomics.  workspace: om_jpeg_workspace_bytes(desc, n) bytes, contents undefined on entry, as out's.
+ * Every row is checked against coef_elems, quant_elems, out_bytes and ws_bytes before anything is launched.  The streams must
+ * be ones the host SUPPORTS: nothing here looks at a coefficient's value. */
+size_t om_jpeg_workspace_bytes(const int64_t* desc, int n);      /* 0: a bad row, see om_last_error */
+int om_jpeg_decode_batch(const int64_t* desc, int n, const int16_t* coef, size_t coef_elems, const uint16_t* quant,
+                         size_t quant_elems, void* workspace, size_t ws_bytes, uint8_t* out, size_t out_bytes, om_stream stream);
+
 /* ---- postprocess --------------------------------------------------------------------------
  * workspace (every om_postprocess* entry and the buffer handed to om_model_attach_postprocess): om_postprocess_workspace_bytes
  * bytes, 256-byte aligned, contents undefined on entry -- candidate keys, per-tile counts, the radix histograms and the list

@@ -13,7 +13,14 @@ reference config unchanged and ``val_loader.dataset.CAT2LABEL`` / ``.with_mask``
 ``imread`` is a callable from a path to an [h,w,3] RGB uint8 array.  The default decodes with cv2 exactly as the reference does
 (``cv2.imread`` + ``COLOR_BGR2RGB``) when cv2 can be imported and with PIL (``Image.open(p).convert('RGB')``) otherwise.  PIL's
 JPEG decoder is NOT pinned to cv2's: the two may differ in the last bits of a pixel.  Lossless formats (PNG, BMP) decode
-identically.
+identically.  The project's own JPEG decoder (``orienmask_amd.jpeg``: host entropy decoding, HIP IDCT and colour) IS pinned: bit
+for bit PIL's pixels.
+
+A host-only reader of your own goes in as ``COCODataset(..., imread=my_reader)``: any callable path -> [h,w,3] uint8 RGB that
+touches no GPU, since it runs in the loader's worker processes.  Of the JPEG decoder a worker may call the two HOST entries
+(``jpeg.host_info`` / ``jpeg.host_entropy_decode``, i.e. ``om_jpeg_info`` and ``om_jpeg_entropy_decode``: they make no HIP
+call), never ``om_jpeg_decode_batch`` or ``JpegDecoder.decode``: those launch kernels and belong to the process that owns the
+device.  Carrying coefficients through ``collate`` into the training augmentation is not done yet.
 """
 import csv
 import json
@@ -71,7 +78,8 @@ class BaseDataset(Dataset):
 
 class COCODataset(BaseDataset):
     """anno_file: {key: {'image_id': id, 'anno': {'bbox': [[cx, cy, w, h] normalised], 'cls': [label], 'mask': [segmentation]}}},
-    the label json of the reference's tools."""
+    the label json of the reference's tools.  imread: a host-only reader, path -> [h,w,3] uint8 RGB (the module docstring says
+    what it may call); None: cv2 as the reference reads, else PIL."""
     CAT2LABEL = list(_CAT2LABEL["COCO"])
     CLASSES = list(_CLASSES["COCO"])
 

@@ -106,6 +106,18 @@ OM_VIS_BATCH = 16
 OM_PRE_BATCH = 16               # include/orienmask_hip.h: om_preprocess_batch, images per launch and the flags of a geom row
 OM_PRE_U8 = 1
 OM_PRE_BGR = 2
+# include/orienmask_hip.h: the JPEG decoder -- images per launch set, the int32 words of an info record, the int64 words of a
+# descriptor row, the reasons a stream is left to a host reader, the bound on |coefficient * quantiser| of the int32 IDCT
+OM_JPEG_BATCH = 16
+OM_JPEG_COEF_BOUND = 1170
+OM_JPEG_INFO_WORDS = 32
+OM_JPEG_I_WIDTH, OM_JPEG_I_HEIGHT, OM_JPEG_I_NCOMP, OM_JPEG_I_SUPPORTED, OM_JPEG_I_REASON = 0, 1, 2, 3, 4
+OM_JPEG_I_HMAX, OM_JPEG_I_VMAX, OM_JPEG_I_RESTART, OM_JPEG_I_BLOCKS, OM_JPEG_I_COMP = 5, 6, 7, 8, 10
+OM_JPEG_COMP_WORDS = 6
+OM_JPEG_DESC_WORDS = 8
+(OM_JPEG_R_NONE, OM_JPEG_R_PROGRESSIVE, OM_JPEG_R_ARITHMETIC, OM_JPEG_R_LOSSLESS, OM_JPEG_R_PRECISION, OM_JPEG_R_FRAME,
+ OM_JPEG_R_QUANT16, OM_JPEG_R_COMPONENTS, OM_JPEG_R_ADOBE, OM_JPEG_R_SAMPLING, OM_JPEG_R_SCANS, OM_JPEG_R_DNL,
+ OM_JPEG_R_ORIENTATION, OM_JPEG_R_SIZE, OM_JPEG_R_RANGE) = range(15)
 
 _vp, _i, _f, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 
@@ -177,6 +189,10 @@ SIGNATURES = {
                            _i, _i, _i, _i, _f, _vp, _vp]),
     "om_preprocess_batch": (_i, [ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_int32), _i, ctypes.POINTER(ctypes.c_float),
                                  ctypes.POINTER(ctypes.c_float), _i, _i, _f, _vp, _vp]),
+    "om_jpeg_info": (_i, [_vp, _sz, ctypes.POINTER(ctypes.c_int32)]),
+    "om_jpeg_entropy_decode": (_i, [_vp, _sz, _vp, _sz, _vp, ctypes.POINTER(ctypes.c_int32)]),
+    "om_jpeg_workspace_bytes": (_sz, [ctypes.POINTER(ctypes.c_int64), _i]),
+    "om_jpeg_decode_batch": (_i, [ctypes.POINTER(ctypes.c_int64), _i, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
     "om_pad_nchw": (_i, [_vp, ctypes.c_longlong, _i, _i, _i, _i, _i, _i, _f, _vp, _vp]),
     "om_postprocess_workspace_bytes": (_sz, [ctypes.POINTER(PostCfg), _i]),
     "om_postprocess": (_i, [ctypes.POINTER(PostCfg), _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

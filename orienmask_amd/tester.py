@@ -140,7 +140,7 @@ class Tester:
 
 
 def infer_loop(model, transform, postprocess, images, device, warmup=10, size_divisor=32, use_graph=True, latency_mode=True,
-               visualizer=None, batch_size=1, channel_order="rgb"):
+               visualizer=None, batch_size=1, channel_order="rgb", decoder=None):
     """images: list of [h,w,3] float32 tensors (what cv2.imread + cvtColor give infer.py).
     Returns (list of per-image detections, list of pad_info, timer log in ms).
 
@@ -150,6 +150,11 @@ def infer_loop(model, transform, postprocess, images, device, warmup=10, size_di
     the postprocess as ONE batch ('Forward & Postprocess').  The last, shorter group is a second input shape (a second graph).
     Detections and pad_infos come back per image in input order; the visualizer gets each image as float32 RGB, derived on the
     device from the staged source.  The model's latency setting is left alone for batch_size > 1: it is a one-image device.
+
+    decoder (a jpeg.JpegDecoder): `images` are then JPEG files -- paths or bytes -- and every group is decoded on the device
+    (decoder.decode: host entropy decoding, HIP IDCT and colour) in front of transform.batch, all of it timed as 'Load data'; the
+    loop goes through the batched path at any batch_size, in RGB order.  The detections are those of the same images decoded by
+    PIL: the pixels are (tests/test_jpeg.py).
 
     visualizer (infer.py -v, :166-172): called as visualizer(detections, image on the device, pad_info) after each image's
     forward + postprocess and timed as 'Visualize'; the loop then returns a fourth element, the list of what it returned (for
@@ -173,7 +178,9 @@ def infer_loop(model, transform, postprocess, images, device, warmup=10, size_di
     batch_size = int(batch_size)
     if batch_size < 1:
         raise ValueError("infer_loop: batch_size must be at least 1, got %d" % batch_size)
-    through_batch = batch_size > 1 or channel_order != "rgb"
+    if decoder is not None and channel_order != "rgb":
+        raise ValueError("infer_loop: a decoder gives RGB images; channel_order must be 'rgb'")
+    through_batch = batch_size > 1 or channel_order != "rgb" or decoder is not None
     if (latency_mode and batch_size == 1 and getattr(model, "precision", None) == "f32_split"
             and hasattr(model, "set_latency_mode")):
         restore = model.latency_cells
@@ -205,6 +212,8 @@ def infer_loop(model, transform, postprocess, images, device, warmup=10, size_di
 
     def batched():
         def load(group):
+            if decoder is not None:
+                group = decoder.decode(group)
             return transform._batch(group, size_divisor, 0, channel_order, device)
 
         if warmup and images:
